@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — Tacotron2-VAE training-step throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one full training iteration of the reference loop (train.py:208-229): H2D of the
@@ -10,7 +10,13 @@ BASELINE.json configs[1] workload: batch 6 per GPU, fixed shape T_in=84 symbols 
 frames (SURVEY.md §8(d) cfg-2 "train-fixed"), fp32, dropout on, synthetic data, random-init
 weights from seed 1234.  Multi-GPU is weak scaling (6 utterances per rank).
 
-The single JSON line also carries:
+A plain run sets up, warms up, times the K steps and prints the JSON line (headline figure,
+ms_per_step, step configuration).  --dump-outputs DIR writes what the last timed step computed
+as DIR/<name>.npy (see step_outputs).  With --full the line also carries (each leg takes runs of
+its own):
+  graph_vs_eager_ms — the same step issued eagerly right after the timed replays
+  decode, frontend, secondary — the free-running decode loop, the STFT->mel front end, the koemo
+                 and bf16 workloads
   roofline     — the dominant kernel (k_lstm_fwd256: both decoder LSTM gate GEMVs, weights streamed
                  every time step).  Algorithmic bytes per launch = fp32 weights of the two cells
                  (4096×1536 + 4096×2560)×4 B = 67.1 MB; duration = events on the launch stream
@@ -33,6 +39,8 @@ import torch.distributed as dist  # noqa: E402
 T_IN, T_OUT = 84, 400
 LSTM_WEIGHT_BYTES = (4096 * 1536 + 4096 * 2560) * 4
 HBM_PEAK_GBS = 8000.0
+DUMP_SAMPLE = 1 << 22          # elements drawn from each flat arena by --dump-outputs (16 MiB of float32 each)
+DUMP_SEED = 20240601
 
 
 def synthetic_batch(B, T_in, T_out, seed, lens_in=None, lens_out=None):
@@ -449,8 +457,42 @@ def roofline_table(B, T_in, T, reps=3):
     return rows
 
 
-def run_workload(args, world, rank, bf16, koemo, steps, warmup, graph, eager_steps=0):
-    """one timed configuration; returns (engine, result dict)"""
+def step_outputs(engine, last):
+    """What a caller of TrainEngine.step holds after the last timed step, as float arrays (host copies, taken after the
+    sync that ends the timed region): the five values the step returns (loss, reconstruction loss, KL term, KL weight,
+    gradient norm), the BatchNorm running statistics in full, and the same fixed, seeded sample of DUMP_SAMPLE positions
+    of the flat parameter arena (after clip + Adam) and of the flat gradient arena of that step (both arenas hold ~29 M
+    floats; the positions depend only on the arena size and DUMP_SEED)."""
+    import numpy as np
+
+    def f64(x):
+        x = 0.0 if x is None else x
+        return (x.detach().double().cpu().numpy() if torch.is_tensor(x) else np.asarray(x, dtype=np.float64)).reshape(-1)
+
+    loss, recon, kl, w, grad_norm = last
+    out = {"loss": f64(loss), "recon_loss": f64(recon), "kl_loss": f64(kl), "kl_weight": f64(w), "grad_norm": f64(grad_norm)}
+    stats = [b.detach().reshape(-1).float() for n, b in engine.model.named_buffers() if n.endswith(('running_mean', 'running_var'))]
+    if stats:
+        out["bn_running_stats"] = torch.cat(stats).cpu().numpy()
+    opt = engine.optimizer
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, opt.numel, (min(DUMP_SAMPLE, opt.numel),), generator=g).unique()      # sorted, fixed
+    idx_dev = idx.to(opt.params.device)
+    out["params_sample"] = opt.params[idx_dev].cpu().numpy()
+    out["grads_sample"] = opt.grads[idx_dev].cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
+
+
+def run_workload(args, world, rank, bf16, koemo, steps, warmup, graph, eager_steps=0, outputs=None):
+    """one timed configuration; returns (engine, result dict).  `outputs`: a dict that receives step_outputs() of the last
+    timed step"""
     import hparams as HP
     import t2v_hip
     import train as TR
@@ -489,10 +531,13 @@ def run_workload(args, world, rank, bf16, koemo, steps, warmup, graph, eager_ste
         sync()
         t0 = time.perf_counter()
         for _ in range(steps):
-            loss = engine.step(batch, it)[0]
+            last = engine.step(batch, it)
             it += 1
         sync()
         elapsed = time.perf_counter() - t0
+        loss = last[0]
+        if outputs is not None:         # before anything else runs on the engine (a graph replay's outputs are static buffers)
+            outputs.update(step_outputs(engine, last))
         # a rank's own clock up to ITS last step's completion would need a sync before the barrier; what a straggler shows
         # in is the per-rank time to issue + finish its steps, taken around the same region with a device sync only
         eager_ms = None
@@ -580,6 +625,12 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, ~32 MB; rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beyond the headline figure: graph vs eager step, roofline replays, decode loop,\n'
+                         'front end, secondary workloads, CPU baselines (the --no-* / --cpu-* / --eager-steps options below\n'
+                         'shape these legs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-steps', type=int, default=5)
     ap.add_argument('--cpu-warmup', type=int, default=2)
@@ -640,10 +691,13 @@ def main():
 
     import t2v_hip
     t2v_hip.load_library()
-    t2v_hip.DecoderCore.keep_last = True       # the roofline leg replays the last step's kernels on its arena
+    t2v_hip.DecoderCore.keep_last = args.full  # the roofline leg replays the last step's kernels on its arena
     kind = 'bf16' if args.bf16 else ('koemo' if args.koemo else 'headline')
+    outputs = {} if args.dump_outputs and rank == 0 else None
     engine, res = run_workload(args, world, rank, args.bf16, args.koemo and not args.bf16, args.steps, args.warmup,
-                               not args.no_graph, eager_steps=args.eager_steps)
+                               not args.no_graph, eager_steps=args.eager_steps if args.full else 0, outputs=outputs)
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     bpg = res["batch_per_gpu"]
     out = {
         "metric": "mel-frames/s (train step, batch=%d, 80-mel)" % bpg, "value": res["value"],
@@ -675,7 +729,7 @@ def main():
             out["allreduce_exposed_ms"] = res["allreduce_exposed_ms"]
             out["allreduce_buckets_bytes"] = res["allreduce_buckets"]
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline leg: the four per-time-step kernels of the decoder recurrence (87 % of the GPU time of a step)
         rows = roofline_table(bpg, T_IN, T_OUT)
         top = rows[0]                   # the kernel with the most time per step
@@ -775,6 +829,7 @@ def main():
             if "decode" in out:                 # cfg-4 gets its CPU figure beside it as well
                 out["decode"]["cpu_baseline"] = decode_cpu_baseline(threads=args.cpu_threads)
                 out["decode"]["speedup_vs_cpu"] = round(out["decode"]["frames_per_s"] / out["decode"]["cpu_baseline"]["frames_per_s"], 1)
+    if rank == 0:
         # the secondary headline figures as scalars at the FRONT of the line (the driver stores a tail of stdout,
         # and configs[4]'s number used to sit in the part that was cut off)
         front = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step") if k in out}

@@ -193,6 +193,11 @@ def main():
     model = R.Tacotron2(hp)
     model.train()
     init_digest = {k: digest(v) for k, v in model.state_dict().items()}
+    # the same tensors byte for byte (the float64 sums above depend on the summation order of the machine that computes them)
+    import hashlib
+    with open(os.path.join(OUT, 'init_sha256.json'), 'w') as f:
+        json.dump({k: hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest()
+                   for k, v in model.state_dict().items()}, f, indent=0)
     manifest = [[k, list(v.shape), str(v.dtype).replace('torch.', '')] for k, v in model.state_dict().items()]
 
     B, T_in, T_out = 2, 20, 40
@@ -397,6 +402,11 @@ def main():
             with open(fl, encoding='utf-8') as f:
                 sents += [ln.strip().split('|')[1] for ln in f if ln.strip()]
     uniq = sorted(set(sents))
+    # the sentences themselves (data: the text column of the filelists), so that the test needs nothing outside the repository
+    import gzip
+    with open(os.path.join(OUT, 'koemo_sentences.txt.gz'), 'wb') as f:
+        with gzip.GzipFile(filename='', mode='wb', fileobj=f, mtime=0, compresslevel=9) as z:
+            z.write(''.join(t + '\n' for t in uniq).encode('utf-8'))
     h = hashlib.sha256()
     n_ok, max_len = 0, 0
     for t in uniq:

@@ -19,5 +19,5 @@ def test_bench_cli_flags():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True,
                          timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr
-    for flag in ('--gpus', '--steps', '--warmup', '--bf16', '--koemo'):
+    for flag in ('--gpus', '--steps', '--warmup', '--bf16', '--koemo', '--full', '--dump-outputs'):
         assert flag in out.stdout, flag

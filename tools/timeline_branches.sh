@@ -1,5 +1,6 @@
+REPO=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof2 -o r -- python /root/repo/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-decode > /tmp/p2.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/prof2 -o r -- python $REPO/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-decode > /tmp/p2.log 2>&1
 KT=$(find /tmp/prof2 -name '*kernel_trace.csv' | head -1)
 python - "$KT" <<'PY'
 import csv, sys
