@@ -16,7 +16,6 @@
 #include "t2v_kernels.h"
 #include "t2v_coop.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define CG_BM 64
 #define CG_BN 64
@@ -490,12 +489,6 @@ __global__ __launch_bounds__(256) void k_conv5_dw(ConvTiledArgs a) {
 //             flip/transpose is folded into that pass), so a tile's A rows are 160 contiguous bytes;
 //   LDS     : As[tap][row][16 (+8 pad)] and Xt[position][16 (+8 pad)] (channel-contiguous, transposed while
 //             staging): every MFMA operand is one ds_read_b64, rows 48 B apart -> conflict-free.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-    bf16x2_t p = {(__bf16)lo, (__bf16)hi};
-    return *(unsigned*)&p;
-}
 #define CB_RS 24     // LDS row stride in bf16 elements (48 B)
 
 // W (M, Cin, 5) fp32 -> Wp bf16.  flipT = 0: rows = M, channels = Cin, Wp[r][cb][kx][c16] = W[r][16cb+c16][kx].
@@ -576,7 +569,7 @@ __global__ __launch_bounds__(256) void k_conv5_fwd_bf16(ConvBf16Args a) {
             if (a_lds[i] >= 0) *(uint4*)(&As[buf][0][0][0] + a_lds[i]) = ra[i];
 #pragma unroll
         for (int i = 0; i < NXP; ++i)
-            if (x_lds[i] >= 0) *(unsigned*)(&Xt[buf][0][0] + x_lds[i]) = pack_bf16x2(rx[i][0], rx[i][1]);
+            if (x_lds[i] >= 0) *(unsigned*)(&Xt[buf][0][0] + x_lds[i]) = t2v_pack_bf16x2(rx[i][0], rx[i][1]);
     };
 
     f32x4 acc[NTW];
@@ -590,10 +583,10 @@ __global__ __launch_bounds__(256) void k_conv5_fwd_bf16(ConvBf16Args a) {
         load_tiles(min(kt + 1, ncb - 1));
 #pragma unroll
         for (int kx = 0; kx < 5; ++kx) {
-            const s16x4 av = *(const s16x4*)&As[buf][kx][16 * wave + j][4 * kq];
+            const t2v_s16x4 av = *(const t2v_s16x4*)&As[buf][kx][16 * wave + j][4 * kq];
 #pragma unroll
             for (int n = 0; n < NTW; ++n) {
-                const s16x4 bv = *(const s16x4*)&Xt[buf][16 * n + j + kx][4 * kq];
+                const t2v_s16x4 bv = *(const t2v_s16x4*)&Xt[buf][16 * n + j + kx][4 * kq];
                 acc[n] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(av, bv, acc[n], 0, 0, 0);
             }
         }
@@ -641,7 +634,6 @@ __global__ __launch_bounds__(256) void k_conv5_fwd_bf16(ConvBf16Args a) {
 // sets, loop unrolled by two): the 16-channel kernel above spent ~3 us per k-tile — one memory round trip under load — for 400
 // cycles of MFMA work (the B = 16 Postnet convolution: 16.8 GFLOP in 97 us).
 #define CB2_RS 40    // LDS row stride in bf16 elements (80 B)
-typedef __bf16 cb2_bf16x8 __attribute__((ext_vector_type(8)));
 template <int NTW>
 __global__ __launch_bounds__(256) void k_conv5_fwd_bf16k32(ConvBf16Args a) {
     constexpr int BN = 16 * NTW;
@@ -696,7 +688,7 @@ __global__ __launch_bounds__(256) void k_conv5_fwd_bf16k32(ConvBf16Args a) {
         for (int i = 0; i < 5; ++i) *(uint4*)(&As[buf][0][0][0] + a_lds[i]) = ra[i];
 #pragma unroll
         for (int i = 0; i < NXP; ++i)
-            if (x_lds[i] >= 0) *(unsigned*)(&Xt[buf][0][0] + x_lds[i]) = pack_bf16x2(rx[i][0], rx[i][1]);
+            if (x_lds[i] >= 0) *(unsigned*)(&Xt[buf][0][0] + x_lds[i]) = t2v_pack_bf16x2(rx[i][0], rx[i][1]);
     };
     f32x4 acc[NTW];
 #pragma unroll
@@ -704,10 +696,10 @@ __global__ __launch_bounds__(256) void k_conv5_fwd_bf16k32(ConvBf16Args a) {
     auto multiply = [&](int buf) {
 #pragma unroll
         for (int kx = 0; kx < 5; ++kx) {
-            const cb2_bf16x8 av = *(const cb2_bf16x8*)&As[buf][kx][16 * wave + j][8 * kq];
+            const t2v_bf16x8 av = *(const t2v_bf16x8*)&As[buf][kx][16 * wave + j][8 * kq];
 #pragma unroll
             for (int n = 0; n < NTW; ++n) {
-                const cb2_bf16x8 bv = *(const cb2_bf16x8*)&Xt[buf][16 * n + j + kx][8 * kq];
+                const t2v_bf16x8 bv = *(const t2v_bf16x8*)&Xt[buf][16 * n + j + kx][8 * kq];
                 acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[n], 0, 0, 0);
             }
         }
@@ -829,7 +821,7 @@ __global__ __launch_bounds__(256) void k_conv5_dw_bf16(ConvTiledArgs a) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int k = 4 * ((tid >> 6) + 4 * i);
-            *(uint2*)&As[buf][a_m][k] = make_uint2(pack_bf16x2(ra[i].x, ra[i].y), pack_bf16x2(ra[i].z, ra[i].w));
+            *(uint2*)&As[buf][a_m][k] = make_uint2(t2v_pack_bf16x2(ra[i].x, ra[i].y), t2v_pack_bf16x2(ra[i].z, ra[i].w));
         }
 #pragma unroll
         for (int i = 0; i < NXI; ++i) {
@@ -838,7 +830,7 @@ __global__ __launch_bounds__(256) void k_conv5_dw_bf16(ConvTiledArgs a) {
             if (c < 16) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    *(uint2*)&Xs[buf][r][c][4 * q] = make_uint2(pack_bf16x2(rx[i][r], rx[i][r + 1]), pack_bf16x2(rx[i][r + 2], rx[i][r + 3]));
+                    *(uint2*)&Xs[buf][r][c][4 * q] = make_uint2(t2v_pack_bf16x2(rx[i][r], rx[i][r + 1]), t2v_pack_bf16x2(rx[i][r + 2], rx[i][r + 3]));
             }
         }
     };
@@ -865,10 +857,10 @@ __global__ __launch_bounds__(256) void k_conv5_dw_bf16(ConvTiledArgs a) {
         const unsigned short* xp = &Xs[buf][0][0][0];
 #pragma unroll
         for (int s = 0; s < BT / 16; ++s) {
-            const s16x4 av = *(const s16x4*)(ap + 16 * s);
+            const t2v_s16x4 av = *(const t2v_s16x4*)(ap + 16 * s);
 #pragma unroll
             for (int n = 0; n < 5; ++n) {
-                const s16x4 bv = *(const s16x4*)(xp + boff[n] + 16 * s);
+                const t2v_s16x4 bv = *(const t2v_s16x4*)(xp + boff[n] + 16 * s);
                 acc[n] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(av, bv, acc[n], 0, 0, 0);
             }
         }

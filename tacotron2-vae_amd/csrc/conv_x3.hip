@@ -19,37 +19,16 @@
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_coop.h"
+#include "t2v_x3.h"
+#include "t2v_xchg.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 cx_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cx_bf16x2 __attribute__((ext_vector_type(2)));
 #define CX_BM 128
 #define CX_BN 128
 #define CX_XS 136                   // activation slots per tile and channel group: 128 positions + 4 halo (+ 4: the DMA's last piece is 8 lanes)
 
-__device__ __forceinline__ unsigned cx_pack(float lo, float hi) {
-    cx_bf16x2 p = {(__bf16)lo, (__bf16)hi};
-    return *(unsigned*)&p;
-}
-__device__ __forceinline__ void cx_split8(const float (&v)[8], uint4& p0, uint4& p1, uint4& p2) {
-    unsigned q0[4], q1[4], q2[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float x = v[2 * c], y = v[2 * c + 1];
-        const unsigned h = cx_pack(x, y);
-        const float r1x = x - __uint_as_float(h << 16), r1y = y - __uint_as_float(h & 0xffff0000u);
-        const unsigned m = cx_pack(r1x, r1y);
-        const float r2x = r1x - __uint_as_float(m << 16), r2y = r1y - __uint_as_float(m & 0xffff0000u);
-        q0[c] = h; q1[c] = m; q2[c] = cx_pack(r2x, r2y);
-    }
-    p0 = make_uint4(q0[0], q0[1], q0[2], q0[3]);
-    p1 = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-    p2 = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-}
-
 // NP = 3: the x3 planes of an fp32 operand; NP = 1: ONE plane, the operand rounded to bf16 (bf16_run)
 __device__ __forceinline__ uint4 cx_round8(const float (&v)[8]) {
-    return make_uint4(cx_pack(v[0], v[1]), cx_pack(v[2], v[3]), cx_pack(v[4], v[5]), cx_pack(v[6], v[7]));
+    return make_uint4(t2v_pack_bf16x2(v[0], v[1]), t2v_pack_bf16x2(v[2], v[3]), t2v_pack_bf16x2(v[4], v[5]), t2v_pack_bf16x2(v[6], v[7]));
 }
 // W (M, Cin, 5) fp32 -> Wp[tap][plane][g][Mp]: thread = (row m, channel group g), all five taps
 template <int NP>
@@ -74,7 +53,7 @@ __global__ __launch_bounds__(256) void k_cx3_split_w(const float* __restrict__ W
         for (int c = 0; c < 8; ++c) v[c] = w[c][k];
         if (NP == 3) {
             uint4 p0, p1, p2;
-            cx_split8(v, p0, p1, p2);
+            t2v_split8(v, p0, p1, p2);
             Wp[((size_t)(k * NP + 0) * G + g) * Mp + m] = p0;
             Wp[((size_t)(k * NP + (NP > 1 ? 1 : 0)) * G + g) * Mp + m] = p1;
             Wp[((size_t)(k * NP + (NP > 2 ? 2 : 0)) * G + g) * Mp + m] = p2;
@@ -101,7 +80,7 @@ __global__ __launch_bounds__(256) void k_cx3_split_x(const float* __restrict__ X
     uint4* dst = Xp + (((size_t)b * NP) * G + g) * Tp + s;
     if (NP == 3) {
         uint4 p0, p1, p2;
-        cx_split8(v, p0, p1, p2);
+        t2v_split8(v, p0, p1, p2);
         dst[0] = p0;
         dst[(size_t)(NP > 1 ? 1 : 0) * G * Tp] = p1;
         dst[(size_t)(NP > 2 ? 2 : 0) * G * Tp] = p2;
@@ -118,26 +97,7 @@ struct ConvX3Args {
     float* part; unsigned* tile_ctr;
 };
 
-// 16 bytes per lane global -> LDS without a destination register (lane i lands at lds_addr + 16 i; lds_addr wave-uniform, in an SGPR).
-// Inline asm on purpose: hipcc counts the builtin form as an LDS write and puts `s_waitcnt vmcnt(0)` in front of EVERY later ds_read —
-// the prefetch issued at the top of a step was waited for before the step's own MFMAs (first version of these kernels: 1.9 us per step
-// of 0.35 us of MFMA work).  The asm form is invisible to its bookkeeping; the waits are counted by hand below.
-__device__ __forceinline__ void cx_dma16(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_addr) : "memory");
-}
 #define CX_NW 4                     // weight tiles in flight + 1: the tile of step i + 3 is requested during step i
-template <int N>
-__device__ __forceinline__ void cx_wait() {
-    if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else static_assert(N == 6, "add the literal");
-}
 // NP planes per operand, NG channel groups (of 8) per stage: <3, 2> = fp32 operands cut into three bf16 planes (six MFMAs per 16
 // channels and tap, 24 per wave and step); <1, 4> = bf16_run on operands rounded once (8 MFMAs per wave and step of 32 channels)
 template <int NP, int NG>
@@ -166,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
         for (int i = 0; i < WPW; ++i) {
             const int q = wave + 4 * i, p = q / (2 * NG), g = (q >> 1) % NG, half = q & 1;
             const uint4* src = a.Wp + ((size_t)(tap * NP + p) * a.G + NG * st + g) * a.Mp + i0 + 64 * half + lane;
-            cx_dma16(src, lds0 + 16u * (unsigned)(((buf * NP + p) * NG + g) * CX_BM + 64 * half));
+            t2v_dma16(src, lds0 + 16u * (unsigned)(((buf * NP + p) * NG + g) * CX_BM + 64 * half));
         }
     };
     // activation tile of a stage: NP planes x NG channel groups x (64 + 64 + 8 slots): 3 NP NG pieces, the short ones with 8 lanes
@@ -179,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
                 const int pg = q / 3, piece = q - 3 * pg, p = pg / NG, g = pg % NG;
                 const uint4* src = a.Xp + (((size_t)bb * NP + p) * a.G + NG * st + g) * a.Tp + t0 + 64 * piece + lane;
                 const unsigned dst = lds0 + 16u * (unsigned)(CX_NW * WSL + ((buf * NP + p) * NG + g) * CX_XS + 64 * piece);
-                if (piece < 2 || lane < 8) cx_dma16(src, dst);
+                if (piece < 2 || lane < 8) t2v_dma16(src, dst);
             }
         }
     };
@@ -191,13 +151,13 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
     const int am = 64 * wm + (lane & 31), bn = 64 * wn + (lane & 31), kq = lane >> 5;
-#define CX_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const cx_bf16x8*)&(A_), *(const cx_bf16x8*)&(B_), C_, 0, 0, 0)
+#define CX_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const t2v_bf16x8*)&(A_), *(const t2v_bf16x8*)&(B_), C_, 0, 0, 0)
     // prologue: the activation tile of the first stage and the weight tiles of steps 0, 1, 2
     dma_x(s0, 0);
     dma_w(s0, 0, 0);
     dma_w(s0, 1, 1);
     dma_w(s0, 2, 2);
-    cx_wait<2 * WPW>();         // everything but the tiles of steps 1 and 2
+    t2v_wait_vmcnt<2 * WPW>();         // everything but the tiles of steps 1 and 2
     __syncthreads();
     int idx = 0;
     for (int st = s0; st < s1; ++st) {
@@ -230,8 +190,8 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
             // the weight tile of step idx + 1 (requested two steps ago) must have landed before anybody passes the barrier; requests
             // come back in order, so it has once at most the younger ones are outstanding: the weight requests of the last two steps
             // (WPW each per wave) and — until tap 3 — this stage's activation request (>= XPW per wave), which is younger as well
-            if (tap < 3) cx_wait<2 * WPW + XPW>();
-            else cx_wait<2 * WPW>();
+            if (tap < 3) t2v_wait_vmcnt<2 * WPW + XPW>();
+            else t2v_wait_vmcnt<2 * WPW>();
             __syncthreads();    // ... and this step's LDS reads are done (the next step overwrites nothing that is still read: CX_NW = 4)
         }
     }
@@ -242,16 +202,15 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
     if (gridDim.z > 1) {
         // channel split: raw accumulators to scratch in accumulator order (write-through), the workgroup that arrives last at its
         // tile's counter adds the partials in the fixed order z = 0, 1, ... and runs the epilogue (see gemm.hip)
-        typedef unsigned cx_u32x4 __attribute__((ext_vector_type(4)));
         {
-            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (blockIdx.z * tiles + tile) * (CX_BM * CX_BN), 0, 0x7fffffff, 0x00020000);
+            __amdgpu_buffer_rsrc_t rs = t2v_rsrc(a.part + (blockIdx.z * tiles + tile) * (CX_BM * CX_BN));
 #pragma unroll
             for (int x = 0; x < 2; ++x)
 #pragma unroll
                 for (int y = 0; y < 2; ++y)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        cx_u32x4 v;
+                        u32x4 v;
                         v.x = __float_as_uint(acc[x][y][4 * q]); v.y = __float_as_uint(acc[x][y][4 * q + 1]);
                         v.z = __float_as_uint(acc[x][y][4 * q + 2]); v.w = __float_as_uint(acc[x][y][4 * q + 3]);
                         __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((((x * 2 + y) * 4 + q) * 256) + tid) * 16, 0, 16);
@@ -273,11 +232,11 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
         for (int z0 = 0; z0 < nz; z0 += 2) {
-            cx_u32x4 v[2][16];
+            u32x4 v[2][16];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int z = min(z0 + u, nz - 1);
-                __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (z * tiles + tile) * (CX_BM * CX_BN), 0, 0x7fffffff, 0x00020000);
+                __amdgpu_buffer_rsrc_t rs = t2v_rsrc(a.part + (z * tiles + tile) * (CX_BM * CX_BN));
 #pragma unroll
                 for (int g = 0; g < 16; ++g) v[u][g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (g * 256 + tid) * 16, 0, 16);
             }

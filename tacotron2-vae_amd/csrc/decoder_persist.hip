@@ -3,7 +3,7 @@
 // loop lives in registers / LDS, and the five dependent stages of a frame
 //     attention_rnn -> attention -> decoder_rnn -> projection (+ folded Prenet layer 0) -> Prenet layer 1
 // hand their small result vectors (1024 / 512 / 256 values per item) from CU to CU as plain 4-byte values in a FRESH,
-// sentinel-filled exchange row per frame (write-through sc1 stores, sc1 loads; a word that is no longer 0xFFFFFFFF IS the
+// sentinel-filled exchange row per frame (write-through sc1 stores, sc1 loads; a word that is no longer T2V_SENT IS the
 // data — no tags, no counters, no fences, no grid barrier).  Round 3: half the bytes of the former 8-byte {value, tag}
 // granules — what a gather costs is its bytes (a CU pulls ~11 B/cycle from beyond its L2) — and an adaptive nap
 // in front of every poll, so that the first round of a gather is not the one that is bound to fail.  Nothing is streamed from HBM per frame: the 71 MB of LSTM weights that the launch-per-stage
@@ -22,6 +22,7 @@
 // everything else (and the stepwise decode() API).
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_xchg.h"
 #include <limits.h>
 
 #define PD_THREADS 512
@@ -78,40 +79,13 @@ __host__ __device__ static inline unsigned pd_ex(int B) { return (unsigned)B * 3
 __host__ __device__ static inline unsigned pd_stop(int B) { return (unsigned)B * 5120u; }
 __host__ __device__ static inline unsigned pd_row(int B) { return (unsigned)B * 5120u + 32u; }
 
-#define PD_SENT 0xFFFFFFFFu
 #ifndef PD_POLL2
 #define PD_POLL2 0
 #endif
-#define PD_SC1 16
-typedef unsigned pd_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pd_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pd_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-// offsets in floats
+// 4-byte publish at a float offset.  Kept as a function: with the offset arithmetic written out at the call sites the
+// compiler schedules the kernel differently.
 __device__ __forceinline__ void pd_put(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)(off * 4u), 0, PD_SC1);
-}
-__device__ __forceinline__ void pd_put4(__amdgpu_buffer_rsrc_t r, unsigned off, float v0, float v1, float v2, float v3) {
-    const pd_u32x4 x = {__float_as_uint(v0), __float_as_uint(v1), __float_as_uint(v2), __float_as_uint(v3)};
-    __builtin_amdgcn_raw_buffer_store_b128(x, r, (int)(off * 4u), 0, PD_SC1);
-}
-__device__ __forceinline__ unsigned pd_get(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)(off * 4u), 0, PD_SC1);
-}
-__device__ __forceinline__ pd_u32x2 pd_get2(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b64(r, (int)(off * 4u), 0, PD_SC1);
-}
-__device__ __forceinline__ pd_u32x4 pd_get4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 4u), 0, PD_SC1);
-}
-__device__ __forceinline__ bool pd_give_up(unsigned& spins, unsigned* err, int* flag) {
-    if (++spins > PD_SPIN || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = 0;
-        return true;
-    }
-    return false;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)(off * 4u), 0, T2V_SC1);
 }
 
 // Poll the n (<= 2 * 512, even) values at `off` until none is the sentinel, then copy them to LDS: thread = two adjacent
@@ -121,28 +95,28 @@ __device__ __forceinline__ int pd_gather(float* dst, __amdgpu_buffer_rsrc_t r, u
     const int tid = threadIdx.x;
     for (int i = 0; i < nap; i += 4) __builtin_amdgcn_s_sleep(4);
     const bool on = 2 * tid < n;
-    pd_u32x2 x = {0u, 0u};
+    u32x2 x = {0u, 0u};
     unsigned spins = 0;
 #if PD_POLL2
     // (measurement variant, -DPD_POLL2=1: two polls in flight, half a round trip apart.  Same-box A/B: 14.68 vs 14.39 us per
     // frame — twice the requests on lines that 256 workgroups already poll cost more than the quarter round trip they save)
-    pd_u32x2 x0 = {PD_SENT, PD_SENT}, x1 = {PD_SENT, PD_SENT};
-    if (on) x0 = pd_get2(r, off + 2u * (unsigned)tid);
+    u32x2 x0 = {T2V_SENT, T2V_SENT}, x1 = {T2V_SENT, T2V_SENT};
+    if (on) x0 = t2v_ld_b64(r, (off + 2u * (unsigned)tid) * 4u);
     __builtin_amdgcn_s_sleep(4);
-    if (on) x1 = pd_get2(r, off + 2u * (unsigned)tid);
+    if (on) x1 = t2v_ld_b64(r, (off + 2u * (unsigned)tid) * 4u);
     for (;;) {
-        if (__all(!on || (x0[0] != PD_SENT && x0[1] != PD_SENT))) { x = x0; break; }
-        if (on) x0 = pd_get2(r, off + 2u * (unsigned)tid);
-        if (__all(!on || (x1[0] != PD_SENT && x1[1] != PD_SENT))) { x = x1; break; }
-        if (on) x1 = pd_get2(r, off + 2u * (unsigned)tid);
-        if (pd_give_up(spins, err, flag)) break;
+        if (__all(!on || (x0[0] != T2V_SENT && x0[1] != T2V_SENT))) { x = x0; break; }
+        if (on) x0 = t2v_ld_b64(r, (off + 2u * (unsigned)tid) * 4u);
+        if (__all(!on || (x1[0] != T2V_SENT && x1[1] != T2V_SENT))) { x = x1; break; }
+        if (on) x1 = t2v_ld_b64(r, (off + 2u * (unsigned)tid) * 4u);
+        if (t2v_give_up(spins, PD_SPIN, err, flag)) break;
     }
 #else
     for (;;) {
-        if (on) x = pd_get2(r, off + 2u * (unsigned)tid);
-        if (__all(x[0] != PD_SENT && x[1] != PD_SENT)) break;
+        if (on) x = t2v_ld_b64(r, (off + 2u * (unsigned)tid) * 4u);
+        if (__all(x[0] != T2V_SENT && x[1] != T2V_SENT)) break;
         __builtin_amdgcn_s_sleep(1);
-        if (pd_give_up(spins, err, flag)) break;
+        if (t2v_give_up(spins, PD_SPIN, err, flag)) break;
     }
 #endif
     if (on) *(float2*)(dst + 2 * tid) = make_float2(__uint_as_float(x[0]), __uint_as_float(x[1]));
@@ -157,21 +131,21 @@ __device__ __forceinline__ int pd_gather_items(float* dst, __amdgpu_buffer_rsrc_
     const int tid = threadIdx.x;
     for (int i = 0; i < nap; i += 4) __builtin_amdgcn_s_sleep(4);
     const bool on = 2 * tid < n;
-    pd_u32x2 x[PD_MAXB];
+    u32x2 x[PD_MAXB];
 #pragma unroll
-    for (int b = 0; b < PD_MAXB; ++b) x[b] = pd_u32x2{0u, 0u};
+    for (int b = 0; b < PD_MAXB; ++b) x[b] = u32x2{0u, 0u};
     unsigned spins = 0;
     for (;;) {
         bool ok = true;
         if (on) {
 #pragma unroll
-            for (int b = 0; b < PD_MAXB; ++b) x[b] = pd_get2(r, off + (unsigned)min(b, B - 1) * stride + 2u * (unsigned)tid);
+            for (int b = 0; b < PD_MAXB; ++b) x[b] = t2v_ld_b64(r, (off + (unsigned)min(b, B - 1) * stride + 2u * (unsigned)tid) * 4u);
 #pragma unroll
-            for (int b = 0; b < PD_MAXB; ++b) ok = ok && x[b][0] != PD_SENT && x[b][1] != PD_SENT;
+            for (int b = 0; b < PD_MAXB; ++b) ok = ok && x[b][0] != T2V_SENT && x[b][1] != T2V_SENT;
         }
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(1);
-        if (pd_give_up(spins, err, flag)) break;
+        if (t2v_give_up(spins, PD_SPIN, err, flag)) break;
     }
     if (on) {
 #pragma unroll
@@ -332,7 +306,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
     for (int i = tid; i < B * T2V_PRE; i += PD_THREADS) X[(i >> 8) * PD_XW + PD_X_P1 + (i & 255)] = a.pre_first[i];
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t rx = pd_rsrc(a.xg);
+    const __amdgpu_buffer_rsrc_t rx = t2v_rsrc(a.xg);
     int nap_e = 0, nap_h = 0, nap_x = 0, nap_c = 0, nap_p = 0, nap_q = 0;      // adaptive naps in front of the polls (64-cycle units)
     // partial gate sums carried from where their inputs appear to where the gates are needed (see pd_gemv_part); frame 0
     // starts from h_att = ctx = h_dec = 0, i.e. from zero partial sums
@@ -348,17 +322,17 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
             // lines behind it were a hot spot that took ~4 us to hand the values over (time line of tools/dbg_persist.py).  So
             // ONE wave per item polls (one 16-byte load per lane) and thread 0 alone watches the stop word.
             if (tid < 64 * B) {
-                pd_u32x4 pv = {0u, 0u, 0u, 0u};
+                u32x4 pv = {0u, 0u, 0u, 0u};
                 unsigned spins = 0, sx = 0u;
                 for (int i = 0; i < nap_e; i += 4) __builtin_amdgcn_s_sleep(4);
                 for (;;) {
-                    pv = pd_get4(rx, xprev + pd_pre1(B) + 4u * (unsigned)tid);          // [b][256] is contiguous
-                    if (tid == 0) sx = pd_get(rx, xprev + pd_stop(B));
+                    pv = t2v_ld_b128(rx, (xprev + pd_pre1(B) + 4u * (unsigned)tid) * 4u);          // [b][256] is contiguous
+                    if (tid == 0) sx = t2v_ld_b32(rx, (xprev + pd_stop(B)) * 4u);
                     if (tid == 0 && sx == 2u) flag[0] = 2;              // the gate fired on the previous frame: nothing runs after it
-                    if (__all(pv[0] != PD_SENT && pv[1] != PD_SENT && pv[2] != PD_SENT && pv[3] != PD_SENT && sx != PD_SENT)) break;
+                    if (__all(pv[0] != T2V_SENT && pv[1] != T2V_SENT && pv[2] != T2V_SENT && pv[3] != T2V_SENT && sx != T2V_SENT)) break;
                     if (__any(tid == 0 && sx == 2u)) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (pd_give_up(spins, a.err, flag)) break;
+                    if (t2v_give_up(spins, PD_SPIN, a.err, flag)) break;
                 }
                 nap_e = pd_adapt(nap_e, (int)spins);
                 const int i = 4 * tid;
@@ -398,7 +372,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
             const float h1 = T2V_DPP_QUAD_F(h, 1), h2 = T2V_DPP_QUAD_F(h, 2), h3 = T2V_DPP_QUAD_F(h, 3);      // (used by lane u == 0 only)
             // (offset rebuilt from an opaque copy of the thread index: hoisted out of the frame loop it was spilled, and its reload from
             // scratch — a vector-memory load + s_waitcnt vmcnt(0) — sat in front of this store on every frame's chain; round 6)
-            if (u == 0) pd_put4(rx, xcur + pd_hatt(B) + (unsigned)((pd_opaque(threadIdx.x) >> 2) * 1024 + 4 * wg), h, h1, h2, h3);
+            if (u == 0) t2v_st(rx, (xcur + pd_hatt(B) + (unsigned)((pd_opaque(threadIdx.x) >> 2) * 1024 + 4 * wg)) * 4u, u32x4{__float_as_uint(h), __float_as_uint(h1), __float_as_uint(h2), __float_as_uint(h3)});
         }
         PD_STAMP(0, 1);
         PD_RT(1);
@@ -505,13 +479,13 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
                     bool ok = true;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        const unsigned x = pd_get(rx, e0 + (unsigned)(i * 256));
+                        const unsigned x = t2v_ld_b32(rx, (e0 + (unsigned)(i * 256)) * 4u);
                         p[i] = __uint_as_float(x);
-                        ok = ok && x != PD_SENT;
+                        ok = ok && x != T2V_SENT;
                     }
                     if (__all(ok)) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (pd_give_up(spins, a.err, flag)) break;
+                    if (t2v_give_up(spins, PD_SPIN, a.err, flag)) break;
                 }
                 nap_x = pd_adapt(nap_x, (int)spins);
                 const float ev = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
@@ -597,7 +571,7 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
             cst[PD_MAXB * 4 + b * 4 + u] = c;
             const float h = go * tanhf_(c);
             const float h1 = T2V_DPP_QUAD_F(h, 1), h2 = T2V_DPP_QUAD_F(h, 2), h3 = T2V_DPP_QUAD_F(h, 3);      // (used by lane u == 0 only)
-            if (u == 0) pd_put4(rx, xcur + pd_hdec(B) + (unsigned)((pd_opaque(threadIdx.x) >> 2) * 1024 + 4 * wg), h, h1, h2, h3);
+            if (u == 0) t2v_st(rx, (xcur + pd_hdec(B) + (unsigned)((pd_opaque(threadIdx.x) >> 2) * 1024 + 4 * wg)) * 4u, u32x4{__float_as_uint(h), __float_as_uint(h1), __float_as_uint(h2), __float_as_uint(h3)});
         }
         PD_STAMP(0, 7); PD_STAMP(64, 12);
         PD_RT(7);
@@ -706,28 +680,28 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
                 for (int i = 0; i < nap_q; i += 4) __builtin_amdgcn_s_sleep(4);
                 if (B == 1) {
                     const unsigned gq = xcur + pd_pre0(B) + (unsigned)(4 * lane);
-                    pd_u32x4 x;
+                    u32x4 x;
                     for (;;) {
-                        x = pd_get4(rx, gq);
-                        if (__all(x[0] != PD_SENT && x[1] != PD_SENT && x[2] != PD_SENT && x[3] != PD_SENT)) break;
+                        x = t2v_ld_b128(rx, gq * 4u);
+                        if (__all(x[0] != T2V_SENT && x[1] != T2V_SENT && x[2] != T2V_SENT && x[3] != T2V_SENT)) break;
                         __builtin_amdgcn_s_sleep(1);
-                        if (pd_give_up(spins, a.err, flag)) break;
+                        if (t2v_give_up(spins, PD_SPIN, a.err, flag)) break;
                     }
                     *(float4*)(p0_s + 4 * lane) = make_float4(__uint_as_float(x[0]), __uint_as_float(x[1]), __uint_as_float(x[2]), __uint_as_float(x[3]));
                 } else {
                     // (all items in one polling pass, their loads in flight together: item by item every item paid its own round trip)
-                    pd_u32x4 x[PD_MAXB];
+                    u32x4 x[PD_MAXB];
                     for (;;) {
                         bool ok = true;
     #pragma unroll
                         for (int b = 0; b < PD_MAXB; ++b) {
-                            if (b < B || b == 0) x[b] = pd_get4(rx, xcur + pd_pre0(B) + (unsigned)(min(b, B - 1) * 256 + 4 * lane));
+                            if (b < B || b == 0) x[b] = t2v_ld_b128(rx, (xcur + pd_pre0(B) + (unsigned)(min(b, B - 1) * 256 + 4 * lane)) * 4u);
                             else x[b] = x[0];
-                            ok = ok && x[b][0] != PD_SENT && x[b][1] != PD_SENT && x[b][2] != PD_SENT && x[b][3] != PD_SENT;
+                            ok = ok && x[b][0] != T2V_SENT && x[b][1] != T2V_SENT && x[b][2] != T2V_SENT && x[b][3] != T2V_SENT;
                         }
                         if (__all(ok)) break;
                         __builtin_amdgcn_s_sleep(1);
-                        if (pd_give_up(spins, a.err, flag)) break;
+                        if (t2v_give_up(spins, PD_SPIN, a.err, flag)) break;
                     }
     #pragma unroll
                     for (int b = 0; b < PD_MAXB; ++b)
@@ -770,49 +744,19 @@ static size_t pd_lds_bytes(int B, int T_in) {
     f += attn > proj ? attn : proj;
     return f * sizeof(float);
 }
-#define PD_LDS_MAX (160 * 1024)
 
 // exchange scratch: one sentinel-filled row per frame
 extern "C" long t2v_decoder_persist_scratch_floats(int B, int t_end) {
     return (B < 1 || B > PD_MAXB || t_end < 1) ? 0 : (long)((size_t)t_end * pd_row(B));
 }
-__global__ void k_pd_fill(uint4* p, size_t n16) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x)
-        p[i] = make_uint4(PD_SENT, PD_SENT, PD_SENT, PD_SENT);
-}
 // The workgroups of this kernel spin on each other's granules, so ALL 256 must be resident at once: one per CU on a
 // device with >= 256 CUs whose occupancy query admits this launch configuration (512 threads, the run-time LDS carve).
-// Answered once per device and (B, T_in) class; a device that is shared with other work can still fail to co-schedule
-// them — the bounded spins then set the error word and Decoder.inference re-runs the utterance on the launch-per-stage
-// loop.
-static int pd_device_ok(size_t lds) {
-    static int cus = -1;
-    if (cus < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        cus = prop.multiProcessorCount;
-    }
-    if (cus < T2V_NWG) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_decode_persist, hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        attr_set = true;
-    }
-    int nblk = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, (const void*)k_decode_persist, PD_THREADS, lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return nblk >= 1;
-}
-
+// A device that is shared with other work can still fail to co-schedule them — the bounded spins then set the error word
+// and Decoder.inference re-runs the utterance on the launch-per-stage loop.
 extern "C" int t2v_decoder_persist_supported(int B, int T_in) {
-    if (!(B >= 1 && B <= PD_MAXB && T_in >= 1 && T_in <= PD_MAXT && pd_lds_bytes(B, T_in) <= PD_LDS_MAX)) return 0;
-    return pd_device_ok(pd_lds_bytes(B, T_in));
+    if (!(B >= 1 && B <= PD_MAXB && T_in >= 1 && T_in <= PD_MAXT && pd_lds_bytes(B, T_in) <= T2V_LDS_MAX)) return 0;
+    static bool raised = false;
+    return t2v_persist_resident((const void*)k_decode_persist, PD_THREADS, pd_lds_bytes(B, T_in), {(const void*)k_decode_persist}, raised);
 }
 
 extern "C" int t2v_decoder_infer_persistent(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
@@ -825,7 +769,7 @@ extern "C" int t2v_decoder_infer_persistent(const t2v_dec_persist_weights* w, co
         return T2V_ERR_ARG;
     if (((uintptr_t)s->exchange & 15) || (size_t)t_end * pd_row(B) * 4 >= 0x7fffffffull) return T2V_ERR_ARG;      // 31-bit buffer offsets
     const size_t lds = pd_lds_bytes(B, T_in);     // (t2v_decoder_persist_supported raised the dynamic-LDS limit)
-    k_pd_fill<<<1024, 256, 0, stream>>>((uint4*)s->exchange, (size_t)t_end * pd_row(B) / 4);
+    t2v_fill_sentinel(s->exchange, (size_t)t_end * pd_row(B) / 4, 1024, stream);
     (void)hipMemsetAsync(s->err_word, 0, sizeof(unsigned), stream);
     PersistArgs a;
     a.w_ih_att = w->w_ih_att; a.w_hh_att = w->w_hh_att; a.w_ih_dec = w->w_ih_dec; a.w_hh_dec = w->w_hh_dec;

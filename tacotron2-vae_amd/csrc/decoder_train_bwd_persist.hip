@@ -12,52 +12,19 @@
 //   A  attention_rnn + attention (k_achain_bwd): dga(t+1) -> Wcat_att^T -> [d h_att(t) | d ctx(t)] -> attention(t)
 //      backward (workgroups split over encoder positions) -> dq(t) -> W_q^T -> cell backward -> dga(t).
 // Hand-offs as in decoder_train_persist.hip: every exchanged value is produced exactly once per pass, so the exchange
-// buffers are pre-filled with a NaN sentinel (0xFFFFFFFF) and a word that is no longer the sentinel IS the data — 4 bytes
+// buffers are pre-filled with a NaN sentinel (T2V_SENT, t2v_xchg.h) and a word that is no longer the sentinel IS the data — 4 bytes
 // per value on the wire, sc1 (write-through) stores, sc1 loads, no flags, no ordering.  Gate-gradient rows travel as
 // [plane][k][items] so that a consumer's 16-byte (items 0..3) / 8-byte (items 4, 5) load is an LDS-ready GEMV operand.
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_xchg.h"
 
-#ifndef PBA_WHOLE_ITEM
-#define PBA_WHOLE_ITEM 0      // 1 (measurement): ONE attention workgroup per item up to 96 symbols instead of 16-position slices
-#endif
-#ifndef PBA_DQ_DIRECT
-#define PBA_DQ_DIRECT 0       // 1 (measurement): the attention_rnn workgroups sum the slices' partial dq rows themselves
-#endif
 #define PB_THREADS 512
 #define PB_MAXB 6
 #define PB_MAXT 224                   // 16- / 32-position attention slices up to here
 #define PB_MAXT_LONG 576              // 96-position slices on eight waves beyond (k_achain_bwd<.., true>): at most six per item
 #define PB_SPIN 400000
-#define PB_SENT 0xFFFFFFFFu
 #define PB_KJ (T2V_G / PB_THREADS)          // 8 gate rows per thread: k = tid + 512 j
-
-typedef unsigned pb_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned pb_u32x2 __attribute__((ext_vector_type(2)));
-typedef float pb_f32x2 __attribute__((ext_vector_type(2)));
-#define PB_SC1 16
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pb_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ f32x4 pb_ld16(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, PB_SC1));
-}
-__device__ __forceinline__ pb_f32x2 pb_ld8(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(pb_f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, PB_SC1));
-}
-__device__ __forceinline__ unsigned pb_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, PB_SC1);
-}
-__device__ __forceinline__ void pb_st16(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pb_u32x4, v), r, (int)off, 0, PB_SC1);
-}
-__device__ __forceinline__ void pb_st8(__amdgpu_buffer_rsrc_t r, unsigned off, pb_f32x2 v) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(pb_u32x2, v), r, (int)off, 0, PB_SC1);
-}
-__device__ __forceinline__ void pb_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)off, 0, PB_SC1);
-}
-__device__ __forceinline__ bool pb_ok(float v) { return __float_as_uint(v) != PB_SENT; }
 
 // ---- a gate-gradient row (4096 gate rows x B items) in the exchange buffer / in LDS:
 //   plane 0: k -> 16 bytes (items 0..3) at byte 16 k          (64 KB)
@@ -66,34 +33,30 @@ __device__ __forceinline__ bool pb_ok(float v) { return __float_as_uint(v) != PB
 
 // gather one row into LDS (X0: f32x4[4096], X1: f32x2[4096]); nap first, then poll the payload itself.  Returns rounds.
 template <int NB>
-__device__ __forceinline__ int pb_gather_row(f32x4* X0, pb_f32x2* X1, __amdgpu_buffer_rsrc_t r, unsigned row_off, int B, int nap,
+__device__ __forceinline__ int pb_gather_row(f32x4* X0, f32x2* X1, __amdgpu_buffer_rsrc_t r, unsigned row_off, int B, int nap,
                                              unsigned* err, int* flag) {
     const int tid = threadIdx.x;
     for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
     f32x4 v0[PB_KJ];
-    pb_f32x2 v1[PB_KJ];
+    f32x2 v1[PB_KJ];
     int rounds = 0;
     const int nw0 = min(B, 4), nw1 = B - 4;
     for (;;) {
 #pragma unroll
-        for (int j = 0; j < PB_KJ; ++j) v0[j] = pb_ld16(r, row_off + 16u * (unsigned)(tid + PB_THREADS * j));
+        for (int j = 0; j < PB_KJ; ++j) v0[j] = t2v_ld_f32x4(r, row_off + 16u * (unsigned)(tid + PB_THREADS * j));
         if (NB > 4) {
 #pragma unroll
-            for (int j = 0; j < PB_KJ; ++j) v1[j] = pb_ld8(r, row_off + 65536u + 8u * (unsigned)(tid + PB_THREADS * j));
+            for (int j = 0; j < PB_KJ; ++j) v1[j] = t2v_ld_f32x2(r, row_off + 65536u + 8u * (unsigned)(tid + PB_THREADS * j));
         }
         bool ok = true;
 #pragma unroll
         for (int j = 0; j < PB_KJ; ++j) {
-            ok = ok && pb_ok(v0[j][0]) && (nw0 < 2 || pb_ok(v0[j][1])) && (nw0 < 3 || pb_ok(v0[j][2])) && (nw0 < 4 || pb_ok(v0[j][3]));
-            if (NB > 4) ok = ok && pb_ok(v1[j][0]) && (nw1 < 2 || pb_ok(v1[j][1]));
+            ok = ok && t2v_ok(v0[j][0]) && (nw0 < 2 || t2v_ok(v0[j][1])) && (nw0 < 3 || t2v_ok(v0[j][2])) && (nw0 < 4 || t2v_ok(v0[j][3]));
+            if (NB > 4) ok = ok && t2v_ok(v1[j][0]) && (nw1 < 2 || t2v_ok(v1[j][1]));
         }
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(2);
-        if (++rounds > PB_SPIN || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = 0;
-            break;
-        }
+        if (t2v_give_up(rounds, PB_SPIN, err, flag)) break;
     }
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
@@ -117,7 +80,7 @@ __device__ __forceinline__ int pb_gather_row(f32x4* X0, pb_f32x2* X1, __amdgpu_b
 // a 4-byte word per lane global -> LDS (lane i lands at ldsbase + 4 i) without a destination register; aux: cache policy
 __device__ __forceinline__ void pb_dma4(const void* g, float* ldsbase, const int aux_sc1) {
     if (aux_sc1)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)ldsbase, 4, 0, PB_SC1);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)ldsbase, 4, 0, T2V_SC1);
     else
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)ldsbase, 4, 0, 0);
 }
@@ -134,7 +97,7 @@ __device__ __forceinline__ void pb_park_factors(float* ldsX, const float* Frow) 
     }
 }
 template <int NB>
-__device__ __forceinline__ int pb_build_row(f32x4* X0, pb_f32x2* X1, __amdgpu_buffer_rsrc_t r, unsigned row_off, int B,
+__device__ __forceinline__ int pb_build_row(f32x4* X0, f32x2* X1, __amdgpu_buffer_rsrc_t r, unsigned row_off, int B,
                                             int nap, unsigned* err, int* flag) {
     const int tid = threadIdx.x;
     for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
@@ -145,31 +108,27 @@ __device__ __forceinline__ int pb_build_row(f32x4* X0, pb_f32x2* X1, __amdgpu_bu
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const unsigned U = (unsigned)(tid + PB_THREADS * h);
-            dc[h] = pb_ld16(r, row_off + 32u * U);
-            dh[h] = pb_ld16(r, row_off + 32u * U + 16u);
-            if (NB > 4) dx[h] = pb_ld16(r, row_off + 32768u + 16u * U);
+            dc[h] = t2v_ld_f32x4(r, row_off + 32u * U);
+            dh[h] = t2v_ld_f32x4(r, row_off + 32u * U + 16u);
+            if (NB > 4) dx[h] = t2v_ld_f32x4(r, row_off + 32768u + 16u * U);
         }
         bool ok = true;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            ok = ok && pb_ok(dc[h][0]) && (nw0 < 2 || pb_ok(dc[h][1])) && (nw0 < 3 || pb_ok(dc[h][2])) && (nw0 < 4 || pb_ok(dc[h][3]));
-            ok = ok && pb_ok(dh[h][0]) && (nw0 < 2 || pb_ok(dh[h][1])) && (nw0 < 3 || pb_ok(dh[h][2])) && (nw0 < 4 || pb_ok(dh[h][3]));
-            if (NB > 4) ok = ok && pb_ok(dx[h][0]) && pb_ok(dx[h][2]) && (nw1 < 2 || (pb_ok(dx[h][1]) && pb_ok(dx[h][3])));
+            ok = ok && t2v_ok(dc[h][0]) && (nw0 < 2 || t2v_ok(dc[h][1])) && (nw0 < 3 || t2v_ok(dc[h][2])) && (nw0 < 4 || t2v_ok(dc[h][3]));
+            ok = ok && t2v_ok(dh[h][0]) && (nw0 < 2 || t2v_ok(dh[h][1])) && (nw0 < 3 || t2v_ok(dh[h][2])) && (nw0 < 4 || t2v_ok(dh[h][3]));
+            if (NB > 4) ok = ok && t2v_ok(dx[h][0]) && t2v_ok(dx[h][2]) && (nw1 < 2 || (t2v_ok(dx[h][1]) && t2v_ok(dx[h][3])));
         }
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(2);
-        if (++rounds > PB_SPIN || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = 0;
-            break;
-        }
+        if (t2v_give_up(rounds, PB_SPIN, err, flag)) break;
     }
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
         const int h = j & 1;
         const f32x4 d = (j >> 1) == 3 ? dh[h] : dc[h];
         X0[tid + PB_THREADS * j] = X0[tid + PB_THREADS * j] * d;
-        if (NB > 4) X1[tid + PB_THREADS * j] = X1[tid + PB_THREADS * j] * ((j >> 1) == 3 ? pb_f32x2{dx[h][2], dx[h][3]} : pb_f32x2{dx[h][0], dx[h][1]});
+        if (NB > 4) X1[tid + PB_THREADS * j] = X1[tid + PB_THREADS * j] * ((j >> 1) == 3 ? f32x2{dx[h][2], dx[h][3]} : f32x2{dx[h][0], dx[h][1]});
     }
     return rounds;
 }
@@ -201,7 +160,7 @@ __global__ __launch_bounds__(256) void k_pb_factors(const float* __restrict__ G,
     }
     float* row = F + (size_t)t * (nb > 4 ? 6 : 4) * T2V_G;
     *(f32x4*)(row + 4 * (size_t)k) = f32x4{f[0], f[1], f[2], f[3]};
-    if (nb > 4) *(pb_f32x2*)(row + 4 * T2V_G + 2 * (size_t)k) = pb_f32x2{f[4], f[5]};
+    if (nb > 4) *(f32x2*)(row + 4 * T2V_G + 2 * (size_t)k) = f32x2{f[4], f[5]};
 }
 
 // CP[t][U][item (nb slots)][8] of one cell: everything the cell backward of (unit U, item) needs at step t that is a function
@@ -238,7 +197,7 @@ __global__ __launch_bounds__(256) void k_pb_cellpre(const float* __restrict__ G,
 // acc[c][pair] += w[c][j] * x[k_j][pair] for NC output columns: packed FMAs (two items per op, weight broadcast through
 // op_sel; even j = low word of the weight pair, odd j = high word) in volatile asm so the k loop keeps its shape.
 template <bool ODD>
-__device__ __forceinline__ void pb_pk3(pb_f32x2& a01, pb_f32x2& a23, pb_f32x2& a45, pb_f32x2 w, pb_f32x2 x01, pb_f32x2 x23, pb_f32x2 x45) {
+__device__ __forceinline__ void pb_pk3(f32x2& a01, f32x2& a23, f32x2& a45, f32x2 w, f32x2 x01, f32x2 x23, f32x2 x45) {
     if (ODD)
         asm volatile("v_pk_fma_f32 %0, %3, %4, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
                      "v_pk_fma_f32 %1, %3, %5, %1 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
@@ -251,21 +210,21 @@ __device__ __forceinline__ void pb_pk3(pb_f32x2& a01, pb_f32x2& a23, pb_f32x2& a
                      : "+v"(a01), "+v"(a23), "+v"(a45) : "v"(w), "v"(x01), "v"(x23), "v"(x45));
 }
 template <int NC, int NB>
-__device__ __forceinline__ void pb_gemv(const pb_f32x2 (&w)[NC][PB_KJ / 2], const f32x4* X0, const pb_f32x2* X1, pb_f32x2 (&acc)[NC][3]) {
+__device__ __forceinline__ void pb_gemv(const f32x2 (&w)[NC][PB_KJ / 2], const f32x4* X0, const f32x2* X1, f32x2 (&acc)[NC][3]) {
     const int tid = threadIdx.x;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = pb_f32x2{0.f, 0.f};
+    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = f32x2{0.f, 0.f};
     f32x4 xa[PB_KJ];
-    pb_f32x2 xb[PB_KJ];
+    f32x2 xb[PB_KJ];
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
         xa[j] = X0[tid + PB_THREADS * j];
-        xb[j] = pb_f32x2{0.f, 0.f};
+        xb[j] = f32x2{0.f, 0.f};
         if (NB > 4) xb[j] = X1[tid + PB_THREADS * j];
     }
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
-        const pb_f32x2 x01 = {xa[j][0], xa[j][1]}, x23 = {xa[j][2], xa[j][3]};
+        const f32x2 x01 = {xa[j][0], xa[j][1]}, x23 = {xa[j][2], xa[j][3]};
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (j & 1) pb_pk3<true>(acc[c][0], acc[c][1], acc[c][2], w[c][j / 2], x01, x23, xb[j]);
@@ -277,7 +236,6 @@ __device__ __forceinline__ void pb_gemv(const pb_f32x2 (&w)[NC][PB_KJ / 2], cons
 // Sum NV <= 32 per-thread values over the 512 threads of the workgroup: 16-lane transposing butterfly (lane c of a row
 // ends with the row sums of values 2c, 2c + 1), then the 32 row partials (8 waves x 4 rows) through LDS:
 // part[(wave * 4 + row) * 32 + idx].  The caller syncs and sums the 32 partials of the values it needs.
-#define PB_DPP(v, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, true))
 __device__ __forceinline__ void pb_reduce32(float (&v)[32], float* part) {
     const int tid = threadIdx.x, lane = tid & 63;
     const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2, b0 = lane & 1;
@@ -285,22 +243,22 @@ __device__ __forceinline__ void pb_reduce32(float (&v)[32], float* part) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const float keep = b3 ? v[16 + i] : v[i], send = b3 ? v[i] : v[16 + i];
-        w16[i] = keep + PB_DPP(send, 0x140);
+        w16[i] = keep + T2V_DPP_F(send, 0x140);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float keep = b2 ? w16[8 + i] : w16[i], send = b2 ? w16[i] : w16[8 + i];
-        w8[i] = keep + PB_DPP(send, 0x141);
+        w8[i] = keep + T2V_DPP_F(send, 0x141);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const float keep = b1 ? w8[4 + i] : w8[i], send = b1 ? w8[i] : w8[4 + i];
-        w4[i] = keep + PB_DPP(send, 0x4E);
+        w4[i] = keep + T2V_DPP_F(send, 0x4E);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const float keep = b0 ? w4[2 + i] : w4[i], send = b0 ? w4[i] : w4[2 + i];
-        w2[i] = keep + PB_DPP(send, 0xB1);
+        w2[i] = keep + T2V_DPP_F(send, 0xB1);
     }
     *(float2*)(part + ((tid >> 6) * 4 + (lane >> 4)) * 32 + 2 * (lane & 15)) = make_float2(w2[0], w2[1]);
 }
@@ -337,10 +295,10 @@ __device__ __forceinline__ void pb_reduce16(float (&v)[16], float* part) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const float keep = b1 ? w4[2 + i] : w4[i], send = b1 ? w4[i] : w4[2 + i];
-        w2[i] = keep + PB_DPP(send, 0x4E);
+        w2[i] = keep + T2V_DPP_F(send, 0x4E);
     }
     const float keep = b0 ? w2[1] : w2[0], send = b0 ? w2[0] : w2[1];
-    part[((tid >> 6) * 4 + (lane >> 4)) * 16 + (lane & 15)] = keep + PB_DPP(send, 0xB1);
+    part[((tid >> 6) * 4 + (lane >> 4)) * 16 + (lane & 15)] = keep + T2V_DPP_F(send, 0xB1);
 }
 __device__ __forceinline__ float pb_sum16(const float* part, int idx) {
     float s[8];
@@ -368,16 +326,16 @@ template <int NB>
 __global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd(PBDArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     f32x4* X0 = (f32x4*)lds;                               // [4096] items 0..3
-    pb_f32x2* X1 = (pb_f32x2*)(lds + 4 * T2V_G);           // [4096] items 4, 5
+    f32x2* X1 = (f32x2*)(lds + 4 * T2V_G);           // [4096] items 4, 5
     float* part = lds + (NB > 4 ? 6 : 4) * T2V_G;          // [32][32]
     float* stage = part + 32 * 32;                         // [4 units][4 gates][8 items]
     int* flag = (int*)(stage + 128);
     const uint64_t seed = t2v_step_seed(a.seed, a.step);
     const int wg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int B = a.B, T = a.T;
-    const __amdgpu_buffer_rsrc_t rX = pb_rsrc(a.GX);
+    const __amdgpu_buffer_rsrc_t rX = t2v_rsrc(a.GX);
     // W_hh_dec^T columns of this workgroup's 4 units: w[u][j] = W_hh_dec[k = tid + 512 j][4 wg + u]
-    pb_f32x2 w[4][PB_KJ / 2];
+    f32x2 w[4][PB_KJ / 2];
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
         const float4 w4 = *(const float4*)(a.w_hh_dec + (size_t)(tid + PB_THREADS * j) * T2V_H + 4 * wg);
@@ -401,7 +359,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd(PBDArgs a) {
             nap = t2v_adapt_nap(nap, rounds);
             __syncthreads();
             if (flag[0] != 1) return;
-            pb_f32x2 acc[4][3];
+            f32x2 acc[4][3];
             pb_gemv<4, NB>(w, X0, X1, acc);
             float v[32];
 #pragma unroll
@@ -448,8 +406,8 @@ __global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd(PBDArgs a) {
                     const int u = tid >> 2, r = tid & 3;
                     const int k = r * T2V_H + 4 * wg + u;
                     const float* sp = stage + (u * 4 + r) * 8;
-                    pb_st16(rX, (unsigned)t * PB_ROW_BYTES(NB) + 16u * (unsigned)k, f32x4{sp[0], sp[1], sp[2], sp[3]});
-                    if (NB > 4) pb_st8(rX, (unsigned)t * PB_ROW_BYTES(NB) + 65536u + 8u * (unsigned)k, pb_f32x2{sp[4], sp[5]});
+                    t2v_st(rX, (unsigned)t * PB_ROW_BYTES(NB) + 16u * (unsigned)k, f32x4{sp[0], sp[1], sp[2], sp[3]});
+                    if (NB > 4) t2v_st(rX, (unsigned)t * PB_ROW_BYTES(NB) + 65536u + 8u * (unsigned)k, f32x2{sp[4], sp[5]});
                 }
             }
         }
@@ -457,30 +415,12 @@ __global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd(PBDArgs a) {
     }
 }
 
-// sentinel fill (16 bytes per thread and iteration)
-__global__ __launch_bounds__(256) void k_pb_fill(uint4* p, size_t n16) {
-    const uint4 s = {PB_SENT, PB_SENT, PB_SENT, PB_SENT};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = s;
-}
-
 static size_t pb_row_bytes(int B) { return B > 4 ? 98304u : 65536u; }
 static size_t pbd_lds_bytes(int B) { return sizeof(float) * ((B > 4 ? 6 : 4) * T2V_G + 32 * 32 + 128 + 4); }
-#define PB_LDS_MAX (160 * 1024)
-
-static int pb_device_ok() {
-    static int cus = -1;
-    if (cus < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        cus = prop.multiProcessorCount;
-    }
-    return cus >= T2V_NWG;
-}
 
 extern "C" int t2v_decoder_bwd_persist_supported(int B, int T_in) {
     if (!(B >= 1 && B <= PB_MAXB && T_in >= 1 && T_in <= PB_MAXT_LONG)) return 0;
-    return pb_device_ok();
+    return t2v_persist_cus_ok();
 }
 // floats of exchange scratch for the decoder_rnn chain (t2v_decoder_bwd_dchain)
 extern "C" long t2v_decoder_bwd_dchain_scratch_floats(int B, int T_out) {
@@ -491,18 +431,13 @@ extern "C" long t2v_decoder_bwd_dchain_scratch_floats(int B, int T_out) {
 extern "C" int t2v_decoder_bwd_dchain(const float* w_hh_dec, const float* dHC, const float* GD, const float* CD, float* DGD,
                                       float* scratch, uint32_t* err_word, int B, int T_out, float p_dec, uint64_t seed, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!w_hh_dec || !dHC || !GD || !CD || !DGD || !scratch || !err_word || B < 1 || B > PB_MAXB || T_out < 1 || !pb_device_ok())
+    if (!w_hh_dec || !dHC || !GD || !CD || !DGD || !scratch || !err_word || B < 1 || B > PB_MAXB || T_out < 1 || !t2v_persist_cus_ok())
         return T2V_ERR_ARG;
     if (((uintptr_t)scratch & 15) || (size_t)T_out * pb_row_bytes(B) >= 0x7fffffffull) return T2V_ERR_ARG;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_dchain_bwd<4>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_dchain_bwd<6>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess)
-            return t2v_check_launch();
-        attr_set = true;
-    }
+    static bool raised = false;
+    if (!t2v_persist_raise_lds({(const void*)k_dchain_bwd<4>, (const void*)k_dchain_bwd<6>}, raised)) return t2v_check_launch();
     (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
-    k_pb_fill<<<1024, 256, 0, stream>>>((uint4*)scratch, (size_t)T_out * pb_row_bytes(B) / 16);
+    t2v_fill_sentinel(scratch, (size_t)T_out * pb_row_bytes(B) / 16, 1024, stream);
     PBDArgs a;
     a.w_hh_dec = w_hh_dec; a.dHC = dHC; a.GD = GD; a.CD = CD; a.DGD = DGD; a.GX = scratch; a.err = err_word;
     a.B = B; a.T = T_out; a.p_dec = p_dec; a.seed = seed; a.step = t2v_step_for(stream);
@@ -602,7 +537,7 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
     // 96 registers of memory rows they spilled)
     constexpr bool AREG_LDS = NWV == 8;
     float* wcs = (float*)(flag + 40);         // [64 rows (c,k)][128] when AREG_LDS
-    const __amdgpu_buffer_rsrc_t rC = pb_rsrc(a.CX), rQ = pb_rsrc(a.DQX), rP = pb_rsrc(a.GPX), rQT = pb_rsrc(a.DQT);
+    const __amdgpu_buffer_rsrc_t rC = t2v_rsrc(a.CX), rQ = t2v_rsrc(a.DQX), rP = t2v_rsrc(a.GPX), rQT = t2v_rsrc(a.DQT);
     // ---- operands resident for the whole pass
     const int d4 = tid & 31, rg = (tid >> 5) & (NRG - 1);
     float4 m0[JS / NWV], m1[JS / NWV];
@@ -671,15 +606,11 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
                     unsigned x0, x1;
                     int spins = 0;
                     for (;;) {          // published at the end of the previous reverse step: almost always there
-                        x0 = pb_ld4(rP, off);
-                        x1 = pb_ld4(rP, off + 4u * GPW);
-                        if (x0 != PB_SENT && x1 != PB_SENT) break;
+                        x0 = t2v_ld_b32(rP, off);
+                        x1 = t2v_ld_b32(rP, off + 4u * GPW);
+                        if (x0 != T2V_SENT && x1 != T2V_SENT) break;
                         __builtin_amdgcn_s_sleep(1);
-                        if (++spins > PB_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                            __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            flag[0] = 0;
-                            break;
-                        }
+                        if (t2v_give_up(spins, PB_SPIN, a.err, flag)) break;
                     }
                     gp += __uint_as_float(x0);
                     gc += __uint_as_float(x1);
@@ -698,21 +629,16 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
             for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
             // TWO polls in flight, half a round trip apart (round 4): with one, a row that lands just after a poll left is
             // only seen a full memory round trip later — this hand-off is on the chain of every reverse step
-            f32x4 x, x0 = pb_ld16(rC, off);
+            f32x4 x, x0 = t2v_ld_f32x4(rC, off);
             __builtin_amdgcn_s_sleep(4);
-            f32x4 x1 = pb_ld16(rC, off);
+            f32x4 x1 = t2v_ld_f32x4(rC, off);
             int rounds = 0;
             for (;;) {
-                if (__all(pb_ok(x0[0]) && pb_ok(x0[1]) && pb_ok(x0[2]) && pb_ok(x0[3]))) { x = x0; break; }
-                x0 = pb_ld16(rC, off);
-                if (__all(pb_ok(x1[0]) && pb_ok(x1[1]) && pb_ok(x1[2]) && pb_ok(x1[3]))) { x = x1; break; }
-                x1 = pb_ld16(rC, off);
-                if (++rounds > PB_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    flag[0] = 0;
-                    x = x0;
-                    break;
-                }
+                if (__all(t2v_ok(x0[0]) && t2v_ok(x0[1]) && t2v_ok(x0[2]) && t2v_ok(x0[3]))) { x = x0; break; }
+                x0 = t2v_ld_f32x4(rC, off);
+                if (__all(t2v_ok(x1[0]) && t2v_ok(x1[1]) && t2v_ok(x1[2]) && t2v_ok(x1[3]))) { x = x1; break; }
+                x1 = t2v_ld_f32x4(rC, off);
+                if (t2v_give_up(rounds, PB_SPIN, a.err, flag)) { x = x0; break; }
             }
             nap = t2v_adapt_nap(nap, rounds);
             // slot (workgroup ja, half h) holds columns c0(ja) + 4 h .. of this item
@@ -791,9 +717,9 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
                     vv += ((p2[0] + p2[T2V_A]) + (p2[2 * T2V_A] + p2[3 * T2V_A])) + ((p2[4 * T2V_A] + p2[5 * T2V_A]) + (p2[6 * T2V_A] + p2[7 * T2V_A]));
                 }
             }
-            pb_st4(rQ, (unsigned)(((t * B + b) * S + s) * T2V_A + tid) * 4u, q);       // partial row (the d W_q GEMM reads them later)
+            t2v_st(rQ, (unsigned)(((t * B + b) * S + s) * T2V_A + tid) * 4u, q);       // partial row (the d W_q GEMM reads them later)
             dvacc += vv;
-            if (s == 0 && !PBA_DQ_DIRECT) {
+            if (s == 0) {
                 // Round 4: slice 0 of an item sums the S partial rows in slice order and publishes ONE row per item.  The ≥ 79
                 // attention_rnn workgroups used to pull all B*S partial rows each (18 KB per workgroup and step through the
                 // ≈ 11 B/cycle a CU gets from beyond its L2: 2.7 us from "published" to "gathered"); now they pull B rows (3 KB)
@@ -806,22 +732,18 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
                     bool ok = true;
 #pragma unroll
                     for (int s2 = 1; s2 < SMAX; ++s2) {
-                        x[s2] = pb_ld4(rQ, off0 + (unsigned)(min(s2, S - 1) * T2V_A) * 4u);
+                        x[s2] = t2v_ld_b32(rQ, off0 + (unsigned)(min(s2, S - 1) * T2V_A) * 4u);
                     }
 #pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) ok = ok && (s2 >= S || x[s2] != PB_SENT);
+                    for (int s2 = 1; s2 < SMAX; ++s2) ok = ok && (s2 >= S || x[s2] != T2V_SENT);
                     if (__all(ok)) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (++spins > PB_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        flag[0] = 0;
-                        break;
-                    }
+                    if (t2v_give_up(spins, PB_SPIN, a.err, flag)) break;
                 }
                 float tot = q;
 #pragma unroll
                 for (int s2 = 1; s2 < SMAX; ++s2) tot += s2 < S ? __uint_as_float(x[s2]) : 0.f;
-                pb_st4(rQT, (unsigned)((t * B + b) * T2V_A + tid) * 4u, tot);           // the cell workgroups wait for this
+                t2v_st(rQT, (unsigned)((t * B + b) * T2V_A + tid) * 4u, tot);           // the cell workgroups wait for this
             }
         }
         PBA_STAMP(blockIdx.x == 0, 10);
@@ -867,7 +789,7 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
 #pragma unroll
                 for (int k = 0; k + 3 < T2V_KS; k += 4) { acc0 += tt[k]; acc1 += tt[k + 1]; acc2 += tt[k + 2]; acc3 += tt[k + 3]; }
                 acc0 += tt[28]; acc1 += tt[29]; acc2 += tt[30];
-                pb_st4(rP, (unsigned)(((t * B + b) * S + s) * (2 * GPW) + c * GPW + jj) * 4u, (acc0 + acc1) + (acc2 + acc3));
+                t2v_st(rP, (unsigned)(((t * B + b) * S + s) * (2 * GPW) + c * GPW + jj) * 4u, (acc0 + acc1) + (acc2 + acc3));
             }
         }
         __syncthreads();
@@ -880,25 +802,25 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
 // y[C0 + c][pair] = sum_j w[C0 + c][j] * x[k_j][pair] for NC of the thread's columns; one LDS operand per gate row with two
 // more in flight (the 168 weight registers leave no room for all eight)
 template <int NCT, int C0, int NC, int NB, int VS = 8>
-__device__ __forceinline__ void pb_gemv_cols(const pb_f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const pb_f32x2* X1, float (&v)[32]) {
+__device__ __forceinline__ void pb_gemv_cols(const f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const f32x2* X1, float (&v)[32]) {
     const int tid = threadIdx.x;
-    pb_f32x2 acc[NC][3];
+    f32x2 acc[NC][3];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = pb_f32x2{0.f, 0.f};
+    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = f32x2{0.f, 0.f};
     constexpr int PF = 3;
     f32x4 xa[PF];
-    pb_f32x2 xb[PF];
+    f32x2 xb[PF];
 #pragma unroll
     for (int d = 0; d < PF; ++d) {
         xa[d] = X0[tid + PB_THREADS * d];
-        xb[d] = pb_f32x2{0.f, 0.f};
+        xb[d] = f32x2{0.f, 0.f};
         if (NB > 4) xb[d] = X1[tid + PB_THREADS * d];
     }
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
         const f32x4 xc = xa[j % PF];
-        const pb_f32x2 yc = xb[j % PF];
-        const pb_f32x2 x01 = {xc[0], xc[1]}, x23 = {xc[2], xc[3]};
+        const f32x2 yc = xb[j % PF];
+        const f32x2 x01 = {xc[0], xc[1]}, x23 = {xc[2], xc[3]};
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (j & 1) pb_pk3<true>(acc[c][0], acc[c][1], acc[c][2], w[C0 + c][j / 2], x01, x23, yc);
@@ -919,26 +841,26 @@ __device__ __forceinline__ void pb_gemv_cols(const pb_f32x2 (&w)[NCT][PB_KJ / 2]
 
 // the same for <= 2 columns into v[16] (two columns x 8 item slots): the operand rows are re-read per round
 template <int NCT, int C0, int NC, int NB>
-__device__ __forceinline__ void pb_gemv_cols16(const pb_f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const pb_f32x2* X1, float (&v)[16]) {
+__device__ __forceinline__ void pb_gemv_cols16(const f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const f32x2* X1, float (&v)[16]) {
     static_assert(NC >= 1 && NC <= 2, "one or two columns");
     const int tid = threadIdx.x;
-    pb_f32x2 acc[NC][3];
+    f32x2 acc[NC][3];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = pb_f32x2{0.f, 0.f};
+    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = f32x2{0.f, 0.f};
     constexpr int PF = 4;
     f32x4 xa[PF];
-    pb_f32x2 xb[PF];
+    f32x2 xb[PF];
 #pragma unroll
     for (int d = 0; d < PF; ++d) {
         xa[d] = X0[tid + PB_THREADS * d];
-        xb[d] = pb_f32x2{0.f, 0.f};
+        xb[d] = f32x2{0.f, 0.f};
         if (NB > 4) xb[d] = X1[tid + PB_THREADS * d];
     }
 #pragma unroll
     for (int j = 0; j < PB_KJ; ++j) {
         const f32x4 xc = xa[j % PF];
-        const pb_f32x2 yc = xb[j % PF];
-        const pb_f32x2 x01 = {xc[0], xc[1]}, x23 = {xc[2], xc[3]};
+        const f32x2 yc = xb[j % PF];
+        const f32x2 x01 = {xc[0], xc[1]}, x23 = {xc[2], xc[3]};
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             if (j & 1) pb_pk3<true>(acc[c][0], acc[c][1], acc[c][2], w[C0 + c][j / 2], x01, x23, yc);
@@ -959,7 +881,7 @@ __device__ __forceinline__ void pb_gemv_cols16(const pb_f32x2 (&w)[NCT][PB_KJ / 
 
 // columns [C0, C0 + N) two at a time: round r leaves its 32 row partials x 16 values at part + 512 r
 template <int NCT, int C0, int N, int NB, int R = 0>
-__device__ __forceinline__ void pba_rounds16(const pb_f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const pb_f32x2* X1, float* part) {
+__device__ __forceinline__ void pba_rounds16(const f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const f32x2* X1, float* part) {
     if constexpr (2 * R < N) {
         float v[16];
         pb_gemv_cols16<NCT, C0 + 2 * R, (N - 2 * R >= 2 ? 2 : 1), NB>(w, X0, X1, v);
@@ -1003,14 +925,10 @@ __device__ __forceinline__ float pba_wait_word(__amdgpu_buffer_rsrc_t r, unsigne
     unsigned x;
     int spins = 0;
     for (;;) {
-        x = pb_ld4(r, off);
-        if (x != PB_SENT) break;
+        x = t2v_ld_b32(r, off);
+        if (x != T2V_SENT) break;
         __builtin_amdgcn_s_sleep(1);
-        if (++spins > PB_SPIN || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = 0;
-            break;
-        }
+        if (t2v_give_up(spins, PB_SPIN, err, flag)) break;
     }
     return __uint_as_float(x);
 }
@@ -1022,8 +940,8 @@ __device__ __forceinline__ void pba_publish_rows(__amdgpu_buffer_rsrc_t r, unsig
     if (tid < 2 * nu) {
         const int u = tid >> 1, q = tid & 1;
         const float* sp = stage + (u * 2 + q) * 8;
-        pb_st16(r, row_off + 32u * (unsigned)(u0 + u) + 16u * (unsigned)q, f32x4{sp[0], sp[1], sp[2], sp[3]});
-        if (NB > 4) pb_st8(r, row_off + 32768u + 16u * (unsigned)(u0 + u) + 8u * (unsigned)q, pb_f32x2{sp[4], sp[5]});
+        t2v_st(r, row_off + 32u * (unsigned)(u0 + u) + 16u * (unsigned)q, f32x4{sp[0], sp[1], sp[2], sp[3]});
+        if (NB > 4) t2v_st(r, row_off + 32768u + 16u * (unsigned)(u0 + u) + 8u * (unsigned)q, f32x2{sp[4], sp[5]});
     }
 }
 
@@ -1032,7 +950,7 @@ template <int NB>
 __device__ __forceinline__ void pba_decoder_role(const PBAArgs& a, float* lds, const int jd, const int ND) {
     const int B = a.B, T = a.T;
     f32x4* X0 = (f32x4*)lds;
-    pb_f32x2* X1 = (pb_f32x2*)(lds + 4 * T2V_G);
+    f32x2* X1 = (f32x2*)(lds + 4 * T2V_G);
     float* part = lds + (NB > 4 ? 6 : 4) * T2V_G;          // [10 rounds][32 row partials][16]
     float* stage = part + 10 * 512;                        // [8 units][2][8]
     float* cpd = stage + 256;                              // [2][64 rows][8] cell-layout factors of steps td, td-1 (k_pb_cellpre)
@@ -1040,9 +958,9 @@ __device__ __forceinline__ void pba_decoder_role(const PBAArgs& a, float* lds, c
     int* flag = (int*)(dhcs + 128);
     const int u0 = (jd * T2V_H) / ND, nu = ((jd + 1) * T2V_H) / ND - u0;      // <= 8 units
     const int c0 = (jd * T2V_E) / ND, nc = ((jd + 1) * T2V_E) / ND - c0;      // <= 4 context columns
-    const __amdgpu_buffer_rsrc_t rD = pb_rsrc(a.GXD), rE = pb_rsrc(a.EX), rDG = pb_rsrc(a.DGD);
+    const __amdgpu_buffer_rsrc_t rD = t2v_rsrc(a.GXD), rE = t2v_rsrc(a.EX), rDG = t2v_rsrc(a.DGD);
     // columns: [0, 8) recurrent (W_hh_dec[k][U]), [8, 16) h_att input (W_ih_dec[k][U]), [16, 20) ctx input (W_ih_dec[k][1024 + C])
-    pb_f32x2 w[20][PB_KJ / 2];
+    f32x2 w[20][PB_KJ / 2];
     {
         const int tid = threadIdx.x;
 #pragma unroll
@@ -1137,8 +1055,8 @@ __device__ __forceinline__ void pba_decoder_role(const PBAArgs& a, float* lds, c
                 const int i = tid - 64, col = i >> 3, b = i & 7;      // col 0..7: unit, 8..11: ctx column
                 if (b < B) {
                     const float val = pb_sum16(part + (4 + (col >> 1)) * 512, (col & 1) * 8 + b);
-                    if (col < 8) { if (col < nu) pb_st4(rE, (unsigned)(((t * B + b) * T2V_KATT) + u0 + col) * 4u, val); }
-                    else if (col - 8 < nc) pb_st4(rE, (unsigned)(((t * B + b) * T2V_KATT) + T2V_H + c0 + col - 8) * 4u, val);
+                    if (col < 8) { if (col < nu) t2v_st(rE, (unsigned)(((t * B + b) * T2V_KATT) + u0 + col) * 4u, val); }
+                    else if (col - 8 < nc) t2v_st(rE, (unsigned)(((t * B + b) * T2V_KATT) + T2V_H + c0 + col - 8) * 4u, val);
                 }
             }
         }
@@ -1189,7 +1107,7 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
     const int tid = threadIdx.x;
     const int B = a.B, T = a.T, S = a.S_sl;
     f32x4* X0 = (f32x4*)lds;
-    pb_f32x2* X1 = (pb_f32x2*)(lds + 4 * T2V_G);
+    f32x2* X1 = (f32x2*)(lds + 4 * T2V_G);
     float* part = lds + (NB > 4 ? 6 : 4) * T2V_G;          // [6 groups][32 partials][32]
     float* ysum = part + 6 * 1024;                         // [21 cols -> 24][8]
     float* dhA = ysum + 192;                               // [14 units -> 16][8]  E_h(t) + ya_h(t+1)
@@ -1202,15 +1120,11 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
     float* dump = eps + 256 + 64;                          // [8 waves][64] landing zone of the prefetch DMAs (never read)
     const int u0 = (ja * T2V_H) / NA, nu = ((ja + 1) * T2V_H) / NA - u0;      // <= 14 units
     const int c0 = (ja * T2V_E) / NA, nc = ((ja + 1) * T2V_E) / NA - c0;      // <= 7 context columns
-    const __amdgpu_buffer_rsrc_t rA = pb_rsrc(a.GXA), rC = pb_rsrc(a.CX), rE = pb_rsrc(a.EX);
-#if PBA_DQ_DIRECT
-    const __amdgpu_buffer_rsrc_t rQ = pb_rsrc(a.DQX);
-#else
-    const __amdgpu_buffer_rsrc_t rQT = pb_rsrc(a.DQT);
-#endif
-    const __amdgpu_buffer_rsrc_t rDC = pb_rsrc(a.DCTX), rDG = pb_rsrc(a.DGA);
+    const __amdgpu_buffer_rsrc_t rA = t2v_rsrc(a.GXA), rC = t2v_rsrc(a.CX), rE = t2v_rsrc(a.EX);
+    const __amdgpu_buffer_rsrc_t rQT = t2v_rsrc(a.DQT);
+    const __amdgpu_buffer_rsrc_t rDC = t2v_rsrc(a.DCTX), rDG = t2v_rsrc(a.DGA);
     // columns: [0, NUA) W_hh_att[k][U], [NUA, NUA + NCA) W_ih_att[k][256 + C]
-    pb_f32x2 w[NCT][PB_KJ / 2];
+    f32x2 w[NCT][PB_KJ / 2];
 #pragma unroll
     for (int jj = 0; jj < PB_KJ; ++jj) {
         const size_t k = (size_t)(tid + PB_THREADS * jj);
@@ -1300,7 +1214,7 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
             const bool on = c < nc && b < B;
             if (on) {
                 float e = eps[tid];
-                if (__float_as_uint(e) == PB_SENT) e = pba_wait_word(rE, e_off, a.err, flag);
+                if (__float_as_uint(e) == T2V_SENT) e = pba_wait_word(rE, e_off, a.err, flag);
                 val = (e + eps[192 + tid]) + (have ? pb_sum16(part + (tid >> 4) * 512, tid & 15) : 0.f);        // column c: round c / 2
             }
             // lane b collects the columns of item b (lanes b + 8 c) and publishes them as one 16-byte store + the rest
@@ -1312,8 +1226,8 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
                 f32x4 hi = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int c2 = 4; c2 < NCA; ++c2) hi[c2 - 4] = g[c2];          // (columns past nc carry 0: val = 0 there)
-                pb_st16(rC, o, f32x4{g[0], g[1], g[2], g[3]});
-                pb_st16(rC, o + 16u, hi);
+                t2v_st(rC, o, f32x4{g[0], g[1], g[2], g[3]});
+                t2v_st(rC, o + 16u, hi);
             }
             // (the saved copy for the d_memory GEMM goes out AFTER the hand-off, addressed off a scalar base: nothing the
             // attention workgroups wait for may sit behind a wait on this wave's memory counter)
@@ -1330,7 +1244,7 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
             const int i = tid - 64, u = i >> 3, b = i & 7;
             if (u < nu && b < B) {
                 float e = eps[tid];
-                if (__float_as_uint(e) == PB_SENT) e = pba_wait_word(rE, e_off, a.err, flag);
+                if (__float_as_uint(e) == T2V_SENT) e = pba_wait_word(rE, e_off, a.err, flag);
                 dhA[i] = e + (have ? pb_sum16(part + 512 * NCR + (i >> 4) * 512, i & 15) : 0.f);                 // unit u: round u / 2
             }
         }
@@ -1376,38 +1290,6 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
             PBA_STAMP(ja == 0, 13);
         }
         // ---- P4: dq(t) of every item (sum of the position slices' partial rows)
-#if PBA_DQ_DIRECT
-        // (measurement variant: the attention_rnn workgroups sum the S partial rows of every item themselves — one hop less than
-        // through slice 0, but B*S*512 bytes per workgroup and step instead of B*512)
-        if (tid >= 320 && tid < 320 + B * 32) {
-            const int i = tid - 320, b = i >> 5, q = i & 31;
-            const unsigned off = (unsigned)(((t * B + b) * S) * T2V_A + 4 * q) * 4u;
-            for (int n = 0; n < napQ; n += 8) __builtin_amdgcn_s_sleep(8);
-            f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-            int rounds = 0;
-            for (;;) {
-                constexpr int SMAX = PB_MAXT / 16;
-                f32x4 x[SMAX];
-#pragma unroll
-                for (int k = 0; k < SMAX; ++k)
-                    if (k < S) x[k] = pb_ld16(rQ, off + (unsigned)(k * T2V_A) * 4u);
-                bool ok = true;
-                sum = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int k = 0; k < SMAX; ++k)
-                    if (k < S) { ok = ok && pb_ok(x[k][0]) && pb_ok(x[k][1]) && pb_ok(x[k][2]) && pb_ok(x[k][3]); sum += x[k]; }
-                if (__all(ok)) break;
-                __builtin_amdgcn_s_sleep(1);
-                if (++rounds > PB_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    flag[0] = 0;
-                    break;
-                }
-            }
-            napQ = t2v_adapt_nap(napQ, rounds);
-            *(f32x4*)(dqs + b * T2V_A + 4 * q) = sum;
-        }
-#else
         if (tid >= 320 && tid < 320 + B * 32) {
             const int i = tid - 320, b = i >> 5, q = i & 31;
             const unsigned off = (unsigned)((t * B + b) * T2V_A + 4 * q) * 4u;
@@ -1415,20 +1297,15 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
             f32x4 sum = {0.f, 0.f, 0.f, 0.f};
             int rounds = 0;
             for (;;) {
-                sum = pb_ld16(rQT, off);
-                const bool ok = pb_ok(sum[0]) && pb_ok(sum[1]) && pb_ok(sum[2]) && pb_ok(sum[3]);
+                sum = t2v_ld_f32x4(rQT, off);
+                const bool ok = t2v_ok(sum[0]) && t2v_ok(sum[1]) && t2v_ok(sum[2]) && t2v_ok(sum[3]);
                 if (__all(ok)) break;
                 __builtin_amdgcn_s_sleep(1);
-                if (++rounds > PB_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    flag[0] = 0;
-                    break;
-                }
+                if (t2v_give_up(rounds, PB_SPIN, a.err, flag)) break;
             }
             napQ = t2v_adapt_nap(napQ, rounds);
             *(f32x4*)(dqs + b * T2V_A + 4 * q) = sum;
         }
-#endif
         __syncthreads();
         if (flag[0] != 1) return;
         PBA_STAMP(ja == 0, 4);
@@ -1491,7 +1368,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     // (-DPBA_ONLY=1..4 builds ONE role into the kernel: `hipcc -Rpass-analysis=kernel-resource-usage` then reports that role's
     // own register pressure — the combined kernel always shows the maximum over the roles; tools/dbg/role_regs.sh)
 #if defined(PBA_ONLY) && PBA_ONLY == 1
-    if (PBA_WHOLE_ITEM) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB); else pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
+    pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
 #elif defined(PBA_ONLY) && PBA_ONLY == 2
     pba_attention_rnn_role<NB, 12, 6>(a, lds, wg - NT, NA);
 #elif defined(PBA_ONLY) && PBA_ONLY == 3
@@ -1500,7 +1377,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     pba_decoder_role<NB>(a, lds, wg - NT - NA, ND);
 #else
     if (wg < NT) {
-        if (LONG || (PBA_WHOLE_ITEM && a.T_in <= 96)) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB);
+        if (LONG) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB);
         else if (a.T_in <= 128) pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
         else pba_attention_role<32, 4>(a, lds, wg / S, wg % S, NB);
     } else if (wg < NT + NA) {
@@ -1524,7 +1401,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd_ta(PBAArgs a) {
     const int wg = blockIdx.x;
     const int S = a.S_sl, NT = a.B * S, NL = T2V_NWG - NT, NA = pba_na(NL);
     if (wg < NT) {
-        if (LONG || (PBA_WHOLE_ITEM && a.T_in <= 96)) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB);
+        if (LONG) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB);
         else if (a.T_in <= 128) pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
         else pba_attention_role<32, 4>(a, lds, wg / S, wg % S, NB);
     } else {
@@ -1540,11 +1417,8 @@ __global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd_free(PBAArgs a) {
     pba_decoder_role<NB>(a, lds, blockIdx.x, ND);
 }
 
-// slice geometry of the one-launch reverse pass: ONE workgroup per item up to 96 symbols, else the launch-per-step geometry
-// (PBA_WHOLE_ITEM: measured at B = 6, T_in = 84 — 11.0 us per reverse step against 10.4 with six 16-position slices per item:
-// the hand-off through slice 0 disappears (-1.4 us), but ONE workgroup needs 3.3 us from "context gradient seen" to "dq
-// published" (1.3 with slices) and 11 us for its whole loop, so it becomes the chain.  Parity-green, kept for the record.)
-static inline int pba_js(int T_in) { return ((PBA_WHOLE_ITEM && T_in <= 96) || T_in > PB_MAXT) ? 96 : t2v_attn_bwd_js(T_in); }
+// slice geometry of the one-launch reverse pass: the launch-per-step geometry up to PB_MAXT symbols, 96-position slices beyond
+static inline int pba_js(int T_in) { return T_in > PB_MAXT ? 96 : t2v_attn_bwd_js(T_in); }
 static inline int pba_slices(int T_in) { const int js = pba_js(T_in); return (T_in + js - 1) / js; }
 extern "C" int t2v_decoder_bwd_persist_slices(int T_in) { return T_in < 1 ? 0 : pba_slices(T_in); }
 
@@ -1612,26 +1486,18 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
     const size_t n_gp = (size_t)T_out * B * S * 2 * gpw;
     const size_t n_ex = (size_t)T_out * B * T2V_KATT, n_dqt = (size_t)T_out * 8 * T2V_A;
     if (((uintptr_t)scratch & 15) || ((uintptr_t)DQP & 15) || n_gx * 4 >= 0x7fffffffull || n_dq * 4 >= 0x7fffffffull) return T2V_ERR_ARG;
-    if (pba_lds_bytes(B, T_in) > PB_LDS_MAX) return T2V_ERR_ARG;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_achain_bwd<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd<6, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd_ta<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd_ta<6, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd_ta<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_achain_bwd_ta<6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_dchain_bwd_free<4>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_dchain_bwd_free<6>, hipFuncAttributeMaxDynamicSharedMemorySize, PB_LDS_MAX) != hipSuccess)
-            return t2v_check_launch();
-        attr_set = true;
-    }
+    if (pba_lds_bytes(B, T_in) > T2V_LDS_MAX) return T2V_ERR_ARG;
+    static bool raised = false;
+    if (!t2v_persist_raise_lds({(const void*)k_achain_bwd<4, false>, (const void*)k_achain_bwd<6, false>, (const void*)k_achain_bwd_ta<4, false>,
+                                (const void*)k_achain_bwd_ta<6, false>, (const void*)k_achain_bwd<4, true>, (const void*)k_achain_bwd<6, true>,
+                                (const void*)k_achain_bwd_ta<4, true>, (const void*)k_achain_bwd_ta<6, true>, (const void*)k_dchain_bwd_free<4>,
+                                (const void*)k_dchain_bwd_free<6>},
+                               raised))
+        return t2v_check_launch();
     if (do_prepare) {
         (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
-        k_pb_fill<<<1024, 256, 0, stream>>>((uint4*)scratch, (2 * n_gx + n_cx + n_gp + n_ex + n_dqt) / 4);
-        k_pb_fill<<<256, 256, 0, stream>>>((uint4*)DQP, n_dq / 4);
+        t2v_fill_sentinel(scratch, (2 * n_gx + n_cx + n_gp + n_ex + n_dqt) / 4, 1024, stream);
+        t2v_fill_sentinel(DQP, n_dq / 4, 256, stream);
     }
     PBAArgs a;
     if (do_run) {

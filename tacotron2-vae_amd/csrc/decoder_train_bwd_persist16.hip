@@ -22,10 +22,11 @@
 // ahead; the attention chain per step is  C_a publishes dga(t+1) -> G_a -> partial ya -> T: d ctx(t) -> attention backward
 // -> dq(t) -> C_a: W_q^T dq + cell -> dga(t).
 // Hand-offs as everywhere in this library: every exchanged value is produced exactly once per pass, the exchange arrays are
-// pre-filled with 0xFFFFFFFF and a word that is no longer the sentinel IS the data (sc1 write-through stores, sc1 loads).
+// pre-filled with T2V_SENT (t2v_xchg.h) and a word that is no longer the sentinel IS the data (sc1 write-through stores, sc1 loads).
 #include <stdlib.h>
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_xchg.h"
 
 #define Q16_THREADS 512
 #define Q16_MAXB 16
@@ -33,7 +34,6 @@
 #define Q16_MAXT_LONG 560               // 96-position slices on eight waves from 193 symbols on (six per item: 16 x 6 = 96 workgroups);
                                         // the range of the forward kernel, k_dec_train_persist16<true>
 #define Q16_SPIN 400000
-#define Q16_SENT 0xFFFFFFFFu
 #define Q16_NGA 48                      // (1536 / 128) column groups x 4 row quarters
 #define Q16_NGD 80                      // (2560 / 128) x 4
 #define Q16_NCA 16                      // 1024 / 64 units
@@ -69,53 +69,19 @@ struct Q16Args {
 #define Q16_RT(SLOT) do { if (a.prof && (t == a.T / 2 || t == a.T / 2 + 1) && threadIdx.x == 0) \
         a.prof[64 + blockIdx.x * 8 + (SLOT) + (t == a.T / 2 ? 0 : 4)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 
-typedef unsigned q16_u32x4 __attribute__((ext_vector_type(4)));
-#define Q16_SC1 16
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t q16_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ q16_u32x4 q16_ld16u(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, Q16_SC1);
-}
-__device__ __forceinline__ f32x4 q16_ld16(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, Q16_SC1));
-}
-__device__ __forceinline__ unsigned q16_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, Q16_SC1);
-}
-__device__ __forceinline__ void q16_st16(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(q16_u32x4, v), r, (int)off, 0, Q16_SC1);
-}
-__device__ __forceinline__ void q16_st16u(__amdgpu_buffer_rsrc_t r, unsigned off, q16_u32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, Q16_SC1);
-}
-__device__ __forceinline__ void q16_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)off, 0, Q16_SC1);
-}
-__device__ __forceinline__ bool q16_okf(float v) { return __float_as_uint(v) != Q16_SENT; }
-__device__ __forceinline__ bool q16_ok4(f32x4 v) { return q16_okf(v[0]) && q16_okf(v[1]) && q16_okf(v[2]) && q16_okf(v[3]); }
-__device__ __forceinline__ bool q16_ok4u(q16_u32x4 v) { return v[0] != Q16_SENT && v[1] != Q16_SENT && v[2] != Q16_SENT && v[3] != Q16_SENT; }
-__device__ __forceinline__ bool q16_give_up(int& rounds, unsigned* err, int* flag) {
-    if (++rounds > Q16_SPIN || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = 0;
-        return true;
-    }
-    return false;
-}
 // NQ sixteen-byte words (stride `stride` bytes) polled until none carries the sentinel; per-thread loop (callers sync after it)
 template <int NQ>
 __device__ __forceinline__ void q16_poll_words(f32x4 (&x)[NQ], __amdgpu_buffer_rsrc_t r, unsigned off, unsigned stride, unsigned* err, int* flag) {
     int rounds = 0;
     for (;;) {
 #pragma unroll
-        for (int i = 0; i < NQ; ++i) x[i] = q16_ld16(r, off + stride * (unsigned)i);
+        for (int i = 0; i < NQ; ++i) x[i] = t2v_ld_f32x4(r, off + stride * (unsigned)i);
         bool ok = true;
 #pragma unroll
-        for (int i = 0; i < NQ; ++i) ok = ok && q16_ok4(x[i]);
+        for (int i = 0; i < NQ; ++i) ok = ok && t2v_ok4(x[i]);
         if (ok) break;
         __builtin_amdgcn_s_sleep(2);
-        if (q16_give_up(rounds, err, flag)) break;
+        if (t2v_give_up(rounds, Q16_SPIN, err, flag)) break;
     }
 }
 
@@ -131,15 +97,15 @@ __device__ __forceinline__ void q16_gemv_role(const Q16Args& a, float* lds, cons
     const bool live = n < a.B;
     f32x4* red = (f32x4*)lds;                             // [parity 2][wave 8][tile 8][lane 64]
     int* flag = (int*)(lds + 2 * 8 * 8 * 64 * 4);
-    const __amdgpu_buffer_rsrc_t rX = q16_rsrc(DEC ? a.GXD : a.GXA), rP = q16_rsrc(DEC ? a.PD : a.PA);
+    const __amdgpu_buffer_rsrc_t rX = t2v_rsrc(DEC ? a.GXD : a.GXA), rP = t2v_rsrc(DEC ? a.PD : a.PA);
     // ---- weights: tile m, A row = output column col = 128 cg + 16 m + (lane & 15); this wave's k-blocks kb = 32 q + 4 wave + i,
     // 8 consecutive k = 32 kb + 8 g + e -> unit = k >> 2, gate = k & 3 -> gate row gate * 1024 + unit
-    q16_u32x4 wreg[8][4];
+    u32x4 wreg[8][4];
     {
         // (32-bit buffer offsets, one tile's 32 values in flight at a time: with 64-bit addresses the compiler kept the 32 row offsets
         // of BOTH matrices live across the unrolled tiles, ran out of registers and spilled every loaded value on arrival — 256
         // serialised round trips per launch and 280 B/lane of scratch in the kernel's resource record)
-        const __amdgpu_buffer_rsrc_t rHH = q16_rsrc(DEC ? a.w_hh_dec : a.w_hh_att), rIH = q16_rsrc(DEC ? a.w_ih_dec : a.w_ih_att);
+        const __amdgpu_buffer_rsrc_t rHH = t2v_rsrc(DEC ? a.w_hh_dec : a.w_hh_att), rIH = t2v_rsrc(DEC ? a.w_ih_dec : a.w_ih_att);
         unsigned chain = 0;     // always 0, but data-dependent on the previous tile's last packed word: its address arithmetic cannot be hoisted
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
@@ -164,7 +130,7 @@ __device__ __forceinline__ void q16_gemv_role(const Q16Args& a, float* lds, cons
 #pragma unroll
                 for (int ii = 0; ii < 2; ++ii) {
                     const uint4 u = t2v_pack_bf16x8(make_float4(wv[ii][0], wv[ii][1], wv[ii][2], wv[ii][3]), make_float4(wv[ii][4], wv[ii][5], wv[ii][6], wv[ii][7]));
-                    wreg[m][2 * h + ii] = q16_u32x4{u.x, u.y, u.z, u.w};
+                    wreg[m][2 * h + ii] = u32x4{u.x, u.y, u.z, u.w};
                 }
                 asm volatile("v_and_b32 %0, 0, %1" : "=v"(chain) : "v"(wreg[m][2 * h + 1].x));
             }
@@ -178,25 +144,25 @@ __device__ __forceinline__ void q16_gemv_role(const Q16Args& a, float* lds, cons
     for (int t = a.T - 1; t >= t_last; --t) {
         Q16_RT(0);
         // ---- this wave's 4 k-blocks of row t, straight into the B operands
-        q16_u32x4 x[4];
+        u32x4 x[4];
         {
             for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
             int rounds = 0;
             const unsigned off = (unsigned)t * Q16_ROW + off_w;
             for (;;) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) x[i] = q16_ld16u(rX, off + 1024u * (unsigned)i);
+                for (int i = 0; i < 4; ++i) x[i] = t2v_ld_b128(rX, off + 1024u * (unsigned)i);
                 bool ok = true;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) ok = ok && q16_ok4u(x[i]);
+                for (int i = 0; i < 4; ++i) ok = ok && t2v_ok4(x[i]);
                 if (__all(ok || !live)) break;
                 __builtin_amdgcn_s_sleep(2);
-                if (q16_give_up(rounds, a.err, flag)) break;
+                if (t2v_give_up(rounds, Q16_SPIN, a.err, flag)) break;
             }
             nap = t2v_adapt_nap(nap, rounds);
             if (!live) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) x[i] = q16_u32x4{0u, 0u, 0u, 0u};
+                for (int i = 0; i < 4; ++i) x[i] = u32x4{0u, 0u, 0u, 0u};
             }
         }
         Q16_RT(1);
@@ -215,7 +181,7 @@ __device__ __forceinline__ void q16_gemv_role(const Q16Args& a, float* lds, cons
         {
             const f32x4* rp = redp + wave * 64 + lane;          // K-slice stride: 8 * 64
             const f32x4 s4 = ((rp[0] + rp[512]) + (rp[1024] + rp[1536])) + ((rp[2048] + rp[2560]) + (rp[3072] + rp[3584]));
-            if (live) q16_st16(rP, (unsigned)(((t * 4 + q) * 16 + n) * NCOL + 128 * cg + 16 * wave + 4 * g) * 4u, s4);
+            if (live) t2v_st(rP, (unsigned)(((t * 4 + q) * 16 + n) * NCOL + 128 * cg + 16 * wave + 4 * g) * 4u, s4);
         }
         Q16_RT(2);
     }
@@ -253,8 +219,8 @@ __device__ __forceinline__ void q16_cell_role(const Q16Args& a, float* lds, cons
     const int U0 = 64 * j;
     const int cb = tid >> 4, uq = tid & 15, U = U0 + 4 * uq;
     const bool cell_thr = tid < 256 && cb < B;
-    const __amdgpu_buffer_rsrc_t rPA = q16_rsrc(a.PA), rPD = q16_rsrc(a.PD), rQT = q16_rsrc(a.DQT);
-    const __amdgpu_buffer_rsrc_t rX = q16_rsrc(ATT ? a.GXA : a.GXD);
+    const __amdgpu_buffer_rsrc_t rPA = t2v_rsrc(a.PA), rPD = t2v_rsrc(a.PD), rQT = t2v_rsrc(a.DQT);
+    const __amdgpu_buffer_rsrc_t rX = t2v_rsrc(ATT ? a.GXA : a.GXD);
     const float* Gs = ATT ? a.GA : a.GD;
     const float* Cs = ATT ? a.CA : a.CD;
     float* DG = ATT ? a.DGA : a.DGD;
@@ -360,8 +326,8 @@ __device__ __forceinline__ void q16_cell_role(const Q16Args& a, float* lds, cons
                 const unsigned o = (unsigned)t * Q16_ROW + (kg * 16u + (unsigned)cb) * 16u;
                 const uint4 c0 = t2v_pack_bf16x8(make_float4(dg[0][0], dg[0][1], dg[0][2], dg[0][3]), make_float4(dg[1][0], dg[1][1], dg[1][2], dg[1][3]));
                 const uint4 c1 = t2v_pack_bf16x8(make_float4(dg[2][0], dg[2][1], dg[2][2], dg[2][3]), make_float4(dg[3][0], dg[3][1], dg[3][2], dg[3][3]));
-                q16_st16u(rX, o, q16_u32x4{c0.x, c0.y, c0.z, c0.w});
-                q16_st16u(rX, o + 256u, q16_u32x4{c1.x, c1.y, c1.z, c1.w});
+                t2v_st(rX, o, u32x4{c0.x, c0.y, c0.z, c0.w});
+                t2v_st(rX, o + 256u, u32x4{c1.x, c1.y, c1.z, c1.w});
             }
             float* o = DG + ((size_t)t * B + cb) * T2V_G + U;
 #pragma unroll
@@ -406,7 +372,7 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
     int* flag = (int*)(rv + NRG * T2V_A);
     constexpr bool AREG_LDS = NWV == 8;
     float* wcs = (float*)(flag + 40);         // [64 rows (c,k)][132] when AREG_LDS
-    const __amdgpu_buffer_rsrc_t rPA = q16_rsrc(a.PA), rPD = q16_rsrc(a.PD), rQ = q16_rsrc(a.DQX), rP = q16_rsrc(a.GPX), rQT = q16_rsrc(a.DQT);
+    const __amdgpu_buffer_rsrc_t rPA = t2v_rsrc(a.PA), rPD = t2v_rsrc(a.PD), rQ = t2v_rsrc(a.DQX), rP = t2v_rsrc(a.GPX), rQT = t2v_rsrc(a.DQT);
     // ---- operands resident for the whole pass
     float4 m0[JS / NWV], m1[JS / NWV];
     float areg[AREG_LDS ? 1 : 32];
@@ -481,11 +447,11 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
                     unsigned x0, x1;
                     int spins = 0;
                     for (;;) {          // published at the end of the previous reverse step: almost always there
-                        x0 = q16_ld4(rP, off);
-                        x1 = q16_ld4(rP, off + 4u * GPW);
-                        if (x0 != Q16_SENT && x1 != Q16_SENT) break;
+                        x0 = t2v_ld_b32(rP, off);
+                        x1 = t2v_ld_b32(rP, off + 4u * GPW);
+                        if (t2v_ok(x0) && t2v_ok(x1)) break;
                         __builtin_amdgcn_s_sleep(1);
-                        if (q16_give_up(spins, a.err, flag)) break;
+                        if (t2v_give_up(spins, Q16_SPIN, a.err, flag)) break;
                     }
                     gp += __uint_as_float(x0);
                     gc += __uint_as_float(x1);
@@ -509,13 +475,13 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
                 int rounds = 0;
                 for (;;) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) y[i] = q16_ld16(rPA, off + 16u * Q16_NCOLA * 4u * (unsigned)i);
+                    for (int i = 0; i < 4; ++i) y[i] = t2v_ld_f32x4(rPA, off + 16u * Q16_NCOLA * 4u * (unsigned)i);
                     bool ok = true;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) ok = ok && q16_ok4(y[i]);
+                    for (int i = 0; i < 4; ++i) ok = ok && t2v_ok4(y[i]);
                     if (__all(ok)) break;
                     __builtin_amdgcn_s_sleep(2);
-                    if (q16_give_up(rounds, a.err, flag)) break;
+                    if (t2v_give_up(rounds, Q16_SPIN, a.err, flag)) break;
                 }
                 nap = t2v_adapt_nap(nap, rounds);
                 dc = dc + ((y[0] + y[1]) + (y[2] + y[3]));
@@ -588,7 +554,7 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
                 q += ((p[0] + p[T2V_A]) + (p[2 * T2V_A] + p[3 * T2V_A])) + ((p[4 * T2V_A] + p[5 * T2V_A]) + (p[6 * T2V_A] + p[7 * T2V_A]));
                 vv += ((p2[0] + p2[T2V_A]) + (p2[2 * T2V_A] + p2[3 * T2V_A])) + ((p2[4 * T2V_A] + p2[5 * T2V_A]) + (p2[6 * T2V_A] + p2[7 * T2V_A]));
             }
-            q16_st4(rQ, (unsigned)(((t * B + b) * S + s) * T2V_A + tid) * 4u, q);       // partial row (the d W_q GEMM reads them later)
+            t2v_st(rQ, (unsigned)(((t * B + b) * S + s) * T2V_A + tid) * 4u, q);       // partial row (the d W_q GEMM reads them later)
             dvacc += vv;
             if (s == 0) {
                 // slice 0 of an item sums the S partial rows in slice order and publishes ONE row per item (all partial rows are
@@ -600,17 +566,17 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
                 for (;;) {
                     bool ok = true;
 #pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) x[s2] = q16_ld4(rQ, off0 + (unsigned)(min(s2, S - 1) * T2V_A) * 4u);
+                    for (int s2 = 1; s2 < SMAX; ++s2) x[s2] = t2v_ld_b32(rQ, off0 + (unsigned)(min(s2, S - 1) * T2V_A) * 4u);
 #pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) ok = ok && (s2 >= S || x[s2] != Q16_SENT);
+                    for (int s2 = 1; s2 < SMAX; ++s2) ok = ok && (s2 >= S || t2v_ok(x[s2]));
                     if (__all(ok)) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (q16_give_up(spins, a.err, flag)) break;
+                    if (t2v_give_up(spins, Q16_SPIN, a.err, flag)) break;
                 }
                 float tot = q;
 #pragma unroll
                 for (int s2 = 1; s2 < SMAX; ++s2) tot += s2 < S ? __uint_as_float(x[s2]) : 0.f;
-                q16_st4(rQT, (unsigned)((t * 16 + b) * T2V_A + tid) * 4u, tot);          // the attention_rnn cell workgroups wait for this
+                t2v_st(rQT, (unsigned)((t * 16 + b) * T2V_A + tid) * 4u, tot);          // the attention_rnn cell workgroups wait for this
             }
         }
         Q16_RT(2);
@@ -655,7 +621,7 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
 #pragma unroll
                 for (int k = 0; k + 3 < T2V_KS; k += 4) { acc0 += tt[k]; acc1 += tt[k + 1]; acc2 += tt[k + 2]; acc3 += tt[k + 3]; }
                 acc0 += tt[28]; acc1 += tt[29]; acc2 += tt[30];
-                q16_st4(rP, (unsigned)(((t * B + b) * S + s) * (2 * GPW) + c * GPW + jj) * 4u, (acc0 + acc1) + (acc2 + acc3));
+                t2v_st(rP, (unsigned)(((t * B + b) * S + s) * (2 * GPW) + c * GPW + jj) * 4u, (acc0 + acc1) + (acc2 + acc3));
             }
         }
         __syncthreads();
@@ -695,19 +661,12 @@ __global__ __launch_bounds__(Q16_THREADS) void k_bwd_persist16(Q16Args a) {
 #endif
 }
 
-// sentinel fill (16 bytes per thread and iteration)
-__global__ __launch_bounds__(256) void k_q16_fill(uint4* p, size_t n16) {
-    const uint4 s = {Q16_SENT, Q16_SENT, Q16_SENT, Q16_SENT};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = s;
-}
-
 // slices of the attention role: 16 positions up to 96 symbols, 32 up to 192, else 96 (B * S attention workgroups must fit into
 // 96: with at most six slices per item B = 16 always does)
 static inline int q16_js(int T_in) { return T_in <= 96 ? 16 : T_in <= Q16_T32 ? 32 : 96; }
 static inline int q16_slices(int T_in) { const int js = q16_js(T_in); return (T_in + js - 1) / js; }
 extern "C" int t2v_decoder_bwd_persist16_slices(int T_in) { return T_in < 1 ? 0 : q16_slices(T_in); }
 
-#define Q16_LDS_MAX (160 * 1024)
 static size_t q16_lds_bytes(int T_in) {
     const size_t grole = 2 * 8 * 8 * 64 * 4 + 4;
     const size_t crole = 128 * 16 + 2 * 64 * 16 + 4;
@@ -718,36 +677,12 @@ static size_t q16_lds_bytes(int T_in) {
     m = m > trole ? m : trole;
     return sizeof(float) * m;
 }
-static int q16_device_ok(size_t lds, bool lng) {
-    static int cus = -1;
-    if (cus < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        cus = prop.multiProcessorCount;
-    }
-    if (cus < T2V_NWG) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_bwd_persist16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, Q16_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_bwd_persist16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, Q16_LDS_MAX) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        attr_set = true;
-    }
-    int nblk = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, lng ? (const void*)k_bwd_persist16<true> : (const void*)k_bwd_persist16<false>,
-                                                     Q16_THREADS, lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return nblk >= 1;
-}
 extern "C" int t2v_decoder_bwd_persist16_supported(int B, int T_in) {
     if (!(B >= 1 && B <= Q16_MAXB && T_in >= 1 && T_in <= Q16_MAXT_LONG)) return 0;
-    if (B * q16_slices(T_in) > Q16_MAXTWG || q16_lds_bytes(T_in) > Q16_LDS_MAX) return 0;
-    return q16_device_ok(q16_lds_bytes(T_in), T_in > Q16_T32);
+    if (B * q16_slices(T_in) > Q16_MAXTWG || q16_lds_bytes(T_in) > T2V_LDS_MAX) return 0;
+    static bool raised = false;
+    return t2v_persist_resident(T_in > Q16_T32 ? (const void*)k_bwd_persist16<true> : (const void*)k_bwd_persist16<false>, Q16_THREADS,
+                                q16_lds_bytes(T_in), {(const void*)k_bwd_persist16<false>, (const void*)k_bwd_persist16<true>}, raised);
 }
 // layout of `scratch` (floats): GXA | GXD | PA | PD | GPX | DQT
 static void q16_layout(int B, int T_in, int T_out, size_t (&n)[6]) {
@@ -798,8 +733,8 @@ extern "C" int t2v_decoder_bwd_persistent16_prepare(float* DQP, float* scratch, 
     q16_layout(B, T_in, T_out, n);
     const size_t n_dq = (size_t)T_out * B * q16_slices(T_in) * 128;
     (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
-    k_q16_fill<<<2048, 256, 0, stream>>>((uint4*)scratch, (n[0] + n[1] + n[2] + n[3] + n[4] + n[5]) / 4);
-    k_q16_fill<<<256, 256, 0, stream>>>((uint4*)DQP, n_dq / 4);
+    t2v_fill_sentinel(scratch, (n[0] + n[1] + n[2] + n[3] + n[4] + n[5]) / 4, 2048, stream);
+    t2v_fill_sentinel(DQP, n_dq / 4, 256, stream);
     return t2v_check_launch();
 }
 

@@ -17,14 +17,14 @@
 //
 // Hand-off = the saved activations themselves.  Every recurrent value is produced exactly once per pass, so it needs no
 // tag and no flag: the exchange buffer G (one row per step, laid out [plane][k][4 items] so that a consumer's 16-byte
-// load is an LDS-ready operand) is pre-filled with a NaN sentinel (0xFFFFFFFF, never produced by arithmetic); producers
+// load is an LDS-ready operand) is pre-filled with a NaN sentinel (T2V_SENT, t2v_xchg.h: never produced by arithmetic); producers
 // store with sc1 (write-through), consumers poll their own words with sc1 loads until none is the sentinel.  4 bytes per
 // value on the wire instead of an 8-byte {value, tag} granule, 16-byte loads, no memory ordering needed (MI355X guide
 // G16 form R2 with an implicit tag).  The partial energies of the 8 attention slices of an item travel the same way (EX).
 // The backward pass reads the usual arena (XS, CA, CD, GA, GD, AL, ACUM, S), written here with plain stores.
-#include <stdlib.h>
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_xchg.h"
 
 #define PT_THREADS 512
 #define PT_MAXB 6
@@ -33,7 +33,6 @@
 #define PT_NTI_LONG 5                // 16-position tiles per wave of the long form: 8 waves x 5 x 16 = 640 >= 560
 #define PT_MAXU 5
 #define PT_SPIN 1500000u
-#define PT_SENT 0xFFFFFFFFu
 #define PT_JA (T2V_KATT / 128)       // 12 k per thread, attention_rnn  [h_att | ctx]
 #define PT_JD (T2V_XW / 128)         // 20 k per thread, decoder_rnn    [h_att | ctx | h_dec]
 
@@ -54,35 +53,6 @@ struct PTArgs {
 // wall clock (100 MHz, the same counter on every CU): hop latencies between workgroups
 #define PT_WALL(COND, I) do { if (a.prof && (COND) && tid == 0) a.prof[(I)] = wall_clock64(); } while (0)
 #define PT_STAMP(COND, I) do { if (a.prof && (COND) && tid == 0) a.prof[(I)] = __builtin_readcyclecounter(); } while (0)
-
-// 16-byte / 4-byte accesses at agent scope (sc1: bypass the CU's vector L1, stores are write-through) as raw buffer
-// operations: the compiler tracks their vmcnt itself (an inline-asm load is invisible to its scoreboard — the result
-// registers can be read or copied before the data has landed).  Offsets are BYTES from the buffer base (< 2 GiB).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define PT_SC1 16
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pt_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ f32x4 pt_ld16(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, PT_SC1);
-    return __builtin_bit_cast(f32x4, v);
-}
-__device__ __forceinline__ void pt_st16(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)off, 0, PT_SC1);
-}
-__device__ __forceinline__ void pt_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)off, 0, PT_SC1);
-}
-__device__ __forceinline__ unsigned pt_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, PT_SC1);
-}
-__device__ __forceinline__ bool pt_valid(f32x4 v, int nw) {      // the first nw words are not the sentinel
-    bool ok = __float_as_uint(v[0]) != PT_SENT;
-    ok = ok && (nw < 2 || __float_as_uint(v[1]) != PT_SENT);
-    ok = ok && (nw < 3 || __float_as_uint(v[2]) != PT_SENT);
-    ok = ok && (nw < 4 || __float_as_uint(v[3]) != PT_SENT);
-    return ok;
-}
 
 // Gather nk columns [k0, k0 + nk) of all planes of one G row (byte offset row_off) into the LDS state planes.  PER
 // chunks per thread (NP * nk <= PER * 512).  A chunk is valid when the words of the items it carries are all written.
@@ -113,17 +83,13 @@ __device__ __forceinline__ int pt_gather(f32x4* X, __amdgpu_buffer_rsrc_t rG, un
     int rounds = 0;
     for (;;) {
 #pragma unroll
-        for (int u = 0; u < PER; ++u) v[u] = pt_ld16(rG, src[u]);
+        for (int u = 0; u < PER; ++u) v[u] = t2v_ld_f32x4(rG, src[u]);
         bool ok = true;
 #pragma unroll
-        for (int u = 0; u < PER; ++u) ok = ok && pt_valid(v[u], nw[u]);
+        for (int u = 0; u < PER; ++u) ok = ok && t2v_ok_n(v[u], nw[u]);
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(2);
-        if (++rounds > (int)(PT_SPIN / 4) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = 0;
-            break;
-        }
+        if (t2v_give_up(rounds, (int)(PT_SPIN / 4), err, flag)) break;
     }
 #pragma unroll
     for (int u = 0; u < PER; ++u)
@@ -144,13 +110,10 @@ __device__ __forceinline__ int pt_wait_words(__amdgpu_buffer_rsrc_t r, unsigned 
     unsigned spins = 0;
     for (;;) {
         bool ok = true;
-        if (tid < npoll) ok = pt_ld4(r, off) != PT_SENT;
+        if (tid < npoll) ok = t2v_ok(t2v_ld_b32(r, off));
         if (__syncthreads_and(ok)) break;
         ++rounds;
-        if (tid == 0 && (++spins > PT_SPIN / 8 || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = 0;
-        }
+        if (tid == 0) t2v_give_up(spins, PT_SPIN / 8, err, flag);
         __syncthreads();
         if (*flag != 1) break;
     }
@@ -164,7 +127,6 @@ __device__ __forceinline__ int pt_wait_words(__amdgpu_buffer_rsrc_t r, unsigned 
 // (b) volatile asm, because left to itself the compiler sinks the (pure) FMAs of the fully unrolled k loop to the end of
 // the function, first loads all operand vectors (80 registers) and then walks one accumulator at a time as a dependent
 // chain — with 160 weight registers live that spills, and the chains stall.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int NB>
 struct PTAcc {
     static constexpr int NPAIR = NB > 4 ? 3 : 2;
@@ -279,7 +241,6 @@ __device__ __forceinline__ void pt_fma_range(const f32x2 (&w2)[PT_MAXU][NJ2], co
 // copy of that half (row_mirror, row_half_mirror, quad xor 2, quad xor 1: the partner always differs in the selector
 // bit) — 30 DPP adds + 60 selects instead of 120 dependent DPP adds + 30 masked stores.  Lane c of a row ends with the
 // row sums of values 2c and 2c + 1 and stores them as one float2: red[gate][partial = 2 waves x 4 rows][32].
-#define PT_DPP_F(v, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, true))
 template <int NB>
 __device__ __forceinline__ void pt_reduce_store(const PTAcc<NB>& acc, float* red) {
     const int tid = threadIdx.x, lane = tid & 63, g = tid >> 7;
@@ -298,22 +259,22 @@ __device__ __forceinline__ void pt_reduce_store(const PTAcc<NB>& acc, float* red
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const float keep = b3 ? v[16 + i] : v[i], send = b3 ? v[i] : v[16 + i];
-        w16[i] = keep + PT_DPP_F(send, 0x140);            // row_mirror
+        w16[i] = keep + T2V_DPP_F(send, 0x140);            // row_mirror
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float keep = b2 ? w16[8 + i] : w16[i], send = b2 ? w16[i] : w16[8 + i];
-        w8[i] = keep + PT_DPP_F(send, 0x141);             // row_half_mirror
+        w8[i] = keep + T2V_DPP_F(send, 0x141);             // row_half_mirror
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const float keep = b1 ? w8[4 + i] : w8[i], send = b1 ? w8[i] : w8[4 + i];
-        w4[i] = keep + PT_DPP_F(send, 0x4E);              // quad_perm [2,3,0,1]
+        w4[i] = keep + T2V_DPP_F(send, 0x4E);              // quad_perm [2,3,0,1]
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const float keep = b0 ? w4[2 + i] : w4[i], send = b0 ? w4[i] : w4[2 + i];
-        w2[i] = keep + PT_DPP_F(send, 0xB1);              // quad_perm [1,0,3,2]
+        w2[i] = keep + T2V_DPP_F(send, 0xB1);              // quad_perm [1,0,3,2]
     }
     const int part = ((tid >> 6) & 1) * 4 + (lane >> 4);
     *(float2*)(red + (g * 8 + part) * 32 + 2 * (lane & 15)) = make_float2(w2[0], w2[1]);
@@ -332,7 +293,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
     const int B = a.B, Tp = a.T_in, T = a.T_out;
     const int NT = 8 * B, NL = T2V_NWG - NT;
     const unsigned grow_b = (unsigned)NP * T2V_XW * 16u;      // bytes per G row
-    const __amdgpu_buffer_rsrc_t rG = pt_rsrc(a.G), rE = pt_rsrc(a.EX);
+    const __amdgpu_buffer_rsrc_t rG = t2v_rsrc(a.G), rE = t2v_rsrc(a.EX);
     const int Tcap = (Tp + 15) & ~15;
 
     if (wg >= NT) {
@@ -435,7 +396,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                         const float x = __shfl(hd, min(pu, PT_MAXU - 1) * NB + min(bb, NB - 1), 64);
                         v4[i] = bb < B ? x : 0.f;
                     }
-                    if (lane < PT_MAXU * NP && pu < nu) pt_st16(rG, grow + (unsigned)(pp * T2V_XW + u0 + pu) * 16u, v4);
+                    if (lane < PT_MAXU * NP && pu < nu) t2v_st(rG, grow + (unsigned)(pp * T2V_XW + u0 + pu) * 16u, v4);
                     PT_WALL(wg == NT && t == T / 2, 20);
                 }
             }
@@ -480,13 +441,13 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                         const float x = __shfl(hd, min(pu, PT_MAXU - 1) * NB + min(bb, NB - 1), 64);
                         v4[i] = bb < B ? x : 0.f;
                     }
-                    if (t < T && lane < PT_MAXU * NP && pu < nu) pt_st16(rG, grow + (unsigned)(pp * T2V_XW + T2V_KATT + u0 + pu) * 16u, v4);
+                    if (t < T && lane < PT_MAXU * NP && pu < nu) t2v_st(rG, grow + (unsigned)(pp * T2V_XW + T2V_KATT + u0 + pu) * 16u, v4);
                 }
             } else if (wave == 0) {
                 // t = 0: h_dec(-1) = 0 (XS row 1 was cleared by the reset launch)
                 const int pu = lane / NP, pp = lane - pu * NP;
                 if (lane < PT_MAXU * NP && pu < nu)
-                    pt_st16(rG, grow + (unsigned)(pp * T2V_XW + T2V_KATT + u0 + pu) * 16u, f32x4{0.f, 0.f, 0.f, 0.f});
+                    t2v_st(rG, grow + (unsigned)(pp * T2V_XW + T2V_KATT + u0 + pu) * 16u, f32x4{0.f, 0.f, 0.f, 0.f});
             }
             if (t == T) break;
             PT_STAMP(wg == NT && t == T / 2, 2);
@@ -613,15 +574,11 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
             for (int i = 0; i < h_nap; i += 8) __builtin_amdgcn_s_sleep(8);
             int rounds = 0;
             for (;;) {
-                v0 = __uint_as_float(pt_ld4(rG, s0));
-                v1 = __uint_as_float(pt_ld4(rG, s0 + PT_THREADS * 16u));
-                if (__all(__float_as_uint(v0) != PT_SENT && __float_as_uint(v1) != PT_SENT)) break;
+                v0 = __uint_as_float(t2v_ld_b32(rG, s0));
+                v1 = __uint_as_float(t2v_ld_b32(rG, s0 + PT_THREADS * 16u));
+                if (__all(t2v_ok(v0) && t2v_ok(v1))) break;
                 __builtin_amdgcn_s_sleep(1);
-                if (++rounds > (int)(PT_SPIN / 4) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    flag[0] = 0;
-                    break;
-                }
+                if (t2v_give_up(rounds, (int)(PT_SPIN / 4), a.err, flag)) break;
             }
             h_nap = t2v_adapt_nap(h_nap, rounds);
             PT_WALL(wg == 0 && t == T / 2, 21);
@@ -668,7 +625,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                 float esum = vr.x * sv.x + vr.y * sv.y + vr.z * sv.z + vr.w * sv.w;
                 esum += __shfl_xor(esum, 16, 64);
                 esum += __shfl_xor(esum, 32, 64);
-                if (g == 0 && jp < Tp) pt_st4(rE, exw + 4u * (unsigned)jp, esum);
+                if (g == 0 && jp < Tp) t2v_st(rE, exw + 4u * (unsigned)jp, esum);
                 if (a.S && jp < Tp) *(float4*)(a.S + (((size_t)t * B + ab) * Tp + jp) * T2V_A + 16 * as + 4 * g) = sv;
             }
         }
@@ -686,16 +643,12 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                     bool ok = true;
     #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        p[i] = pt_ld4(rE, e0 + (unsigned)(i * Tcap) * 4u);
-                        ok = ok && p[i] != PT_SENT;
+                        p[i] = t2v_ld_b32(rE, e0 + (unsigned)(i * Tcap) * 4u);
+                        ok = ok && t2v_ok(p[i]);
                     }
                     if (ok) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (++spins > PT_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        flag[0] = 0;
-                        break;
-                    }
+                    if (t2v_give_up(spins, PT_SPIN, a.err, flag)) break;
                 }
                 const float ev = ((__uint_as_float(p[0]) + __uint_as_float(p[1])) + (__uint_as_float(p[2]) + __uint_as_float(p[3]))) +
                                  ((__uint_as_float(p[4]) + __uint_as_float(p[5])) + (__uint_as_float(p[6]) + __uint_as_float(p[7])));
@@ -758,17 +711,13 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                         const unsigned eu = e0 + ((u > 0 && tid + PT_THREADS * u < Tp) ? (unsigned)(PT_THREADS * u) * 4u : 0u);
     #pragma unroll
                         for (int i = 0; i < 8; ++i) {
-                            p[u][i] = pt_ld4(rE, eu + (unsigned)(i * Tcap) * 4u);
-                            ok = ok && p[u][i] != PT_SENT;
+                            p[u][i] = t2v_ld_b32(rE, eu + (unsigned)(i * Tcap) * 4u);
+                            ok = ok && t2v_ok(p[u][i]);
                         }
                     }
                     if (ok) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (++spins > PT_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        flag[0] = 0;
-                        break;
-                    }
+                    if (t2v_give_up(spins, PT_SPIN, a.err, flag)) break;
                 }
     #pragma unroll
                 for (int u = 0; u < NPP; ++u) {
@@ -850,7 +799,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
             float acc = 0.f;
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc += cred[u * 64 + tid];
-            pt_st4(rG, grow + (unsigned)(mypl * T2V_XW + T2V_H + 64 * as + tid) * 16u + 4u * (unsigned)myw, acc);
+            t2v_st(rG, grow + (unsigned)(mypl * T2V_XW + T2V_H + 64 * as + tid) * 16u + 4u * (unsigned)myw, acc);
             a.XS[((size_t)(t + 1) * B + ab) * T2V_XW + T2V_H + 64 * as + tid] = acc;       // (after the publish)
         }
         PT_WALL(wg == 0 && t == T / 2, 22);
@@ -858,60 +807,27 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
     }
 }
 
-// sentinel fill of the exchange buffers (16 bytes per thread and iteration)
-__global__ __launch_bounds__(256) void k_pt_fill(uint4* p, size_t n16) {
-    const uint4 s = {PT_SENT, PT_SENT, PT_SENT, PT_SENT};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = s;
-}
-
-// the long form of the attention role: beyond PT_MAXT symbols (T2V_PT_LONG=1: for every length — a measurement switch)
-static bool pt_long(int T_in) {
-    static const int forced = [] { const char* e = getenv("T2V_PT_LONG"); return e && e[0] == '1' ? 1 : 0; }();
-    return T_in > PT_MAXT || forced;
-}
 static size_t pt_lds_bytes(int B, int T_in) {
     const size_t Tcap = (size_t)((T_in + 15) / 16) * 16;
     const size_t np = B > 4 ? 2 : 1;
     const size_t lrole = np * T2V_XW * 4 + 4 * 8 * 32 + 8 * 32 + 4;
-    const size_t resident = pt_long(T_in) ? Tcap * 64 : 16 * 1028 + Tcap * 64 + Tcap * 16;      // LONG: W_q / processed memory in registers
-    const size_t trole = resident + 2 * (Tcap + 32) + Tcap + (pt_long(T_in) ? T2V_CTX_PAD : 0) + T2V_H + 16 + 32 * 16 + 8 * 64 + 64 + 4;
+    const size_t resident = T_in > PT_MAXT ? Tcap * 64 : 16 * 1028 + Tcap * 64 + Tcap * 16;      // LONG: W_q / processed memory in registers
+    const size_t trole = resident + 2 * (Tcap + 32) + Tcap + (T_in > PT_MAXT ? T2V_CTX_PAD : 0) + T2V_H + 16 + 32 * 16 + 8 * 64 + 64 + 4;
     return sizeof(float) * (lrole > trole ? lrole : trole);
 }
-#define PT_LDS_MAX (160 * 1024)
 static size_t pt_g_floats(int B, int T_out) { return (size_t)(T_out + 2) * (B > 4 ? 2 : 1) * T2V_XW * 4; }
 static size_t pt_ex_floats(int B, int T_in, int T_out) { return (size_t)T_out * B * 8 * t2v_tcap(T_in); }
 
 static const void* pt_kernel(int B, int T_in) {
-    if (pt_long(T_in)) return B > 4 ? (const void*)k_dec_train_persist<6, true> : (const void*)k_dec_train_persist<4, true>;
+    if (T_in > PT_MAXT) return B > 4 ? (const void*)k_dec_train_persist<6, true> : (const void*)k_dec_train_persist<4, true>;
     return B > 4 ? (const void*)k_dec_train_persist<6, false> : (const void*)k_dec_train_persist<4, false>;
-}
-static int pt_device_ok(int B, int T_in, size_t lds) {
-    static int cus = -1;
-    if (cus < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        cus = prop.multiProcessorCount;
-    }
-    if (cus < T2V_NWG) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (int b = 4; b <= 6; b += 2)
-            for (int tin = PT_MAXT; tin <= PT_MAXT + 1; ++tin)
-                if (hipFuncSetAttribute(pt_kernel(b, tin), hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS_MAX) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return 0;
-                }
-        attr_set = true;
-    }
-    int nblk = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, pt_kernel(B, T_in), PT_THREADS, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return nblk >= 1;
 }
 
 extern "C" int t2v_decoder_train_persist_supported(int B, int T_in) {
-    if (!(B >= 1 && B <= PT_MAXB && T_in >= 1 && T_in <= PT_MAXT_LONG && pt_lds_bytes(B, T_in) <= PT_LDS_MAX)) return 0;
-    return pt_device_ok(B, T_in, pt_lds_bytes(B, T_in));
+    if (!(B >= 1 && B <= PT_MAXB && T_in >= 1 && T_in <= PT_MAXT_LONG && pt_lds_bytes(B, T_in) <= T2V_LDS_MAX)) return 0;
+    static bool raised = false;
+    return t2v_persist_resident(pt_kernel(B, T_in), PT_THREADS, pt_lds_bytes(B, T_in),
+                                {pt_kernel(4, PT_MAXT), pt_kernel(4, PT_MAXT + 1), pt_kernel(6, PT_MAXT), pt_kernel(6, PT_MAXT + 1)}, raised);
 }
 extern "C" long t2v_decoder_train_persist_scratch_floats(int B, int T_in, int T_out) {
     if (B < 1 || B > PT_MAXB || T_in < 1 || T_out < 1) return 0;
@@ -922,23 +838,10 @@ extern "C" int t2v_decoder_train_fwd_persistent(const t2v_dec_train_persist_weig
                                                 int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!w || !s || !scratch || T_out < 1 || !t2v_decoder_train_persist_supported(B, T_in)) return T2V_ERR_ARG;
-    if (!w->w_ih_att || !w->w_hh_att || !w->w_ih_dec || !w->w_hh_dec || !w->bias_dec || !w->wq || !w->wcomb || !w->v || !s->gpre ||
-        !s->memory || !s->pm || !s->XS || !s->CA || !s->CD || !s->QP || !s->AL || !s->ACUM)
-        return T2V_ERR_ARG;
-    if ((uintptr_t)scratch & 15) return T2V_ERR_ARG;
     if (pt_g_floats(B, T_out) * 4 >= 0x7fffffffull || pt_ex_floats(B, T_in, T_out) * 4 >= 0x7fffffffull) return T2V_ERR_ARG;   // 31-bit buffer offsets
-    // per-pass resets: the sync / error words, the zero initial states of the arena (as t2v_decoder_train_fwd)
-    unsigned* sync = (unsigned*)(s->QP + t2v_qp_sync_off(B));
-    T2VZeroRegions z;
-    z.add(sync, 64 * sizeof(uint32_t));
-    z.add(s->XS, sizeof(float) * 2 * B * T2V_XW);
-    z.add(s->CA, sizeof(float) * B * T2V_H);
-    z.add(s->CD, sizeof(float) * B * T2V_H);
-    z.add(s->AL, sizeof(float) * B * T_in);
-    z.add(s->ACUM, sizeof(float) * B * T_in);
-    t2v_zero_regions(z, stream);
-    const size_t nfl = pt_g_floats(B, T_out) + pt_ex_floats(B, T_in, T_out);
-    k_pt_fill<<<1024, 256, 0, stream>>>((uint4*)scratch, nfl / 4);
+    unsigned* sync = t2v_persist_fwd_begin(w, s, scratch, B, T_in, stream);
+    if (!sync) return T2V_ERR_ARG;
+    t2v_fill_sentinel(scratch, (pt_g_floats(B, T_out) + pt_ex_floats(B, T_in, T_out)) / 4, 1024, stream);
     PTArgs a;
     a.w_ih_att = w->w_ih_att; a.w_hh_att = w->w_hh_att; a.w_ih_dec = w->w_ih_dec; a.w_hh_dec = w->w_hh_dec;
     a.bias_dec = w->bias_dec; a.wq = w->wq; a.wcomb = w->wcomb; a.v = w->v;
@@ -951,7 +854,7 @@ extern "C" int t2v_decoder_train_fwd_persistent(const t2v_dec_train_persist_weig
     a.step = t2v_step_for(stream);
     a.prof = g_t2v_prof;
     const size_t lds = pt_lds_bytes(B, T_in);
-    if (pt_long(T_in)) {
+    if (T_in > PT_MAXT) {
         if (B > 4) k_dec_train_persist<6, true><<<T2V_NWG, PT_THREADS, lds, stream>>>(a);
         else k_dec_train_persist<4, true><<<T2V_NWG, PT_THREADS, lds, stream>>>(a);
     } else {

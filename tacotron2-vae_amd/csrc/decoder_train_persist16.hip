@@ -21,7 +21,7 @@
 // l & 15, k-group l >> 4) is the 16 bytes at kb * 1024 + 16 l: a wave polls ITS OWN k-blocks with fully coalesced 1-KB loads
 // straight into the registers the MFMA reads.  No LDS staging of the state, no all-threads gather, no barrier between
 // "arrived" and "multiplied"; what a workgroup pulls per step is 80 KB (B = 16) where the fp32 kernel pulls 61 KB at B = 6.
-// Sentinel protocol as in decoder_train_persist.hip: rows are pre-filled with 0xFFFFFFFF (a pair of bf16 NaNs that rounding
+// Sentinel protocol as in decoder_train_persist.hip: rows are pre-filled with T2V_SENT (a pair of bf16 NaNs that rounding
 // a finite fp32 never produces), producers store write-through (sc1), consumers poll the payload with sc1 loads.
 // The attention slices read h_att(t) in fp32 from HX (T rows x 16 items x 1024) — the attention stays fp32 like the
 // launch-per-step path — and publish their 64 context columns as eight 16-byte bf16 chunks.
@@ -37,6 +37,7 @@
 // an LDS transpose 9.51 -> 9.63 (the extra barrier costs more than the narrower stores); a gentler nap rule: no change.
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_xchg.h"
 
 #define P16_THREADS 512
 #define P16_MAXB 16
@@ -46,7 +47,6 @@
 #define P16_NL 128
 #define P16_L0 (T2V_NWG - P16_NL)
 #define P16_SPIN 1500000u
-#define P16_SENT 0xFFFFFFFFu
 #define P16_GROW (T2V_XW / 8 * 16 * 16)        // bytes per GH row: 320 k-groups x 16 items x 16 B = 81 920
 #define P16_HROW (16 * T2V_H * 4)              // bytes per HX row: 16 items x 1024 fp32 = 65 536
 
@@ -71,67 +71,39 @@ struct P16Args {
 // (tools/dbg/persist16_prof.py passes a buffer of 64 + 256 * 8 words)
 #define P16_RT(SLOT) do { if (a.prof && t == a.T_out / 2 && threadIdx.x == 0) a.prof[64 + blockIdx.x * 8 + (SLOT)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 
-typedef unsigned p16_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned p16_u32x2 __attribute__((ext_vector_type(2)));
-#define P16_SC1 16
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t p16_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ p16_u32x4 p16_ld16(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, P16_SC1);
-}
-__device__ __forceinline__ unsigned p16_ld4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, P16_SC1);
-}
-__device__ __forceinline__ void p16_st16(__amdgpu_buffer_rsrc_t r, unsigned off, p16_u32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, P16_SC1);
-}
-__device__ __forceinline__ void p16_st8(__amdgpu_buffer_rsrc_t r, unsigned off, p16_u32x2 v) {
-    __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, P16_SC1);
-}
-__device__ __forceinline__ void p16_st4(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)off, 0, P16_SC1);
-}
-__device__ __forceinline__ bool p16_ok4(p16_u32x4 v) {
-    return v[0] != P16_SENT && v[1] != P16_SENT && v[2] != P16_SENT && v[3] != P16_SENT;
-}
-__device__ __forceinline__ f32x4 p16_mfma(p16_u32x4 w, p16_u32x4 x, f32x4 c) {
+__device__ __forceinline__ f32x4 p16_mfma(u32x4 w, u32x4 x, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(t2v_bf16x8, w), __builtin_bit_cast(t2v_bf16x8, x), c, 0, 0, 0);
 }
 
 // Poll N consecutive k-blocks of one GH row straight into MFMA B operands.  off = row + kb0 * 1024 + 16 * lane.  A lane
 // whose item does not exist (live == false) never waits and reads zeros.  Wave-uniform loop; returns the failed rounds.
 template <int N>
-__device__ __forceinline__ int p16_poll(p16_u32x4 (&x)[N], __amdgpu_buffer_rsrc_t rG, unsigned off, bool live, int nap,
+__device__ __forceinline__ int p16_poll(u32x4 (&x)[N], __amdgpu_buffer_rsrc_t rG, unsigned off, bool live, int nap,
                                         unsigned* err, int* flag) {
     for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
     int rounds = 0;
     for (;;) {
 #pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = p16_ld16(rG, off + 1024u * (unsigned)i);
+        for (int i = 0; i < N; ++i) x[i] = t2v_ld_b128(rG, off + 1024u * (unsigned)i);
         bool ok = true;
 #pragma unroll
-        for (int i = 0; i < N; ++i) ok = ok && p16_ok4(x[i]);
+        for (int i = 0; i < N; ++i) ok = ok && t2v_ok4(x[i]);
         if (__all(ok || !live)) break;
         __builtin_amdgcn_s_sleep(2);
-        if (++rounds > (int)(P16_SPIN / 4) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = 0;
-            break;
-        }
+        if (t2v_give_up(rounds, (int)(P16_SPIN / 4), err, flag)) break;
     }
     if (!live) {
 #pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = p16_u32x4{0u, 0u, 0u, 0u};
+        for (int i = 0; i < N; ++i) x[i] = u32x4{0u, 0u, 0u, 0u};
     }
     return rounds;
 }
 
 // bf16x8 A operand of one (tile, k-block): 8 consecutive columns of one gate row, read from the nn.LSTMCell tensors
-__device__ __forceinline__ p16_u32x4 p16_wload(const float* p) {
+__device__ __forceinline__ u32x4 p16_wload(const float* p) {
     const float4 lo = *(const float4*)p, hi = *(const float4*)(p + 4);
     const uint4 u = t2v_pack_bf16x8(lo, hi);
-    return p16_u32x4{u.x, u.y, u.z, u.w};
+    return u32x4{u.x, u.y, u.z, u.w};
 }
 
 template <bool LONG>          // the attention role for 224 < T_in <= 560, as in k_dec_train_persist<.., true>
@@ -141,7 +113,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
     const int wg = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int B = a.B, Tp = a.T_in, T = a.T_out;
     const int NT = 8 * B;
-    const __amdgpu_buffer_rsrc_t rG = p16_rsrc(a.GH), rH = p16_rsrc(a.HX), rE = p16_rsrc(a.EX);
+    const __amdgpu_buffer_rsrc_t rG = t2v_rsrc(a.GH), rH = t2v_rsrc(a.HX), rE = t2v_rsrc(a.EX);
     const int Tcap = (Tp + 15) & ~15;
 
 #ifndef P16_ONLY_T     // (per-role register reports: tools/dbg/role_regs.sh builds the kernel with one role compiled out)
@@ -154,7 +126,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
         const int n = lane & 15, g = lane >> 4;              // MFMA: item column / k-group (operands), unit of the tile (results)
         const bool live = n < B;
         // ---- weights: tile m, A row (lane & 15) = 4 * unit + gate -> gate row gate * 1024 + u0 + 4 m + unit; k-group g
-        p16_u32x4 wa[2][6], wd[2][10];
+        u32x4 wa[2][6], wd[2][10];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const size_t row = (size_t)(n & 3) * T2V_H + u0 + 4 * m + (n >> 2);
@@ -194,7 +166,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
         const unsigned off_h = (unsigned)(4 * wave) * 1024u + 16u * (unsigned)lane;
         const unsigned off_c = (unsigned)(32 + 2 * wave) * 1024u + 16u * (unsigned)lane;
         const unsigned off_d = (unsigned)(48 + 4 * wave) * 1024u + 16u * (unsigned)lane;
-        p16_u32x4 xc[2] = {p16_u32x4{0u, 0u, 0u, 0u}, p16_u32x4{0u, 0u, 0u, 0u}};     // ctx(-1) = 0
+        u32x4 xc[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};     // ctx(-1) = 0
         f32x4 pA[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};         // h_att part of attention_rnn(t)
         f32x4 pD[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};         // h_att + h_dec parts of decoder_rnn(t-1)
         int nap_h = 0, nap_c = 0;
@@ -260,12 +232,12 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
                 hs[wave * 64 + 4 * n + g] = hd;
                 const float4 hv4 = *(const float4*)(hs + wave * 64 + 4 * (lane & 15));
                 if (lane < B && (ccell == 0 || t < T)) {
-                    const p16_u32x2 pk = {t2v_pack_bf16x2(hv4.x, hv4.y), t2v_pack_bf16x2(hv4.z, hv4.w)};
+                    const u32x2 pk = {t2v_pack_bf16x2(hv4.x, hv4.y), t2v_pack_bf16x2(hv4.z, hv4.w)};
                     const unsigned kg = (unsigned)((ccell == 0 ? 0 : T2V_KATT) / 8 + j);
-                    p16_st8(rG, grow + (kg * 16u + (unsigned)lane) * 16u + 8u * (unsigned)cm, pk);
+                    t2v_st(rG, grow + (kg * 16u + (unsigned)lane) * 16u + 8u * (unsigned)cm, pk);
                     if (ccell == 0)
-                        p16_st16(rH, (unsigned)t * (unsigned)P16_HROW + (unsigned)(lane * T2V_H + u0 + 4 * cm) * 4u,
-                                 p16_u32x4{__float_as_uint(hv4.x), __float_as_uint(hv4.y), __float_as_uint(hv4.z), __float_as_uint(hv4.w)});
+                        t2v_st(rH, (unsigned)t * (unsigned)P16_HROW + (unsigned)(lane * T2V_H + u0 + 4 * cm) * 4u,
+                                 u32x4{__float_as_uint(hv4.x), __float_as_uint(hv4.y), __float_as_uint(hv4.z), __float_as_uint(hv4.w)});
                 }
                 P16_STAMP(wg == P16_L0 && wave == 0 && t == T / 2, 15);
                 if (cell_on) {          // the saved activations follow (plain stores)
@@ -292,7 +264,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
             // ---- row t+1 in the shadow of attention(t): h_att(t) -> its share of attention_rnn(t+1) and decoder_rnn(t);
             // h_dec(t-1) -> decoder_rnn(t); ctx(t) last (the chain)
             {
-                p16_u32x4 xh[4];
+                u32x4 xh[4];
                 const int rounds = p16_poll<4>(xh, rG, grow + off_h, live, nap_h, a.err, flag);
                 nap_h = t2v_adapt_nap(nap_h, rounds);
 #pragma unroll
@@ -310,7 +282,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
             P16_STAMP(wg == P16_L0 && wave == 0 && t == T / 2, 4);
             P16_RT(3);
             if (t >= 1) {
-                p16_u32x4 xd[4];
+                u32x4 xd[4];
                 p16_poll<4>(xd, rG, grow + off_d, live, 0, a.err, flag);
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
@@ -417,18 +389,14 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
         // ---- h_att(t) of this item: 4 KB of fp32 in HX, 16 bytes per thread of waves 0..3; nap, then poll the payload
         if (tid < 256) {
             const unsigned s0 = (unsigned)t * (unsigned)P16_HROW + (unsigned)(ab * T2V_H + 4 * tid) * 4u;
-            p16_u32x4 v;
+            u32x4 v;
             for (int i = 0; i < h_nap; i += 8) __builtin_amdgcn_s_sleep(8);
             int rounds = 0;
             for (;;) {
-                v = p16_ld16(rH, s0);
-                if (__all(p16_ok4(v))) break;
+                v = t2v_ld_b128(rH, s0);
+                if (__all(t2v_ok4(v))) break;
                 __builtin_amdgcn_s_sleep(1);
-                if (++rounds > (int)(P16_SPIN / 4) || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    flag[0] = 0;
-                    break;
-                }
+                if (t2v_give_up(rounds, (int)(P16_SPIN / 4), a.err, flag)) break;
             }
             h_nap = t2v_adapt_nap(h_nap, rounds);
             P16_WALL(wg == 0 && wave == 0 && t == T / 2, 21);
@@ -473,7 +441,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
                 float esum = vr.x * sv.x + vr.y * sv.y + vr.z * sv.z + vr.w * sv.w;
                 esum += __shfl_xor(esum, 16, 64);
                 esum += __shfl_xor(esum, 32, 64);
-                if (g == 0 && jp < Tp) p16_st4(rE, exw + 4u * (unsigned)jp, esum);
+                if (g == 0 && jp < Tp) t2v_st(rE, exw + 4u * (unsigned)jp, esum);
                 if (a.S && jp < Tp) *(float4*)(a.S + (((size_t)t * B + ab) * Tp + jp) * T2V_A + 16 * as + 4 * g) = sv;
             }
         }
@@ -492,16 +460,12 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
                     bool ok = true;
     #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        p[i] = p16_ld4(rE, e0 + (unsigned)(i * Tcap) * 4u);
-                        ok = ok && p[i] != P16_SENT;
+                        p[i] = t2v_ld_b32(rE, e0 + (unsigned)(i * Tcap) * 4u);
+                        ok = ok && t2v_ok(p[i]);
                     }
                     if (ok) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (++spins > P16_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        flag[0] = 0;
-                        break;
-                    }
+                    if (t2v_give_up(spins, P16_SPIN, a.err, flag)) break;
                 }
                 const float ev = ((__uint_as_float(p[0]) + __uint_as_float(p[1])) + (__uint_as_float(p[2]) + __uint_as_float(p[3]))) +
                                  ((__uint_as_float(p[4]) + __uint_as_float(p[5])) + (__uint_as_float(p[6]) + __uint_as_float(p[7])));
@@ -564,17 +528,13 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
                         const unsigned eu = e0 + ((u > 0 && tid + P16_THREADS * u < Tp) ? (unsigned)(P16_THREADS * u) * 4u : 0u);
     #pragma unroll
                         for (int i = 0; i < 8; ++i) {
-                            p[u][i] = p16_ld4(rE, eu + (unsigned)(i * Tcap) * 4u);
-                            ok = ok && p[u][i] != P16_SENT;
+                            p[u][i] = t2v_ld_b32(rE, eu + (unsigned)(i * Tcap) * 4u);
+                            ok = ok && t2v_ok(p[u][i]);
                         }
                     }
                     if (ok) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (++spins > P16_SPIN || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        flag[0] = 0;
-                        break;
-                    }
+                    if (t2v_give_up(spins, P16_SPIN, a.err, flag)) break;
                 }
     #pragma unroll
                 for (int u = 0; u < NPP; ++u) {
@@ -664,7 +624,7 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
                 const float4 c0 = *(const float4*)(cfin + 8 * tid), c1 = *(const float4*)(cfin + 8 * tid + 4);
                 const uint4 pk = t2v_pack_bf16x8(c0, c1);
                 const unsigned kg = (unsigned)(T2V_H / 8 + 8 * as + tid);
-                p16_st16(rG, grow + (kg * 16u + (unsigned)ab) * 16u, p16_u32x4{pk.x, pk.y, pk.z, pk.w});
+                t2v_st(rG, grow + (kg * 16u + (unsigned)ab) * 16u, u32x4{pk.x, pk.y, pk.z, pk.w});
             }
             a.XS[((size_t)(t + 1) * B + ab) * T2V_XW + T2V_H + 64 * as + tid] = acc;       // (after the publish)
         }
@@ -675,12 +635,6 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
 #endif
 }
 
-// sentinel fill of the exchange buffers (16 bytes per thread and iteration)
-__global__ __launch_bounds__(256) void k_p16_fill(uint4* p, size_t n16) {
-    const uint4 s = {P16_SENT, P16_SENT, P16_SENT, P16_SENT};
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = s;
-}
-
 static size_t p16_lds_bytes(int T_in) {
     const size_t Tcap = (size_t)((T_in + 15) / 16) * 16;
     const size_t lrole = 2 * 2 * 8 * 2 * 64 * 4 + 4 * 64 + 4;
@@ -688,7 +642,6 @@ static size_t p16_lds_bytes(int T_in) {
     const size_t trole = resident + 2 * (Tcap + 32) + Tcap + (T_in > P16_MAXT ? T2V_CTX_PAD : 0) + T2V_H + 16 + 32 * 16 + 8 * 64 + 64 + 64 + 4;
     return sizeof(float) * (lrole > trole ? lrole : trole);
 }
-#define P16_LDS_MAX (160 * 1024)
 static size_t p16_gh_floats(int T_out) { return (size_t)(T_out + 2) * (P16_GROW / 4); }
 static size_t p16_hx_floats(int T_out) { return (size_t)T_out * (P16_HROW / 4); }
 static size_t p16_ex_floats(int B, int T_in, int T_out) { return (size_t)T_out * B * 8 * t2v_tcap(T_in); }
@@ -696,35 +649,10 @@ static size_t p16_ex_floats(int B, int T_in, int T_out) { return (size_t)T_out *
 static const void* p16_kernel(int T_in) {
     return T_in > P16_MAXT ? (const void*)k_dec_train_persist16<true> : (const void*)k_dec_train_persist16<false>;
 }
-static int p16_device_ok(int T_in, size_t lds) {
-    static int cus = -1;
-    if (cus < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        cus = prop.multiProcessorCount;
-    }
-    if (cus < T2V_NWG) return 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(p16_kernel(P16_MAXT), hipFuncAttributeMaxDynamicSharedMemorySize, P16_LDS_MAX) != hipSuccess ||
-            hipFuncSetAttribute(p16_kernel(P16_MAXT + 1), hipFuncAttributeMaxDynamicSharedMemorySize, P16_LDS_MAX) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        attr_set = true;
-    }
-    int nblk = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, p16_kernel(T_in), P16_THREADS, lds) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return nblk >= 1;
-}
-
 extern "C" int t2v_decoder_train_persist16_supported(int B, int T_in) {
-    if (!(B >= 1 && B <= P16_MAXB && T_in >= 1 && T_in <= P16_MAXT_LONG && p16_lds_bytes(T_in) <= P16_LDS_MAX)) return 0;
-    return p16_device_ok(T_in, p16_lds_bytes(T_in));
+    if (!(B >= 1 && B <= P16_MAXB && T_in >= 1 && T_in <= P16_MAXT_LONG && p16_lds_bytes(T_in) <= T2V_LDS_MAX)) return 0;
+    static bool raised = false;
+    return t2v_persist_resident(p16_kernel(T_in), P16_THREADS, p16_lds_bytes(T_in), {p16_kernel(P16_MAXT), p16_kernel(P16_MAXT + 1)}, raised);
 }
 extern "C" long t2v_decoder_train_persist16_scratch_floats(int B, int T_in, int T_out) {
     if (B < 1 || B > P16_MAXB || T_in < 1 || T_out < 1) return 0;
@@ -735,25 +663,12 @@ extern "C" int t2v_decoder_train_fwd_persistent16(const t2v_dec_train_persist_we
                                                   int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!w || !s || !scratch || T_out < 1 || !t2v_decoder_train_persist16_supported(B, T_in)) return T2V_ERR_ARG;
-    if (!w->w_ih_att || !w->w_hh_att || !w->w_ih_dec || !w->w_hh_dec || !w->bias_dec || !w->wq || !w->wcomb || !w->v || !s->gpre ||
-        !s->memory || !s->pm || !s->XS || !s->CA || !s->CD || !s->QP || !s->AL || !s->ACUM)
-        return T2V_ERR_ARG;
-    if ((uintptr_t)scratch & 15) return T2V_ERR_ARG;
     if (p16_gh_floats(T_out) * 4 >= 0x7fffffffull || p16_hx_floats(T_out) * 4 >= 0x7fffffffull ||
         p16_ex_floats(B, T_in, T_out) * 4 >= 0x7fffffffull)
         return T2V_ERR_ARG;                                  // 31-bit buffer offsets
-    // per-pass resets: the sync / error words, the zero initial states of the arena (as t2v_decoder_train_fwd)
-    unsigned* sync = (unsigned*)(s->QP + t2v_qp_sync_off(B));
-    T2VZeroRegions z;
-    z.add(sync, 64 * sizeof(uint32_t));
-    z.add(s->XS, sizeof(float) * 2 * B * T2V_XW);
-    z.add(s->CA, sizeof(float) * B * T2V_H);
-    z.add(s->CD, sizeof(float) * B * T2V_H);
-    z.add(s->AL, sizeof(float) * B * T_in);
-    z.add(s->ACUM, sizeof(float) * B * T_in);
-    t2v_zero_regions(z, stream);
-    const size_t nfl = p16_gh_floats(T_out) + p16_hx_floats(T_out) + p16_ex_floats(B, T_in, T_out);
-    k_p16_fill<<<1024, 256, 0, stream>>>((uint4*)scratch, nfl / 4);
+    unsigned* sync = t2v_persist_fwd_begin(w, s, scratch, B, T_in, stream);
+    if (!sync) return T2V_ERR_ARG;
+    t2v_fill_sentinel(scratch, (p16_gh_floats(T_out) + p16_hx_floats(T_out) + p16_ex_floats(B, T_in, T_out)) / 4, 1024, stream);
     P16Args a;
     a.w_ih_att = w->w_ih_att; a.w_hh_att = w->w_hh_att; a.w_ih_dec = w->w_ih_dec; a.w_hh_dec = w->w_hh_dec;
     a.bias_dec = w->bias_dec; a.wq = w->wq; a.wcomb = w->wcomb; a.v = w->v;

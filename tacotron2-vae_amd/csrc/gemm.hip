@@ -11,8 +11,9 @@
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_coop.h"
+#include "t2v_x3.h"
+#include "t2v_xchg.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GM_BM 64
 #define GM_BN 64
 #define GM_BK 32
@@ -409,12 +410,6 @@ static bool gemm_big_ok(const GemmArgs& a) {
 // ---- bf16 variant (hparams bf16_run): operands rounded to bf16 (RNE) while staged, fp32 accumulate on
 // v_mfma_f32_32x32x8_bf16, fp32 in / fp32 out.  LDS tiles are k-contiguous [row][32 (+4 pad)] so each MFMA operand
 // is one ds_read_b64 (row stride 72 B: conflict-free).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_g __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned gemm_pack_bf16x2(float lo, float hi) {
-    bf16x2_g p = {(__bf16)lo, (__bf16)hi};
-    return *(unsigned*)&p;
-}
 #define GB_RS 36
 
 template <bool A_KC, bool B_KC>
@@ -468,11 +463,11 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(GemmArgs a) {
     };
     auto store_tiles = [&](int buf) {
         uint2* pa = (uint2*)&As[buf][a_r][a_k];
-        pa[0] = make_uint2(gemm_pack_bf16x2(ra[0], ra[1]), gemm_pack_bf16x2(ra[2], ra[3]));
-        pa[1] = make_uint2(gemm_pack_bf16x2(ra[4], ra[5]), gemm_pack_bf16x2(ra[6], ra[7]));
+        pa[0] = make_uint2(t2v_pack_bf16x2(ra[0], ra[1]), t2v_pack_bf16x2(ra[2], ra[3]));
+        pa[1] = make_uint2(t2v_pack_bf16x2(ra[4], ra[5]), t2v_pack_bf16x2(ra[6], ra[7]));
         uint2* pb = (uint2*)&Bs[buf][b_r][b_k];
-        pb[0] = make_uint2(gemm_pack_bf16x2(rb[0], rb[1]), gemm_pack_bf16x2(rb[2], rb[3]));
-        pb[1] = make_uint2(gemm_pack_bf16x2(rb[4], rb[5]), gemm_pack_bf16x2(rb[6], rb[7]));
+        pb[0] = make_uint2(t2v_pack_bf16x2(rb[0], rb[1]), t2v_pack_bf16x2(rb[2], rb[3]));
+        pb[1] = make_uint2(t2v_pack_bf16x2(rb[4], rb[5]), t2v_pack_bf16x2(rb[6], rb[7]));
     };
     f32x16 acc;
 #pragma unroll
@@ -487,8 +482,8 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(GemmArgs a) {
         if (kt + 1 < nkt) load_tiles(kbeg + (kt + 1) * GM_BK);
 #pragma unroll
         for (int s4 = 0; s4 < GM_BK / 8; ++s4) {
-            const s16x4 av = *(const s16x4*)&As[buf][ai][8 * s4 + 4 * kh];
-            const s16x4 bv = *(const s16x4*)&Bs[buf][bj][8 * s4 + 4 * kh];
+            const t2v_s16x4 av = *(const t2v_s16x4*)&As[buf][ai][8 * s4 + 4 * kh];
+            const t2v_s16x4 bv = *(const t2v_s16x4*)&Bs[buf][bj][8 * s4 + 4 * kh];
             acc = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(av, bv, acc, 0, 0, 0);
         }
         if (kt + 1 < nkt) store_tiles(buf ^ 1);
@@ -549,22 +544,22 @@ __global__ __launch_bounds__(256) void k_gemm_bf16_big_rr(GemmArgs a) {
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 const float4 lo = rg[2 * rr], hi = rg[2 * rr + 1];
-                dst[rr] = make_uint4(gemm_pack_bf16x2(lo.x * z_row, lo.y * z_row), gemm_pack_bf16x2(lo.z * z_row, lo.w * z_row),
-                                     gemm_pack_bf16x2(hi.x * z_row, hi.y * z_row), gemm_pack_bf16x2(hi.z * z_row, hi.w * z_row));
+                dst[rr] = make_uint4(t2v_pack_bf16x2(lo.x * z_row, lo.y * z_row), t2v_pack_bf16x2(lo.z * z_row, lo.w * z_row),
+                                     t2v_pack_bf16x2(hi.x * z_row, hi.y * z_row), t2v_pack_bf16x2(hi.z * z_row, hi.w * z_row));
             }
             return;
         }
         float zk[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) zk[u] = (k0 + 8 * kg + u < kend ? 1.f : 0.f) * z_row;
-        dst[0] = make_uint4(gemm_pack_bf16x2(rg[0].x * zk[0], rg[1].x * zk[1]), gemm_pack_bf16x2(rg[2].x * zk[2], rg[3].x * zk[3]),
-                            gemm_pack_bf16x2(rg[4].x * zk[4], rg[5].x * zk[5]), gemm_pack_bf16x2(rg[6].x * zk[6], rg[7].x * zk[7]));
-        dst[1] = make_uint4(gemm_pack_bf16x2(rg[0].y * zk[0], rg[1].y * zk[1]), gemm_pack_bf16x2(rg[2].y * zk[2], rg[3].y * zk[3]),
-                            gemm_pack_bf16x2(rg[4].y * zk[4], rg[5].y * zk[5]), gemm_pack_bf16x2(rg[6].y * zk[6], rg[7].y * zk[7]));
-        dst[2] = make_uint4(gemm_pack_bf16x2(rg[0].z * zk[0], rg[1].z * zk[1]), gemm_pack_bf16x2(rg[2].z * zk[2], rg[3].z * zk[3]),
-                            gemm_pack_bf16x2(rg[4].z * zk[4], rg[5].z * zk[5]), gemm_pack_bf16x2(rg[6].z * zk[6], rg[7].z * zk[7]));
-        dst[3] = make_uint4(gemm_pack_bf16x2(rg[0].w * zk[0], rg[1].w * zk[1]), gemm_pack_bf16x2(rg[2].w * zk[2], rg[3].w * zk[3]),
-                            gemm_pack_bf16x2(rg[4].w * zk[4], rg[5].w * zk[5]), gemm_pack_bf16x2(rg[6].w * zk[6], rg[7].w * zk[7]));
+        dst[0] = make_uint4(t2v_pack_bf16x2(rg[0].x * zk[0], rg[1].x * zk[1]), t2v_pack_bf16x2(rg[2].x * zk[2], rg[3].x * zk[3]),
+                            t2v_pack_bf16x2(rg[4].x * zk[4], rg[5].x * zk[5]), t2v_pack_bf16x2(rg[6].x * zk[6], rg[7].x * zk[7]));
+        dst[1] = make_uint4(t2v_pack_bf16x2(rg[0].y * zk[0], rg[1].y * zk[1]), t2v_pack_bf16x2(rg[2].y * zk[2], rg[3].y * zk[3]),
+                            t2v_pack_bf16x2(rg[4].y * zk[4], rg[5].y * zk[5]), t2v_pack_bf16x2(rg[6].y * zk[6], rg[7].y * zk[7]));
+        dst[2] = make_uint4(t2v_pack_bf16x2(rg[0].z * zk[0], rg[1].z * zk[1]), t2v_pack_bf16x2(rg[2].z * zk[2], rg[3].z * zk[3]),
+                            t2v_pack_bf16x2(rg[4].z * zk[4], rg[5].z * zk[5]), t2v_pack_bf16x2(rg[6].z * zk[6], rg[7].z * zk[7]));
+        dst[3] = make_uint4(t2v_pack_bf16x2(rg[0].w * zk[0], rg[1].w * zk[1]), t2v_pack_bf16x2(rg[2].w * zk[2], rg[3].w * zk[3]),
+                            t2v_pack_bf16x2(rg[4].w * zk[4], rg[5].w * zk[5]), t2v_pack_bf16x2(rg[6].w * zk[6], rg[7].w * zk[7]));
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -578,7 +573,6 @@ __global__ __launch_bounds__(256) void k_gemm_bf16_big_rr(GemmArgs a) {
     store_tiles(0, kbeg);
     __syncthreads();
     const int am = 64 * wm + (lane & 31), bn = 64 * wn + (lane & 31), kq = lane >> 5;
-    typedef __bf16 gbb_bf16x8 __attribute__((ext_vector_type(8)));
     for (int kt = 0; kt < nkt; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nkt) load_tiles(kbeg + (kt + 1) * GBB_BK);
@@ -596,7 +590,7 @@ __global__ __launch_bounds__(256) void k_gemm_bf16_big_rr(GemmArgs a) {
             for (int x = 0; x < 2; ++x)
 #pragma unroll
                 for (int y = 0; y < 2; ++y)
-                    acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const gbb_bf16x8*)&av[s2][x], *(const gbb_bf16x8*)&bv[s2][y], acc[x][y], 0, 0, 0);
+                    acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const t2v_bf16x8*)&av[s2][x], *(const t2v_bf16x8*)&bv[s2][y], acc[x][y], 0, 0, 0);
         if (kt + 1 < nkt) store_tiles(buf ^ 1, kbeg + (kt + 1) * GBB_BK);
         __syncthreads();
     }
@@ -604,17 +598,16 @@ __global__ __launch_bounds__(256) void k_gemm_bf16_big_rr(GemmArgs a) {
         // the raw accumulators go to scratch in ACCUMULATOR order ([split][tile][16-byte group g = 0..15][thread]: a wave's
         // store / load is 1 KB contiguous), write-through; the workgroup that arrives LAST at its tile's counter adds the
         // partials in the fixed order z = 0, 1, ... (bit-identical whichever workgroup does it) and runs the epilogue
-        typedef unsigned gbb_u32x4 __attribute__((ext_vector_type(4)));
         const size_t tiles = (size_t)gridDim.x * gridDim.y, tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
         {
-            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (blockIdx.z * tiles + tile) * (GBB_BM * GBB_BN), 0, 0x7fffffff, 0x00020000);
+            __amdgpu_buffer_rsrc_t rs = t2v_rsrc(a.part + (blockIdx.z * tiles + tile) * (GBB_BM * GBB_BN));
 #pragma unroll
             for (int x = 0; x < 2; ++x)
 #pragma unroll
                 for (int y = 0; y < 2; ++y)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        gbb_u32x4 v;
+                        u32x4 v;
                         v.x = __float_as_uint(acc[x][y][4 * q]); v.y = __float_as_uint(acc[x][y][4 * q + 1]);
                         v.z = __float_as_uint(acc[x][y][4 * q + 2]); v.w = __float_as_uint(acc[x][y][4 * q + 3]);
                         __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((((x * 2 + y) * 4 + q) * 256) + tid) * 16, 0, 16);
@@ -636,11 +629,11 @@ __global__ __launch_bounds__(256) void k_gemm_bf16_big_rr(GemmArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
         for (int z0 = 0; z0 < nz; z0 += 2) {            // two partial tiles (32 loads per thread) requested before the first add
-            gbb_u32x4 v[2][16];
+            u32x4 v[2][16];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int z = min(z0 + u, nz - 1);
-                __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (z * tiles + tile) * (GBB_BM * GBB_BN), 0, 0x7fffffff, 0x00020000);
+                __amdgpu_buffer_rsrc_t rs = t2v_rsrc(a.part + (z * tiles + tile) * (GBB_BM * GBB_BN));
 #pragma unroll
                 for (int g = 0; g < 16; ++g) v[u][g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (g * 256 + tid) * 16, 0, 16);
             }
@@ -743,23 +736,6 @@ extern "C" long t2v_gemm_bf16_splitk_scratch_floats(int M, int N, int K) {
 #define GX_BM 128
 #define GX_BN 128
 #define GX_SK 16                    // k per stage (two k-groups of 8)
-typedef __bf16 gx_bf16x8 __attribute__((ext_vector_type(8)));
-// 8 consecutive-k fp32 values of one operand row -> the row's 16-byte word in each of the three planes
-__device__ __forceinline__ void gx_split8(const float (&v)[8], uint4& p0, uint4& p1, uint4& p2) {
-    unsigned q0[4], q1[4], q2[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float x = v[2 * c], y = v[2 * c + 1];
-        const unsigned h = gemm_pack_bf16x2(x, y);
-        const float r1x = x - __uint_as_float(h << 16), r1y = y - __uint_as_float(h & 0xffff0000u);
-        const unsigned m = gemm_pack_bf16x2(r1x, r1y);
-        const float r2x = r1x - __uint_as_float(m << 16), r2y = r1y - __uint_as_float(m & 0xffff0000u);
-        q0[c] = h; q1[c] = m; q2[c] = gemm_pack_bf16x2(r2x, r2y);
-    }
-    p0 = make_uint4(q0[0], q0[1], q0[2], q0[3]);
-    p1 = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-    p2 = make_uint4(q2[0], q2[1], q2[2], q2[3]);
-}
 // planes of an operand with `rows` rows and K columns: Rp = rows rounded up to 128, G = k-groups rounded up to 4 (32 k);
 // plane p, k-group g, row r -> 16-byte slot (p * G + g) * Rp + r.  Rows >= rows and k >= K are zero.
 static inline long gx_rp(int rows) { return ((long)rows + 127) / 128 * 128; }
@@ -794,10 +770,10 @@ __global__ __launch_bounds__(256) void k_x3_split(const float* __restrict__ src,
     }
     if (NP == 3) {
         uint4 p0, p1, p2;
-        gx_split8(v, p0, p1, p2);
+        t2v_split8(v, p0, p1, p2);
         sm[0][g][r] = p0; sm[NP > 1 ? 1 : 0][g][r] = p1; sm[NP > 2 ? 2 : 0][g][r] = p2;
     } else {        // bf16_run: the operand rounded to bf16 (RNE), nothing else
-        sm[0][g][r] = make_uint4(gemm_pack_bf16x2(v[0], v[1]), gemm_pack_bf16x2(v[2], v[3]), gemm_pack_bf16x2(v[4], v[5]), gemm_pack_bf16x2(v[6], v[7]));
+        sm[0][g][r] = make_uint4(t2v_pack_bf16x2(v[0], v[1]), t2v_pack_bf16x2(v[2], v[3]), t2v_pack_bf16x2(v[4], v[5]), t2v_pack_bf16x2(v[6], v[7]));
     }
     __syncthreads();
     const int g2 = tid >> 6, r2 = tid & 63;
@@ -826,15 +802,6 @@ struct GemmX3Args {
     int st_chunk;           // split-K: stages per blockIdx.z (0 = all)
     float* part; unsigned* tile_ctr;
 };
-// 16 bytes per lane global -> LDS without a destination register (lane i lands at lds_addr + 16 i; lds_addr wave-uniform, in an SGPR).
-// Inline asm on purpose: hipcc counts the builtin form as an LDS write and puts `s_waitcnt vmcnt(0)` in front of EVERY later ds_read —
-// the prefetch issued at the top of a stage was waited for before the stage's own MFMAs.  The asm form is invisible to its
-// bookkeeping; the waits are counted by hand below.
-__device__ __forceinline__ void gx_dma16(const void* gsrc, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_addr) : "memory");
-}
 #ifndef GX_NB
 #define GX_NB 2                     // stage buffers: the planes of stage i + GX_NB - 1 are requested during stage i.  Two (48 KB, three
                                     // workgroups per CU) and three (72 KB, two per CU) measure the same alone and in the step (10.82 .. 10.95 ms):
@@ -847,19 +814,6 @@ __device__ __forceinline__ void gx_dma16(const void* gsrc, unsigned lds_addr) {
 #ifndef GX_NG1
 #define GX_NG1 4                   // k-groups per stage of the one-plane (bf16_run) form (2 / 4 / 8 measured: 432 / 453 / 423 TFLOP/s on 4096 x 2560 x 6400)
 #endif
-#define GX_STR2(x) #x
-#define GX_STR(x) GX_STR2(x)
-// wait until at most N of this wave's memory requests are outstanding (N a compile-time constant <= 63)
-template <int N>
-__device__ __forceinline__ void gx_wait_stage() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else static_assert(N == 0, "add the literal");
-}
 // NP planes per operand, NG k-groups (of 8) per stage: <3, 2> = the x3 form of an fp32 product (six MFMAs per k-block of 16, 24 per
 // wave and stage); <1, GX_NG1> = a bf16_run product on pre-rounded operands (one MFMA per k-block of 16)
 template <int NP, int NG>
@@ -894,7 +848,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3p(GemmX3Args a) {
             const int op = q / (2 * NP * NG), rem = q - (2 * NP * NG) * op, p = rem / (2 * NG), g = (rem >> 1) % NG, half = rem & 1;
             const uint4* src = op ? P.Bp + (p * a.G + NG * st + g) * P.RpB + j0 + 64 * half + lane
                                   : P.Ap + (p * a.G + NG * st + g) * P.RpA + i0 + 64 * half + lane;
-            gx_dma16(src, lds0 + 16u * (unsigned)(((((buf * 2 + op) * NP + p) * NG + g) * GX_BM) + 64 * half));
+            t2v_dma16(src, lds0 + 16u * (unsigned)(((((buf * 2 + op) * NP + p) * NG + g) * GX_BM) + 64 * half));
         }
     };
     f32x16 acc[2][2];
@@ -905,10 +859,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3p(GemmX3Args a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
     const int am = 64 * wm + (lane & 31), bn = 64 * wn + (lane & 31), kq = lane >> 5;
-#define GX_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const gx_bf16x8*)&(A_), *(const gx_bf16x8*)&(B_), C_, 0, 0, 0)
+#define GX_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const t2v_bf16x8*)&(A_), *(const t2v_bf16x8*)&(B_), C_, 0, 0, 0)
 #pragma unroll
     for (int d = 0; d < GX_NB - 1; ++d) stage_dma(st0 + d, d);
-    gx_wait_stage<NPIECE * (GX_NB - 2)>();          // the first stage has landed, the later ones may still be on their way
+    t2v_wait_vmcnt<NPIECE * (GX_NB - 2)>();          // the first stage has landed, the later ones may still be on their way
     __syncthreads();
     int buf = 0;
     for (int st = st0; st < st1; ++st) {
@@ -938,7 +892,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3p(GemmX3Args a) {
 #undef GX_ALL
         // stage st + 1 must have landed before anybody passes the barrier: requests come back in order, so it has once only the
         // requests of the GX_NB - 2 stages behind it (six per wave and stage) are outstanding
-        gx_wait_stage<NPIECE * (GX_NB - 2)>();
+        t2v_wait_vmcnt<NPIECE * (GX_NB - 2)>();
         __syncthreads();        // ... and this stage's LDS reads are done
         buf = buf == GX_NB - 1 ? 0 : buf + 1;
     }
@@ -947,17 +901,16 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3p(GemmX3Args a) {
     if (a.part) {
         // split-K exactly as in k_gemm_bf16_big_rr: raw accumulators to scratch in accumulator order (write-through), the workgroup
         // that arrives last at its tile's counter adds the partials in the fixed order z = 0, 1, ... and runs the epilogue
-        typedef unsigned gx_u32x4 __attribute__((ext_vector_type(4)));
         const size_t tiles = (size_t)a.ntiles, tile = (size_t)lin;
         {
-            __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (blockIdx.z * tiles + tile) * (GX_BM * GX_BN), 0, 0x7fffffff, 0x00020000);
+            __amdgpu_buffer_rsrc_t rs = t2v_rsrc(a.part + (blockIdx.z * tiles + tile) * (GX_BM * GX_BN));
 #pragma unroll
             for (int x = 0; x < 2; ++x)
 #pragma unroll
                 for (int y = 0; y < 2; ++y)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        gx_u32x4 v;
+                        u32x4 v;
                         v.x = __float_as_uint(acc[x][y][4 * q]); v.y = __float_as_uint(acc[x][y][4 * q + 1]);
                         v.z = __float_as_uint(acc[x][y][4 * q + 2]); v.w = __float_as_uint(acc[x][y][4 * q + 3]);
                         __builtin_amdgcn_raw_buffer_store_b128(v, rs, ((((x * 2 + y) * 4 + q) * 256) + tid) * 16, 0, 16);
@@ -979,11 +932,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3p(GemmX3Args a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
         for (int z0 = 0; z0 < nz; z0 += 2) {
-            gx_u32x4 v[2][16];
+            u32x4 v[2][16];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int z = min(z0 + u, nz - 1);
-                __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.part + (z * tiles + tile) * (GX_BM * GX_BN), 0, 0x7fffffff, 0x00020000);
+                __amdgpu_buffer_rsrc_t rs = t2v_rsrc(a.part + (z * tiles + tile) * (GX_BM * GX_BN));
 #pragma unroll
                 for (int g = 0; g < 16; ++g) v[u][g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (g * 256 + tid) * 16, 0, 16);
             }

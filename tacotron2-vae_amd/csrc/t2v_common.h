@@ -3,7 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Model geometry of the decoder path at the reference's default hparams
 // (reference hparams.py:81-101).  The C API rejects anything else.
@@ -71,11 +75,11 @@ __device__ __forceinline__ float4 ld_nt(const float4* p) {
 __device__ __forceinline__ float sigmoidf_(float x) { return fast_rcp(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * fast_rcp(1.0f + __expf(2.0f * x)); }
 
+// value of the lane that DPP control CTRL selects (row_mask = bank_mask = 0xF, bound_ctrl)
+#define T2V_DPP_F(v, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, true))
 // 16-lane row sum with DPP (no LDS crossbar): every lane of a row ends with the row's sum.
-#define T2V_DPP_ADD(v, CTRL) \
-    ((v) + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, true)))
-#define T2V_DPP_MAX(v, CTRL) \
-    fmaxf((v), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, true)))
+#define T2V_DPP_ADD(v, CTRL) ((v) + T2V_DPP_F((v), (CTRL)))
+#define T2V_DPP_MAX(v, CTRL) fmaxf((v), T2V_DPP_F((v), (CTRL)))
 __device__ __forceinline__ float row16_sum(float v) {
     v = T2V_DPP_ADD(v, 0xB1);    // quad_perm [1,0,3,2]
     v = T2V_DPP_ADD(v, 0x4E);    // quad_perm [2,3,0,1]
@@ -202,7 +206,7 @@ __device__ __forceinline__ float rows2_sum(float v) {
 }
 __device__ __forceinline__ float wave_sum_rl(float v) { return rows4_sum(row16_sum(v)); }
 // value of lane Q of the own quad (DPP quad_perm broadcast)
-#define T2V_DPP_QUAD_F(v, Q) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (Q) * 0x55, 0xF, 0xF, true))
+#define T2V_DPP_QUAD_F(v, Q) T2V_DPP_F((v), (Q) * 0x55)
 
 __device__ __forceinline__ float wave_sum(float v) {
     v = row16_sum(v);

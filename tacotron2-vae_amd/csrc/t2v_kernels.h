@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include "../../include/t2vae.h"
+#include "t2v_common.h"
 
 enum { T2V_RNG_ATT_H = 1, T2V_RNG_ATT_C = 2, T2V_RNG_DEC_H = 3, T2V_RNG_DEC_C = 4,
        T2V_RNG_PRENET0 = 5, T2V_RNG_PRENET1 = 6 };
@@ -22,6 +24,18 @@ struct T2VZeroRegions {
     void add(void* ptr, size_t nbytes) { p[n] = ptr; bytes[n] = nbytes; ++n; }
 };
 void t2v_zero_regions(T2VZeroRegions& z, hipStream_t stream);
+
+// persistent decoder kernels (t2v_xchg.h, t2v_runtime.hip):
+// n16 16-byte words at p set to the exchange sentinel by `grid` workgroups of 256 threads
+__global__ void k_sentinel_fill(uint4* p, size_t n16);
+void t2v_fill_sentinel(void* p, size_t n16, int grid, hipStream_t stream);
+// the device has >= T2V_NWG CUs (one resident workgroup each)
+bool t2v_persist_cus_ok();
+// dynamic-LDS limit of `kernels` raised to T2V_LDS_MAX once (`raised`: the launcher's flag); false leaves the runtime error pending
+bool t2v_persist_raise_lds(std::initializer_list<const void*> kernels, bool& raised);
+// 1 when T2V_NWG workgroups of `kernel` (`threads` threads, `lds` bytes of dynamic LDS) can all be resident: enough CUs, the
+// limit raised (as above), occupancy >= 1 per CU; a runtime error on the way is cleared
+int t2v_persist_resident(const void* kernel, int threads, size_t lds, std::initializer_list<const void*> kernels, bool& raised);
 struct LstmFwdArgs;
 struct AttnFwdArgs;
 
@@ -43,6 +57,26 @@ static inline int t2v_attn_bwd_js(int T_in) { return T_in <= 128 ? 16 : 32; }
 static inline int t2v_attn_bwd_slices_(int T_in) { const int js = t2v_attn_bwd_js(T_in); return (T_in + js - 1) / js; }
 void t2v_launch_lstm_fwd(int mode, const LstmFwdArgs& a, hipStream_t stream);
 void t2v_launch_attn_fwd(const AttnFwdArgs& f, int B, int T_in, hipStream_t stream);
+// The two persistent forward launchers (fp32 / bf16), after their shape and offset checks: the checks of the remaining
+// arguments, then the per-pass resets — the sync / error words, the zero initial states of the arena (as
+// t2v_decoder_train_fwd).  Returns the sync words, or NULL (nothing issued) on a bad argument.
+static inline unsigned* t2v_persist_fwd_begin(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* scratch,
+                                              int B, int T_in, hipStream_t stream) {
+    if (!w->w_ih_att || !w->w_hh_att || !w->w_ih_dec || !w->w_hh_dec || !w->bias_dec || !w->wq || !w->wcomb || !w->v || !s->gpre ||
+        !s->memory || !s->pm || !s->XS || !s->CA || !s->CD || !s->QP || !s->AL || !s->ACUM)
+        return nullptr;
+    if ((uintptr_t)scratch & 15) return nullptr;
+    unsigned* sync = (unsigned*)(s->QP + t2v_qp_sync_off(B));
+    T2VZeroRegions z;
+    z.add(sync, 64 * sizeof(uint32_t));
+    z.add(s->XS, sizeof(float) * 2 * B * T2V_XW);
+    z.add(s->CA, sizeof(float) * B * T2V_H);
+    z.add(s->CD, sizeof(float) * B * T2V_H);
+    z.add(s->AL, sizeof(float) * B * T_in);
+    z.add(s->ACUM, sizeof(float) * B * T_in);
+    t2v_zero_regions(z, stream);
+    return sync;
+}
 
 struct LstmFwdArgs {
     const float4* packA;

@@ -1,6 +1,7 @@
 // Library-level plumbing: version string, error recording.
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_xchg.h"
 #include <string.h>
 
 static thread_local char g_err[256] = "";
@@ -86,6 +87,48 @@ void t2v_zero_regions(T2VZeroRegions& z, hipStream_t stream) {
     size_t bx = (mx + 4095) / 4096;
     if (bx > 1024) bx = 1024;
     k_zero_regions<<<dim3((unsigned)bx, (unsigned)n), 256, 0, stream>>>(z);
+}
+
+// Sentinel fill of the persistent kernels' exchange buffers (t2v_xchg.h): 16 bytes per thread and iteration.
+__global__ __launch_bounds__(256) void k_sentinel_fill(uint4* p, size_t n16) {
+    const uint4 s = {T2V_SENT, T2V_SENT, T2V_SENT, T2V_SENT};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = s;
+}
+void t2v_fill_sentinel(void* p, size_t n16, int grid, hipStream_t stream) {
+    k_sentinel_fill<<<grid, 256, 0, stream>>>((uint4*)p, n16);
+}
+
+// Residency of the persistent kernels: their workgroups spin on each other's results, so all T2V_NWG of them must be resident at
+// once — one per CU.  The CU count is asked once per process, each launcher raises the dynamic-LDS limit of its kernels once.
+bool t2v_persist_cus_ok() {
+    static int cus = -1;
+    if (cus < 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)hipGetLastError(); return false; }
+        cus = prop.multiProcessorCount;
+    }
+    return cus >= T2V_NWG;
+}
+bool t2v_persist_raise_lds(std::initializer_list<const void*> kernels, bool& raised) {
+    if (raised) return true;
+    for (const void* k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, T2V_LDS_MAX) != hipSuccess) return false;
+    raised = true;
+    return true;
+}
+int t2v_persist_resident(const void* kernel, int threads, size_t lds, std::initializer_list<const void*> kernels, bool& raised) {
+    if (!t2v_persist_cus_ok()) return 0;
+    if (!t2v_persist_raise_lds(kernels, raised)) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    int nblk = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, kernel, threads, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return nblk >= 1;
 }
 
 // Measurement aid: one thread writes the chip-wide 100 MHz wall clock into buf[slot].  A training engine drops these
