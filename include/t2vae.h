@@ -520,6 +520,9 @@ int t2v_gemm_bf16_grouped(const t2v_gemm_group* groups, int ngroups, int M, int 
  * tiles) outweigh the faster loop, at B = 16 it runs a Postnet layer in 152 us against 212.  Only effective while
  * t2v_gemm_f32_set_mode is 1.  t2v_conv1d_stat_blocks answers for the current mode.  Pass -1 to query.  Returns the previous mode. */
 int t2v_conv1d_x3_set_mode(int mode);
+/* 1 when the k = 5 convolution Cin -> Cout of t2v_conv1d_fwd (bf16 = 0) / t2v_conv1d_fwd_bf16 (bf16 = 1) takes the plane kernels of
+ * conv_x3.hip in the current mode, 0 when it runs on the tiled kernels (mode, tile count, and whether the call's scratch fits) */
+int t2v_conv1d_takes_x3(int B, int Cin, int T, int Cout, int KS, int bf16);
 
 /* nbatch independent products C_z = A_z · B_z^T (z-th operands at A + z*sAb, B + z*sBb, C + z*sCb; element strides as in
  * t2v_gemm_f32, no bias / epilogue) in one launch.  Replaces the per-item loop that autograd's bmm backward of

@@ -29,9 +29,15 @@ def get_mask_from_lengths(lengths, max_len=None):
 
 
 def _bn(x, sd, prefix, training, stats_out=None):
-    """BatchNorm1d/2d, SURVEY Appendix C: train = biased batch variance, eps 1e-5."""
+    """BatchNorm1d/2d, SURVEY Appendix C: train = biased batch variance, eps 1e-5.
+    stats_out (dict, training only): stats_out[prefix] = (batch mean, UNBIASED batch variance) per channel, detached — what
+    nn.BatchNorm folds into running_mean / running_var with momentum 0.1 (the output does not depend on it)."""
     w, b = sd[prefix + '.weight'], sd[prefix + '.bias']
     if training:
+        if stats_out is not None:
+            xd = x.detach()
+            dims = [0] + list(range(2, xd.dim()))
+            stats_out[prefix] = (xd.mean(dims), xd.var(dims, unbiased=True))
         return F.batch_norm(x, None, None, w, b, True, 0.0, 1e-5)
     return F.batch_norm(x, sd[prefix + '.running_mean'], sd[prefix + '.running_var'],
                         w, b, False, 0.0, 1e-5)
@@ -56,13 +62,13 @@ def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
 
 
 # --------------------------------------------------------------------------- encoder (a-9, a-10)
-def encoder_forward(sd, text, input_lengths, training=True, drop=None, p_conv=0.5):
+def encoder_forward(sd, text, input_lengths, training=True, drop=None, p_conv=0.5, bn_stats=None):
     """model.py:528 + Encoder.forward model.py:175-192 (packed BiLSTM == per-sequence lengths)."""
     x = F.embedding(text, sd['transcript_embedding.weight']).transpose(1, 2)
     for i in range(3):
         pre = 'encoder.convolutions.%d' % i
         x = F.conv1d(x, sd[pre + '.0.conv.weight'], sd[pre + '.0.conv.bias'], padding=2)
-        x = F.relu(_bn(x, sd, pre + '.1', training))
+        x = F.relu(_bn(x, sd, pre + '.1', training, bn_stats))
         if training:
             x = _apply_keep(x, None if drop is None else drop.get('enc%d' % i), p_conv)
     x = x.transpose(1, 2)  # (B, T, 512)
@@ -115,7 +121,7 @@ def gru_last(x, w_ih, w_hh, b_ih, b_hh):
     return h
 
 
-def vae_gst_forward(sd, mel, training=True, eps=None):
+def vae_gst_forward(sd, mel, training=True, eps=None, bn_stats=None):
     """VAE_GST.forward modules.py:24-31; ReferenceEncoder.forward modules.py:65-80.
     NB modules.py:67: (B,80,T) memory is *reinterpreted* as (B,1,T,80) — no transpose."""
     N = mel.shape[0]
@@ -125,7 +131,7 @@ def vae_gst_forward(sd, mel, training=True, eps=None):
         wk = 'vae_gst.ref_encoder.convs.%d.%s' % (i, 'conv.weight' if i == 0 else 'weight')
         bk = 'vae_gst.ref_encoder.convs.%d.%s' % (i, 'conv.bias' if i == 0 else 'bias')
         out = F.conv2d(out, sd[wk], sd[bk], stride=2, padding=1)
-        out = F.relu(_bn(out, sd, 'vae_gst.ref_encoder.bns.%d' % i, training))
+        out = F.relu(_bn(out, sd, 'vae_gst.ref_encoder.bns.%d' % i, training, bn_stats))
     out = out.transpose(1, 2)
     T = out.shape[1]
     out = out.contiguous().view(N, T, -1)
@@ -247,12 +253,12 @@ def decoder_inference(sd, memory, max_steps=1000, gate_threshold=0.5, prenet_kee
 
 
 # --------------------------------------------------------------------------- postnet (a-17)
-def postnet_forward(sd, x, training=True, drop=None, p=0.5):
+def postnet_forward(sd, x, training=True, drop=None, p=0.5, bn_stats=None):
     """Postnet.forward model.py:143-148."""
     for i in range(5):
         pre = 'postnet.convolutions.%d' % i
         x = F.conv1d(x, sd[pre + '.0.conv.weight'], sd[pre + '.0.conv.bias'], padding=2)
-        x = _bn(x, sd, pre + '.1', training)
+        x = _bn(x, sd, pre + '.1', training, bn_stats)
         if i < 4:
             x = torch.tanh(x)
         if training:
@@ -263,19 +269,20 @@ def postnet_forward(sd, x, training=True, drop=None, p=0.5):
 # --------------------------------------------------------------------------- whole model (a-8, a-18)
 def tacotron2_forward(sd, text, input_lengths, mels, output_lengths, training=True, eps=None,
                       p_att=0.0, p_dec=0.0, drop=None, p_conv=0.0, p_prenet=0.0,
-                      quirk_inplace_mask=True):
+                      quirk_inplace_mask=True, bn_stats=None):
     """Tacotron2.forward model.py:522-547 + parse_output 509-520.
 
     quirk_inplace_mask reproduces Appendix B-5: the reference zero-fills padded frames of
     the decoder mel *in place on .data* (model.py:515-517) after Postnet conv-0 saved that very
     tensor for backward, so conv-0's weight gradient is computed from the masked tensor.  We do
     literally the same (.data masked_fill_); False gives the clean out-of-place graph.
+    bn_stats (dict): filled with every BatchNorm layer's batch statistics, see _bn.
     """
-    enc = encoder_forward(sd, text, input_lengths, training, drop, p_conv)
-    style, mu, logvar, z = vae_gst_forward(sd, mels, training, eps)
+    enc = encoder_forward(sd, text, input_lengths, training, drop, p_conv, bn_stats)
+    style, mu, logvar, z = vae_gst_forward(sd, mels, training, eps, bn_stats)
     memory = enc + style[:, None, :]
     mel, gate, align = decoder_forward(sd, memory, mels, input_lengths, p_att, p_dec, drop, p_prenet)
-    post = mel + postnet_forward(sd, mel, training, drop, p_conv)
+    post = mel + postnet_forward(sd, mel, training, drop, p_conv, bn_stats)
     pad = ~get_mask_from_lengths(output_lengths, mels.shape[2])          # (B,T) True at padding
     if quirk_inplace_mask:
         mel.data.masked_fill_(pad[:, None, :], 0.0)

@@ -292,19 +292,17 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
 // scratch of the x3 convolutions (weight planes, activation planes, raw tiles of the channel split): slices of one ring, handed out
 // in call order.  A step's sixteen convolutions take ~330 MB; a slice comes round again 1 GB later — long after the launches that
 // used it have retired (convolutions of one stream run in order, a training step ends with a join of its streams).  A captured graph
-// keeps the slices of its nodes.
-static float* cx_scratch(size_t floats) {
-    constexpr size_t RING = (size_t)256 << 20;       // floats (1 GB)
+// keeps the slices of its nodes.  One call may take at most a quarter of the ring (CX_SCRATCH_CAP floats)
+#define CX_SCRATCH_RING ((size_t)256 << 20)      // floats (1 GB)
+#define CX_SCRATCH_CAP (CX_SCRATCH_RING / 4)
+static float* cx_ring() {           // the ring, allocated on first use; nullptr when it cannot be
     static float* ring = nullptr;
-    static std::atomic<size_t> pos{0};
     static std::atomic<int> state{0};
-    floats = (floats + 63) & ~(size_t)63;
-    if (floats > RING / 4) return nullptr;
     if (state.load(std::memory_order_acquire) != 2) {
         int expect = 0;
         if (state.compare_exchange_strong(expect, 1)) {
             float* p = nullptr;
-            if (hipMalloc((void**)&p, RING * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); state.store(0); return nullptr; }
+            if (hipMalloc((void**)&p, CX_SCRATCH_RING * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); state.store(0); return nullptr; }
             ring = p;
             state.store(2, std::memory_order_release);
         } else {
@@ -312,9 +310,47 @@ static float* cx_scratch(size_t floats) {
             if (state.load() != 2) return nullptr;
         }
     }
-    size_t at = pos.fetch_add(floats) % RING;
-    if (at + floats > RING) { pos.store(floats); at = 0; }
+    return ring;
+}
+static float* cx_scratch(size_t floats) {
+    static std::atomic<size_t> pos{0};
+    floats = (floats + 63) & ~(size_t)63;
+    if (floats > CX_SCRATCH_CAP) return nullptr;
+    float* ring = cx_ring();
+    if (!ring) return nullptr;
+    size_t at = pos.fetch_add(floats) % CX_SCRATCH_RING;
+    if (at + floats > CX_SCRATCH_RING) { pos.store(floats); at = 0; }
     return ring + at;
+}
+
+// launch geometry of t2v_conv5_x3_run and the scratch it takes (floats)
+struct CxPlan {
+    int NG, Mp, G, ntile, Tp, nst, ns;
+    size_t w_slots, x_slots, part_floats;
+    long tiles;
+    size_t floats() const { return 4 * (w_slots + x_slots) + part_floats; }
+};
+static int cx_splits(long tiles, int nst);
+static CxPlan cx_plan(int B, int Cin, int T, int M, int np) {
+    CxPlan p;
+    p.NG = np == 3 ? 2 : 4;
+    p.Mp = (M + CX_BM - 1) / CX_BM * CX_BM;
+    p.G = (Cin + 8 * p.NG - 1) / (8 * p.NG) * p.NG;
+    p.ntile = (T + CX_BN - 1) / CX_BN;
+    p.Tp = (p.ntile * CX_BN + CX_XS - CX_BN + 63) / 64 * 64;         // the last tile's DMA reads slots up to ntile * 128 + 8
+    p.w_slots = (size_t)5 * np * p.G * p.Mp;
+    p.x_slots = (size_t)B * np * p.G * p.Tp;
+    p.tiles = (long)B * p.ntile * (p.Mp / CX_BM);
+    p.nst = p.G / p.NG;
+    p.ns = cx_splits(p.tiles, p.nst);
+    p.part_floats = p.ns > 1 ? (size_t)p.ns * p.tiles * CX_BM * CX_BN : 0;
+    return p;
+}
+// can t2v_conv5_x3_run get its scratch for this call?  (the _ok functions ask, so that the BatchNorm partial count and the launch
+// agree: a call the ring cannot serve runs on the fp32 / bf16 tiled kernels instead of failing.  fp32, B = 64, 512 channels: up to
+// T = 1152)
+static bool cx_scratch_ok(int B, int Cin, int T, int M, int np) {
+    return ((cx_plan(B, Cin, T, M, np).floats() + 63) & ~(size_t)63) <= CX_SCRATCH_CAP && cx_ring() != nullptr;
 }
 
 extern "C" int t2v_gemm_f32_set_mode(int x3);
@@ -336,7 +372,7 @@ bool t2v_conv5_x3_ok(int B, int Cin, int T, int Cout, int KS) {
     const int mode = t2v_conv1d_x3_set_mode(-1);
     if (!mode || KS != 5 || Cin % 16 || Cin < 64 || Cout < 64 || B < 1 || T < 1) return false;
     if (mode == 2 && (long)B * ((T + CX_BN - 1) / CX_BN) * ((Cout + CX_BM - 1) / CX_BM) < 192) return false;
-    return t2v_gemm_f32_set_mode(-1) != 0;
+    return t2v_gemm_f32_set_mode(-1) != 0 && cx_scratch_ok(B, Cin, T, Cout, 3);
 }
 int t2v_conv5_x3_stat_blocks(int B, int T) { return B * ((T + CX_BN - 1) / CX_BN); }
 
@@ -364,20 +400,21 @@ bool t2v_conv5_planes_bf16_ok(int B, int Cin, int T, int Cout, int KS) {
     const int mode = t2v_conv1d_x3_set_mode(-1);
     if (!mode || KS != 5 || Cin % 16 || Cin < 64 || Cout < 64 || B < 1 || T < 1) return false;
     if (mode == 2 && (long)B * ((T + CX_BN - 1) / CX_BN) * ((Cout + CX_BM - 1) / CX_BM) < 192) return false;
-    return true;
+    return cx_scratch_ok(B, Cin, T, Cout, 1);
+}
+// which form a k = 5 convolution Cin -> Cout takes, as the entry points decide it (tests assert the path they were written for):
+// 1 = the x3 / one-plane kernels of this file, 0 = the tiled kernels of conv_gemm.hip
+extern "C" int t2v_conv1d_takes_x3(int B, int Cin, int T, int Cout, int KS, int bf16) {
+    return (bf16 ? t2v_conv5_planes_bf16_ok(B, Cin, T, Cout, KS) : t2v_conv5_x3_ok(B, Cin, T, Cout, KS)) ? 1 : 0;
 }
 // W: (M, Cin, 5) weights of the convolution to run (the data gradient passes the flipped, transposed weights); np = 3: fp32 operands
 // as three bf16 planes, np = 1: bf16_run
 int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B, int Cin, int T, int M,
                      hipStream_t stream, int np) {
-    const int NG = np == 3 ? 2 : 4;
-    const int Mp = (M + CX_BM - 1) / CX_BM * CX_BM, G = (Cin + 8 * NG - 1) / (8 * NG) * NG, ntile = (T + CX_BN - 1) / CX_BN;
-    const int Tp = (ntile * CX_BN + CX_XS - CX_BN + 63) / 64 * 64;          // the last tile's DMA reads slots up to ntile * 128 + 8
-    const size_t w_slots = (size_t)5 * np * G * Mp, x_slots = (size_t)B * np * G * Tp;
-    const long tiles = (long)B * ntile * (Mp / CX_BM);
-    const int nst = G / NG, ns = cx_splits(tiles, nst);
-    const size_t part_floats = ns > 1 ? (size_t)ns * tiles * CX_BM * CX_BN : 0;
-    float* scr = cx_scratch(4 * (w_slots + x_slots) + part_floats);
+    const CxPlan pl = cx_plan(B, Cin, T, M, np);
+    const int Mp = pl.Mp, G = pl.G, ntile = pl.ntile, Tp = pl.Tp, nst = pl.nst, ns = pl.ns;
+    const size_t w_slots = pl.w_slots, x_slots = pl.x_slots;
+    float* scr = cx_scratch(pl.floats());          // (the _ok functions checked that it is there)
     if (!scr) return T2V_ERR_LAUNCH;
     uint4* Wp = (uint4*)scr;
     uint4* Xp = Wp + w_slots;

@@ -923,6 +923,8 @@ class DecoderCore(torch.autograd.Function):
     persistent16 = None
     last_kernel = None      # name of the forward kernel of the most recent chunk
     last_bwd_kernel = None
+    chunk_kernels = []      # forward kernel of every chunk of the most recent forward, in batch order (a step can mix them)
+    chunk_bwd_kernels = []  # ... and of the most recent reverse pass
 
     @staticmethod
     def use_persistent16(lib, B, T_in, T):
@@ -1014,6 +1016,7 @@ class DecoderCore(torch.autograd.Function):
             _err_note('decoder forward (persistent kernel hand-off)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
             DecoderCore.last_mode = 'persistent'
             DecoderCore.last_kernel = 'k_dec_train_persist16' if p16 else 'k_dec_train_persist'
+            DecoderCore.chunk_kernels.append(DecoderCore.last_kernel)
             if DecoderCore.keep_last:
                 DecoderCore.last_persist = (PW, Sb, scratch, (B, T_in, T, float(p_att), float(p_dec), int(seed)), raw)
             if need_grad and bwd_prepare and DecoderCore.use_persistent16_bwd(lib, B, T_in, T):
@@ -1053,6 +1056,7 @@ class DecoderCore(torch.autograd.Function):
         _err_note('decoder forward (attention exchange)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
         DecoderCore.last_mode = 'launch-per-step'
         DecoderCore.last_kernel = 'k_lstm_fwd256 + k_attn_fwd'
+        DecoderCore.chunk_kernels.append(DecoderCore.last_kernel)
         return W, Sb, (gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S), None
 
     @staticmethod
@@ -1095,6 +1099,7 @@ class DecoderCore(torch.autograd.Function):
         loc_conv, loc_dense, vv = _f32c(loc_conv.detach()), _f32c(loc_dense.detach()), _f32c(v.detach()).view(-1)
         wcomb = fuse_location_weights(loc_conv, loc_dense)
         chunks = []
+        DecoderCore.chunk_kernels = []
         for b0 in range(0, B, MAX_DEC_B):
             b1 = min(B, b0 + MAX_DEC_B)
             if b0 == 0 and b1 == B:
@@ -1148,6 +1153,7 @@ class DecoderCore(torch.autograd.Function):
         acc = bacc = None
         wg = None
         dga_l, dmem_l, dpm_l, dpre_l = [], [], [], []
+        DecoderCore.chunk_bwd_kernels = []
         b0 = 0
         for ci, keep in enumerate(ctx.chunks):
             gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S = keep
@@ -1252,6 +1258,7 @@ class DecoderCore(torch.autograd.Function):
                     DecoderCore.last_bwd = (W, Sb, Gb, (B, T_in, T, p_att, p_dec, seed),
                                             keep + (dhc_c, DGA, DGD, DQ, DCTX, YD, YA, DCA, DCD, GPREV, GCUM, DV, packs, bias_dec,
                                                     wqT, wcomb, vv))
+            DecoderCore.chunk_bwd_kernels.append(DecoderCore.last_bwd_kernel)
             TB = T * B
             stamp('dec_bwd_end')
             fork = mark()

@@ -39,16 +39,24 @@ def _oracle(dec, memory, mels, lengths, wm, wg):
                                                (2, 300, 4, [300, 211]), (2, 555, 3, [555, 290]), (1, 257, 2, [257]),
                                                (20, 33, 3, list(range(33, 13, -1))), (2, 1000, 2, [1000, 700]),
                                                # very short texts: fewer positions than one 16-position tile / one position
-                                               (2, 5, 3, [5, 1]), (1, 1, 2, [1]), (2, 16, 2, [16, 15])])
-@pytest.mark.parametrize("engine", ["persistent", "launch-per-step"])
+                                               (2, 5, 3, [5, 1]), (1, 1, 2, [1]), (2, 16, 2, [16, 15]),
+                                               # chunks of 16 + 4 / 6 / 7 and 4 x 16 with ragged, descending lengths: under the
+                                               # default selection a 16-item chunk runs launch-per-step, a <= 6-item one persistent
+                                               (20, 33, 3, [max(1, 33 - 2 * i) for i in range(20)]),
+                                               (22, 40, 4, [max(1, 40 - 2 * i) for i in range(22)]),
+                                               (23, 30, 3, [max(1, 30 - i) for i in range(23)]),
+                                               (64, 50, 3, [max(1, 50 - i) for i in range(64)])])
+@pytest.mark.parametrize("engine", ["persistent", "launch-per-step", "default"])
 def test_decoder_core_matches_oracle(B, T_in, T_out, lens, engine, monkeypatch):
     """both forward engines against the oracle: the one-launch persistent kernel (csrc/decoder_train_persist.hip: B <= 6,
-    T_in <= 560) and the launch-per-step loop (any shape); the hand-written BPTT runs on the arena either of them saved"""
+    T_in <= 560) and the launch-per-step loop (any shape); the hand-written BPTT runs on the arena either of them saved.
+    engine "default" (persistent = None): every chunk of <= 16 items picks its own engine, so a batch of 16 + 4 mixes both
+    in one forward pass — asserted chunk by chunk"""
     import t2v_hip
     persistent_ok = B <= 6 and T_in <= 560
     if engine == "persistent" and not persistent_ok:
         pytest.skip("outside the persistent kernel's range: the launch-per-step loop serves this shape")
-    monkeypatch.setattr(t2v_hip.DecoderCore, 'persistent', engine == "persistent")
+    monkeypatch.setattr(t2v_hip.DecoderCore, 'persistent', None if engine == "default" else engine == "persistent")
     hp, M, dec, memory, mels, lengths, wm, wg = _setup(B, T_in, T_out, lens)
     o_mel, o_gate, o_align, o_sd, o_mem = _oracle(dec, memory, mels, lengths, wm, wg)
 
@@ -58,7 +66,13 @@ def test_decoder_core_matches_oracle(B, T_in, T_out, lens, engine, monkeypatch):
     dec.p_decoder_dropout = 0.0
     mem = memory.to(dev).requires_grad_(True)
     mel, gate, align = dec(mem, mels.to(dev), lengths.to(dev))
-    assert t2v_hip.DecoderCore.last_mode == engine
+    if engine == "default":
+        sizes = [min(B, b0 + 16) - b0 for b0 in range(0, B, 16)]
+        assert t2v_hip.DecoderCore.chunk_kernels == ['k_dec_train_persist' if c <= 6 and T_in <= 560 else 'k_lstm_fwd256 + k_attn_fwd'
+                                                     for c in sizes], t2v_hip.DecoderCore.chunk_kernels
+    else:
+        assert t2v_hip.DecoderCore.last_mode == engine
+        assert len(t2v_hip.DecoderCore.chunk_kernels) == (B + 15) // 16
     loss = (mel * wm.to(dev)).sum() + (gate * wg.to(dev)).sum()
     loss.backward()
     torch.cuda.synchronize()

@@ -88,7 +88,14 @@ def test_two_optimizer_steps_match_reference(run):
     gmax = max(np.sqrt(v['digest'][2]) for v in gd.values())
     sd = run['eng'].model.state_dict()
     for k, ref in dig['after_2_steps'].items():
-        if not sd[k].dtype.is_floating_point or 'running_' in k:
+        if not sd[k].dtype.is_floating_point:
+            continue
+        if 'running_' in k:
+            # BatchNorm buffers after two steps: 0.81 * init + 0.09 * s1 + 0.1 * s2, s = a batch statistic.  s1 comes from the
+            # reference's own weights (fp32 round-off, ~1e-5); s2 from the weights after one Adam step, which sit within the
+            # 3e-4 of the weight check below — a mean moves linearly with them (3e-4), a variance quadratically (2 * 3e-4)
+            tol = (3e-4 if 'running_mean' in k else 6e-4) * ref[1] + 1e-6
+            assert abs(_digest(sd[k])[1] - ref[1]) <= tol, (k, _digest(sd[k])[1], ref[1])
             continue
         # Adam's first steps move every element by ~lr whatever the gradient magnitude, so an element whose
         # gradient is at the fp32 noise floor can land 2*lr away; 3e-4 of the digest covers a handful of those
