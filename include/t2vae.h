@@ -614,6 +614,35 @@ int t2v_mel_frontend(const float* wav_f32, const int16_t* wav_i16, const int64_t
                      const int32_t* mel_len, const float* mel_w, int maxw, float* mel_out,
                      int t_stride, void* stream);
 
+/* ------------------------------------------------------------------ STFT / inverse STFT / Griffin-Lim vocoder
+ * stft.STFT and audio_processing.griffin_lim (reference stft.py:77-140, audio_processing.py:52-68) for n_fft = win = 1024,
+ * hop = 256, periodic Hann (T2V_ERR_DIMS otherwise), fp32.  Tables as for t2v_mel_frontend: window (1024), tw512 (512,2),
+ * tw1024 (513,2).  Spectra are (B, 513, t_stride); n_frames[b] (int32, <= t_stride) is utterance b's frame count T_b and
+ * its signal has (T_b - 1) * 256 samples.  Everything past an utterance's length is written as zero.
+ *
+ * t2v_stft_polar: STFT.transform — reflect pad 512, window, |X| and atan2(Im, Re) (0 where X = 0); T_b = n_samples[b]/256 + 1;
+ *   the host refuses n_samples <= 512 as the reference's reflect pad does. */
+int t2v_stft_polar(const float* wav, const int64_t* n_samples, int B, int n_stride, int n_fft, int hop,
+                   const float* window, const float* tw512, const float* tw1024, float* mag, float* phase,
+                   int t_stride, void* stream);
+/* t2v_istft: STFT.inverse — the reference's pinv basis is the inverse real FFT (imaginary parts of bins 0 and 512 ignored);
+ * frames windowed, overlap-added, divided by window_sumsquare where it is > FLT_MIN, 512 samples trimmed at each end.
+ * out: (B, out_stride).  scratch: t2v_istft_scratch_bytes(B, t_stride) bytes of device memory. */
+size_t t2v_istft_scratch_bytes(int B, int t_stride);
+int t2v_istft(const float* mag, const float* phase, const int32_t* n_frames, int B, int t_stride, int n_fft, int hop,
+              const float* window, const float* tw512, const float* tw1024, void* scratch, float* out, int out_stride,
+              void* stream);
+/* t2v_griffin_lim: audio_processing.griffin_lim from the initial `angles` (B, 513, t_stride): one inverse, n_iters fused
+ * iterations (one launch each, no host synchronisation), a final overlap-add.  scratch: t2v_griffin_lim_scratch_bytes. */
+size_t t2v_griffin_lim_scratch_bytes(int B, int t_stride);
+int t2v_griffin_lim(const float* mag, const float* angles, const int32_t* n_frames, int B, int t_stride, int n_fft,
+                    int hop, int n_iters, const float* window, const float* tw512, const float* tw1024, void* scratch,
+                    float* out, int out_stride, void* stream);
+/* t2v_mel_to_magnitude: linear magnitude from a log mel, M = max(P exp(mel), 0) with P = pinv(mel_basis) (513, n_mel)
+ * row-major; mel (B, n_mel, t_stride) -> mag (B, 513, t_stride).  n_mel = 80 only. */
+int t2v_mel_to_magnitude(const float* mel, const float* pinv_basis, const int32_t* n_frames, int B, int t_stride,
+                         int n_mel, float* mag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

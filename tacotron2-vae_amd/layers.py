@@ -4,6 +4,9 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from audio_processing import dynamic_range_compression, dynamic_range_decompression
+from stft import STFT
+
 
 def _xavier(weight, gain_name):
     nn.init.xavier_uniform_(weight, gain=nn.init.calculate_gain(gain_name))
@@ -122,6 +125,8 @@ class TacotronSTFT(nn.Module):
                                  mel_w=rows)
         self._maxw = maxw
         self._dev_tables = {}
+        self.stft_fn = STFT(filter_length, hop_length, win_length)      # no state: state_dict keys stay ['mel_basis']
+        self._pinv = {}
 
     def _tables(self, device):
         key = str(device)
@@ -146,3 +151,22 @@ class TacotronSTFT(nn.Module):
         n = torch.full((yd.size(0),), yd.size(1), dtype=torch.int64) if lengths is None else lengths
         mel = t2v_hip.mel_frontend(yd, n, self._tables(yd.device), scale)
         return mel if src.type == 'cuda' else mel.to(src)
+
+    def spectral_normalize(self, magnitudes):
+        return dynamic_range_compression(magnitudes)
+
+    def spectral_de_normalize(self, magnitudes):
+        return dynamic_range_decompression(magnitudes)
+
+    def mel_to_magnitude(self, mel, lengths=None):
+        """log mel (B, 80, T) -> linear magnitude (B, 513, T) = max(pinv(mel_basis) exp(mel), 0) on the device (the reference
+        has no mel -> linear map; this is the least-squares inverse of the filterbank, clamped at 0).  lengths: optional
+        per-utterance frame counts.  The pseudo-inverse is computed once per device on the host in fp64."""
+        import numpy as np
+        import t2v_hip
+        md = STFT.on_gpu(mel)
+        key = str(md.device)
+        if key not in self._pinv:
+            pinv = np.linalg.pinv(self.mel_basis.detach().cpu().double().numpy())
+            self._pinv[key] = torch.from_numpy(pinv.astype(np.float32)).to(md.device)
+        return t2v_hip.mel_to_magnitude(md, lengths, self._pinv[key]).to(mel.device)

@@ -5,8 +5,9 @@ mel from text conditioned either on a reference utterance or on an emotion-ratio
 Differences by design:
 * the decode loop runs in the HIP inference session (`Decoder.inference`, 4 launches per frame) instead of
   Python-stepping `decode()`; the stepwise API is still there for callers that want it;
-* the vocoder is pluggable: any callable mel(1,80,T) -> waveform.  WaveGlow is an unpinned submodule of the
-  reference and is out of scope here; without a vocoder `synthesize` writes the mel as `<path>.npy`.
+* the vocoder is pluggable: any callable mel(1,80,T) -> waveform, or `vocoder='griffin_lim'` for the built-in
+  GriffinLimVocoder.  WaveGlow is an unpinned submodule of the reference and is out of scope here; without a vocoder
+  `synthesize` writes the mel as `<path>.npy`.
 """
 import os
 
@@ -19,6 +20,20 @@ from text import text_to_sequence
 from utils import load_wav_to_torch
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists
+
+
+class GriffinLimVocoder(object):
+    """mel (B, 80, T) -> waveform (B, (T-1)*256) on the device: `stft.mel_to_magnitude` (pinv of the mel filterbank,
+    clamped at 0) and n_iters Griffin-Lim iterations on `stft.stft_fn` (audio_processing.griffin_lim, initial phase from
+    np.random).  The samples are not clipped: Griffin-Lim's output may exceed +-1 slightly.  Needs T >= 4 frames."""
+
+    def __init__(self, stft, n_iters=60):
+        self.stft, self.n_iters = stft, n_iters
+
+    def __call__(self, mel, lengths=None):
+        from audio_processing import griffin_lim
+        magnitudes = self.stft.mel_to_magnitude(mel, lengths)
+        return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths)
 
 
 class Synthesizer(object):
@@ -55,7 +70,8 @@ class Synthesizer(object):
         """Positional order of the reference (synthesizer.py:74: `load(checkpoint_path, waveglow_path)`, called from
         app.py:161).  waveglow_path: a WaveGlow checkpoint `{'model': module}` exactly as the reference loads it
         (needs the `waveglow` package importable: it is an un-vendored submodule of the reference); `vocoder`: any
-        callable mel (1,80,T) -> audio instead.  A callable passed in the second position is taken as the vocoder."""
+        callable mel (1,80,T) -> audio instead, or 'griffin_lim' for GriffinLimVocoder(self.stft).  A callable passed in
+        the second position is taken as the vocoder."""
         from train import load_model
         self.model = load_model(self.hparams)
         self.model.load_state_dict(torch.load(checkpoint_path, map_location='cpu')['state_dict'])
@@ -72,6 +88,10 @@ class Synthesizer(object):
             if vocoder is None:
                 waveglow = self.waveglow
                 vocoder = lambda mel: waveglow.infer(mel, sigma=0.666)      # reference synthesizer.py:163
+        if isinstance(vocoder, str):
+            if vocoder != 'griffin_lim':
+                raise ValueError("unknown vocoder %r (a callable, or 'griffin_lim')" % vocoder)
+            vocoder = GriffinLimVocoder(self.stft)
         self.vocoder = vocoder
         npz_path = self.centroid_cache_path(checkpoint_path, filelist_path)
         if os.path.exists(npz_path):

@@ -85,7 +85,9 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_decoder_bwd_persist16_scratch_floats', 't2v_decoder_bwd_persist16_dq_offset', 't2v_decoder_bwd_persist16_slices',
            't2v_decoder_bwd_persist16_fits', 't2v_gemm_f32_set_mode', 't2v_conv1d_x3_set_mode', 't2v_gemm_f32_grouped',
            't2v_gemm_f32_grouped_scratch_floats', 't2v_gemm_bf16_grouped', 't2v_gemm_bf16_grouped_scratch_floats',
-           't2v_decoder_bwd_persistent16_prepare', 't2v_decoder_bwd_persistent16_prepared')
+           't2v_decoder_bwd_persistent16_prepare', 't2v_decoder_bwd_persistent16_prepared',
+           't2v_stft_polar', 't2v_istft', 't2v_istft_scratch_bytes', 't2v_griffin_lim', 't2v_griffin_lim_scratch_bytes',
+           't2v_mel_to_magnitude')
 
 
 def lib_path():
@@ -197,6 +199,15 @@ def load_library():
     lib.t2v_decoder_infer_steps.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecInferBufs), C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_void_p]
     vp = C.c_void_p
+    lib.t2v_stft_polar.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+    lib.t2v_istft_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    lib.t2v_istft_scratch_bytes.restype = C.c_size_t
+    lib.t2v_istft.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+    lib.t2v_griffin_lim_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    lib.t2v_griffin_lim_scratch_bytes.restype = C.c_size_t
+    lib.t2v_griffin_lim.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
+                                    vp]
+    lib.t2v_mel_to_magnitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.t2v_conv1d_stat_blocks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_stat_blocks_bf16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -1398,6 +1409,80 @@ def mel_frontend(wav, n_samples, tables, scale=1.0, t_stride=None):
                                 _p(tables['mel_w']), int(tables['maxw']), _p(out), t_stride, _stream()),
            't2v_mel_frontend')
     return out
+
+
+def _frame_counts(n_frames, B, T, device, min_frames=1):
+    """per-utterance frame counts as a device int32 vector (all T when None), checked on the host"""
+    n = torch.full((B,), T, dtype=torch.int64) if n_frames is None else torch.as_tensor(n_frames).reshape(-1).cpu()
+    if n.numel() != B or int(n.min()) < min_frames or int(n.max()) > T:
+        raise ValueError("every utterance needs %d <= frames <= %d, got %s" % (min_frames, T, n.tolist()))
+    return n.to(device=device, dtype=torch.int32)
+
+
+def stft_polar(wav, n_samples, tables, t_stride=None):
+    """STFT.transform on device (csrc/vocoder.hip k_stft_polar).  wav: (B,N) float32 CUDA tensor; n_samples: (B) int64
+    or None (all N).  tables: window / tw512 / tw1024 device tensors (stft.STFT).  Returns magnitude, phase (B,513,T_max)."""
+    lib = _require_gpu(wav)
+    B, N = wav.shape
+    wav = _f32c(wav)
+    n = torch.full((B,), N, dtype=torch.int64) if n_samples is None else torch.as_tensor(n_samples).reshape(-1).cpu()
+    if n.numel() != B or int(n.min()) <= 512 or int(n.max()) > N:
+        # the reference's F.pad(mode='reflect') of n_fft/2 needs more than n_fft/2 samples
+        raise ValueError("stft: every utterance needs 512 < n_samples <= %d, got %s" % (N, n.tolist()))
+    if t_stride is None:
+        t_stride = int(n.max()) // 256 + 1
+    mag = torch.empty(B, 513, t_stride, device=wav.device, dtype=torch.float32)
+    phase = torch.empty_like(mag)
+    _check(lib.t2v_stft_polar(_p(wav), _p(n.to(wav.device)), B, N, 1024, 256, _p(tables['window']), _p(tables['tw512']),
+                              _p(tables['tw1024']), _p(mag), _p(phase), t_stride, _stream()), 't2v_stft_polar')
+    return mag, phase
+
+
+def istft(mag, phase, n_frames, tables):
+    """STFT.inverse on device (k_spec_to_frames + k_ola).  mag, phase: (B,513,T) float32 CUDA tensors; n_frames: (B)
+    frame counts or None (all T).  Returns (B, (T-1)*256), zero past each utterance's (T_b-1)*256 samples."""
+    lib = _require_gpu(mag, phase)
+    B, nb, T = mag.shape
+    if nb != 513 or phase.shape != mag.shape:
+        raise ValueError("istft: magnitude and phase must both be (B, 513, T)")
+    mag, phase = _f32c(mag), _f32c(phase)
+    n = _frame_counts(n_frames, B, T, mag.device)
+    out = torch.empty(B, 256 * (T - 1), device=mag.device, dtype=torch.float32)
+    scratch = torch.empty(lib.t2v_istft_scratch_bytes(B, T), device=mag.device, dtype=torch.uint8)
+    _check(lib.t2v_istft(_p(mag), _p(phase), _p(n), B, T, 1024, 256, _p(tables['window']), _p(tables['tw512']),
+                         _p(tables['tw1024']), _p(scratch), _p(out), out.size(1), _stream()), 't2v_istft')
+    return out
+
+
+def griffin_lim(mag, angles, n_frames, tables, n_iters):
+    """audio_processing.griffin_lim on device: one inverse from `angles`, n_iters fused iterations (k_gl_iter, one launch
+    each, no host synchronisation), final overlap-add.  mag, angles: (B,513,T) float32 CUDA tensors; every utterance needs
+    >= 4 frames (the reflect pad of each iteration's transform).  Returns (B, (T-1)*256), zero past each length."""
+    lib = _require_gpu(mag, angles)
+    B, nb, T = mag.shape
+    if nb != 513 or angles.shape != mag.shape:
+        raise ValueError("griffin_lim: magnitudes and angles must both be (B, 513, T)")
+    mag, angles = _f32c(mag), _f32c(angles)
+    n = _frame_counts(n_frames, B, T, mag.device, min_frames=4)
+    out = torch.empty(B, 256 * (T - 1), device=mag.device, dtype=torch.float32)
+    scratch = torch.empty(lib.t2v_griffin_lim_scratch_bytes(B, T), device=mag.device, dtype=torch.uint8)
+    _check(lib.t2v_griffin_lim(_p(mag), _p(angles), _p(n), B, T, 1024, 256, int(n_iters), _p(tables['window']),
+                               _p(tables['tw512']), _p(tables['tw1024']), _p(scratch), _p(out), out.size(1), _stream()),
+           't2v_griffin_lim')
+    return out
+
+
+def mel_to_magnitude(mel, n_frames, pinv_basis):
+    """max(pinv(mel_basis) exp(mel), 0) on device (k_mel_to_mag).  mel: (B,80,T) float32 CUDA tensor; pinv_basis: (513,80)
+    device tensor.  Returns (B,513,T), zero past each utterance's frame count."""
+    lib = _require_gpu(mel, pinv_basis)
+    B, n_mel, T = mel.shape
+    mel = _f32c(mel)
+    n = _frame_counts(n_frames, B, T, mel.device)
+    mag = torch.empty(B, 513, T, device=mel.device, dtype=torch.float32)
+    _check(lib.t2v_mel_to_magnitude(_p(mel), _p(_f32c(pinv_basis)), _p(n), B, T, n_mel, _p(mag), _stream()),
+           't2v_mel_to_magnitude')
+    return mag
 
 
 class InferenceSession(object):
