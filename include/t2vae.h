@@ -358,6 +358,23 @@ int t2v_decoder_persist_supported(int B, int T_in);
 int t2v_decoder_infer_persistent(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
                                  int t_end, float gate_threshold, float p_prenet, uint64_t seed, void* stream);
 
+/* Per-item variants of both decode loops, for a batch of texts decoded together (model.py Decoder.inference_batch).
+ * The global stop rule is unchanged (every item fired); in addition
+ *   stop_item[b]  receives the first frame on which item b's gate fired (atomicMin; the caller presets INT_MAX);
+ *   item_seeds[b] replaces `seed` for item b, and its Prenet-0/1 dropout masks use the element index of item 0: exactly the
+ *                 mask stream of a B = 1 decode with seed item_seeds[b].
+ * Both pointers are device arrays of B entries and must be set.  The entries without `_items` are unchanged. */
+typedef struct t2v_dec_items {
+    int32_t* stop_item;          /* (B) */
+    const uint64_t* item_seeds;  /* (B) */
+} t2v_dec_items;
+int t2v_decoder_infer_steps_items(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
+                                  int t_begin, int t_end, float gate_threshold, float p_prenet,
+                                  int external_prenet, uint64_t seed, const t2v_dec_items* items, void* stream);
+int t2v_decoder_infer_persistent_items(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
+                                       int t_end, float gate_threshold, float p_prenet, uint64_t seed,
+                                       const t2v_dec_items* items, void* stream);
+
 /* ------------------------------------------------------------------ Conv1d + BatchNorm1d + activation
  * The encoder conv bank (model.py:159-177) and the Postnet (model.py:110-148): stride-1 "same" Conv1d as
  * an implicit GEMM on fp32 MFMA, BatchNorm1d (train: biased batch statistics over B*T incl. padded frames;
@@ -400,6 +417,12 @@ int t2v_bn_act_fwd(const float* y, const float* stat_part, int nblk, const float
                    float* running_mean, float* running_var, float* mean_out, float* rstd_out, float* out,
                    int B, int M, int T, int act, int training, float p_drop, float momentum, float eps,
                    uint64_t seed, uint32_t rng_stream, uint32_t rng_t, void* stream);
+/* eval-mode forward over a ragged batch: out = act(BN(y)) with the running statistics at t < lengths[b] and 0 at every
+ * t >= lengths[b] (lengths: (B) int32 on the device), so that the next convolution of the stack reads each item's tail as
+ * the zero padding of that item convolved alone.  No dropout (eval), one launch like t2v_bn_act_fwd. */
+int t2v_bn_act_fwd_len(const float* y, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, float* out, const int32_t* lengths, int B, int M, int T, int act, float eps,
+                       void* stream);
 int t2v_bn_act_bwd(const float* y, const float* dout, const float* mean, const float* rstd,
                    const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta,
                    float* dconv_bias, int B, int M, int T, int act, float p_drop, uint64_t seed,
@@ -440,6 +463,9 @@ int t2v_colsum(const float* A, long lda, long M, long N, float* scratch, float* 
  * host mirror collects the error words of a step's cooperative kernels with it. */
 int t2v_mask_outputs(float* mel, float* mel_post, float* gate, const int* lengths, int B, int C, int T, float gate_fill,
                      void* stream);
+/* t2v_mask_time: out (B,C,T) = x at t < lengths[b], 0 at t >= lengths[b] (out may be x): the input of a length-masked
+ * conv stack (Encoder.inference / Postnet.forward with lengths). */
+int t2v_mask_time(const float* x, float* out, const int32_t* lengths, int B, int C, int T, void* stream);
 int t2v_reparam_fwd(const float* eps, const float* mu, const float* logvar, float* z, long n, void* stream);
 int t2v_reparam_bwd(const float* dz, const float* eps, const float* logvar, float* dlogvar, long n, void* stream);
 int t2v_gather_words(const void* const* src, void* const* dst, int n, void* stream);

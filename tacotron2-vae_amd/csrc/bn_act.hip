@@ -198,6 +198,34 @@ __global__ __launch_bounds__(256) void k_bn_act_fwd(BnFwdArgs a) {
     }
 }
 
+// Eval-mode forward over a ragged batch (t2v_bn_act_fwd_len): the arithmetic of k_bn_act_fwd's eval branch at t < lengths[b],
+// 0 at every t >= lengths[b] — the zero padding the next convolution of the stack must read.  Grid (M, B): one workgroup per
+// (channel, item) row of T contiguous floats.
+struct BnLenArgs {
+    const float* y; const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+    float* out;
+    const int32_t* lengths;
+    int M, T, act;
+    float eps;
+};
+__global__ __launch_bounds__(256) void k_bn_act_fwd_len(BnLenArgs a) {
+    const int m = blockIdx.x, b = blockIdx.y;
+    const float mean = a.running_mean[m];
+    const float rstd = 1.0f / sqrtf(a.running_var[m] + a.eps);
+    const float g = a.gamma[m] * rstd, bt = a.beta[m] - mean * a.gamma[m] * rstd;
+    const int len = a.lengths[b];
+    const size_t row = ((size_t)b * a.M + m) * a.T;
+    for (int t = threadIdx.x; t < a.T; t += 256) {
+        float z = 0.f;
+        if (t < len) {
+            z = fmaf(a.y[row + t], g, bt);
+            if (a.act == ACT_TANH) z = tanhf_(z);
+            else if (a.act == ACT_RELU) z = fmaxf(z, 0.f);
+        }
+        a.out[row + t] = z;
+    }
+}
+
 struct BnBwdArgs {
     const float* y;          // conv output (B,M,T)
     const float* dout;       // grad wrt the block output (B,M,T)
@@ -473,6 +501,18 @@ extern "C" int t2v_bn_act_fwd(const float* y, const float* stat_part, int nblk, 
         }
     }
     k_bn_act_fwd<<<M, 256, 0, stream>>>(a);
+    return t2v_check_launch();
+}
+
+extern "C" int t2v_bn_act_fwd_len(const float* y, const float* gamma, const float* beta, const float* running_mean,
+                                  const float* running_var, float* out, const int32_t* lengths, int B, int M, int T, int act, float eps,
+                                  void* stream_) {
+    if (!y || !gamma || !beta || !running_mean || !running_var || !out || !lengths || B < 1 || M < 1 || T < 1 || B > 65535)
+        return T2V_ERR_ARG;
+    BnLenArgs a;
+    a.y = y; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var; a.out = out;
+    a.lengths = lengths; a.M = M; a.T = T; a.act = act; a.eps = eps;
+    k_bn_act_fwd_len<<<dim3((unsigned)M, (unsigned)B), 256, 0, (hipStream_t)stream_>>>(a);
     return t2v_check_launch();
 }
 

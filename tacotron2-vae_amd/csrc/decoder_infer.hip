@@ -37,89 +37,18 @@ struct ProjPrenetArgs {
 //   stage 2: Prenet layer 1, one of its 256 rows per wave: polls the 256 granules of every item, ReLU + dropout, PRE[t+1]
 // One in-kernel hop instead of two counter barriers; 2.6 MB of weights per frame spread over 64 CUs.
 #define PP_NWG 64
-__global__ __launch_bounds__(256) void k_proj_prenet(ProjPrenetArgs a) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int gw = blockIdx.x * 4 + wave;                 // global wave index 0..255
-    const int HC = T2V_H + T2V_E;
-    const int nrows = a.pre_next ? T2V_NMEL + 1 + T2V_PRE : T2V_NMEL + 1;
-    // stage-2 operands requested up front: this wave's row of W1 (4 floats per lane)
-    float4 w1r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.pre_next) w1r = *(const float4*)(a.w1 + (size_t)gw * T2V_PRE + 4 * lane);
-    // ---- stage 1: rows gw, gw + 256 (the second pass only for the first 81 waves)
-    for (int o = gw; o < nrows; o += 4 * PP_NWG) {
-        const float4* wr = (const float4*)(a.proj_w + (size_t)o * HC);
-        float4 wv[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) wv[i] = wr[lane + 64 * i];
-        const float bias = a.proj_b[o];
-        bool all_fired = true;
-        for (int b = 0; b < a.B; ++b) {
-            // (the Prenet-0 dropout factor of this row: a counter hash that needs none of the operands below — evaluated while
-            // their loads are in flight, not behind the wave sum; round 6, as in the persistent decode kernel)
-            const float drop0 = o > T2V_NMEL ? t2v_drop_scale(a.seed, T2V_RNG_PRENET0, a.t + 1, (uint32_t)(b * T2V_PRE + (o - (T2V_NMEL + 1))), a.p_prenet) : 0.f;
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const int k = 4 * (lane + 64 * i);               // [h_dec_t (1024) | ctx_t (512)]
-                const float* src = k < T2V_H ? a.xs_next + (size_t)b * T2V_XW + T2V_KATT + k : a.xs_cur + (size_t)b * T2V_XW + k;
-                const float4 xv = *(const float4*)src;
-                acc = fmaf(wv[i].x, xv.x, acc); acc = fmaf(wv[i].y, xv.y, acc);
-                acc = fmaf(wv[i].z, xv.z, acc); acc = fmaf(wv[i].w, xv.w, acc);
-            }
-            acc = wave_sum(acc) + bias;
-            if (o < T2V_NMEL) {
-                if (lane == 0) a.mel_t[(size_t)b * T2V_NMEL + o] = acc;
-            } else if (o == T2V_NMEL) {
-                if (lane == 0) a.gate_t[b] = acc;
-                // stop rule sigmoid(gate) > threshold (model.py:453; B == 1 in the reference): all items must fire.
-                // This wave sees every item's gate in turn, so it can decide alone.
-                all_fired = all_fired && acc > a.gate_logit_thr;
-            } else if (lane == 0) {
-                const int r = o - (T2V_NMEL + 1);
-                float v = fmaxf(acc, 0.f) * drop0;
-                __hip_atomic_store(a.xchg + (size_t)b * T2V_PRE + r, ((t2v_u64)a.epoch << 32) | (t2v_u64)__float_as_uint(v),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (o == T2V_NMEL && lane == 0 && all_fired) atomicMin(a.stop_flag, a.t);
-    }
-    if (!a.pre_next) return;
-    // ---- stage 2: Prenet layer 1, row gw (dropout always on)
-    for (int b = 0; b < a.B; ++b) {
-        const t2v_u64* gq = a.xchg + (size_t)b * T2V_PRE + 4 * lane;
-        const float drop1 = t2v_drop_scale(a.seed, T2V_RNG_PRENET1, a.t + 1, (uint32_t)(b * T2V_PRE + gw), a.p_prenet);      // (in front of the wait)
-        float xv[4];
-        unsigned spins = 0;
-        for (;;) {
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const t2v_u64 x = __hip_atomic_load(gq + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                xv[i] = __uint_as_float((unsigned)x);
-                ok = ok && (unsigned)(x >> 32) == a.epoch;
-            }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > 4000000u || __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return;
-            }
-        }
-        float acc = w1r.x * xv[0];
-        acc = fmaf(w1r.y, xv[1], acc); acc = fmaf(w1r.z, xv[2], acc); acc = fmaf(w1r.w, xv[3], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) {
-            acc = fmaxf(acc, 0.f) * drop1;
-            a.pre_next[(size_t)b * T2V_PRE + gw] = acc;
-        }
-    }
-}
+#define PP_ITEMS 0
+#include "proj_prenet_kernel.inc"
+#undef PP_ITEMS
+#define PP_ITEMS 1
+#include "proj_prenet_kernel.inc"
+#undef PP_ITEMS
 
-extern "C" int t2v_decoder_infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
-                                       int t_begin, int t_end, float gate_threshold, float p_prenet,
-                                       int external_prenet, uint64_t seed, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+static int infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in, int t_begin, int t_end,
+                       float gate_threshold, float p_prenet, int external_prenet, uint64_t seed, const t2v_dec_items* items,
+                       hipStream_t stream) {
     if (!w || !s || B < 1 || B > 8 || T_in < 1 || T_in > T2V_MAX_T_IN || t_begin < 0 || t_end <= t_begin) return T2V_ERR_ARG;
+    if (items && (!items->stop_item || !items->item_seeds)) return T2V_ERR_ARG;
     if (!w->bias_att || !w->bias_dec || !w->wcomb) return T2V_ERR_ARG;
     unsigned* sync = (unsigned*)(s->QP + t2v_qp_sync_off(B));
     t2v_u64* ex = (t2v_u64*)(s->QP + t2v_qp_ex_off(B));
@@ -213,8 +142,23 @@ extern "C" int t2v_decoder_infer_steps(const t2v_dec_weights* w, const t2v_dec_i
         p.xchg = (t2v_u64*)(s->QP + t2v_qp_xchg_off(B));
         p.err = sync + 47;
         p.epoch = (unsigned)t + 1u;
-        k_proj_prenet<<<PP_NWG, 256, 0, stream>>>(p);
+        if (items) k_proj_prenet_items<<<PP_NWG, 256, 0, stream>>>(p, items->stop_item, items->item_seeds);
+        else k_proj_prenet<<<PP_NWG, 256, 0, stream>>>(p);
         DBG(8, "proj_prenet");
     }
     return t2v_check_launch();
+}
+
+extern "C" int t2v_decoder_infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
+                                       int t_begin, int t_end, float gate_threshold, float p_prenet,
+                                       int external_prenet, uint64_t seed, void* stream_) {
+    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, nullptr, (hipStream_t)stream_);
+}
+
+// per-item stop frames and dropout seeds (batched synthesis, include/t2vae.h)
+extern "C" int t2v_decoder_infer_steps_items(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
+                                             int t_begin, int t_end, float gate_threshold, float p_prenet,
+                                             int external_prenet, uint64_t seed, const t2v_dec_items* items, void* stream_) {
+    if (!items) return T2V_ERR_ARG;
+    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, items, (hipStream_t)stream_);
 }

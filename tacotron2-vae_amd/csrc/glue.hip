@@ -26,6 +26,18 @@ extern "C" int t2v_mask_outputs(float* mel, float* mel_post, float* gate, const 
     return t2v_check_launch();
 }
 
+// out (B,C,T) = x at t < lengths[b], else 0 (t2v_mask_time; out may be x): grid (C, B), one row of T per workgroup
+__global__ __launch_bounds__(256) void k_mask_time(const float* x, float* out, const int32_t* __restrict__ lengths, int C, int T) {
+    const int b = blockIdx.y, len = lengths[b];
+    const size_t row = ((size_t)b * C + blockIdx.x) * T;
+    for (int t = threadIdx.x; t < T; t += 256) out[row + t] = t < len ? x[row + t] : 0.f;
+}
+extern "C" int t2v_mask_time(const float* x, float* out, const int32_t* lengths, int B, int C, int T, void* stream_) {
+    if (!x || !out || !lengths || B < 1 || C < 1 || T < 1 || B > 65535) return T2V_ERR_ARG;
+    k_mask_time<<<dim3((unsigned)C, (unsigned)B), 256, 0, (hipStream_t)stream_>>>(x, out, lengths, C, T);
+    return t2v_check_launch();
+}
+
 __global__ void k_reparam_fwd(const float* __restrict__ eps, const float* __restrict__ mu, const float* __restrict__ logvar,
                               float* __restrict__ z, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

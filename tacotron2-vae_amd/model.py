@@ -70,6 +70,24 @@ class Prenet(nn.Module):
         return x
 
 
+def _check_eval_lengths(module, lengths, x):
+    """the int32 device copy of `lengths` for a length-masked eval conv stack; masking is an inference feature"""
+    if module.training:
+        raise RuntimeError("%s: lengths are an eval-mode (inference) argument; training convolves over the padding "
+                           "like the reference" % type(module).__name__)
+    if lengths.numel() != x.size(0):
+        raise ValueError("lengths: %d entries for a batch of %d" % (lengths.numel(), x.size(0)))
+    return lengths_i32(torch.as_tensor(lengths), x.device)
+
+
+def _conv_bn_len(block, x, act, lengths):
+    """act(bn(conv(x))) of one `_conv_bn` block in eval mode, 0 at every t >= lengths[b] (x must be 0 there already)"""
+    conv, bn = block[0].conv, block[1]
+    _block_calls[0] += 1
+    return t2v_hip.conv_bn_act_eval_len(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                        act, lengths)
+
+
 def _conv_bn(cin, cout, k, gain):
     return nn.Sequential(ConvNorm(cin, cout, kernel_size=k, stride=1, padding=(k - 1) // 2, dilation=1,
                                   w_init_gain=gain), nn.BatchNorm1d(cout))
@@ -97,8 +115,16 @@ class Postnet(nn.Module):
         blocks.append(_conv_bn(d, hparams.n_mel_channels, k, 'linear'))
         self.convolutions = nn.ModuleList(blocks)
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """lengths (B,) (eval mode only): a ragged batch of mels — each item's first lengths[b] frames come out as that item
+        convolved alone; the input past each length is ignored and the output there is 0"""
         last = len(self.convolutions) - 1
+        if lengths is not None:
+            lengths = _check_eval_lengths(self, lengths, x)
+            x = t2v_hip.mask_time(x, lengths)
+            for i, block in enumerate(self.convolutions):
+                x = _conv_bn_len(block, x, t2v_hip.ACT_TANH if i < last else t2v_hip.ACT_NONE, lengths)
+            return x
         for i, block in enumerate(self.convolutions):
             x = _conv_bn_act(block, x, t2v_hip.ACT_TANH if i < last else t2v_hip.ACT_NONE, self.training, 32 + i)
         t2v_hip.flush_bn_counters()
@@ -129,7 +155,15 @@ class Encoder(nn.Module):
         x = self._convs(x)
         return self._bilstm(x, lengths_i32(input_lengths, x.device))
 
-    def inference(self, x):
+    def inference(self, x, input_lengths=None):
+        """input_lengths (B,) (eval mode only): a ragged batch of embedded texts (B,512,T) — each item's first
+        input_lengths[b] rows come out as that item encoded alone (the pad symbols' embeddings are not read), 0 past them"""
+        if input_lengths is not None:
+            lengths = _check_eval_lengths(self, input_lengths, x)
+            x = t2v_hip.mask_time(x, lengths)
+            for block in self.convolutions:
+                x = _conv_bn_len(block, x, t2v_hip.ACT_RELU, lengths)
+            return self._bilstm(x.transpose(1, 2), lengths)
         x = self._convs(x)
         lengths = torch.full((x.size(0),), x.size(1), device=x.device, dtype=torch.int32)
         return self._bilstm(x, lengths)
@@ -192,7 +226,7 @@ class Decoder(nn.Module):
                 a.location_layer.location_dense.weight, a.v.weight)
 
     # -- free-running decode ------------------------------------------------------------------
-    def _session(self, memory, mask, max_steps):
+    def _session(self, memory, mask, max_steps, item_seeds=None):
         att, dec, al = self.attention_rnn, self.decoder_rnn, self.attention_layer
         lengths = None if mask is None else (~mask).sum(1).to(device=memory.device, dtype=torch.int32)
         pm = t2v_hip.LinearHIP.apply(memory, al.memory_layer.weight, None, False, 0.0, 0, 0, 0)
@@ -201,7 +235,7 @@ class Decoder(nn.Module):
             dec.weight_hh, dec.bias_ih + dec.bias_hh, al.query_layer.weight,
             al.location_layer.location_conv.conv.weight, al.location_layer.location_dense.weight, al.v.weight,
             self.prenet.layers[0].weight, self.prenet.layers[1].weight, self.linear_projection.weight,
-            self.linear_projection.bias, self.gate_layer.weight, self.gate_layer.bias, max_steps)
+            self.linear_projection.bias, self.gate_layer.weight, self.gate_layer.bias, max_steps, item_seeds)
 
     def initialize_decoder_states(self, memory, mask):
         """reference model.py:260-291 — zero states; stores memory / processed memory / mask."""
@@ -282,6 +316,91 @@ class Decoder(nn.Module):
         mel = s.MEL[:n].permute(1, 2, 0).contiguous()           # (B,80,T)
         gate = s.GATE[:n].transpose(0, 1).unsqueeze(-1).contiguous()   # (B,T,1)
         return mel, gate, s.AL[1:n + 1].transpose(0, 1)
+
+    # -- batched free-running decode (Synthesizer.synthesize_batch) ------------------------------------------------
+    SEED_MASK = 0x7FFFFFFFFFFFFFFF
+
+    def call_seed(self, call):
+        """the Prenet dropout seed of the `call`-th inference() of this decoder (1-based)"""
+        return (int(self.dropout_seed) * 1000003 + int(call)) & self.SEED_MASK
+
+    def reserve_seeds(self, n):
+        """the seeds of the next n inference() calls, in order; bumps the call counter by n"""
+        seeds = [self.call_seed(self._calls + 1 + i) for i in range(n)]
+        self._calls += n
+        return seeds
+
+    def inference_batch(self, memory, memory_lengths, seeds=None, chunk=32, persistent=None):
+        """Decode B texts of different lengths together; item b comes out as `inference(memory[b:b+1, :L_b])` would give it
+        with Prenet dropout seed seeds[b] (default: the seeds of the next B inference() calls, in item order — so a batch
+        equals B sequential inference() calls).  Returns (mel (B,80,N), gate (B,N,1), alignments (B,N,T_in),
+        n_frames (B,) int64 on the host), N = max n_frames; past n_frames[b]: mel 0, gate logit 1e3, alignment 0.
+        The items are sorted by length and decoded in groups of at most 8 (one decode session each, attention masked to
+        each item's length, a group runs until all of its gates fired); each group on the persistent kernel when it fits."""
+        B, T_in = memory.size(0), memory.size(1)
+        lens = [int(x) for x in torch.as_tensor(memory_lengths).cpu().tolist()]
+        if len(lens) != B or min(lens) < 1 or max(lens) > T_in:
+            raise ValueError("memory_lengths must hold B = %d lengths in [1, %d]" % (B, T_in))
+        if seeds is None:
+            seeds = self.reserve_seeds(B)
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != B:
+            raise ValueError("seeds: %d seeds for %d utterances" % (len(seeds), B))
+        order = sorted(range(B), key=lambda b: -lens[b])
+        items = [None] * B
+        for g0 in range(0, B, 8):
+            idx = order[g0:g0 + 8]
+            L = max(lens[b] for b in idx)
+            sel = torch.as_tensor(idx, device=memory.device)
+            outs = self._decode_group(memory.index_select(0, sel)[:, :L].contiguous(), [lens[b] for b in idx],
+                                      [seeds[b] for b in idx], chunk, persistent)
+            for b, o in zip(idx, outs):
+                items[b] = o
+        N = max(o[0].size(1) for o in items)
+        mel = memory.new_zeros(B, self.n_mel_channels, N)
+        gate = memory.new_full((B, N, 1), 1e3)
+        al = memory.new_zeros(B, N, T_in)
+        for b, (m, g, a) in enumerate(items):
+            n = m.size(1)
+            mel[b, :, :n] = m
+            gate[b, :n, 0] = g
+            al[b, :n, :a.size(1)] = a
+        return mel, gate, al, torch.tensor([o[0].size(1) for o in items], dtype=torch.int64)
+
+    def _decode_group(self, memory, lens, seeds, chunk, persistent):
+        """one decode session over <= 8 items; returns per item (mel (80,n), gate (n,), alignments (n,T_in))"""
+        lengths = torch.tensor(lens, dtype=torch.int32).to(memory.device)
+        mask = torch.arange(memory.size(1), device=memory.device)[None, :] >= lengths[:, None]
+        s = self._session(memory, mask, self.max_decoder_steps, item_seeds=seeds)
+        s.PRE[0].copy_(self.prenet(self.get_go_frame(memory)))
+        done, t = False, 0
+        if persistent is None:
+            persistent = os.environ.get('T2V_DECODE_PERSISTENT', '1') != '0'
+        if persistent and s.persistent_supported():
+            s.run_persistent(self.gate_threshold, drop_rate, 0)
+            int(s.stop.item())
+            if s.persistent_timed_out():
+                print("Warning! persistent decode kernel could not be co-scheduled; using the launch-per-stage loop")
+                s.reset_for_rerun()
+            else:
+                t2v_hip.check_async_errors()
+                done = True
+        while not done and t < s.max_steps:
+            t1 = min(s.max_steps, t + chunk)
+            s.run(t, t1, self.gate_threshold, drop_rate, False, 0)
+            if int(s.stop.item()) < t1:
+                break
+            t = t1
+        stops = s.stop_item.cpu().tolist()
+        out = []
+        for j, st in enumerate(stops):
+            if st < s.max_steps:
+                n = st + 1
+            else:
+                print("Warning! Reached max decoder steps")
+                n = s.max_steps
+            out.append((s.MEL[:n, j].t(), s.GATE[:n, j], s.AL[1:n + 1, j]))
+        return out
 
     def _tf_rng_t(self):
         """mask index of the teacher-forced Prenet call: set per model forward by Tacotron2._forward (None = the running

@@ -35,6 +35,20 @@ class GriffinLimVocoder(object):
         magnitudes = self.stft.mel_to_magnitude(mel, lengths)
         return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths)
 
+    def batch(self, mel, lengths):
+        """A ragged batch in one set of launches, item by item as `self(mel[b:b+1, :, :lengths[b]])` would give it: the
+        initial phases are drawn from np.random per item, in item order, with shape (1, 513, lengths[b]) — what B calls in
+        a row draw.  Returns a list of B waveforms ((lengths[b]-1)*256 samples each) on the device."""
+        from audio_processing import griffin_lim
+        n = [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
+        B, T = mel.size(0), mel.size(2)
+        angles = np.zeros((B, 513, T), dtype=np.float32)
+        for b, nb in enumerate(n):
+            angles[b, :, :nb] = np.angle(np.exp(2j * np.pi * np.random.rand(1, 513, nb)))[0]
+        magnitudes = self.stft.mel_to_magnitude(mel, n)
+        wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, angles=torch.from_numpy(angles), lengths=n)
+        return [wav[b, :(nb - 1) * 256] for b, nb in enumerate(n)]
+
 
 class Synthesizer(object):
     def __init__(self, hparams=None):
@@ -140,10 +154,129 @@ class Synthesizer(object):
         mel_outputs_postnet = mel_outputs + self.model.postnet(mel_outputs)
         if path is not None:
             if self.vocoder is not None:
-                from scipy.io.wavfile import write
-                audio = self.vocoder(mel_outputs)
-                audio = audio[0] if torch.is_tensor(audio) and audio.dim() > 1 else audio
-                write(path, self.hparams.sampling_rate, np.asarray(torch.as_tensor(audio).detach().cpu().float()))
+                self._write_wav(path, self.vocoder(mel_outputs))
             else:
                 np.save(path + '.npy', mel_outputs_postnet[0].detach().cpu().numpy())
         return mel_outputs_postnet, alignments
+
+    def _write_wav(self, path, audio):
+        from scipy.io.wavfile import write
+        audio = audio[0] if torch.is_tensor(audio) and audio.dim() > 1 else audio
+        write(path, self.hparams.sampling_rate, np.asarray(torch.as_tensor(audio).detach().cpu().float()))
+
+    @torch.no_grad()
+    def synthesize_batch(self, texts, paths=None, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0)):
+        """`synthesize` for several texts at once: returns the list of what `synthesize(texts[i], paths[i], ...)` called
+        for i = 0, 1, ... in turn would return from the same model state — frame counts, mels, alignments and Prenet dropout
+        masks (the decoder reserves the seeds of len(texts) consecutive inference() calls), and, with the Griffin-Lim
+        vocoder and the same np.random state, the same waveforms.  The texts run through the encoder, the decoder (groups
+        of <= 8, sorted by length) and the Postnet as one ragged batch; each is masked to its own length.
+        ratios: one (neu, sad, hap, ang) tuple for all texts, or one per text; ref_audios: one path per text
+        (condition_on_ref); paths: None or one output path per text (wav through the vocoder, else `<path>.npy`)."""
+        B = len(texts)
+        if B == 0:
+            return []
+        if paths is not None and len(paths) != B:
+            raise ValueError("paths: %d paths for %d texts" % (len(paths), B))
+        if condition_on_ref and (ref_audios is None or len(ref_audios) != B):
+            raise ValueError("condition_on_ref needs one reference audio per text")
+        if len(ratios) and not np.isscalar(ratios[0]):
+            if len(ratios) != B:
+                raise ValueError("ratios: %d tuples for %d texts" % (len(ratios), B))
+            per_text = list(ratios)
+        else:
+            per_text = [ratios] * B
+        seqs = [text_to_sequence(t, ['korean_cleaners']) for t in texts]
+        lens = [len(q) for q in seqs]
+        if min(lens) < 1:
+            raise ValueError("a text maps to no symbols")
+        ids = np.zeros((B, max(lens)), dtype=np.int64)        # pad id 0: masked out by the encoder, never read
+        for b, q in enumerate(seqs):
+            ids[b, :len(q)] = q
+        ids = torch.from_numpy(ids).cuda()
+        lengths = torch.tensor(lens, dtype=torch.int32).cuda()
+        embedded = self.model.transcript_embedding(self.model.parse_input(ids)).transpose(1, 2)
+        transcript_outputs = self.model.encoder.inference(embedded, lengths)              # (B, L, 512), 0 past each length
+        styles = [self.style_vector(transcript_outputs[b:b + 1, :lens[b]], condition_on_ref,
+                                    ref_audios[b] if condition_on_ref else None, per_text[b]) for b in range(B)]
+        encoder_outputs = torch.cat([transcript_outputs[b:b + 1] + styles[b].reshape(1, -1, styles[b].size(-1))[:, :1]
+                                     for b in range(B)], 0)
+        mel, _, alignments, n_frames = self.model.decoder.inference_batch(encoder_outputs, lens)
+        mel_postnet = mel + self.model.postnet(mel, n_frames.to(torch.int32).cuda())
+        n = n_frames.tolist()
+        out = [(mel_postnet[b:b + 1, :, :n[b]], alignments[b:b + 1, :n[b], :lens[b]]) for b in range(B)]
+        if paths is not None:
+            if self.vocoder is None:
+                for b in range(B):
+                    np.save(paths[b] + '.npy', out[b][0][0].detach().cpu().numpy())
+            elif isinstance(self.vocoder, GriffinLimVocoder):
+                for b, audio in enumerate(self.vocoder.batch(mel, n)):
+                    self._write_wav(paths[b], audio)
+            else:
+                for b in range(B):
+                    self._write_wav(paths[b], self.vocoder(mel[b:b + 1, :, :n[b]]))
+        return out
+
+
+# ---------------------------------------------------------------------- command line
+DEFAULT_BATCH_SIZE = 8
+
+
+def build_arg_parser():
+    """The reference's flags where they exist (synthesizer.py:171-179: --load_path, --sample_path, --text) and the batched
+    front end's own."""
+    import argparse
+    p = argparse.ArgumentParser(description="text -> <sample_path>/<i>.wav (or <i>.npy mels without a vocoder)")
+    p.add_argument('--load_path', required=True, help="checkpoint written by train.py")
+    p.add_argument('--sample_path', default="samples")
+    p.add_argument('--text', action='append', default=[], help="a sentence (repeatable)")
+    p.add_argument('--text_file', default=None, help="one sentence per line (after the --text sentences)")
+    p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="texts per synthesize_batch call")
+    p.add_argument('--vocoder', choices=['griffin_lim'], default=None, help="without it the post-net mels are written")
+    p.add_argument('--ratios', default='1,0,0,0', help="emotion mix neu,sad,hap,ang")
+    p.add_argument('--ref_audio', default=None, help="condition every text on this reference wav instead of --ratios")
+    p.add_argument('--filelist_path', default='./web/static/uploads/koemo_spk_emo_all_test.txt',
+                   help="reference utterances of the emotion centroids (or their cache next to the checkpoint)")
+    p.add_argument('--hparams', default='', help="comma separated name=value overrides")
+    return p
+
+
+def parse_args(argv=None):
+    args = build_arg_parser().parse_args(argv)
+    ratios = tuple(float(x) for x in args.ratios.split(','))
+    if len(ratios) != 4:
+        raise SystemExit("--ratios takes four comma separated numbers, got %r" % args.ratios)
+    args.ratios = ratios
+    if args.batch_size < 1:
+        raise SystemExit("--batch_size must be >= 1")
+    texts = list(args.text)
+    if args.text_file:
+        with open(args.text_file, encoding='utf-8') as f:
+            texts += [line.strip() for line in f if line.strip()]
+    if not texts:
+        raise SystemExit("no text: give --text and/or --text_file")
+    args.texts = texts
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    hp = create_hparams()
+    hp.sampling_rate = 16000                 # the reference's Synthesizer() overrides (synthesizer.py:47-51)
+    hp.max_decoder_steps = 600
+    if args.hparams:
+        hp.parse(args.hparams)
+    syn = Synthesizer(hp).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
+    os.makedirs(args.sample_path, exist_ok=True)
+    texts = args.texts
+    for i0 in range(0, len(texts), args.batch_size):
+        chunk = texts[i0:i0 + args.batch_size]
+        paths = [os.path.join(args.sample_path, str(i0 + j) + ('.wav' if syn.vocoder is not None else '')) for j in range(len(chunk))]
+        syn.synthesize_batch(chunk, paths, args.ref_audio is not None,
+                             [args.ref_audio] * len(chunk) if args.ref_audio else None, args.ratios)
+        for p in paths:
+            print(p if syn.vocoder is not None else p + '.npy')
+
+
+if __name__ == "__main__":
+    main()

@@ -66,6 +66,11 @@ class _DecInferBufs(C.Structure):
         'prenet_w1', 'proj_w', 'proj_b')]
 
 
+class _DecItems(C.Structure):
+    C_NAME = 't2v_dec_items'
+    _fields_ = [(n, C.c_void_p) for n in ('stop_item', 'item_seeds')]
+
+
 EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_pack_lstm_weights', 't2v_pack_lstm_weights_bf16', 't2v_decoder_train_fwd',
            't2v_decoder_train_bwd', 't2v_clip_adam_step', 't2v_clip_adam_step_guarded', 't2v_decoder_replay_fwd_kernels', 't2v_mel_frontend', 't2v_set_phase_profile', 't2v_decoder_infer_steps', 't2v_conv1d_stat_blocks', 't2v_conv1d_stat_blocks_bf16', 't2v_conv1d_fwd', 't2v_conv1d_bwd', 't2v_conv1d_fwd_bf16', 't2v_conv1d_bwd_bf16', 't2v_conv1d_dw_scratch_floats', 't2v_conv1d_flip_weights', 't2v_gemm_bf16', 't2v_gemm_bf16_splitk', 't2v_gemm_bf16_splitk_scratch_floats', 't2v_attn_wgrad', 't2v_attn_wgrad_scratch_floats',
            't2v_bn_act_fwd', 't2v_bn_act_bwd', 't2v_bn_act_bwd_eval', 't2v_bilstm_fwd', 't2v_bilstm_bwd', 't2v_gemm_f32', 't2v_conv2d_s2_fwd', 't2v_conv2d_s2_bwd', 't2v_conv2d_s2_dw_scratch_floats', 't2v_conv2d_s2_fwd_gemm', 't2v_conv2d_s2_bwd_gemm',
@@ -87,7 +92,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_gemm_f32_grouped_scratch_floats', 't2v_gemm_bf16_grouped', 't2v_gemm_bf16_grouped_scratch_floats',
            't2v_decoder_bwd_persistent16_prepare', 't2v_decoder_bwd_persistent16_prepared',
            't2v_stft_polar', 't2v_istft', 't2v_istft_scratch_bytes', 't2v_griffin_lim', 't2v_griffin_lim_scratch_bytes',
-           't2v_mel_to_magnitude')
+           't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
+           't2v_mask_time')
 
 
 def lib_path():
@@ -193,11 +199,14 @@ def load_library():
     lib.t2v_debug_spin.argtypes = [C.c_int, C.c_int, C.c_void_p]
     lib.t2v_decoder_infer_persistent.argtypes = [C.POINTER(_DecPersistWeights), C.POINTER(_DecPersistBufs), C.c_int, C.c_int,
                                                  C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
+    lib.t2v_decoder_infer_persistent_items.argtypes = lib.t2v_decoder_infer_persistent.argtypes[:-1] + [C.POINTER(_DecItems),
+                                                                                                        C.c_void_p]
     lib.t2v_decoder_persist_supported.argtypes = [C.c_int, C.c_int]
     lib.t2v_decoder_persist_scratch_floats.argtypes = [C.c_int, C.c_int]
     lib.t2v_decoder_persist_scratch_floats.restype = C.c_long
     lib.t2v_decoder_infer_steps.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecInferBufs), C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_void_p]
+    lib.t2v_decoder_infer_steps_items.argtypes = lib.t2v_decoder_infer_steps.argtypes[:-1] + [C.POINTER(_DecItems), C.c_void_p]
     vp = C.c_void_p
     lib.t2v_stft_polar.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
     lib.t2v_istft_scratch_bytes.argtypes = [C.c_int, C.c_int]
@@ -221,6 +230,8 @@ def load_library():
     lib.t2v_bn_act_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                    C.c_uint64, C.c_uint32, C.c_uint32, vp]
     lib.t2v_bn_act_bwd_eval.argtypes = lib.t2v_bn_act_bwd.argtypes
+    lib.t2v_bn_act_fwd_len.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]
+    lib.t2v_mask_time.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.t2v_bilstm_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.t2v_bilstm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.t2v_gemm_f32.argtypes = [vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp, vp, C.c_int, C.c_int, C.c_int,
@@ -1491,7 +1502,7 @@ class InferenceSession(object):
     INT_MAX = 2 ** 31 - 1
 
     def __init__(self, memory, pm, lengths, w_ih_att, w_hh_att, b_att, w_ih_dec, w_hh_dec, b_dec, wq, loc_conv,
-                 loc_dense, v, prenet_w0, prenet_w1, proj_w, proj_b, gate_w, gate_b, max_steps):
+                 loc_dense, v, prenet_w0, prenet_w1, proj_w, proj_b, gate_w, gate_b, max_steps, item_seeds=None):
         if 'T2V_HOST_THREADS' in os.environ:        # (an inference session no longer throttles the host application)
             limit_host_threads()
         lib = _require_gpu(memory, pm, w_ih_att)
@@ -1529,6 +1540,17 @@ class InferenceSession(object):
         self.GATE = torch.empty(T, B, **f32)
         self.stop = torch.full((1,), self.INT_MAX, device=dev, dtype=torch.int32)
         self.t = 0
+        # item_seeds (B ints): per-item Prenet dropout seeds — item b's masks are those of a B = 1 decode with seed
+        # item_seeds[b] — and per-item stop frames (stop_item[b]: first frame on which item b's gate fired, INT_MAX if none)
+        self.item_seeds = self.stop_item = self._items = None
+        if item_seeds is not None:
+            if len(item_seeds) != B:
+                raise T2VHipError("item_seeds: %d seeds for %d utterances" % (len(item_seeds), B))
+            seeds = [int(x) & 0xFFFFFFFFFFFFFFFF for x in item_seeds]
+            seeds = [x - (1 << 64) if x >= (1 << 63) else x for x in seeds]            # the bits as a signed int64
+            self.item_seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
+            self.stop_item = torch.full((B,), self.INT_MAX, device=dev, dtype=torch.int32)
+            self._items = _DecItems(_p(self.stop_item), _p(self.item_seeds))
 
     def _stage_arena(self):
         if self.S is not None:
@@ -1560,6 +1582,12 @@ class InferenceSession(object):
                                _p(self.wq), _p(self.wcomb), _p(self.v), _p(self.proj_w), _p(self.proj_b), _p(self.w1))
         Bf = _DecPersistBufs(_p(self.memory), _p(self.pm), _p(self.lengths), _p(self.PRE[0]), _p(self.MEL), _p(self.GATE),
                              _p(self.AL), _p(self.stop), _p(self._gran), _p(self._perr))
+        if self._items is not None:
+            _check(lib.t2v_decoder_infer_persistent_items(C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
+                                                          float(gate_threshold), float(p_prenet), int(seed),
+                                                          C.byref(self._items), _stream()),
+                   't2v_decoder_infer_persistent_items')
+            return
         _check(lib.t2v_decoder_infer_persistent(C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
                                                 float(gate_threshold), float(p_prenet), int(seed), _stream()),
                't2v_decoder_infer_persistent')
@@ -1573,6 +1601,8 @@ class InferenceSession(object):
         """after a failed persistent run: the launch-per-stage loop starts again from the zero state (rows 0 of the state
         arenas are still zero — the persistent kernel keeps its state on chip — and PRE[0] still holds Prenet(go frame))"""
         self.stop.fill_(self.INT_MAX)
+        if self.stop_item is not None:
+            self.stop_item.fill_(self.INT_MAX)
         self._perr.zero_()
 
     def run(self, t0, t1, gate_threshold, p_prenet, external_prenet, seed):
@@ -1582,6 +1612,13 @@ class InferenceSession(object):
                                                                         False)
             self.W = _DecWeights(_p(self.packF_att), _p(self.packF_dec), None, None, _p(self.b_att), _p(self.b_dec),
                                  _p(self.wqT), _p(self.wcomb), _p(self.v))
+        if self._items is not None:
+            _check(load_library().t2v_decoder_infer_steps_items(C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0),
+                                                                int(t1), float(gate_threshold), float(p_prenet),
+                                                                int(bool(external_prenet)), int(seed), C.byref(self._items),
+                                                                _stream()),
+                   't2v_decoder_infer_steps_items')
+            return
         _check(load_library().t2v_decoder_infer_steps(C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0),
                                                       int(t1), float(gate_threshold), float(p_prenet),
                                                       int(bool(external_prenet)), int(seed), _stream()),
@@ -1776,6 +1813,39 @@ def mask_outputs(mel, mel_post, gate, lengths_i32, gate_fill=1e3):
     B, Cn, T = mel.shape
     _check(lib.t2v_mask_outputs(_p(mel), _p(mel_post), _p(gate), _p(lengths_i32), B, Cn, T, float(gate_fill), _stream()),
            't2v_mask_outputs')
+
+
+def mask_time(x, lengths_i32):
+    """(B,C,T) -> a new tensor equal to x at t < lengths[b] and 0 past it (one launch): the input of a length-masked conv stack"""
+    lib = _require_gpu(x, lengths_i32)
+    assert x.dim() == 3 and lengths_i32.dtype == torch.int32 and lengths_i32.numel() == x.size(0)
+    x = _f32c(x)
+    out = torch.empty_like(x)
+    B, Cn, T = x.shape
+    _check(lib.t2v_mask_time(_p(x), _p(out), _p(lengths_i32), B, Cn, T, _stream()), 't2v_mask_time')
+    return out
+
+
+def conv_bn_act_eval_len(x, weight, bias, gamma, beta, running_mean, running_var, act, lengths_i32):
+    """act(BatchNorm1d_eval(Conv1d(x))) over a ragged batch, 0 at every t >= lengths[b]: x must already be 0 there, so each
+    item's valid frames are those of the item convolved alone (its zero padding).  No autograd (inference only)."""
+    lib = _require_gpu(x, weight, lengths_i32)
+    assert lengths_i32.dtype == torch.int32 and lengths_i32.numel() == x.size(0)
+    x = _f32c(x)
+    B, Cin, T = x.shape
+    Cout, _, KS = weight.shape
+    y = torch.empty(B, Cout, T, device=x.device, dtype=torch.float32)
+    w = _f32c(weight.detach())
+    if _BF16 and KS == 5 and Cin % 16 == 0 and Cin >= 128 and Cout >= 128:      # the kernel ConvBNAct1d picks
+        wp = torch.empty(w.numel(), device=x.device, dtype=torch.bfloat16)
+        _check(lib.t2v_conv1d_fwd_bf16(_p(w), _p(x), _p(bias), _p(y), None, _p(wp), B, Cin, T, Cout, KS, _stream()),
+               't2v_conv1d_fwd_bf16')
+    else:
+        _check(lib.t2v_conv1d_fwd(_p(w), _p(x), _p(bias), _p(y), None, B, Cin, T, Cout, KS, _stream()), 't2v_conv1d_fwd')
+    out = torch.empty_like(y)
+    _check(lib.t2v_bn_act_fwd_len(_p(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(out), _p(lengths_i32),
+                                  B, Cout, T, int(act), 1e-5, _stream()), 't2v_bn_act_fwd_len')
+    return out
 
 
 class Reparam(torch.autograd.Function):
