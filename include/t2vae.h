@@ -600,6 +600,26 @@ int t2v_gru_fwd(const float* gi, const float* whh, const float* bhh, float* hs, 
                 uint32_t* sync2, int B, int T, void* stream);
 int t2v_gru_bwd(const float* whh, const float* hs, const float* gsave, const float* dh_last, float* dgi,
                 float* dgh, float* xchg, uint32_t* sync2, int B, int T, void* stream);
+
+/* Ragged inference instances (eval only, no backward): item b of a padded batch comes out as if run alone.
+ * hlen (B, int32, device): item b's input height; H = the padded height (>= every hlen[b]).  Rows h >= hlen[b] are item b's
+ * zero padding and are never read; with coord the xx channel is normalised by hlen[b] - 1.  x_tstride == 0: x is (B, Cx, H, W).
+ * x_tstride > 0 (layer 0, Cx == 1, x_tstride >= H): x is the padded mel (B, W, x_tstride) and item b's (hlen[b], W) image is the
+ * reinterpretation of its own contiguous (W, hlen[b]) block (modules.py:67), gathered in place: element (h, w) is
+ * x[b][f / hlen[b]][f % hlen[b]], f = h*W + w.  Output rows past (hlen[b] - 1) / 2 + 1 are left with values nobody should read.
+ * T2V_ERR_ARG for a null pointer (hlen included), bad sizes, or x_tstride with Cx != 1 or x_tstride < H.  The per-item
+ * heights are the caller's to check on the host (2 <= hlen[b] <= H with coord); the kernels clamp them to H, so no length
+ * addresses outside x.  The GEMM form's scratch: t2v_conv2d_s2_gemm_ragged_scratch_floats(...) floats (the im2col matrix). */
+int t2v_conv2d_s2_fwd_ragged(const float* x, const float* w, const float* bias, float* y, const int32_t* hlen, int B, int Cx,
+                             int H, int W, int Cout, int coord, int x_tstride, void* stream);
+long t2v_conv2d_s2_gemm_ragged_scratch_floats(int B, int Cx, int H, int W, int Cout, int coord);
+int t2v_conv2d_s2_fwd_gemm_ragged(const float* x, const float* w, const float* bias, float* y, float* scratch,
+                                  const int32_t* hlen, int B, int Cx, int H, int W, int Cout, int coord, int x_tstride,
+                                  void* stream);
+/* t2v_gru_fwd plus h_last (B,256): h_last[b] = hs[b, steps[b]], written inside the recurrence.  steps (B, int32, device),
+ * each in 1..T (checked by the caller; an item outside that range gets no h_last row).  gsave may be NULL. */
+int t2v_gru_fwd_len(const float* gi, const float* whh, const float* bhh, float* hs, float* gsave, float* xchg,
+                    uint32_t* sync2, const int32_t* steps, float* h_last, int B, int T, void* stream);
 int t2v_loss_fwd_bwd(const float* mel, const float* post, const float* mel_t, const float* gate,
                      const float* gate_t, const float* mu, const float* logvar, float* dmel, float* dpost,
                      float* dgate, float* dmu, float* dlogvar, float* part192, float* out4, uint32_t* ticket,

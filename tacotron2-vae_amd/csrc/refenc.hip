@@ -1,6 +1,7 @@
 // Reference-encoder building blocks (reference modules.py:34-85, CoordConv.py:37-74,142-161):
 //   k_conv2d_s2_{fwd,dx,dw} : Conv2d 3x3, stride 2, pad 1 (direct form — the six layers total 0.28 GMAC),
 //                             with the CoordConv coordinate channels generated on the fly for layer 1
+//   *_ragged, k_gru_fwd_len : the inference instances over a ragged batch, each item as if alone (refenc_fwd.inc)
 //   k_gru_{fwd,bwd}         : nn.GRU(256 -> 256) recurrence over the <= 16 frames that survive 6 stride-2
 //                             convs (input projections are a time-batched GEMM outside)
 //   k_loss                  : Tacotron2Loss_VAE forward + gradient in one pass (loss_function.py:27-44)
@@ -32,25 +33,69 @@ __device__ __forceinline__ float refenc_in(const Conv2dArgs& a, int b, int c, in
     return sqrtf((xx - 0.5f) * (xx - 0.5f) + (yy - 0.5f) * (yy - 0.5f));
 }
 
-// grid = (tiles of Ho*Wo, B*Cout): the filter of this output channel sits in LDS (broadcast reads)
-__global__ __launch_bounds__(256) void k_conv2d_s2_fwd(Conv2dArgs a) {
-    __shared__ float wsh[131 * 9];
-    const int Cin = a.Cx + (a.coord ? 3 : 0);
-    const int b = blockIdx.y / a.Cout, co = blockIdx.y % a.Cout;
-    for (int i = threadIdx.x; i < Cin * 9; i += 256) wsh[i] = a.w[(size_t)co * Cin * 9 + i];
-    __syncthreads();
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= a.Ho * a.Wo) return;
-    const int ho = r / a.Wo, wo = r - ho * a.Wo;
-    float acc = a.bias ? a.bias[co] : 0.f;
-    for (int c = 0; c < Cin; ++c)
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw)
-                acc = fmaf(wsh[c * 9 + kh * 3 + kw], refenc_in(a, b, c, 2 * ho - 1 + kh, 2 * wo - 1 + kw), acc);
-    a.y[((size_t)b * a.Cout + co) * a.Ho * a.Wo + r] = acc;
+
+// The ragged inference instance: item b's input has its own height hlen[b] <= a.H.  Rows at h >= hlen[b] are
+// its zero padding (so whatever a previous layer left there is never read), and the CoordConv xx channel is normalised by
+// hlen[b] - 1, as for the item run alone.  tstride > 0 (layer 0, Cx == 1): x is the padded mel (B, a.W, tstride) and the
+// (hlen[b], a.W) image is the reinterpretation of the item's own contiguous (a.W, hlen[b]) block (modules.py:67): element
+// (h, w) is mel[b][f / hlen[b]][f % hlen[b]] with f = h * a.W + w — nothing at t >= hlen[b] is read.
+struct RaggedSrc {
+    const int* hlen;     // (B) per-item input heights, on the device
+    int tstride;         // 0: x is (B, Cx, H, W); > 0: layer-0 gather from the (B, W, tstride) mel
+};
+
+__device__ __forceinline__ float refenc_in_ragged(const Conv2dArgs& a, const RaggedSrc& r, int b, int c, int h, int w) {
+    const int hb = min(r.hlen[b], a.H);            // clamped: a bad length can never address past the tensor
+    if (h < 0 || h >= hb || w < 0 || w >= a.W) return 0.f;
+    if (c < a.Cx) {
+        if (r.tstride > 0) {
+            const int f = h * a.W + w;
+            return a.x[((size_t)b * a.W + f / hb) * r.tstride + f % hb];
+        }
+        return a.x[(((size_t)b * a.Cx + c) * a.H + h) * a.W + w];
+    }
+    const float xx = (float)h / (float)(hb - 1) * 2.f - 1.f;
+    const float yy = (float)w / (float)(a.W - 1) * 2.f - 1.f;
+    const int k = c - a.Cx;
+    if (k == 0) return xx;
+    if (k == 1) return yy;
+    return sqrtf((xx - 0.5f) * (xx - 0.5f) + (yy - 0.5f) * (yy - 0.5f));
 }
+
+// ------------------------------------------------------------------------------------------------ GRU
+// nn.GRU semantics (SURVEY Appendix C): r,z,n gates; n = tanh(gi_n + r * (W_hn h + b_hn)); h' = (1-z) n + z h.
+// gi (B,T,768) = x·W_ih^T + b_ih is computed outside (time-batched GEMM).  T = T_out/64 steps (<= 16), B <= 16.
+// PERSISTENT cooperative kernels like the encoder BiLSTM: 8 workgroups, each owning 32 hidden units whose three
+// gate rows of W_hh (fp32, 96 x 256) stay in VGPRs as v_mfma_f32_16x16x4_f32 A fragments for all steps; a tile
+// is 4 units x 4 gate slots (slot 3 empty) so the accumulator registers of a lane are (r, z, n) of ONE unit and
+// the gate math is lane-local.  Per step the workgroups exchange the new hidden state (forward) / the gate
+// gradients (backward) with write-through stores + one bounded group barrier (t2v_coop.h).
+#define GRU_H 256
+#define GRU_G (3 * GRU_H)
+#define GRU_NW 8
+#define GRU_UNITS (GRU_H / GRU_NW)   // 32
+
+struct GruArgs {
+    const float* gi;      // (B,T,768)
+    const float* whh;     // (768,256)
+    const float* bhh;     // (768)
+    float* hs;            // (B,T+1,256) hidden states, hs[:,0] = 0 written here
+    float* gsave;         // (B,T,4,256): r, z, n, (W_hn h + b_hn) for the backward; or NULL
+    const float* dh_last; // bwd: (B,256) gradient of the last hidden state
+    float* dgi;           // bwd: (B,T,768) grad wrt gi
+    float* dgh;           // bwd: (B,T,768) grad wrt (W_hh h + b_hh) rows
+    float* xchg;          // fwd: (2,16,256) h exchange; bwd: (2,16,768) gate-gradient exchange (step parity)
+    unsigned* sync;       // [0] arrival counter, [1] error word; zeroed by the launcher
+    int B, T;
+};
+
+// k_conv2d_s2_fwd, k_im2col_s2, k_gru_fwd and their ragged inference instances
+#define REFENC_RAGGED 0
+#include "refenc_fwd.inc"
+#undef REFENC_RAGGED
+#define REFENC_RAGGED 1
+#include "refenc_fwd.inc"
+#undef REFENC_RAGGED
 
 // dx[b][c][h][w] = sum_{co, kh, kw : 2ho-1+kh = h, 2wo-1+kw = w} w[co][c][kh][kw] dy[b][co][ho][wo]
 // grid = (tiles of H*W, B*Cx): the 9 x Cout taps of input channel c sit in LDS
@@ -193,18 +238,6 @@ extern "C" int t2v_conv2d_s2_bwd(const float* x, const float* w, const float* dy
 int t2v_gemm_f32_batched_ex(const float* A, long sAb, long sAs, long sAi, long sAk, const float* B, long sBb, long sBs, long sBj, long sBk,
                             const float* bias_row, float* C, long sCb, int ldc, int nbatch, int nsub, int M, int N, int K, hipStream_t stream);
 
-__global__ __launch_bounds__(256) void k_im2col_s2(Conv2dArgs a, float* __restrict__ col) {
-    const int Cin = a.Cx + (a.coord ? 3 : 0), K = Cin * 9, P = a.Ho * a.Wo;
-    const size_t n = (size_t)a.B * P * K;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
-        const int k = (int)(e % K);
-        const size_t bp = e / K;
-        const int pos = (int)(bp % P), b = (int)(bp / P);
-        const int c = k / 9, t9 = k - c * 9, kh = t9 / 3, kw = t9 - kh * 3;
-        const int ho = pos / a.Wo, wo = pos - ho * a.Wo;
-        col[e] = refenc_in(a, b, c, 2 * ho - 1 + kh, 2 * wo - 1 + kw);
-    }
-}
 // dx[b][c][h][w] = sum of dcol[b][(ho, wo)][c*9 + kh*3 + kw] over the taps with 2ho-1+kh = h, 2wo-1+kw = w (c < Cx only)
 __global__ __launch_bounds__(256) void k_col2im_s2(Conv2dArgs a, const float* __restrict__ dcol) {
     const int Cin = a.Cx + (a.coord ? 3 : 0), K = Cin * 9, P = a.Ho * a.Wo;
@@ -259,6 +292,52 @@ extern "C" int t2v_conv2d_s2_fwd_gemm(const float* x, const float* w, const floa
     k_im2col_s2<<<(unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256), 256, 0, stream>>>(a, scratch);
     return t2v_gemm_f32_batched_ex(w, 0, 0, K, 1, scratch, (long)P * K, 0, K, 1, bias, y, (long)Cout * P, P, B, 1, Cout, P, K, stream);
 }
+// ---- the ragged inference instance of both forms.  H is the padded input height (max of hlen), hlen (B) the
+// per-item heights on the device; x_tstride > 0 selects the layer-0 gather from the padded (B, W, x_tstride) mel (Cx == 1,
+// x_tstride >= H).  Output rows past an item's own (hlen[b] - 1) / 2 + 1 hold values the next layer never reads.  The
+// per-item heights themselves are checked by the caller on the host (2 <= hlen[b] <= H with coord, 1 <= hlen[b] <= H
+// without); the kernels clamp them to H, so no length can make them address outside x.
+static int conv2d_ragged_check(const float* x, const float* w, const float* y, const int* hlen, int B, int Cx, int H, int W,
+                               int Cout, int coord, int x_tstride) {
+    if (!x || !w || !y || !hlen || B < 1 || Cx < 1 || H < 1 || W < 1 || Cout < 1 || x_tstride < 0) return T2V_ERR_ARG;
+    if (coord && (H < 2 || W < 2)) return T2V_ERR_ARG;
+    if (x_tstride > 0 && (Cx != 1 || x_tstride < H)) return T2V_ERR_ARG;
+    if (Cx + (coord ? 3 : 0) > 131) return T2V_ERR_DIMS;
+    return T2V_OK;
+}
+extern "C" int t2v_conv2d_s2_fwd_ragged(const float* x, const float* w, const float* bias, float* y, const int* hlen, int B, int Cx,
+                                        int H, int W, int Cout, int coord, int x_tstride, void* stream_) {
+    const int rc = conv2d_ragged_check(x, w, y, hlen, B, Cx, H, W, Cout, coord, x_tstride);
+    if (rc != T2V_OK) return rc;
+    Conv2dArgs a = conv2d_args(x, w, B, Cx, H, W, Cout, coord);
+    a.bias = bias; a.y = y;
+    RaggedSrc r;
+    r.hlen = hlen; r.tstride = x_tstride;
+    k_conv2d_s2_fwd_ragged<<<dim3((a.Ho * a.Wo + 255) / 256, B * Cout), 256, 0, (hipStream_t)stream_>>>(a, r);
+    return t2v_check_launch();
+}
+// scratch of the ragged GEMM form (floats): the im2col matrix only (no backward)
+extern "C" long t2v_conv2d_s2_gemm_ragged_scratch_floats(int B, int Cx, int H, int W, int Cout, int coord) {
+    if (B < 1 || Cx < 1 || H < 1 || W < 1 || Cout < 1) return 0;
+    const long Cin = Cx + (coord ? 3 : 0), P = (long)((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+    return B * P * Cin * 9;
+}
+extern "C" int t2v_conv2d_s2_fwd_gemm_ragged(const float* x, const float* w, const float* bias, float* y, float* scratch,
+                                             const int* hlen, int B, int Cx, int H, int W, int Cout, int coord, int x_tstride,
+                                             void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = conv2d_ragged_check(x, w, y, hlen, B, Cx, H, W, Cout, coord, x_tstride);
+    if (rc != T2V_OK) return rc;
+    if (!scratch) return T2V_ERR_ARG;
+    Conv2dArgs a = conv2d_args(x, w, B, Cx, H, W, Cout, coord);
+    RaggedSrc r;
+    r.hlen = hlen; r.tstride = x_tstride;
+    const int K = (Cx + (coord ? 3 : 0)) * 9, P = a.Ho * a.Wo;
+    const size_t n = (size_t)B * P * K;
+    k_im2col_s2_ragged<<<(unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256), 256, 0, stream>>>(a, r, scratch);
+    return t2v_gemm_f32_batched_ex(w, 0, 0, K, 1, scratch, (long)P * K, 0, K, 1, bias, y, (long)Cout * P, P, B, 1, Cout, P, K, stream);
+}
+
 // `scratch` must still hold the im2col of the forward pass (t2v_conv2d_s2_fwd_gemm leaves it there); it is overwritten.
 extern "C" int t2v_conv2d_s2_bwd_gemm(const float* x, const float* w, const float* dy, float* dx, float* dw, float* scratch, int B, int Cx,
                                       int H, int W, int Cout, int coord, void* stream_) {
@@ -285,108 +364,7 @@ extern "C" int t2v_conv2d_s2_bwd_gemm(const float* x, const float* w, const floa
     return t2v_check_launch();
 }
 
-// ------------------------------------------------------------------------------------------------ GRU
-// nn.GRU semantics (SURVEY Appendix C): r,z,n gates; n = tanh(gi_n + r * (W_hn h + b_hn)); h' = (1-z) n + z h.
-// gi (B,T,768) = x·W_ih^T + b_ih is computed outside (time-batched GEMM).  T = T_out/64 steps (<= 16), B <= 16.
-// PERSISTENT cooperative kernels like the encoder BiLSTM: 8 workgroups, each owning 32 hidden units whose three
-// gate rows of W_hh (fp32, 96 x 256) stay in VGPRs as v_mfma_f32_16x16x4_f32 A fragments for all steps; a tile
-// is 4 units x 4 gate slots (slot 3 empty) so the accumulator registers of a lane are (r, z, n) of ONE unit and
-// the gate math is lane-local.  Per step the workgroups exchange the new hidden state (forward) / the gate
-// gradients (backward) with write-through stores + one bounded group barrier (t2v_coop.h).
-#define GRU_H 256
-#define GRU_G (3 * GRU_H)
-#define GRU_NW 8
-#define GRU_UNITS (GRU_H / GRU_NW)   // 32
 
-struct GruArgs {
-    const float* gi;      // (B,T,768)
-    const float* whh;     // (768,256)
-    const float* bhh;     // (768)
-    float* hs;            // (B,T+1,256) hidden states, hs[:,0] = 0 written here
-    float* gsave;         // (B,T,4,256): r, z, n, (W_hn h + b_hn) for the backward; or NULL
-    const float* dh_last; // bwd: (B,256) gradient of the last hidden state
-    float* dgi;           // bwd: (B,T,768) grad wrt gi
-    float* dgh;           // bwd: (B,T,768) grad wrt (W_hh h + b_hh) rows
-    float* xchg;          // fwd: (2,16,256) h exchange; bwd: (2,16,768) gate-gradient exchange (step parity)
-    unsigned* sync;       // [0] arrival counter, [1] error word; zeroed by the launcher
-    int B, T;
-};
-
-__global__ __launch_bounds__(256) void k_gru_fwd(GruArgs a) {
-    const int j = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int b = lane & 15, g = lane >> 4;
-    const bool bvalid = b < a.B;
-    __shared__ float hbuf[16][GRU_H + 4];
-    // A fragments of this wave's two tiles: row i = lane&15 -> (unit i>>2, gate slot i&3), k = 4s + g
-    float wreg[2][64];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        const int unit = j * GRU_UNITS + (2 * wave + tt) * 4 + ((lane & 15) >> 2);
-        const int slot = lane & 3;
-#pragma unroll
-        for (int s = 0; s < 64; ++s)
-            wreg[tt][s] = slot < 3 ? a.whh[(size_t)(slot * GRU_H + unit) * GRU_H + 4 * s + g] : 0.f;
-    }
-    float bh[2][3];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        const int U = j * GRU_UNITS + (2 * wave + tt) * 4 + g;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) bh[tt][r] = a.bhh[r * GRU_H + U];
-        if (bvalid) a.hs[((size_t)b * (a.T + 1)) * GRU_H + U] = 0.f;
-    }
-    for (int i = tid; i < 16 * (GRU_H + 4); i += 256) (&hbuf[0][0])[i] = 0.f;
-    __syncthreads();
-
-    for (int t = 0; t < a.T; ++t) {
-        float giv[2][3];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const int U = j * GRU_UNITS + (2 * wave + tt) * 4 + g;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) giv[tt][r] = bvalid ? a.gi[((size_t)b * a.T + t) * GRU_G + r * GRU_H + U] : 0.f;
-        }
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        const float* hrow = &hbuf[b][g];
-#pragma unroll
-        for (int s = 0; s < 64; ++s) {
-            const float hv = hrow[4 * s];
-            acc0 = mfma16x4(wreg[0][s], hv, acc0);
-            acc1 = mfma16x4(wreg[1][s], hv, acc1);
-        }
-        float* hx_w = a.xchg + (size_t)(t & 1) * 16 * GRU_H;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const f32x4 acc = tt == 0 ? acc0 : acc1;
-            const int U = j * GRU_UNITS + (2 * wave + tt) * 4 + g;
-            if (bvalid) {
-                const float r = sigmoidf_(giv[tt][0] + acc[0] + bh[tt][0]);
-                const float z = sigmoidf_(giv[tt][1] + acc[1] + bh[tt][1]);
-                const float hn = acc[2] + bh[tt][2];
-                const float n = tanhf_(giv[tt][2] + r * hn);
-                const float hnew = (1.f - z) * n + z * hbuf[b][U];
-                if (a.gsave) {
-                    float* sv = a.gsave + (((size_t)b * a.T + t) * 4) * GRU_H + U;
-                    sv[0] = r; sv[GRU_H] = z; sv[2 * GRU_H] = n; sv[3 * GRU_H] = hn;
-                }
-                a.hs[((size_t)b * (a.T + 1) + t + 1) * GRU_H + U] = hnew;
-                st_sc1(hx_w + (size_t)b * GRU_H + U, hnew);
-            }
-        }
-        if (t + 1 == a.T) break;
-        if (!group_barrier(a.sync, (unsigned)(GRU_NW * (t + 1)), a.sync + 1)) return;
-        {   // the new hidden state of every item: all loads of a thread in flight at once (round 6 — as a plain loop over the items
-            // every iteration waited for its own load: one memory round trip per item and step; rows past B re-read row B - 1)
-            float hv[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) hv[u] = ld_sc1(hx_w + (size_t)min(u, a.B - 1) * GRU_H + tid);
-#pragma unroll
-            for (int u = 0; u < 16; ++u)
-                if (u < a.B) hbuf[u][tid] = hv[u];
-        }
-        __syncthreads();
-    }
-}
 
 // BPTT.  Thread (item bb = tid>>5 (+8), unit uu = tid&31) does the gate gradients of its (item, unit); the
 // transposed recurrent product dh_prev[b][unit] = sum_rows W_hh[row][unit] * dg[b][row] (768 rows split over the
@@ -485,6 +463,20 @@ extern "C" int t2v_gru_fwd(const float* gi, const float* whh, const float* bhh, 
     a.gi = gi; a.whh = whh; a.bhh = bhh; a.hs = hs; a.gsave = gsave; a.dh_last = nullptr; a.dgi = nullptr; a.dgh = nullptr;
     a.xchg = xchg; a.sync = sync2; a.B = B; a.T = T;
     k_gru_fwd<<<GRU_NW, 256, 0, stream>>>(a);
+    return t2v_check_launch();
+}
+
+// t2v_gru_fwd plus h_last[b] = hs[b, steps[b]] (steps: (B) int32 on the device, each in 1..T, checked by the caller; an
+// item whose count is outside that range gets no h_last row).
+extern "C" int t2v_gru_fwd_len(const float* gi, const float* whh, const float* bhh, float* hs, float* gsave, float* xchg,
+                               uint32_t* sync2, const int* steps, float* h_last, int B, int T, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!gi || !whh || !bhh || !hs || !xchg || !sync2 || !steps || !h_last || B < 1 || B > 16 || T < 1) return T2V_ERR_ARG;
+    (void)hipMemsetAsync(sync2, 0, 2 * sizeof(uint32_t), stream);
+    GruArgs a;
+    a.gi = gi; a.whh = whh; a.bhh = bhh; a.hs = hs; a.gsave = gsave; a.dh_last = nullptr; a.dgi = nullptr; a.dgh = nullptr;
+    a.xchg = xchg; a.sync = sync2; a.B = B; a.T = T;
+    k_gru_fwd_len<<<GRU_NW, 256, 0, stream>>>(a, steps, h_last);
     return t2v_check_launch();
 }
 

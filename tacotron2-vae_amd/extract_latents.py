@@ -1,0 +1,64 @@
+"""Latent export: prosody, mu, logvar and z of every utterance of a filelist, for the scatter / t-SNE plots of the
+reference README's "Visualization" section.
+
+    python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...]
+
+Filelist rows are `path|text|speaker|emotion`.  OUT.npz holds, row i for filelist row i: prosody (N, E), mus, logvars,
+zs (N, z_latent_dim), emotions (N,) int and paths (N,) str.  The wavs run through `Synthesizer.latents`: sorted by
+length, in ragged batches of at most --batch_size, each row what model.vae_gst(load_mel(path)) gives for the wav alone.
+"""
+import argparse
+
+import numpy as np
+
+DEFAULT_BATCH_SIZE = 64
+
+
+def build_arg_parser():
+    p = argparse.ArgumentParser(description="filelist -> prosody / mu / logvar / z of every utterance (.npz)")
+    p.add_argument('--load_path', required=True, help="checkpoint written by train.py")
+    p.add_argument('--filelist_path', required=True, help="rows path|text|speaker|emotion")
+    p.add_argument('--out', required=True, help="output .npz")
+    p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="wavs per ragged vae_gst call")
+    p.add_argument('--hparams', default='', help="comma separated name=value overrides")
+    return p
+
+
+def parse_args(argv=None):
+    args = build_arg_parser().parse_args(argv)
+    if args.batch_size < 1:
+        raise SystemExit("--batch_size must be >= 1")
+    return args
+
+
+def read_filelist(path):
+    """(paths, emotion ids) of the rows `path|text|speaker|emotion`"""
+    paths, emotions = [], []
+    with open(path, encoding='utf-8') as f:
+        for line in f:
+            if not line.strip():
+                continue
+            audio_path, _, _, emotion = line.strip().split("|")
+            paths.append(audio_path)
+            emotions.append(int(emotion))
+    return paths, np.array(emotions, dtype=np.int64)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from hparams import create_hparams
+    from synthesizer import Synthesizer
+    hp = create_hparams()
+    hp.sampling_rate = 16000                 # the reference's Synthesizer() overrides, as synthesizer.py's command line
+    hp.max_decoder_steps = 600
+    if args.hparams:
+        hp.parse(args.hparams)
+    syn = Synthesizer(hp).load_checkpoint(args.load_path)
+    paths, emotions = read_filelist(args.filelist_path)
+    prosody, mu, logvar, z = (t.cpu().numpy() for t in syn.latents(paths, args.batch_size))
+    np.savez(args.out, prosody=prosody, mus=mu, logvars=logvar, zs=z, emotions=emotions, paths=np.array(paths))
+    print("%s: %d utterances" % (args.out, len(paths)))
+
+
+if __name__ == "__main__":
+    main()

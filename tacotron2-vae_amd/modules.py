@@ -32,7 +32,13 @@ class ReferenceEncoder(nn.Module):
             L = (L - kernel_size + 2 * pad) // stride + 1
         return L
 
-    def forward(self, inputs):
+    def forward(self, inputs, lengths=None):
+        """lengths: None (the reference's padded-batch semantics, trainable), or the frame count of every item (a list, CPU
+        tensor or device int tensor): eval only, row b is then what `forward(inputs[b:b+1, :, :lengths[b]])` returns, up to fp32
+        summation order; nothing past an item's frames is read.  The ragged path has no backward: its result is
+        computed outside autograd and carries no history."""
+        if lengths is not None:
+            return self.forward_ragged(inputs, lengths)
         import t2v_hip
         n = inputs.size(0)
         out = inputs.contiguous().view(n, 1, -1, self.n_mels)      # raw reinterpretation, no transpose (B-1)
@@ -47,6 +53,20 @@ class ReferenceEncoder(nn.Module):
         out = out.contiguous().view(n, out.size(1), -1)
         g = self.gru
         return t2v_hip.GRULast.apply(out, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)
+
+    def forward_ragged(self, inputs, lengths):
+        import t2v_hip
+        if self.training:
+            raise RuntimeError("ReferenceEncoder: per-item lengths are an eval-mode (inference) path; call .eval() first")
+        B, _, T = inputs.shape
+        n = [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if len(n) != B or min(n) < 2 or max(n) > T:      # CoordConv divides by (frames - 1)
+            raise ValueError("every item needs 2 <= frames <= %d, got %s (%d items)" % (T, n, B))
+        layers = [((conv.conv if i == 0 else conv).weight, (conv.conv if i == 0 else conv).bias, bn.weight, bn.bias,
+                   bn.running_mean, bn.running_var) for i, (conv, bn) in enumerate(zip(self.convs, self.bns))]
+        g = self.gru
+        with torch.no_grad():
+            return t2v_hip.refenc_ragged(inputs, n, layers, (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0))
 
 
 class VAE_GST(nn.Module):
@@ -67,10 +87,18 @@ class VAE_GST(nn.Module):
         import t2v_hip
         return t2v_hip.Reparam.apply(eps, mu, logvar)      # eps * exp(0.5 logvar) + mu, one launch (raises for CPU tensors)
 
-    def forward(self, inputs):
+    def forward(self, inputs, lengths=None):
+        """lengths: optional frame count per item (eval only): each row of (prosody, mu, logvar, z) is then what the item
+        alone, `forward(inputs[b:b+1, :, :lengths[b]])`, returns, up to fp32 summation order; the outputs carry no autograd
+        history (ReferenceEncoder.forward)."""
+        if lengths is not None:
+            with torch.no_grad():
+                return self._heads(self.ref_encoder(inputs, lengths))
+        return self._heads(self.ref_encoder(inputs))
+
+    def _heads(self, enc_out):
         import t2v_hip
         lin = t2v_hip.LinearHIP.apply
-        enc_out = self.ref_encoder(inputs)
         mu = lin(enc_out, self.fc1.weight, self.fc1.bias, False, 0.0, 0, 0, 0)
         logvar = lin(enc_out, self.fc2.weight, self.fc2.bias, False, 0.0, 0, 0, 0)
         z = self.reparameterize(mu, logvar)

@@ -22,6 +22,21 @@ from utils import load_wav_to_torch
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists
 
 
+def length_groups(lengths, batch_size):
+    """Indices of `lengths` sorted by length (longest first, ties in input order) and cut into groups of at most batch_size:
+    the ragged batches of Synthesizer.latents, each padded only to its own longest item."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+def wav_num_samples(path):
+    """sample count of a wav from its header (the data is memory-mapped, not read)"""
+    from scipy.io.wavfile import read
+    return len(read(path, mmap=True)[1])
+
+
 class GriffinLimVocoder(object):
     """mel (B, 80, T) -> waveform (B, (T-1)*256) on the device: `stft.mel_to_magnitude` (pinv of the mel filterbank,
     clamped at 0) and n_iters Griffin-Lim iterations on `stft.stft_fn` (audio_processing.griffin_lim, initial phase from
@@ -72,6 +87,42 @@ class Synthesizer(object):
         audio_norm = (audio / self.hparams.max_wav_value).unsqueeze(0)
         return self.stft.mel_spectrogram(audio_norm.cuda())
 
+    def load_mels(self, paths):
+        """`load_mel` for several wavs in one ragged front-end call: returns (mels (B, 80, T_max) on the device, frame counts);
+        item b equals load_mel(paths[b]) on its first counts[b] frames, and what lies past them is padding."""
+        audios = []
+        for path in paths:
+            audio, sampling_rate = load_wav_to_torch(path)
+            if sampling_rate != self.hparams.sampling_rate:
+                raise ValueError("{} SR doesn't match target {} SR".format(sampling_rate, self.hparams.sampling_rate))
+            audios.append(audio / self.hparams.max_wav_value)
+        if not audios:
+            raise ValueError("load_mels: no paths")
+        n = [a.numel() for a in audios]
+        y = torch.zeros(len(audios), max(n))
+        for b, a in enumerate(audios):
+            y[b, :n[b]] = a
+        mels = self.stft.mel_spectrogram(y.cuda(), torch.tensor(n, dtype=torch.int64))
+        return mels, [k // self.hparams.hop_length + 1 for k in n]
+
+    @torch.no_grad()
+    def latents(self, paths, batch_size=64):
+        """(prosody (N, E), mu, logvar, z (N, z_latent_dim)) of every wav, in input order, each row what
+        `model.vae_gst(load_mel(paths[i]))` returns (up to fp32 summation order).  The wavs are sorted by length and run in
+        ragged batches of at most batch_size (one front-end call and one vae_gst call each)."""
+        paths = list(paths)
+        if not paths:
+            raise ValueError("latents: no paths")
+        parts, order = [], []
+        for idx in length_groups([wav_num_samples(p) for p in paths], batch_size):
+            mels, n = self.load_mels([paths[i] for i in idx])
+            parts.append(self.model.vae_gst(mels, n))
+            order += idx
+        inv = torch.empty(len(paths), dtype=torch.int64)
+        inv[torch.tensor(order)] = torch.arange(len(paths))
+        inv = inv.to(parts[0][0].device)
+        return tuple(torch.cat([p[k] for p in parts], 0)[inv] for k in range(4))
+
     # ------------------------------------------------------------------ checkpoint + centroids (synthesizer.py:74-110)
     @staticmethod
     def centroid_cache_path(checkpoint_path, filelist_path):
@@ -79,17 +130,23 @@ class Synthesizer(object):
         suffix = filelist_path.rsplit('_', 1)[1].split('.')[0] if '_' in filelist_path else 'refs'
         return os.path.join(os.path.dirname(checkpoint_path), os.path.basename(checkpoint_path) + '_' + suffix + '.npz')
 
-    def load(self, checkpoint_path, waveglow_path=None, vocoder=None,
-             filelist_path='./web/static/uploads/koemo_spk_emo_all_test.txt'):
-        """Positional order of the reference (synthesizer.py:74: `load(checkpoint_path, waveglow_path)`, called from
-        app.py:161).  waveglow_path: a WaveGlow checkpoint `{'model': module}` exactly as the reference loads it
-        (needs the `waveglow` package importable: it is an un-vendored submodule of the reference); `vocoder`: any
-        callable mel (1,80,T) -> audio instead, or 'griffin_lim' for GriffinLimVocoder(self.stft).  A callable passed in
-        the second position is taken as the vocoder."""
+    def load_checkpoint(self, checkpoint_path):
+        """the model of a train.py checkpoint, in eval mode (the first step of `load`)"""
         from train import load_model
         self.model = load_model(self.hparams)
         self.model.load_state_dict(torch.load(checkpoint_path, map_location='cpu')['state_dict'])
         self.model.eval()
+        return self
+
+    def load(self, checkpoint_path, waveglow_path=None, vocoder=None,
+             filelist_path='./web/static/uploads/koemo_spk_emo_all_test.txt', batch_size=64):
+        """Positional order of the reference (synthesizer.py:74: `load(checkpoint_path, waveglow_path)`, called from
+        app.py:161).  waveglow_path: a WaveGlow checkpoint `{'model': module}` exactly as the reference loads it
+        (needs the `waveglow` package importable: it is an un-vendored submodule of the reference); `vocoder`: any
+        callable mel (1,80,T) -> audio instead, or 'griffin_lim' for GriffinLimVocoder(self.stft).  A callable passed in
+        the second position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
+        (`latents`), when there is no centroid cache yet."""
+        self.load_checkpoint(checkpoint_path)
         if callable(waveglow_path) and vocoder is None:
             vocoder, waveglow_path = waveglow_path, None
         self.waveglow = None
@@ -114,14 +171,12 @@ class Synthesizer(object):
         else:
             with open(filelist_path, encoding='utf-8') as f:
                 rows = [line.strip().split("|") for line in f if line.strip()]
-            zs, emotions = [], []
-            with torch.no_grad():
-                for audio_path, _, _, emotion in rows:
-                    _, _, _, z = self.model.vae_gst(self.load_mel(audio_path))
-                    zs.append(z.detach().cpu())
-                    emotions.append(int(emotion))
+            paths, emotions = [], []
+            for audio_path, _, _, emotion in rows:
+                paths.append(audio_path)
+                emotions.append(int(emotion))
             emotions = np.array(emotions)
-            zs = torch.cat(zs, dim=0).numpy()
+            zs = self.latents(paths, batch_size)[3].cpu().numpy()          # filelist order
             np.savez(npz_path, zs=zs, emotions=emotions)
         for i, name in enumerate(EMOTIONS):
             sel = zs[emotions == i, :]
@@ -197,8 +252,13 @@ class Synthesizer(object):
         lengths = torch.tensor(lens, dtype=torch.int32).cuda()
         embedded = self.model.transcript_embedding(self.model.parse_input(ids)).transpose(1, 2)
         transcript_outputs = self.model.encoder.inference(embedded, lengths)              # (B, L, 512), 0 past each length
-        styles = [self.style_vector(transcript_outputs[b:b + 1, :lens[b]], condition_on_ref,
-                                    ref_audios[b] if condition_on_ref else None, per_text[b]) for b in range(B)]
+        if condition_on_ref:        # every distinct reference wav once, all in one ragged front-end + vae_gst call
+            uniq = list(dict.fromkeys(ref_audios))
+            mels, n = self.load_mels(uniq)
+            latent = self.model.vae_gst(mels, n)[0]
+            styles = [latent[uniq.index(p)].view(1, 1, -1) for p in ref_audios]
+        else:
+            styles = [self.style_vector(transcript_outputs[b:b + 1, :lens[b]], False, None, per_text[b]) for b in range(B)]
         encoder_outputs = torch.cat([transcript_outputs[b:b + 1] + styles[b].reshape(1, -1, styles[b].size(-1))[:, :1]
                                      for b in range(B)], 0)
         mel, _, alignments, n_frames = self.model.decoder.inference_batch(encoder_outputs, lens)

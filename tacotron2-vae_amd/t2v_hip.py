@@ -93,7 +93,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_decoder_bwd_persistent16_prepare', 't2v_decoder_bwd_persistent16_prepared',
            't2v_stft_polar', 't2v_istft', 't2v_istft_scratch_bytes', 't2v_griffin_lim', 't2v_griffin_lim_scratch_bytes',
            't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
-           't2v_mask_time')
+           't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
+           't2v_gru_fwd_len')
 
 
 def lib_path():
@@ -256,6 +257,11 @@ def load_library():
     lib.t2v_conv2d_s2_dw_scratch_floats.argtypes = [C.c_int] * 6
     lib.t2v_gru_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.t2v_gru_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
+    lib.t2v_conv2d_s2_fwd_ragged.argtypes = [vp, vp, vp, vp, vp] + [C.c_int] * 7 + [vp]
+    lib.t2v_conv2d_s2_fwd_gemm_ragged.argtypes = [vp, vp, vp, vp, vp, vp] + [C.c_int] * 7 + [vp]
+    lib.t2v_conv2d_s2_gemm_ragged_scratch_floats.argtypes = [C.c_int] * 6
+    lib.t2v_conv2d_s2_gemm_ragged_scratch_floats.restype = C.c_long
+    lib.t2v_gru_fwd_len.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.t2v_loss_fwd_bwd.argtypes = [vp] * 15 + [C.c_uint64, C.c_int, C.c_int, C.c_float, vp]
     for name in EXPORTS:
         getattr(lib, name)
@@ -2256,6 +2262,62 @@ class GRULast(torch.autograd.Function):
             hprev = hs[:, :T].reshape(B * T, 256)
             g = (gemm(dgi2.t(), x2.t()), gemm(dgh2.t(), hprev.t()))
         return (dx,) + g + (colsum(dgi2), colsum(dgh2))
+
+
+def refenc_heights(n_frames, n_layers):
+    """per-item input heights of the reference encoder's layers, host side: row 0 = the frame counts, row l + 1 =
+    (row l - 1) // 2 + 1 (a 3x3 stride-2 pad-1 convolution); the last row is the GRU's step count"""
+    h = [[int(x) for x in n_frames]]
+    for _ in range(n_layers):
+        h.append([(x - 1) // 2 + 1 for x in h[-1]])
+    return h
+
+
+def refenc_ragged(mel, n_frames, layers, gru):
+    """Eval-mode ReferenceEncoder over a ragged batch, no autograd: row b is what the encoder gives for
+    mel[b:b+1, :, :n_frames[b]] alone.  mel: (B, n_mels, T) CUDA float32, anything past an item's frames is never read;
+    n_frames: host ints, already checked (2 <= n <= T).  layers: per conv layer (weight, bias, gamma, beta, running_mean,
+    running_var), layer 0 the CoordConv inner conv; gru: (w_ih, w_hh, b_ih, b_hh).  Returns the last GRU states (B, 256)
+    at each item's own step count.  Same conv form as Conv2dBNReLU (CONV2D_GEMM), BatchNorm2d eval + ReLU on t2v_bn_act_fwd."""
+    lib = _require_gpu(mel)
+    x = _f32c(mel)
+    B, n_mels, T = x.shape
+    f32 = dict(device=x.device, dtype=torch.float32)
+    heights = torch.tensor(refenc_heights(n_frames, len(layers)), dtype=torch.int32).to(x.device)    # one upload
+    Hh, Ww, Cx = T, n_mels, 1
+    for i, (weight, bias, gamma, beta, running_mean, running_var) in enumerate(layers):
+        coord, tstride = int(i == 0), (T if i == 0 else 0)          # layer 0 gathers the reinterpreted rows from the mel
+        Cout = weight.shape[0]
+        Ho, Wo = (Hh - 1) // 2 + 1, (Ww - 1) // 2 + 1
+        w = _f32c(weight.detach())
+        y = torch.empty(B, Cout, Ho, Wo, **f32)
+        hlen = heights[i]
+        if CONV2D_GEMM:
+            scr = torch.empty(lib.t2v_conv2d_s2_gemm_ragged_scratch_floats(B, Cx, Hh, Ww, Cout, coord), **f32)
+            _check(lib.t2v_conv2d_s2_fwd_gemm_ragged(_p(x), _p(w), _p(bias), _p(y), _p(scr), _p(hlen), B, Cx, Hh, Ww, Cout, coord,
+                                                     tstride, _stream()), 't2v_conv2d_s2_fwd_gemm_ragged')
+        else:
+            _check(lib.t2v_conv2d_s2_fwd_ragged(_p(x), _p(w), _p(bias), _p(y), _p(hlen), B, Cx, Hh, Ww, Cout, coord, tstride,
+                                                _stream()), 't2v_conv2d_s2_fwd_ragged')
+        x = torch.empty_like(y)
+        _check(lib.t2v_bn_act_fwd(_p(y), None, 0, _p(gamma), _p(beta), _p(running_mean), _p(running_var), None, None, _p(x),
+                                  B, Cout, Ho * Wo, ACT_RELU, 0, 0.0, 0.1, 1e-5, 0, 0, 0, _stream()), 't2v_bn_act_fwd')
+        Hh, Ww, Cx = Ho, Wo, Cout
+    steps = heights[len(layers)]
+    seq = x.transpose(1, 2).contiguous().view(B * Hh, Cx * Ww)     # (B, steps_max, C*W) as ReferenceEncoder.forward
+    w_ih, w_hh, b_ih, b_hh = gru
+    gi = gemm(seq, w_ih.detach(), b_ih.detach()).view(B, Hh, 768)
+    hs = torch.empty(B, Hh + 1, 256, **f32)
+    h_last = torch.empty(B, 256, **f32)
+    whh = _f32c(w_hh.detach())
+    xchg = torch.empty(2 * 16 * 256, **f32)
+    for b0 in range(0, B, MAX_DEC_B):          # 16 sequences per cooperative launch, as GRULast
+        b1 = min(B, b0 + MAX_DEC_B)
+        sync = torch.empty(2, device=x.device, dtype=torch.int32)
+        _check(lib.t2v_gru_fwd_len(_p(gi[b0:b1]), _p(whh), _p(b_hh), _p(hs[b0:b1]), None, _p(xchg), _p(sync), _p(steps[b0:b1]),
+                                   _p(h_last[b0:b1]), b1 - b0, Hh, _stream()), 't2v_gru_fwd_len')
+        _err_note('GRU forward', sync[1:2])
+    return h_last
 
 
 class VAELoss(torch.autograd.Function):
