@@ -217,18 +217,10 @@ int t2v_attn_wgrad(const float* dpre, const float* al, const float* acum, const 
 
 
 /* ------------------------------------------------------------------ persistent BPTT (csrc/decoder_train_bwd_persist.hip)
- * The reverse recurrence of the decoder loop as persistent launches for the shapes of the persistent forward
+ * The reverse recurrence of the decoder loop as one persistent launch for the shapes of the persistent forward
  * (t2v_decoder_bwd_persist_supported: B <= 6, T_in <= 576 — 96-position attention slices beyond 224 symbols —, >= 256 CUs).
- * decoder_rnn's chain does not depend on the attention path, so it runs first for all steps:
- *   t2v_decoder_bwd_dchain : dHC[:, :, :1024] (grad wrt h_dec from the projection), GD, CD (saved by the forward pass)
- *                            -> DGD (T,B,4096), grad wrt decoder_rnn's pre-activations.  256 workgroups x 4 hidden units,
- *                            W_hh_dec^T in registers; the gate-gradient rows travel between CUs through `scratch`
- *                            (t2v_decoder_bwd_dchain_scratch_floats(B, T_out) floats, 16-byte aligned, filled by the call).
  * err_word (1 x uint32, zeroed by the call): != 0 afterwards = a bounded spin timed out. */
 int t2v_decoder_bwd_persist_supported(int B, int T_in);
-long t2v_decoder_bwd_dchain_scratch_floats(int B, int T_out);
-int t2v_decoder_bwd_dchain(const float* w_hh_dec, const float* dHC, const float* GD, const float* CD, float* DGD,
-                           float* scratch, uint32_t* err_word, int B, int T_out, float p_dec, uint64_t seed, void* stream);
 /* The WHOLE reverse pass as ONE persistent launch (k_achain_bwd): attention_rnn + attention form the per-step dependency
  * chain (all-gather dga(t+1) -> Wcat_att^T columns -> d ctx(t) -> attention(t) backward on position-split workgroups ->
  * dq(t) -> W_q^T, cell backward -> dga(t)); decoder_rnn's chain (cell backward, all-gather of dgd, Wcat_dec^T columns)
@@ -277,15 +269,7 @@ int t2v_decoder_bwd_persistent16_prepared(const t2v_dec_train_persist_weights* w
 /* float offset inside `scratch` of dq(t) summed over the position slices, (T_out,B,128) floats, valid when the pass has ended
  * (-1: shape outside the persistent range) */
 long t2v_decoder_bwd_achain_dq_offset(int B, int T_in, int T_out);
-/* The same pass as TWO launches (round 4): the attention chain on `stream`, the free-running decoder_rnn chain on `stream_d`
- * (which this call orders behind the preparation launches on `stream`).  DGD is complete when stream_d is — the decoder_rnn
- * weight-gradient GEMMs can be queued behind it and run while the attention chain is still going — everything else when
- * `stream` is; the caller joins stream_d back.  stream_d NULL or == stream: one launch, as t2v_decoder_bwd_achain. */
-int t2v_decoder_bwd_achain2(const t2v_dec_train_persist_weights* w, const float* reserved, const t2v_dec_train_bufs* s,
-                           const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
-                           uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                           void* stream, void* stream_d);
-/* The preparation of that pass as a call of its own (error word, sentinel fills, the factor arrays of both cells — functions
+/* The preparation of t2v_decoder_bwd_achain as a call of its own (error word, sentinel fills, the factor arrays of both cells — functions
  * of the forward pass's saved activations alone, so a training step issues it right after the decoder forward, on a side
  * stream, next to the Postnet), and the pass without it.  scratch / DQP / err_word: the same buffers in both calls. */
 int t2v_decoder_bwd_achain_prepare(const t2v_dec_train_bufs* s, float* DQP, float* scratch, uint32_t* err_word, int B, int T_in,
@@ -293,7 +277,7 @@ int t2v_decoder_bwd_achain_prepare(const t2v_dec_train_bufs* s, float* DQP, floa
 int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const float* reserved, const t2v_dec_train_bufs* s,
                            const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                            uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                           void* stream, void* stream_d);
+                           void* stream);
 
 /* ------------------------------------------------------------------ free-running decode
  * Decoder.inference (model.py:428-464) == the synthesizer loop (synthesizer.py:139-154): steps

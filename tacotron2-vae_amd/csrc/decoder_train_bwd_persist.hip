@@ -1,20 +1,24 @@
-// Hand-written BPTT of the teacher-forced decoder loop as persistent launches (reference: autograd over Decoder.decode,
-// model.py:346-389 / train.py:225).  The launch-per-step backward (decoder_bwd.hip: 2 launches and a 67 MB transposed
-// weight stream per reverse step) stays the general path; these kernels serve the shapes of the persistent forward
-// (B <= 6, T_in <= 224).
+// Hand-written BPTT of the teacher-forced decoder loop as ONE persistent launch, fp32 weights (reference: autograd over
+// Decoder.decode, model.py:346-389 / train.py:225).  The launch-per-step backward (decoder_bwd.hip: 2 launches and a 67 MB
+// transposed weight stream per reverse step) stays the general path; this file serves B <= 6, T_in <= 576
+// (t2v_decoder_bwd_persist_supported); decoder_train_bwd_persist16.hip is its bf16 counterpart for B <= 16.
 //
-// The reverse recurrence splits into two chains that meet only through a time-batched GEMM:
-//   D  decoder_rnn:   dgd(t+1) -> W_hh_dec^T -> dh_dec(t) -> cell backward -> dgd(t).  Nothing of the attention path
-//      enters it (teacher forcing: h_dec feeds only the projection and its own next step), so it runs FIRST, for all
-//      steps, as k_dchain_bwd: 256 workgroups x 4 hidden units, W_hh_dec^T (16 MB) in registers.
-//   -- then ONE GEMM  E = DGD · W_ih_dec  (T*B x 4096 x 1536, own fp32 MFMA GEMM, host side) gives every step's
-//      decoder_rnn contribution to d h_att(t) and d ctx(t) at once.
-//   A  attention_rnn + attention (k_achain_bwd): dga(t+1) -> Wcat_att^T -> [d h_att(t) | d ctx(t)] -> attention(t)
-//      backward (workgroups split over encoder positions) -> dq(t) -> W_q^T -> cell backward -> dga(t).
+// k_achain_bwd<NB, LONG> runs the whole reverse recurrence on 256 resident workgroups in three roles (details at PBAArgs and
+// at pba_na below):
+//   T  attention(t) backward of one item and one slice of encoder positions,
+//   A  attention_rnn: dga(t+1) -> Wcat_att^T -> [d h_att(t) | d ctx(t)] -> (T role) -> dq(t) -> W_q^T -> cell backward -> dga(t)
+//      — the per-step dependency chain,
+//   D  decoder_rnn: dgd(t+1) -> W_hh_dec^T -> dh_dec(t) -> cell backward -> dgd(t).  Nothing of the attention path enters it
+//      (teacher forcing: h_dec feeds only the projection and its own next step), so it free-runs ahead of the A chain and
+//      leaves E(t) = Wcat_dec[:, :1536]^T dgd(t), its contribution to d h_att(t) / d ctx(t), for the A workgroups.
+// All transposed LSTM weight columns live in registers, read once per pass from the nn.LSTMCell tensors.
+// In front of the pass two small kernels turn the forward pass's saved activations into per-step factor arrays
+// (k_pb_factors, k_pb_cellpre); they and the sentinel fills are the "preparation", which a training step issues right behind
+// the decoder forward (t2v_decoder_bwd_achain_prepare / _prepared; t2v_decoder_bwd_achain does both).
+// Host side at the end of the file: pba_layout() is the one description of the scratch buffer's sections.
 // Hand-offs as in decoder_train_persist.hip: every exchanged value is produced exactly once per pass, so the exchange
 // buffers are pre-filled with a NaN sentinel (T2V_SENT, t2v_xchg.h) and a word that is no longer the sentinel IS the data — 4 bytes
-// per value on the wire, sc1 (write-through) stores, sc1 loads, no flags, no ordering.  Gate-gradient rows travel as
-// [plane][k][items] so that a consumer's 16-byte (items 0..3) / 8-byte (items 4, 5) load is an LDS-ready GEMV operand.
+// per value on the wire, sc1 (write-through) stores, sc1 loads, no flags, no ordering.
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_xchg.h"
@@ -30,41 +34,6 @@
 //   plane 0: k -> 16 bytes (items 0..3) at byte 16 k          (64 KB)
 //   plane 1: k -> 8 bytes (items 4, 5)  at byte 65536 + 8 k   (32 KB, B > 4 only)
 #define PB_ROW_BYTES(NB) ((NB) > 4 ? 98304u : 65536u)
-
-// gather one row into LDS (X0: f32x4[4096], X1: f32x2[4096]); nap first, then poll the payload itself.  Returns rounds.
-template <int NB>
-__device__ __forceinline__ int pb_gather_row(f32x4* X0, f32x2* X1, __amdgpu_buffer_rsrc_t r, unsigned row_off, int B, int nap,
-                                             unsigned* err, int* flag) {
-    const int tid = threadIdx.x;
-    for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
-    f32x4 v0[PB_KJ];
-    f32x2 v1[PB_KJ];
-    int rounds = 0;
-    const int nw0 = min(B, 4), nw1 = B - 4;
-    for (;;) {
-#pragma unroll
-        for (int j = 0; j < PB_KJ; ++j) v0[j] = t2v_ld_f32x4(r, row_off + 16u * (unsigned)(tid + PB_THREADS * j));
-        if (NB > 4) {
-#pragma unroll
-            for (int j = 0; j < PB_KJ; ++j) v1[j] = t2v_ld_f32x2(r, row_off + 65536u + 8u * (unsigned)(tid + PB_THREADS * j));
-        }
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < PB_KJ; ++j) {
-            ok = ok && t2v_ok(v0[j][0]) && (nw0 < 2 || t2v_ok(v0[j][1])) && (nw0 < 3 || t2v_ok(v0[j][2])) && (nw0 < 4 || t2v_ok(v0[j][3]));
-            if (NB > 4) ok = ok && t2v_ok(v1[j][0]) && (nw1 < 2 || t2v_ok(v1[j][1]));
-        }
-        if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(2);
-        if (t2v_give_up(rounds, PB_SPIN, err, flag)) break;
-    }
-#pragma unroll
-    for (int j = 0; j < PB_KJ; ++j) {
-        X0[tid + PB_THREADS * j] = v0[j];
-        if (NB > 4) X1[tid + PB_THREADS * j] = v1[j];
-    }
-    return rounds;
-}
 
 // ---- the one-launch reverse pass exchanges (d c, d h) of a cell instead of its four gate gradients: a row is
 //   plane 0: unit U -> 32 bytes [dc items 0..3 | dh items 0..3] at byte 32 U          (32 KB)
@@ -209,68 +178,10 @@ __device__ __forceinline__ void pb_pk3(f32x2& a01, f32x2& a23, f32x2& a45, f32x2
                      "v_pk_fma_f32 %2, %3, %6, %2 op_sel:[0,0,0] op_sel_hi:[0,1,1]\n\t"
                      : "+v"(a01), "+v"(a23), "+v"(a45) : "v"(w), "v"(x01), "v"(x23), "v"(x45));
 }
-template <int NC, int NB>
-__device__ __forceinline__ void pb_gemv(const f32x2 (&w)[NC][PB_KJ / 2], const f32x4* X0, const f32x2* X1, f32x2 (&acc)[NC][3]) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = f32x2{0.f, 0.f};
-    f32x4 xa[PB_KJ];
-    f32x2 xb[PB_KJ];
-#pragma unroll
-    for (int j = 0; j < PB_KJ; ++j) {
-        xa[j] = X0[tid + PB_THREADS * j];
-        xb[j] = f32x2{0.f, 0.f};
-        if (NB > 4) xb[j] = X1[tid + PB_THREADS * j];
-    }
-#pragma unroll
-    for (int j = 0; j < PB_KJ; ++j) {
-        const f32x2 x01 = {xa[j][0], xa[j][1]}, x23 = {xa[j][2], xa[j][3]};
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            if (j & 1) pb_pk3<true>(acc[c][0], acc[c][1], acc[c][2], w[c][j / 2], x01, x23, xb[j]);
-            else pb_pk3<false>(acc[c][0], acc[c][1], acc[c][2], w[c][j / 2], x01, x23, xb[j]);
-        }
-    }
-}
 
-// Sum NV <= 32 per-thread values over the 512 threads of the workgroup: 16-lane transposing butterfly (lane c of a row
-// ends with the row sums of values 2c, 2c + 1), then the 32 row partials (8 waves x 4 rows) through LDS:
-// part[(wave * 4 + row) * 32 + idx].  The caller syncs and sums the 32 partials of the values it needs.
-__device__ __forceinline__ void pb_reduce32(float (&v)[32], float* part) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2, b0 = lane & 1;
-    float w16[16], w8[8], w4[4], w2[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float keep = b3 ? v[16 + i] : v[i], send = b3 ? v[i] : v[16 + i];
-        w16[i] = keep + T2V_DPP_F(send, 0x140);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float keep = b2 ? w16[8 + i] : w16[i], send = b2 ? w16[i] : w16[8 + i];
-        w8[i] = keep + T2V_DPP_F(send, 0x141);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float keep = b1 ? w8[4 + i] : w8[i], send = b1 ? w8[i] : w8[4 + i];
-        w4[i] = keep + T2V_DPP_F(send, 0x4E);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float keep = b0 ? w4[2 + i] : w4[i], send = b0 ? w4[i] : w4[2 + i];
-        w2[i] = keep + T2V_DPP_F(send, 0xB1);
-    }
-    *(float2*)(part + ((tid >> 6) * 4 + (lane >> 4)) * 32 + 2 * (lane & 15)) = make_float2(w2[0], w2[1]);
-}
-__device__ __forceinline__ float pb_sum32(const float* part, int idx) {
-    float s[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s[i] = (part[(4 * i) * 32 + idx] + part[(4 * i + 1) * 32 + idx]) + (part[(4 * i + 2) * 32 + idx] + part[(4 * i + 3) * 32 + idx]);
-    return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-}
-
-// Round 4, attention_rnn role: the same reduction over 16 values (2 columns x 8 item slots) at a time.  Twice the rounds of
-// pb_reduce32 for the same number of DPP operations, but the GEMV's working set next to the weight registers halves
+// Sum 16 per-thread values (2 columns x 8 item slots) over the 512 threads of the workgroup: 16-lane transposing butterfly,
+// then the 32 row partials (8 waves x 4 rows) through LDS; the caller syncs and sums the partials it needs (pb_sum16).
+// Twice the rounds of a 32-value reduction for the same number of DPP operations, but the GEMV's working set next to the weight registers halves
 // (12 accumulator registers + 16 values instead of 24 + 32) — with 32-value rounds the role spilled loop-invariant offsets
 // and every reload sat behind an s_waitcnt vmcnt(0) on the chain.  The first two levels write complementary register banks
 // with bank-masked DPP adds (2 operations per output instead of select + select + add).  part[(wave * 4 + row) * 16 + idx].
@@ -307,155 +218,22 @@ __device__ __forceinline__ float pb_sum16(const float* part, int idx) {
     return ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
 }
 
-// ============================================================================================ chain D: decoder_rnn
-struct PBDArgs {
-    const float* w_hh_dec;      // (4096,1024)
-    const float* dHC;           // (T,B,1536): [:, :, :1024] = grad wrt h_dec from the projection
-    const float* GD;            // (T,B,4096) gate activations of decoder_rnn
-    const float* CD;            // (T+1,B,1024): CD[t+1] = c_dec(t) (pre-dropout), CD[0] = 0
-    float* DGD;                 // (T,B,4096) out
-    float* GX;                  // exchange: T rows of PB_ROW_BYTES, sentinel-filled
-    unsigned* err;
-    int B, T;
-    float p_dec;
-    uint64_t seed;
-    const t2v_step_params* step;
-};
-
-template <int NB>
-__global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd(PBDArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    f32x4* X0 = (f32x4*)lds;                               // [4096] items 0..3
-    f32x2* X1 = (f32x2*)(lds + 4 * T2V_G);           // [4096] items 4, 5
-    float* part = lds + (NB > 4 ? 6 : 4) * T2V_G;          // [32][32]
-    float* stage = part + 32 * 32;                         // [4 units][4 gates][8 items]
-    int* flag = (int*)(stage + 128);
-    const uint64_t seed = t2v_step_seed(a.seed, a.step);
-    const int wg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int B = a.B, T = a.T;
-    const __amdgpu_buffer_rsrc_t rX = t2v_rsrc(a.GX);
-    // W_hh_dec^T columns of this workgroup's 4 units: w[u][j] = W_hh_dec[k = tid + 512 j][4 wg + u]
-    f32x2 w[4][PB_KJ / 2];
-#pragma unroll
-    for (int j = 0; j < PB_KJ; ++j) {
-        const float4 w4 = *(const float4*)(a.w_hh_dec + (size_t)(tid + PB_THREADS * j) * T2V_H + 4 * wg);
-        w[0][j / 2][j & 1] = w4.x; w[1][j / 2][j & 1] = w4.y; w[2][j / 2][j & 1] = w4.z; w[3][j / 2][j & 1] = w4.w;
-    }
-    if (tid == 0) flag[0] = 1;
-    // cell threads: tid = u * 8 + b (u < 4, b < B)
-    const int cu = tid >> 3, cb = tid & 7;
-    const bool cell_on = tid < 32 && cb < B;
-    const int U = 4 * wg + (cu & 3);
-    const uint32_t idx = (uint32_t)cb * T2V_H + U;
-    float dcd = 0.f;                                        // grad wrt the (post-dropout) cell handed to step t+1
-    int nap = 0;
-    __syncthreads();
-
-    for (int t = T - 1; t >= 0; --t) {
-        float yd = 0.f;
-        if (t < T - 1) {
-            // dgd(t+1) from everybody, then this workgroup's 4 columns of W_hh_dec^T · dgd(t+1)
-            const int rounds = pb_gather_row<NB>(X0, X1, rX, (unsigned)(t + 1) * PB_ROW_BYTES(NB), B, nap, a.err, flag);
-            nap = t2v_adapt_nap(nap, rounds);
-            __syncthreads();
-            if (flag[0] != 1) return;
-            f32x2 acc[4][3];
-            pb_gemv<4, NB>(w, X0, X1, acc);
-            float v[32];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) { v[u * 8 + 2 * i] = acc[u][i][0]; v[u * 8 + 2 * i + 1] = acc[u][i][1]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u * 8 + 6] = v[u * 8 + 7] = 0.f;
-            pb_reduce32(v, part);
-            __syncthreads();
-            if (cell_on) yd = pb_sum32(part, tid);
-        }
-        if (tid < 64) {
-            // ---- cell backward of decoder_rnn(t) for (unit U, item cb)
-            float dg[4] = {0.f, 0.f, 0.f, 0.f};
-            if (cell_on) {
-                const float dh = a.dHC[((size_t)t * B + cb) * (T2V_H + T2V_E) + U] + yd;
-                const float* gp = a.GD + ((size_t)t * B + cb) * T2V_G + U;
-                const float gi = gp[0], gf = gp[T2V_H], gg = gp[2 * T2V_H], go = gp[3 * T2V_H];
-                const float cdc = a.CD[((size_t)(t + 1) * B + cb) * T2V_H + U];
-                float cprev = a.CD[((size_t)t * B + cb) * T2V_H + U];
-                const float fh = t2v_drop_scale(seed, T2V_RNG_DEC_H, t, idx, a.p_dec);
-                const float fc = t2v_drop_scale(seed, T2V_RNG_DEC_C, t, idx, a.p_dec);
-                if (t > 0) cprev *= t2v_drop_scale(seed, T2V_RNG_DEC_C, t - 1, idx, a.p_dec);
-                const float tc = tanhf_(cdc);
-                const float dht = dh * fh;
-                const float dct = dcd * fc + dht * go * (1.0f - tc * tc);
-                dg[0] = dct * gg * gi * (1.0f - gi);
-                dg[1] = dct * cprev * gf * (1.0f - gf);
-                dg[2] = dct * gi * (1.0f - gg * gg);
-                dg[3] = dht * tc * go * (1.0f - go);
-                dcd = dct * gf;
-                float* o = a.DGD + ((size_t)t * B + cb) * T2V_G + U;
-                o[0] = dg[0]; o[T2V_H] = dg[1]; o[2 * T2V_H] = dg[2]; o[3 * T2V_H] = dg[3];
-            }
-            // publish the 16 gate-gradient rows of this workgroup (only while somebody still needs them: t > 0)
-            if (t > 0) {
-                if (tid < 32) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) stage[((cu & 3) * 4 + r) * 8 + cb] = cb < B ? dg[r] : 0.f;
-                }
-                // (same wave: LDS operations of one wave complete in order)
-                if (tid < 16) {
-                    const int u = tid >> 2, r = tid & 3;
-                    const int k = r * T2V_H + 4 * wg + u;
-                    const float* sp = stage + (u * 4 + r) * 8;
-                    t2v_st(rX, (unsigned)t * PB_ROW_BYTES(NB) + 16u * (unsigned)k, f32x4{sp[0], sp[1], sp[2], sp[3]});
-                    if (NB > 4) t2v_st(rX, (unsigned)t * PB_ROW_BYTES(NB) + 65536u + 8u * (unsigned)k, f32x2{sp[4], sp[5]});
-                }
-            }
-        }
-        __syncthreads();            // part / stage / X are reused by the next step
-    }
-}
-
 static size_t pb_row_bytes(int B) { return B > 4 ? 98304u : 65536u; }
-static size_t pbd_lds_bytes(int B) { return sizeof(float) * ((B > 4 ? 6 : 4) * T2V_G + 32 * 32 + 128 + 4); }
 
 extern "C" int t2v_decoder_bwd_persist_supported(int B, int T_in) {
     if (!(B >= 1 && B <= PB_MAXB && T_in >= 1 && T_in <= PB_MAXT_LONG)) return 0;
     return t2v_persist_cus_ok();
 }
-// floats of exchange scratch for the decoder_rnn chain (t2v_decoder_bwd_dchain)
-extern "C" long t2v_decoder_bwd_dchain_scratch_floats(int B, int T_out) {
-    if (B < 1 || B > PB_MAXB || T_out < 1) return 0;
-    return (long)((size_t)T_out * pb_row_bytes(B) / 4);
-}
 
-extern "C" int t2v_decoder_bwd_dchain(const float* w_hh_dec, const float* dHC, const float* GD, const float* CD, float* DGD,
-                                      float* scratch, uint32_t* err_word, int B, int T_out, float p_dec, uint64_t seed, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!w_hh_dec || !dHC || !GD || !CD || !DGD || !scratch || !err_word || B < 1 || B > PB_MAXB || T_out < 1 || !t2v_persist_cus_ok())
-        return T2V_ERR_ARG;
-    if (((uintptr_t)scratch & 15) || (size_t)T_out * pb_row_bytes(B) >= 0x7fffffffull) return T2V_ERR_ARG;
-    static bool raised = false;
-    if (!t2v_persist_raise_lds({(const void*)k_dchain_bwd<4>, (const void*)k_dchain_bwd<6>}, raised)) return t2v_check_launch();
-    (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
-    t2v_fill_sentinel(scratch, (size_t)T_out * pb_row_bytes(B) / 16, 1024, stream);
-    PBDArgs a;
-    a.w_hh_dec = w_hh_dec; a.dHC = dHC; a.GD = GD; a.CD = CD; a.DGD = DGD; a.GX = scratch; a.err = err_word;
-    a.B = B; a.T = T_out; a.p_dec = p_dec; a.seed = seed; a.step = t2v_step_for(stream);
-    if (B > 4) k_dchain_bwd<6><<<T2V_NWG, PB_THREADS, pbd_lds_bytes(B), stream>>>(a);
-    else k_dchain_bwd<4><<<T2V_NWG, PB_THREADS, pbd_lds_bytes(B), stream>>>(a);
-    return t2v_check_launch();
-}
-
-// ======================================================================= chain A: attention_rnn + attention, one launch
+// ======================================================================= the reverse pass as one launch
 // Roles (one workgroup per CU):
 //   T : workgroups [0, B*S) — attention(t) backward of item b, encoder positions [s*JS, s*JS + JS) (the position-split
 //       body of decoder_bwd.hip: softmax / tanh / fused-location-filter backward), operands that do not change over the
 //       pass (memory rows, W_comb^T tile, v) resident in registers, the cumulative-weights gradient resident in LDS.
 //       Runs on the first 256 threads; waves 4..7 only keep the barriers company.
-//   L : the other workgroups — workgroup j owns hidden units [j*1024/NL, ..) (4 or 5) and context columns
-//       [j*512/NL, ..) (2 or 3): their columns of Wcat_att^T (attention_rnn) AND of Wcat_dec^T (decoder_rnn) live in
-//       registers (thread = 8 of the 4096 gate rows, <= 21 columns).  decoder_rnn's chain runs ONE STEP AHEAD in the
-//       shadow of attention(t): cell D(t-1), all-gather of dgd(t-1), D-GEMV(t-1) happen while the T workgroups work.
+//   A, D : the other NL = 256 - B*S workgroups, one set per LSTM cell (pba_na below): a workgroup owns a range of hidden
+//       units and of context columns and keeps their columns of Wcat_att^T (A) or Wcat_dec^T (D) in registers (thread = 8
+//       of the 4096 gate rows).  decoder_rnn's chain needs nothing of the attention path and free-runs ahead of it.
 // Per reverse step the dependency chain is
 //   all-gather dga(t+1) -> A-GEMV -> [d ctx(t)] -> hop -> attention(t) backward -> [dq(t)] -> hop -> W_q^T dq + cell A(t)
 //   -> [dga(t)] -> all-gather ...
@@ -799,47 +577,9 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
     PBA_PROF_FLUSH(blockIdx.x == 0, 8, 4);
 }
 
-// y[C0 + c][pair] = sum_j w[C0 + c][j] * x[k_j][pair] for NC of the thread's columns; one LDS operand per gate row with two
-// more in flight (the 168 weight registers leave no room for all eight)
-template <int NCT, int C0, int NC, int NB, int VS = 8>
-__device__ __forceinline__ void pb_gemv_cols(const f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const f32x2* X1, float (&v)[32]) {
-    const int tid = threadIdx.x;
-    f32x2 acc[NC][3];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c][0] = acc[c][1] = acc[c][2] = f32x2{0.f, 0.f};
-    constexpr int PF = 3;
-    f32x4 xa[PF];
-    f32x2 xb[PF];
-#pragma unroll
-    for (int d = 0; d < PF; ++d) {
-        xa[d] = X0[tid + PB_THREADS * d];
-        xb[d] = f32x2{0.f, 0.f};
-        if (NB > 4) xb[d] = X1[tid + PB_THREADS * d];
-    }
-#pragma unroll
-    for (int j = 0; j < PB_KJ; ++j) {
-        const f32x4 xc = xa[j % PF];
-        const f32x2 yc = xb[j % PF];
-        const f32x2 x01 = {xc[0], xc[1]}, x23 = {xc[2], xc[3]};
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            if (j & 1) pb_pk3<true>(acc[c][0], acc[c][1], acc[c][2], w[C0 + c][j / 2], x01, x23, yc);
-            else pb_pk3<false>(acc[c][0], acc[c][1], acc[c][2], w[C0 + c][j / 2], x01, x23, yc);
-        }
-        if (j + PF < PB_KJ) {
-            xa[j % PF] = X0[tid + PB_THREADS * (j + PF)];
-            if (NB > 4) xb[j % PF] = X1[tid + PB_THREADS * (j + PF)];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 32; ++i) v[i] = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { v[c * VS + 2 * i] = acc[c][i][0]; v[c * VS + 2 * i + 1] = acc[c][i][1]; }
-}
-
-// the same for <= 2 columns into v[16] (two columns x 8 item slots): the operand rows are re-read per round
+// y[C0 + c][pair] = sum_j w[C0 + c][j] * x[k_j][pair] for NC <= 2 of the thread's columns into v[16] (two columns x 8 item
+// slots); one LDS operand per gate row with three more in flight (the weight registers leave no room for all eight), and
+// the operand rows are re-read per round
 template <int NCT, int C0, int NC, int NB>
 __device__ __forceinline__ void pb_gemv_cols16(const f32x2 (&w)[NCT][PB_KJ / 2], const f32x4* X0, const f32x2* X1, float (&v)[16]) {
     static_assert(NC >= 1 && NC <= 2, "one or two columns");
@@ -912,12 +652,6 @@ __host__ __device__ static inline int pba_na(int NL) {
     if (NL - 128 >= 86) return NL - 128;
     const int n = (3 * NL + 4) / 8;
     return n < 79 ? 79 : n;
-}
-
-// final sums of a column-grouped GEMV: NCOL columns x 8 item slots -> ysum[col * 8 + b]
-__device__ __forceinline__ void pba_finish_sums(const float* part, float* ysum, int ncol) {
-    const int tid = threadIdx.x;
-    if (tid < ncol * 8) ysum[tid] = pb_sum32(part + (tid >> 5) * 1024, tid & 31);
 }
 
 // poll one word of a sentinel-filled array until it is written (bounded)
@@ -1390,33 +1124,6 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
 #endif
 }
 
-// Round 4: the same roles as TWO launches on two streams — the attention chain (T + A roles, NT + NA workgroups) and the
-// free-running decoder_rnn chain (D role, ND workgroups).  Together they still fill the chip and talk through the same
-// sentinel-filled arrays; but the decoder_rnn chain ends ~20 % earlier (8.5 vs 10.5 us per step), and as a launch of its own
-// its END is something a stream can wait for: the two decoder_rnn weight-gradient GEMMs (which need all of DGD and nothing
-// of the other chain) are queued behind it and run on the CUs it frees while the attention chain is still going.
-template <int NB, bool LONG>
-__global__ __launch_bounds__(PB_THREADS) void k_achain_bwd_ta(PBAArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int wg = blockIdx.x;
-    const int S = a.S_sl, NT = a.B * S, NL = T2V_NWG - NT, NA = pba_na(NL);
-    if (wg < NT) {
-        if (LONG) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB);
-        else if (a.T_in <= 128) pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
-        else pba_attention_role<32, 4>(a, lds, wg / S, wg % S, NB);
-    } else {
-        if (NA >= 114) pba_attention_rnn_role<NB, 9, 5>(a, lds, wg - NT, NA);
-        else if (NA >= 86) pba_attention_rnn_role<NB, 12, 6>(a, lds, wg - NT, NA);
-        else pba_attention_rnn_role<NB, PBA_NUA, PBA_NCA>(a, lds, wg - NT, NA);
-    }
-}
-template <int NB>
-__global__ __launch_bounds__(PB_THREADS) void k_dchain_bwd_free(PBAArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int S = a.S_sl, NT = a.B * S, NL = T2V_NWG - NT, NA = pba_na(NL), ND = NL - NA;
-    pba_decoder_role<NB>(a, lds, blockIdx.x, ND);
-}
-
 // slice geometry of the one-launch reverse pass: the launch-per-step geometry up to PB_MAXT symbols, 96-position slices beyond
 static inline int pba_js(int T_in) { return T_in > PB_MAXT ? 96 : t2v_attn_bwd_js(T_in); }
 static inline int pba_slices(int T_in) { const int js = pba_js(T_in); return (T_in + js - 1) / js; }
@@ -1430,41 +1137,47 @@ static size_t pba_lds_bytes(int B, int T_in) {
     return sizeof(float) * (lrole > trole ? lrole : trole);
 }
 
-// exchange scratch of the attention chain (floats): gate-gradient rows of both cells, context gradients, window partials.
-// The dq partials (T,B,S,128) are an OUTPUT (the caller reduces them into d W_q) and are passed separately.
+// The sections of `scratch`, in floats and in this order (what every host function below reads):
+//   GXA, GXD   n_gx each   (dc, dh) rows of attention_rnn / decoder_rnn: half a gate row per step (PB_DROW_BYTES)
+//   CX         n_cx        context-gradient rows (PB_CX_ROW_BYTES)
+//   GPX        n_gp        window partials of the attention slices
+//   EX         n_ex        E(t) (T,B,1536), decoder_rnn's contribution to d h_att(t) / d ctx(t)
+//   DQT        n_dqt       dq(t) summed over the slices, B padded to 8 (16-byte rows)
+//   -- up to here exchange arrays: sentinel-filled by the preparation --
+//   FA, FD     n_f each    gate-gradient factors of both cells (k_pb_factors): a gate row per step
+//   CPA, CPD   n_cp each   cell-layout factors of both cells (k_pb_cellpre)
+// The dq partials DQP (T,B,S,128), n_dq floats, are an OUTPUT (the caller passes them separately) and not part of scratch.
+struct PBALayout {
+    size_t n_gx, n_cx, n_gp, n_ex, n_dqt, n_f, n_cp, n_dq;
+    size_t dqt_off() const { return 2 * n_gx + n_cx + n_gp + n_ex; }
+    size_t n_exchange() const { return dqt_off() + n_dqt; }
+    size_t total() const { return n_exchange() + 2 * n_f + 2 * n_cp; }
+};
+static PBALayout pba_layout(int B, int T_in, int T_out) {
+    const size_t T = (size_t)T_out, S = (size_t)pba_slices(T_in), gpw = pba_js(T_in) + 30 <= 64 ? 64 : 128;
+    const size_t rowf = pb_row_bytes(B) / 4, cxf = (size_t)(B > 4 ? 32768 : 16384) / 4;
+    PBALayout l;
+    l.n_gx = T * rowf / 2;
+    l.n_cx = T * cxf;
+    l.n_gp = T * B * S * 2 * gpw;
+    l.n_ex = T * B * T2V_KATT;
+    l.n_dqt = T * 8 * T2V_A;
+    l.n_f = T * rowf;
+    l.n_cp = T * T2V_H * (B > 4 ? 6 : 4) * 8;
+    l.n_dq = T * B * S * 128;
+    return l;
+}
+
 extern "C" long t2v_decoder_bwd_achain_scratch_floats(int B, int T_in, int T_out) {
     if (B < 1 || B > PB_MAXB || T_in < 1 || T_in > PB_MAXT_LONG || T_out < 1) return 0;
-    const size_t S = (size_t)pba_slices(T_in), gpw = pba_js(T_in) + 30 <= 64 ? 64 : 128;
-    const size_t cx = (size_t)T_out * (B > 4 ? 32768 : 16384) / 4;
-    // (dc, dh) rows of both cells (half a gate row each) + context rows + window partials + E + the two factor arrays
-    const size_t cp = 2 * (size_t)T_out * T2V_H * (B > 4 ? 6 : 4) * 8;   // cell-layout factors of both cells (k_pb_cellpre)
-    const size_t dqt = (size_t)T_out * 8 * T2V_A;                         // dq(t) summed over the slices (B padded to 8: 16-byte rows)
-    return (long)((size_t)T_out * pb_row_bytes(B) / 4 + cx + (size_t)T_out * B * S * 2 * gpw + (size_t)T_out * B * T2V_KATT + dqt +
-                  2 * (size_t)T_out * pb_row_bytes(B) / 4 + cp);
+    return (long)pba_layout(B, T_in, T_out).total();
 }
 
 // float offset, inside `scratch`, of dq(t) summed over the position slices — (T_out, B, 128), complete when the pass has ended:
 // the d W_q product of the caller reads it there (the sum over the slice axis of DQP was a reduction launch behind the pass)
 extern "C" long t2v_decoder_bwd_achain_dq_offset(int B, int T_in, int T_out) {
     if (!t2v_decoder_bwd_persist_supported(B, T_in) || T_out < 1) return -1;
-    const int S = pba_slices(T_in);
-    const size_t gpw = pba_js(T_in) + 30 <= 64 ? 64 : 128;
-    const size_t rowf = pb_row_bytes(B) / 4, cxf = (size_t)(B > 4 ? 32768 : 16384) / 4;
-    const size_t n_gx = (size_t)T_out * rowf / 2, n_cx = (size_t)T_out * cxf, n_gp = (size_t)T_out * B * S * 2 * gpw;
-    const size_t n_ex = (size_t)T_out * B * T2V_KATT;
-    return (long)(2 * n_gx + n_cx + n_gp + n_ex);
-}
-
-extern "C" int t2v_decoder_bwd_achain2(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
-                                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
-                                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                                       void* stream_, void* stream_d_);
-extern "C" int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
-                                      const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
-                                      uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                                      void* stream_) {
-    return t2v_decoder_bwd_achain2(w, w_unused, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed,
-                                   stream_, nullptr);
+    return (long)pba_layout(B, T_in, T_out).dqt_off();
 }
 
 // do_prepare: error word, sentinel fills, the factor arrays of both cells (functions of the forward activations alone: they may
@@ -1472,32 +1185,24 @@ extern "C" int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, co
 static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s,
                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                      void* stream_, void* stream_d_, bool do_prepare, bool do_run) {
-    hipStream_t stream = (hipStream_t)stream_, stream_d = (hipStream_t)stream_d_;
+                      void* stream_, bool do_prepare, bool do_run) {
+    hipStream_t stream = (hipStream_t)stream_;
     if (!s || !DQP || !scratch || !err_word) return T2V_ERR_ARG;
     if (do_run && (!w || !dHC || !DGA || !DGD || !DCTX || !DV)) return T2V_ERR_ARG;
     if (!t2v_decoder_bwd_persist_supported(B, T_in) || T_out < 1) return T2V_ERR_ARG;
     if (do_run && (!w->w_ih_att || !w->w_hh_att || !w->w_ih_dec || !w->w_hh_dec || !w->wq || !w->wcomb || !w->v)) return T2V_ERR_ARG;
     if (!s->memory || !s->XS || !s->CA || !s->CD || !s->GA || !s->GD || !s->AL || !s->S) return T2V_ERR_ARG;
-    const int S = pba_slices(T_in);
-    const size_t gpw = pba_js(T_in) + 30 <= 64 ? 64 : 128;
-    const size_t rowf = pb_row_bytes(B) / 4, cxf = (size_t)(B > 4 ? 32768 : 16384) / 4;
-    const size_t n_gx = (size_t)T_out * rowf / 2, n_f = (size_t)T_out * rowf, n_cx = (size_t)T_out * cxf, n_dq = (size_t)T_out * B * S * 128;
-    const size_t n_gp = (size_t)T_out * B * S * 2 * gpw;
-    const size_t n_ex = (size_t)T_out * B * T2V_KATT, n_dqt = (size_t)T_out * 8 * T2V_A;
-    if (((uintptr_t)scratch & 15) || ((uintptr_t)DQP & 15) || n_gx * 4 >= 0x7fffffffull || n_dq * 4 >= 0x7fffffffull) return T2V_ERR_ARG;
+    const PBALayout l = pba_layout(B, T_in, T_out);
+    if (((uintptr_t)scratch & 15) || ((uintptr_t)DQP & 15) || l.n_gx * 4 >= 0x7fffffffull || l.n_dq * 4 >= 0x7fffffffull) return T2V_ERR_ARG;
     if (pba_lds_bytes(B, T_in) > T2V_LDS_MAX) return T2V_ERR_ARG;
     static bool raised = false;
-    if (!t2v_persist_raise_lds({(const void*)k_achain_bwd<4, false>, (const void*)k_achain_bwd<6, false>, (const void*)k_achain_bwd_ta<4, false>,
-                                (const void*)k_achain_bwd_ta<6, false>, (const void*)k_achain_bwd<4, true>, (const void*)k_achain_bwd<6, true>,
-                                (const void*)k_achain_bwd_ta<4, true>, (const void*)k_achain_bwd_ta<6, true>, (const void*)k_dchain_bwd_free<4>,
-                                (const void*)k_dchain_bwd_free<6>},
-                               raised))
+    if (!t2v_persist_raise_lds({(const void*)k_achain_bwd<4, false>, (const void*)k_achain_bwd<6, false>,
+                                (const void*)k_achain_bwd<4, true>, (const void*)k_achain_bwd<6, true>}, raised))
         return t2v_check_launch();
     if (do_prepare) {
         (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
-        t2v_fill_sentinel(scratch, (2 * n_gx + n_cx + n_gp + n_ex + n_dqt) / 4, 1024, stream);
-        t2v_fill_sentinel(DQP, n_dq / 4, 256, stream);
+        t2v_fill_sentinel(scratch, l.n_exchange() / 4, 1024, stream);
+        t2v_fill_sentinel(DQP, l.n_dq / 4, 256, stream);
     }
     PBAArgs a;
     if (do_run) {
@@ -1505,16 +1210,21 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
         a.wq = w->wq; a.wcomb = w->wcomb; a.v = w->v;
     }
     a.memory = s->memory; a.XS = s->XS; a.CA = s->CA; a.CD = s->CD; a.GA = s->GA; a.GD = s->GD; a.AL = s->AL; a.S = s->S;
-    a.dHC = dHC; a.DGA = DGA; a.DGD = DGD; a.DCTX = DCTX; a.DV = DV;
-    a.GXA = scratch; a.GXD = scratch + n_gx; a.CX = scratch + 2 * n_gx; a.GPX = scratch + 2 * n_gx + n_cx; a.EX = scratch + 2 * n_gx + n_cx + n_gp; a.DQX = DQP;
-    a.DQT = scratch + 2 * n_gx + n_cx + n_gp + n_ex;
-    float* FA = a.DQT + n_dqt;
-    float* FD = FA + n_f;
-    float* CPA = FD + n_f;
-    float* CPD = CPA + (size_t)T_out * T2V_H * (B > 4 ? 6 : 4) * 8;
+    a.dHC = dHC; a.DGA = DGA; a.DGD = DGD; a.DCTX = DCTX; a.DV = DV; a.DQX = DQP;
+    // the walk over the sections of pba_layout, in its order
+    a.GXA = scratch;
+    a.GXD = a.GXA + l.n_gx;
+    a.CX = a.GXD + l.n_gx;
+    a.GPX = a.CX + l.n_cx;
+    a.EX = a.GPX + l.n_gp;
+    a.DQT = a.EX + l.n_ex;
+    float* FA = a.DQT + l.n_dqt;
+    float* FD = FA + l.n_f;
+    float* CPA = FD + l.n_f;
+    float* CPD = CPA + l.n_cp;
     a.FA = FA; a.FD = FD; a.CPA = CPA; a.CPD = CPD;
     a.err = err_word;
-    a.B = B; a.T_in = T_in; a.T = T_out; a.S_sl = S; a.p_att = p_att; a.p_dec = p_dec; a.seed = seed;
+    a.B = B; a.T_in = T_in; a.T = T_out; a.S_sl = pba_slices(T_in); a.p_att = p_att; a.p_dec = p_dec; a.seed = seed;
     a.step = t2v_step_for(stream);
     a.prof = g_t2v_prof;
     if (do_prepare) {
@@ -1528,54 +1238,36 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
     }
     if (!do_run) return t2v_check_launch();
     const size_t lds = pba_lds_bytes(B, T_in);
-    const bool lng = T_in > PB_MAXT;
-    if (!stream_d || stream_d == stream) {
-        if (lng) {
-            if (B > 4) k_achain_bwd<6, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
-            else k_achain_bwd<4, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
-        } else {
-            if (B > 4) k_achain_bwd<6, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
-            else k_achain_bwd<4, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
-        }
-        return t2v_check_launch();
-    }
-    // two launches: stream_d joins `stream` here (fills / factor kernels above), the caller joins it back (DGD is complete when
-    // stream_d is, everything else when `stream` is)
-    static thread_local hipEvent_t ev = nullptr;
-    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return t2v_check_launch();
-    if (hipEventRecord(ev, stream) != hipSuccess || hipStreamWaitEvent(stream_d, ev, 0) != hipSuccess) return t2v_check_launch();
-    const int NT = B * S, NL = T2V_NWG - NT, NA = pba_na(NL), ND = NL - NA;
-    if (B > 4) {
-        k_dchain_bwd_free<6><<<ND, PB_THREADS, lds, stream_d>>>(a);
-        if (lng) k_achain_bwd_ta<6, true><<<NT + NA, PB_THREADS, lds, stream>>>(a);
-        else k_achain_bwd_ta<6, false><<<NT + NA, PB_THREADS, lds, stream>>>(a);
+    if (T_in > PB_MAXT) {
+        if (B > 4) k_achain_bwd<6, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
+        else k_achain_bwd<4, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
     } else {
-        k_dchain_bwd_free<4><<<ND, PB_THREADS, lds, stream_d>>>(a);
-        if (lng) k_achain_bwd_ta<4, true><<<NT + NA, PB_THREADS, lds, stream>>>(a);
-        else k_achain_bwd_ta<4, false><<<NT + NA, PB_THREADS, lds, stream>>>(a);
+        if (B > 4) k_achain_bwd<6, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
+        else k_achain_bwd<4, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
     }
     return t2v_check_launch();
 }
 
-extern "C" int t2v_decoder_bwd_achain2(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
-                                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
-                                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                                       void* stream_, void* stream_d_) {
+// preparation + pass
+extern "C" int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
+                                      const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
+                                      uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
+                                      void* stream_) {
     (void)w_unused;
-    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, stream_d_, true, true);
+    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true, true);
 }
 
-// Round 4: the preparation of the reverse pass on its own (everything it needs exists when the FORWARD pass has ended) ...
+// The preparation on its own (everything it needs exists when the FORWARD pass has ended) ...
 extern "C" int t2v_decoder_bwd_achain_prepare(const t2v_dec_train_bufs* s, float* DQP, float* scratch, uint32_t* err_word, int B, int T_in,
                                               int T_out, float p_att, float p_dec, uint64_t seed, void* stream_) {
     return pba_launch(nullptr, s, nullptr, nullptr, nullptr, nullptr, nullptr, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed,
-                      stream_, nullptr, true, false);
+                      stream_, true, false);
 }
-// ... and the pass without it (same arguments as t2v_decoder_bwd_achain2; scratch / DQP / err_word as handed to _prepare)
+// ... and the pass without it (same arguments as t2v_decoder_bwd_achain; scratch / DQP / err_word as handed to _prepare)
 extern "C" int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
                                                const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                                uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                                               void* stream_, void* stream_d_) {
+                                               void* stream_) {
     (void)w_unused;
-    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, stream_d_, false, true);
+    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false, true);
 }

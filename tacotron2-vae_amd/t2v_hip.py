@@ -4,6 +4,7 @@ the boundary modules in model.py call.
 There is no CPU fallback: every op raises `T2VHipError` when the shared library or a GPU
 is missing, so a silent eager path can never stand in for the HIP kernels.
 """
+import collections
 import ctypes as C
 import os
 
@@ -81,8 +82,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_attn_bwd_slices', 't2v_colsum', 't2v_colsum_scratch_floats', 't2v_gemm_epilogue_bwd',
            't2v_decoder_train_fwd_persistent', 't2v_decoder_train_persist_supported',
            't2v_decoder_train_persist_scratch_floats', 't2v_decoder_bwd_persist_supported',
-           't2v_decoder_bwd_dchain_scratch_floats', 't2v_decoder_bwd_dchain', 't2v_decoder_bwd_achain_scratch_floats',
-           't2v_decoder_bwd_achain', 't2v_decoder_bwd_achain2', 't2v_decoder_bwd_achain_prepare',
+           't2v_decoder_bwd_achain_scratch_floats', 't2v_decoder_bwd_achain', 't2v_decoder_bwd_achain_prepare',
            't2v_decoder_bwd_achain_prepared', 't2v_decoder_bwd_persist_slices', 't2v_decoder_bwd_achain_dq_offset', 't2v_mask_outputs', 't2v_reparam_fwd',
            't2v_reparam_bwd', 't2v_gather_words', 't2v_concat2_rows',
            't2v_decoder_train_fwd_persistent16', 't2v_decoder_train_persist16_supported',
@@ -154,18 +154,14 @@ def load_library():
     lib.t2v_decoder_train_persist_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_decoder_train_persist_scratch_floats.restype = C.c_long
     lib.t2v_decoder_bwd_persist_supported.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_dchain_scratch_floats.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_dchain_scratch_floats.restype = C.c_long
-    lib.t2v_decoder_bwd_dchain.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_void_p]
     lib.t2v_decoder_bwd_achain_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_decoder_bwd_achain_scratch_floats.restype = C.c_long
     lib.t2v_decoder_bwd_achain.argtypes = [C.POINTER(_DecTrainPersistWeights), C.c_void_p, C.POINTER(_DecTrainBufs)] + [C.c_void_p] * 8 + [
         C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_bwd_achain2.argtypes = lib.t2v_decoder_bwd_achain.argtypes + [C.c_void_p]
     lib.t2v_decoder_bwd_persist_slices.argtypes = [C.c_int]
     lib.t2v_decoder_bwd_achain_dq_offset.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_decoder_bwd_achain_dq_offset.restype = C.c_long
-    lib.t2v_decoder_bwd_achain_prepared.argtypes = lib.t2v_decoder_bwd_achain2.argtypes
+    lib.t2v_decoder_bwd_achain_prepared.argtypes = lib.t2v_decoder_bwd_achain.argtypes
     lib.t2v_decoder_bwd_achain_prepare.argtypes = [C.POINTER(_DecTrainBufs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                    C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.t2v_decoder_replay_fwd_kernels.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecTrainBufs), C.c_int,
@@ -410,7 +406,7 @@ _STEP_ALL = []
 class Overlap(object):
     # reference-encoder branch; deferred ("nobody waits for it") work: weight gradients, Prenet; the four chip-filling LSTM
     # weight-gradient GEMMs of the decoder get a stream of their own so the long tail of small deferred kernels runs next to them
-    # 'd': the free-running decoder_rnn chain of the persistent reverse pass and, behind it, its two weight-gradient GEMMs
+    # 'd': idle — the step has no work for it any more; it stays so that every stream created after these keeps its pooled handle
     NAMES = ('vae', 'w', 'g', 'd')
 
     def __init__(self, device=None):
@@ -839,6 +835,54 @@ def _f32c(t):
 
 MAX_DEC_B = 16      # batch columns of one MFMA tile in the per-step kernels; larger batches run in chunks
 
+# ---- the kernel sets of the teacher-forced decoder.  DecoderCore.plan() picks one forward and one reverse engine per batch
+# chunk; _fwd_chunk(), backward() and the replay_* functions read the engine's record and never choose themselves.
+# Library entry points are held by name.  The launch-per-step pair ('steps') has no record: it is the general path.
+_FwdEngine = collections.namedtuple('_FwdEngine', 'kernel scratch run')
+_FWD_ENGINES = {
+    'persist': _FwdEngine('k_dec_train_persist', 't2v_decoder_train_persist_scratch_floats', 't2v_decoder_train_fwd_persistent'),
+    'persist16': _FwdEngine('k_dec_train_persist16', 't2v_decoder_train_persist16_scratch_floats',
+                            't2v_decoder_train_fwd_persistent16'),
+}
+# slices / scratch / dq_offset: size queries.  dq_rows: row stride of the (T, rows, 128) view of dq(t) inside scratch (None = the
+# chunk's batch).  prepare / prepared / run: the preparation alone, the pass behind it, both in one call.  arena_prepare: the
+# preparation reads the forward arena (its factor arrays) and takes the dropout arguments; reserved: prepared / run take the
+# header's `reserved` pointer behind the weights.  keep: arena tensors the preparation reads on the deferred-work stream.
+_BwdEngine = collections.namedtuple('_BwdEngine', 'kernel slices scratch dq_offset dq_rows prepare prepared run arena_prepare '
+                                                  'reserved keep')
+_BWD_ENGINES = {
+    'achain': _BwdEngine('k_achain_bwd', 't2v_decoder_bwd_persist_slices', 't2v_decoder_bwd_achain_scratch_floats',
+                         't2v_decoder_bwd_achain_dq_offset', None, 't2v_decoder_bwd_achain_prepare',
+                         't2v_decoder_bwd_achain_prepared', 't2v_decoder_bwd_achain', True, True, ('XS', 'CA', 'CD', 'GA', 'GD')),
+    'persist16': _BwdEngine('k_bwd_persist16', 't2v_decoder_bwd_persist16_slices', 't2v_decoder_bwd_persist16_scratch_floats',
+                            't2v_decoder_bwd_persist16_dq_offset', 16, 't2v_decoder_bwd_persistent16_prepare',
+                            't2v_decoder_bwd_persistent16_prepared', 't2v_decoder_bwd_persistent16', False, False, ('XS',)),
+}
+_STEPS_KERNELS = {'fwd': 'k_lstm_fwd256 + k_attn_fwd', 'bwd': 'k_lstm_bwd256 + k_attn_cell_bwd'}
+# the forward arena of a chunk, in the order DecoderCore keeps it (last_call[3], ctx.chunks): the fields of t2v_dec_train_bufs
+_ARENA = tuple(n for n, _ in _DecTrainBufs._fields_)
+# one batch chunk [b0, b1): fwd 'persist' | 'persist16' | 'steps'; bwd 'achain' | 'persist16' | 'steps' | None (no gradient);
+# prepare: the reverse pass's preparation is issued right behind the forward launch
+ChunkPlan = collections.namedtuple('ChunkPlan', 'b0 b1 fwd bwd prepare')
+
+
+def _chunk_seed(seed, b0):
+    """dropout seed of the batch chunk that starts at item b0 (the same in the forward and the reverse pass)"""
+    return (int(seed) + 7919 * b0) & 0x7FFFFFFFFFFFFFFF
+
+
+def _persist_weights(raw, bias_dec, wcomb, vv):
+    w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, wq = raw
+    return _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq), _p(wcomb), _p(vv))
+
+
+def _bwd_launch(lib, eng, prepared, PW, Sb, bufs, dims):
+    """one-launch reverse pass of engine `eng`: bufs = (dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word),
+    dims = (B, T_in, T, p_att, p_dec, seed); prepared: the preparation has been issued on these buffers"""
+    name = eng.prepared if prepared else eng.run
+    head = (C.byref(PW), None, C.byref(Sb)) if eng.reserved else (C.byref(PW), C.byref(Sb))
+    _check(getattr(lib, name)(*(head + tuple(_p(t) for t in bufs) + tuple(dims) + (_stream(),))), name)
+
 
 def replay_fwd_kernels(kernel_mask):
     """Re-issue the k_lstm_fwd256 (mask 1) / k_attn_fwd (mask 2) launches of the most recent DecoderCore.forward
@@ -858,10 +902,9 @@ def replay_persistent_forward():
     if DecoderCore.last_persist is None:
         raise T2VHipError("replay_persistent_forward: the last forward pass did not run on the persistent kernel (or "
                           "DecoderCore.keep_last was off)")
-    PW, Sb, scratch, (B, T_in, T, p_att, p_dec, seed), _keep = DecoderCore.last_persist
-    lib = load_library()
-    fn = lib.t2v_decoder_train_fwd_persistent16 if DecoderCore.last_kernel == 'k_dec_train_persist16' else lib.t2v_decoder_train_fwd_persistent
-    _check(fn(C.byref(PW), C.byref(Sb), _p(scratch), B, T_in, T, p_att, p_dec, seed, _stream()), 't2v_decoder_train_fwd_persistent')
+    PW, Sb, scratch, dims, _keep = DecoderCore.last_persist
+    eng = _FWD_ENGINES['persist16' if DecoderCore.last_kernel == _FWD_ENGINES['persist16'].kernel else 'persist']
+    _check(getattr(load_library(), eng.run)(C.byref(PW), C.byref(Sb), _p(scratch), *(tuple(dims) + (_stream(),))), eng.run)
     return 1
 
 
@@ -871,15 +914,9 @@ def replay_persistent_backward():
     if DecoderCore.last_bwd_persist is None:
         raise T2VHipError("replay_persistent_backward: the last backward pass did not run on the persistent kernel (or "
                           "DecoderCore.keep_last was off)")
-    PW, Sb, (dhc, DGA, DGD, DCTX, DV, DQP, scratch, errw), (B, T_in, T, p_att, p_dec, seed), _keep = DecoderCore.last_bwd_persist
-    if DecoderCore.last_bwd_kernel == 'k_bwd_persist16':
-        _check(load_library().t2v_decoder_bwd_persistent16(C.byref(PW), C.byref(Sb), _p(dhc), _p(DGA), _p(DGD), _p(DCTX), _p(DV), _p(DQP),
-                                                           _p(scratch), _p(errw), B, T_in, T, p_att, p_dec, seed, _stream()),
-               't2v_decoder_bwd_persistent16')
-        return 1
-    _check(load_library().t2v_decoder_bwd_achain(C.byref(PW), None, C.byref(Sb), _p(dhc), _p(DGA), _p(DGD), _p(DCTX), _p(DV), _p(DQP),
-                                                 _p(scratch), _p(errw), B, T_in, T, p_att, p_dec, seed, _stream()),
-           't2v_decoder_bwd_achain')
+    PW, Sb, bufs, dims, _keep = DecoderCore.last_bwd_persist
+    eng = _BWD_ENGINES['persist16' if DecoderCore.last_bwd_kernel == _BWD_ENGINES['persist16'].kernel else 'achain']
+    _bwd_launch(load_library(), eng, False, PW, Sb, bufs, dims)
     return 1
 
 
@@ -932,87 +969,111 @@ class DecoderCore(torch.autograd.Function):
     outputs: HC (T,B,1536) = [h_dec_t | ctx_t],  alignments (B,T,T_in)
     Batches larger than 16 run as independent chunks of <= 16 items (the loop has no cross-item coupling), so the
     reference's default batch_size = 64 works; weight gradients are summed over the chunks.
+    forward() asks plan() once which kernels every chunk runs on and carries the answer on the autograd context.
     """
-    last_call = None
-    last_bwd = None
-    keep_last = False       # bench / tests: keep the (first chunk's) arena of the last forward for replays
-
+    # ---- switches (read by plan() alone)
     # T2V_TRAIN_PERSISTENT=0 forces the launch-per-step forward; the default takes the one-launch persistent kernel
     # (csrc/decoder_train_persist.hip) whenever t2v_decoder_train_persist_supported(B, T_in): B <= 6, T_in <= 560
     persistent = None
     persistent_bwd = None   # same switch for the reverse pass (env T2V_BWD_PERSISTENT, default: as T2V_TRAIN_PERSISTENT)
-    last_bwd_mode = None
-    last_mode = None        # 'persistent' | 'launch-per-step' of the most recent forward chunk (bench / tests)
-    last_bwd_persist = None
-    last_persist = None     # keep_last: (weights, bufs, scratch, dims, tensors) of the last persistent forward, for replays
     # round 5: under bf16_run, batches of 7..16 items take the MFMA-batched persistent forward (csrc/decoder_train_persist16.hip:
     # bf16 weight tiles in registers, the batch is the N dimension of the MFMA).  None: on (env T2V_PERSIST16=0 switches it
     # off); False: off; 'force': also for B <= 6, where the fp32-weight kernel is the default (tests)
     persistent16 = None
+    # ---- what the most recent call ran on (written by _note() alone; bench / tests / tools read them)
+    keep_last = False       # bench / tests: keep the (first chunk's) arena of the last forward for replays
+    last_call = None        # keep_last: (weights, bufs, dims, arena + constants) of the first chunk of the last forward
+    last_persist = None     # keep_last: (weights, bufs, scratch, dims, tensors) of the last persistent forward, for replays
+    last_bwd = None         # keep_last: the same for the launch-per-step / ...
+    last_bwd_persist = None     # ... the one-launch reverse pass of the first chunk
+    last_mode = None        # 'persistent' | 'launch-per-step' of the most recent forward chunk
+    last_bwd_mode = None
     last_kernel = None      # name of the forward kernel of the most recent chunk
     last_bwd_kernel = None
     chunk_kernels = []      # forward kernel of every chunk of the most recent forward, in batch order (a step can mix them)
     chunk_bwd_kernels = []  # ... and of the most recent reverse pass
 
     @staticmethod
-    def use_persistent16(lib, B, T_in, T):
-        flag = DecoderCore.persistent16
-        if flag is None:
-            flag = os.environ.get('T2V_PERSIST16', '1') != '0'
-        if not flag or not _BF16:
-            return False
-        gate = DecoderCore.persistent
-        if gate is None:
-            gate = os.environ.get('T2V_TRAIN_PERSISTENT', '1') != '0'
-        if not gate or not lib.t2v_decoder_train_persist16_supported(int(B), int(T_in)):
-            return False
-        if flag != 'force' and DecoderCore.use_persistent(lib, B, T_in, T):
-            return False            # B <= 6: the fp32-weight persistent kernel
-        return 4 * lib.t2v_decoder_train_persist16_scratch_floats(int(B), int(T_in), int(T)) < 2 ** 31 - 1
+    def plan(lib, B, T_in, T, need_grad):
+        """The kernels of one call: a ChunkPlan per chunk of <= MAX_DEC_B items.  The only reader of the class switches, of
+        bf16_run and of T2V_TRAIN_PERSISTENT / T2V_BWD_PERSISTENT / T2V_PERSIST16 / T2V_PERSIST16_BWD, and the only caller of
+        the library's *_supported / *_fits / *_scratch_floats queries.  A class switch that is not None wins over its variable.
+
+        Switches.  Forward: DecoderCore.persistent, else T2V_TRAIN_PERSISTENT != '0'.  Reverse: DecoderCore.persistent_bwd, else
+        T2V_BWD_PERSISTENT != '0', which defaults to T2V_TRAIN_PERSISTENT (measured, B = 6, T_in = 84, T = 400, round 3: 12.9 us
+        per reverse step against 18.2 for the launch-per-step pass; both kernels want the GPU to themselves).  bf16 kernels:
+        DecoderCore.persistent16, else T2V_PERSIST16 != '0'; they exist under bf16_run only.
+
+        Forward engine of a chunk of b items:
+          'persist'    forward switch on, t2v_decoder_train_persist_supported(b, T_in) (b <= 6, T_in <= 560), and its scratch
+                       below 2^31 - 1 bytes (31-bit buffer offsets);
+          'persist16'  bf16 switch and forward switch on, t2v_decoder_train_persist16_supported(b, T_in) (b <= 16), scratch
+                       below 2^31 - 1 bytes — and 'persist' not possible, unless persistent16 == 'force';
+          'steps'      otherwise (launch per step).
+        Reverse engine of a chunk (need_grad only; None without):
+          'achain'     reverse switch on, t2v_decoder_bwd_persist_supported(b, T_in) (b <= 6, T_in <= 576), scratch below
+                       2^31 - 1 bytes;
+          'persist16'  bf16 switch on, T2V_PERSIST16_BWD != '0', reverse switch on, t2v_decoder_bwd_persist16_fits(b, T_in, T)
+                       (supported AND every exchange array below the kernel's 31-bit buffer offsets at this T: a long
+                       utterance leaves it HERE, not after the forward) — and 'achain' not possible, unless 'force';
+          'steps'      otherwise — and then for EVERY chunk of the call: the launch-per-step pass reads transposed weight
+                       packs that one call either builds or does not.
+        The 16 forward follows the forward switch, the 16 reverse pass the reverse switch.  The preparation of a one-launch
+        reverse pass is issued behind the forward launch when that chunk's forward is a persistent kernel too."""
+        D = DecoderCore
+        env = os.environ.get
+        fwd_on = D.persistent if D.persistent is not None else env('T2V_TRAIN_PERSISTENT', '1') != '0'
+        bwd_on = D.persistent_bwd if D.persistent_bwd is not None else env('T2V_BWD_PERSISTENT', env('T2V_TRAIN_PERSISTENT', '1')) != '0'
+        on16 = D.persistent16 if D.persistent16 is not None else env('T2V_PERSIST16', '1') != '0'
+        force = on16 == 'force'
+        on16 = bool(on16) and bool(_BF16)
+        small = lambda floats: 4 * floats < 2 ** 31 - 1
+        chunks = [(b0, min(B, b0 + MAX_DEC_B)) for b0 in range(0, B, MAX_DEC_B)]
+        fwd, bwd = [], []
+        for b0, b1 in chunks:
+            b = b1 - b0
+            p32 = bool(fwd_on) and bool(lib.t2v_decoder_train_persist_supported(b, T_in)) and \
+                small(lib.t2v_decoder_train_persist_scratch_floats(b, T_in, T))
+            f16 = on16 and bool(fwd_on) and bool(lib.t2v_decoder_train_persist16_supported(b, T_in)) and (force or not p32) and \
+                small(lib.t2v_decoder_train_persist16_scratch_floats(b, T_in, T))
+            fwd.append('persist16' if f16 else 'persist' if p32 else 'steps')
+            if need_grad:
+                r32 = bool(bwd_on) and bool(lib.t2v_decoder_bwd_persist_supported(b, T_in)) and \
+                    small(lib.t2v_decoder_bwd_achain_scratch_floats(b, T_in, T))
+                r16 = on16 and env('T2V_PERSIST16_BWD', '1') != '0' and bool(bwd_on) and \
+                    bool(lib.t2v_decoder_bwd_persist16_fits(b, T_in, T)) and (force or not r32)
+                bwd.append('persist16' if r16 else 'achain' if r32 else 'steps')
+            else:
+                bwd.append(None)
+        if 'steps' in bwd:
+            bwd = ['steps'] * len(bwd)
+        return [ChunkPlan(b0, b1, f, r, f != 'steps' and r in _BWD_ENGINES) for (b0, b1), f, r in zip(chunks, fwd, bwd)]
 
     @staticmethod
-    def use_persistent(lib, B, T_in, T):
-        flag = DecoderCore.persistent
-        if flag is None:
-            flag = os.environ.get('T2V_TRAIN_PERSISTENT', '1') != '0'
-        if not (bool(flag) and bool(lib.t2v_decoder_train_persist_supported(int(B), int(T_in)))):
-            return False
-        return 4 * lib.t2v_decoder_train_persist_scratch_floats(int(B), int(T_in), int(T)) < 2 ** 31 - 1     # 31-bit buffer offsets
+    def _note(fwd=None, bwd=None, **kept):
+        """The one place that records what ran: the engine of a forward / reverse chunk, and the keep_last records by name."""
+        D = DecoderCore
+        if fwd is not None:
+            D.last_mode = 'launch-per-step' if fwd == 'steps' else 'persistent'
+            D.last_kernel = _STEPS_KERNELS['fwd'] if fwd == 'steps' else _FWD_ENGINES[fwd].kernel
+            D.chunk_kernels.append(D.last_kernel)
+        if bwd is not None:
+            D.last_bwd_mode = 'launch-per-step' if bwd == 'steps' else 'persistent'
+            D.last_bwd_kernel = _STEPS_KERNELS['bwd'] if bwd == 'steps' else _BWD_ENGINES[bwd].kernel
+            D.chunk_bwd_kernels.append(D.last_bwd_kernel)
+        for name, value in kept.items():
+            setattr(D, name, value)
 
     @staticmethod
-    def use_persistent_bwd(lib, B, T_in, T):
-        flag = DecoderCore.persistent_bwd
-        if flag is None:
-            # measured (B = 6, T_in = 84, T = 400, round 3): 12.9 us per reverse step against 18.2 for the launch-per-step
-            # pass.  Follows T2V_TRAIN_PERSISTENT unless set itself (both kernels want the GPU to themselves)
-            flag = os.environ.get('T2V_BWD_PERSISTENT', os.environ.get('T2V_TRAIN_PERSISTENT', '1')) != '0'
-        if not (bool(flag) and bool(lib.t2v_decoder_bwd_persist_supported(int(B), int(T_in)))):
-            return False
-        return 4 * lib.t2v_decoder_bwd_achain_scratch_floats(int(B), int(T_in), int(T)) < 2 ** 31 - 1
+    def _bwd_buffers(lib, eng, B, T_in, T, dev):
+        """dq partials, scratch and error word of a one-launch reverse pass"""
+        f32 = dict(device=dev, dtype=torch.float32)
+        DQP = torch.empty(T, B, getattr(lib, eng.slices)(T_in), A, **f32)
+        scratch = torch.empty(getattr(lib, eng.scratch)(B, T_in, T), **f32)
+        return DQP, scratch, torch.zeros(1, device=dev, dtype=torch.int32)
 
     @staticmethod
-    def use_persistent16_bwd(lib, B, T_in, T):
-        """bf16_run, B <= 16: the MFMA-batched one-launch reverse pass (csrc/decoder_train_bwd_persist16.hip).  Follows
-        persistent16 / T2V_PERSIST16 and the reverse-pass switches; B <= 6 keeps the fp32-weight reverse pass unless forced."""
-        flag = DecoderCore.persistent16
-        if flag is None:
-            flag = os.environ.get('T2V_PERSIST16', '1') != '0'
-        if not flag or not _BF16 or os.environ.get('T2V_PERSIST16_BWD', '1') == '0':
-            return False
-        gate = DecoderCore.persistent_bwd
-        if gate is None:
-            gate = os.environ.get('T2V_BWD_PERSISTENT', os.environ.get('T2V_TRAIN_PERSISTENT', '1')) != '0'
-        # ..._fits = supported(B, T_in) AND every exchange array below the kernel's 31-bit buffer offsets at this T_out (the
-        # same test q16_run makes: a long utterance falls back to the launch-per-step pass HERE, not after the forward)
-        if not gate or not lib.t2v_decoder_bwd_persist16_fits(int(B), int(T_in), int(T)):
-            return False
-        if flag != 'force' and DecoderCore.use_persistent_bwd(lib, B, T_in, T):
-            return False
-        return True
-
-    @staticmethod
-    def _fwd_chunk(lib, gpre, memory, pm, lengths, packs, bias_dec, wqT, wcomb, vv, need_grad, p_att, p_dec, seed, wbf=False,
-                   raw=None, bwd_prepare=False):
+    def _fwd_chunk(lib, plan, gpre, memory, pm, lengths, packs, bias_dec, wqT, wcomb, vv, need_grad, p_att, p_dec, seed, wbf, raw):
         T, B, _ = gpre.shape
         T_in = memory.shape[1]
         f32 = dict(device=gpre.device, dtype=torch.float32)
@@ -1026,66 +1087,43 @@ class DecoderCore(torch.autograd.Function):
         AL = torch.empty(T + 1, B, T_in, **f32)
         ACUM = torch.empty(T + 1, B, T_in, **f32)
         S = torch.empty(T, B, T_in, A, **f32) if need_grad else None
+        keep = (gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S)          # the order of _ARENA
         packF_att, packF_dec, packB_att, packB_dec = packs
         W = _DecWeights(_p(packF_att), _p(packF_dec), _p(packB_att), _p(packB_dec), None, _p(bias_dec),
                         _p(wqT), _p(wcomb), _p(vv), int(bool(wbf)))
-        Sb = _DecTrainBufs(_p(gpre), _p(memory), _p(pm), _p(lengths), _p(XS), _p(CA), _p(CD), _p(GA), _p(GD),
-                           _p(QP), _p(AL), _p(ACUM), _p(S))
-        p16 = raw is not None and DecoderCore.use_persistent16(lib, B, T_in, T)
-        if p16 or (raw is not None and DecoderCore.use_persistent(lib, B, T_in, T)):
-            w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, wq = raw
-            nscr = (lib.t2v_decoder_train_persist16_scratch_floats if p16 else lib.t2v_decoder_train_persist_scratch_floats)(B, T_in, T)
-            scratch = torch.empty(nscr, **f32)
-            PW = _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq),
-                                         _p(wcomb), _p(vv))
-            run = lib.t2v_decoder_train_fwd_persistent16 if p16 else lib.t2v_decoder_train_fwd_persistent
-            _check(run(C.byref(PW), C.byref(Sb), _p(scratch), B, T_in, T, float(p_att), float(p_dec), int(seed), _stream()),
-                   't2v_decoder_train_fwd_persistent')
-            _err_note('decoder forward (persistent kernel hand-off)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
-            DecoderCore.last_mode = 'persistent'
-            DecoderCore.last_kernel = 'k_dec_train_persist16' if p16 else 'k_dec_train_persist'
-            DecoderCore.chunk_kernels.append(DecoderCore.last_kernel)
-            if DecoderCore.keep_last:
-                DecoderCore.last_persist = (PW, Sb, scratch, (B, T_in, T, float(p_att), float(p_dec), int(seed)), raw)
-            if need_grad and bwd_prepare and DecoderCore.use_persistent16_bwd(lib, B, T_in, T):
-                # bf16 reverse pass: its sentinel fills (1.4 MB per time step) go out NOW, on the deferred-work stream
-                # (round 5, measured: issued at the TOP of the step instead, next to the encoder, the step time does not change —
-                # 12.90 vs 12.91 ms — so the buffers are not held for the whole forward pass)
-                NS = lib.t2v_decoder_bwd_persist16_slices(T_in)
-                DQP = torch.empty(T, B, NS, A, **f32)
-                bscr = torch.empty(lib.t2v_decoder_bwd_persist16_scratch_floats(B, T_in, T), **f32)
-                errw = torch.zeros(1, device=gpre.device, dtype=torch.int32)
-                with side('w', keep=(XS,)):
-                    _check(lib.t2v_decoder_bwd_persistent16_prepare(_p(DQP), _p(bscr), _p(errw), B, T_in, T, _stream()),
-                           't2v_decoder_bwd_persistent16_prepare')
-                    ev = torch.cuda.Event()
-                    ev.record()
-                prep = (DQP, bscr, errw, ev, torch.cuda.current_stream())
-                return W, Sb, (gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S), prep
-            if need_grad and bwd_prepare and DecoderCore.use_persistent_bwd(lib, B, T_in, T):
-                # the preparation of the reverse pass (sentinel fills, factor arrays of both cells: ~150 us of launches that
-                # need nothing but this forward pass) goes out NOW, on the deferred-work stream, next to the Postnet
-                NS = lib.t2v_decoder_bwd_persist_slices(T_in)
-                DQP = torch.empty(T, B, NS, A, **f32)
-                bscr = torch.empty(lib.t2v_decoder_bwd_achain_scratch_floats(B, T_in, T), **f32)
-                errw = torch.zeros(1, device=gpre.device, dtype=torch.int32)
-                with side('w', keep=(XS, CA, CD, GA, GD)):
-                    _check(lib.t2v_decoder_bwd_achain_prepare(C.byref(Sb), _p(DQP), _p(bscr), _p(errw), B, T_in, T, float(p_att),
-                                                              float(p_dec), int(seed), _stream()), 't2v_decoder_bwd_achain_prepare')
-                    ev = torch.cuda.Event()
-                    ev.record()
-                # (the prepared buffers travel with the chunk on the autograd ctx — a process-wide table keyed by id(XS) could hand
-                # a later chunk the scratch of a forward pass whose backward never ran)
-                prep = (DQP, bscr, errw, ev, torch.cuda.current_stream())
-                return W, Sb, (gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S), prep
-            return W, Sb, (gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S), None
-        _check(lib.t2v_decoder_train_fwd(C.byref(W), C.byref(Sb), B, T_in, T, float(p_att), float(p_dec),
-                                         int(seed), _stream()), 't2v_decoder_train_fwd')
-        _err_note('decoder forward (attention exchange)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
-        DecoderCore.last_mode = 'launch-per-step'
-        DecoderCore.last_kernel = 'k_lstm_fwd256 + k_attn_fwd'
-        DecoderCore.chunk_kernels.append(DecoderCore.last_kernel)
-        return W, Sb, (gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S), None
+        Sb = _DecTrainBufs(*(_p(t) for t in keep))
+        dims = (B, T_in, T, float(p_att), float(p_dec), int(seed))
+        if plan.fwd == 'steps':
+            _check(lib.t2v_decoder_train_fwd(C.byref(W), C.byref(Sb), *(dims + (_stream(),))), 't2v_decoder_train_fwd')
+            _err_note('decoder forward (attention exchange)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
+            DecoderCore._note(fwd='steps')
+            return W, Sb, keep, None
+        eng = _FWD_ENGINES[plan.fwd]
+        scratch = torch.empty(getattr(lib, eng.scratch)(B, T_in, T), **f32)
+        PW = _persist_weights(raw, bias_dec, wcomb, vv)
+        _check(getattr(lib, eng.run)(C.byref(PW), C.byref(Sb), _p(scratch), *(dims + (_stream(),))), eng.run)
+        _err_note('decoder forward (persistent kernel hand-off)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
+        DecoderCore._note(fwd=plan.fwd)
+        if DecoderCore.keep_last:
+            DecoderCore._note(last_persist=(PW, Sb, scratch, dims, raw))
+        if not plan.prepare:
+            return W, Sb, keep, None
+        # the preparation of the reverse pass (sentinel fills — 1.4 MB per time step for the bf16 pass — and, for the fp32 pass,
+        # the factor arrays of both cells: ~150 us of launches that need nothing but this forward pass) goes out NOW, on the
+        # deferred-work stream, next to the Postnet.  (round 5, measured: issued at the TOP of the step instead, next to the
+        # encoder, the step time does not change — 12.90 vs 12.91 ms — so the buffers are not held for the whole forward pass)
+        beng = _BWD_ENGINES[plan.bwd]
+        DQP, bscr, errw = DecoderCore._bwd_buffers(lib, beng, B, T_in, T, gpre.device)
+        with side('w', keep=tuple(keep[_ARENA.index(n)] for n in beng.keep)):
+            args = (_p(DQP), _p(bscr), _p(errw), B, T_in, T)
+            if beng.arena_prepare:
+                args = (C.byref(Sb),) + args + dims[3:]
+            _check(getattr(lib, beng.prepare)(*(args + (_stream(),))), beng.prepare)
+            ev = torch.cuda.Event()
+            ev.record()
+        # (the prepared buffers travel with the chunk on the autograd ctx — a process-wide table keyed by id(XS) could hand
+        # a later chunk the scratch of a forward pass whose backward never ran)
+        return W, Sb, keep, (DQP, bscr, errw, ev)
 
     @staticmethod
     def forward(ctx, gpre, memory, pm, lengths, w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, bias_dec,
@@ -1109,15 +1147,13 @@ class DecoderCore(torch.autograd.Function):
         # no_grad (validate(), inference) nothing is saved and the backward-only buffers are not even allocated
         need_grad = bool(grad_mode) and any(ctx.needs_input_grad)
         wbf = bool(_BF16)
-        # the persistent forward reads the nn.LSTMCell tensors themselves; the forward packs are only built when some
-        # chunk takes the launch-per-step path (the transposed packs of the backward are always needed)
-        fwd_persist = all(DecoderCore.use_persistent(lib, min(B, b0 + MAX_DEC_B) - b0, T_in, T) or
-                          DecoderCore.use_persistent16(lib, min(B, b0 + MAX_DEC_B) - b0, T_in, T) for b0 in range(0, B, MAX_DEC_B))
-        bwd_persist = need_grad and all(DecoderCore.use_persistent_bwd(lib, min(B, b0 + MAX_DEC_B) - b0, T_in, T) or
-                                        DecoderCore.use_persistent16_bwd(lib, min(B, b0 + MAX_DEC_B) - b0, T_in, T)
-                                        for b0 in range(0, B, MAX_DEC_B))
+        plans = DecoderCore.plan(lib, B, T_in, T, need_grad)
+        # the persistent kernels read the nn.LSTMCell tensors themselves; the forward packs are only built when some chunk
+        # takes the launch-per-step forward, the transposed packs when the reverse pass is the launch-per-step one
+        fwd_persist = all(p.fwd != 'steps' for p in plans)
+        bwd_persist = need_grad and all(p.bwd != 'steps' for p in plans)
         if fwd_persist and (bwd_persist or not need_grad):
-            packs = (None, None, None, None)        # both passes read the nn.LSTMCell tensors themselves
+            packs = (None, None, None, None)
         else:
             packs = pack_decoder_weights(w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, KATT, need_grad and not bwd_persist, bf16=wbf,
                                          need_fwd=not fwd_persist)
@@ -1127,17 +1163,15 @@ class DecoderCore(torch.autograd.Function):
         loc_conv, loc_dense, vv = _f32c(loc_conv.detach()), _f32c(loc_dense.detach()), _f32c(v.detach()).view(-1)
         wcomb = fuse_location_weights(loc_conv, loc_dense)
         chunks = []
-        DecoderCore.chunk_kernels = []
-        for b0 in range(0, B, MAX_DEC_B):
-            b1 = min(B, b0 + MAX_DEC_B)
-            if b0 == 0 and b1 == B:
+        DecoderCore._note(chunk_kernels=[])
+        for p in plans:
+            if p.b0 == 0 and p.b1 == B:
                 g_c, m_c, pm_c, l_c = gpre, memory, pm, lengths
             else:
-                g_c, m_c, pm_c = gpre[:, b0:b1].contiguous(), memory[b0:b1].contiguous(), pm[b0:b1].contiguous()
-                l_c = None if lengths is None else lengths[b0:b1].contiguous()
-            chunks.append(DecoderCore._fwd_chunk(lib, g_c, m_c, pm_c, l_c, packs, bias_dec, wqT, wcomb, vv, need_grad,
-                                                 p_att, p_dec, (int(seed) + 7919 * b0) & 0x7FFFFFFFFFFFFFFF, wbf, raw,
-                                                 bwd_prepare=bwd_persist))
+                g_c, m_c, pm_c = gpre[:, p.b0:p.b1].contiguous(), memory[p.b0:p.b1].contiguous(), pm[p.b0:p.b1].contiguous()
+                l_c = None if lengths is None else lengths[p.b0:p.b1].contiguous()
+            chunks.append(DecoderCore._fwd_chunk(lib, p, g_c, m_c, pm_c, l_c, packs, bias_dec, wqT, wcomb, vv, need_grad,
+                                                 p_att, p_dec, _chunk_seed(seed, p.b0), wbf, raw))
         hcs = []
         for _w, _s, k, _prep in chunks:          # (h_dec(t), context(t)) rows of the projection, gathered from the arena in one launch
             XSc = k[4]
@@ -1156,13 +1190,14 @@ class DecoderCore(torch.autograd.Function):
         ctx.raw = raw
         ctx.pre2 = pre2
         ctx.pre_on_side = gpre_ready is not None     # Decoder.prepare ran the Prenet on the engine's deferred-work stream
+        ctx.plans = plans
         ctx.chunks = [k for _, _, k, _ in chunks] if need_grad else None
         ctx.prepared = [pr for _, _, _, pr in chunks] if need_grad else None
         ctx.mark_non_differentiable(align)
         if DecoderCore.keep_last:
             W0, S0, k0, _ = chunks[0]
-            DecoderCore.last_call = (W0, S0, (k0[0].shape[1], T_in, T, float(p_att), float(p_dec), int(seed)),
-                                     k0 + (packs, bias_dec, wqT, wcomb, vv))
+            DecoderCore._note(last_call=(W0, S0, (k0[0].shape[1], T_in, T, float(p_att), float(p_dec), int(seed)),
+                                         k0 + (packs, bias_dec, wqT, wcomb, vv)))
         return HC, align
 
     @staticmethod
@@ -1176,100 +1211,47 @@ class DecoderCore(torch.autograd.Function):
         dev = dHC.device
         f32 = dict(device=dev, dtype=torch.float32)
         dHC = _f32c(dHC)
-        NS = lib.t2v_attn_bwd_slices(T_in)
         tcap = (T_in + 15) // 16 * 16
         acc = bacc = None
         wg = None
         dga_l, dmem_l, dpm_l, dpre_l = [], [], [], []
-        DecoderCore.chunk_bwd_kernels = []
-        b0 = 0
-        for ci, keep in enumerate(ctx.chunks):
+        DecoderCore._note(chunk_bwd_kernels=[])
+        for ci, (plan, keep) in enumerate(zip(ctx.plans, ctx.chunks)):
             gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S = keep
-            B = gpre.shape[1]
+            b0, B = plan.b0, plan.b1 - plan.b0
+            kept = DecoderCore.keep_last and b0 == 0
             dhc_c = dHC if B == Bt else dHC[:, b0:b0 + B].contiguous()
             DGA = torch.empty(T, B, G4, **f32)
             DGD = torch.empty(T, B, G4, **f32)
             DCTX = torch.empty(T, B, E, **f32)
-            p16b = packB_att is None and DecoderCore.use_persistent16_bwd(lib, B, T_in, T)
-            if p16b:
-                NS = lib.t2v_decoder_bwd_persist16_slices(T_in)
-            elif packB_att is None:     # the one-launch reverse pass has its own slice geometry (one workgroup per item up to 96 symbols)
-                NS = lib.t2v_decoder_bwd_persist_slices(T_in)
+            # (a one-launch reverse pass has its own slice geometry, e.g. one workgroup per item up to 96 symbols)
+            eng = _BWD_ENGINES.get(plan.bwd)
+            NS = lib.t2v_attn_bwd_slices(T_in) if eng is None else getattr(lib, eng.slices)(T_in)
             DV = torch.empty(B, NS, A, **f32)
-            W = _DecWeights(_p(packF_att), _p(packF_dec), _p(packB_att), _p(packB_dec), None, _p(bias_dec),
-                            _p(wqT), _p(wcomb), _p(vv), int(bool(ctx.wbf)))
-            Sb = _DecTrainBufs(_p(gpre), _p(memory), _p(pm), _p(lengths), _p(XS), _p(CA), _p(CD), _p(GA), _p(GD),
-                               _p(QP), _p(AL), _p(ACUM), _p(S))
-            if p16b:
-                # bf16_run, B <= 16: the whole reverse pass as ONE persistent launch on bf16 MFMA tiles (csrc/decoder_train_bwd_persist16.hip)
-                w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, wq_raw = ctx.raw
-                PW = _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq_raw),
-                                             _p(wcomb), _p(vv))
+            Sb = _DecTrainBufs(*(_p(t) for t in keep))
+            if eng is not None:
+                # the whole reverse pass as ONE persistent launch (csrc/decoder_train_bwd_persist.hip; bf16_run, B <= 16: on bf16
+                # MFMA tiles, csrc/decoder_train_bwd_persist16.hip)
+                PW = _persist_weights(ctx.raw, bias_dec, wcomb, vv)
                 prep, ctx.prepared[ci] = ctx.prepared[ci], None
                 if prep is not None:
-                    DQP, scratch, errw, pev, pst = prep
+                    DQP, scratch, errw, pev = prep
                     torch.cuda.current_stream().wait_event(pev)     # (always: the preparation ran on a side stream)
-                    run16 = lib.t2v_decoder_bwd_persistent16_prepared
                 else:
-                    DQP = torch.empty(T, B, NS, A, **f32)
-                    scratch = torch.empty(lib.t2v_decoder_bwd_persist16_scratch_floats(B, T_in, T), **f32)
-                    errw = torch.zeros(1, device=dev, dtype=torch.int32)
-                    run16 = lib.t2v_decoder_bwd_persistent16
+                    DQP, scratch, errw = DecoderCore._bwd_buffers(lib, eng, B, T_in, T, dev)
                 stamp('dec_bwd_begin')
-                _check(run16(C.byref(PW), C.byref(Sb), _p(dhc_c), _p(DGA), _p(DGD), _p(DCTX), _p(DV), _p(DQP),
-                                                        _p(scratch), _p(errw), B, T_in, T, p_att, p_dec,
-                                                        (seed + 7919 * b0) & 0x7FFFFFFFFFFFFFFF, _stream()), 't2v_decoder_bwd_persistent16')
-                split_d = False
+                bufs = (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw)
+                _bwd_launch(lib, eng, prep is not None, PW, Sb, bufs, (B, T_in, T, p_att, p_dec, _chunk_seed(seed, b0)))
                 _err_note('decoder backward (persistent kernel hand-off)', errw)
-                DecoderCore.last_bwd_mode = 'persistent'
-                DecoderCore.last_bwd_kernel = 'k_bwd_persist16'
-                dq_off = lib.t2v_decoder_bwd_persist16_dq_offset(B, T_in, T)      # (T, 16, 128): slice 0 of every item has summed the slices
-                dq_sum = scratch[dq_off:dq_off + T * 16 * A].view(T, 16, A)[:, :B].reshape(T * B, A)
-                if DecoderCore.keep_last and b0 == 0:
-                    DecoderCore.last_bwd_persist = (PW, Sb, (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw), (B, T_in, T, p_att, p_dec, seed),
-                                                    keep + (ctx.raw, wcomb, vv, bias_dec))
-            elif packB_att is None:
-                # the whole reverse pass as ONE persistent launch (csrc/decoder_train_bwd_persist.hip)
-                DecoderCore.last_bwd_kernel = 'k_achain_bwd'
-                w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, wq_raw = ctx.raw
-                PW = _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq_raw),
-                                             _p(wcomb), _p(vv))
-                prep, ctx.prepared[ci] = ctx.prepared[ci], None
-                if prep is not None:
-                    DQP, scratch, errw, pev, pst = prep
-                    torch.cuda.current_stream().wait_event(pev)     # (always: the preparation ran on a side stream)
-                    run_fn = lib.t2v_decoder_bwd_achain_prepared
-                else:
-                    DQP = torch.empty(T, B, NS, A, **f32)
-                    scratch = torch.empty(lib.t2v_decoder_bwd_achain_scratch_floats(B, T_in, T), **f32)
-                    errw = torch.zeros(1, device=dev, dtype=torch.int32)
-                    run_fn = lib.t2v_decoder_bwd_achain2
-                stamp('dec_bwd_begin')
-                # T2V_BWD_SPLIT=1 (opt-in): the decoder_rnn chain as a launch of its own on stream 'd' — its END is then something
-                # the two decoder_rnn weight-gradient GEMMs can wait for, and they run on the CUs it frees while the attention
-                # chain goes on.  Measured: graph replay 11.43 -> 11.24 ms per step, eager 11.44 -> 11.77.  Not the default: the
-                # two launches need each other's progress, and a replayed HIP graph does not promise that two branches run
-                # CONCURRENTLY — with a few more nodes in the graph the executor put the attention chain BEHIND the other branch
-                # (correct, the decoder_rnn chain needs nothing from it, but 8 ms instead of 4.4); one launch has no such cliff.
-                ov = overlap()
-                st_d = ov.stream('d') if (ov is not None and ov.on and os.environ.get('T2V_BWD_SPLIT', '0') == '1') else None
-                if st_d is not None:
-                    with ov.side('d', keep=(dhc_c, DGD, scratch) + tuple(keep)):
-                        pass        # registers the stream for the engine's join (and orders it behind this point)
-                _check(run_fn(C.byref(PW), None, C.byref(Sb), _p(dhc_c), _p(DGA), _p(DGD), _p(DCTX), _p(DV),
-                                                   _p(DQP), _p(scratch), _p(errw), B, T_in, T, p_att, p_dec,
-                                                   (seed + 7919 * b0) & 0x7FFFFFFFFFFFFFFF, _stream(),
-                                                   None if st_d is None else C.c_void_p(st_d.cuda_stream)), 't2v_decoder_bwd_achain2')
-                split_d = st_d is not None
-                _err_note('decoder backward (persistent kernel hand-off)', errw)
-                DecoderCore.last_bwd_mode = 'persistent'
-                dq_off = lib.t2v_decoder_bwd_achain_dq_offset(B, T_in, T)      # slice 0 of every item has summed the slices already
-                dq_sum = scratch[dq_off:dq_off + T * B * A].view(T * B, A)
-                if DecoderCore.keep_last and b0 == 0:
-                    DecoderCore.last_bwd_persist = (PW, Sb, (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw), (B, T_in, T, p_att, p_dec, seed),
-                                                    keep + (ctx.raw, wcomb, vv, bias_dec))
+                dq_off = getattr(lib, eng.dq_offset)(B, T_in, T)       # slice 0 of every item has summed the slices already
+                rows = eng.dq_rows or B
+                dq_sum = scratch[dq_off:dq_off + T * rows * A].view(T, rows, A)[:, :B].reshape(T * B, A)
+                DecoderCore._note(bwd=plan.bwd)
+                if kept:
+                    DecoderCore._note(last_bwd_persist=(PW, Sb, bufs, (B, T_in, T, p_att, p_dec, seed), keep + (ctx.raw, wcomb, vv, bias_dec)))
             else:
-                split_d = False
+                W = _DecWeights(_p(packF_att), _p(packF_dec), _p(packB_att), _p(packB_dec), None, _p(bias_dec),
+                                _p(wqT), _p(wcomb), _p(vv), int(bool(ctx.wbf)))
                 DQ = torch.empty(T, B, NS, A, 2, **f32)
                 YD = torch.empty(B, XW, **f32); YA = torch.empty(B, KATT, **f32)
                 DCA = torch.empty(B, H, **f32); DCD = torch.empty(B, H, **f32)
@@ -1277,16 +1259,14 @@ class DecoderCore(torch.autograd.Function):
                 Gb = _DecBwdBufs(_p(dhc_c), _p(DGA), _p(DGD), _p(DQ), _p(DCTX), _p(YD), _p(YA), _p(DCA),
                                  _p(DCD), _p(GPREV), _p(GCUM), _p(DV))
                 _check(lib.t2v_decoder_train_bwd(C.byref(W), C.byref(Sb), C.byref(Gb), B, T_in, T, p_att, p_dec,
-                                                 (seed + 7919 * b0) & 0x7FFFFFFFFFFFFFFF, _stream()), 't2v_decoder_train_bwd')
+                                                 _chunk_seed(seed, b0), _stream()), 't2v_decoder_train_bwd')
                 _err_note('decoder backward (dq hand-off)', GCUM.view(torch.int32)[B * NS * tcap + 1:][:1])
-                DecoderCore.last_bwd_mode = 'launch-per-step'
-                DecoderCore.last_bwd_kernel = 'k_lstm_bwd256 + k_attn_cell_bwd'
                 dq_sum = DQ[..., 0].sum(2).view(T * B, A)
-                if DecoderCore.keep_last and b0 == 0:
-                    DecoderCore.last_bwd = (W, Sb, Gb, (B, T_in, T, p_att, p_dec, seed),
-                                            keep + (dhc_c, DGA, DGD, DQ, DCTX, YD, YA, DCA, DCD, GPREV, GCUM, DV, packs, bias_dec,
-                                                    wqT, wcomb, vv))
-            DecoderCore.chunk_bwd_kernels.append(DecoderCore.last_bwd_kernel)
+                DecoderCore._note(bwd='steps')
+                if kept:
+                    DecoderCore._note(last_bwd=(W, Sb, Gb, (B, T_in, T, p_att, p_dec, seed),
+                                                keep + (dhc_c, DGA, DGD, DQ, DCTX, YD, YA, DCA, DCD, GPREV, GCUM, DV, packs, bias_dec,
+                                                        wqT, wcomb, vv)))
             TB = T * B
             stamp('dec_bwd_end')
             fork = mark()
@@ -1317,8 +1297,7 @@ class DecoderCore(torch.autograd.Function):
                 d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec = wg
                 # round 6: the five LSTM weight-gradient products as ONE launch of the plane kernel — both gate-gradient operands split
                 # (fp32: x3 planes; bf16_run: rounded) once, 1 024 tiles = two full rounds of the chip (T2V_DW_GROUPED=0: one by one)
-                grouped = (not split_d and os.environ.get('T2V_DW_GROUPED', '1') != '0'
-                           and os.environ.get('T2V_DW_TWO_STREAMS', '0') != '1')
+                grouped = os.environ.get('T2V_DW_GROUPED', '1') != '0'
                 if ctx.pre2 is not None:    # the input projection of the prenet output, folded into this node: the Prenet's
                     # own backward (issued on this same stream when an engine is active) waits for d_pre, so it goes first
                     pre_c = ctx.pre2 if B == Bt else ctx.pre2.view(T, Bt, PRE)[:, b0:b0 + B].reshape(TB, PRE)
@@ -1331,7 +1310,6 @@ class DecoderCore(torch.autograd.Function):
                 # accumulation) — no library GEMM is left in either step
                 # (measured round 4: without these four products the step is 0.71 ms shorter, alone they take 0.82 ms — they run
                 # NEXT to the other chains but the chip is shared, so almost all of their time is still on the step's clock)
-                two = os.environ.get('T2V_DW_TWO_STREAMS', '0') == '1' and not split_d      # measurement: the two pairs side by side
                 with side('g', after=fork):
                     if grouped:
                         att = [(x_prev[:, :H].t(), d_w_hh_att), (x_prev[:, H:KATT].t(), d_w_ih_att[:, PRE:])]
@@ -1342,35 +1320,22 @@ class DecoderCore(torch.autograd.Function):
                     else:
                         gemm(dga2.t(), x_prev[:, :H].t(), out=d_w_hh_att, accumulate=not first)
                         gemm(dga2.t(), x_prev[:, H:KATT].t(), out=d_w_ih_att[:, PRE:], accumulate=not first)
-                    if not grouped and not split_d and not two:
-                        gemm(dgd2.t(), x_cur[:, :KATT].t(), out=d_w_ih_dec, accumulate=not first)
-                        gemm(dgd2.t(), x_cur[:, KATT:].t(), out=d_w_hh_dec, accumulate=not first)
-                if two:
-                    with side('d', keep=(DGD, dgd2), after=fork):
-                        gemm(dgd2.t(), x_cur[:, :KATT].t(), out=d_w_ih_dec, accumulate=not first)
-                        gemm(dgd2.t(), x_cur[:, KATT:].t(), out=d_w_hh_dec, accumulate=not first)
-                if split_d:         # in order behind the decoder_rnn chain on ITS stream: they start the moment it ends
-                    with torch.cuda.stream(overlap().stream('d')):
                         gemm(dgd2.t(), x_cur[:, :KATT].t(), out=d_w_ih_dec, accumulate=not first)
                         gemm(dgd2.t(), x_cur[:, KATT:].t(), out=d_w_hh_dec, accumulate=not first)
                 # the attention weight gradients stay on the deferred-work stream.  (Round 5: the captured DAG's longest path behind the
                 # reverse pass is this stream's serial order — Prenet data gradient, these ~450 us, the Prenet backward, the BiLSTM
-                # and encoder-conv weight gradients: 1.3 .. 1.7 ms — so they were tried on a stream of their own, T2V_ATTN_WGRAD_STREAM=d:
-                # fp32 step 11.24 -> 11.36 ms, bf16 12.86 -> 12.91, two alternating pairs of 60 steps.  A fifth concurrent branch on
+                # and encoder-conv weight gradients: 1.3 .. 1.7 ms — so they were tried on a stream of their own: fp32 step
+                # 11.24 -> 11.36 ms, bf16 12.86 -> 12.91, two alternating pairs of 60 steps.  A fifth concurrent branch on
                 # the graph executor's four queues costs more than the shorter path buys; tools/graph_critical_path.py)
-                with side(os.environ.get('T2V_ATTN_WGRAD_STREAM', 'w'), keep=(dq_sum, DV, dpre, AL, ACUM), after=fork):
-                    d_wq = gemm(dq_sum.t(), x_cur[:, :H].t())            # (128,1024)
-                    d_v = DV.sum((0, 1)).view(1, A)
-                    d_loc_dense, d_loc_conv = attn_wgrad(dpre, AL, ACUM, loc_conv, loc_dense, B, T_in, T)
-                    parts = [d_wq, d_loc_conv, d_loc_dense, d_v]
-                    acc = parts if acc is None else [x + y for x, y in zip(acc, parts)]
+                d_wq = gemm(dq_sum.t(), x_cur[:, :H].t())            # (128,1024)
+                d_v = DV.sum((0, 1)).view(1, A)
+                d_loc_dense, d_loc_conv = attn_wgrad(dpre, AL, ACUM, loc_conv, loc_dense, B, T_in, T)
+                parts = [d_wq, d_loc_conv, d_loc_dense, d_v]
+                acc = parts if acc is None else [x + y for x, y in zip(acc, parts)]
             # bias gradients flow on through an Add node (bias_ih + bias_hh) / are handed to two inputs: node's stream
-            if split_d:
-                torch.cuda.current_stream().wait_stream(overlap().stream('d'))       # (DGD: that chain ended long before this one)
             bparts = [colsum(DGD.view(TB, G4))] + ([colsum(DGA.view(TB, G4))] if ctx.pre2 is not None else [])
             bacc = bparts if bacc is None else [x + y for x, y in zip(bacc, bparts)]
             dga_l.append(DGA)
-            b0 += B
         ctx.chunks = ctx.prepared = None   # the arena is released as soon as the backward has consumed it (side-stream readers: keep=)
         d_wq, d_loc_conv, d_loc_dense, d_v = acc
         d_bias_dec = bacc[0]
