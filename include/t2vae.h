@@ -673,6 +673,23 @@ int t2v_griffin_lim(const float* mag, const float* angles, const int32_t* n_fram
 int t2v_mel_to_magnitude(const float* mel, const float* pinv_basis, const int32_t* n_frames, int B, int t_stride,
                          int n_mel, float* mag, void* stream);
 
+/* ------------------------------------------------------------------ mel-spectral distortion with dynamic time warping
+ * The distance between two log-mels of different lengths (csrc/dtw.hip), for scoring free-running synthesis against its
+ * ground truth.  X is (B, n_mel, x_stride) and Y (B, n_mel, y_stride), fp32; pair b uses the first nx[b] / ny[b] frames and
+ * nothing past them is read.  Local cost d(i, j) = ||x_i - y_j||_2 computed from the differences; recurrence Sakoe-Chiba
+ * "symmetric2" without a band: D(1,1) = 2 d(1,1), D(i,j) = min(D(i-1,j) + d, D(i,j-1) + d, D(i-1,j-1) + 2 d);
+ * dist[b] = D(nx[b], ny[b]) / (nx[b] + ny[b]), which is exact for this step pattern (every path has weight nx + ny).
+ * One launch, one workgroup per pair; a pair's result does not depend on B or on its place in the batch.
+ * n_mel = 80 only (T2V_ERR_DIMS).  A null pointer, B < 1 or a stride < 1 is T2V_ERR_ARG.  The lengths are device data and
+ * the caller's to check on the host: 1 <= nx[b] <= min(x_stride, T2V_DTW_MAX_FRAMES), the same for ny.  A pair that
+ * breaks this is refused by the kernel before it addresses anything, and its dist[b] is NaN.
+ * scratch: t2v_mel_dtw_scratch_bytes(B, x_stride, y_stride) bytes (one row of D per pair, handed from one strip of 512
+ * X-frames to the next); call it with the strides, or with any tx_max / ty_max not below them. */
+#define T2V_DTW_MAX_FRAMES 2048     /* per side: the longest pair the tests check against an fp64 recurrence */
+size_t t2v_mel_dtw_scratch_bytes(int B, int tx_max, int ty_max);
+int t2v_mel_dtw(const float* X, const int32_t* nx, int x_stride, const float* Y, const int32_t* ny, int y_stride,
+                int B, int n_mel, float* dist, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,20 +219,10 @@ class Synthesizer(object):
         audio = audio[0] if torch.is_tensor(audio) and audio.dim() > 1 else audio
         write(path, self.hparams.sampling_rate, np.asarray(torch.as_tensor(audio).detach().cpu().float()))
 
-    @torch.no_grad()
-    def synthesize_batch(self, texts, paths=None, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0)):
-        """`synthesize` for several texts at once: returns the list of what `synthesize(texts[i], paths[i], ...)` called
-        for i = 0, 1, ... in turn would return from the same model state — frame counts, mels, alignments and Prenet dropout
-        masks (the decoder reserves the seeds of len(texts) consecutive inference() calls), and, with the Griffin-Lim
-        vocoder and the same np.random state, the same waveforms.  The texts run through the encoder, the decoder (groups
-        of <= 8, sorted by length) and the Postnet as one ragged batch; each is masked to its own length.
-        ratios: one (neu, sad, hap, ang) tuple for all texts, or one per text; ref_audios: one path per text
-        (condition_on_ref); paths: None or one output path per text (wav through the vocoder, else `<path>.npy`)."""
+    def _synthesize_ragged(self, texts, condition_on_ref, ref_audios, ratios, ref_mels=None):
+        """The device part of synthesize_batch: (mel, mel_postnet (B,80,N), gate (B,N,1), alignments, n_frames (B,) int64 on
+        the host, text lengths).  ref_mels: `load_mels(list(dict.fromkeys(ref_audios)))` when the caller has it already."""
         B = len(texts)
-        if B == 0:
-            return []
-        if paths is not None and len(paths) != B:
-            raise ValueError("paths: %d paths for %d texts" % (len(paths), B))
         if condition_on_ref and (ref_audios is None or len(ref_audios) != B):
             raise ValueError("condition_on_ref needs one reference audio per text")
         if len(ratios) and not np.isscalar(ratios[0]):
@@ -254,15 +244,32 @@ class Synthesizer(object):
         transcript_outputs = self.model.encoder.inference(embedded, lengths)              # (B, L, 512), 0 past each length
         if condition_on_ref:        # every distinct reference wav once, all in one ragged front-end + vae_gst call
             uniq = list(dict.fromkeys(ref_audios))
-            mels, n = self.load_mels(uniq)
+            mels, n = self.load_mels(uniq) if ref_mels is None else ref_mels
             latent = self.model.vae_gst(mels, n)[0]
             styles = [latent[uniq.index(p)].view(1, 1, -1) for p in ref_audios]
         else:
             styles = [self.style_vector(transcript_outputs[b:b + 1, :lens[b]], False, None, per_text[b]) for b in range(B)]
         encoder_outputs = torch.cat([transcript_outputs[b:b + 1] + styles[b].reshape(1, -1, styles[b].size(-1))[:, :1]
                                      for b in range(B)], 0)
-        mel, _, alignments, n_frames = self.model.decoder.inference_batch(encoder_outputs, lens)
+        mel, gate, alignments, n_frames = self.model.decoder.inference_batch(encoder_outputs, lens)
         mel_postnet = mel + self.model.postnet(mel, n_frames.to(torch.int32).cuda())
+        return mel, mel_postnet, gate, alignments, n_frames, lens
+
+    @torch.no_grad()
+    def synthesize_batch(self, texts, paths=None, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0)):
+        """`synthesize` for several texts at once: returns the list of what `synthesize(texts[i], paths[i], ...)` called
+        for i = 0, 1, ... in turn would return from the same model state — frame counts, mels, alignments and Prenet dropout
+        masks (the decoder reserves the seeds of len(texts) consecutive inference() calls), and, with the Griffin-Lim
+        vocoder and the same np.random state, the same waveforms.  The texts run through the encoder, the decoder (groups
+        of <= 8, sorted by length) and the Postnet as one ragged batch; each is masked to its own length.
+        ratios: one (neu, sad, hap, ang) tuple for all texts, or one per text; ref_audios: one path per text
+        (condition_on_ref); paths: None or one output path per text (wav through the vocoder, else `<path>.npy`)."""
+        B = len(texts)
+        if B == 0:
+            return []
+        if paths is not None and len(paths) != B:
+            raise ValueError("paths: %d paths for %d texts" % (len(paths), B))
+        mel, mel_postnet, _, alignments, n_frames, lens = self._synthesize_ragged(texts, condition_on_ref, ref_audios, ratios)
         n = n_frames.tolist()
         out = [(mel_postnet[b:b + 1, :, :n[b]], alignments[b:b + 1, :n[b], :lens[b]]) for b in range(B)]
         if paths is not None:
@@ -276,6 +283,52 @@ class Synthesizer(object):
                 for b in range(B):
                     self._write_wav(paths[b], self.vocoder(mel[b:b + 1, :, :n[b]]))
         return out
+
+    @torch.no_grad()
+    def evaluate(self, rows, batch_size=8, condition='ref'):
+        """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
+        (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
+        recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
+        computed once, for the style and for the comparison); 'emotion': from the centroid of the row's emotion label, which
+        needs `load()`.  The decoder consumes its seeds as len(rows) consecutive synthesize() calls.
+        Returns one record per row, in input order: dtw, n_frames, n_ref_frames, hit_max (decoding ended at
+        max_decoder_steps, not at the gate; such a row is still scored) and emotion (the label id)."""
+        import t2v_hip
+        if condition not in ('ref', 'emotion'):
+            raise ValueError("condition must be 'ref' or 'emotion', got %r" % (condition,))
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
+        if self.model is None:
+            raise RuntimeError("evaluate: no model (load_checkpoint() or load() first)")
+        if condition == 'emotion' and self.neu is None:
+            raise RuntimeError("evaluate(condition='emotion') needs the emotion centroids: use load(), not load_checkpoint()")
+        rows = [(r[0], r[1], r[2], int(r[3])) for r in rows]
+        one_hot = {0: (1.0, 0.0, 0.0, 0.0), 1: (0.0, 1.0, 0.0, 0.0), 2: (0.0, 0.0, 0.0, 1.0), 3: (0.0, 0.0, 1.0, 0.0)}
+        for r in rows:                      # ratio order (neu, sad, hap, ang), label order EMOTIONS
+            if r[3] not in one_hot:
+                raise ValueError("emotion label %r outside 0..3" % (r[3],))
+        dec = self.model.decoder
+        records = []
+        for i0 in range(0, len(rows), batch_size):
+            group = rows[i0:i0 + batch_size]
+            paths, texts = [r[0] for r in group], [r[1] for r in group]
+            uniq = list(dict.fromkeys(paths))
+            ref_mels, n_uniq = self.load_mels(uniq)
+            if condition == 'ref':
+                _, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), (ref_mels, n_uniq))
+            else:
+                _, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, False, None, [one_hot[r[3]] for r in group])
+            which = [uniq.index(p) for p in paths]
+            truth = ref_mels if which == list(range(len(paths))) else ref_mels[torch.tensor(which, device=ref_mels.device)]
+            n_ref = [n_uniq[k] for k in which]
+            n = n_frames.tolist()
+            dtw = t2v_hip.mel_dtw(mel_postnet, n, truth, n_ref).cpu().tolist()
+            last = gate[torch.arange(len(group), device=gate.device), (n_frames - 1).to(gate.device), 0].cpu()
+            fired = (torch.sigmoid(last) > dec.gate_threshold).tolist()
+            for b, r in enumerate(group):
+                records.append({'dtw': dtw[b], 'n_frames': n[b], 'n_ref_frames': n_ref[b],
+                                'hit_max': bool(n[b] >= dec.max_decoder_steps and not fired[b]), 'emotion': r[3]})
+        return records
 
 
 # ---------------------------------------------------------------------- command line

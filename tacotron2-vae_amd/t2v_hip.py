@@ -94,7 +94,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_stft_polar', 't2v_istft', 't2v_istft_scratch_bytes', 't2v_griffin_lim', 't2v_griffin_lim_scratch_bytes',
            't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
            't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
-           't2v_gru_fwd_len')
+           't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes')
 
 
 def lib_path():
@@ -214,6 +214,9 @@ def load_library():
     lib.t2v_griffin_lim.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
                                     vp]
     lib.t2v_mel_to_magnitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.t2v_mel_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.t2v_mel_dtw_scratch_bytes.restype = C.c_size_t
+    lib.t2v_mel_dtw.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.t2v_conv1d_stat_blocks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_stat_blocks_bf16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -1465,6 +1468,52 @@ def mel_to_magnitude(mel, n_frames, pinv_basis):
     _check(lib.t2v_mel_to_magnitude(_p(mel), _p(_f32c(pinv_basis)), _p(n), B, T, n_mel, _p(mag), _stream()),
            't2v_mel_to_magnitude')
     return mag
+
+
+DTW_MAX_FRAMES = 2048                   # T2V_DTW_MAX_FRAMES of include/t2vae.h
+DTW_SCRATCH_CAP = 256 << 20             # bytes of scratch one t2v_mel_dtw call may ask of the allocator; larger batches run in groups
+
+
+def _dtw_lengths(n, B, stride, what):
+    """frame counts of mel_dtw as a host list, checked: a list, a CPU tensor or a device int tensor"""
+    n = torch.as_tensor(n).reshape(-1).cpu()
+    if n.dtype.is_floating_point or n.numel() != B:
+        raise ValueError("mel_dtw: %s must be %d integer frame counts, got %s" % (what, B, n.tolist()))
+    if int(n.min()) < 1 or int(n.max()) > min(stride, DTW_MAX_FRAMES):
+        raise ValueError("mel_dtw: every %s must be in 1..%d (%d frames stored, at most %d supported), got %s"
+                         % (what, min(stride, DTW_MAX_FRAMES), stride, DTW_MAX_FRAMES, n.tolist()))
+    return n.to(torch.int32)
+
+
+def mel_dtw(x, nx, y, ny):
+    """Mel-spectral distortion with dynamic time warping (csrc/dtw.hip k_mel_dtw): x (B,80,Sx), y (B,80,Sy) float32 CUDA
+    tensors, pair b compared on its first nx[b] / ny[b] frames (lists, CPU tensors or device int tensors); nothing past a
+    length is read.  Local cost: the Euclidean distance of two frames; recurrence: symmetric2 without a band; returns
+    D(nx, ny) / (nx + ny) as a (B,) float32 device tensor.  A pair gives the same bits alone and in any batch.  Batches whose
+    scratch would exceed DTW_SCRATCH_CAP run in groups."""
+    lib = _require_gpu(x, y)
+    if x.dim() != 3 or y.dim() != 3 or x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError("mel_dtw: x and y must be float32 (B, 80, T) tensors")
+    B, n_mel, sx = x.shape
+    if y.size(0) != B or B < 1:
+        raise ValueError("mel_dtw: %d sequences in x, %d in y" % (B, y.size(0)))
+    if n_mel != 80 or y.size(1) != 80:
+        raise ValueError("mel_dtw: 80 mel channels only, got %d and %d" % (n_mel, y.size(1)))
+    sy = y.size(2)
+    if sx < 1 or sy < 1:
+        raise ValueError("mel_dtw: empty time axis")
+    nx = _dtw_lengths(nx, B, sx, 'nx').to(x.device)
+    ny = _dtw_lengths(ny, B, sy, 'ny').to(x.device)
+    x, y = _f32c(x), _f32c(y)
+    dist = torch.empty(B, device=x.device, dtype=torch.float32)
+    per_pair = lib.t2v_mel_dtw_scratch_bytes(1, sx, sy)
+    group = max(1, min(B, DTW_SCRATCH_CAP // per_pair))
+    for b0 in range(0, B, group):
+        nb = min(group, B - b0)
+        scratch = torch.empty(lib.t2v_mel_dtw_scratch_bytes(nb, sx, sy), device=x.device, dtype=torch.uint8)
+        _check(lib.t2v_mel_dtw(_p(x[b0:]), _p(nx[b0:]), sx, _p(y[b0:]), _p(ny[b0:]), sy, nb, n_mel, _p(dist[b0:]), _p(scratch),
+                               _stream()), 't2v_mel_dtw')
+    return dist
 
 
 class InferenceSession(object):
