@@ -234,7 +234,22 @@ long t2v_decoder_bwd_achain_scratch_floats(int B, int T_in, int T_out);
 /* position slices per item of the ONE-LAUNCH reverse pass (second-to-last dimension of its DQP (T,B,S,128) and DV (B,S,128)):
  * t2v_attn_bwd_slices(T_in) up to 224 symbols, ceil(T_in / 96) beyond */
 int t2v_decoder_bwd_persist_slices(int T_in);
-int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const float* reserved, const t2v_dec_train_bufs* s,
+/* Weight-gradient epilogue of the pass (dw, may be NULL = none): the decoder_rnn workgroups finish their chain well before the
+ * attention_rnn chain ends; with dw they then work on [d_w_ih_dec | d_w_hh_dec] (+)= DGD^T · x_cur, the second group of the grouped
+ * product t2v_gemm_f32_grouped {(DGA^T, ...), (DGD^T, [x_cur[:, :1536], x_cur[:, 1536:]])} with M = 4096, K = T_out * B: they write that
+ * group's operand planes to `planes` (= grouped scratch + t2v_gemm_f32_grouped_group_offset(.., 1)) and take 128 x 128 tiles from the
+ * counter at scratch + t2v_decoder_bwd_achain_dw_offset() until the attention_rnn chain is about to end or tile_cap (< 0: none)
+ * is reached.  t2v_gemm_f32_grouped_handed(.., handed = 1, that counter, tile_cap) must follow on the same buffers: it computes the
+ * rest.  A tile has the same bits whichever kernel computes it.  x3 mode only (t2v_gemm_f32_set_mode), T_out * B >= 32. */
+typedef struct t2v_achain_dw {
+    float* planes;
+    float* d_w_ih; int ld_ih;       /* (4096, 1536), row stride in floats */
+    float* d_w_hh; int ld_hh;       /* (4096, 1024) */
+    int accumulate;                 /* add to d_w_* instead of overwriting them */
+    int tile_cap;                   /* tests: at most this many tiles in the pass (< 0: no cap; 0: planes only) */
+} t2v_achain_dw;
+long t2v_decoder_bwd_achain_dw_offset(int B, int T_in, int T_out);
+int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
                            const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                            uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                            void* stream);
@@ -274,7 +289,7 @@ long t2v_decoder_bwd_achain_dq_offset(int B, int T_in, int T_out);
  * stream, next to the Postnet), and the pass without it.  scratch / DQP / err_word: the same buffers in both calls. */
 int t2v_decoder_bwd_achain_prepare(const t2v_dec_train_bufs* s, float* DQP, float* scratch, uint32_t* err_word, int B, int T_in,
                                    int T_out, float p_att, float p_dec, uint64_t seed, void* stream);
-int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const float* reserved, const t2v_dec_train_bufs* s,
+int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
                            const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                            uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                            void* stream);
@@ -519,6 +534,13 @@ typedef struct t2v_gemm_group {
 } t2v_gemm_group;
 long t2v_gemm_f32_grouped_scratch_floats(const t2v_gemm_group* groups, int ngroups, int M, int K);
 int t2v_gemm_f32_grouped(const t2v_gemm_group* groups, int ngroups, int M, int K, int accumulate, float* scratch, void* stream);
+/* The grouped product behind a kernel that has worked on group `handed` already (t2v_achain_dw): the group's planes exist at float
+ * offset t2v_gemm_f32_grouped_group_offset(groups, ngroups, M, K, handed) of `scratch` (-1: these shapes have no plane form), and the
+ * first min(*done_ctr, done_cap) tiles of the group (row-major over 128 x 128 tiles of A_g x [B_g0 | B_g1 | ..]) are done; *done_ctr
+ * is read on the device.  No split launches for that group; everything else as t2v_gemm_f32_grouped. */
+long t2v_gemm_f32_grouped_group_offset(const t2v_gemm_group* groups, int ngroups, int M, int K, int g);
+int t2v_gemm_f32_grouped_handed(const t2v_gemm_group* groups, int ngroups, int M, int K, int accumulate, float* scratch, int handed,
+                                const uint32_t* done_ctr, int done_cap, void* stream);
 /* bf16_run form: the same grouping on ONE bf16 plane per operand (operands rounded to bf16, RNE, once by the split pass; fp32
  * accumulation — the arithmetic of t2v_gemm_bf16). */
 long t2v_gemm_bf16_grouped_scratch_floats(const t2v_gemm_group* groups, int ngroups, int M, int K);

@@ -22,6 +22,7 @@
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_xchg.h"
+#include "gemm_x3_tile.h"
 
 #define PB_THREADS 512
 #define PB_MAXB 6
@@ -29,6 +30,8 @@
 #define PB_MAXT_LONG 576              // 96-position slices on eight waves beyond (k_achain_bwd<.., true>): at most six per item
 #define PB_SPIN 400000
 #define PB_KJ (T2V_G / PB_THREADS)          // 8 gate rows per thread: k = tid + 512 j
+// floats of LDS of an LSTM role (the attention_rnn role's carve, the larger one) with NBS = 4 / 6 item slots
+#define PBA_LROLE_FLOATS(NBS) ((NBS) * T2V_G + 6 * 1024 + 192 + 128 + 512 + 16 * T2V_A + 8 * T2V_A + 2048 + 256 + 64 + 512)
 
 // ---- a gate-gradient row (4096 gate rows x B items) in the exchange buffer / in LDS:
 //   plane 0: k -> 16 bytes (items 0..3) at byte 16 k          (64 KB)
@@ -261,6 +264,9 @@ struct PBAArgs {
     uint64_t seed;
     const t2v_step_params* step;
     unsigned long long* prof;
+    // weight-gradient epilogue of the decoder_rnn role (pba_dw_epilogue; dw_planes == nullptr: the role returns as before)
+    uint4* dw_planes; float* dw_ih; float* dw_hh; unsigned* dw_ctr;
+    int dw_ld_ih, dw_ld_hh, dw_accumulate, dw_cap, dw_margin;
 };
 // phase profile (tools/dbg/persist_bwd_prof.py): slot I accumulates, over all steps, the cycles since the previous stamp
 #define PBA_STAMP(COND, I) do { if (a.prof && (COND) && threadIdx.x == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); \
@@ -679,6 +685,117 @@ __device__ __forceinline__ void pba_publish_rows(__amdgpu_buffer_rsrc_t r, unsig
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------ D role, behind its time loop
+// The decoder_rnn workgroups finish their chain T x (chain step - own step) before the attention_rnn chain ends (0.88 ms at B = 6,
+// T = 400) and used to return.  Now they work on decoder_rnn's own weight gradients, [d_w_ih_dec | d_w_hh_dec] = DGD^T · x_cur — the
+// larger of the two groups of the grouped launch behind the pass (t2v_gemm_f32_grouped_handed), which needs nothing but what this
+// role has finished — with that launch's own code (gemm_x3_tile.h), so that a tile has the same bits whoever computes it:
+//   1. barrier over the ND decoder_rnn workgroups (DGD left with plain stores: one release / acquire pair per workgroup and pass);
+//   2. the split passes of DGD and x_cur into the grouped launch's planes, blocks dealt round robin; barrier;
+//   3. 128 x 128 tiles, two side by side per workgroup (one per 256 threads, 48 KB of LDS each), taken in pairs from a counter.
+// A workgroup stops taking tiles once the attention_rnn chain has published its (dc, dh) row of step dw_margin: the pass must never
+// end later because of this.  The grouped launch reads the counter and computes the tiles from there on.
+// A barrier that gives up (bounded spin) makes its workgroup return with the group's planes incomplete, and the grouped launch behind
+// the pass — which issues no split launches for this group — then computes garbage from them: a.err, which the give-up sets and the
+// host raises on, is the sole guard for that case, as for every other wait of this kernel.
+// Control words in the pass's scratch (zeroed by the preparation): [0] tiles taken, [1], [2] the two barriers' arrivals.
+// Profile (a.prof, workgroup jd = 0): [44] entry, [45] barrier 1 passed, [46] planes made + barrier 2 passed, [47] last tile done,
+// [48] tile pairs of this workgroup; all on the 100 MHz counter.
+struct PBADw {
+    const float* DGD; const float* XC; uint4* planes; float* c_ih; float* c_hh; unsigned* ctr; const float* GXA; unsigned* err;
+    unsigned long long* prof;
+    int K, ld_ih, ld_hh, accumulate, cap, margin_off, jd, ND;
+};
+#define PBA_DW_CTL_SLOT (2 * GX_TILE_SLOTS(3, 2))       // control words in LDS behind the two tile buffers
+static_assert(16 * (PBA_DW_CTL_SLOT + 1) <= 4 * PBA_LROLE_FLOATS(4), "the epilogue's LDS fits the LSTM roles' allocation");
+
+// all threads of the workgroup; every store of this workgroup issued so far is visible to whoever passes.  False: gave up (a.err set).
+// ONE wave per workgroup releases and acquires at agent scope (behind / in front of a workgroup barrier that covers the others): each
+// such fence writes back resp. invalidates the XCD's L2 under the attention_rnn chain — with all eight waves at it the pass in the
+// training step was 0.13 ms longer than without the epilogue, with one 0.08 ms
+__device__ __forceinline__ bool pba_dw_barrier(unsigned* ctr, int n, unsigned* err, int* flag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        int rounds = 0;
+        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)n) {
+            __builtin_amdgcn_s_sleep(8);
+            if (t2v_give_up(rounds, PB_SPIN, err, flag)) break;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    }
+    __syncthreads();
+    return flag[0] == 1;
+}
+
+__device__ __noinline__ void pba_dw_epilogue(const PBADw d, float* lds) {
+    const int tid = threadIdx.x, half = tid >> 8, t2 = tid & 255;
+    uint4* const slots = (uint4*)lds;
+    int* const flag = (int*)(slots + PBA_DW_CTL_SLOT);          // [0] healthy, [1] first tile of the pair taken (-1: stop)
+    const bool prof = d.prof && d.jd == 0 && tid == 0;
+    if (prof) d.prof[44] = __builtin_amdgcn_s_memrealtime();
+    __syncthreads();                                            // (the time loop's last LDS reads)
+    if (tid == 0) flag[0] = 1;
+    if (!pba_dw_barrier(d.ctr + 1, d.ND, d.err, flag)) return;
+    if (prof) d.prof[45] = __builtin_amdgcn_s_memrealtime();
+    // ---- 2. planes: A = DGD as (4096 rows, K), B = x_cur as (2560 rows, K), both contiguous along their rows
+    const long G = gx_groups(d.K);
+    uint4* const Ap = d.planes;
+    uint4* const Bp = Ap + gx_plane_slots(T2V_G, d.K);
+    {
+        uint4 (*sm)[4][64] = (uint4 (*)[4][64])(slots + half * (3 * 4 * 64));
+        const int gy = (int)(G / 4), nA = (T2V_G / 64) * gy, total = nA + (T2V_XW / 64) * gy;
+        const int W = 2 * d.ND, w = 2 * d.jd + half;
+        for (int i0 = 0; i0 < total; i0 += W) {
+            const bool on = i0 + w < total;
+            const int i = on ? i0 + w : 0;
+            const bool isA = i < nA;
+            const int rows = isA ? T2V_G : T2V_XW, j = isA ? i : i - nA, nbx = rows / 64;
+            gx_split_block<false, 3>(isA ? d.DGD : d.XC, 1, rows, rows, d.K, isA ? Ap : Bp, rows, G, j % nbx, j / nbx, t2, sm, on);
+            __syncthreads();                                    // sm is free again
+        }
+    }
+    if (!pba_dw_barrier(d.ctr + 2, d.ND, d.err, flag)) return;
+    if (prof) d.prof[46] = __builtin_amdgcn_s_memrealtime();
+    // ---- 3. tiles
+    GemmX3Args ga;
+    {
+        GemmX3Prod& P = ga.pr[0];
+        P.Ap = Ap; P.Bp = Bp; P.RpA = T2V_G; P.RpB = T2V_XW; P.N = T2V_XW; P.tiles_x = T2V_XW / GX_BN; P.tile0 = 0; P.nseg = 2;
+        P.seg_col[0] = 0; P.seg_col[1] = T2V_KATT; P.seg_col[2] = 0x7fffffff;
+        P.segC[0] = d.c_ih; P.segC[1] = d.c_hh; P.segC[2] = d.c_hh;
+        P.seg_ldc[0] = d.ld_ih; P.seg_ldc[1] = d.ld_hh; P.seg_ldc[2] = d.ld_hh;
+        ga.pr[1] = P;
+        ga.nprod = 1; ga.ntiles = (T2V_G / GX_BM) * (T2V_XW / GX_BN); ga.G = G; ga.bias = nullptr; ga.M = T2V_G; ga.relu = 0;
+        ga.accumulate = d.accumulate; ga.p_drop = 0.f; ga.seed = 0; ga.rng_stream = 0; ga.rng_t = 0; ga.step = nullptr;
+        ga.st_chunk = 0; ga.part = nullptr; ga.tile_ctr = nullptr; ga.done_ctr = nullptr; ga.done_prod = 0; ga.done_cap = 0;
+    }
+    const int limit = min(ga.ntiles, d.cap);
+    const __amdgpu_buffer_rsrc_t rA = t2v_rsrc(d.GXA);
+    unsigned npair = 0;
+    for (;;) {
+        if (tid == 0) {
+            int take = -1;
+            // (margin_off < 0: a pass too short for a single pair)
+            if (limit > 0 && d.margin_off >= 0 && t2v_ld_b32(rA, (unsigned)d.margin_off) == T2V_SENT) {
+                const unsigned t = __hip_atomic_fetch_add(d.ctr, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t < (unsigned)limit) take = (int)t;
+            }
+            flag[1] = take;
+        }
+        __syncthreads();
+        const int take = flag[1];
+        __syncthreads();
+        if (take < 0) break;
+        const int lin = take + half;
+        gx_tile<3, 2, false>(ga, ga.pr[0], min(lin, limit - 1), t2, slots + half * GX_TILE_SLOTS(3, 2), 0, 1, lin < limit);
+        ++npair;
+    }
+    if (prof) { d.prof[47] = __builtin_amdgcn_s_memrealtime(); d.prof[48] = npair; }
+}
+
 // ------------------------------------------------------------------------------------------------ D role (free-running)
 template <int NB>
 __device__ __forceinline__ void pba_decoder_role(const PBAArgs& a, float* lds, const int jd, const int ND) {
@@ -797,6 +914,15 @@ __device__ __forceinline__ void pba_decoder_role(const PBAArgs& a, float* lds, c
         __syncthreads();
     }
     if (a.prof && jd == 0 && threadIdx.x == 0) a.prof[41] = __builtin_amdgcn_s_memrealtime();
+    if (a.dw_planes) {
+        PBADw d;
+        d.DGD = a.DGD; d.XC = a.XS + (size_t)B * T2V_XW; d.planes = a.dw_planes; d.c_ih = a.dw_ih; d.c_hh = a.dw_hh; d.ctr = a.dw_ctr;
+        d.GXA = a.GXA; d.err = a.err; d.prof = a.prof;
+        d.K = T * B; d.ld_ih = a.dw_ld_ih; d.ld_hh = a.dw_ld_hh; d.accumulate = a.dw_accumulate; d.cap = a.dw_cap;
+        d.margin_off = a.dw_margin >= 1 && a.dw_margin < T ? (int)((unsigned)a.dw_margin * PB_DROW_BYTES(NB)) : -1;
+        d.jd = jd; d.ND = ND;
+        pba_dw_epilogue(d, lds);
+    }
 }
 
 // the activation-only part of attention_rnn's cell backward at step t -> cpre[row][8] = {fh, fc, go(1-tanh(c)^2), gf, e0..e3}.
@@ -1130,7 +1256,7 @@ static inline int pba_slices(int T_in) { const int js = pba_js(T_in); return (T_
 extern "C" int t2v_decoder_bwd_persist_slices(int T_in) { return T_in < 1 ? 0 : pba_slices(T_in); }
 
 static size_t pba_lds_bytes(int B, int T_in) {
-    const size_t lrole = (B > 4 ? 6 : 4) * T2V_G + 6 * 1024 + 192 + 128 + 512 + 16 * T2V_A + 8 * T2V_A + 2048 + 256 + 64 + 512;
+    const size_t lrole = PBA_LROLE_FLOATS(B > 4 ? 6 : 4);
     const size_t Tcap = (size_t)((T_in + 15) / 16) * 16, JS = (size_t)pba_js(T_in), NWV = JS == 96 ? 8 : 4;
     const size_t trole = 4 * Tcap + T2V_E + JS + (1 + JS / NWV) * 4 * NWV + T2V_A * (JS == 96 ? JS + 17 : JS + 1) + 64 * (JS + 1) +
                          2 * 2 * NWV * T2V_A + 40 + (NWV == 8 ? 64 * 132 : 0);
@@ -1146,12 +1272,14 @@ static size_t pba_lds_bytes(int B, int T_in) {
 //   -- up to here exchange arrays: sentinel-filled by the preparation --
 //   FA, FD     n_f each    gate-gradient factors of both cells (k_pb_factors): a gate row per step
 //   CPA, CPD   n_cp each   cell-layout factors of both cells (k_pb_cellpre)
+//   DWC        n_dwc       control words of the weight-gradient epilogue (pba_dw_epilogue): zeroed by the preparation
 // The dq partials DQP (T,B,S,128), n_dq floats, are an OUTPUT (the caller passes them separately) and not part of scratch.
 struct PBALayout {
-    size_t n_gx, n_cx, n_gp, n_ex, n_dqt, n_f, n_cp, n_dq;
+    size_t n_gx, n_cx, n_gp, n_ex, n_dqt, n_f, n_cp, n_dwc, n_dq;
     size_t dqt_off() const { return 2 * n_gx + n_cx + n_gp + n_ex; }
     size_t n_exchange() const { return dqt_off() + n_dqt; }
-    size_t total() const { return n_exchange() + 2 * n_f + 2 * n_cp; }
+    size_t dwc_off() const { return n_exchange() + 2 * n_f + 2 * n_cp; }
+    size_t total() const { return dwc_off() + n_dwc; }
 };
 static PBALayout pba_layout(int B, int T_in, int T_out) {
     const size_t T = (size_t)T_out, S = (size_t)pba_slices(T_in), gpw = pba_js(T_in) + 30 <= 64 ? 64 : 128;
@@ -1164,6 +1292,7 @@ static PBALayout pba_layout(int B, int T_in, int T_out) {
     l.n_dqt = T * 8 * T2V_A;
     l.n_f = T * rowf;
     l.n_cp = T * T2V_H * (B > 4 ? 6 : 4) * 8;
+    l.n_dwc = 16;
     l.n_dq = T * B * S * 128;
     return l;
 }
@@ -1180,12 +1309,28 @@ extern "C" long t2v_decoder_bwd_achain_dq_offset(int B, int T_in, int T_out) {
     return (long)pba_layout(B, T_in, T_out).dqt_off();
 }
 
+// float offset, inside `scratch`, of the weight-gradient epilogue's control words; word 0 = the tiles of the decoder_rnn group it took
+// (what t2v_gemm_f32_grouped_handed reads)
+extern "C" long t2v_decoder_bwd_achain_dw_offset(int B, int T_in, int T_out) {
+    if (!t2v_decoder_bwd_persist_supported(B, T_in) || T_out < 1) return -1;
+    return (long)pba_layout(B, T_in, T_out).dwc_off();
+}
+
+// Reverse steps the attention_rnn chain must still have in front of it when a workgroup of the epilogue takes another pair of
+// tiles, for K = T_out * B.  Measured (profiles/dw_epilogue_bwd_persist_timeline.txt, B = 6, T = 400, K = 2400): 227 .. 234 us per pair
+// (two tiles side by side on one CU, 128 CUs at it), taken as 20 us + 0.09 us per unit of K; the chain advances one step per
+// 10.58 .. 10.86 us.  A quarter of a pair on top for what the estimate misses at other shapes.
+static int pba_dw_margin(int B, int T_out) {
+    const double pair_us = 20.0 + 0.09 * (double)T_out * B;
+    return (int)(1.25 * pair_us / 10.58) + 1;
+}
+
 // do_prepare: error word, sentinel fills, the factor arrays of both cells (functions of the forward activations alone: they may
 // run long before the reverse pass, next to the Postnet).  do_run: the pass itself.
 static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s,
                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                      void* stream_, bool do_prepare, bool do_run) {
+                      void* stream_, bool do_prepare, bool do_run, const t2v_achain_dw* dw = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!s || !DQP || !scratch || !err_word) return T2V_ERR_ARG;
     if (do_run && (!w || !dHC || !DGA || !DGD || !DCTX || !DV)) return T2V_ERR_ARG;
@@ -1195,6 +1340,9 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
     const PBALayout l = pba_layout(B, T_in, T_out);
     if (((uintptr_t)scratch & 15) || ((uintptr_t)DQP & 15) || l.n_gx * 4 >= 0x7fffffffull || l.n_dq * 4 >= 0x7fffffffull) return T2V_ERR_ARG;
     if (pba_lds_bytes(B, T_in) > T2V_LDS_MAX) return T2V_ERR_ARG;
+    if (do_run && dw && (!dw->planes || ((uintptr_t)dw->planes & 15) || !dw->d_w_ih || !dw->d_w_hh || dw->ld_ih < T2V_KATT || dw->ld_hh < T2V_H ||
+                         (long)T_out * B < 32))
+        return T2V_ERR_ARG;
     static bool raised = false;
     if (!t2v_persist_raise_lds({(const void*)k_achain_bwd<4, false>, (const void*)k_achain_bwd<6, false>,
                                 (const void*)k_achain_bwd<4, true>, (const void*)k_achain_bwd<6, true>}, raised))
@@ -1203,6 +1351,7 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
         (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
         t2v_fill_sentinel(scratch, l.n_exchange() / 4, 1024, stream);
         t2v_fill_sentinel(DQP, l.n_dq / 4, 256, stream);
+        (void)hipMemsetAsync(scratch + l.dwc_off(), 0, l.n_dwc * sizeof(float), stream);
     }
     PBAArgs a;
     if (do_run) {
@@ -1227,6 +1376,14 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
     a.B = B; a.T_in = T_in; a.T = T_out; a.S_sl = pba_slices(T_in); a.p_att = p_att; a.p_dec = p_dec; a.seed = seed;
     a.step = t2v_step_for(stream);
     a.prof = g_t2v_prof;
+    a.dw_planes = nullptr; a.dw_ih = a.dw_hh = nullptr; a.dw_ctr = (unsigned*)(scratch + l.dwc_off());
+    a.dw_ld_ih = a.dw_ld_hh = a.dw_accumulate = a.dw_cap = a.dw_margin = 0;
+    if (do_run && dw) {
+        a.dw_planes = (uint4*)dw->planes; a.dw_ih = dw->d_w_ih; a.dw_hh = dw->d_w_hh; a.dw_ld_ih = dw->ld_ih; a.dw_ld_hh = dw->ld_hh;
+        a.dw_accumulate = dw->accumulate ? 1 : 0;
+        a.dw_cap = dw->tile_cap < 0 ? 0x7fffffff : dw->tile_cap;
+        a.dw_margin = pba_dw_margin(B, T_out);
+    }
     if (do_prepare) {
         const unsigned nblk = (unsigned)(((size_t)T_out * T2V_G + 255) / 256);
         k_pb_factors<<<nblk, 256, 0, stream>>>(s->GA, s->CA, FA, B, T_out, B, p_att, T2V_RNG_ATT_C, seed, a.step);
@@ -1249,12 +1406,11 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
 }
 
 // preparation + pass
-extern "C" int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
+extern "C" int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
                                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                                       void* stream_) {
-    (void)w_unused;
-    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true, true);
+    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true, true, dw);
 }
 
 // The preparation on its own (everything it needs exists when the FORWARD pass has ended) ...
@@ -1264,10 +1420,9 @@ extern "C" int t2v_decoder_bwd_achain_prepare(const t2v_dec_train_bufs* s, float
                       stream_, true, false);
 }
 // ... and the pass without it (same arguments as t2v_decoder_bwd_achain; scratch / DQP / err_word as handed to _prepare)
-extern "C" int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const float* w_unused, const t2v_dec_train_bufs* s,
+extern "C" int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
                                                const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                                uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                                                void* stream_) {
-    (void)w_unused;
-    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false, true);
+    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false, true, dw);
 }

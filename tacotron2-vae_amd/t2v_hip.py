@@ -61,6 +61,12 @@ class _GemmGroup(C.Structure):
                 ('sBk', C.c_long * 3), ('N', C.c_int * 3), ('C', C.c_void_p * 3), ('ldc', C.c_int * 3)]
 
 
+class _AchainDw(C.Structure):
+    C_NAME = 't2v_achain_dw'
+    _fields_ = [('planes', C.c_void_p), ('d_w_ih', C.c_void_p), ('ld_ih', C.c_int), ('d_w_hh', C.c_void_p), ('ld_hh', C.c_int),
+                ('accumulate', C.c_int), ('tile_cap', C.c_int)]
+
+
 class _DecInferBufs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         'memory', 'pm', 'lengths', 'XS', 'CA', 'CD', 'QP', 'AL', 'ACUM', 'PRE', 'MEL', 'GATE', 'stop_flag',
@@ -83,7 +89,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_decoder_train_fwd_persistent', 't2v_decoder_train_persist_supported',
            't2v_decoder_train_persist_scratch_floats', 't2v_decoder_bwd_persist_supported',
            't2v_decoder_bwd_achain_scratch_floats', 't2v_decoder_bwd_achain', 't2v_decoder_bwd_achain_prepare',
-           't2v_decoder_bwd_achain_prepared', 't2v_decoder_bwd_persist_slices', 't2v_decoder_bwd_achain_dq_offset', 't2v_mask_outputs', 't2v_reparam_fwd',
+           't2v_decoder_bwd_achain_prepared', 't2v_decoder_bwd_persist_slices', 't2v_decoder_bwd_achain_dq_offset',
+           't2v_decoder_bwd_achain_dw_offset', 't2v_gemm_f32_grouped_handed', 't2v_gemm_f32_grouped_group_offset', 't2v_mask_outputs', 't2v_reparam_fwd',
            't2v_reparam_bwd', 't2v_gather_words', 't2v_concat2_rows',
            't2v_decoder_train_fwd_persistent16', 't2v_decoder_train_persist16_supported',
            't2v_decoder_train_persist16_scratch_floats', 't2v_decoder_bwd_persistent16', 't2v_decoder_bwd_persist16_supported',
@@ -156,7 +163,13 @@ def load_library():
     lib.t2v_decoder_bwd_persist_supported.argtypes = [C.c_int, C.c_int]
     lib.t2v_decoder_bwd_achain_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_decoder_bwd_achain_scratch_floats.restype = C.c_long
-    lib.t2v_decoder_bwd_achain.argtypes = [C.POINTER(_DecTrainPersistWeights), C.c_void_p, C.POINTER(_DecTrainBufs)] + [C.c_void_p] * 8 + [
+    lib.t2v_gemm_f32_grouped_handed.argtypes = [C.POINTER(_GemmGroup), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_void_p]
+    lib.t2v_gemm_f32_grouped_group_offset.argtypes = [C.POINTER(_GemmGroup), C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.t2v_gemm_f32_grouped_group_offset.restype = C.c_long
+    lib.t2v_decoder_bwd_achain_dw_offset.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.t2v_decoder_bwd_achain_dw_offset.restype = C.c_long
+    lib.t2v_decoder_bwd_achain.argtypes = [C.POINTER(_DecTrainPersistWeights), C.POINTER(_AchainDw), C.POINTER(_DecTrainBufs)] + [C.c_void_p] * 8 + [
         C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
     lib.t2v_decoder_bwd_persist_slices.argtypes = [C.c_int]
     lib.t2v_decoder_bwd_achain_dq_offset.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -850,7 +863,7 @@ _FWD_ENGINES = {
 # slices / scratch / dq_offset: size queries.  dq_rows: row stride of the (T, rows, 128) view of dq(t) inside scratch (None = the
 # chunk's batch).  prepare / prepared / run: the preparation alone, the pass behind it, both in one call.  arena_prepare: the
 # preparation reads the forward arena (its factor arrays) and takes the dropout arguments; reserved: prepared / run take the
-# header's `reserved` pointer behind the weights.  keep: arena tensors the preparation reads on the deferred-work stream.
+# header's `dw` pointer (weight-gradient epilogue, None = none) behind the weights.  keep: arena tensors the preparation reads on the deferred-work stream.
 _BwdEngine = collections.namedtuple('_BwdEngine', 'kernel slices scratch dq_offset dq_rows prepare prepared run arena_prepare '
                                                   'reserved keep')
 _BWD_ENGINES = {
@@ -865,8 +878,9 @@ _STEPS_KERNELS = {'fwd': 'k_lstm_fwd256 + k_attn_fwd', 'bwd': 'k_lstm_bwd256 + k
 # the forward arena of a chunk, in the order DecoderCore keeps it (last_call[3], ctx.chunks): the fields of t2v_dec_train_bufs
 _ARENA = tuple(n for n, _ in _DecTrainBufs._fields_)
 # one batch chunk [b0, b1): fwd 'persist' | 'persist16' | 'steps'; bwd 'achain' | 'persist16' | 'steps' | None (no gradient);
-# prepare: the reverse pass's preparation is issued right behind the forward launch
-ChunkPlan = collections.namedtuple('ChunkPlan', 'b0 b1 fwd bwd prepare')
+# prepare: the reverse pass's preparation is issued right behind the forward launch; dw_epilogue: the decoder_rnn workgroups of
+# the fp32 one-launch reverse pass work on decoder_rnn's weight gradients once their chain has ended (t2v_achain_dw)
+ChunkPlan = collections.namedtuple('ChunkPlan', 'b0 b1 fwd bwd prepare dw_epilogue')
 
 
 def _chunk_seed(seed, b0):
@@ -879,11 +893,13 @@ def _persist_weights(raw, bias_dec, wcomb, vv):
     return _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq), _p(wcomb), _p(vv))
 
 
-def _bwd_launch(lib, eng, prepared, PW, Sb, bufs, dims):
+def _bwd_launch(lib, eng, prepared, PW, Sb, bufs, dims, dw=None):
     """one-launch reverse pass of engine `eng`: bufs = (dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word),
-    dims = (B, T_in, T, p_att, p_dec, seed); prepared: the preparation has been issued on these buffers"""
+    dims = (B, T_in, T, p_att, p_dec, seed); prepared: the preparation has been issued on these buffers;
+    dw: the _AchainDw of the weight-gradient epilogue ('achain' only: the slot behind the weights)"""
     name = eng.prepared if prepared else eng.run
-    head = (C.byref(PW), None, C.byref(Sb)) if eng.reserved else (C.byref(PW), C.byref(Sb))
+    assert dw is None or eng.reserved
+    head = (C.byref(PW), None if dw is None else C.byref(dw), C.byref(Sb)) if eng.reserved else (C.byref(PW), C.byref(Sb))
     _check(getattr(lib, name)(*(head + tuple(_p(t) for t in bufs) + tuple(dims) + (_stream(),))), name)
 
 
@@ -919,7 +935,10 @@ def replay_persistent_backward():
                           "DecoderCore.keep_last was off)")
     PW, Sb, bufs, dims, _keep = DecoderCore.last_bwd_persist
     eng = _BWD_ENGINES['persist16' if DecoderCore.last_bwd_kernel == _BWD_ENGINES['persist16'].kernel else 'achain']
-    _bwd_launch(load_library(), eng, False, PW, Sb, bufs, dims)
+    # (with the weight-gradient epilogue when the pass had one: the call's own preparation zeroes its control words, the tiles it
+    # takes are computed again)
+    dwh = _keep[-1] if isinstance(_keep[-1], GroupedHandOver) else None
+    _bwd_launch(load_library(), eng, False, PW, Sb, bufs, dims, None if dwh is None else dwh.dw)
     return 1
 
 
@@ -989,6 +1008,7 @@ class DecoderCore(torch.autograd.Function):
     last_persist = None     # keep_last: (weights, bufs, scratch, dims, tensors) of the last persistent forward, for replays
     last_bwd = None         # keep_last: the same for the launch-per-step / ...
     last_bwd_persist = None     # ... the one-launch reverse pass of the first chunk
+    dw_tile_cap = None      # tests: at most this many tiles in the weight-gradient epilogue of a reverse pass (None: no cap)
     last_mode = None        # 'persistent' | 'launch-per-step' of the most recent forward chunk
     last_bwd_mode = None
     last_kernel = None      # name of the forward kernel of the most recent chunk
@@ -1022,7 +1042,9 @@ class DecoderCore(torch.autograd.Function):
           'steps'      otherwise — and then for EVERY chunk of the call: the launch-per-step pass reads transposed weight
                        packs that one call either builds or does not.
         The 16 forward follows the forward switch, the 16 reverse pass the reverse switch.  The preparation of a one-launch
-        reverse pass is issued behind the forward launch when that chunk's forward is a persistent kernel too."""
+        reverse pass is issued behind the forward launch when that chunk's forward is a persistent kernel too.
+        Weight-gradient epilogue (dw_epilogue): 'achain' chunks of an fp32 run whose LSTM weight gradients take the grouped
+        plane launch — not under bf16_run, T2V_F32_GEMM=native or T2V_DW_GROUPED=0; T2V_DW_EPILOGUE=0 switches it off."""
         D = DecoderCore
         env = os.environ.get
         fwd_on = D.persistent if D.persistent is not None else env('T2V_TRAIN_PERSISTENT', '1') != '0'
@@ -1050,7 +1072,10 @@ class DecoderCore(torch.autograd.Function):
                 bwd.append(None)
         if 'steps' in bwd:
             bwd = ['steps'] * len(bwd)
-        return [ChunkPlan(b0, b1, f, r, f != 'steps' and r in _BWD_ENGINES) for (b0, b1), f, r in zip(chunks, fwd, bwd)]
+        dw_on = (not _BF16 and env('T2V_DW_EPILOGUE', '1') != '0' and env('T2V_DW_GROUPED', '1') != '0' and
+                 env('T2V_F32_GEMM', '') not in ('native', '0'))
+        return [ChunkPlan(b0, b1, f, r, f != 'steps' and r in _BWD_ENGINES, dw_on and r == 'achain')
+                for (b0, b1), f, r in zip(chunks, fwd, bwd)]
 
     @staticmethod
     def _note(fwd=None, bwd=None, **kept):
@@ -1066,6 +1091,23 @@ class DecoderCore(torch.autograd.Function):
             D.chunk_bwd_kernels.append(D.last_bwd_kernel)
         for name, value in kept.items():
             setattr(D, name, value)
+
+    @staticmethod
+    def _wgrad_tensors(ctx, f32):
+        """gradient tensors of the four nn.LSTMCell weights (arena slots when FlatAdam registered them)"""
+        wg = [grad_slot(w) for w in ctx.wrefs]
+        return [torch.empty(w.shape, **f32) if g is None else g for g, w in zip(wg, ctx.wrefs)]
+
+    @staticmethod
+    def _dw_groups(DGA, DGD, XS, wg, pre_c, T, B):
+        """the five LSTM weight-gradient products of a chunk as the two groups of gemm_grouped"""
+        TB = T * B
+        x_prev, x_cur = XS[0:T].reshape(TB, XW), XS[1:T + 1].reshape(TB, XW)
+        d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec = wg
+        att = [(x_prev[:, :H].t(), d_w_hh_att), (x_prev[:, H:KATT].t(), d_w_ih_att[:, PRE:])]
+        if pre_c is not None:
+            att.insert(0, (pre_c.t(), d_w_ih_att[:, :PRE]))
+        return [(DGA.view(TB, G4).t(), att), (DGD.view(TB, G4).t(), [(x_cur[:, :KATT].t(), d_w_ih_dec), (x_cur[:, KATT:].t(), d_w_hh_dec)])]
 
     @staticmethod
     def _bwd_buffers(lib, eng, B, T_in, T, dev):
@@ -1217,6 +1259,7 @@ class DecoderCore(torch.autograd.Function):
         tcap = (T_in + 15) // 16 * 16
         acc = bacc = None
         wg = None
+        wg_fresh = False        # wg was made in front of this chunk's reverse pass (weight-gradient epilogue): nothing is in it yet
         dga_l, dmem_l, dpm_l, dpre_l = [], [], [], []
         DecoderCore._note(chunk_bwd_kernels=[])
         for ci, (plan, keep) in enumerate(zip(ctx.plans, ctx.chunks)):
@@ -1232,6 +1275,7 @@ class DecoderCore(torch.autograd.Function):
             NS = lib.t2v_attn_bwd_slices(T_in) if eng is None else getattr(lib, eng.slices)(T_in)
             DV = torch.empty(B, NS, A, **f32)
             Sb = _DecTrainBufs(*(_p(t) for t in keep))
+            dwh = None          # the GroupedHandOver of this chunk's weight-gradient epilogue
             if eng is not None:
                 # the whole reverse pass as ONE persistent launch (csrc/decoder_train_bwd_persist.hip; bf16_run, B <= 16: on bf16
                 # MFMA tiles, csrc/decoder_train_bwd_persist16.hip)
@@ -1242,16 +1286,32 @@ class DecoderCore(torch.autograd.Function):
                     torch.cuda.current_stream().wait_event(pev)     # (always: the preparation ran on a side stream)
                 else:
                     DQP, scratch, errw = DecoderCore._bwd_buffers(lib, eng, B, T_in, T, dev)
+                if plan.dw_epilogue and set_f32_gemm_mode(None) and T * B >= 32:
+                    # the decoder_rnn workgroups go on with decoder_rnn's weight gradients when their chain has ended: the gradient
+                    # tensors, the grouped launch's scratch and its groups have to exist before the pass
+                    if wg is None:
+                        wg, wg_fresh = DecoderCore._wgrad_tensors(ctx, f32), True
+                    pre_c = None
+                    if ctx.pre2 is not None:
+                        pre_c = ctx.pre2 if B == Bt else ctx.pre2.view(T, Bt, PRE)[:, b0:b0 + B].reshape(T * B, PRE)
+                    groups = DecoderCore._dw_groups(DGA, DGD, XS, wg, pre_c, T, B)
+                    dwh = GroupedHandOver(groups, 1, scratch[lib.t2v_decoder_bwd_achain_dw_offset(B, T_in, T):][:1], not wg_fresh,
+                                          DecoderCore.dw_tile_cap)
+                    if not wg_fresh and overlap() is not None:
+                        # this pass adds to d_w_*_dec on the current stream; the tiles an earlier chunk left over were added by its
+                        # grouped launch on the deferred-GEMM stream
+                        overlap().wait('g')
                 stamp('dec_bwd_begin')
                 bufs = (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw)
-                _bwd_launch(lib, eng, prep is not None, PW, Sb, bufs, (B, T_in, T, p_att, p_dec, _chunk_seed(seed, b0)))
+                _bwd_launch(lib, eng, prep is not None, PW, Sb, bufs, (B, T_in, T, p_att, p_dec, _chunk_seed(seed, b0)),
+                            None if dwh is None else dwh.dw)
                 _err_note('decoder backward (persistent kernel hand-off)', errw)
                 dq_off = getattr(lib, eng.dq_offset)(B, T_in, T)       # slice 0 of every item has summed the slices already
                 rows = eng.dq_rows or B
                 dq_sum = scratch[dq_off:dq_off + T * rows * A].view(T, rows, A)[:, :B].reshape(T * B, A)
                 DecoderCore._note(bwd=plan.bwd)
                 if kept:
-                    DecoderCore._note(last_bwd_persist=(PW, Sb, bufs, (B, T_in, T, p_att, p_dec, seed), keep + (ctx.raw, wcomb, vv, bias_dec)))
+                    DecoderCore._note(last_bwd_persist=(PW, Sb, bufs, (B, T_in, T, p_att, p_dec, seed), keep + (ctx.raw, wcomb, vv, bias_dec, dwh)))
             else:
                 W = _DecWeights(_p(packF_att), _p(packF_dec), _p(packB_att), _p(packB_dec), None, _p(bias_dec),
                                 _p(wqT), _p(wcomb), _p(vv), int(bool(ctx.wbf)))
@@ -1291,12 +1351,12 @@ class DecoderCore(torch.autograd.Function):
                 dga2, dgd2 = DGA.view(TB, G4), DGD.view(TB, G4)
                 x_prev = XS[0:T].reshape(TB, XW)          # [h_att_{t-1} | ctx_{t-1} | .]
                 x_cur = XS[1:T + 1].reshape(TB, XW)       # [h_att_t | ctx_t | h_dec_{t-1}]
-                first = wg is None
-                if first:       # gradient tensors of the four nn.LSTMCell weights (arena slots when FlatAdam registered them)
-                    wg = [grad_slot(w) for w in ctx.wrefs]
-                    wg = [torch.empty(w.shape, **f32) if g is None else g for g, w in zip(wg, ctx.wrefs)]
-                    if ctx.pre2 is None:        # the prenet columns of attention_rnn.weight_ih get their gradient via gpre
-                        wg[0][:, :PRE].zero_()
+                first = wg is None or wg_fresh
+                if wg is None:  # gradient tensors of the four nn.LSTMCell weights (arena slots when FlatAdam registered them)
+                    wg = DecoderCore._wgrad_tensors(ctx, f32)
+                wg_fresh = False
+                if first and ctx.pre2 is None:      # the prenet columns of attention_rnn.weight_ih get their gradient via gpre
+                    wg[0][:, :PRE].zero_()
                 d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec = wg
                 # round 6: the five LSTM weight-gradient products as ONE launch of the plane kernel — both gate-gradient operands split
                 # (fp32: x3 planes; bf16_run: rounded) once, 1 024 tiles = two full rounds of the chip (T2V_DW_GROUPED=0: one by one)
@@ -1313,8 +1373,11 @@ class DecoderCore(torch.autograd.Function):
                 # accumulation) — no library GEMM is left in either step
                 # (measured round 4: without these four products the step is 0.71 ms shorter, alone they take 0.82 ms — they run
                 # NEXT to the other chains but the chip is shared, so almost all of their time is still on the step's clock)
-                with side('g', after=fork):
-                    if grouped:
+                with side('g', after=fork, keep=() if dwh is None else (dwh.scr,)):
+                    if dwh is not None:
+                        # (the pass has written the decoder_rnn group's planes and taken tiles of it: this launch does the rest)
+                        gemm_grouped(dwh.groups, accumulate=not first, handed=dwh)
+                    elif grouped:
                         att = [(x_prev[:, :H].t(), d_w_hh_att), (x_prev[:, H:KATT].t(), d_w_ih_att[:, PRE:])]
                         if ctx.pre2 is not None:
                             att.insert(0, (pre_c.t(), d_w_ih_att[:, :PRE]))
@@ -2040,13 +2103,51 @@ def _small_grads(params, n, f32):
     return out
 
 
-def gemm_grouped(groups, accumulate=False):
+def _group_array(groups):
+    arr = (_GemmGroup * len(groups))()
+    for g, (A, parts) in zip(arr, groups):
+        g.A, g.sAi, g.sAk, g.nb = A.data_ptr(), A.stride(0), A.stride(1), len(parts)
+        for p, (Bp, out) in enumerate(parts):
+            g.B[p], g.sBj[p], g.sBk[p], g.N[p] = Bp.data_ptr(), Bp.stride(0), Bp.stride(1), Bp.shape[0]
+            g.C[p], g.ldc[p] = out.data_ptr(), out.stride(0)
+    return arr
+
+
+class GroupedHandOver(object):
+    """What a kernel in FRONT of gemm_grouped(groups) needs to start on group `g` (the one-launch reverse pass on decoder_rnn's
+    weight gradients, t2v_achain_dw), and what gemm_grouped(groups, handed=this) needs to finish it: the launch's scratch, made
+    here; the counter word the first kernel takes tiles from; the test-only cap on those tiles (None: no cap)."""
+
+    def __init__(self, groups, g, counter, accumulate, cap=None):
+        lib = load_library()
+        assert g == 1 and len(groups) == 2 and len(groups[1][1]) == 2
+        M, K = groups[0][0].shape
+        self.groups, self.g, self.counter = groups, g, counter
+        arr = _group_array(groups)
+        off = lib.t2v_gemm_f32_grouped_group_offset(arr, len(groups), M, K, g)
+        if off < 0:
+            raise T2VHipError("GroupedHandOver: these products do not take the grouped plane launch")
+        self.scr = torch.empty(lib.t2v_gemm_f32_grouped_scratch_floats(arr, len(groups), M, K), device=counter.device, dtype=torch.float32)
+        self.cap = -1 if cap is None else int(cap)
+        (_, out_ih), (_, out_hh) = groups[g][1]
+        self.dw = _AchainDw(self.scr.data_ptr() + 4 * off, out_ih.data_ptr(), out_ih.stride(0), out_hh.data_ptr(), out_hh.stride(0),
+                            int(bool(accumulate)), self.cap)
+
+
+def gemm_grouped(groups, accumulate=False, handed=None):
     """groups: [(A (M,K), [(B_p (N_p,K), out_p (M,N_p)), ...]), ...] (at most two groups of at most three parts, one common M and K):
     out_p (+)= A · B_p^T for every part.  Every operand is split (fp32: into its three bf16 planes; bf16_run: rounded to bf16) once, all
     tiles run as ONE launch (t2v_gemm_f32_grouped / t2v_gemm_bf16_grouped); shapes the grouped kernel does not take: the products one by
-    one through gemm()."""
+    one through gemm().  handed: the GroupedHandOver of these groups — an earlier kernel has made one group's planes and some of
+    its tiles."""
     lib = _require_gpu(groups[0][0])
     M, K = groups[0][0].shape
+    if handed is not None:
+        assert handed.groups is groups and not _BF16
+        cap = handed.cap if handed.cap >= 0 else 2 ** 31 - 1
+        _check(lib.t2v_gemm_f32_grouped_handed(_group_array(groups), len(groups), M, K, int(bool(accumulate)), _p(handed.scr), handed.g,
+                                               _p(handed.counter), cap, _stream()), 't2v_gemm_f32_grouped_handed')
+        return
     ok = 1 <= len(groups) <= 2
     for A, parts in groups:
         ok = ok and A.shape == (M, K) and A.dtype == torch.float32 and 1 <= len(parts) <= 3
@@ -2057,12 +2158,7 @@ def gemm_grouped(groups, accumulate=False):
             for Bp, out in parts:
                 gemm(A, Bp, out=out, accumulate=accumulate)
         return
-    arr = (_GemmGroup * len(groups))()
-    for g, (A, parts) in zip(arr, groups):
-        g.A, g.sAi, g.sAk, g.nb = A.data_ptr(), A.stride(0), A.stride(1), len(parts)
-        for p, (Bp, out) in enumerate(parts):
-            g.B[p], g.sBj[p], g.sBk[p], g.N[p] = Bp.data_ptr(), Bp.stride(0), Bp.stride(1), Bp.shape[0]
-            g.C[p], g.ldc[p] = out.data_ptr(), out.stride(0)
+    arr = _group_array(groups)
     size_fn, run_fn = ((lib.t2v_gemm_bf16_grouped_scratch_floats, lib.t2v_gemm_bf16_grouped) if _BF16 else
                        (lib.t2v_gemm_f32_grouped_scratch_floats, lib.t2v_gemm_f32_grouped))
     nscr = size_fn(arr, len(groups), M, K)

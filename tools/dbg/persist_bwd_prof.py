@@ -39,6 +39,10 @@ print('   inside: park %d, cell pre-part %d' % (pv[12], pv[13]))
 print('T role (cycles per step): prefetch + wait dctx %d | softmax/tanh backward -> dq published %d | location backward + window partials %d | loop top %d || step %d'
       % (pv[9], pv[10], pv[11], pv[8], sum(pv[8:12])))
 print('decoder_rnn role (free-running): %.2f us per step; attention_rnn role: %.2f us per step' % ((raw[41] - raw[40]) * 0.01 / T, (raw[43] - raw[42]) * 0.01 / T))
+if raw[44]:     # the weight-gradient epilogue of the decoder_rnn role (workgroup 0 of the role), us on the 100 MHz counter
+    us = lambda i, j: (raw[j] - raw[i]) * 0.01
+    print('dW epilogue: barrier %.1f us | planes + barrier %.1f us | %d tile pairs in %.1f us (%.1f us per pair) | done %.1f us before the '
+          'attention_rnn chain ended' % (us(44, 45), us(45, 46), raw[48], us(46, 47), us(46, 47) / max(raw[48], 1), us(47, 43)))
 # per-workgroup time line of step T/2 (100 MHz chip-wide counter -> ns), relative to the first 'dq published' of that step
 S = lib.t2v_attn_bwd_slices(T_in); NT = B * S
 def col(w0, w1, slot):
