@@ -5,7 +5,7 @@
 //
 // k_achain_bwd<NB, LONG> runs the whole reverse recurrence on 256 resident workgroups in three roles (details at PBAArgs and
 // at pba_na below):
-//   T  attention(t) backward of one item and one slice of encoder positions,
+//   T  attention(t) backward of one item and one slice of encoder positions (t2v_attn_role_bwd.h, shared with the bf16 kernel),
 //   A  attention_rnn: dga(t+1) -> Wcat_att^T -> [d h_att(t) | d ctx(t)] -> (T role) -> dq(t) -> W_q^T -> cell backward -> dga(t)
 //      — the per-step dependency chain,
 //   D  decoder_rnn: dgd(t+1) -> W_hh_dec^T -> dh_dec(t) -> cell backward -> dgd(t).  Nothing of the attention path enters it
@@ -23,10 +23,11 @@
 #include "t2v_kernels.h"
 #include "t2v_xchg.h"
 #include "gemm_x3_tile.h"
+#include "t2v_attn_role_bwd.h"
 
-#define PB_THREADS 512
+#define PB_THREADS T2V_AB_THREADS
 #define PB_MAXB 6
-#define PB_MAXT 224                   // 16- / 32-position attention slices up to here
+#define PB_MAXT T2V_AB_MAXT           // 16- / 32-position attention slices up to here
 #define PB_MAXT_LONG 576              // 96-position slices on eight waves beyond (k_achain_bwd<.., true>): at most six per item
 #define PB_SPIN 400000
 #define PB_KJ (T2V_G / PB_THREADS)          // 8 gate rows per thread: k = tid + 512 j
@@ -285,142 +286,34 @@ struct PBAArgs {
 #define PB_CX_ROW_BYTES(NB) ((NB) > 4 ? 32768u : 16384u)
 
 __host__ __device__ static inline int pba_na(int NL);
-// JS: positions per slice (16 / 32: position-split slices on 4 waves; 96 (round 4): ONE workgroup per item on all 8 waves for
-// T_in <= 96 — no partial dq rows to sum, no window partials to exchange: one dependent hand-off less per reverse step).
-// NWV: waves that compute (4 or 8).  GPW: floats per channel of a slice's window-partial row in GPX.
-template <int JS, int NWV>
-__device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds, const int b, const int s, const int NB) {
-    constexpr int NJT = JS / 16;
-    constexpr int PW = JS + 30;
-    constexpr int GPW = PW <= 64 ? 64 : 128;
-    constexpr int NRG = 2 * NWV;                     // row groups of 32 lanes in the dpre loop
-    constexpr int DPS = JS == 96 ? JS + 17 : JS + 1; // row stride of dpT: = 17 mod 32, the four k-rows of an MFMA operand read land in
-                                                     // disjoint banks (JS + 1 = 97 = 1 mod 32 made that read 4-way conflicted)
-    static_assert(JS % NRG == 0 && JS % NWV == 0 && PW <= GPW, "slice geometry");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool act = tid < 64 * NWV;
-    const int g = lane >> 4, c16 = lane & 15;
-    const int B = a.B, Tp = a.T_in, T = a.T, S = a.S_sl, j0 = s * JS;
-    const int Tcap = (Tp + 15) & ~15;
-    const int nown = min(JS, Tp - j0);
-    const int NAw = pba_na(T2V_NWG - B * S);          // attention_rnn workgroups: producers of the context gradient
-    // ---- LDS carve
-    float* gfull0 = lds;                      // [Tcap]
-    float* gfull1 = gfull0 + Tcap;            // [Tcap]
-    float* alf = gfull1 + Tcap;               // [Tcap]
-    float* gcum = alf + Tcap;                 // [Tcap] running cumulative-weights gradient (this workgroup's copy)
-    float* dctx = gcum + Tcap;                // [512]
-    float* de = dctx + T2V_E;                 // [JS]
-    float* red = de + JS;                     // [1 + JS/NWV][4 NWV]
-    float* dpT = red + (1 + JS / NWV) * 4 * NWV;     // [128][JS+1]
-    float* Tl = dpT + T2V_A * DPS;            // [64][JS+1]
-    float* rq = Tl + 64 * (JS + 1);           // [NRG][128] (also: the 32 row partials of the dot product)
-    float* rv = rq + NRG * T2V_A;             // [NRG][128]
-    int* flag = (int*)(rv + NRG * T2V_A);
-    // (8-wave form: the W_comb^T operand tile of the location backward lives in LDS, not in 32 registers per thread — next to the
-    // 96 registers of memory rows they spilled)
-    constexpr bool AREG_LDS = NWV == 8;
-    float* wcs = (float*)(flag + 40);         // [64 rows (c,k)][128] when AREG_LDS
-    const __amdgpu_buffer_rsrc_t rC = t2v_rsrc(a.CX), rQ = t2v_rsrc(a.DQX), rP = t2v_rsrc(a.GPX), rQT = t2v_rsrc(a.DQT);
-    // ---- operands resident for the whole pass
-    const int d4 = tid & 31, rg = (tid >> 5) & (NRG - 1);
-    float4 m0[JS / NWV], m1[JS / NWV];
-    float areg[AREG_LDS ? 1 : 32];
-    float4 vd4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (act) {
-#pragma unroll
-        for (int r = 0; r < JS / NWV; ++r) {
-            const int jl = wave + NWV * r;
-            const float* mrow = a.memory + ((size_t)b * Tp + j0 + (jl < nown ? jl : 0)) * T2V_E + lane * 4;
-            m0[r] = *(const float4*)mrow;
-            m1[r] = *(const float4*)(mrow + 256);
-        }
-        if (!AREG_LDS) {
-            const float4* wp = (const float4*)(a.wcomb + T2V_A * 64 + (16 * (wave & 3) + c16) * 128 + 32 * g);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float4 w4 = wp[u];
-                areg[4 * u + 0] = w4.x; areg[4 * u + 1] = w4.y; areg[4 * u + 2] = w4.z; areg[4 * u + 3] = w4.w;
-            }
-        }
-        vd4 = *(const float4*)(a.v + 4 * d4);
-    }
-    if (AREG_LDS)
-        for (int i = tid; i < 64 * 128; i += PB_THREADS)          // row stride 132, 33 floats per k-group: conflict-free operand reads
-            wcs[(i >> 7) * 132 + ((i & 127) >> 5) * 33 + (i & 31)] = a.wcomb[T2V_A * 64 + i];
-    for (int j = tid; j < Tcap; j += PB_THREADS) gcum[j] = 0.f;
-    if (tid == 0) flag[0] = 1;
-    float dvacc = 0.f;                          // tid < 128: running dv[tid] of this slice
-    int nap = 0;
-    PBA_PROF_INIT(flag);
-    __syncthreads();
-    unsigned long long tprev_ = __builtin_readcyclecounter();
-
-    for (int t = T - 1; t >= 0; --t) {
-        // (thread-derived indices are recomputed per step from an opaque copy — see the attention_rnn role: hoisted, they are
-        // spilled next to the 96 registers of memory rows, and every reload is a drain of the wave's memory queue)
-        int tid_op = threadIdx.x;
-        asm volatile("" : "+v"(tid_op));
-        const int tid = tid_op, lane = tid & 63, wave = tid >> 6;
-        const bool act = tid < 64 * NWV;
-        const int g = lane >> 4, c16 = lane & 15;
-        const int d4 = tid & 31, rg = (tid >> 5) & (NRG - 1);
-        PBA_STAMP(blockIdx.x == 0, 8);
-        // ---- operands that do not wait for the context gradient: tanh outputs, alpha(t), ctx(t), window partials of step t+1
-        float4 sreg[JS / NRG];
-        float2 ctx2 = make_float2(0.f, 0.f);
-        if (act) {
-            const float* sp = a.S + (((size_t)t * B + b) * Tp + j0) * T2V_A + 4 * d4;
-#pragma unroll
-            for (int i = 0; i < JS / NRG; ++i) {
-                const int jl = rg + NRG * i;
-                sreg[i] = *(const float4*)(sp + (size_t)min(jl, nown - 1) * T2V_A);
-            }
-            if (tid < 256) ctx2 = *(const float2*)(a.XS + ((size_t)(t + 1) * B + b) * T2V_XW + T2V_H + 2 * tid);
-        }
-        float dot_g = 0.f;
-        for (int j = tid; j < Tp; j += PB_THREADS) {
-            float gp = 0.f, gc = gcum[j];
-            if (t < T - 1) {
-                const int lo = max(0, (j + 15 - PW + JS) / JS), hi = min(S - 1, (j + 15) / JS);
-                for (int sp2 = lo; sp2 <= hi; ++sp2) {
-                    const int jj = j - sp2 * JS + 15;
-                    if (jj < 0 || jj >= PW) continue;
-                    const unsigned off = (unsigned)((((t + 1) * B + b) * S + sp2) * (2 * GPW) + jj) * 4u;
-                    unsigned x0, x1;
-                    int spins = 0;
-                    for (;;) {          // published at the end of the previous reverse step: almost always there
-                        x0 = t2v_ld_b32(rP, off);
-                        x1 = t2v_ld_b32(rP, off + 4u * GPW);
-                        if (x0 != T2V_SENT && x1 != T2V_SENT) break;
-                        __builtin_amdgcn_s_sleep(1);
-                        if (t2v_give_up(spins, PB_SPIN, a.err, flag)) break;
-                    }
-                    gp += __uint_as_float(x0);
-                    gc += __uint_as_float(x1);
-                }
-            }
-            gcum[j] = gc;
-            gfull0[j] = gp;
-            gfull1[j] = gc;
-            const float al = a.AL[((size_t)(t + 1) * B + b) * Tp + j];
-            alf[j] = al;
-            dot_g = fmaf(al, gp + gc, dot_g);
-        }
-        // ---- the context gradient of this item (16 bytes per thread of waves 0 and 1), nap first
+// The attention role is t2v_attn_role_bwd.h; here is what it takes from this kernel.  d ctx(t) of item b lies in CX as the NAw
+// attention_rnn workgroups published it: threads [0, 2 NAw) poll their 16-byte slots, scatter by the producers' column ranges.
+template <int NB>
+struct PBAAttnHooks {
+    static constexpr int SPIN = PB_SPIN;
+    const PBAArgs& a;
+    const int b, NAw;                     // NAw: attention_rnn workgroups, the producers of the context gradient
+    const __amdgpu_buffer_rsrc_t rC;
+    unsigned long long* lprof_;
+    unsigned long long tprev_;
+    __device__ __forceinline__ PBAAttnHooks(const PBAArgs& a_, int b_, int)
+        : a(a_), b(b_), NAw(pba_na(T2V_NWG - a_.B * a_.S_sl)), rC(t2v_rsrc(a_.CX)), lprof_(nullptr), tprev_(0ull) {}
+    __device__ __forceinline__ int dqt_items() const { return a.B; }
+    __device__ __forceinline__ void dctx_early(int, int, int*) {}
+    __device__ __forceinline__ void dctx_arrive(int t, int tid, float* dctx, int& nap, int* flag) {
         if (tid < 2 * NAw) {
             const unsigned off = (unsigned)t * PB_CX_ROW_BYTES(NB) + (unsigned)b * 4096u + 16u * (unsigned)tid;
             for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
             // TWO polls in flight, half a round trip apart (round 4): with one, a row that lands just after a poll left is
-            // only seen a full memory round trip later — this hand-off is on the chain of every reverse step
+            // only seen a full memory round trip later
             f32x4 x, x0 = t2v_ld_f32x4(rC, off);
             __builtin_amdgcn_s_sleep(4);
             f32x4 x1 = t2v_ld_f32x4(rC, off);
             int rounds = 0;
             for (;;) {
-                if (__all(t2v_ok(x0[0]) && t2v_ok(x0[1]) && t2v_ok(x0[2]) && t2v_ok(x0[3]))) { x = x0; break; }
+                if (__all(t2v_ok4(x0))) { x = x0; break; }
                 x0 = t2v_ld_f32x4(rC, off);
-                if (__all(t2v_ok(x1[0]) && t2v_ok(x1[1]) && t2v_ok(x1[2]) && t2v_ok(x1[3]))) { x = x1; break; }
+                if (__all(t2v_ok4(x1))) { x = x1; break; }
                 x1 = t2v_ld_f32x4(rC, off);
                 if (t2v_give_up(rounds, PB_SPIN, a.err, flag)) { x = x0; break; }
             }
@@ -432,155 +325,23 @@ __device__ __forceinline__ void pba_attention_role(const PBAArgs& a, float* lds,
             for (int i = 0; i < 4; ++i)
                 if (h4 + i < ncc) dctx[cc0 + h4 + i] = x[i];
         }
-        __syncthreads();
-        if (flag[0] != 1) return;
-        PBA_STAMP(blockIdx.x == 0, 9);
-        PBA_RT(0);
-        // ---- dot = dctx·ctx_t + sum_j alpha_j (Gprev_j + Gcum_j); dalpha of the own positions = dctx·memory_j + G_j
-        {
-            float dotp = dot_g;
-            if (tid < 256) dotp += dctx[2 * tid] * ctx2.x + dctx[2 * tid + 1] * ctx2.y;
-            dotp = row16_sum(dotp);
-            // 32 row partials (8 waves x 4 rows): waves 4..7 carry only their share of dot_g
-            if (c16 == 0) rq[4 * wave + g] = dotp;
-            if (act) {
-                const float4 d0 = *(const float4*)(dctx + lane * 4), d1 = *(const float4*)(dctx + 256 + lane * 4);
-#pragma unroll
-                for (int r = 0; r < JS / NWV; ++r) {
-                    float acc = m0[r].x * d0.x;
-                    acc = fmaf(m0[r].y, d0.y, acc); acc = fmaf(m0[r].z, d0.z, acc); acc = fmaf(m0[r].w, d0.w, acc);
-                    acc = fmaf(m1[r].x, d1.x, acc); acc = fmaf(m1[r].y, d1.y, acc);
-                    acc = fmaf(m1[r].z, d1.z, acc); acc = fmaf(m1[r].w, d1.w, acc);
-                    acc = row16_sum(acc);
-                    if (c16 == 0) red[(1 + r) * 4 * NWV + 4 * wave + g] = acc;
-                }
-            }
-        }
-        __syncthreads();
-        if (tid < JS) {
-            float dsum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 32; ++u) dsum += rq[u];
-            const int wv = tid % NWV, r = tid / NWV;              // position tid = wv + NWV r
-            const float* rr = red + (1 + r) * 4 * NWV + 4 * wv;
-            const float dalv = ((rr[0] + rr[1]) + (rr[2] + rr[3])) + gfull0[j0 + min(tid, nown - 1)] + gfull1[j0 + min(tid, nown - 1)];
-            de[tid] = tid < nown ? alf[j0 + tid] * (dalv - dsum) : 0.f;
-        }
-        __syncthreads();
-        // ---- through v·tanh(.): dpre, partial dq / dv
-        if (act) {
-            float4 dq = make_float4(0.f, 0.f, 0.f, 0.f), dv = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int i = 0; i < JS / NRG; ++i) {
-                const int jl = rg + NRG * i;
-                const float dej = de[jl];
-                const float4 sv = sreg[i];
-                float4 dp;
-                dp.x = dej * vd4.x * (1.0f - sv.x * sv.x); dp.y = dej * vd4.y * (1.0f - sv.y * sv.y);
-                dp.z = dej * vd4.z * (1.0f - sv.z * sv.z); dp.w = dej * vd4.w * (1.0f - sv.w * sv.w);
-                sreg[i] = dp;           // the saved copy (operand of the d W_comb / d memory_layer products) leaves AFTER the hand-off
-                dq.x += dp.x; dq.y += dp.y; dq.z += dp.z; dq.w += dp.w;
-                dv.x = fmaf(dej, sv.x, dv.x); dv.y = fmaf(dej, sv.y, dv.y); dv.z = fmaf(dej, sv.z, dv.z); dv.w = fmaf(dej, sv.w, dv.w);
-                dpT[(4 * d4 + 0) * DPS + jl] = dp.x; dpT[(4 * d4 + 1) * DPS + jl] = dp.y;
-                dpT[(4 * d4 + 2) * DPS + jl] = dp.z; dpT[(4 * d4 + 3) * DPS + jl] = dp.w;
-            }
-            *(float4*)&rq[rg * T2V_A + 4 * d4] = dq;
-            *(float4*)&rv[rg * T2V_A + 4 * d4] = dv;
-        }
-        __syncthreads();
-        if (tid < T2V_A) {
-            float q = 0.f, vv = 0.f;
-            {
-                const float* p = rq + tid;
-                q = ((p[0] + p[T2V_A]) + (p[2 * T2V_A] + p[3 * T2V_A])) + ((p[4 * T2V_A] + p[5 * T2V_A]) + (p[6 * T2V_A] + p[7 * T2V_A]));
-                const float* p2 = rv + tid;
-                vv = ((p2[0] + p2[T2V_A]) + (p2[2 * T2V_A] + p2[3 * T2V_A])) + ((p2[4 * T2V_A] + p2[5 * T2V_A]) + (p2[6 * T2V_A] + p2[7 * T2V_A]));
-                if (NRG > 8) {
-                    p += 8 * T2V_A; p2 += 8 * T2V_A;
-                    q += ((p[0] + p[T2V_A]) + (p[2 * T2V_A] + p[3 * T2V_A])) + ((p[4 * T2V_A] + p[5 * T2V_A]) + (p[6 * T2V_A] + p[7 * T2V_A]));
-                    vv += ((p2[0] + p2[T2V_A]) + (p2[2 * T2V_A] + p2[3 * T2V_A])) + ((p2[4 * T2V_A] + p2[5 * T2V_A]) + (p2[6 * T2V_A] + p2[7 * T2V_A]));
-                }
-            }
-            t2v_st(rQ, (unsigned)(((t * B + b) * S + s) * T2V_A + tid) * 4u, q);       // partial row (the d W_q GEMM reads them later)
-            dvacc += vv;
-            if (s == 0) {
-                // Round 4: slice 0 of an item sums the S partial rows in slice order and publishes ONE row per item.  The ≥ 79
-                // attention_rnn workgroups used to pull all B*S partial rows each (18 KB per workgroup and step through the
-                // ≈ 11 B/cycle a CU gets from beyond its L2: 2.7 us from "published" to "gathered"); now they pull B rows (3 KB)
-                // (all partial rows are requested in ONE round: a round trip per slice would cost 0.45 us each)
-                constexpr int SMAX = PB_MAXT / 16;              // 14 slices at most
-                const unsigned off0 = (unsigned)(((t * B + b) * S) * T2V_A + tid) * 4u;
-                unsigned x[SMAX];
-                int spins = 0;
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) {
-                        x[s2] = t2v_ld_b32(rQ, off0 + (unsigned)(min(s2, S - 1) * T2V_A) * 4u);
-                    }
-#pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) ok = ok && (s2 >= S || x[s2] != T2V_SENT);
-                    if (__all(ok)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (t2v_give_up(spins, PB_SPIN, a.err, flag)) break;
-                }
-                float tot = q;
-#pragma unroll
-                for (int s2 = 1; s2 < SMAX; ++s2) tot += s2 < S ? __uint_as_float(x[s2]) : 0.f;
-                t2v_st(rQT, (unsigned)((t * B + b) * T2V_A + tid) * 4u, tot);           // the cell workgroups wait for this
-            }
-        }
-        PBA_STAMP(blockIdx.x == 0, 10);
-        PBA_RT(1);
-        if (act) {      // dpre rows: 8 KB of stores that must not sit in this CU's memory pipe in front of the dq words above
-            float* sp = a.S + (((size_t)t * B + b) * Tp + j0) * T2V_A + 4 * d4;
-#pragma unroll
-            for (int i = 0; i < JS / NRG; ++i) {
-                const int jl = rg + NRG * i;
-                if (jl < nown) *(float4*)(sp + (size_t)jl * T2V_A) = sreg[i];
-            }
-        }
-        // ---- through the fused location filter on MFMA: T[(c,k)][jl] = sum_d W_comb[d][(c,k)] dpre[jl][d], K = 128
-        if (act) {
-#pragma unroll
-            for (int jt = (wave >> 2); jt < NJT; jt += NWV / 4) {     // (8 waves: waves 4..7 take the odd position tiles)
-                f32x4 ac4[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ac4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int st = 0; st < 32; ++st) {
-                    const float av = AREG_LDS ? wcs[(16 * (wave & 3) + c16) * 132 + 33 * g + st] : areg[AREG_LDS ? 0 : st];
-                    ac4[st & 3] = mfma16x4(av, dpT[(4 * st + g) * DPS + 16 * jt + c16], ac4[st & 3]);
-                }
-                const f32x4 acc = (ac4[0] + ac4[1]) + (ac4[2] + ac4[3]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Tl[(16 * (wave & 3) + 4 * g + r) * (JS + 1) + 16 * jt + c16] = acc[r];
-            }
-        }
-        __syncthreads();
-        // ---- gradient wrt the alignment window of this slice -> the slices of step t-1 (their window partials)
-        if (tid < 2 * GPW && t > 0) {
-            const int c = tid / GPW, jj = tid % GPW;
-            if (jj < PW) {
-                float tt[T2V_KS];
-#pragma unroll
-                for (int k = 0; k < T2V_KS; ++k) {
-                    const int jl = jj - k;
-                    const float tv = Tl[(32 * c + k) * (JS + 1) + min(max(jl, 0), JS - 1)];
-                    tt[k] = (jl >= 0 && jl < JS) ? tv : 0.f;
-                }
-                float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-#pragma unroll
-                for (int k = 0; k + 3 < T2V_KS; k += 4) { acc0 += tt[k]; acc1 += tt[k + 1]; acc2 += tt[k + 2]; acc3 += tt[k + 3]; }
-                acc0 += tt[28]; acc1 += tt[29]; acc2 += tt[30];
-                t2v_st(rP, (unsigned)(((t * B + b) * S + s) * (2 * GPW) + c * GPW + jj) * 4u, (acc0 + acc1) + (acc2 + acc3));
-            }
-        }
-        __syncthreads();
-        PBA_STAMP(blockIdx.x == 0, 11);
     }
-    if (tid < T2V_A) a.DV[((size_t)b * S + s) * T2V_A + tid] = dvacc;
-    PBA_PROF_FLUSH(blockIdx.x == 0, 8, 4);
+    // phase profile of workgroup 0 (slots 8..11) + the time line of step T/2
+    __device__ __forceinline__ void prof_init(int* flag) {
+        lprof_ = (unsigned long long*)(flag + 4);
+        if (threadIdx.x < 16) lprof_[threadIdx.x] = 0ull;
+    }
+    __device__ __forceinline__ void pass_begin() { tprev_ = __builtin_readcyclecounter(); }
+    __device__ __forceinline__ void stamp(int t, int point) {
+        PBA_STAMP(blockIdx.x == 0, 8 + point);
+        if (point == T2V_AB_DCTX) PBA_RT(0);
+        if (point == T2V_AB_DQ) PBA_RT(1);
+    }
+    __device__ __forceinline__ void pass_end() { PBA_PROF_FLUSH(blockIdx.x == 0, 8, 4); }
+};
+template <int JS, int NWV, int NB>
+__device__ __forceinline__ void pba_attention(const PBAArgs& a, float* lds, const int b, const int s) {
+    t2v_attn_role_bwd<JS, NWV, PBAAttnHooks<NB>>(a, lds, b, s);
 }
 
 // y[C0 + c][pair] = sum_j w[C0 + c][j] * x[k_j][pair] for NC <= 2 of the thread's columns into v[16] (two columns x 8 item
@@ -1228,7 +989,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     // (-DPBA_ONLY=1..4 builds ONE role into the kernel: `hipcc -Rpass-analysis=kernel-resource-usage` then reports that role's
     // own register pressure — the combined kernel always shows the maximum over the roles; tools/dbg/role_regs.sh)
 #if defined(PBA_ONLY) && PBA_ONLY == 1
-    pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
+    pba_attention<16, 4, NB>(a, lds, wg / S, wg % S);
 #elif defined(PBA_ONLY) && PBA_ONLY == 2
     pba_attention_rnn_role<NB, 12, 6>(a, lds, wg - NT, NA);
 #elif defined(PBA_ONLY) && PBA_ONLY == 3
@@ -1237,9 +998,9 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     pba_decoder_role<NB>(a, lds, wg - NT - NA, ND);
 #else
     if (wg < NT) {
-        if (LONG) pba_attention_role<96, 8>(a, lds, wg / S, wg % S, NB);
-        else if (a.T_in <= 128) pba_attention_role<16, 4>(a, lds, wg / S, wg % S, NB);
-        else pba_attention_role<32, 4>(a, lds, wg / S, wg % S, NB);
+        if (LONG) pba_attention<96, 8, NB>(a, lds, wg / S, wg % S);
+        else if (a.T_in <= 128) pba_attention<16, 4, NB>(a, lds, wg / S, wg % S);
+        else pba_attention<32, 4, NB>(a, lds, wg / S, wg % S);
     } else if (wg < NT + NA) {
         if (NA >= 114) pba_attention_rnn_role<NB, 9, 5>(a, lds, wg - NT, NA);
         else if (NA >= 86) pba_attention_rnn_role<NB, 12, 6>(a, lds, wg - NT, NA);
@@ -1257,9 +1018,7 @@ extern "C" int t2v_decoder_bwd_persist_slices(int T_in) { return T_in < 1 ? 0 : 
 
 static size_t pba_lds_bytes(int B, int T_in) {
     const size_t lrole = PBA_LROLE_FLOATS(B > 4 ? 6 : 4);
-    const size_t Tcap = (size_t)((T_in + 15) / 16) * 16, JS = (size_t)pba_js(T_in), NWV = JS == 96 ? 8 : 4;
-    const size_t trole = 4 * Tcap + T2V_E + JS + (1 + JS / NWV) * 4 * NWV + T2V_A * (JS == 96 ? JS + 17 : JS + 1) + 64 * (JS + 1) +
-                         2 * 2 * NWV * T2V_A + 40 + (NWV == 8 ? 64 * 132 : 0);
+    const size_t trole = t2v_attn_bwd_lds_floats(T_in, pba_js(T_in));
     return sizeof(float) * (lrole > trole ? lrole : trole);
 }
 

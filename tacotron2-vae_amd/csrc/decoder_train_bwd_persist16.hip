@@ -16,8 +16,8 @@
 //   C : 16 + 16 workgroups — the LSTM cells of 64 hidden units each (attention_rnn / decoder_rnn): sum the four partials of
 //       their columns, add what else flows into d h (projection gradient; W_q^T dq on the fp32 MFMA; E_h from the other
 //       chain), run the cell backward, save the gate gradients and publish them as the next bf16 row.
-//   T : B * S workgroups — attention(t) backward, split over encoder positions (the role of decoder_train_bwd_persist.hip;
-//       its context gradient is now the sum of 4 + 4 partial rows + the projection's share).
+//   T : B * S workgroups — attention(t) backward, split over encoder positions (t2v_attn_role_bwd.h, shared with
+//       decoder_train_bwd_persist.hip; here its context gradient is the sum of 4 + 4 partial rows + the projection's share).
 // The decoder_rnn chain (C_d -> G_d -> C_d, two hand-offs per step) needs nothing from the attention chain and free-runs
 // ahead; the attention chain per step is  C_a publishes dga(t+1) -> G_a -> partial ya -> T: d ctx(t) -> attention backward
 // -> dq(t) -> C_a: W_q^T dq + cell -> dga(t).
@@ -27,10 +27,10 @@
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_xchg.h"
+#include "t2v_attn_role_bwd.h"
 
-#define Q16_THREADS 512
+#define Q16_THREADS T2V_AB_THREADS
 #define Q16_MAXB 16
-#define Q16_MAXT 224                    // (SMAX below: 16- / 32-position slices up to here)
 #define Q16_MAXT_LONG 560               // 96-position slices on eight waves from 193 symbols on (six per item: 16 x 6 = 96 workgroups);
                                         // the range of the forward kernel, k_dec_train_persist16<true>
 #define Q16_SPIN 400000
@@ -338,137 +338,32 @@ __device__ __forceinline__ void q16_cell_role(const Q16Args& a, float* lds, cons
 }
 
 // ======================================================================= T role: attention(t) backward of (item b, slice s)
-// The position-split body of decoder_train_bwd_persist.hip (softmax / tanh / fused-location-filter backward; operands that do
-// not change over the pass resident in registers, the cumulative-weights gradient in LDS), with the context gradient taken
-// from the partial rows of the G workgroups: d ctx(t) = sum_q PA(t+1)[q][ctx] + sum_q PD(t)[q][E_c] + dHC(t)[ctx].
-// NWV: waves that compute — 4 (16- / 32-position slices) or 8 (96-position slices: the form decoder_train_bwd_persist.hip
-// built in round 4; W_comb^T operand tile in LDS, dpT row stride 17 mod 32, window-partial rows of 128 floats per channel).
-template <int JS, int NWV = 4>
-__device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds, const int b, const int s) {
-    constexpr int NJT = JS / 16;
-    constexpr int PW = JS + 30;
-    constexpr int GPW = PW <= 64 ? 64 : 128;
-    constexpr int NRG = 2 * NWV;                     // row groups of 32 lanes in the dpre loop
-    constexpr int DPS = JS == 96 ? JS + 17 : JS + 1;
-    static_assert(JS % NRG == 0 && JS % NWV == 0 && PW <= GPW, "slice geometry");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool act = tid < 64 * NWV;
-    const int g = lane >> 4, c16 = lane & 15;
-    const int B = a.B, Tp = a.T_in, T = a.T, S = a.S_sl, j0 = s * JS;
-    const int Tcap = (Tp + 15) & ~15;
-    const int nown = min(JS, Tp - j0);
-    // ---- LDS carve
-    float* gfull0 = lds;                      // [Tcap]
-    float* gfull1 = gfull0 + Tcap;            // [Tcap]
-    float* alf = gfull1 + Tcap;               // [Tcap]
-    float* gcum = alf + Tcap;                 // [Tcap] running cumulative-weights gradient (this workgroup's copy)
-    float* dctx = gcum + Tcap;                // [512]
-    float* de = dctx + T2V_E;                 // [JS]
-    float* red = de + JS;                     // [1 + JS/NWV][4 NWV]
-    float* dpT = red + (1 + JS / NWV) * 4 * NWV;     // [128][JS+1]
-    float* Tl = dpT + T2V_A * DPS;            // [64][JS+1]
-    float* rq = Tl + 64 * (JS + 1);           // [NRG][128] (also: the 32 row partials of the dot product)
-    float* rv = rq + NRG * T2V_A;             // [NRG][128]
-    int* flag = (int*)(rv + NRG * T2V_A);
-    constexpr bool AREG_LDS = NWV == 8;
-    float* wcs = (float*)(flag + 40);         // [64 rows (c,k)][132] when AREG_LDS
-    const __amdgpu_buffer_rsrc_t rPA = t2v_rsrc(a.PA), rPD = t2v_rsrc(a.PD), rQ = t2v_rsrc(a.DQX), rP = t2v_rsrc(a.GPX), rQT = t2v_rsrc(a.DQT);
-    // ---- operands resident for the whole pass
-    float4 m0[JS / NWV], m1[JS / NWV];
-    float areg[AREG_LDS ? 1 : 32];
-    float4 vd4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (act) {
-        const int d4 = tid & 31;
-#pragma unroll
-        for (int r = 0; r < JS / NWV; ++r) {
-            const int jl = wave + NWV * r;
-            const float* mrow = a.memory + ((size_t)b * Tp + j0 + (jl < nown ? jl : 0)) * T2V_E + lane * 4;
-            m0[r] = *(const float4*)mrow;
-            m1[r] = *(const float4*)(mrow + 256);
-        }
-        if constexpr (!AREG_LDS) {
-            const float4* wp = (const float4*)(a.wcomb + T2V_A * 64 + (16 * (wave & 3) + c16) * 128 + 32 * g);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float4 w4 = wp[u];
-                areg[4 * u + 0] = w4.x; areg[4 * u + 1] = w4.y; areg[4 * u + 2] = w4.z; areg[4 * u + 3] = w4.w;
-            }
-        }
-        vd4 = *(const float4*)(a.v + 4 * d4);
-    }
-    if (AREG_LDS)
-        for (int i = tid; i < 64 * 128; i += Q16_THREADS)          // row stride 132, 33 floats per k-group: conflict-free operand reads
-            wcs[(i >> 7) * 132 + ((i & 127) >> 5) * 33 + (i & 31)] = a.wcomb[T2V_A * 64 + i];
-    for (int j = tid; j < Tcap; j += Q16_THREADS) gcum[j] = 0.f;
-    if (tid == 0) flag[0] = 1;
-    float dvacc = 0.f;                          // tid < 128: running dv[tid] of this slice
-    int nap = 0;
-    __syncthreads();
-
-    for (int t = T - 1; t >= 0; --t) {
-        // (thread-derived indices are recomputed per step from an opaque copy: hoisted, they are spilled next to the registers of
-        // memory rows, and every reload is a drain of the wave's memory queue)
-        int tid_op = threadIdx.x;
-        asm volatile("" : "+v"(tid_op));
-        const int tid = tid_op, lane = tid & 63, wave = tid >> 6;
-        const bool act = tid < 64 * NWV;
-        const int g = lane >> 4, c16 = lane & 15;
-        const int d4 = tid & 31, rg = (tid >> 5) & (NRG - 1);
-        Q16_RT(0);
-        // ---- operands that do not wait for the context gradient: tanh outputs, alpha(t), ctx(t), window partials of step t+1,
-        // and the early part of the context gradient (decoder_rnn's E_c(t) — that chain runs ahead — + the projection's share)
-        float4 sreg[JS / NRG];
-        float2 ctx2 = make_float2(0.f, 0.f);
-        f32x4 dc_early = {0.f, 0.f, 0.f, 0.f};
-        if (act) {
-            const float* sp = a.S + (((size_t)t * B + b) * Tp + j0) * T2V_A + 4 * d4;
-#pragma unroll
-            for (int i = 0; i < JS / NRG; ++i) {
-                const int jl = rg + NRG * i;
-                sreg[i] = *(const float4*)(sp + (size_t)min(jl, nown - 1) * T2V_A);
-            }
-            if (tid < 256) ctx2 = *(const float2*)(a.XS + ((size_t)(t + 1) * B + b) * T2V_XW + T2V_H + 2 * tid);
-        }
+// The role itself is t2v_attn_role_bwd.h; here is what it takes from this kernel.  The context gradient comes from the partial
+// rows of the G workgroups: d ctx(t) = sum_q PA(t+1)[q][ctx] + sum_q PD(t)[q][E_c] + dHC(t)[ctx], 16 bytes x 4 quarters per
+// thread of waves 0 and 1.  The early part (decoder_rnn's E_c(t) — that chain runs ahead — + the projection's share) is fetched
+// before the window loop, the four PA rows at the hand-off; slice 0 also saves the sum (DCTX) for the d_memory product.
+struct Q16AttnHooks {
+    static constexpr int SPIN = Q16_SPIN;
+    const Q16Args& a;
+    const __amdgpu_buffer_rsrc_t rPA, rPD;
+    const int b, s;
+    f32x4 dc_early;
+    __device__ __forceinline__ Q16AttnHooks(const Q16Args& a_, int b_, int s_)
+        : a(a_), rPA(t2v_rsrc(a_.PA)), rPD(t2v_rsrc(a_.PD)), b(b_), s(s_), dc_early{0.f, 0.f, 0.f, 0.f} {}
+    __device__ __forceinline__ int dqt_items() const { return 16; }
+    __device__ __forceinline__ void dctx_early(int t, int tid, int* flag) {
+        dc_early = f32x4{0.f, 0.f, 0.f, 0.f};
         if (tid < 128) {
-            const float4 hc = *(const float4*)(a.dHC + ((size_t)t * B + b) * (T2V_H + T2V_E) + T2V_H + 4 * tid);
+            const float4 hc = *(const float4*)(a.dHC + ((size_t)t * a.B + b) * (T2V_H + T2V_E) + T2V_H + 4 * tid);
             f32x4 e[4];
             q16_poll_words<4>(e, rPD, (unsigned)(((t * 4) * 16 + b) * Q16_NCOLD + 2 * T2V_H + 4 * tid) * 4u, 16u * Q16_NCOLD * 4u, a.err, flag);
             dc_early = ((e[0] + e[1]) + (e[2] + e[3])) + f32x4{hc.x, hc.y, hc.z, hc.w};
         }
-        float dot_g = 0.f;
-        for (int j = tid; j < Tp; j += Q16_THREADS) {
-            float gp = 0.f, gc = gcum[j];
-            if (t < T - 1) {
-                const int lo = max(0, (j + 15 - PW + JS) / JS), hi = min(S - 1, (j + 15) / JS);
-                for (int sp2 = lo; sp2 <= hi; ++sp2) {
-                    const int jj = j - sp2 * JS + 15;
-                    if (jj < 0 || jj >= PW) continue;
-                    const unsigned off = (unsigned)((((t + 1) * B + b) * S + sp2) * (2 * GPW) + jj) * 4u;
-                    unsigned x0, x1;
-                    int spins = 0;
-                    for (;;) {          // published at the end of the previous reverse step: almost always there
-                        x0 = t2v_ld_b32(rP, off);
-                        x1 = t2v_ld_b32(rP, off + 4u * GPW);
-                        if (t2v_ok(x0) && t2v_ok(x1)) break;
-                        __builtin_amdgcn_s_sleep(1);
-                        if (t2v_give_up(spins, Q16_SPIN, a.err, flag)) break;
-                    }
-                    gp += __uint_as_float(x0);
-                    gc += __uint_as_float(x1);
-                }
-            }
-            gcum[j] = gc;
-            gfull0[j] = gp;
-            gfull1[j] = gc;
-            const float al = a.AL[((size_t)(t + 1) * B + b) * Tp + j];
-            alf[j] = al;
-            dot_g = fmaf(al, gp + gc, dot_g);
-        }
-        // ---- the context gradient of this item: the four partial rows of Wcat_att^T dga(t+1) (16 bytes x 4 per thread of waves
-        // 0 and 1), nap first — this hand-off is on the chain of every reverse step
+    }
+    __device__ __forceinline__ void dctx_arrive(int t, int tid, float* dctx, int& nap, int* flag) {
         if (tid < 128) {
             f32x4 dc = dc_early;
-            if (t < T - 1) {
+            if (t < a.T - 1) {
                 for (int i = 0; i < nap; i += 8) __builtin_amdgcn_s_sleep(8);
                 const unsigned off = (unsigned)((((t + 1) * 4) * 16 + b) * Q16_NCOLA + T2V_H + 4 * tid) * 4u;
                 f32x4 y[4];
@@ -487,147 +382,17 @@ __device__ __forceinline__ void q16_attention_role(const Q16Args& a, float* lds,
                 dc = dc + ((y[0] + y[1]) + (y[2] + y[3]));
             }
             *(f32x4*)(dctx + 4 * tid) = dc;
-            if (s == 0) *(f32x4*)(a.DCTX + ((size_t)t * B + b) * T2V_E + 4 * tid) = dc;      // saved copy for the d_memory product
+            if (s == 0) *(f32x4*)(a.DCTX + ((size_t)t * a.B + b) * T2V_E + 4 * tid) = dc;      // saved copy for the d_memory product
         }
-        __syncthreads();
-        if (flag[0] != 1) return;
-        Q16_RT(1);
-        // ---- dot = dctx·ctx_t + sum_j alpha_j (Gprev_j + Gcum_j); dalpha of the own positions = dctx·memory_j + G_j
-        {
-            float dotp = dot_g;
-            if (tid < 256) dotp += dctx[2 * tid] * ctx2.x + dctx[2 * tid + 1] * ctx2.y;
-            dotp = row16_sum(dotp);
-            // 32 row partials (8 waves x 4 rows): waves 4..7 carry only their share of dot_g
-            if (c16 == 0) rq[4 * wave + g] = dotp;
-            if (act) {
-                const float4 d0 = *(const float4*)(dctx + lane * 4), d1 = *(const float4*)(dctx + 256 + lane * 4);
-#pragma unroll
-                for (int r = 0; r < JS / NWV; ++r) {
-                    float acc = m0[r].x * d0.x;
-                    acc = fmaf(m0[r].y, d0.y, acc); acc = fmaf(m0[r].z, d0.z, acc); acc = fmaf(m0[r].w, d0.w, acc);
-                    acc = fmaf(m1[r].x, d1.x, acc); acc = fmaf(m1[r].y, d1.y, acc);
-                    acc = fmaf(m1[r].z, d1.z, acc); acc = fmaf(m1[r].w, d1.w, acc);
-                    acc = row16_sum(acc);
-                    if (c16 == 0) red[(1 + r) * 4 * NWV + 4 * wave + g] = acc;
-                }
-            }
-        }
-        __syncthreads();
-        if (tid < JS) {
-            float dsum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 32; ++u) dsum += rq[u];
-            const int wv = tid % NWV, r = tid / NWV;              // position tid = wv + NWV r
-            const float* rr = red + (1 + r) * 4 * NWV + 4 * wv;
-            const float dalv = ((rr[0] + rr[1]) + (rr[2] + rr[3])) + gfull0[j0 + min(tid, nown - 1)] + gfull1[j0 + min(tid, nown - 1)];
-            de[tid] = tid < nown ? alf[j0 + tid] * (dalv - dsum) : 0.f;
-        }
-        __syncthreads();
-        // ---- through v·tanh(.): dpre, partial dq / dv
-        if (act) {
-            float4 dq = make_float4(0.f, 0.f, 0.f, 0.f), dv = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int i = 0; i < JS / NRG; ++i) {
-                const int jl = rg + NRG * i;
-                const float dej = de[jl];
-                const float4 sv = sreg[i];
-                float4 dp;
-                dp.x = dej * vd4.x * (1.0f - sv.x * sv.x); dp.y = dej * vd4.y * (1.0f - sv.y * sv.y);
-                dp.z = dej * vd4.z * (1.0f - sv.z * sv.z); dp.w = dej * vd4.w * (1.0f - sv.w * sv.w);
-                sreg[i] = dp;           // the saved copy (operand of the d W_comb / d memory_layer products) leaves AFTER the hand-off
-                dq.x += dp.x; dq.y += dp.y; dq.z += dp.z; dq.w += dp.w;
-                dv.x = fmaf(dej, sv.x, dv.x); dv.y = fmaf(dej, sv.y, dv.y); dv.z = fmaf(dej, sv.z, dv.z); dv.w = fmaf(dej, sv.w, dv.w);
-                dpT[(4 * d4 + 0) * DPS + jl] = dp.x; dpT[(4 * d4 + 1) * DPS + jl] = dp.y;
-                dpT[(4 * d4 + 2) * DPS + jl] = dp.z; dpT[(4 * d4 + 3) * DPS + jl] = dp.w;
-            }
-            *(float4*)&rq[rg * T2V_A + 4 * d4] = dq;
-            *(float4*)&rv[rg * T2V_A + 4 * d4] = dv;
-        }
-        __syncthreads();
-        if (tid < T2V_A) {
-            const float* p = rq + tid;
-            float q = ((p[0] + p[T2V_A]) + (p[2 * T2V_A] + p[3 * T2V_A])) + ((p[4 * T2V_A] + p[5 * T2V_A]) + (p[6 * T2V_A] + p[7 * T2V_A]));
-            const float* p2 = rv + tid;
-            float vv = ((p2[0] + p2[T2V_A]) + (p2[2 * T2V_A] + p2[3 * T2V_A])) + ((p2[4 * T2V_A] + p2[5 * T2V_A]) + (p2[6 * T2V_A] + p2[7 * T2V_A]));
-            if (NRG > 8) {
-                p += 8 * T2V_A; p2 += 8 * T2V_A;
-                q += ((p[0] + p[T2V_A]) + (p[2 * T2V_A] + p[3 * T2V_A])) + ((p[4 * T2V_A] + p[5 * T2V_A]) + (p[6 * T2V_A] + p[7 * T2V_A]));
-                vv += ((p2[0] + p2[T2V_A]) + (p2[2 * T2V_A] + p2[3 * T2V_A])) + ((p2[4 * T2V_A] + p2[5 * T2V_A]) + (p2[6 * T2V_A] + p2[7 * T2V_A]));
-            }
-            t2v_st(rQ, (unsigned)(((t * B + b) * S + s) * T2V_A + tid) * 4u, q);       // partial row (the d W_q GEMM reads them later)
-            dvacc += vv;
-            if (s == 0) {
-                // slice 0 of an item sums the S partial rows in slice order and publishes ONE row per item (all partial rows are
-                // requested in ONE round: a round trip per slice would cost 0.45 us each)
-                constexpr int SMAX = Q16_MAXT / 16;             // 14 slices at most
-                const unsigned off0 = (unsigned)(((t * B + b) * S) * T2V_A + tid) * 4u;
-                unsigned x[SMAX];
-                int spins = 0;
-                for (;;) {
-                    bool ok = true;
-#pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) x[s2] = t2v_ld_b32(rQ, off0 + (unsigned)(min(s2, S - 1) * T2V_A) * 4u);
-#pragma unroll
-                    for (int s2 = 1; s2 < SMAX; ++s2) ok = ok && (s2 >= S || t2v_ok(x[s2]));
-                    if (__all(ok)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (t2v_give_up(spins, Q16_SPIN, a.err, flag)) break;
-                }
-                float tot = q;
-#pragma unroll
-                for (int s2 = 1; s2 < SMAX; ++s2) tot += s2 < S ? __uint_as_float(x[s2]) : 0.f;
-                t2v_st(rQT, (unsigned)((t * 16 + b) * T2V_A + tid) * 4u, tot);          // the attention_rnn cell workgroups wait for this
-            }
-        }
-        Q16_RT(2);
-        if (act) {      // dpre rows: 8 KB of stores that must not sit in this CU's memory pipe in front of the dq words above
-            float* sp = a.S + (((size_t)t * B + b) * Tp + j0) * T2V_A + 4 * d4;
-#pragma unroll
-            for (int i = 0; i < JS / NRG; ++i) {
-                const int jl = rg + NRG * i;
-                if (jl < nown) *(float4*)(sp + (size_t)jl * T2V_A) = sreg[i];
-            }
-        }
-        // ---- through the fused location filter on MFMA: T[(c,k)][jl] = sum_d W_comb[d][(c,k)] dpre[jl][d], K = 128
-        if (act) {
-#pragma unroll
-            for (int jt = (NWV == 8 ? (wave >> 2) : 0); jt < NJT; jt += NWV / 4) {     // (8 waves: waves 4..7 take the odd position tiles)
-                f32x4 ac4[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ac4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int st = 0; st < 32; ++st) {
-                    const float av = AREG_LDS ? wcs[(16 * (wave & 3) + c16) * 132 + 33 * g + st] : areg[AREG_LDS ? 0 : st];
-                    ac4[st & 3] = mfma16x4(av, dpT[(4 * st + g) * DPS + 16 * jt + c16], ac4[st & 3]);
-                }
-                const f32x4 acc = (ac4[0] + ac4[1]) + (ac4[2] + ac4[3]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Tl[(16 * (wave & 3) + 4 * g + r) * (JS + 1) + 16 * jt + c16] = acc[r];
-            }
-        }
-        __syncthreads();
-        // ---- gradient wrt the alignment window of this slice -> the slices of step t-1 (their window partials)
-        if (tid < 2 * GPW && t > 0) {
-            const int c = tid / GPW, jj = tid % GPW;
-            if (jj < PW) {
-                float tt[T2V_KS];
-#pragma unroll
-                for (int k = 0; k < T2V_KS; ++k) {
-                    const int jl = jj - k;
-                    const float tv = Tl[(32 * c + k) * (JS + 1) + min(max(jl, 0), JS - 1)];
-                    tt[k] = (jl >= 0 && jl < JS) ? tv : 0.f;
-                }
-                float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-#pragma unroll
-                for (int k = 0; k + 3 < T2V_KS; k += 4) { acc0 += tt[k]; acc1 += tt[k + 1]; acc2 += tt[k + 2]; acc3 += tt[k + 3]; }
-                acc0 += tt[28]; acc1 += tt[29]; acc2 += tt[30];
-                t2v_st(rP, (unsigned)(((t * B + b) * S + s) * (2 * GPW) + c * GPW + jj) * 4u, (acc0 + acc1) + (acc2 + acc3));
-            }
-        }
-        __syncthreads();
-        Q16_RT(3);
     }
-    if (tid < T2V_A) a.DV[((size_t)b * S + s) * T2V_A + tid] = dvacc;
+    __device__ __forceinline__ void prof_init(int*) {}
+    __device__ __forceinline__ void pass_begin() {}
+    __device__ __forceinline__ void stamp(int t, int point) { Q16_RT(point); }
+    __device__ __forceinline__ void pass_end() {}
+};
+template <int JS, int NWV>
+__device__ __forceinline__ void q16_attention(const Q16Args& a, float* lds, const int b, const int s) {
+    t2v_attn_role_bwd<JS, NWV, Q16AttnHooks>(a, lds, b, s);
 }
 
 template <bool LONG>          // the attention role on 96-position slices (T_in > Q16_T32); the other roles are the same
@@ -637,9 +402,9 @@ __global__ __launch_bounds__(Q16_THREADS) void k_bwd_persist16(Q16Args a) {
     const int S = a.S_sl, NT = a.B * S;
 #if defined(Q16_ONLY_T)
     if (wg < NT) {
-        if (LONG) q16_attention_role<96, 8>(a, lds, wg / S, wg % S);
-        else if (a.T_in <= 96) q16_attention_role<16>(a, lds, wg / S, wg % S);
-        else q16_attention_role<32>(a, lds, wg / S, wg % S);
+        if (LONG) q16_attention<96, 8>(a, lds, wg / S, wg % S);
+        else if (a.T_in <= 96) q16_attention<16, 4>(a, lds, wg / S, wg % S);
+        else q16_attention<32, 4>(a, lds, wg / S, wg % S);
     }
 #elif defined(Q16_ONLY_G)
     if (wg < 48) q16_gemv_role<false>(a, lds, wg); else q16_gemv_role<true>(a, lds, wg - 48);
@@ -648,9 +413,9 @@ __global__ __launch_bounds__(Q16_THREADS) void k_bwd_persist16(Q16Args a) {
 #else
     if (wg < Q16_MAXTWG) {
         if (wg >= NT) return;
-        if (LONG) q16_attention_role<96, 8>(a, lds, wg / S, wg % S);
-        else if (a.T_in <= 96) q16_attention_role<16>(a, lds, wg / S, wg % S);
-        else q16_attention_role<32>(a, lds, wg / S, wg % S);
+        if (LONG) q16_attention<96, 8>(a, lds, wg / S, wg % S);
+        else if (a.T_in <= 96) q16_attention<16, 4>(a, lds, wg / S, wg % S);
+        else q16_attention<32, 4>(a, lds, wg / S, wg % S);
         return;
     }
     const int j = wg - Q16_MAXTWG;
@@ -670,9 +435,7 @@ extern "C" int t2v_decoder_bwd_persist16_slices(int T_in) { return T_in < 1 ? 0 
 static size_t q16_lds_bytes(int T_in) {
     const size_t grole = 2 * 8 * 8 * 64 * 4 + 4;
     const size_t crole = 128 * 16 + 2 * 64 * 16 + 4;
-    const size_t Tcap = (size_t)((T_in + 15) / 16) * 16, JS = (size_t)q16_js(T_in), NWV = JS == 96 ? 8 : 4;
-    const size_t trole = 4 * Tcap + T2V_E + JS + (1 + JS / NWV) * 4 * NWV + T2V_A * (JS == 96 ? JS + 17 : JS + 1) + 64 * (JS + 1) +
-                         2 * 2 * NWV * T2V_A + 40 + (NWV == 8 ? 64 * 132 : 0);
+    const size_t trole = t2v_attn_bwd_lds_floats(T_in, q16_js(T_in));
     size_t m = grole > crole ? grole : crole;
     m = m > trole ? m : trole;
     return sizeof(float) * m;
