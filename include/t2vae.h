@@ -712,6 +712,32 @@ size_t t2v_mel_dtw_scratch_bytes(int B, int tx_max, int ty_max);
 int t2v_mel_dtw(const float* X, const int32_t* nx, int x_stride, const float* Y, const int32_t* ny, int y_stride,
                 int B, int n_mel, float* dist, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------ exact t-SNE of the latents to 2 dimensions
+ * The map of the reference README's "Visualization" section (csrc/tsne.hip): X (N, D) fp32 -> Y (N, 2), all pairs, no
+ * approximation.  4 <= N <= T2V_TSNE_MAX_POINTS and 2 <= D <= 64, else T2V_ERR_DIMS; a null pointer, a perplexity outside
+ * (0, N/3), n_iter < 1 or a non-positive exaggeration / learning rate is T2V_ERR_ARG.  Nothing past row N of any array is
+ * read.  No floating-point atomics: the order of every sum depends on N alone, so equal inputs give equal bits.
+ * scratch: t2v_tsne_scratch_bytes(N, D) bytes serve all three calls (0 for sizes that are refused).
+ * t2v_tsne_affinities: P (N, N) dense fp32, P_ij = (p_j|i + p_i|j) / (2N) with p_j|i the Gaussian conditional whose precision
+ *   a 100-step binary search fits to `perplexity` (entropy tolerance 1e-5, p_i|i = 0).  P is symmetric to the bit, and
+ *   t2v_tsne_gradient / t2v_tsne_run rely on that: they read P_ij as P[j][i].
+ * t2v_tsne_gradient: one pass over all pairs at the map Y: grad (N, 2) = 4 [ex sum_j P_ij w_ij (y_i - y_j) -
+ *   (1/Z) sum_j w_ij^2 (y_i - y_j)], w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{k != l} w_kl; *kl_or_null, when given, receives
+ *   sum_{i != j} P' log(max(P', 2^-52) / Q) with P' = ex P, Q = w / Z (zero entries of P add nothing).
+ * t2v_tsne_run: n_iter iterations from Y_inout on `stream`, no host synchronisation: T2V_TSNE_EXAG_ITERS iterations at
+ *   exaggeration 12 and momentum 0.5, then exaggeration 1 and momentum 0.8; per coordinate gains += 0.2 where update and
+ *   gradient differ in sign, *= 0.8 elsewhere, floor 0.01; update = momentum * update - learning_rate * gains * grad.
+ *   kl_trace: ceil(n_iter / 50) floats; slot k is the objective (with the exaggeration of that iteration) at the map after
+ *   min(50 (k + 1), n_iter) updates. */
+#define T2V_TSNE_MAX_POINTS 16384   /* dense fp32 P: 1 GiB */
+#define T2V_TSNE_EXAG_ITERS 250
+size_t t2v_tsne_scratch_bytes(int N, int D);
+int t2v_tsne_affinities(const float* X, int N, int D, float perplexity, float* P, void* scratch, void* stream);
+int t2v_tsne_gradient(const float* P, const float* Y, int N, float exaggeration, float* grad, float* kl_or_null,
+                      void* scratch, void* stream);
+int t2v_tsne_run(const float* P, float* Y_inout, int N, int n_iter, float learning_rate, float* kl_trace, void* scratch,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

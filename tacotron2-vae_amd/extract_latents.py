@@ -1,11 +1,13 @@
-"""Latent export: prosody, mu, logvar and z of every utterance of a filelist, for the scatter / t-SNE plots of the
-reference README's "Visualization" section.
+"""Latent export: prosody, mu, logvar and z of every utterance of a filelist, for the plots of the reference README's
+"Visualization" section: the scatter of two latent dimensions is the reader's to draw from OUT.npz, the t-SNE map is
+latent_map.py's (or --tsne here).
 
-    python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...]
+    python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...] [--tsne [KEY]]
 
 Filelist rows are `path|text|speaker|emotion`.  OUT.npz holds, row i for filelist row i: prosody (N, E), mus, logvars,
 zs (N, z_latent_dim), emotions (N,) int and paths (N,) str.  The wavs run through `Synthesizer.latents`: sorted by
-length, in ragged batches of at most --batch_size, each row what model.vae_gst(load_mel(path)) gives for the wav alone.
+length, in ragged batches of at most --batch_size, each row what model.vae_gst(load_mel(path)) gives for the wav alone.  --tsne [mus|zs|prosody] adds tsne (N, 2), the
+map of that array by latent_map.compute_map with its defaults, and tsne_kl; without it the file is what it always was.
 """
 import argparse
 
@@ -21,6 +23,8 @@ def build_arg_parser():
     p.add_argument('--out', required=True, help="output .npz")
     p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="wavs per ragged vae_gst call")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
+    p.add_argument('--tsne', nargs='?', const='mus', default=None, choices=('mus', 'zs', 'prosody'),
+                   help="also store the t-SNE map of this array (default mus) as tsne, tsne_kl")
     return p
 
 
@@ -56,7 +60,13 @@ def main(argv=None):
     syn = Synthesizer(hp).load_checkpoint(args.load_path)
     paths, emotions = read_filelist(args.filelist_path)
     prosody, mu, logvar, z = (t.cpu().numpy() for t in syn.latents(paths, args.batch_size))
-    np.savez(args.out, prosody=prosody, mus=mu, logvars=logvar, zs=z, emotions=emotions, paths=np.array(paths))
+    out = dict(prosody=prosody, mus=mu, logvars=logvar, zs=z, emotions=emotions, paths=np.array(paths))
+    if args.tsne:
+        import latent_map
+        latent_map.check_perplexity(latent_map.DEFAULT_PERPLEXITY, len(paths))
+        points, trace = latent_map.compute_map(out[args.tsne])
+        out.update(tsne=points, tsne_kl=trace[-1])
+    np.savez(args.out, **out)
     print("%s: %d utterances" % (args.out, len(paths)))
 
 

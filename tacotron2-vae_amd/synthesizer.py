@@ -123,6 +123,15 @@ class Synthesizer(object):
         inv = inv.to(parts[0][0].device)
         return tuple(torch.cat([p[k] for p in parts], 0)[inv] for k in range(4))
 
+    def latent_map(self, paths, key='mus', batch_size=64, **tsne_kwargs):
+        """(N, 2) exact t-SNE map of the wavs' latents: `latents(paths)` followed by `t2v_hip.tsne` on prosody, mus, logvars
+        or zs (key); tsne_kwargs (perplexity, n_iter, seed, init, return_trace) go to `t2v_hip.tsne` as they are."""
+        import t2v_hip
+        keys = ('prosody', 'mus', 'logvars', 'zs')
+        if key not in keys:
+            raise ValueError("key must be one of %s, got %r" % (', '.join(keys), key))
+        return t2v_hip.tsne(self.latents(paths, batch_size)[keys.index(key)].float().contiguous(), **tsne_kwargs)
+
     # ------------------------------------------------------------------ checkpoint + centroids (synthesizer.py:74-110)
     @staticmethod
     def centroid_cache_path(checkpoint_path, filelist_path):

@@ -101,7 +101,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_stft_polar', 't2v_istft', 't2v_istft_scratch_bytes', 't2v_griffin_lim', 't2v_griffin_lim_scratch_bytes',
            't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
            't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
-           't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes')
+           't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
+           't2v_tsne_gradient', 't2v_tsne_run')
 
 
 def lib_path():
@@ -230,6 +231,11 @@ def load_library():
     lib.t2v_mel_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_mel_dtw_scratch_bytes.restype = C.c_size_t
     lib.t2v_mel_dtw.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.t2v_tsne_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    lib.t2v_tsne_scratch_bytes.restype = C.c_size_t
+    lib.t2v_tsne_affinities.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
+    lib.t2v_tsne_gradient.argtypes = [vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
+    lib.t2v_tsne_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
     lib.t2v_conv1d_stat_blocks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_stat_blocks_bf16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -1577,6 +1583,102 @@ def mel_dtw(x, nx, y, ny):
         _check(lib.t2v_mel_dtw(_p(x[b0:]), _p(nx[b0:]), sx, _p(y[b0:]), _p(ny[b0:]), sy, nb, n_mel, _p(dist[b0:]), _p(scratch),
                                _stream()), 't2v_mel_dtw')
     return dist
+
+
+TSNE_MAX_POINTS = 16384                 # T2V_TSNE_MAX_POINTS of include/t2vae.h: P is dense fp32, 1 GiB there
+TSNE_MAX_DIM = 64
+TSNE_EXAG_ITERS = 250                   # T2V_TSNE_EXAG_ITERS
+TSNE_KL_EVERY = 50
+
+
+def _tsne_check(what, N, D=None, perplexity=None):
+    if N < 4 or N > TSNE_MAX_POINTS:
+        raise ValueError("%s: %d points; 4..%d are supported (P is a dense N x N fp32 matrix)" % (what, N, TSNE_MAX_POINTS))
+    if D is not None and (D < 2 or D > TSNE_MAX_DIM):
+        raise ValueError("%s: %d input dimensions; 2..%d are supported" % (what, D, TSNE_MAX_DIM))
+    if perplexity is not None and not (0.0 < perplexity and 3.0 * perplexity < N):
+        raise ValueError("%s: perplexity %g with %d points; it must lie in (0, N/3) = (0, %g)" % (what, perplexity, N, N / 3.0))
+
+
+def _tsne_scratch(lib, N, D, device):
+    return torch.empty(lib.t2v_tsne_scratch_bytes(N, D), device=device, dtype=torch.uint8)
+
+
+def tsne_learning_rate(N):
+    """scikit-learn's learning_rate='auto': max(N / early_exaggeration / 4, 50)"""
+    return max(N / 12.0 / 4.0, 50.0)
+
+
+def tsne_affinities(x, perplexity=30.0):
+    """The joint probabilities of exact t-SNE (csrc/tsne.hip k_tsne_cond, k_tsne_sym): x (N, D) float32 CUDA tensor ->
+    dense (N, N) float32 P, P_ij = (p_j|i + p_i|j) / (2N), each row's Gaussian fitted to `perplexity` by a 100-step binary
+    search (entropy tolerance 1e-5).  P is symmetric to the bit and its diagonal is 0.  Only x[:N] is read."""
+    lib = _require_gpu(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("tsne_affinities: x must be a float32 (N, D) tensor")
+    N, D = x.shape
+    perplexity = float(perplexity)
+    _tsne_check("tsne_affinities", N, D, perplexity)
+    x = _f32c(x)
+    P = torch.empty(N, N, device=x.device, dtype=torch.float32)
+    _check(lib.t2v_tsne_affinities(_p(x), N, D, perplexity, _p(P), None, _stream()), 't2v_tsne_affinities')
+    return P
+
+
+def tsne_gradient(P, Y, exaggeration=1.0):
+    """One all-pairs pass at the map Y (N, 2) with the symmetric P (N, N) of tsne_affinities (k_tsne_pairs, k_tsne_finish):
+    returns (grad (N, 2), kl ()), the gradient of the KL divergence of exaggeration * P from the Student-t Q of Y, and that
+    divergence."""
+    lib = _require_gpu(P, Y)
+    if P.dim() != 2 or P.size(0) != P.size(1) or P.dtype != torch.float32:
+        raise ValueError("tsne_gradient: P must be a float32 (N, N) tensor, got %s" % (tuple(P.shape),))
+    N = P.size(0)
+    if tuple(Y.shape) != (N, 2) or Y.dtype != torch.float32:
+        raise ValueError("tsne_gradient: Y must be a float32 (%d, 2) tensor, got %s" % (N, tuple(Y.shape)))
+    _tsne_check("tsne_gradient", N)
+    if not float(exaggeration) > 0.0:
+        raise ValueError("tsne_gradient: exaggeration %g must be positive" % exaggeration)
+    P, Y = _f32c(P), _f32c(Y)
+    grad = torch.empty(N, 2, device=P.device, dtype=torch.float32)
+    kl = torch.empty((), device=P.device, dtype=torch.float32)
+    scratch = _tsne_scratch(lib, N, 2, P.device)
+    _check(lib.t2v_tsne_gradient(_p(P), _p(Y), N, float(exaggeration), _p(grad), _p(kl), _p(scratch), _stream()),
+           't2v_tsne_gradient')
+    return grad, kl
+
+
+def tsne_init(N, seed=0):
+    """scikit-learn's init='random': 1e-4 * standard_normal((N, 2)) of a numpy RandomState(seed), as float32"""
+    import numpy as np
+    return torch.from_numpy((1e-4 * np.random.RandomState(seed).standard_normal(size=(N, 2))).astype(np.float32))
+
+
+def tsne(x, perplexity=30.0, n_iter=1000, seed=0, init=None, return_trace=False):
+    """Exact t-SNE of x (N, D) float32 CUDA tensor to a (N, 2) float32 map on x's device (csrc/tsne.hip): affinities once,
+    then n_iter iterations of scikit-learn's gradient descent (250 at exaggeration 12 and momentum 0.5, then 1 and 0.8;
+    learning rate max(N / 48, 50); gains) queued on the current stream; no early stop, no host synchronisation.
+    init: a (N, 2) start, else tsne_init(N, seed).  return_trace: also the KL divergence after 50, 100, ..., n_iter
+    iterations (a float32 device tensor; its last entry is the final map's).  Equal inputs give equal bits."""
+    lib = _require_gpu(x)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("tsne: x must be a float32 (N, D) tensor")
+    N, D = x.shape
+    perplexity, n_iter = float(perplexity), int(n_iter)
+    _tsne_check("tsne", N, D, perplexity)
+    if n_iter < 1:
+        raise ValueError("tsne: n_iter %d must be >= 1" % n_iter)
+    if init is None:
+        Y = tsne_init(N, seed).to(x.device)
+    else:
+        init = torch.as_tensor(init)
+        if tuple(init.shape) != (N, 2):
+            raise ValueError("tsne: init must be (%d, 2), got %s" % (N, tuple(init.shape)))
+        Y = init.to(device=x.device, dtype=torch.float32).contiguous().clone()
+    P = tsne_affinities(x, perplexity)
+    trace = torch.empty((n_iter + TSNE_KL_EVERY - 1) // TSNE_KL_EVERY, device=x.device, dtype=torch.float32)
+    scratch = _tsne_scratch(lib, N, D, x.device)
+    _check(lib.t2v_tsne_run(_p(P), _p(Y), N, n_iter, tsne_learning_rate(N), _p(trace), _p(scratch), _stream()), 't2v_tsne_run')
+    return (Y, trace) if return_trace else Y
 
 
 class InferenceSession(object):
