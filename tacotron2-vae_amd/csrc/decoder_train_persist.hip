@@ -7,7 +7,8 @@
 // Roles (one workgroup per CU, all co-resident):
 //   T  : workgroups [0, 8B)   — location-sensitive attention of item b = wg / 8, attention dims [16s, 16s + 16) and context
 //        columns [64s, 64s + 64), s = wg % 8.  W_q slice, memory / processed-memory slices and the alignment window stay
-//        in LDS for all steps (as in decoder_persist.hip).
+//        in LDS for all steps (as in decoder_persist.hip).  The role's body is t2v_attn_role_fwd.inc, included below and
+//        shared with k_dec_train_persist16; this file has what is its own: how h_att(t) arrives and how the context leaves.
 //   L  : workgroups [8B, 256) — LSTM rows of BOTH cells: workgroup j owns hidden units [j*1024/NL, (j+1)*1024/NL) (4 or 5
 //        units = 16 or 20 gate rows per cell), weights in VGPRs (thread = (gate, 1/128 of K): 60 + 100 registers).
 // Teacher forcing takes decoder_rnn off the critical path: attention_rnn(t+1) needs only h_att(t) and ctx(t) (the Prenet
@@ -26,13 +27,8 @@
 #include "t2v_kernels.h"
 #include "t2v_xchg.h"
 
-#define PT_THREADS 512
-#define PT_MAXB 6
-#define PT_MAXT 224                  // LDS-resident W_q / processed-memory slices up to here
-#define PT_MAXT_LONG 560             // register-resident ones beyond (k_dec_train_persist<.., true>)
-#define PT_NTI_LONG 5                // 16-position tiles per wave of the long form: 8 waves x 5 x 16 = 640 >= 560
+#define PT_MAXB 6                    // (thread count, spin limit and the T_in bounds: T2V_AF_*, t2v_kernels.h)
 #define PT_MAXU 5
-#define PT_SPIN 1500000u
 #define PT_JA (T2V_KATT / 128)       // 12 k per thread, attention_rnn  [h_att | ctx]
 #define PT_JD (T2V_XW / 128)         // 20 k per thread, decoder_rnn    [h_att | ctx | h_dec]
 
@@ -65,7 +61,7 @@ __device__ __forceinline__ int pt_gather(f32x4* X, __amdgpu_buffer_rsrc_t rG, un
     int dsti[PER], nw[PER];
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
-        int c = tid + PT_THREADS * u;
+        int c = tid + T2V_AF_THREADS * u;
         const bool on = c < NP * nk;
         c = on ? c : 0;
         const int pl = c / nk;
@@ -89,7 +85,7 @@ __device__ __forceinline__ int pt_gather(f32x4* X, __amdgpu_buffer_rsrc_t rG, un
         for (int u = 0; u < PER; ++u) ok = ok && t2v_ok_n(v[u], nw[u]);
         if (__all(ok)) break;
         __builtin_amdgcn_s_sleep(2);
-        if (t2v_give_up(rounds, (int)(PT_SPIN / 4), err, flag)) break;
+        if (t2v_give_up(rounds, (int)(T2V_AF_SPIN / 4), err, flag)) break;
     }
 #pragma unroll
     for (int u = 0; u < PER; ++u)
@@ -113,7 +109,7 @@ __device__ __forceinline__ int pt_wait_words(__amdgpu_buffer_rsrc_t r, unsigned 
         if (tid < npoll) ok = t2v_ok(t2v_ld_b32(r, off));
         if (__syncthreads_and(ok)) break;
         ++rounds;
-        if (tid == 0) t2v_give_up(spins, PT_SPIN / 8, err, flag);
+        if (tid == 0) t2v_give_up(spins, T2V_AF_SPIN / 8, err, flag);
         __syncthreads();
         if (*flag != 1) break;
     }
@@ -285,7 +281,7 @@ __device__ __forceinline__ void pt_reduce_store(const PTAcc<NB>& acc, float* red
 // attention workgroup holds no LSTM weights), which leaves the 160 KB to the memory slice (560 x 64 floats = 140 KB); five
 // position tiles per wave instead of two, two positions per thread in the softmax.
 template <int NB, bool LONG>
-__global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
+__global__ __launch_bounds__(T2V_AF_THREADS) void k_dec_train_persist(PTArgs a) {
     constexpr int NP = NB > 4 ? 2 : 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint64_t seed = t2v_step_seed(a.seed, a.step);
@@ -324,7 +320,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                 wd[u][jj / 2][jj & 1] = on ? w : 0.f;
             }
         }
-        for (int i = tid; i < NP * T2V_XW; i += PT_THREADS) X[i] = f32x4{0.f, 0.f, 0.f, 0.f};      // row 0: zero initial states
+        for (int i = tid; i < NP * T2V_XW; i += T2V_AF_THREADS) X[i] = f32x4{0.f, 0.f, 0.f, 0.f};      // row 0: zero initial states
         if (tid == 0) flag[0] = 1;
         // cell threads: tid = u * NB + b (wave 0); each keeps its two cell states in registers for the whole pass
         const int cu = tid / NB, cb = tid - cu * NB;
@@ -458,9 +454,9 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
             {
                 // (both segments in ONE pass — 8 loads of 16 bytes in flight per thread — measured slower: the 32 extra
                 // registers spill next to the 160 weight registers and the cell phases pay for it: 9.2 vs 8.7 us per step)
-                pt_gather<(NP * T2V_H + PT_THREADS - 1) / PT_THREADS, NP>(X, rG, grow, 0, T2V_H, B, 0, a.err, flag);
+                pt_gather<(NP * T2V_H + T2V_AF_THREADS - 1) / T2V_AF_THREADS, NP>(X, rG, grow, 0, T2V_H, B, 0, a.err, flag);
                 PT_STAMP(wg == NT && t == T / 2, 3);
-                pt_gather<(NP * T2V_H + PT_THREADS - 1) / PT_THREADS, NP>(X, rG, grow, T2V_KATT, T2V_H, B, 0, a.err, flag);
+                pt_gather<(NP * T2V_H + T2V_AF_THREADS - 1) / T2V_AF_THREADS, NP>(X, rG, grow, T2V_KATT, T2V_H, B, 0, a.err, flag);
                 PT_STAMP(wg == NT && t == T / 2, 4);
                 __syncthreads();
                 if (flag[0] != 1) return;
@@ -473,7 +469,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
                     fdrop[32 + tid] = t2v_drop_scale(seed, T2V_RNG_ATT_H, t + 1, idx, a.p_att);
                 }
                 PT_STAMP(wg == NT && t == T / 2, 6);
-                const int rounds = pt_gather<(NP * T2V_E + PT_THREADS - 1) / PT_THREADS, NP>(X, rG, grow, T2V_H, T2V_E, B, ctx_nap, a.err, flag);
+                const int rounds = pt_gather<(NP * T2V_E + T2V_AF_THREADS - 1) / T2V_AF_THREADS, NP>(X, rG, grow, T2V_H, T2V_E, B, ctx_nap, a.err, flag);
                 // adaptive nap: wake up just before the context lands (a poll round is about 16 nap units long)
                 ctx_nap = t2v_adapt_nap(ctx_nap, rounds);
                 PT_WALL(wg == NT && t == T / 2, 23);
@@ -487,347 +483,71 @@ __global__ __launch_bounds__(PT_THREADS) void k_dec_train_persist(PTArgs a) {
     }
 
     // =============================================================================== T role: attention slice (b, s)
-    const int ab = wg >> 3, as = wg & 7;
-    constexpr int NTI = LONG ? PT_NTI_LONG : 2;          // position tiles per wave: tile jt = wave + 8 i
-    constexpr int NPP = LONG ? 2 : 1;                    // positions per thread in the softmax: tid + 512 u
-    const int TW = Tcap + 32;
-    float* wq_s = lds;                                   // [16][1028]   (LONG: in registers)
-    float* mem_s = wq_s + (LONG ? 0 : 16 * 1028);        // [Tcap][64]
-    float* pm_s = mem_s + Tcap * 64;                     // [Tcap][16]   (LONG: in registers)
-    float* win = pm_s + (LONG ? 0 : Tcap * 16);          // [2][TW]: alignment window, index x <-> position x - 15
-    float* eall = win + 2 * TW;                          // [Tcap] (LONG: + T2V_CTX_PAD, zero from Tp on: t2v_ctx_partial)
-    float* hx = eall + Tcap + (LONG ? T2V_CTX_PAD : 0);  // [1024] h_att(t) of this item
-    float* qv = hx + T2V_H;                              // [16]
-    float* qred = qv + 16;                               // [32][16]
-    float* cred = qred + 32 * 16;                        // [8][64]
-    float* rsm = cred + 8 * 64;                          // [32]
-    float* rss = rsm + 32;                               // [32]
-    int* flag = (int*)(rss + 32);
-    const int g = lane >> 4, c16 = lane & 15;
-    float4 wqr[LONG ? 8 : 1], pmr[LONG ? NTI : 1];
-    if constexpr (LONG) {
-        // the operands of a thread's own part of the query product (dim tid >> 5, k = 4 (tid & 31) + 128 i) and of its tiles'
-        // energies (position 16 jt + c16, dims 16 as + 4 g ..) never change over the pass
-        const float* wrow = a.wq + (size_t)(16 * as + (tid >> 5)) * 1024 + 4 * (tid & 31);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wqr[i] = *(const float4*)(wrow + 128 * i);
-#pragma unroll
-        for (int i = 0; i < NTI; ++i) {
-            const int jp = 16 * (wave + 8 * i) + c16;
-            pmr[i] = *(const float4*)(a.pm + ((size_t)ab * Tp + min(jp, Tp - 1)) * T2V_A + 16 * as + 4 * g);
+    // t2v_attn_role_fwd.inc, shared with k_dec_train_persist16; what is this kernel's own: item ab is word myw of plane mypl of
+    // a G row, h_att(t) arrives as 1024 of those words (two per thread), a context column leaves as one.
+#define AF_TAIL 0
+#define AF_SETUP const int mypl = ab >> 2, myw = ab & 3;
+#define AF_GROW grow_b
+#define AF_STAMP_STEP PT_STAMP(wg == 0 && t == T / 2, 8)
+#define AF_STAMP_H PT_STAMP(wg == 0 && t == T / 2, 9)
+#define AF_STAMP_Q PT_STAMP(wg == 0 && t == T / 2, 13)
+#define AF_STAMP_E PT_STAMP(wg == 0 && t == T / 2, 10)
+#define AF_STAMP_EX PT_STAMP(wg == 0 && t == T / 2, 14)
+#define AF_STAMP_ALPHA PT_STAMP(wg == 0 && t == T / 2, 11)
+#define AF_STAMP_END PT_WALL(wg == 0 && t == T / 2, 22); PT_STAMP(wg == 0 && t == T / 2, 12)
+#define AF_H_INGEST {                                                                                                           \
+            const unsigned s0 = grow + (unsigned)(mypl * T2V_XW + tid) * 16u + 4u * (unsigned)myw;                              \
+            float v0, v1;                                                                                                       \
+            for (int i = 0; i < h_nap; i += 8) __builtin_amdgcn_s_sleep(8);                                                     \
+            int rounds = 0;                                                                                                     \
+            for (;;) {                                                                                                          \
+                v0 = __uint_as_float(t2v_ld_b32(rG, s0));                                                                       \
+                v1 = __uint_as_float(t2v_ld_b32(rG, s0 + T2V_AF_THREADS * 16u));                                                \
+                if (__all(t2v_ok(v0) && t2v_ok(v1))) break;                                                                     \
+                __builtin_amdgcn_s_sleep(1);                                                                                    \
+                if (t2v_give_up(rounds, (int)(T2V_AF_SPIN / 4), a.err, flag)) break;                                            \
+            }                                                                                                                   \
+            h_nap = t2v_adapt_nap(h_nap, rounds);                                                                               \
+            PT_WALL(wg == 0 && t == T / 2, 21);                                                                                 \
+            if (a.prof && wg == 0 && t == T / 2 && tid == 0) { a.prof[26] = (unsigned long long)rounds; a.prof[27] = (unsigned long long)h_nap; } \
+            hx[tid] = v0;                                                                                                       \
+            hx[tid + T2V_AF_THREADS] = v1;                                                                                      \
         }
-    } else {
-        for (int i = tid; i < 16 * 1024; i += PT_THREADS) wq_s[(i >> 10) * 1028 + (i & 1023)] = a.wq[(size_t)(16 * as) * 1024 + i];
-    }
-    for (int i = tid; i < Tp * 64; i += PT_THREADS) mem_s[i] = a.memory[((size_t)ab * Tp + (i >> 6)) * T2V_E + 64 * as + (i & 63)];
-    if constexpr (!LONG)
-        for (int i = tid; i < Tp * 16; i += PT_THREADS) pm_s[i] = a.pm[((size_t)ab * Tp + (i >> 4)) * T2V_A + 16 * as + (i & 15)];
-    for (int i = tid; i < 2 * TW; i += PT_THREADS) win[i] = 0.f;
-    if constexpr (LONG)
-        for (int i = Tp + tid; i < Tcap + T2V_CTX_PAD; i += PT_THREADS) eall[i] = 0.f;
-    if (tid == 0) flag[0] = 1;
-    float areg[16];
-    {
-        const float4* wp = (const float4*)(a.wcomb + (16 * as + c16) * 64 + 16 * g);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float4 w4 = wp[u];
-            areg[4 * u] = w4.x; areg[4 * u + 1] = w4.y; areg[4 * u + 2] = w4.z; areg[4 * u + 3] = w4.w;
-        }
-    }
-    const float4 vr = *(const float4*)(a.v + 16 * as + 4 * g);
-    const int len = a.lengths ? a.lengths[ab] : Tp;
-    const int mypl = ab >> 2, myw = ab & 3;
-    __syncthreads();
-    int h_nap = 0;
-
-    for (int t = 0; t < T; ++t) {
-        const unsigned grow = (unsigned)(t + 1) * grow_b;
-        PT_STAMP(wg == 0 && t == T / 2, 8);
-        // ---- location features of this step's tiles (fused filter, K = 64): they depend on alpha(t-1) only, so they
-        // are evaluated BEFORE h_att(t) arrives (wave -> tiles wave, wave + 8)
-        f32x4 lacc[NTI];
-#pragma unroll
-        for (int i = 0; i < NTI; ++i) {
-            const int jt = wave + 8 * i;
-            lacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (16 * jt < Tp) {
-                float bop[16];
-#pragma unroll
-                for (int st = 0; st < 16; ++st) {
-                    const int kk = 4 * st + g;
-                    bop[st] = win[(kk >> 5) * TW + 16 * jt + c16 + (kk & 31)];
-                }
-                f32x4 l0 = {0.f, 0.f, 0.f, 0.f}, l1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int st = 0; st < 16; st += 2) {
-                    l0 = mfma16x4(areg[st], bop[st], l0);
-                    l1 = mfma16x4(areg[st + 1], bop[st + 1], l1);
-                }
-                lacc[i] = l0 + l1;
-            }
-        }
-        // ---- h_att(t) of this item: word myw of the 1024 chunks of plane mypl (two per thread); nap, then poll the payload
-        {
-            const unsigned s0 = grow + (unsigned)(mypl * T2V_XW + tid) * 16u + 4u * (unsigned)myw;
-            float v0, v1;
-            for (int i = 0; i < h_nap; i += 8) __builtin_amdgcn_s_sleep(8);
-            int rounds = 0;
-            for (;;) {
-                v0 = __uint_as_float(t2v_ld_b32(rG, s0));
-                v1 = __uint_as_float(t2v_ld_b32(rG, s0 + PT_THREADS * 16u));
-                if (__all(t2v_ok(v0) && t2v_ok(v1))) break;
-                __builtin_amdgcn_s_sleep(1);
-                if (t2v_give_up(rounds, (int)(PT_SPIN / 4), a.err, flag)) break;
-            }
-            h_nap = t2v_adapt_nap(h_nap, rounds);
-            PT_WALL(wg == 0 && t == T / 2, 21);
-            if (a.prof && wg == 0 && t == T / 2 && tid == 0) { a.prof[26] = (unsigned long long)rounds; a.prof[27] = (unsigned long long)h_nap; }
-            hx[tid] = v0;
-            hx[tid + PT_THREADS] = v1;
-        }
-        __syncthreads();
-        if (flag[0] != 1) return;
-        PT_STAMP(wg == 0 && t == T / 2, 9);
-        // ---- query slice: thread = (dim d = tid >> 5, k part kq = tid & 31): k = 4 kq + 128 i, 16-byte LDS operands;
-        // 32-lane sum = 16-lane DPP row sum + one cross-row exchange
-        {
-            const int d = tid >> 5, kq = tid & 31;
-            const float* wrow = wq_s + d * 1028 + 4 * kq;
-            const float* hp = hx + 4 * kq;
-            float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float4 w4 = LONG ? wqr[LONG ? i : 0] : *(const float4*)(wrow + 128 * i);
-                const float4 h4 = *(const float4*)(hp + 128 * i);
-                acc0 = fmaf(w4.x, h4.x, acc0); acc1 = fmaf(w4.y, h4.y, acc1);
-                acc0 = fmaf(w4.z, h4.z, acc0); acc1 = fmaf(w4.w, h4.w, acc1);
-            }
-            float q = row16_sum(acc0 + acc1);
-            q += __shfl_xor(q, 16, 64);
-            if (kq == 0) qv[d] = q;
-        }
-        __syncthreads();
-        const float4 q4 = *(const float4*)(qv + 4 * g);
-        PT_STAMP(wg == 0 && t == T / 2, 13);
-        // ---- partial energies of this slice
-        const unsigned exw = (unsigned)(((t * B + ab) * 8 + as) * Tcap) * 4u;
-#pragma unroll
-        for (int i = 0; i < NTI; ++i) {
-            const int jt = wave + 8 * i;
-            if (16 * jt < Tp) {
-                const f32x4 acc = lacc[i];
-                const int jp = 16 * jt + c16;
-                const float4 pm4 = LONG ? pmr[LONG ? i : 0] : *(const float4*)(pm_s + min(jp, Tp - 1) * 16 + 4 * g);
-                float4 sv;
-                sv.x = tanhf_(q4.x + acc[0] + pm4.x); sv.y = tanhf_(q4.y + acc[1] + pm4.y);
-                sv.z = tanhf_(q4.z + acc[2] + pm4.z); sv.w = tanhf_(q4.w + acc[3] + pm4.w);
-                float esum = vr.x * sv.x + vr.y * sv.y + vr.z * sv.z + vr.w * sv.w;
-                esum += __shfl_xor(esum, 16, 64);
-                esum += __shfl_xor(esum, 32, 64);
-                if (g == 0 && jp < Tp) t2v_st(rE, exw + 4u * (unsigned)jp, esum);
-                if (a.S && jp < Tp) *(float4*)(a.S + (((size_t)t * B + ab) * Tp + jp) * T2V_A + 16 * as + 4 * g) = sv;
-            }
-        }
-        PT_STAMP(wg == 0 && t == T / 2, 10);
-        // (two copies of the softmax: the one-position form is kept word for word so that the short kernels keep their instruction
-        // stream — round 6 checked the ISA of <.., false> against the previous build, identical)
-        if constexpr (!LONG) {
-            // ---- the 8 partials of every position (fixed order), masked softmax
-            float ev0 = -INFINITY;
-            if (tid < Tp) {
-                const unsigned e0 = (unsigned)((t * B + ab) * 8 * Tcap + tid) * 4u;
-                unsigned p[8];
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-    #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        p[i] = t2v_ld_b32(rE, e0 + (unsigned)(i * Tcap) * 4u);
-                        ok = ok && t2v_ok(p[i]);
-                    }
-                    if (ok) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (t2v_give_up(spins, PT_SPIN, a.err, flag)) break;
-                }
-                const float ev = ((__uint_as_float(p[0]) + __uint_as_float(p[1])) + (__uint_as_float(p[2]) + __uint_as_float(p[3]))) +
-                                 ((__uint_as_float(p[4]) + __uint_as_float(p[5])) + (__uint_as_float(p[6]) + __uint_as_float(p[7])));
-                ev0 = tid < len ? ev : -INFINITY;
-            }
-            PT_STAMP(wg == 0 && t == T / 2, 14);
-            {
-                float mloc = ev0;
-                mloc = T2V_DPP_MAX(mloc, 0xB1); mloc = T2V_DPP_MAX(mloc, 0x4E);
-                mloc = T2V_DPP_MAX(mloc, 0x141); mloc = T2V_DPP_MAX(mloc, 0x140);
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-                if (lane == 0) rsm[wave] = mloc;
-            }
-            __syncthreads();
-            if (flag[0] != 1) return;
-            float m;
-            {
-                const float4 a0 = *(const float4*)rsm, a1 = *(const float4*)(rsm + 4);
-                m = fmaxf(fmaxf(fmaxf(a0.x, a0.y), fmaxf(a0.z, a0.w)), fmaxf(fmaxf(a1.x, a1.y), fmaxf(a1.z, a1.w)));
-            }
-            const float e0v = tid < Tp ? expf(ev0 - m) : 0.f;
-            {
-                float sloc = row16_sum(e0v);
-                sloc += __shfl_xor(sloc, 16, 64);
-                sloc += __shfl_xor(sloc, 32, 64);
-                if (lane == 0) rss[wave] = sloc;
-            }
-            __syncthreads();
-            float ssum;
-            {
-                const float4 a0 = *(const float4*)rss, a1 = *(const float4*)(rss + 4);
-                ssum = ((a0.x + a0.y) + (a0.z + a0.w)) + ((a1.x + a1.y) + (a1.z + a1.w));
-            }
-            const float al = e0v * (1.0f / ssum);
-            if (tid < Tp) {
-                eall[tid] = al;
-                win[15 + tid] = al;                                        // previous weights of the next step
-                const float cum = win[TW + 15 + tid] + al;                 // cumulative weights
-                win[TW + 15 + tid] = cum;
-                if (as == 0) {
-                    a.AL[((size_t)(t + 1) * B + ab) * Tp + tid] = al;
-                    a.ACUM[((size_t)(t + 1) * B + ab) * Tp + tid] = cum;
-                }
-            }
-        } else {
-            // ---- the 8 partials of every position (fixed order), masked softmax; thread -> positions tid + 512 u
-            float ev0[NPP];
-    #pragma unroll
-            for (int u = 0; u < NPP; ++u) ev0[u] = -INFINITY;
-            if (tid < Tp) {
-                const unsigned e0 = (unsigned)((t * B + ab) * 8 * Tcap + tid) * 4u;
-                unsigned p[NPP][8];
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-    #pragma unroll
-                    for (int u = 0; u < NPP; ++u) {
-                        // (a second position past the end re-reads the first one's words: no branch around the loads)
-                        const unsigned eu = e0 + ((u > 0 && tid + PT_THREADS * u < Tp) ? (unsigned)(PT_THREADS * u) * 4u : 0u);
-    #pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            p[u][i] = t2v_ld_b32(rE, eu + (unsigned)(i * Tcap) * 4u);
-                            ok = ok && t2v_ok(p[u][i]);
-                        }
-                    }
-                    if (ok) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (t2v_give_up(spins, PT_SPIN, a.err, flag)) break;
-                }
-    #pragma unroll
-                for (int u = 0; u < NPP; ++u) {
-                    const float ev = ((__uint_as_float(p[u][0]) + __uint_as_float(p[u][1])) + (__uint_as_float(p[u][2]) + __uint_as_float(p[u][3]))) +
-                                     ((__uint_as_float(p[u][4]) + __uint_as_float(p[u][5])) + (__uint_as_float(p[u][6]) + __uint_as_float(p[u][7])));
-                    ev0[u] = tid + PT_THREADS * u < len ? ev : -INFINITY;
-                }
-            }
-            PT_STAMP(wg == 0 && t == T / 2, 14);
-            {
-                float mloc = ev0[0];
-    #pragma unroll
-                for (int u = 1; u < NPP; ++u) mloc = fmaxf(mloc, ev0[u]);
-                mloc = T2V_DPP_MAX(mloc, 0xB1); mloc = T2V_DPP_MAX(mloc, 0x4E);
-                mloc = T2V_DPP_MAX(mloc, 0x141); mloc = T2V_DPP_MAX(mloc, 0x140);
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-                if (lane == 0) rsm[wave] = mloc;
-            }
-            __syncthreads();
-            if (flag[0] != 1) return;
-            float m;
-            {
-                const float4 a0 = *(const float4*)rsm, a1 = *(const float4*)(rsm + 4);
-                m = fmaxf(fmaxf(fmaxf(a0.x, a0.y), fmaxf(a0.z, a0.w)), fmaxf(fmaxf(a1.x, a1.y), fmaxf(a1.z, a1.w)));
-            }
-            float e0v[NPP];
-    #pragma unroll
-            for (int u = 0; u < NPP; ++u) e0v[u] = tid + PT_THREADS * u < Tp ? expf(ev0[u] - m) : 0.f;
-            {
-                float sloc = e0v[0];
-    #pragma unroll
-                for (int u = 1; u < NPP; ++u) sloc += e0v[u];
-                sloc = row16_sum(sloc);
-                sloc += __shfl_xor(sloc, 16, 64);
-                sloc += __shfl_xor(sloc, 32, 64);
-                if (lane == 0) rss[wave] = sloc;
-            }
-            __syncthreads();
-            float ssum;
-            {
-                const float4 a0 = *(const float4*)rss, a1 = *(const float4*)(rss + 4);
-                ssum = ((a0.x + a0.y) + (a0.z + a0.w)) + ((a1.x + a1.y) + (a1.z + a1.w));
-            }
-            const float rinv = 1.0f / ssum;
-    #pragma unroll
-            for (int u = 0; u < NPP; ++u) {
-                const int pos = tid + PT_THREADS * u;
-                const float al = e0v[u] * rinv;
-                if (pos < Tp) {
-                    eall[pos] = al;
-                    win[15 + pos] = al;                                        // previous weights of the next step
-                    const float cum = win[TW + 15 + pos] + al;                 // cumulative weights
-                    win[TW + 15 + pos] = cum;
-                    if (as == 0) {
-                        a.AL[((size_t)(t + 1) * B + ab) * Tp + pos] = al;
-                        a.ACUM[((size_t)(t + 1) * B + ab) * Tp + pos] = cum;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        PT_STAMP(wg == 0 && t == T / 2, 11);
-        // ---- context columns [64 as, 64 as + 64): thread = (column c = tid & 63, part = tid >> 6)
-        {
-            const int c = tid & 63, part = tid >> 6;
-            if constexpr (LONG) {
-                // (up to 70 positions per thread: eight per round, reads first — 8 000 -> 6 500 cycles at 555 symbols; at <= 224 symbols
-                // the plain loop is as fast and the short kernels keep their instruction stream)
-                cred[part * 64 + c] = t2v_ctx_partial<8>(eall, mem_s, part, c, Tp);
-            } else {
-                float acc = 0.f;
-                for (int jj = part; jj < Tp; jj += 8) acc = fmaf(eall[jj], mem_s[jj * 64 + c], acc);
-                cred[part * 64 + c] = acc;
-            }
-        }
-        __syncthreads();
-        if (tid < 64) {
-            float acc = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += cred[u * 64 + tid];
-            t2v_st(rG, grow + (unsigned)(mypl * T2V_XW + T2V_H + 64 * as + tid) * 16u + 4u * (unsigned)myw, acc);
-            a.XS[((size_t)(t + 1) * B + ab) * T2V_XW + T2V_H + 64 * as + tid] = acc;       // (after the publish)
-        }
-        PT_WALL(wg == 0 && t == T / 2, 22);
-        PT_STAMP(wg == 0 && t == T / 2, 12);
-    }
+#define AF_CTX_PUBLISH t2v_st(rG, grow + (unsigned)(mypl * T2V_XW + T2V_H + 64 * as + tid) * 16u + 4u * (unsigned)myw, acc);
+#include "t2v_attn_role_fwd.inc"
+#undef AF_TAIL
+#undef AF_SETUP
+#undef AF_GROW
+#undef AF_STAMP_STEP
+#undef AF_STAMP_H
+#undef AF_STAMP_Q
+#undef AF_STAMP_E
+#undef AF_STAMP_EX
+#undef AF_STAMP_ALPHA
+#undef AF_STAMP_END
+#undef AF_H_INGEST
+#undef AF_CTX_PUBLISH
 }
 
 static size_t pt_lds_bytes(int B, int T_in) {
-    const size_t Tcap = (size_t)((T_in + 15) / 16) * 16;
     const size_t np = B > 4 ? 2 : 1;
     const size_t lrole = np * T2V_XW * 4 + 4 * 8 * 32 + 8 * 32 + 4;
-    const size_t resident = T_in > PT_MAXT ? Tcap * 64 : 16 * 1028 + Tcap * 64 + Tcap * 16;      // LONG: W_q / processed memory in registers
-    const size_t trole = resident + 2 * (Tcap + 32) + Tcap + (T_in > PT_MAXT ? T2V_CTX_PAD : 0) + T2V_H + 16 + 32 * 16 + 8 * 64 + 64 + 4;
+    const size_t trole = t2v_attn_fwd_lds_floats(T_in, 0);
     return sizeof(float) * (lrole > trole ? lrole : trole);
 }
 static size_t pt_g_floats(int B, int T_out) { return (size_t)(T_out + 2) * (B > 4 ? 2 : 1) * T2V_XW * 4; }
 static size_t pt_ex_floats(int B, int T_in, int T_out) { return (size_t)T_out * B * 8 * t2v_tcap(T_in); }
 
 static const void* pt_kernel(int B, int T_in) {
-    if (T_in > PT_MAXT) return B > 4 ? (const void*)k_dec_train_persist<6, true> : (const void*)k_dec_train_persist<4, true>;
+    if (T_in > T2V_AF_MAXT) return B > 4 ? (const void*)k_dec_train_persist<6, true> : (const void*)k_dec_train_persist<4, true>;
     return B > 4 ? (const void*)k_dec_train_persist<6, false> : (const void*)k_dec_train_persist<4, false>;
 }
 
 extern "C" int t2v_decoder_train_persist_supported(int B, int T_in) {
-    if (!(B >= 1 && B <= PT_MAXB && T_in >= 1 && T_in <= PT_MAXT_LONG && pt_lds_bytes(B, T_in) <= T2V_LDS_MAX)) return 0;
+    if (!(B >= 1 && B <= PT_MAXB && T_in >= 1 && T_in <= T2V_AF_MAXT_LONG && pt_lds_bytes(B, T_in) <= T2V_LDS_MAX)) return 0;
     static bool raised = false;
-    return t2v_persist_resident(pt_kernel(B, T_in), PT_THREADS, pt_lds_bytes(B, T_in),
-                                {pt_kernel(4, PT_MAXT), pt_kernel(4, PT_MAXT + 1), pt_kernel(6, PT_MAXT), pt_kernel(6, PT_MAXT + 1)}, raised);
+    return t2v_persist_resident(pt_kernel(B, T_in), T2V_AF_THREADS, pt_lds_bytes(B, T_in),
+                                {pt_kernel(4, T2V_AF_MAXT), pt_kernel(4, T2V_AF_MAXT + 1), pt_kernel(6, T2V_AF_MAXT), pt_kernel(6, T2V_AF_MAXT + 1)}, raised);
 }
 extern "C" long t2v_decoder_train_persist_scratch_floats(int B, int T_in, int T_out) {
     if (B < 1 || B > PT_MAXB || T_in < 1 || T_out < 1) return 0;
@@ -854,12 +574,12 @@ extern "C" int t2v_decoder_train_fwd_persistent(const t2v_dec_train_persist_weig
     a.step = t2v_step_for(stream);
     a.prof = g_t2v_prof;
     const size_t lds = pt_lds_bytes(B, T_in);
-    if (T_in > PT_MAXT) {
-        if (B > 4) k_dec_train_persist<6, true><<<T2V_NWG, PT_THREADS, lds, stream>>>(a);
-        else k_dec_train_persist<4, true><<<T2V_NWG, PT_THREADS, lds, stream>>>(a);
+    if (T_in > T2V_AF_MAXT) {
+        if (B > 4) k_dec_train_persist<6, true><<<T2V_NWG, T2V_AF_THREADS, lds, stream>>>(a);
+        else k_dec_train_persist<4, true><<<T2V_NWG, T2V_AF_THREADS, lds, stream>>>(a);
     } else {
-        if (B > 4) k_dec_train_persist<6, false><<<T2V_NWG, PT_THREADS, lds, stream>>>(a);
-        else k_dec_train_persist<4, false><<<T2V_NWG, PT_THREADS, lds, stream>>>(a);
+        if (B > 4) k_dec_train_persist<6, false><<<T2V_NWG, T2V_AF_THREADS, lds, stream>>>(a);
+        else k_dec_train_persist<4, false><<<T2V_NWG, T2V_AF_THREADS, lds, stream>>>(a);
     }
     return t2v_check_launch();
 }

@@ -9,8 +9,8 @@
 // cell: 4 units x 4 gates, unit-major), and the batch is the N dimension of v_mfma_f32_16x16x32_bf16: B <= 16 is one tile.
 //
 // Roles (one 512-thread workgroup per CU, all co-resident):
-//   T : workgroups [0, 8B)      — attention slice (item b = wg / 8, s = wg % 8): the role of decoder_train_persist.hip,
-//                                 unchanged arithmetic (fp32: bf16_run keeps the attention in fp32)
+//   T : workgroups [0, 8B)      — attention slice (item b = wg / 8, s = wg % 8): the role of decoder_train_persist.hip, the
+//                                 same program text (t2v_attn_role_fwd.inc; fp32: bf16_run keeps the attention in fp32)
 //   L : workgroups [128, 256)   — LSTM rows of both cells: workgroup j owns units [8j, 8j + 8).  K is split over the 8 waves:
 //                                 wave w multiplies h_att k-blocks [4w, 4w+4), ctx k-blocks [32+2w, 32+2w+2) and h_dec
 //                                 k-blocks [48+4w, 48+4w+4) (32 columns each) of both cells — 48 + 80 weight registers.
@@ -39,14 +39,9 @@
 #include "t2v_kernels.h"
 #include "t2v_xchg.h"
 
-#define P16_THREADS 512
-#define P16_MAXB 16
-#define P16_MAXT 224                 // LDS-resident W_q / processed-memory slices up to here
-#define P16_MAXT_LONG 560            // register-resident ones beyond (k_dec_train_persist16<true>; decoder_train_persist.hip has the arithmetic)
-#define P16_NTI_LONG 5               // 16-position tiles per wave of the long form
+#define P16_MAXB 16                  // (thread count, spin limit and the T_in bounds: T2V_AF_*, t2v_kernels.h)
 #define P16_NL 128
 #define P16_L0 (T2V_NWG - P16_NL)
-#define P16_SPIN 1500000u
 #define P16_GROW (T2V_XW / 8 * 16 * 16)        // bytes per GH row: 320 k-groups x 16 items x 16 B = 81 920
 #define P16_HROW (16 * T2V_H * 4)              // bytes per HX row: 16 items x 1024 fp32 = 65 536
 
@@ -90,7 +85,7 @@ __device__ __forceinline__ int p16_poll(u32x4 (&x)[N], __amdgpu_buffer_rsrc_t rG
         for (int i = 0; i < N; ++i) ok = ok && t2v_ok4(x[i]);
         if (__all(ok || !live)) break;
         __builtin_amdgcn_s_sleep(2);
-        if (t2v_give_up(rounds, (int)(P16_SPIN / 4), err, flag)) break;
+        if (t2v_give_up(rounds, (int)(T2V_AF_SPIN / 4), err, flag)) break;
     }
     if (!live) {
 #pragma unroll
@@ -107,7 +102,7 @@ __device__ __forceinline__ u32x4 p16_wload(const float* p) {
 }
 
 template <bool LONG>          // the attention role for 224 < T_in <= 560, as in k_dec_train_persist<.., true>
-__global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) {
+__global__ __launch_bounds__(T2V_AF_THREADS) void k_dec_train_persist16(P16Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint64_t seed = t2v_step_seed(a.seed, a.step);
     const int wg = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -308,338 +303,63 @@ __global__ __launch_bounds__(P16_THREADS) void k_dec_train_persist16(P16Args a) 
     if (wg >= NT) return;
 
     // =============================================================================== T role: attention slice (b, s)
-    const int ab = wg >> 3, as = wg & 7;
-    constexpr int NTI = LONG ? P16_NTI_LONG : 2;         // position tiles per wave: tile jt = wave + 8 i
-    constexpr int NPP = LONG ? 2 : 1;                    // positions per thread in the softmax: tid + 512 u
-    const int TW = Tcap + 32;
-    float* wq_s = lds;                                   // [16][1028]   (LONG: in registers)
-    float* mem_s = wq_s + (LONG ? 0 : 16 * 1028);        // [Tcap][64]
-    float* pm_s = mem_s + Tcap * 64;                     // [Tcap][16]   (LONG: in registers)
-    float* win = pm_s + (LONG ? 0 : Tcap * 16);          // [2][TW]: alignment window, index x <-> position x - 15
-    float* eall = win + 2 * TW;                          // [Tcap] (LONG: + T2V_CTX_PAD, zero from Tp on: t2v_ctx_partial)
-    float* hx = eall + Tcap + (LONG ? T2V_CTX_PAD : 0);  // [1024] h_att(t) of this item
-    float* qv = hx + T2V_H;                              // [16]
-    float* qred = qv + 16;                               // [32][16]
-    float* cred = qred + 32 * 16;                        // [8][64]
-    float* rsm = cred + 8 * 64;                          // [32]
-    float* rss = rsm + 32;                               // [32]
-    float* cfin = rss + 32;                              // [64] finished context columns (wave 0)
-    int* flag = (int*)(cfin + 64);
-    const int g = lane >> 4, c16 = lane & 15;
-    float4 wqr[LONG ? 8 : 1], pmr[LONG ? NTI : 1];
-    if constexpr (LONG) {
-        const float* wrow = a.wq + (size_t)(16 * as + (tid >> 5)) * 1024 + 4 * (tid & 31);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wqr[i] = *(const float4*)(wrow + 128 * i);
-#pragma unroll
-        for (int i = 0; i < NTI; ++i) {
-            const int jp = 16 * (wave + 8 * i) + c16;
-            pmr[i] = *(const float4*)(a.pm + ((size_t)ab * Tp + min(jp, Tp - 1)) * T2V_A + 16 * as + 4 * g);
+    // t2v_attn_role_fwd.inc, shared with k_dec_train_persist; what is this kernel's own: h_att(t) arrives as 4 KB of fp32 in HX (16
+    // bytes per thread of waves 0..3), the 64 context columns leave as bf16: lanes 0..7 send 8 columns each as one 16-byte chunk
+    // (k-group 128 + 8 as + lane, item ab) out of cfin[64], the finished columns; the LDS round trip stays inside wave 0.
+#define AF_TAIL 64
+#define AF_SETUP float* cfin = rss + 32;
+#define AF_GROW (unsigned)P16_GROW
+#define AF_STAMP_STEP P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 8); P16_RT(0)
+#define AF_STAMP_H P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 9)
+#define AF_STAMP_Q
+#define AF_STAMP_E P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 10); P16_RT(2)
+#define AF_STAMP_EX P16_RT(3)
+#define AF_STAMP_ALPHA P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 11); P16_RT(4)
+#define AF_STAMP_END P16_WALL(wg == 0 && wave == 0 && t == T / 2, 22); P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 12); P16_RT(5)
+#define AF_H_INGEST if (tid < 256) {                                                                                            \
+            const unsigned s0 = (unsigned)t * (unsigned)P16_HROW + (unsigned)(ab * T2V_H + 4 * tid) * 4u;                       \
+            u32x4 v;                                                                                                            \
+            for (int i = 0; i < h_nap; i += 8) __builtin_amdgcn_s_sleep(8);                                                     \
+            int rounds = 0;                                                                                                     \
+            for (;;) {                                                                                                          \
+                v = t2v_ld_b128(rH, s0);                                                                                        \
+                if (__all(t2v_ok4(v))) break;                                                                                   \
+                __builtin_amdgcn_s_sleep(1);                                                                                    \
+                if (t2v_give_up(rounds, (int)(T2V_AF_SPIN / 4), a.err, flag)) break;                                            \
+            }                                                                                                                   \
+            h_nap = t2v_adapt_nap(h_nap, rounds);                                                                               \
+            P16_WALL(wg == 0 && wave == 0 && t == T / 2, 21);                                                                   \
+            P16_RT(1);                                                                                                          \
+            if (a.prof && t == T / 2 && tid == 0) { a.prof[64 + wg * 8 + 6] = (unsigned long long)rounds; a.prof[64 + wg * 8 + 7] = (unsigned long long)h_nap; } \
+            *(float4*)(hx + 4 * tid) = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])); \
         }
-    } else {
-        for (int i = tid; i < 16 * 1024; i += P16_THREADS) wq_s[(i >> 10) * 1028 + (i & 1023)] = a.wq[(size_t)(16 * as) * 1024 + i];
-    }
-    for (int i = tid; i < Tp * 64; i += P16_THREADS) mem_s[i] = a.memory[((size_t)ab * Tp + (i >> 6)) * T2V_E + 64 * as + (i & 63)];
-    if constexpr (!LONG)
-        for (int i = tid; i < Tp * 16; i += P16_THREADS) pm_s[i] = a.pm[((size_t)ab * Tp + (i >> 4)) * T2V_A + 16 * as + (i & 15)];
-    for (int i = tid; i < 2 * TW; i += P16_THREADS) win[i] = 0.f;
-    if constexpr (LONG)
-        for (int i = Tp + tid; i < Tcap + T2V_CTX_PAD; i += P16_THREADS) eall[i] = 0.f;
-    if (tid == 0) flag[0] = 1;
-    float areg[16];
-    {
-        const float4* wp = (const float4*)(a.wcomb + (16 * as + c16) * 64 + 16 * g);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float4 w4 = wp[u];
-            areg[4 * u] = w4.x; areg[4 * u + 1] = w4.y; areg[4 * u + 2] = w4.z; areg[4 * u + 3] = w4.w;
-        }
-    }
-    const float4 vr = *(const float4*)(a.v + 16 * as + 4 * g);
-    const int len = a.lengths ? a.lengths[ab] : Tp;
-    __syncthreads();
-    int h_nap = 0;
-
-    for (int t = 0; t < T; ++t) {
-        const unsigned grow = (unsigned)(t + 1) * (unsigned)P16_GROW;
-        P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 8);
-        P16_RT(0);
-        // ---- location features of this step's tiles (fused filter, K = 64): they depend on alpha(t-1) only
-        f32x4 lacc[NTI];
-#pragma unroll
-        for (int i = 0; i < NTI; ++i) {
-            const int jt = wave + 8 * i;
-            lacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (16 * jt < Tp) {
-                float bop[16];
-#pragma unroll
-                for (int st = 0; st < 16; ++st) {
-                    const int kk = 4 * st + g;
-                    bop[st] = win[(kk >> 5) * TW + 16 * jt + c16 + (kk & 31)];
-                }
-                f32x4 l0 = {0.f, 0.f, 0.f, 0.f}, l1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int st = 0; st < 16; st += 2) {
-                    l0 = mfma16x4(areg[st], bop[st], l0);
-                    l1 = mfma16x4(areg[st + 1], bop[st + 1], l1);
-                }
-                lacc[i] = l0 + l1;
+#define AF_CTX_PUBLISH                                                                                                          \
+            cfin[tid] = acc;                                                                                                    \
+            if (tid < 8) {                                                                                                      \
+                const float4 c0 = *(const float4*)(cfin + 8 * tid), c1 = *(const float4*)(cfin + 8 * tid + 4);                  \
+                const uint4 pk = t2v_pack_bf16x8(c0, c1);                                                                       \
+                const unsigned kg = (unsigned)(T2V_H / 8 + 8 * as + tid);                                                       \
+                t2v_st(rG, grow + (kg * 16u + (unsigned)ab) * 16u, u32x4{pk.x, pk.y, pk.z, pk.w});                              \
             }
-        }
-        // ---- h_att(t) of this item: 4 KB of fp32 in HX, 16 bytes per thread of waves 0..3; nap, then poll the payload
-        if (tid < 256) {
-            const unsigned s0 = (unsigned)t * (unsigned)P16_HROW + (unsigned)(ab * T2V_H + 4 * tid) * 4u;
-            u32x4 v;
-            for (int i = 0; i < h_nap; i += 8) __builtin_amdgcn_s_sleep(8);
-            int rounds = 0;
-            for (;;) {
-                v = t2v_ld_b128(rH, s0);
-                if (__all(t2v_ok4(v))) break;
-                __builtin_amdgcn_s_sleep(1);
-                if (t2v_give_up(rounds, (int)(P16_SPIN / 4), a.err, flag)) break;
-            }
-            h_nap = t2v_adapt_nap(h_nap, rounds);
-            P16_WALL(wg == 0 && wave == 0 && t == T / 2, 21);
-            P16_RT(1);
-            if (a.prof && t == T / 2 && tid == 0) { a.prof[64 + wg * 8 + 6] = (unsigned long long)rounds; a.prof[64 + wg * 8 + 7] = (unsigned long long)h_nap; }
-            *(float4*)(hx + 4 * tid) = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-        }
-        __syncthreads();
-        if (flag[0] != 1) return;
-        P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 9);
-        // ---- query slice: thread = (dim d = tid >> 5, k part kq = tid & 31)
-        {
-            const int d = tid >> 5, kq = tid & 31;
-            const float* wrow = wq_s + d * 1028 + 4 * kq;
-            const float* hp = hx + 4 * kq;
-            float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float4 w4 = LONG ? wqr[LONG ? i : 0] : *(const float4*)(wrow + 128 * i);
-                const float4 h4 = *(const float4*)(hp + 128 * i);
-                acc0 = fmaf(w4.x, h4.x, acc0); acc1 = fmaf(w4.y, h4.y, acc1);
-                acc0 = fmaf(w4.z, h4.z, acc0); acc1 = fmaf(w4.w, h4.w, acc1);
-            }
-            float q = row16_sum(acc0 + acc1);
-            q += __shfl_xor(q, 16, 64);
-            if (kq == 0) qv[d] = q;
-        }
-        __syncthreads();
-        const float4 q4 = *(const float4*)(qv + 4 * g);
-        // ---- partial energies of this slice
-        const unsigned exw = (unsigned)(((t * B + ab) * 8 + as) * Tcap) * 4u;
-#pragma unroll
-        for (int i = 0; i < NTI; ++i) {
-            const int jt = wave + 8 * i;
-            if (16 * jt < Tp) {
-                const f32x4 acc = lacc[i];
-                const int jp = 16 * jt + c16;
-                const float4 pm4 = LONG ? pmr[LONG ? i : 0] : *(const float4*)(pm_s + min(jp, Tp - 1) * 16 + 4 * g);
-                float4 sv;
-                sv.x = tanhf_(q4.x + acc[0] + pm4.x); sv.y = tanhf_(q4.y + acc[1] + pm4.y);
-                sv.z = tanhf_(q4.z + acc[2] + pm4.z); sv.w = tanhf_(q4.w + acc[3] + pm4.w);
-                float esum = vr.x * sv.x + vr.y * sv.y + vr.z * sv.z + vr.w * sv.w;
-                esum += __shfl_xor(esum, 16, 64);
-                esum += __shfl_xor(esum, 32, 64);
-                if (g == 0 && jp < Tp) t2v_st(rE, exw + 4u * (unsigned)jp, esum);
-                if (a.S && jp < Tp) *(float4*)(a.S + (((size_t)t * B + ab) * Tp + jp) * T2V_A + 16 * as + 4 * g) = sv;
-            }
-        }
-        P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 10);
-        P16_RT(2);
-        // (two copies of the softmax: the one-position form is kept word for word so that the short kernels keep their instruction
-        // stream — round 6 checked the ISA of <.., false> against the previous build, identical)
-        if constexpr (!LONG) {
-            // ---- the 8 partials of every position (fixed order), masked softmax
-            float ev0 = -INFINITY;
-            if (tid < Tp) {
-                const unsigned e0 = (unsigned)((t * B + ab) * 8 * Tcap + tid) * 4u;
-                unsigned p[8];
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-    #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        p[i] = t2v_ld_b32(rE, e0 + (unsigned)(i * Tcap) * 4u);
-                        ok = ok && t2v_ok(p[i]);
-                    }
-                    if (ok) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (t2v_give_up(spins, P16_SPIN, a.err, flag)) break;
-                }
-                const float ev = ((__uint_as_float(p[0]) + __uint_as_float(p[1])) + (__uint_as_float(p[2]) + __uint_as_float(p[3]))) +
-                                 ((__uint_as_float(p[4]) + __uint_as_float(p[5])) + (__uint_as_float(p[6]) + __uint_as_float(p[7])));
-                ev0 = tid < len ? ev : -INFINITY;
-            }
-            P16_RT(3);
-            {
-                float mloc = ev0;
-                mloc = T2V_DPP_MAX(mloc, 0xB1); mloc = T2V_DPP_MAX(mloc, 0x4E);
-                mloc = T2V_DPP_MAX(mloc, 0x141); mloc = T2V_DPP_MAX(mloc, 0x140);
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-                if (lane == 0) rsm[wave] = mloc;
-            }
-            __syncthreads();
-            if (flag[0] != 1) return;
-            float m;
-            {
-                const float4 a0 = *(const float4*)rsm, a1 = *(const float4*)(rsm + 4);
-                m = fmaxf(fmaxf(fmaxf(a0.x, a0.y), fmaxf(a0.z, a0.w)), fmaxf(fmaxf(a1.x, a1.y), fmaxf(a1.z, a1.w)));
-            }
-            const float e0v = tid < Tp ? expf(ev0 - m) : 0.f;
-            {
-                float sloc = row16_sum(e0v);
-                sloc += __shfl_xor(sloc, 16, 64);
-                sloc += __shfl_xor(sloc, 32, 64);
-                if (lane == 0) rss[wave] = sloc;
-            }
-            __syncthreads();
-            float ssum;
-            {
-                const float4 a0 = *(const float4*)rss, a1 = *(const float4*)(rss + 4);
-                ssum = ((a0.x + a0.y) + (a0.z + a0.w)) + ((a1.x + a1.y) + (a1.z + a1.w));
-            }
-            const float al = e0v * (1.0f / ssum);
-            if (tid < Tp) {
-                eall[tid] = al;
-                win[15 + tid] = al;                                        // previous weights of the next step
-                const float cum = win[TW + 15 + tid] + al;                 // cumulative weights
-                win[TW + 15 + tid] = cum;
-                if (as == 0) {
-                    a.AL[((size_t)(t + 1) * B + ab) * Tp + tid] = al;
-                    a.ACUM[((size_t)(t + 1) * B + ab) * Tp + tid] = cum;
-                }
-            }
-        } else {
-            // ---- the 8 partials of every position (fixed order), masked softmax; thread -> positions tid + 512 u
-            float ev0[NPP];
-    #pragma unroll
-            for (int u = 0; u < NPP; ++u) ev0[u] = -INFINITY;
-            if (tid < Tp) {
-                const unsigned e0 = (unsigned)((t * B + ab) * 8 * Tcap + tid) * 4u;
-                unsigned p[NPP][8];
-                unsigned spins = 0;
-                for (;;) {
-                    bool ok = true;
-    #pragma unroll
-                    for (int u = 0; u < NPP; ++u) {
-                        // (a second position past the end re-reads the first one's words: no branch around the loads)
-                        const unsigned eu = e0 + ((u > 0 && tid + P16_THREADS * u < Tp) ? (unsigned)(P16_THREADS * u) * 4u : 0u);
-    #pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            p[u][i] = t2v_ld_b32(rE, eu + (unsigned)(i * Tcap) * 4u);
-                            ok = ok && t2v_ok(p[u][i]);
-                        }
-                    }
-                    if (ok) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (t2v_give_up(spins, P16_SPIN, a.err, flag)) break;
-                }
-    #pragma unroll
-                for (int u = 0; u < NPP; ++u) {
-                    const float ev = ((__uint_as_float(p[u][0]) + __uint_as_float(p[u][1])) + (__uint_as_float(p[u][2]) + __uint_as_float(p[u][3]))) +
-                                     ((__uint_as_float(p[u][4]) + __uint_as_float(p[u][5])) + (__uint_as_float(p[u][6]) + __uint_as_float(p[u][7])));
-                    ev0[u] = tid + P16_THREADS * u < len ? ev : -INFINITY;
-                }
-            }
-            P16_RT(3);
-            {
-                float mloc = ev0[0];
-    #pragma unroll
-                for (int u = 1; u < NPP; ++u) mloc = fmaxf(mloc, ev0[u]);
-                mloc = T2V_DPP_MAX(mloc, 0xB1); mloc = T2V_DPP_MAX(mloc, 0x4E);
-                mloc = T2V_DPP_MAX(mloc, 0x141); mloc = T2V_DPP_MAX(mloc, 0x140);
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
-                mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-                if (lane == 0) rsm[wave] = mloc;
-            }
-            __syncthreads();
-            if (flag[0] != 1) return;
-            float m;
-            {
-                const float4 a0 = *(const float4*)rsm, a1 = *(const float4*)(rsm + 4);
-                m = fmaxf(fmaxf(fmaxf(a0.x, a0.y), fmaxf(a0.z, a0.w)), fmaxf(fmaxf(a1.x, a1.y), fmaxf(a1.z, a1.w)));
-            }
-            float e0v[NPP];
-    #pragma unroll
-            for (int u = 0; u < NPP; ++u) e0v[u] = tid + P16_THREADS * u < Tp ? expf(ev0[u] - m) : 0.f;
-            {
-                float sloc = e0v[0];
-    #pragma unroll
-                for (int u = 1; u < NPP; ++u) sloc += e0v[u];
-                sloc = row16_sum(sloc);
-                sloc += __shfl_xor(sloc, 16, 64);
-                sloc += __shfl_xor(sloc, 32, 64);
-                if (lane == 0) rss[wave] = sloc;
-            }
-            __syncthreads();
-            float ssum;
-            {
-                const float4 a0 = *(const float4*)rss, a1 = *(const float4*)(rss + 4);
-                ssum = ((a0.x + a0.y) + (a0.z + a0.w)) + ((a1.x + a1.y) + (a1.z + a1.w));
-            }
-            const float rinv = 1.0f / ssum;
-    #pragma unroll
-            for (int u = 0; u < NPP; ++u) {
-                const int pos = tid + P16_THREADS * u;
-                const float al = e0v[u] * rinv;
-                if (pos < Tp) {
-                    eall[pos] = al;
-                    win[15 + pos] = al;                                        // previous weights of the next step
-                    const float cum = win[TW + 15 + pos] + al;                 // cumulative weights
-                    win[TW + 15 + pos] = cum;
-                    if (as == 0) {
-                        a.AL[((size_t)(t + 1) * B + ab) * Tp + pos] = al;
-                        a.ACUM[((size_t)(t + 1) * B + ab) * Tp + pos] = cum;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 11);
-        P16_RT(4);
-        // ---- context columns [64 as, 64 as + 64): thread = (column c = tid & 63, part = tid >> 6)
-        {
-            const int c = tid & 63, part = tid >> 6;
-            if constexpr (LONG) {
-                // (up to 70 positions per thread: eight per round, reads first — 8 000 -> 6 500 cycles at 555 symbols; at <= 224 symbols
-                // the plain loop is as fast and the short kernels keep their instruction stream)
-                cred[part * 64 + c] = t2v_ctx_partial<8>(eall, mem_s, part, c, Tp);
-            } else {
-                float acc = 0.f;
-                for (int jj = part; jj < Tp; jj += 8) acc = fmaf(eall[jj], mem_s[jj * 64 + c], acc);
-                cred[part * 64 + c] = acc;
-            }
-        }
-        __syncthreads();
-        if (tid < 64) {
-            float acc = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += cred[u * 64 + tid];
-            cfin[tid] = acc;
-            // publish: lanes 0..7 send 8 columns each as one 16-byte bf16 chunk (k-group 128 + 8 as + lane, item ab); the
-            // LDS round trip stays inside this wave
-            if (tid < 8) {
-                const float4 c0 = *(const float4*)(cfin + 8 * tid), c1 = *(const float4*)(cfin + 8 * tid + 4);
-                const uint4 pk = t2v_pack_bf16x8(c0, c1);
-                const unsigned kg = (unsigned)(T2V_H / 8 + 8 * as + tid);
-                t2v_st(rG, grow + (kg * 16u + (unsigned)ab) * 16u, u32x4{pk.x, pk.y, pk.z, pk.w});
-            }
-            a.XS[((size_t)(t + 1) * B + ab) * T2V_XW + T2V_H + 64 * as + tid] = acc;       // (after the publish)
-        }
-        P16_WALL(wg == 0 && wave == 0 && t == T / 2, 22);
-        P16_STAMP(wg == 0 && wave == 0 && t == T / 2, 12);
-        P16_RT(5);
-    }
+#include "t2v_attn_role_fwd.inc"
+#undef AF_TAIL
+#undef AF_SETUP
+#undef AF_GROW
+#undef AF_STAMP_STEP
+#undef AF_STAMP_H
+#undef AF_STAMP_Q
+#undef AF_STAMP_E
+#undef AF_STAMP_EX
+#undef AF_STAMP_ALPHA
+#undef AF_STAMP_END
+#undef AF_H_INGEST
+#undef AF_CTX_PUBLISH
 #endif
 }
 
 static size_t p16_lds_bytes(int T_in) {
-    const size_t Tcap = (size_t)((T_in + 15) / 16) * 16;
     const size_t lrole = 2 * 2 * 8 * 2 * 64 * 4 + 4 * 64 + 4;
-    const size_t resident = T_in > P16_MAXT ? Tcap * 64 : 16 * 1028 + Tcap * 64 + Tcap * 16;     // LONG: W_q / processed memory in registers
-    const size_t trole = resident + 2 * (Tcap + 32) + Tcap + (T_in > P16_MAXT ? T2V_CTX_PAD : 0) + T2V_H + 16 + 32 * 16 + 8 * 64 + 64 + 64 + 4;
+    const size_t trole = t2v_attn_fwd_lds_floats(T_in, 64);         // cfin[64]
     return sizeof(float) * (lrole > trole ? lrole : trole);
 }
 static size_t p16_gh_floats(int T_out) { return (size_t)(T_out + 2) * (P16_GROW / 4); }
@@ -647,12 +367,12 @@ static size_t p16_hx_floats(int T_out) { return (size_t)T_out * (P16_HROW / 4); 
 static size_t p16_ex_floats(int B, int T_in, int T_out) { return (size_t)T_out * B * 8 * t2v_tcap(T_in); }
 
 static const void* p16_kernel(int T_in) {
-    return T_in > P16_MAXT ? (const void*)k_dec_train_persist16<true> : (const void*)k_dec_train_persist16<false>;
+    return T_in > T2V_AF_MAXT ? (const void*)k_dec_train_persist16<true> : (const void*)k_dec_train_persist16<false>;
 }
 extern "C" int t2v_decoder_train_persist16_supported(int B, int T_in) {
-    if (!(B >= 1 && B <= P16_MAXB && T_in >= 1 && T_in <= P16_MAXT_LONG && p16_lds_bytes(T_in) <= T2V_LDS_MAX)) return 0;
+    if (!(B >= 1 && B <= P16_MAXB && T_in >= 1 && T_in <= T2V_AF_MAXT_LONG && p16_lds_bytes(T_in) <= T2V_LDS_MAX)) return 0;
     static bool raised = false;
-    return t2v_persist_resident(p16_kernel(T_in), P16_THREADS, p16_lds_bytes(T_in), {p16_kernel(P16_MAXT), p16_kernel(P16_MAXT + 1)}, raised);
+    return t2v_persist_resident(p16_kernel(T_in), T2V_AF_THREADS, p16_lds_bytes(T_in), {p16_kernel(T2V_AF_MAXT), p16_kernel(T2V_AF_MAXT + 1)}, raised);
 }
 extern "C" long t2v_decoder_train_persist16_scratch_floats(int B, int T_in, int T_out) {
     if (B < 1 || B > P16_MAXB || T_in < 1 || T_out < 1) return 0;
@@ -681,7 +401,7 @@ extern "C" int t2v_decoder_train_fwd_persistent16(const t2v_dec_train_persist_we
     a.B = B; a.T_in = T_in; a.T_out = T_out; a.p_att = p_att; a.p_dec = p_dec; a.seed = seed;
     a.step = t2v_step_for(stream);
     a.prof = g_t2v_prof;
-    if (T_in > P16_MAXT) k_dec_train_persist16<true><<<T2V_NWG, P16_THREADS, p16_lds_bytes(T_in), stream>>>(a);
-    else k_dec_train_persist16<false><<<T2V_NWG, P16_THREADS, p16_lds_bytes(T_in), stream>>>(a);
+    if (T_in > T2V_AF_MAXT) k_dec_train_persist16<true><<<T2V_NWG, T2V_AF_THREADS, p16_lds_bytes(T_in), stream>>>(a);
+    else k_dec_train_persist16<false><<<T2V_NWG, T2V_AF_THREADS, p16_lds_bytes(T_in), stream>>>(a);
     return t2v_check_launch();
 }

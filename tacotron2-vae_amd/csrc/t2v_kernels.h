@@ -78,6 +78,20 @@ static inline unsigned* t2v_persist_fwd_begin(const t2v_dec_train_persist_weight
     return sync;
 }
 
+// What the two persistent forward kernels share with their attention role (t2v_attn_role_fwd.inc)
+#define T2V_AF_THREADS 512           // workgroup size of both kernels
+#define T2V_AF_SPIN 1500000u         // bound of their waits
+#define T2V_AF_MAXT 224              // LDS-resident W_q / processed-memory slices up to here
+#define T2V_AF_MAXT_LONG 560         // register-resident ones beyond (the LONG instantiations)
+#define T2V_AF_NTI_LONG 5            // 16-position tiles per wave of the long form: 8 waves x 5 x 16 = 640 >= 560
+// floats of the role's LDS carve; `tail`: what the kernel keeps between rss and flag (AF_TAIL)
+static inline size_t t2v_attn_fwd_lds_floats(int T_in, size_t tail) {
+    const size_t Tcap = t2v_tcap(T_in);
+    const bool lng = T_in > T2V_AF_MAXT;                 // W_q / processed memory in registers
+    return (lng ? 0 : 16 * 1028) + Tcap * 64 + (lng ? 0 : Tcap * 16) + 2 * (Tcap + 32) + Tcap + (lng ? T2V_CTX_PAD : 0) + T2V_H + 16 +
+           32 * 16 + 8 * 64 + 32 + 32 + tail + 4;
+}
+
 struct LstmFwdArgs {
     const float4* packA;
     const float4* packD;
