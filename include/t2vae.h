@@ -738,6 +738,26 @@ int t2v_tsne_gradient(const float* P, const float* Y, int N, float exaggeration,
 int t2v_tsne_run(const float* P, float* Y_inout, int N, int n_iter, float learning_rate, float* kl_trace, void* scratch,
                  void* stream);
 
+/* ------------------------------------------------------------------ YIN pitch tracker
+ * F0 tracks of B waveforms (csrc/f0.hip) on the mel front end's grid: 16 kHz, hop 256, integration window 1024, so frame t
+ * and mel frame t are the same instant.  y is (B, y_stride) fp32; row b has n[b] samples and n[b] / 256 + 1 frames; every
+ * sample index outside [0, n[b]) counts as 0 and nothing outside is read.  Per frame, with s = 256 t - 512:
+ *   d(tau) = sum_{j<1024} (x[s+j] - x[s+j+tau])^2 for tau = 1..tau_max, from the differences;
+ *   d'(tau) = d(tau) tau / sum_{k<=tau} d(k), 1 where that sum is 0;
+ *   tau* = the smallest tau in [tau_min, tau_max] with d' < threshold, moved to tau + 1 while d'(tau + 1) < d'(tau);
+ *   no such tau: the frame is unvoiced (no fall-back to the global minimum);
+ *   f0 = 16000 / (tau* + delta), delta = clamp((a - c) / (2 (a - 2b + c)), -1, 1) for a, b, c = d'(tau* - 1 .. tau* + 1) when
+ *   both neighbours lie in 1..tau_max and a - 2b + c > 0, else 0.
+ * f0 (B, out_stride): Hz, 0 where unvoiced; aperiodicity (B, out_stride): d'(tau*), 1 where unvoiced.  Columns from a row's
+ * frame count up to y_stride / 256 + 1 are written as 0 / 1; columns past that are not written.
+ * The order of every sum depends on (t, tau) alone: a row gives the same bits alone, in any batch and at any stride.
+ * A null pointer, B < 1, a stride < 1 or out_stride < y_stride / 256 + 1 is T2V_ERR_ARG; tau outside
+ * 1 <= tau_min < tau_max <= T2V_F0_MAX_LAG is T2V_ERR_DIMS.  The lengths are device data and the caller's to check on the
+ * host (1 <= n[b] <= y_stride); the kernel clamps a length to 0..y_stride, so none addresses outside the tensor. */
+#define T2V_F0_MAX_LAG 400          /* 40 Hz at 16 kHz */
+int t2v_f0_yin(const float* y, const int32_t* n, int y_stride, int B, int tau_min, int tau_max, float threshold, float* f0,
+               float* aperiodicity, int out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,12 +2,23 @@
 with its own recording by mel-spectral distortion with dynamic time warping (`Synthesizer.evaluate`, csrc/dtw.hip).
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
-                       [--batch_size N] [--condition ref|emotion] [--limit N] [--hparams ...]
+                       [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
 its cache next to the checkpoint).  OUT.json holds {"summary": evaluation.summarize(rows), "rows": [...]}, row i for
-filelist row i: path, dtw, n_frames, n_ref_frames, hit_max, emotion."""
+filelist row i: path, dtw, n_frames, n_ref_frames, hit_max, emotion.
+
+--prosody also asks whether the synthesised speech carries the style's pitch.  The checkpoint is loaded with the Griffin-Lim
+vocoder; each synthesised mel becomes a waveform, and a YIN pitch track (`t2v_hip.f0`, csrc/f0.hip: 60-500 Hz, one value per
+mel frame) is taken of it and of the recording.  Every row gains f0_median_hz / f0_ref_median_hz (median over voiced
+frames), f0_spread_st / f0_ref_spread_st (standard deviation of the pitch around that median, in semitones: the pitch
+range), voiced_share / voiced_ref_share and f0_shift_st (semitones from the recording's median to the synthesis's); the
+F0 values are null for a side with fewer than 5 voiced frames.  Every summary dict gains n_prosody (rows that stopped at the
+gate and have a shift), f0_shift_st_mean (signed), f0_shift_st_abs_mean, f0_spread_ratio_mean (synthesised spread over the
+recording's: far below 1 is a flat voice, which a DTW mel distance hardly sees), voiced_share_mean and
+voiced_ref_share_mean.  Mel -> Griffin-Lim itself moves a median by about 0.1 semitone (up to 0.3 measured on steady
+tones), and a steady pitch below 140 Hz can come back unvoiced."""
 import argparse
 import json
 
@@ -23,6 +34,9 @@ def build_arg_parser():
     p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="rows per synthesize_batch / mel_dtw call")
     p.add_argument('--condition', choices=CONDITIONS, default='ref', help="style from the row's recording or its emotion centroid")
     p.add_argument('--limit', type=int, default=None, help="score only the first N rows")
+    p.add_argument('--prosody', action='store_true',
+                   help="also track the pitch (YIN, 60-500 Hz) of each synthesised waveform (Griffin-Lim) and of its recording: "
+                        "rows gain median F0, spread in semitones, voiced share and f0_shift_st; the summary their means")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     return p
 
@@ -54,7 +68,7 @@ def main(argv=None):
     args = parse_args(argv)
     from evaluation import summarize
     from hparams import create_hparams
-    from synthesizer import Synthesizer
+    from synthesizer import GriffinLimVocoder, Synthesizer
     hp = create_hparams()
     hp.sampling_rate = 16000                 # the reference's Synthesizer() overrides, as synthesizer.py's command line
     hp.max_decoder_steps = 600
@@ -62,11 +76,13 @@ def main(argv=None):
         hp.parse(args.hparams)
     syn = Synthesizer(hp)
     if args.condition == 'emotion':
-        syn.load(args.load_path, filelist_path=args.filelist_path)
+        syn.load(args.load_path, vocoder='griffin_lim' if args.prosody else None, filelist_path=args.filelist_path)
     else:
         syn.load_checkpoint(args.load_path)
+        if args.prosody:
+            syn.vocoder = GriffinLimVocoder(syn.stft)
     rows = read_rows(args.filelist_path, args.limit)
-    records = syn.evaluate(rows, args.batch_size, args.condition)
+    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody)
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)]}, f, indent=1)

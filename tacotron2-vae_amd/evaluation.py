@@ -2,7 +2,14 @@
 
 A record is one filelist row scored by free-running synthesis: `dtw` (mel-spectral distortion with dynamic time warping
 against the ground-truth mel), `n_frames` (decoded), `n_ref_frames` (ground truth), `hit_max` (decoding ended at
-max_decoder_steps instead of at the gate) and `emotion` (label id of the filelist)."""
+max_decoder_steps instead of at the gate) and `emotion` (label id of the filelist).
+
+`evaluate(prosody=True)` adds the pitch of both sides (`t2v_hip.f0` on the Griffin-Lim waveform of the synthesised mel and
+on the recording): `f0_median_hz` / `f0_ref_median_hz` (median over voiced frames), `f0_spread_st` / `f0_ref_spread_st`
+(standard deviation of 12 log2(f0 / median) over voiced frames, in semitones), `voiced_share` / `voiced_ref_share` and
+`f0_shift_st` = 12 log2(f0_median_hz / f0_ref_median_hz).  The F0 values of a side with fewer than MIN_VOICED_FRAMES voiced
+frames are None, and so is the shift when either side's are."""
+import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
 
@@ -15,6 +22,52 @@ def _median(values):
 
 def _mean(values):
     return sum(values) / len(values) if values else None
+
+
+MIN_VOICED_FRAMES = 5
+PROSODY_KEYS = ('f0_median_hz', 'f0_ref_median_hz', 'f0_spread_st', 'f0_ref_spread_st', 'voiced_share', 'voiced_ref_share',
+                'f0_shift_st')
+
+
+def pitch_stats(track):
+    """(median Hz, spread in semitones, voiced share) of one F0 track (Hz per frame, 0 where unvoiced): the spread is the
+    standard deviation of 12 log2(f0 / median) over the voiced frames; median and spread are None under MIN_VOICED_FRAMES
+    voiced frames, the share is None for an empty track."""
+    track = [float(v) for v in track]
+    voiced = [v for v in track if v > 0.0]
+    share = len(voiced) / len(track) if track else None
+    if len(voiced) < MIN_VOICED_FRAMES:
+        return None, None, share
+    med = _median(voiced)
+    st = [12.0 * math.log2(v / med) for v in voiced]
+    mean = sum(st) / len(st)
+    return med, math.sqrt(sum((v - mean) ** 2 for v in st) / len(st)), share
+
+
+def prosody_fields(track, ref_track):
+    """the PROSODY_KEYS of one record from the F0 tracks of the synthesised waveform and of the recording (track: None when
+    the row has no waveform, i.e. fewer than the vocoder's 4 frames)"""
+    med, spread, share = pitch_stats(track) if track is not None else (None, None, None)
+    rmed, rspread, rshare = pitch_stats(ref_track)
+    return {'f0_median_hz': med, 'f0_ref_median_hz': rmed, 'f0_spread_st': spread, 'f0_ref_spread_st': rspread,
+            'voiced_share': share, 'voiced_ref_share': rshare,
+            'f0_shift_st': 12.0 * math.log2(med / rmed) if med is not None and rmed is not None else None}
+
+
+def _prosody_stats(records):
+    """Over the rows that stopped at the gate (a row that ran to max_decoder_steps has no end, and its waveform's tail says
+    nothing about the style): `n_prosody` of them have a pitch on both sides (`f0_shift_st` not None) and carry
+    `f0_shift_st_mean` (signed: a bias), `f0_shift_st_abs_mean` and `f0_spread_ratio_mean` (synthesised spread / recording's
+    spread, over the rows whose recording's spread is not 0; far below 1 is the flat-voice failure).  The voiced shares are
+    means over every stopped row that has one, so a model whose output is never voiced shows here and in n_prosody."""
+    stopped = [r for r in records if not r['hit_max']]
+    rows = [r for r in stopped if r.get('f0_shift_st') is not None]
+    return {'n_prosody': len(rows),
+            'f0_shift_st_mean': _mean([r['f0_shift_st'] for r in rows]),
+            'f0_shift_st_abs_mean': _mean([abs(r['f0_shift_st']) for r in rows]),
+            'f0_spread_ratio_mean': _mean([r['f0_spread_st'] / r['f0_ref_spread_st'] for r in rows if r['f0_ref_spread_st'] > 0]),
+            'voiced_share_mean': _mean([r['voiced_share'] for r in stopped if r.get('voiced_share') is not None]),
+            'voiced_ref_share_mean': _mean([r['voiced_ref_share'] for r in stopped if r.get('voiced_ref_share') is not None])}
 
 
 def _stats(records):
@@ -34,10 +87,15 @@ def _stats(records):
 
 def summarize(records, emotions=EMOTIONS):
     """{'overall': stats, 'by_emotion': {name: stats}} of evaluate() records; every name of `emotions` appears, with
-    n_rows = 0 and None statistics when it has no rows.  A label outside `emotions` is an error."""
+    n_rows = 0 and None statistics when it has no rows.  A label outside `emotions` is an error.  When the records carry
+    the prosody keys (evaluate(prosody=True)) every stats dict also holds those of `_prosody_stats`."""
     records = list(records)
     for r in records:
         if not 0 <= int(r['emotion']) < len(emotions):
             raise ValueError("emotion label %r outside 0..%d" % (r['emotion'], len(emotions) - 1))
-    return {'overall': _stats(records),
-            'by_emotion': {name: _stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}
+    prosody = any('f0_shift_st' in r for r in records)
+
+    def stats(rows):
+        return dict(_stats(rows), **_prosody_stats(rows)) if prosody else _stats(rows)
+    return {'overall': stats(records),
+            'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}

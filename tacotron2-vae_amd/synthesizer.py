@@ -87,9 +87,9 @@ class Synthesizer(object):
         audio_norm = (audio / self.hparams.max_wav_value).unsqueeze(0)
         return self.stft.mel_spectrogram(audio_norm.cuda())
 
-    def load_mels(self, paths):
-        """`load_mel` for several wavs in one ragged front-end call: returns (mels (B, 80, T_max) on the device, frame counts);
-        item b equals load_mel(paths[b]) on its first counts[b] frames, and what lies past them is padding."""
+    def load_wavs(self, paths):
+        """the wavs as one zero-padded batch on the device: (y (B, S_max) float32 in [-1, 1), sample counts); a wav whose rate
+        is not hparams.sampling_rate is a ValueError"""
         audios = []
         for path in paths:
             audio, sampling_rate = load_wav_to_torch(path)
@@ -97,13 +97,44 @@ class Synthesizer(object):
                 raise ValueError("{} SR doesn't match target {} SR".format(sampling_rate, self.hparams.sampling_rate))
             audios.append(audio / self.hparams.max_wav_value)
         if not audios:
-            raise ValueError("load_mels: no paths")
+            raise ValueError("load_wavs: no paths")
         n = [a.numel() for a in audios]
         y = torch.zeros(len(audios), max(n))
         for b, a in enumerate(audios):
             y[b, :n[b]] = a
-        mels = self.stft.mel_spectrogram(y.cuda(), torch.tensor(n, dtype=torch.int64))
+        return y.cuda(), n
+
+    def _mels_of(self, y, n):
+        mels = self.stft.mel_spectrogram(y, torch.tensor(n, dtype=torch.int64))
         return mels, [k // self.hparams.hop_length + 1 for k in n]
+
+    def load_mels(self, paths):
+        """`load_mel` for several wavs in one ragged front-end call: returns (mels (B, 80, T_max) on the device, frame counts);
+        item b equals load_mel(paths[b]) on its first counts[b] frames, and what lies past them is padding."""
+        paths = list(paths)
+        if not paths:
+            raise ValueError("load_mels: no paths")
+        return self._mels_of(*self.load_wavs(paths))
+
+    @torch.no_grad()
+    def pitch(self, paths, batch_size=64):
+        """F0 tracks of the wavs (`t2v_hip.f0`: YIN on the front end's frames, Hz, 0 where unvoiced), in input order: a list
+        of 1-D device tensors, paths[i]'s of its own samples // 256 + 1 frames, each what f0 gives for that wav alone.  The
+        wavs are sorted by length and run in ragged batches of at most batch_size."""
+        import t2v_hip
+        paths = list(paths)
+        if not paths:
+            raise ValueError("pitch: no paths")
+        if self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE or self.hparams.hop_length != t2v_hip.F0_HOP:
+            raise ValueError("pitch: the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
+                             % (t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
+        tracks = [None] * len(paths)
+        for idx in length_groups([wav_num_samples(p) for p in paths], batch_size):
+            y, n = self.load_wavs([paths[i] for i in idx])
+            hz = t2v_hip.f0(y, n)
+            for b, i in enumerate(idx):
+                tracks[i] = hz[b, :n[b] // t2v_hip.F0_HOP + 1]
+        return tracks
 
     @torch.no_grad()
     def latents(self, paths, batch_size=64):
@@ -294,15 +325,20 @@ class Synthesizer(object):
         return out
 
     @torch.no_grad()
-    def evaluate(self, rows, batch_size=8, condition='ref'):
+    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
         recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
         computed once, for the style and for the comparison); 'emotion': from the centroid of the row's emotion label, which
         needs `load()`.  The decoder consumes its seeds as len(rows) consecutive synthesize() calls.
         Returns one record per row, in input order: dtw, n_frames, n_ref_frames, hit_max (decoding ended at
-        max_decoder_steps, not at the gate; such a row is still scored) and emotion (the label id)."""
+        max_decoder_steps, not at the gate; such a row is still scored) and emotion (the label id).
+        prosody=True (needs the Griffin-Lim vocoder) adds the pitch of both sides to every record (evaluation.PROSODY_KEYS):
+        `t2v_hip.f0` on the waveform `synthesize_batch(paths=...)` would have written (the vocoder on the pre-Postnet mel, with
+        the same np.random draws) and on the recording's samples, which are the ones read for its mel.  A row decoded to
+        fewer than the vocoder's 4 frames has no waveform, and None on its synthesised side."""
         import t2v_hip
+        from evaluation import prosody_fields
         if condition not in ('ref', 'emotion'):
             raise ValueError("condition must be 'ref' or 'emotion', got %r" % (condition,))
         if batch_size < 1:
@@ -311,6 +347,11 @@ class Synthesizer(object):
             raise RuntimeError("evaluate: no model (load_checkpoint() or load() first)")
         if condition == 'emotion' and self.neu is None:
             raise RuntimeError("evaluate(condition='emotion') needs the emotion centroids: use load(), not load_checkpoint()")
+        if prosody and not isinstance(self.vocoder, GriffinLimVocoder):
+            raise RuntimeError("evaluate(prosody=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
+        if prosody and (self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE or self.hparams.hop_length != t2v_hip.F0_HOP):
+            raise ValueError("evaluate(prosody=True): the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
+                             % (t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
         rows = [(r[0], r[1], r[2], int(r[3])) for r in rows]
         one_hot = {0: (1.0, 0.0, 0.0, 0.0), 1: (0.0, 1.0, 0.0, 0.0), 2: (0.0, 0.0, 0.0, 1.0), 3: (0.0, 0.0, 1.0, 0.0)}
         for r in rows:                      # ratio order (neu, sad, hap, ang), label order EMOTIONS
@@ -322,11 +363,12 @@ class Synthesizer(object):
             group = rows[i0:i0 + batch_size]
             paths, texts = [r[0] for r in group], [r[1] for r in group]
             uniq = list(dict.fromkeys(paths))
-            ref_mels, n_uniq = self.load_mels(uniq)
+            y_uniq, samples_uniq = self.load_wavs(uniq)
+            ref_mels, n_uniq = self._mels_of(y_uniq, samples_uniq)
             if condition == 'ref':
-                _, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), (ref_mels, n_uniq))
+                mel, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), (ref_mels, n_uniq))
             else:
-                _, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, False, None, [one_hot[r[3]] for r in group])
+                mel, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, False, None, [one_hot[r[3]] for r in group])
             which = [uniq.index(p) for p in paths]
             truth = ref_mels if which == list(range(len(paths))) else ref_mels[torch.tensor(which, device=ref_mels.device)]
             n_ref = [n_uniq[k] for k in which]
@@ -337,6 +379,22 @@ class Synthesizer(object):
             for b, r in enumerate(group):
                 records.append({'dtw': dtw[b], 'n_frames': n[b], 'n_ref_frames': n_ref[b],
                                 'hit_max': bool(n[b] >= dec.max_decoder_steps and not fired[b]), 'emotion': r[3]})
+            if prosody:
+                # both sides' tracks side by side in one tensor: one copy to the host per group
+                tracks = [t2v_hip.f0(y_uniq, samples_uniq)]
+                can = [b for b in range(len(group)) if n[b] >= 4]
+                if can:
+                    sel = torch.tensor(can, device=mel.device)
+                    wavs = self.vocoder.batch(mel if len(can) == len(group) else mel[sel], [n[b] for b in can])
+                    y_syn = torch.zeros(len(can), max(w.numel() for w in wavs), device=mel.device)
+                    for k, w in enumerate(wavs):
+                        y_syn[k, :w.numel()] = w
+                    tracks.append(t2v_hip.f0(y_syn, [w.numel() for w in wavs]))
+                width = max(t.size(1) for t in tracks)
+                host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in tracks], 0).cpu().tolist()
+                for b in range(len(group)):
+                    syn_track = host[len(uniq) + can.index(b)][:n[b]] if b in can else None
+                    records[i0 + b].update(prosody_fields(syn_track, host[which[b]][:n_ref[b]]))
         return records
 
 

@@ -6,6 +6,7 @@ is missing, so a silent eager path can never stand in for the HIP kernels.
 """
 import collections
 import ctypes as C
+import math
 import os
 
 import torch
@@ -102,7 +103,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
            't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
            't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
-           't2v_tsne_gradient', 't2v_tsne_run')
+           't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin')
 
 
 def lib_path():
@@ -236,6 +237,7 @@ def load_library():
     lib.t2v_tsne_affinities.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
     lib.t2v_tsne_gradient.argtypes = [vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
     lib.t2v_tsne_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
+    lib.t2v_f0_yin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp]
     lib.t2v_conv1d_stat_blocks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_stat_blocks_bf16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -1583,6 +1585,57 @@ def mel_dtw(x, nx, y, ny):
         _check(lib.t2v_mel_dtw(_p(x[b0:]), _p(nx[b0:]), sx, _p(y[b0:]), _p(ny[b0:]), sy, nb, n_mel, _p(dist[b0:]), _p(scratch),
                                _stream()), 't2v_mel_dtw')
     return dist
+
+
+F0_MAX_LAG = 400                        # T2V_F0_MAX_LAG of include/t2vae.h
+F0_SAMPLE_RATE = 16000                  # the tracker's geometry is the front end's: 16 kHz, hop 256, window 1024
+F0_HOP = 256
+
+
+def f0_lags(fmin=60.0, fmax=500.0):
+    """(tau_min, tau_max) of f0(): floor(16000 / fmax), ceil(16000 / fmin); ValueError outside 40 <= fmin < fmax <= 1000"""
+    fmin, fmax = float(fmin), float(fmax)
+    if not 40.0 <= fmin < fmax <= 1000.0:
+        raise ValueError("f0: fmin %g, fmax %g; 40 <= fmin < fmax <= 1000 Hz is supported" % (fmin, fmax))
+    tau_min, tau_max = int(math.floor(F0_SAMPLE_RATE / fmax)), int(math.ceil(F0_SAMPLE_RATE / fmin))
+    if not 1 <= tau_min < tau_max <= F0_MAX_LAG:
+        raise ValueError("f0: fmin %g, fmax %g give the lags %d..%d; 1 <= tau_min < tau_max <= %d is supported"
+                         % (fmin, fmax, tau_min, tau_max, F0_MAX_LAG))
+    return tau_min, tau_max
+
+
+def f0(y, lengths, fmin=60.0, fmax=500.0, threshold=0.1, return_aperiodicity=False):
+    """YIN pitch tracks (csrc/f0.hip k_f0_yin): y (B, S) float32 CUDA tensor of 16 kHz waveforms, row b of lengths[b] samples
+    (a list, a CPU tensor or a device int tensor); samples outside a row's length count as 0 and are not read.  Frames as
+    the mel front end's: hop 256, lengths[b] // 256 + 1 of them, integration window 1024, lags floor(16000 / fmax) ..
+    ceil(16000 / fmin).  Returns f0 (B, max frame count) float32 in Hz, 0 where a frame is unvoiced (no lag with
+    d' < threshold) or past the row's frame count; with return_aperiodicity also d' at the chosen lag (1 where unvoiced or
+    past the end).  A row gives the same bits alone, in any batch and at any stride."""
+    lib = _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("f0: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("f0: empty input %s" % (tuple(y.shape),))
+    tau_min, tau_max = f0_lags(fmin, fmax)
+    threshold = float(threshold)
+    if not 0.0 < threshold < 1.0:
+        raise ValueError("f0: threshold %g must lie in (0, 1)" % threshold)
+    n = torch.as_tensor(lengths).reshape(-1).cpu()
+    if n.dtype.is_floating_point or n.dtype == torch.bool or n.numel() != B:
+        raise ValueError("f0: lengths must be %d integer sample counts, got %s" % (B, n.tolist()))
+    if int(n.min()) < 1 or int(n.max()) > S:
+        raise ValueError("f0: every length must be in 1..%d (samples stored per row), got %s" % (S, n.tolist()))
+    T = int(n.max()) // F0_HOP + 1
+    stride = S // F0_HOP + 1
+    y = _f32c(y)
+    hz = torch.empty(B, stride, device=y.device, dtype=torch.float32)
+    ap = torch.empty(B, stride, device=y.device, dtype=torch.float32)
+    _check(lib.t2v_f0_yin(_p(y), _p(n.to(torch.int32).to(y.device)), S, B, tau_min, tau_max, threshold, _p(hz), _p(ap), stride,
+                          _stream()), 't2v_f0_yin')
+    if T < stride:
+        hz, ap = hz[:, :T].contiguous(), ap[:, :T].contiguous()
+    return (hz, ap) if return_aperiodicity else hz
 
 
 TSNE_MAX_POINTS = 16384                 # T2V_TSNE_MAX_POINTS of include/t2vae.h: P is dense fp32, 1 GiB there
