@@ -758,6 +758,34 @@ int t2v_tsne_run(const float* P, float* Y_inout, int N, int n_iter, float learni
 int t2v_f0_yin(const float* y, const int32_t* n, int y_stride, int B, int tau_min, int tau_max, float threshold, float* f0,
                float* aperiodicity, int out_stride, void* stream);
 
+/* ------------------------------------------------------------------ attention alignment statistics
+ * Did the decoder read the sentence?  Per-row numbers of B alignment matrices (csrc/align.hip).  A is fp32 with element
+ * (b, t, j) at A[b a_stride_b + t a_stride_t + j] (B rows of N frames by T_in text positions); row b has n_frames[b] valid
+ * frames and n_text[b] valid text positions (device int32).  Only A[b, t < n, j < L] is read: padding may hold anything, and
+ * A is never written.  With p[t] = the lowest j < L that maximises A[b, t, j]:
+ *   path  (B, path_stride) int32: p[t] for t < n, -1 from n to the stride;
+ *   mass  (B, mass_stride) fp32:  sum_{t<n} A[b, t, j] for j < L, 0 from L to the stride;
+ *   focus (B) fp32:               (1/n) sum_t A[b, t, p[t]];
+ *   stats (B, 8) int32:           furthest = max_t p[t];  p_last = p[n-1];  n_back = #{t >= 1: p[t] < p[t-1]};
+ *                                 n_jump = #{t >= 1: p[t] - p[t-1] > max_jump};  longest_stall = the longest run of equal
+ *                                 consecutive p, in frames (>= 1);  n_uncovered = #{j < L: mass_j < cover_min};
+ *                                 longest_gap = the longest run of consecutive uncovered positions;  one reserved word, 0.
+ * One pass over A: a workgroup owns T2V_ALIGN_FRAMES consecutive frames of one row and leaves their argmax and its block's
+ * column sums; a second kernel adds the block partials in ascending block order.  No floating-point atomics: the order of
+ * every sum depends on (t, j) alone, so a row gives the same bits alone, in any batch, at any stride and with any padding.
+ * Any B, N, T_in >= 1.  The lengths are device data and the caller's to check on the host (1 <= n <= N, 1 <= L <= T_in); the
+ * kernels clamp them to 0..N and 0..T_in, so none addresses outside the tensor, and a row with n = 0 or L = 0 gets focus 0,
+ * all stats 0, path -1 and mass 0.
+ * A null pointer, B, N or T_in < 1, a_stride_t < T_in, a_stride_b < (N - 1) a_stride_t + T_in, path_stride < N or
+ * mass_stride < T_in is T2V_ERR_ARG; max_jump < 0 or cover_min <= 0 is T2V_ERR_DIMS.
+ * scratch: t2v_alignment_scratch_bytes(B, N, T_in) bytes of device memory, the caller's (0 for sizes that are refused). */
+#define T2V_ALIGN_FRAMES 16         /* frames per workgroup: the block of the column partial sums */
+size_t t2v_alignment_scratch_bytes(int B, int N, int T_in);
+int t2v_alignment_stats(const float* A, long long a_stride_b, long long a_stride_t, const int32_t* n_frames,
+                        const int32_t* n_text, int B, int N, int T_in, int max_jump, float cover_min, int32_t* path,
+                        int path_stride, float* mass, int mass_stride, float* focus, int32_t* stats, void* scratch,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

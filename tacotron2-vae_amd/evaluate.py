@@ -2,7 +2,7 @@
 with its own recording by mel-spectral distortion with dynamic time warping (`Synthesizer.evaluate`, csrc/dtw.hip).
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
-                       [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--hparams ...]
+                       [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment] [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
@@ -18,7 +18,19 @@ F0 values are null for a side with fewer than 5 voiced frames.  Every summary di
 gate and have a shift), f0_shift_st_mean (signed), f0_shift_st_abs_mean, f0_spread_ratio_mean (synthesised spread over the
 recording's: far below 1 is a flat voice, which a DTW mel distance hardly sees), voiced_share_mean and
 voiced_ref_share_mean.  Mel -> Griffin-Lim itself moves a median by about 0.1 semitone (up to 0.3 measured on steady
-tones), and a steady pitch below 140 Hz can come back unvoiced."""
+tones), and a steady pitch below 140 Hz can come back unvoiced.
+
+--alignment asks whether the decoder read the sentence: a skipped or repeated word, attention stuck on one symbol or a stop
+before the end of the text show in the attention alignment and nowhere else.  The alignments the decoder already returns are
+reduced on the device (`t2v_hip.alignment_stats`, csrc/align.hip); p[t] is the text position frame t attends most.  Every row
+gains focus (mean weight on p[t]), reach ((furthest p + 1) / symbols), end_reach ((p of the last frame + 1) / symbols),
+back_share and jump_share (steps back, and forward by more than 3 positions, over the transitions), stall_frames (longest run
+of frames on one position), uncovered_share (symbols whose summed weight stays under 0.5), gap_symbols (longest run of such
+symbols) and n_symbols.  Every summary dict gains, over the n_alignment rows that stopped at the gate, focus_mean, reach_mean,
+back_share_mean, jump_share_mean, uncovered_share_mean, stall_frames_mean / _max, gap_symbols_mean / _max, n_read_through and
+read_through_share: a row reads through when its last frame attends one of the last 4 symbols, fewer than 4 consecutive
+symbols stay uncovered and at most 2 steps go back.  These thresholds are choices, not calibrated on a trained model
+(DESIGN 7h); the per-row numbers are always written, so they can be cut again (evaluation.summarize takes the thresholds)."""
 import argparse
 import json
 
@@ -37,6 +49,10 @@ def build_arg_parser():
     p.add_argument('--prosody', action='store_true',
                    help="also track the pitch (YIN, 60-500 Hz) of each synthesised waveform (Griffin-Lim) and of its recording: "
                         "rows gain median F0, spread in semitones, voiced share and f0_shift_st; the summary their means")
+    p.add_argument('--alignment', action='store_true',
+                   help="also score the attention alignment of each synthesis (did the decoder read the text?): rows gain focus, "
+                        "reach, end_reach, back_share, jump_share, stall_frames, uncovered_share, gap_symbols and n_symbols; "
+                        "the summary their means and read_through_share")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     return p
 
@@ -82,11 +98,15 @@ def main(argv=None):
         if args.prosody:
             syn.vocoder = GriffinLimVocoder(syn.stft)
     rows = read_rows(args.filelist_path, args.limit)
-    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody)
+    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment)
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)]}, f, indent=1)
     print(json.dumps(summary, indent=1))
+    if args.alignment:
+        for name, st in summary['by_emotion'].items():
+            print("%s: dtw_mean %s, read_through_share %s (%d of %d rows that stopped)"
+                  % (name, st['dtw_mean'], st['read_through_share'], st['n_read_through'], st['n_alignment']))
     print("%s: %d utterances" % (args.out, len(records)))
 
 

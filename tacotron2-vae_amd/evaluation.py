@@ -8,7 +8,16 @@ max_decoder_steps instead of at the gate) and `emotion` (label id of the filelis
 on the recording): `f0_median_hz` / `f0_ref_median_hz` (median over voiced frames), `f0_spread_st` / `f0_ref_spread_st`
 (standard deviation of 12 log2(f0 / median) over voiced frames, in semitones), `voiced_share` / `voiced_ref_share` and
 `f0_shift_st` = 12 log2(f0_median_hz / f0_ref_median_hz).  The F0 values of a side with fewer than MIN_VOICED_FRAMES voiced
-frames are None, and so is the shift when either side's are."""
+frames are None, and so is the shift when either side's are.
+
+`evaluate(alignment=True)` adds what the attention alignment says about reading the text (`t2v_hip.alignment_stats` on the
+decoder's alignments; p[t] is the text position frame t attends most, L = `n_symbols`): `focus` (mean weight on p[t]), `reach`
+((furthest p + 1) / L), `end_reach` ((p of the last frame + 1) / L), `back_share` and `jump_share` (steps back, and steps
+forward by more than max_jump, over the n_frames - 1 transitions), `stall_frames` (longest run of frames on one position),
+`uncovered_share` (positions whose summed weight stays under cover_min, over L) and `gap_symbols` (longest run of such
+positions).  `summarize` cuts them into `read_through_share` with END_SLACK, GAP_MIN and BACK_SLACK.  Those three and the
+kernel's max_jump = 3 and cover_min = 0.5 are choices, not measurements (no trained checkpoint exists here); the raw per-row
+numbers are always in the records, so they can be cut again."""
 import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
@@ -70,6 +79,53 @@ def _prosody_stats(records):
             'voiced_ref_share_mean': _mean([r['voiced_ref_share'] for r in stopped if r.get('voiced_ref_share') is not None])}
 
 
+ALIGNMENT_KEYS = ('focus', 'reach', 'end_reach', 'back_share', 'jump_share', 'stall_frames', 'uncovered_share', 'gap_symbols',
+                  'n_symbols')
+END_SLACK = 3        # read through: the last frame attends one of the last END_SLACK + 1 text positions,
+GAP_MIN = 4          # no GAP_MIN consecutive positions stay uncovered,
+BACK_SLACK = 2       # and at most BACK_SLACK transitions go back.  Uncalibrated choices (module docstring).
+
+
+def alignment_fields(focus, stats_row, n_frames, n_symbols):
+    """the ALIGNMENT_KEYS of one record from one row of `t2v_hip.alignment_stats`: focus, the stats columns (furthest, p_last,
+    n_back, n_jump, longest_stall, n_uncovered, longest_gap, in t2v_hip.ALIGN_STATS order; a reserved eighth word is ignored),
+    the row's frame count and its number of text symbols.  The shares of back-steps and jumps are over the n_frames - 1
+    transitions, 0.0 for a single frame."""
+    furthest, p_last, n_back, n_jump, stall, n_unc, gap = [int(v) for v in list(stats_row)[:7]]
+    n, L = int(n_frames), int(n_symbols)
+    if n < 1 or L < 1:
+        raise ValueError("alignment_fields: %d frames, %d symbols; both must be >= 1" % (n, L))
+    steps = n - 1
+    return {'focus': float(focus), 'reach': (furthest + 1) / L, 'end_reach': (p_last + 1) / L,
+            'back_share': n_back / steps if steps else 0.0, 'jump_share': n_jump / steps if steps else 0.0,
+            'stall_frames': stall, 'uncovered_share': n_unc / L, 'gap_symbols': gap, 'n_symbols': L}
+
+
+def reads_through(record, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=BACK_SLACK):
+    """the last frame attends a position within end_slack of the text's end, fewer than gap_min consecutive positions stay
+    uncovered, and at most back_slack transitions go back"""
+    L = record['n_symbols']
+    n_back = round(record['back_share'] * (record['n_frames'] - 1))
+    return bool(round(record['end_reach'] * L) >= L - end_slack and record['gap_symbols'] < gap_min and n_back <= back_slack)
+
+
+def _alignment_stats(records, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=BACK_SLACK):
+    """Over the `n_alignment` rows that stopped at the gate (the alignment of a row that ran to max_decoder_steps has no end to
+    reach): the means of focus, reach, back_share, jump_share and uncovered_share, mean and max of stall_frames and
+    gap_symbols, and `n_read_through` / `read_through_share`, the rows `reads_through` accepts."""
+    rows = [r for r in records if not r['hit_max'] and 'n_symbols' in r]
+    out = {'n_alignment': len(rows)}
+    for k in ('focus', 'reach', 'back_share', 'jump_share', 'uncovered_share'):
+        out[k + '_mean'] = _mean([r[k] for r in rows])
+    for k in ('stall_frames', 'gap_symbols'):
+        out[k + '_mean'] = _mean([r[k] for r in rows])
+        out[k + '_max'] = max([r[k] for r in rows]) if rows else None
+    n_read = sum(1 for r in rows if reads_through(r, end_slack, gap_min, back_slack))
+    out['n_read_through'] = n_read
+    out['read_through_share'] = n_read / len(rows) if rows else None
+    return out
+
+
 def _stats(records):
     """`dtw_mean` / `dtw_median` cover only the `n_scored` rows whose decoding stopped at the gate: a row that ran to
     max_decoder_steps has no end to align, and its distance says nothing about the model but that it did not stop.  Those
@@ -85,17 +141,24 @@ def _stats(records):
             'length_ratio_mean': _mean([r['n_frames'] / r['n_ref_frames'] for r in records])}
 
 
-def summarize(records, emotions=EMOTIONS):
+def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=BACK_SLACK):
     """{'overall': stats, 'by_emotion': {name: stats}} of evaluate() records; every name of `emotions` appears, with
     n_rows = 0 and None statistics when it has no rows.  A label outside `emotions` is an error.  When the records carry
-    the prosody keys (evaluate(prosody=True)) every stats dict also holds those of `_prosody_stats`."""
+    the prosody keys (evaluate(prosody=True)) every stats dict also holds those of `_prosody_stats`; when they carry the
+    alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack."""
     records = list(records)
     for r in records:
         if not 0 <= int(r['emotion']) < len(emotions):
             raise ValueError("emotion label %r outside 0..%d" % (r['emotion'], len(emotions) - 1))
     prosody = any('f0_shift_st' in r for r in records)
+    alignment = any('n_symbols' in r for r in records)
 
     def stats(rows):
-        return dict(_stats(rows), **_prosody_stats(rows)) if prosody else _stats(rows)
+        out = _stats(rows)
+        if prosody:
+            out.update(_prosody_stats(rows))
+        if alignment:
+            out.update(_alignment_stats(rows, end_slack, gap_min, back_slack))
+        return out
     return {'overall': stats(records),
             'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}

@@ -324,8 +324,54 @@ class Synthesizer(object):
                     self._write_wav(paths[b], self.vocoder(mel[b:b + 1, :, :n[b]]))
         return out
 
+    @staticmethod
+    def _alignment_rows(al, n, lens, with_path=False):
+        """(one dict of evaluation.ALIGNMENT_KEYS per row, the host paths or None) of a group's alignments (B, N, T_in), frame
+        counts and text lengths: one `t2v_hip.alignment_stats` call and one copy to the host (focus rides along as an int32
+        bit pattern next to the stats, and the paths when asked for)"""
+        import t2v_hip
+        from evaluation import alignment_fields
+        r = t2v_hip.alignment_stats(al, n, lens)
+        parts = [r.stats, r.focus.view(torch.int32)[:, None]] + ([r.path] if with_path else [])
+        host = torch.cat(parts, 1).cpu()
+        focus = host[:, 8].contiguous().view(torch.float32).tolist()
+        stats = host[:, :8].tolist()
+        fields = [alignment_fields(focus[b], stats[b], n[b], lens[b]) for b in range(len(n))]
+        return fields, (host[:, 9:] if with_path else None)
+
     @torch.no_grad()
-    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False):
+    def alignment(self, texts, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0), batch_size=8):
+        """Did the decoder read these sentences?  The texts are synthesised as `synthesize_batch` does (same conditioning
+        arguments, batch_size texts at a time, in input order, the decoder's seeds as len(texts) synthesize() calls) and
+        their alignments scored by `t2v_hip.alignment_stats`.  Returns one dict per text: evaluation.ALIGNMENT_KEYS,
+        `n_frames`, and `durations`, a host list of n_symbols frame counts: how many frames attended each text symbol most
+        (the histogram of the argmax path; it sums to n_frames)."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
+        if self.model is None:
+            raise RuntimeError("alignment: no model (load_checkpoint() or load() first)")
+        texts = list(texts)
+        if condition_on_ref and (ref_audios is None or len(ref_audios) != len(texts)):
+            raise ValueError("condition_on_ref needs one reference audio per text")
+        per_text = len(ratios) and not np.isscalar(ratios[0])
+        if per_text and len(ratios) != len(texts):
+            raise ValueError("ratios: %d tuples for %d texts" % (len(ratios), len(texts)))
+        out = []
+        for i0 in range(0, len(texts), batch_size):
+            chunk = texts[i0:i0 + batch_size]
+            _, _, _, al, n_frames, lens = self._synthesize_ragged(
+                chunk, condition_on_ref, ref_audios[i0:i0 + batch_size] if condition_on_ref else None,
+                list(ratios[i0:i0 + batch_size]) if per_text else ratios)
+            n = n_frames.tolist()
+            fields, paths = self._alignment_rows(al, n, lens, with_path=True)
+            for b, f in enumerate(fields):
+                f['n_frames'] = n[b]
+                f['durations'] = torch.bincount(paths[b, :n[b]].long(), minlength=lens[b]).tolist()
+                out.append(f)
+        return out
+
+    @torch.no_grad()
+    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
         recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
@@ -336,7 +382,10 @@ class Synthesizer(object):
         prosody=True (needs the Griffin-Lim vocoder) adds the pitch of both sides to every record (evaluation.PROSODY_KEYS):
         `t2v_hip.f0` on the waveform `synthesize_batch(paths=...)` would have written (the vocoder on the pre-Postnet mel, with
         the same np.random draws) and on the recording's samples, which are the ones read for its mel.  A row decoded to
-        fewer than the vocoder's 4 frames has no waveform, and None on its synthesised side."""
+        fewer than the vocoder's 4 frames has no waveform, and None on its synthesised side.
+        alignment=True adds what the decoder's alignments say about reading the text (evaluation.ALIGNMENT_KEYS):
+        `t2v_hip.alignment_stats` on the alignments of each group, one call and one copy to the host per group.  It combines
+        freely with prosody and either condition; without it the records hold exactly the keys above."""
         import t2v_hip
         from evaluation import prosody_fields
         if condition not in ('ref', 'emotion'):
@@ -366,9 +415,9 @@ class Synthesizer(object):
             y_uniq, samples_uniq = self.load_wavs(uniq)
             ref_mels, n_uniq = self._mels_of(y_uniq, samples_uniq)
             if condition == 'ref':
-                mel, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), (ref_mels, n_uniq))
+                mel, mel_postnet, gate, al, n_frames, lens = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), (ref_mels, n_uniq))
             else:
-                mel, mel_postnet, gate, _, n_frames, _ = self._synthesize_ragged(texts, False, None, [one_hot[r[3]] for r in group])
+                mel, mel_postnet, gate, al, n_frames, lens = self._synthesize_ragged(texts, False, None, [one_hot[r[3]] for r in group])
             which = [uniq.index(p) for p in paths]
             truth = ref_mels if which == list(range(len(paths))) else ref_mels[torch.tensor(which, device=ref_mels.device)]
             n_ref = [n_uniq[k] for k in which]
@@ -379,6 +428,9 @@ class Synthesizer(object):
             for b, r in enumerate(group):
                 records.append({'dtw': dtw[b], 'n_frames': n[b], 'n_ref_frames': n_ref[b],
                                 'hit_max': bool(n[b] >= dec.max_decoder_steps and not fired[b]), 'emotion': r[3]})
+            if alignment:
+                for b, fields in enumerate(self._alignment_rows(al, n, lens)[0]):
+                    records[i0 + b].update(fields)
             if prosody:
                 # both sides' tracks side by side in one tensor: one copy to the host per group
                 tracks = [t2v_hip.f0(y_uniq, samples_uniq)]

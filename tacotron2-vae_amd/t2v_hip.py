@@ -103,7 +103,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
            't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
            't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
-           't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin')
+           't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes')
 
 
 def lib_path():
@@ -238,6 +238,10 @@ def load_library():
     lib.t2v_tsne_gradient.argtypes = [vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
     lib.t2v_tsne_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
     lib.t2v_f0_yin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp]
+    lib.t2v_alignment_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.t2v_alignment_scratch_bytes.restype = C.c_size_t
+    lib.t2v_alignment_stats.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp,
+                                        C.c_int, vp, C.c_int, vp, vp, vp, vp]
     lib.t2v_conv1d_stat_blocks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_stat_blocks_bf16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.t2v_conv1d_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -1636,6 +1640,83 @@ def f0(y, lengths, fmin=60.0, fmax=500.0, threshold=0.1, return_aperiodicity=Fal
     if T < stride:
         hz, ap = hz[:, :T].contiguous(), ap[:, :T].contiguous()
     return (hz, ap) if return_aperiodicity else hz
+
+
+ALIGN_FRAMES = 16                       # T2V_ALIGN_FRAMES of include/t2vae.h: frames per workgroup of k_align_scan
+ALIGN_STATS = ('furthest', 'p_last', 'n_back', 'n_jump', 'longest_stall', 'n_uncovered', 'longest_gap')
+
+
+class AlignmentStats(collections.namedtuple('AlignmentStats', 'path mass focus stats')):
+    """What alignment_stats() returns.  path (B, N) int32, mass (B, T_in) float32, focus (B,) float32, stats (B, 8) int32 with
+    the columns ALIGN_STATS and one reserved word; every column of stats is also an attribute (r.n_back: (B,) int32)."""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        if name in ALIGN_STATS:
+            return self.stats[:, ALIGN_STATS.index(name)]
+        raise AttributeError(name)
+
+
+class _AlignDeviceError(T2VHipError, ValueError):
+    """a CPU tensor handed to alignment_stats: a bad argument (ValueError) and, as everywhere here, no CPU path (T2VHipError)"""
+
+
+def _align_lengths(v, B, hi, what, unit):
+    """lengths of alignment_stats as a host int32 tensor, checked: a list, a CPU tensor or a device int tensor"""
+    v = torch.as_tensor(v).reshape(-1).cpu()
+    if v.dtype.is_floating_point or v.dtype == torch.bool or v.numel() != B:
+        raise ValueError("alignment_stats: %s must be %d integer %s counts, got %s" % (what, B, unit, v.tolist()))
+    if int(v.min()) < 1 or int(v.max()) > hi:
+        raise ValueError("alignment_stats: every %s must be in 1..%d (%s stored per row), got %s" % (what, hi, unit + 's', v.tolist()))
+    return v.to(torch.int32)
+
+
+def alignment_stats(alignments, n_frames, text_lengths, max_jump=3, cover_min=0.5):
+    """Did the decoder read the sentence?  (csrc/align.hip k_align_scan + k_align_finish.)  alignments: (B, N, T_in) float32
+    CUDA tensor of attention weights, row b valid on its first n_frames[b] frames and text_lengths[b] text positions (lists,
+    CPU tensors or device int tensors); nothing outside is read and the tensor is never written.  The last dimension must have
+    stride 1 (another one is a ValueError, not a copy); the other two strides are passed through, so a sliced view of a larger
+    tensor works without a copy.  With p[t] = the lowest j that maximises alignments[b, t, j] the AlignmentStats hold
+      path  (B, N) int32: p[t], -1 past n_frames[b];      mass (B, T_in) float32: the column sums over the valid frames, 0 past
+      text_lengths[b];      focus (B,) float32: the mean of alignments[b, t, p[t]];
+      stats (B, 8) int32, columns ALIGN_STATS: furthest (max p), p_last (p of the last frame), n_back (steps p[t] < p[t-1]),
+      n_jump (steps p[t] - p[t-1] > max_jump), longest_stall (longest run of equal consecutive p, frames), n_uncovered (text
+      positions with mass < cover_min), longest_gap (longest run of consecutive uncovered positions), and a reserved 0.
+    A row gives the same bits alone, in any batch, at any stride and with any padding.  max_jump = 3 and cover_min = 0.5 are
+    choices, not calibrated against a trained model.
+    The teacher-forced `alignments` of `model(x)` fit as they are, with its output_lengths and input_lengths."""
+    lib = load_library()
+    if not torch.is_tensor(alignments) or alignments.dim() != 3 or alignments.dtype != torch.float32:
+        raise ValueError("alignment_stats: alignments must be a float32 (B, N, T_in) tensor, got %s %s"
+                         % (getattr(alignments, 'dtype', type(alignments)), tuple(getattr(alignments, 'shape', ()))))
+    if not alignments.is_cuda:
+        raise _AlignDeviceError("alignment_stats: alignments %s live on %s; this path has no CPU fallback"
+                                % (tuple(alignments.shape), alignments.device))
+    B, N, T_in = alignments.shape
+    if B < 1 or N < 1 or T_in < 1:
+        raise ValueError("alignment_stats: empty input %s" % (tuple(alignments.shape),))
+    sb, st, sj = alignments.stride()
+    if (T_in > 1 and sj != 1) or (N > 1 and st < T_in) or (B > 1 and sb < (N - 1) * st + T_in):
+        raise ValueError("alignment_stats: strides %s of shape %s; the last dimension must have stride 1 and rows and frames may "
+                         "not overlap" % ((sb, st, sj), (B, N, T_in)))
+    st = max(st, T_in) if N == 1 else st              # a dimension of size 1 may report any stride
+    sb = max(sb, (N - 1) * st + T_in) if B == 1 else sb
+    if isinstance(max_jump, bool) or int(max_jump) != max_jump or max_jump < 0:
+        raise ValueError("alignment_stats: max_jump %r must be an integer >= 0" % (max_jump,))
+    cover_min = float(cover_min)
+    if not cover_min > 0.0 or math.isinf(cover_min):
+        raise ValueError("alignment_stats: cover_min %g must be a finite number > 0" % cover_min)
+    n = _align_lengths(n_frames, B, N, 'n_frames', 'frame').to(alignments.device)
+    L = _align_lengths(text_lengths, B, T_in, 'text_lengths', 'position').to(alignments.device)
+    dev = alignments.device
+    path = torch.empty(B, N, device=dev, dtype=torch.int32)
+    mass = torch.empty(B, T_in, device=dev, dtype=torch.float32)
+    focus = torch.empty(B, device=dev, dtype=torch.float32)
+    stats = torch.empty(B, 8, device=dev, dtype=torch.int32)
+    scratch = torch.empty(lib.t2v_alignment_scratch_bytes(B, N, T_in), device=dev, dtype=torch.uint8)
+    _check(lib.t2v_alignment_stats(_p(alignments), sb, st, _p(n), _p(L), B, N, T_in, int(max_jump), cover_min, _p(path), N,
+                                   _p(mass), T_in, _p(focus), _p(stats), _p(scratch), _stream()), 't2v_alignment_stats')
+    return AlignmentStats(path, mass, focus, stats)
 
 
 TSNE_MAX_POINTS = 16384                 # T2V_TSNE_MAX_POINTS of include/t2vae.h: P is dense fp32, 1 GiB there
