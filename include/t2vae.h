@@ -694,6 +694,30 @@ int t2v_griffin_lim(const float* mag, const float* angles, const int32_t* n_fram
  * row-major; mel (B, n_mel, t_stride) -> mag (B, 513, t_stride).  n_mel = 80 only. */
 int t2v_mel_to_magnitude(const float* mel, const float* pinv_basis, const int32_t* n_frames, int B, int t_stride,
                          int n_mel, float* mag, void* stream);
+/* t2v_griffin_lim_fast: fast Griffin-Lim (Perraudin, Balazs, Soendergaard 2013, in librosa's form).  With
+ * alpha = momentum / (1 + momentum) and tprev = 0 at the start, every iteration takes rebuilt = STFT(ISTFT(M phase)),
+ * a = rebuilt - alpha tprev, tprev <- rebuilt, and the new phase a / |a| (0 where |a| = 0).  One launch per iteration as
+ * t2v_griffin_lim; tprev is one complex spectrum per frame in scratch, read and written by that frame's workgroup alone.
+ * momentum = 0 is t2v_griffin_lim itself (the same launches); momentum outside [0, 1) is T2V_ERR_ARG.
+ * scratch: t2v_griffin_lim_fast_scratch_bytes. */
+size_t t2v_griffin_lim_fast_scratch_bytes(int B, int t_stride);
+int t2v_griffin_lim_fast(const float* mag, const float* angles, const int32_t* n_frames, int B, int t_stride, int n_fft,
+                         int hop, int n_iters, float momentum, const float* window, const float* tw512,
+                         const float* tw1024, void* scratch, float* out, int out_stride, void* stream);
+/* t2v_mel_to_magnitude_nnls: the non-negative least-squares inverse of the filterbank B (n_mel, 513) by projected gradient.
+ * Per frame, m = exp(mel) and M = max(P m, 0) as t2v_mel_to_magnitude; then n_iters times r = B M - m and
+ * M <- max(M - B^T r / lipschitz, 0), lipschitz = ||B||_2^2, which makes ||B M - m|| non-increasing.  No convergence test;
+ * n_iters = 0 gives t2v_mel_to_magnitude's bits.  B comes in two-tap form (device arrays): bin k lies in the filters
+ * tap_lo[k] and tap_lo[k] + 1 only (0 <= tap_lo <= n_mel - 2) with the weights tap_w0[k] and tap_w1[k], and filter f covers
+ * the bins filt_start[f] .. filt_start[f] + filt_len[f] - 1; the caller checks that this reproduces B exactly, the kernel
+ * clamps the indices so that none addresses outside its tables.  One launch, a workgroup per 16 frames with M and r in LDS
+ * for all iterations; no atomics, and the order of every sum depends on the filter or the bin alone, so a frame gives the
+ * same bits in any batch, at any stride and with any padding.  Frames past n_frames[b] are written 0 and their mel is not
+ * read.  n_mel = 80 only (T2V_ERR_DIMS); a null pointer, B < 1, t_stride < 1, n_iters < 0 or lipschitz <= 0: T2V_ERR_ARG. */
+int t2v_mel_to_magnitude_nnls(const float* mel, const float* pinv_basis, const int32_t* tap_lo, const float* tap_w0,
+                              const float* tap_w1, const int32_t* filt_start, const int32_t* filt_len, float lipschitz,
+                              int n_iters, const int32_t* n_frames, int B, int t_stride, int n_mel, float* mag,
+                              void* stream);
 
 /* ------------------------------------------------------------------ mel-spectral distortion with dynamic time warping
  * The distance between two log-mels of different lengths (csrc/dtw.hip), for scoring free-running synthesis against its

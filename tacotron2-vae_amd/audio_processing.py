@@ -24,13 +24,15 @@ def window_sumsquare(window, n_frames, hop_length=200, win_length=800, n_fft=800
     return x
 
 
-def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lengths=None):
+def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lengths=None, momentum=0.0):
     """magnitudes (B, 513, T) -> signal (B, (T-1)*256) after n_iters Griffin-Lim iterations on the device (t2v_griffin_lim).
     angles: initial phase (B, 513, T); None draws it as the reference does, from np.random on the host, so a caller who
     seeds np.random gets the reference's starting point.  lengths: optional per-utterance frame counts (samples past
-    (T_b-1)*256 are zero).  Every utterance needs T >= 4 frames.  The result is returned on the magnitudes' device."""
+    (T_b-1)*256 are zero).  Every utterance needs T >= 4 frames.  The result is returned on the magnitudes' device.
+    momentum in [0, 1): fast Griffin-Lim (librosa's default is 0.99); 0 is the reference's plain iteration."""
     import t2v_hip
     from stft import STFT
+    momentum = t2v_hip.check_momentum(momentum)
     if not isinstance(stft_fn, STFT):
         raise TypeError("griffin_lim runs on the HIP STFT (stft.STFT, e.g. TacotronSTFT.stft_fn), got %r" % type(stft_fn))
     if angles is None:
@@ -43,7 +45,7 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30, angles=None, lengths=None):
                          "(T-1)*256 samples by 512), got %s" % n)
     m = stft_fn.on_gpu(magnitudes)
     a = angles.to(m.device).float()
-    return t2v_hip.griffin_lim(m, a, lengths, stft_fn.tables(m.device), n_iters).to(magnitudes.device)
+    return t2v_hip.griffin_lim(m, a, lengths, stft_fn.tables(m.device), n_iters, momentum).to(magnitudes.device)
 
 
 def dynamic_range_compression(x, C=1, clip_val=1e-5):

@@ -14,6 +14,8 @@
 //                      window, FFT, magnitude replaced by M (phase kept), inverse FFT, window
 //   k_ola              frames -> signal (B, (T-1)*256): overlap-add / window_sumsquare, trimmed (256 threads, one per sample)
 //   k_mel_to_mag       M = max(P exp(mel), 0), P = pinv(mel_basis) (513 x 80)  (256 threads, 16 frames)
+//   k_gl_iter_fast     k_gl_iter with the momentum step of fast Griffin-Lim between the transform and the projection
+//   k_mel_to_mag_nnls  k_mel_to_mag followed by n_iters projected-gradient steps of min ||B M - m||, M >= 0, in LDS
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_fft.h"
@@ -289,6 +291,59 @@ __global__ __launch_bounds__(64) void k_gl_iter(const float* fin, const float* m
     spectrum_to_frame(ypair, z, tb.window, tb.tw512, tb.tw1024, fout + ((size_t)b * t_stride + t) * VC_NFFT, lane);
 }
 
+// ---------------------------------------------------------------- one fast Griffin-Lim iteration
+// k_gl_iter with the momentum step of Perraudin, Balazs, Soendergaard 2013 between the transform and the projection.  tprev
+// holds each frame's previous transform (B, t_stride, 513); a lane reads and writes only the bins it owns, so one buffer
+// serves.  first: tprev counts as 0 and is not read.  A kernel of its own, so that k_gl_iter keeps its instructions.
+__global__ __launch_bounds__(64) void k_gl_iter_fast(const float* fin, const float* mt, const int32_t* n_frames,
+                                                     int t_stride, VocoderTables tb, float* fout, float alpha, c32* tprev,
+                                                     int first) {
+    __shared__ c32 z[512];
+    const int t = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    const int T = frames_of(n_frames, b, t_stride);
+    if (t >= T) return;
+    const int N = VC_HOP * (T - 1);
+    const float* fr = fin + (size_t)b * t_stride * VC_NFFT;
+    // previous iterate's signal under this frame's reflect-padded window, windowed again, packed as 512 complex points
+    c32 v[8];
+    if (t >= 2 && t + 3 <= T) {         // no reflection: padded sample 256 t + n is OLA position 256 t + n
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int nn = lane + 64 * k;
+            const float2 y = ola_pair(fr, tb.window, VC_HOP * t + 2 * nn, T);
+            const float2 w2 = ((const float2*)tb.window)[nn];
+            v[k] = {y.x * w2.x, y.y * w2.y};
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int nn = lane + 64 * k;
+            const int q = VC_HOP * t + 2 * nn;
+            const float y0 = ola_at(fr, tb.window, reflect_to_ola(q, N), T);
+            const float y1 = ola_at(fr, tb.window, reflect_to_ola(q + 1, N), T);
+            v[k] = {y0 * tb.window[2 * nn], y1 * tb.window[2 * nn + 1]};
+        }
+    }
+    fft512(v, z, tb.tw512, lane);
+    // a = X - alpha tprev, tprev <- X; keep the phase of a, take the target magnitude
+    const float* mrow = mt + ((size_t)b * t_stride + t) * VC_NBIN;
+    c32* tp = tprev + ((size_t)b * t_stride + t) * VC_NBIN;
+    auto momentum = [&](int j, c32& x) {
+        const c32 p = first ? c32{0.f, 0.f} : tp[j];
+        tp[j] = x;
+        x = {x.x - alpha * p.x, x.y - alpha * p.y};
+    };
+    auto ypair = [&](int k, c32& yk, c32& yc) {
+        c32 xk, xc;
+        untangle(z[k], z[(512 - k) & 511], tb.tw1024[k], xk, xc);
+        momentum(k, xk);
+        if (k != 256) momentum(512 - k, xc);
+        yk = with_magnitude(xk, mrow[k]);
+        yc = k == 256 ? yk : with_magnitude(xc, mrow[512 - k]);
+    };
+    spectrum_to_frame(ypair, z, tb.window, tb.tw512, tb.tw1024, fout + ((size_t)b * t_stride + t) * VC_NFFT, lane);
+}
+
 // ---------------------------------------------------------------- frames -> signal
 __global__ __launch_bounds__(256) void k_ola(const float* frames, const int32_t* n_frames, int t_stride,
                                              const float* window, float* out, int out_stride) {
@@ -318,6 +373,80 @@ __global__ __launch_bounds__(256) void k_mel_to_mag(const float* mel, const floa
         float acc = 0.f;
         for (int m = 0; m < n_mel; ++m) acc = fmaf(pinv[k * n_mel + m], e[m][tt], acc);
         mag[((size_t)b * VC_NBIN + k) * t_stride + t] = t < T ? fmaxf(acc, 0.f) : 0.f;
+    }
+}
+
+// ---------------------------------------------------------------- mel -> linear magnitude, non-negative least squares
+// The filterbank in two-tap form: bin k lies in the filters lo[k] and lo[k] + 1 only, with the weights w0[k] and w1[k];
+// filter f covers the bins start[f] .. start[f] + len[f] - 1.  The host builds it from the basis and checks that it
+// reproduces the basis exactly; the kernel clamps the indices, so no table addresses outside LDS.
+struct NnlsTaps {
+    const int32_t* lo;       // (513) 0..78
+    const float* w0;         // (513)
+    const float* w1;         // (513)
+    const int32_t* start;    // (80)
+    const int32_t* len;      // (80)
+};
+
+// A workgroup owns VC_MEL_FR frames: m = exp(mel), M = max(P m, 0) as k_mel_to_mag, then n_iters times r = B M - m and
+// M <- max(M - B^T r / L, 0), with M and r in LDS throughout.  Thread i handles the frame i % 16 of every element it touches,
+// and every sum runs in an order that depends on the filter or the bin alone: a frame's bits depend on that frame alone.
+__global__ __launch_bounds__(256) void k_mel_to_mag_nnls(const float* mel, const float* pinv, NnlsTaps tp,
+                                                         const int32_t* n_frames, int t_stride, int n_iters, float inv_l,
+                                                         float* mag) {
+    __shared__ float M[VC_NBIN][VC_MEL_FR];
+    __shared__ float e[T2V_NMEL][VC_MEL_FR];
+    __shared__ float r[T2V_NMEL][VC_MEL_FR];
+    __shared__ float w0[VC_NBIN], w1[VC_NBIN];
+    __shared__ int lo[VC_NBIN], fs[T2V_NMEL], fl[T2V_NMEL];
+    const int b = blockIdx.y, t0 = blockIdx.x * VC_MEL_FR;
+    const int T = frames_of(n_frames, b, t_stride);
+    for (int i = threadIdx.x; i < T2V_NMEL * VC_MEL_FR; i += 256) {
+        const int m = i / VC_MEL_FR, tt = i % VC_MEL_FR, t = t0 + tt;
+        e[m][tt] = t < T ? expf(mel[((size_t)b * T2V_NMEL + m) * t_stride + t]) : 0.f;
+    }
+    for (int k = threadIdx.x; k < VC_NBIN; k += 256) {
+        lo[k] = min(max(tp.lo[k], 0), T2V_NMEL - 2);
+        w0[k] = tp.w0[k];
+        w1[k] = tp.w1[k];
+    }
+    if (threadIdx.x < T2V_NMEL) {
+        const int s = min(max(tp.start[threadIdx.x], 0), VC_NBIN);
+        fs[threadIdx.x] = s;
+        fl[threadIdx.x] = min(max(tp.len[threadIdx.x], 0), VC_NBIN - s);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int i = threadIdx.x; i < VC_NBIN * VC_MEL_FR; i += 256) {
+        const int k = i / VC_MEL_FR, tt = i % VC_MEL_FR;
+        float acc = 0.f;
+#pragma unroll 8
+        for (int m = 0; m < T2V_NMEL; ++m) acc = fmaf(pinv[k * T2V_NMEL + m], e[m][tt], acc);
+        M[k][tt] = t0 + tt < T ? fmaxf(acc, 0.f) : 0.f;
+    }
+    __syncthreads();
+    for (int it = 0; it < n_iters; ++it) {
+#pragma unroll 1
+        for (int i = threadIdx.x; i < T2V_NMEL * VC_MEL_FR; i += 256) {
+            const int f = i / VC_MEL_FR, tt = i % VC_MEL_FR;
+            const int k0 = fs[f], k1 = k0 + fl[f];
+            float acc = 0.f;
+            for (int k = k0; k < k1; ++k) acc = fmaf(lo[k] == f ? w0[k] : w1[k], M[k][tt], acc);
+            r[f][tt] = acc - e[f][tt];
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int i = threadIdx.x; i < VC_NBIN * VC_MEL_FR; i += 256) {
+            const int k = i / VC_MEL_FR, tt = i % VC_MEL_FR;
+            const int f = lo[k];
+            const float g = fmaf(w1[k], r[f + 1][tt], w0[k] * r[f][tt]);
+            M[k][tt] = fmaxf(fmaf(-g, inv_l, M[k][tt]), 0.f);
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < VC_NBIN * VC_MEL_FR; i += 256) {
+        const int k = i / VC_MEL_FR, tt = i % VC_MEL_FR, t = t0 + tt;
+        if (t < t_stride) mag[((size_t)b * VC_NBIN + k) * t_stride + t] = t < T ? M[k][tt] : 0.f;
     }
 }
 
@@ -404,5 +533,53 @@ extern "C" int t2v_mel_to_magnitude(const float* mel, const float* pinv_basis, c
     if (!mel || !pinv_basis || !n_frames || !mag || B < 1 || t_stride < 1) return T2V_ERR_ARG;
     dim3 grid((t_stride + VC_MEL_FR - 1) / VC_MEL_FR, B);
     k_mel_to_mag<<<grid, 256, 0, (hipStream_t)stream_>>>(mel, pinv_basis, n_frames, t_stride, n_mel, mag);
+    return t2v_check_launch();
+}
+
+extern "C" size_t t2v_griffin_lim_fast_scratch_bytes(int B, int t_stride) {
+    return t2v_griffin_lim_scratch_bytes(B, t_stride) + 4 * round_floats((size_t)B * t_stride * VC_NBIN * 2);
+}
+
+extern "C" int t2v_griffin_lim_fast(const float* mag, const float* angles, const int32_t* n_frames, int B, int t_stride,
+                                    int n_fft, int hop, int n_iters, float momentum, const float* window,
+                                    const float* tw512, const float* tw1024, void* scratch, float* out, int out_stride,
+                                    void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_fft != VC_NFFT || hop != VC_HOP) return T2V_ERR_DIMS;
+    VocoderTables tb;
+    if (tables(window, tw512, tw1024, tb) || !mag || !angles || !n_frames || !scratch || !out || B < 1 || t_stride < 1 ||
+        n_iters < 0 || !(momentum >= 0.f && momentum < 1.f))
+        return T2V_ERR_ARG;
+    if (momentum == 0.f)
+        return t2v_griffin_lim(mag, angles, n_frames, B, t_stride, n_fft, hop, n_iters, window, tw512, tw1024, scratch, out,
+                               out_stride, stream_);
+    const size_t fr = round_floats((size_t)B * t_stride * VC_NFFT);
+    float* frames[2] = {(float*)scratch, (float*)scratch + fr};
+    float* mt = (float*)scratch + 2 * fr;
+    c32* tprev = (c32*)(mt + round_floats((size_t)B * t_stride * VC_NBIN));
+    const float alpha = momentum / (1.f + momentum);
+    const dim3 grid(t_stride, B);
+    k_spec_to_frames<<<grid, 64, 0, stream>>>(mag, angles, n_frames, t_stride, tb, frames[0], mt);
+    if (int rc = t2v_check_launch()) return rc;
+    for (int i = 0; i < n_iters; ++i) {
+        k_gl_iter_fast<<<grid, 64, 0, stream>>>(frames[i & 1], mt, n_frames, t_stride, tb, frames[(i + 1) & 1], alpha, tprev,
+                                                i == 0);
+        if (int rc = t2v_check_launch()) return rc;
+    }
+    return ola(frames[n_iters & 1], n_frames, B, t_stride, window, out, out_stride, stream);
+}
+
+extern "C" int t2v_mel_to_magnitude_nnls(const float* mel, const float* pinv_basis, const int32_t* tap_lo,
+                                         const float* tap_w0, const float* tap_w1, const int32_t* filt_start,
+                                         const int32_t* filt_len, float lipschitz, int n_iters, const int32_t* n_frames,
+                                         int B, int t_stride, int n_mel, float* mag, void* stream_) {
+    if (n_mel != T2V_NMEL) return T2V_ERR_DIMS;
+    if (!mel || !pinv_basis || !tap_lo || !tap_w0 || !tap_w1 || !filt_start || !filt_len || !n_frames || !mag || B < 1 ||
+        t_stride < 1 || n_iters < 0 || !(lipschitz > 0.f))
+        return T2V_ERR_ARG;
+    const NnlsTaps tp = {tap_lo, tap_w0, tap_w1, filt_start, filt_len};
+    dim3 grid((t_stride + VC_MEL_FR - 1) / VC_MEL_FR, B);
+    k_mel_to_mag_nnls<<<grid, 256, 0, (hipStream_t)stream_>>>(mel, pinv_basis, tp, n_frames, t_stride, n_iters,
+                                                              1.f / lipschitz, mag);
     return t2v_check_launch();
 }

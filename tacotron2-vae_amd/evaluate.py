@@ -49,6 +49,8 @@ def build_arg_parser():
     p.add_argument('--prosody', action='store_true',
                    help="also track the pitch (YIN, 60-500 Hz) of each synthesised waveform (Griffin-Lim) and of its recording: "
                         "rows gain median F0, spread in semitones, voiced share and f0_shift_st; the summary their means")
+    p.add_argument('--vocoder', choices=['griffin_lim', 'griffin_lim_fast'], default='griffin_lim',
+                   help="the vocoder of --prosody (griffin_lim_fast: momentum 0.99 and NNLS mel inversion); unused without it")
     p.add_argument('--alignment', action='store_true',
                    help="also score the attention alignment of each synthesis (did the decoder read the text?): rows gain focus, "
                         "reach, end_reach, back_share, jump_share, stall_frames, uncovered_share, gap_symbols and n_symbols; "
@@ -92,11 +94,11 @@ def main(argv=None):
         hp.parse(args.hparams)
     syn = Synthesizer(hp)
     if args.condition == 'emotion':
-        syn.load(args.load_path, vocoder='griffin_lim' if args.prosody else None, filelist_path=args.filelist_path)
+        syn.load(args.load_path, vocoder=args.vocoder if args.prosody else None, filelist_path=args.filelist_path)
     else:
         syn.load_checkpoint(args.load_path)
         if args.prosody:
-            syn.vocoder = GriffinLimVocoder(syn.stft)
+            syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft)
     rows = read_rows(args.filelist_path, args.limit)
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment)
     summary = summarize(records)

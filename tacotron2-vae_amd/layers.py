@@ -127,6 +127,7 @@ class TacotronSTFT(nn.Module):
         self._dev_tables = {}
         self.stft_fn = STFT(filter_length, hop_length, win_length)      # no state: state_dict keys stay ['mel_basis']
         self._pinv = {}
+        self._taps = {}
 
     def _tables(self, device):
         key = str(device)
@@ -158,15 +159,23 @@ class TacotronSTFT(nn.Module):
     def spectral_de_normalize(self, magnitudes):
         return dynamic_range_decompression(magnitudes)
 
-    def mel_to_magnitude(self, mel, lengths=None):
+    def mel_to_magnitude(self, mel, lengths=None, method='pinv', n_iters=100):
         """log mel (B, 80, T) -> linear magnitude (B, 513, T) = max(pinv(mel_basis) exp(mel), 0) on the device (the reference
         has no mel -> linear map; this is the least-squares inverse of the filterbank, clamped at 0).  lengths: optional
-        per-utterance frame counts.  The pseudo-inverse is computed once per device on the host in fp64."""
+        per-utterance frame counts.  The pseudo-inverse is computed once per device on the host in fp64.
+        method='nnls': from there, n_iters projected-gradient steps of the non-negative least-squares problem
+        min ||mel_basis M - exp(mel)||, M >= 0 (t2v_hip.mel_to_magnitude_nnls); the clamped pseudo-inverse does not solve it."""
         import numpy as np
         import t2v_hip
+        if method not in ('pinv', 'nnls'):
+            raise ValueError("mel_to_magnitude: method must be 'pinv' or 'nnls', got %r" % (method,))
         md = STFT.on_gpu(mel)
         key = str(md.device)
         if key not in self._pinv:
             pinv = np.linalg.pinv(self.mel_basis.detach().cpu().double().numpy())
             self._pinv[key] = torch.from_numpy(pinv.astype(np.float32)).to(md.device)
-        return t2v_hip.mel_to_magnitude(md, lengths, self._pinv[key]).to(mel.device)
+        if method == 'pinv':
+            return t2v_hip.mel_to_magnitude(md, lengths, self._pinv[key]).to(mel.device)
+        if key not in self._taps:
+            self._taps[key] = t2v_hip.two_tap_basis(self.mel_basis, md.device)
+        return t2v_hip.mel_to_magnitude_nnls(md, lengths, self._taps[key], self._pinv[key], n_iters).to(mel.device)

@@ -5,8 +5,8 @@ mel from text conditioned either on a reference utterance or on an emotion-ratio
 Differences by design:
 * the decode loop runs in the HIP inference session (`Decoder.inference`, 4 launches per frame) instead of
   Python-stepping `decode()`; the stepwise API is still there for callers that want it;
-* the vocoder is pluggable: any callable mel(1,80,T) -> waveform, or `vocoder='griffin_lim'` for the built-in
-  GriffinLimVocoder.  WaveGlow is an unpinned submodule of the reference and is out of scope here; without a vocoder
+* the vocoder is pluggable: any callable mel(1,80,T) -> waveform, or `vocoder='griffin_lim'` / `'griffin_lim_fast'` for
+  the built-in GriffinLimVocoder.  WaveGlow is an unpinned submodule of the reference and is out of scope here; without a vocoder
   `synthesize` writes the mel as `<path>.npy`.
 """
 import os
@@ -37,18 +37,41 @@ def wav_num_samples(path):
     return len(read(path, mmap=True)[1])
 
 
+VOCODERS = ('griffin_lim', 'griffin_lim_fast')
+
+
 class GriffinLimVocoder(object):
     """mel (B, 80, T) -> waveform (B, (T-1)*256) on the device: `stft.mel_to_magnitude` (pinv of the mel filterbank,
     clamped at 0) and n_iters Griffin-Lim iterations on `stft.stft_fn` (audio_processing.griffin_lim, initial phase from
-    np.random).  The samples are not clipped: Griffin-Lim's output may exceed +-1 slightly.  Needs T >= 4 frames."""
+    np.random).  The samples are not clipped: Griffin-Lim's output may exceed +-1 slightly.  Needs T >= 4 frames.
+    momentum > 0: fast Griffin-Lim; inversion='nnls': the non-negative least-squares inverse of the filterbank
+    (inversion_iters projected-gradient steps from the clamped pinv).  Neither changes which phases are drawn."""
 
-    def __init__(self, stft, n_iters=60):
+    def __init__(self, stft, n_iters=60, momentum=0.0, inversion='pinv', inversion_iters=100):
+        from t2v_hip import check_momentum
+        if inversion not in ('pinv', 'nnls'):
+            raise ValueError("GriffinLimVocoder: inversion must be 'pinv' or 'nnls', got %r" % (inversion,))
         self.stft, self.n_iters = stft, n_iters
+        self.momentum, self.inversion, self.inversion_iters = check_momentum(momentum), inversion, inversion_iters
+
+    @classmethod
+    def named(cls, name, stft):
+        """the vocoder behind load(vocoder=name) and the command lines' --vocoder"""
+        if name == 'griffin_lim':
+            return cls(stft)
+        if name == 'griffin_lim_fast':
+            return cls(stft, momentum=0.99, inversion='nnls')
+        raise ValueError("unknown vocoder %r (a callable, or one of %s)" % (name, ', '.join(repr(v) for v in VOCODERS)))
+
+    def _magnitudes(self, mel, lengths):
+        if self.inversion == 'pinv':
+            return self.stft.mel_to_magnitude(mel, lengths)
+        return self.stft.mel_to_magnitude(mel, lengths, self.inversion, self.inversion_iters)
 
     def __call__(self, mel, lengths=None):
         from audio_processing import griffin_lim
-        magnitudes = self.stft.mel_to_magnitude(mel, lengths)
-        return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths)
+        magnitudes = self._magnitudes(mel, lengths)
+        return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths, momentum=self.momentum)
 
     def batch(self, mel, lengths):
         """A ragged batch in one set of launches, item by item as `self(mel[b:b+1, :, :lengths[b]])` would give it: the
@@ -60,8 +83,9 @@ class GriffinLimVocoder(object):
         angles = np.zeros((B, 513, T), dtype=np.float32)
         for b, nb in enumerate(n):
             angles[b, :, :nb] = np.angle(np.exp(2j * np.pi * np.random.rand(1, 513, nb)))[0]
-        magnitudes = self.stft.mel_to_magnitude(mel, n)
-        wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, angles=torch.from_numpy(angles), lengths=n)
+        magnitudes = self._magnitudes(mel, n)
+        wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, angles=torch.from_numpy(angles), lengths=n,
+                          momentum=self.momentum)
         return [wav[b, :(nb - 1) * 256] for b, nb in enumerate(n)]
 
 
@@ -183,9 +207,12 @@ class Synthesizer(object):
         """Positional order of the reference (synthesizer.py:74: `load(checkpoint_path, waveglow_path)`, called from
         app.py:161).  waveglow_path: a WaveGlow checkpoint `{'model': module}` exactly as the reference loads it
         (needs the `waveglow` package importable: it is an un-vendored submodule of the reference); `vocoder`: any
-        callable mel (1,80,T) -> audio instead, or 'griffin_lim' for GriffinLimVocoder(self.stft).  A callable passed in
-        the second position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
+        callable mel (1,80,T) -> audio instead, or 'griffin_lim' for GriffinLimVocoder(self.stft), or 'griffin_lim_fast' for
+        the same with momentum 0.99 and the non-negative least-squares mel inversion.  A callable passed in the second
+        position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
         (`latents`), when there is no centroid cache yet."""
+        if isinstance(vocoder, str):
+            vocoder = GriffinLimVocoder.named(vocoder, self.stft)       # an unknown name fails before anything is loaded
         self.load_checkpoint(checkpoint_path)
         if callable(waveglow_path) and vocoder is None:
             vocoder, waveglow_path = waveglow_path, None
@@ -199,10 +226,6 @@ class Synthesizer(object):
             if vocoder is None:
                 waveglow = self.waveglow
                 vocoder = lambda mel: waveglow.infer(mel, sigma=0.666)      # reference synthesizer.py:163
-        if isinstance(vocoder, str):
-            if vocoder != 'griffin_lim':
-                raise ValueError("unknown vocoder %r (a callable, or 'griffin_lim')" % vocoder)
-            vocoder = GriffinLimVocoder(self.stft)
         self.vocoder = vocoder
         npz_path = self.centroid_cache_path(checkpoint_path, filelist_path)
         if os.path.exists(npz_path):
@@ -464,7 +487,8 @@ def build_arg_parser():
     p.add_argument('--text', action='append', default=[], help="a sentence (repeatable)")
     p.add_argument('--text_file', default=None, help="one sentence per line (after the --text sentences)")
     p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="texts per synthesize_batch call")
-    p.add_argument('--vocoder', choices=['griffin_lim'], default=None, help="without it the post-net mels are written")
+    p.add_argument('--vocoder', choices=list(VOCODERS), default=None,
+                   help="without it the post-net mels are written; griffin_lim_fast: momentum 0.99 and NNLS mel inversion")
     p.add_argument('--ratios', default='1,0,0,0', help="emotion mix neu,sad,hap,ang")
     p.add_argument('--ref_audio', default=None, help="condition every text on this reference wav instead of --ratios")
     p.add_argument('--filelist_path', default='./web/static/uploads/koemo_spk_emo_all_test.txt',

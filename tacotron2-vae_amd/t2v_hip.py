@@ -103,7 +103,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
            't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
            't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
-           't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes')
+           't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes',
+           't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes')
 
 
 def lib_path():
@@ -229,6 +230,11 @@ def load_library():
     lib.t2v_griffin_lim.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
                                     vp]
     lib.t2v_mel_to_magnitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.t2v_mel_to_magnitude_nnls.argtypes = [vp] * 7 + [C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.t2v_griffin_lim_fast_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    lib.t2v_griffin_lim_fast_scratch_bytes.restype = C.c_size_t
+    lib.t2v_griffin_lim_fast.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp,
+                                         vp, C.c_int, vp]
     lib.t2v_mel_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_mel_dtw_scratch_bytes.restype = C.c_size_t
     lib.t2v_mel_dtw.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
@@ -1514,10 +1520,12 @@ def istft(mag, phase, n_frames, tables):
     return out
 
 
-def griffin_lim(mag, angles, n_frames, tables, n_iters):
+def griffin_lim(mag, angles, n_frames, tables, n_iters, momentum=0.0):
     """audio_processing.griffin_lim on device: one inverse from `angles`, n_iters fused iterations (k_gl_iter, one launch
     each, no host synchronisation), final overlap-add.  mag, angles: (B,513,T) float32 CUDA tensors; every utterance needs
-    >= 4 frames (the reflect pad of each iteration's transform).  Returns (B, (T-1)*256), zero past each length."""
+    >= 4 frames (the reflect pad of each iteration's transform).  Returns (B, (T-1)*256), zero past each length.
+    momentum in (0, 1): fast Griffin-Lim (t2v_griffin_lim_fast, k_gl_iter_fast); 0 is the plain iteration's own entry."""
+    momentum = check_momentum(momentum)
     lib = _require_gpu(mag, angles)
     B, nb, T = mag.shape
     if nb != 513 or angles.shape != mag.shape:
@@ -1525,11 +1533,25 @@ def griffin_lim(mag, angles, n_frames, tables, n_iters):
     mag, angles = _f32c(mag), _f32c(angles)
     n = _frame_counts(n_frames, B, T, mag.device, min_frames=4)
     out = torch.empty(B, 256 * (T - 1), device=mag.device, dtype=torch.float32)
-    scratch = torch.empty(lib.t2v_griffin_lim_scratch_bytes(B, T), device=mag.device, dtype=torch.uint8)
-    _check(lib.t2v_griffin_lim(_p(mag), _p(angles), _p(n), B, T, 1024, 256, int(n_iters), _p(tables['window']),
-                               _p(tables['tw512']), _p(tables['tw1024']), _p(scratch), _p(out), out.size(1), _stream()),
-           't2v_griffin_lim')
+    if momentum == 0.0:
+        scratch = torch.empty(lib.t2v_griffin_lim_scratch_bytes(B, T), device=mag.device, dtype=torch.uint8)
+        _check(lib.t2v_griffin_lim(_p(mag), _p(angles), _p(n), B, T, 1024, 256, int(n_iters), _p(tables['window']),
+                                   _p(tables['tw512']), _p(tables['tw1024']), _p(scratch), _p(out), out.size(1), _stream()),
+               't2v_griffin_lim')
+        return out
+    scratch = torch.empty(lib.t2v_griffin_lim_fast_scratch_bytes(B, T), device=mag.device, dtype=torch.uint8)
+    _check(lib.t2v_griffin_lim_fast(_p(mag), _p(angles), _p(n), B, T, 1024, 256, int(n_iters), momentum,
+                                    _p(tables['window']), _p(tables['tw512']), _p(tables['tw1024']), _p(scratch), _p(out),
+                                    out.size(1), _stream()), 't2v_griffin_lim_fast')
     return out
+
+
+def check_momentum(momentum):
+    """fast Griffin-Lim's momentum as a float in [0, 1); ValueError otherwise"""
+    m = float(momentum)
+    if not 0.0 <= m < 1.0:
+        raise ValueError("griffin_lim: momentum must be in [0, 1), got %r" % (momentum,))
+    return m
 
 
 def mel_to_magnitude(mel, n_frames, pinv_basis):
@@ -1542,6 +1564,61 @@ def mel_to_magnitude(mel, n_frames, pinv_basis):
     mag = torch.empty(B, 513, T, device=mel.device, dtype=torch.float32)
     _check(lib.t2v_mel_to_magnitude(_p(mel), _p(_f32c(pinv_basis)), _p(n), B, T, n_mel, _p(mag), _stream()),
            't2v_mel_to_magnitude')
+    return mag
+
+
+def two_tap_basis(mel_basis, device=None):
+    """The mel filterbank (80, 513) in the two-tap form of k_mel_to_mag_nnls, with L = ||B||_2^2 (fp64 on the host).  With
+    Slaney triangles a bin lies in at most two filters, and those are adjacent: per bin the lower filter `lo` (0..78) and the
+    weights w0 = B[lo, k], w1 = B[lo + 1, k]; per filter the range of bins it covers.  The form is checked to reproduce the
+    basis exactly; a basis without that structure is a ValueError.  Returns a dict of tensors on `device` (the basis' own
+    when None) and the float 'L'."""
+    import numpy as np
+    B = mel_basis.detach().cpu().float().numpy()
+    if B.ndim != 2 or B.shape != (80, 513):
+        raise ValueError("two_tap_basis: the mel basis must be (80, 513), got %s" % (tuple(B.shape),))
+    if not np.isfinite(B).all() or not B.any():
+        raise ValueError("two_tap_basis: the mel basis must be finite and not all zero")
+    k = np.arange(513)
+    nz = B != 0
+    first = np.where(nz.any(0), nz.argmax(0), 0)
+    lo = np.minimum(first, 78).astype(np.int32)
+    w0, w1 = B[lo, k], B[lo + 1, k]
+    start = np.where(nz.any(1), nz.argmax(1), 0).astype(np.int32)
+    last = np.where(nz.any(1), 512 - nz[:, ::-1].argmax(1), -1)
+    length = (last - start + 1).clip(min=0).astype(np.int32)
+    back = np.zeros_like(B)                 # what the kernel multiplies by: filter f takes w0 where lo == f, else w1
+    for f in range(80):
+        r = slice(int(start[f]), int(start[f] + length[f]))
+        back[f, r] = np.where(lo[r] == f, w0[r], w1[r])
+    if not np.array_equal(back, B):
+        bad = np.argwhere(back != B)[0]
+        raise ValueError("two_tap_basis: the mel basis is not a bank of overlapping-by-two filters (every bin in at most two "
+                         "adjacent filters); first difference at filter %d, bin %d" % (bad[0], bad[1]))
+    dev = mel_basis.device if device is None else device
+    t = {n: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for n, v in
+         (('lo', lo), ('w0', w0), ('w1', w1), ('start', start), ('len', length))}
+    t['L'] = float(np.linalg.norm(B.astype(np.float64), 2) ** 2)
+    return t
+
+
+def mel_to_magnitude_nnls(mel, n_frames, mel_basis, pinv_basis, n_iters=100):
+    """Non-negative least-squares inverse of the mel filterbank on device (k_mel_to_mag_nnls): from mel_to_magnitude's
+    max(pinv exp(mel), 0), n_iters projected-gradient steps M <- max(M - B^T (B M - m) / L, 0) in one launch.  mel: (B,80,T)
+    float32 CUDA tensor; mel_basis: the (80, 513) filterbank, or what two_tap_basis made of it (a caller with many calls
+    builds that once); pinv_basis: (513,80) device tensor.  Returns (B,513,T), zero past each utterance's frame count;
+    n_iters = 0 gives mel_to_magnitude's bits."""
+    lib = _require_gpu(mel, pinv_basis)
+    if int(n_iters) < 0:
+        raise ValueError("mel_to_magnitude_nnls: n_iters must be >= 0, got %r" % (n_iters,))
+    B, n_mel, T = mel.shape
+    mel = _f32c(mel)
+    taps = mel_basis if isinstance(mel_basis, dict) else two_tap_basis(mel_basis, mel.device)
+    n = _frame_counts(n_frames, B, T, mel.device)
+    mag = torch.empty(B, 513, T, device=mel.device, dtype=torch.float32)
+    _check(lib.t2v_mel_to_magnitude_nnls(_p(mel), _p(_f32c(pinv_basis)), _p(taps['lo']), _p(taps['w0']), _p(taps['w1']),
+                                         _p(taps['start']), _p(taps['len']), taps['L'], int(n_iters), _p(n), B, T, n_mel,
+                                         _p(mag), _stream()), 't2v_mel_to_magnitude_nnls')
     return mag
 
 
