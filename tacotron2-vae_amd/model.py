@@ -265,6 +265,33 @@ class Decoder(nn.Module):
         self.attention_weights, self.attention_weights_cum = s.AL[t + 1], s.ACUM[t + 1]
         return s.MEL[t], s.GATE[t].unsqueeze(1), s.AL[t + 1]
 
+    def _run_to_end(self, s, chunk, persistent, seed):
+        """Run the prepared session s (PRE[0] holds Prenet(go frame)) until every gate has fired or max_decoder_steps; returns
+        the stop flag as it was last read (>= s.max_steps: no stop).  One read of the flag, one synchronisation, per launch."""
+        if persistent is None:
+            persistent = os.environ.get('T2V_DECODE_PERSISTENT', '1') != '0'
+        stop, t = s.max_steps, 0
+        if persistent and s.persistent_supported():
+            # one persistent launch for the whole utterance: weights resident on chip, state handed between CUs as
+            # tagged granules, the loop ends on the frame the gate fires
+            s.run_persistent(self.gate_threshold, drop_rate, seed)
+            stop = int(s.stop.item())
+            if not s.persistent_timed_out():
+                t2v_hip.check_async_errors()
+                return stop
+            # the 256 workgroups were not co-scheduled (a GPU shared with other work): the bounded spins gave up.
+            # The launch-per-stage loop below restarts from the zero state — nothing of the failed run is kept
+            print("Warning! persistent decode kernel could not be co-scheduled; using the launch-per-stage loop")
+            s.reset_for_rerun()
+        while t < s.max_steps:
+            t1 = min(s.max_steps, t + chunk)
+            s.run(t, t1, self.gate_threshold, drop_rate, False, seed)
+            stop = int(s.stop.item())
+            if stop < t1:
+                break
+            t = t1
+        return stop
+
     def inference(self, memory, chunk=32, persistent=None):
         """reference model.py:428-464: decode until sigmoid(gate) > gate_threshold or max_decoder_steps.
         The loop runs on the GPU in chunks of `chunk` frames between stop-flag reads.
@@ -283,33 +310,8 @@ class Decoder(nn.Module):
         s.PRE[0].copy_(self.prenet(self.get_go_frame(memory)))
         self._calls += 1
         seed = (int(self.dropout_seed) * 1000003 + self._calls) & 0x7FFFFFFFFFFFFFFF
-        n, t = None, 0
-        if persistent is None:
-            persistent = os.environ.get('T2V_DECODE_PERSISTENT', '1') != '0'
-        if persistent and s.persistent_supported():
-            # one persistent launch for the whole utterance: weights resident on chip, state handed between CUs as
-            # tagged granules, the loop ends on the frame the gate fires
-            s.run_persistent(self.gate_threshold, drop_rate, seed)
-            stop = int(s.stop.item())
-            if s.persistent_timed_out():
-                # the 256 workgroups were not co-scheduled (a GPU shared with other work): the bounded spins gave up.
-                # The launch-per-stage loop below restarts from the zero state — nothing of the failed run is kept
-                print("Warning! persistent decode kernel could not be co-scheduled; using the launch-per-stage loop")
-                s.reset_for_rerun()
-            else:
-                t2v_hip.check_async_errors()
-                if stop < s.max_steps:
-                    n = stop + 1
-                t = s.max_steps
-        while t < s.max_steps:
-            t1 = min(s.max_steps, t + chunk)
-            s.run(t, t1, self.gate_threshold, drop_rate, False, seed)
-            stop = int(s.stop.item())
-            if stop < t1:
-                n = stop + 1
-                break
-            t = t1
-        if n is None:
+        n = self._run_to_end(s, chunk, persistent, seed) + 1
+        if n > s.max_steps:
             print("Warning! Reached max decoder steps")
             n = s.max_steps
         s.t = n
@@ -373,24 +375,7 @@ class Decoder(nn.Module):
         mask = torch.arange(memory.size(1), device=memory.device)[None, :] >= lengths[:, None]
         s = self._session(memory, mask, self.max_decoder_steps, item_seeds=seeds)
         s.PRE[0].copy_(self.prenet(self.get_go_frame(memory)))
-        done, t = False, 0
-        if persistent is None:
-            persistent = os.environ.get('T2V_DECODE_PERSISTENT', '1') != '0'
-        if persistent and s.persistent_supported():
-            s.run_persistent(self.gate_threshold, drop_rate, 0)
-            int(s.stop.item())
-            if s.persistent_timed_out():
-                print("Warning! persistent decode kernel could not be co-scheduled; using the launch-per-stage loop")
-                s.reset_for_rerun()
-            else:
-                t2v_hip.check_async_errors()
-                done = True
-        while not done and t < s.max_steps:
-            t1 = min(s.max_steps, t + chunk)
-            s.run(t, t1, self.gate_threshold, drop_rate, False, 0)
-            if int(s.stop.item()) < t1:
-                break
-            t = t1
+        self._run_to_end(s, chunk, persistent, 0)
         stops = s.stop_item.cpu().tolist()
         out = []
         for j, st in enumerate(stops):

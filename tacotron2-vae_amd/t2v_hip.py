@@ -208,6 +208,7 @@ def load_library():
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.t2v_set_phase_profile.argtypes = [C.c_void_p]
+    lib.t2v_set_phase_profile.restype = None
     lib.t2v_stamp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.t2v_debug_spin.argtypes = [C.c_int, C.c_int, C.c_void_p]
     lib.t2v_decoder_infer_persistent.argtypes = [C.POINTER(_DecPersistWeights), C.POINTER(_DecPersistBufs), C.c_int, C.c_int,
@@ -906,6 +907,10 @@ def _chunk_seed(seed, b0):
     return (int(seed) + 7919 * b0) & 0x7FFFFFFFFFFFFFFF
 
 
+def _cat(parts, dim):       # the chunks' tensors as one: torch.cat, without the copy when there is one chunk
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim)
+
+
 def _persist_weights(raw, bias_dec, wcomb, vv):
     w_ih_att, w_hh_att, w_ih_dec, w_hh_dec, wq = raw
     return _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq), _p(wcomb), _p(vv))
@@ -940,7 +945,7 @@ def replay_persistent_forward():
         raise T2VHipError("replay_persistent_forward: the last forward pass did not run on the persistent kernel (or "
                           "DecoderCore.keep_last was off)")
     PW, Sb, scratch, dims, _keep = DecoderCore.last_persist
-    eng = _FWD_ENGINES['persist16' if DecoderCore.last_kernel == _FWD_ENGINES['persist16'].kernel else 'persist']
+    eng = _FWD_ENGINES[DecoderCore.last_persist_engine]
     _check(getattr(load_library(), eng.run)(C.byref(PW), C.byref(Sb), _p(scratch), *(tuple(dims) + (_stream(),))), eng.run)
     return 1
 
@@ -952,11 +957,10 @@ def replay_persistent_backward():
         raise T2VHipError("replay_persistent_backward: the last backward pass did not run on the persistent kernel (or "
                           "DecoderCore.keep_last was off)")
     PW, Sb, bufs, dims, _keep = DecoderCore.last_bwd_persist
-    eng = _BWD_ENGINES['persist16' if DecoderCore.last_bwd_kernel == _BWD_ENGINES['persist16'].kernel else 'achain']
     # (with the weight-gradient epilogue when the pass had one: the call's own preparation zeroes its control words, the tiles it
     # takes are computed again)
     dwh = _keep[-1] if isinstance(_keep[-1], GroupedHandOver) else None
-    _bwd_launch(load_library(), eng, False, PW, Sb, bufs, dims, None if dwh is None else dwh.dw)
+    _bwd_launch(load_library(), _BWD_ENGINES[DecoderCore.last_bwd_persist_engine], False, PW, Sb, bufs, dims, None if dwh is None else dwh.dw)
     return 1
 
 
@@ -1026,6 +1030,7 @@ class DecoderCore(torch.autograd.Function):
     last_persist = None     # keep_last: (weights, bufs, scratch, dims, tensors) of the last persistent forward, for replays
     last_bwd = None         # keep_last: the same for the launch-per-step / ...
     last_bwd_persist = None     # ... the one-launch reverse pass of the first chunk
+    last_persist_engine = last_bwd_persist_engine = None    # key of the engine the chunk of last_persist / last_bwd_persist ran on
     dw_tile_cap = None      # tests: at most this many tiles in the weight-gradient epilogue of a reverse pass (None: no cap)
     last_mode = None        # 'persistent' | 'launch-per-step' of the most recent forward chunk
     last_bwd_mode = None
@@ -1113,8 +1118,10 @@ class DecoderCore(torch.autograd.Function):
     @staticmethod
     def _wgrad_tensors(ctx, f32):
         """gradient tensors of the four nn.LSTMCell weights (arena slots when FlatAdam registered them)"""
-        wg = [grad_slot(w) for w in ctx.wrefs]
-        return [torch.empty(w.shape, **f32) if g is None else g for g, w in zip(wg, ctx.wrefs)]
+        if ctx.wg is None:       # made where a backward first needs them: in front of a pass with an epilogue, else in _chunk_grads
+            wg = [grad_slot(w) for w in ctx.wrefs]
+            ctx.wg = [torch.empty(w.shape, **f32) if g is None else g for g, w in zip(wg, ctx.wrefs)]
+        return ctx.wg
 
     @staticmethod
     def _dw_groups(DGA, DGD, XS, wg, pre_c, T, B):
@@ -1168,7 +1175,7 @@ class DecoderCore(torch.autograd.Function):
         _err_note('decoder forward (persistent kernel hand-off)', QP.view(torch.int32)[B * 256 * A + 31:][:1])
         DecoderCore._note(fwd=plan.fwd)
         if DecoderCore.keep_last:
-            DecoderCore._note(last_persist=(PW, Sb, scratch, dims, raw))
+            DecoderCore._note(last_persist=(PW, Sb, scratch, dims, raw), last_persist_engine=plan.fwd)
         if not plan.prepare:
             return W, Sb, keep, None
         # the preparation of the reverse pass (sentinel fills — 1.4 MB per time step for the bf16 pass — and, for the fp32 pass,
@@ -1244,8 +1251,7 @@ class DecoderCore(torch.autograd.Function):
                                         T * Bc, _stream()), 't2v_concat2_rows')
             hcs.append(hc_c)
         als = [k[10][1:].permute(1, 0, 2) for _, _, k, _ in chunks]
-        HC = hcs[0] if len(hcs) == 1 else torch.cat(hcs, 1)
-        align = als[0] if len(als) == 1 else torch.cat(als, 0)
+        HC, align = _cat(hcs, 1), _cat(als, 0)
         ctx.dims = (B, T_in, T, float(p_att), float(p_dec), int(seed))
         ctx.consts = (packs, bias_dec, wqT, wcomb, vv, loc_conv, loc_dense)
         ctx.wbf = wbf
@@ -1264,181 +1270,189 @@ class DecoderCore(torch.autograd.Function):
         return HC, align
 
     @staticmethod
+    def _pre_chunk(ctx, b0, B):
+        """the chunk's rows of the Prenet output as (T * B, 256); None when the Prenet is not folded into this node"""
+        Bt, _, T = ctx.dims[:3]
+        return ctx.pre2 if ctx.pre2 is None or B == Bt else ctx.pre2.view(T, Bt, PRE)[:, b0:b0 + B].reshape(T * B, PRE)
+
+    @staticmethod
+    def _bwd_persist(ctx, lib, ci, dhc_c, DGA, DGD, DCTX):
+        """The reverse pass of chunk ci as ONE persistent launch (csrc/decoder_train_bwd_persist.hip; bf16_run, B <= 16: on bf16
+        MFMA tiles, csrc/decoder_train_bwd_persist16.hip).  Returns DV, dq_sum (T * B, 128) and the GroupedHandOver of the
+        chunk's weight-gradient epilogue (None: the pass has none)."""
+        plan, keep, b0, B = ctx.plans[ci], ctx.chunks[ci], ctx.plans[ci].b0, DGA.size(1)
+        _, T_in, T, p_att, p_dec, seed = ctx.dims
+        _packs, bias_dec, _wqT, wcomb, vv = ctx.consts[:5]
+        eng = _BWD_ENGINES[plan.bwd]
+        f32 = dict(device=dhc_c.device, dtype=torch.float32)
+        # (a one-launch reverse pass has its own slice geometry, e.g. one workgroup per item up to 96 symbols)
+        DV = torch.empty(B, getattr(lib, eng.slices)(T_in), A, **f32)
+        Sb = _DecTrainBufs(*(_p(t) for t in keep))
+        PW = _persist_weights(ctx.raw, bias_dec, wcomb, vv)
+        prep, ctx.prepared[ci] = ctx.prepared[ci], None
+        if prep is not None:
+            DQP, scratch, errw, pev = prep
+            torch.cuda.current_stream().wait_event(pev)     # (always: the preparation ran on a side stream)
+        else:
+            DQP, scratch, errw = DecoderCore._bwd_buffers(lib, eng, B, T_in, T, dhc_c.device)
+        dwh = None
+        if plan.dw_epilogue and set_f32_gemm_mode(None) and T * B >= 32:
+            # the decoder_rnn workgroups go on with decoder_rnn's weight gradients when their chain has ended: the gradient
+            # tensors, the grouped launch's scratch and its groups have to exist before the pass
+            groups = DecoderCore._dw_groups(DGA, DGD, keep[4], DecoderCore._wgrad_tensors(ctx, f32), DecoderCore._pre_chunk(ctx, b0, B), T, B)
+            dwh = GroupedHandOver(groups, 1, scratch[lib.t2v_decoder_bwd_achain_dw_offset(B, T_in, T):][:1], ci > 0, DecoderCore.dw_tile_cap)
+            if ci > 0 and overlap() is not None:
+                # this pass adds to d_w_*_dec on the current stream; the tiles an earlier chunk left over were added by its
+                # grouped launch on the deferred-GEMM stream
+                overlap().wait('g')
+        stamp('dec_bwd_begin')
+        bufs = (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw)
+        _bwd_launch(lib, eng, prep is not None, PW, Sb, bufs, (B, T_in, T, p_att, p_dec, _chunk_seed(seed, b0)),
+                    None if dwh is None else dwh.dw)
+        _err_note('decoder backward (persistent kernel hand-off)', errw)
+        dq_off = getattr(lib, eng.dq_offset)(B, T_in, T)       # slice 0 of every item has summed the slices already
+        rows = eng.dq_rows or B
+        dq_sum = scratch[dq_off:dq_off + T * rows * A].view(T, rows, A)[:, :B].reshape(T * B, A)
+        DecoderCore._note(bwd=plan.bwd)
+        if DecoderCore.keep_last and b0 == 0:
+            DecoderCore._note(last_bwd_persist=(PW, Sb, bufs, (B, T_in, T, p_att, p_dec, seed), keep + (ctx.raw, wcomb, vv, bias_dec, dwh)),
+                              last_bwd_persist_engine=plan.bwd)
+        return DV, dq_sum, dwh
+
+    @staticmethod
+    def _bwd_step_buffers(lib, B, T_in, T, NS, dev):
+        """dq partials, the cells' carried state and the attention hand-off words of a launch-per-step reverse pass"""
+        f32 = dict(device=dev, dtype=torch.float32)
+        tcap = (T_in + 15) // 16 * 16
+        DQ = torch.empty(T, B, NS, A, 2, **f32)
+        YD, YA, DCA, DCD = (torch.empty(B, n, **f32) for n in (XW, KATT, H, H))
+        GPREV, GCUM = torch.empty(2, B, NS, 2, 64, **f32), torch.empty(B * NS * tcap + 64, **f32)
+        return DQ, YD, YA, DCA, DCD, GPREV, GCUM, GCUM.view(torch.int32)[B * NS * tcap + 1:][:1]
+
+    @staticmethod
+    def _bwd_steps(ctx, lib, ci, dhc_c, DGA, DGD, DCTX):
+        """The reverse pass of chunk ci as one launch pair per step (k_lstm_bwd256 + k_attn_cell_bwd).  Returns DV, dq_sum
+        (T * B, 128) and None (no weight-gradient epilogue)."""
+        keep, b0, B = ctx.chunks[ci], ctx.plans[ci].b0, DGA.size(1)
+        _, T_in, T, p_att, p_dec, seed = ctx.dims
+        packs, bias_dec, wqT, wcomb, vv = ctx.consts[:5]
+        NS = lib.t2v_attn_bwd_slices(T_in)
+        DV = torch.empty(B, NS, A, device=dhc_c.device, dtype=torch.float32)
+        Sb = _DecTrainBufs(*(_p(t) for t in keep))
+        W = _DecWeights(*(_p(t) for t in packs), None, _p(bias_dec), _p(wqT), _p(wcomb), _p(vv), int(bool(ctx.wbf)))
+        DQ, YD, YA, DCA, DCD, GPREV, GCUM, errw = DecoderCore._bwd_step_buffers(lib, B, T_in, T, NS, dhc_c.device)
+        gb = (dhc_c, DGA, DGD, DQ, DCTX, YD, YA, DCA, DCD, GPREV, GCUM, DV)             # the fields of t2v_dec_bwd_bufs
+        Gb = _DecBwdBufs(*(_p(t) for t in gb))
+        _check(lib.t2v_decoder_train_bwd(C.byref(W), C.byref(Sb), C.byref(Gb), B, T_in, T, p_att, p_dec,
+                                         _chunk_seed(seed, b0), _stream()), 't2v_decoder_train_bwd')
+        _err_note('decoder backward (dq hand-off)', errw)
+        dq_sum = DQ[..., 0].sum(2).view(T * B, A)
+        DecoderCore._note(bwd='steps')
+        if DecoderCore.keep_last and b0 == 0:
+            DecoderCore._note(last_bwd=(W, Sb, Gb, (B, T_in, T, p_att, p_dec, seed),
+                                        keep + gb + (packs, bias_dec, wqT, wcomb, vv)))
+        return DV, dq_sum, None
+
+    @staticmethod
+    def _chunk_grads(ctx, lib, ci, dhc_c, DGA, DGD, DCTX, DV, dq_sum, dwh, acc, dpre_l):
+        """The gradients of chunk ci, behind its reverse pass.  Returns d_memory, d_pm, acc + the chunk's [d_wq, d_loc_conv, d_loc_dense,
+        d_v] (acc: the earlier chunks' sums, None for chunk 0; added on the deferred-work stream, where they are made) and the bias
+        gradients.  The LSTM weight gradients go into _wgrad_tensors (chunk 0 writes, later ones add), a Prenet data gradient to dpre_l."""
+        keep, b0, B, first = ctx.chunks[ci], ctx.plans[ci].b0, DGA.size(1), ci == 0
+        XS, AL, ACUM, dpre = keep[4], keep[10], keep[11], keep[12]      # S: overwritten in place by the backward kernels
+        (T_in, T), (loc_conv, loc_dense) = ctx.dims[1:3], ctx.consts[5:]
+        TB = T * B
+        f32 = dict(device=dhc_c.device, dtype=torch.float32)
+        dga2 = DGA.view(TB, G4)
+        stamp('dec_bwd_end')
+        fork = mark()
+        # ---- what the encoder's backward waits for stays on the current stream ...
+        d_memory = torch.empty(B, T_in, E, **f32)
+        # per item: alpha_b^T (T_in x T) · dctx_b (T x 512), all items in one launch
+        _check(lib.t2v_gemm_f32_batched(_p(AL[1:]), T_in, 1, B * T_in, _p(DCTX), E, 1, B * E, _p(d_memory), T_in * E, E, B,
+                                        T_in, E, T, _stream()), 't2v_gemm_f32_batched')
+        d_pm = colsum(dpre.view(T, B * T_in * A)).view(B, T_in, A)
+        want_dpre = ctx.pre2 is not None and ctx.needs_input_grad[17]
+        if want_dpre and not ctx.pre_on_side:
+            # the Prenet ran on the caller's stream: its backward is ordered behind THIS stream only
+            dpre_l.append(gemm(dga2, ctx.wrefs[0].detach()[:, :PRE].t()).view(T, B, PRE))
+        # ---- ... every weight gradient goes to the engine's deferred-work stream (inline without an engine): the
+        # ≈ 80 GFLOP of time-batched LSTM weight-gradient GEMMs then run next to the BiLSTM / reference-encoder
+        # backward chains instead of in front of them
+        with side('w', keep=(DGA, DGD, DCTX, DV, dq_sum, dhc_c) + tuple(keep), after=fork):
+            wg = DecoderCore._wgrad_tensors(ctx, f32)
+            if first and ctx.pre2 is None:      # the prenet columns of attention_rnn.weight_ih get their gradient via gpre
+                wg[0][:, :PRE].zero_()
+            # round 6: the five LSTM weight-gradient products as ONE launch of the plane kernel — both gate-gradient operands split
+            # (fp32: x3 planes; bf16_run: rounded) once, 1 024 tiles = two full rounds of the chip (T2V_DW_GROUPED=0: one by one)
+            grouped = os.environ.get('T2V_DW_GROUPED', '1') != '0'
+            groups = dwh.groups if dwh is not None else DecoderCore._dw_groups(DGA, DGD, XS, wg, DecoderCore._pre_chunk(ctx, b0, B), T, B)
+            products = [(gt, xt, out) for gt, parts in groups for xt, out in parts]        # _dw_groups' order
+            if ctx.pre2 is not None:    # the input projection of the prenet output, folded into this node: the Prenet's
+                # own backward (issued on this same stream when an engine is active) waits for d_pre, so it goes first
+                if want_dpre and ctx.pre_on_side:
+                    dpre_l.append(gemm(dga2, ctx.wrefs[0].detach()[:, :PRE].t()).view(T, B, PRE))
+                if not grouped:         # (one by one: the Prenet columns' product stays on this stream)
+                    gt, xt, out = products.pop(0)
+                    gemm(gt, xt, out=out, accumulate=not first)
+            # each product lands in its own tensor (no split / copy afterwards).  fp32: the own large-tile fp32 MFMA GEMM;
+            # bf16_run: the own large-tile bf16 GEMM (k_gemm_bf16_big_rr: operands rounded to bf16 while staged, fp32
+            # accumulation) — no library GEMM is left in either step.  (What they cost on the step's clock: DESIGN §4.1)
+            with side('g', after=fork, keep=() if dwh is None else (dwh.scr,)):
+                if dwh is not None:
+                    # (the pass has written the decoder_rnn group's planes and taken tiles of it: this launch does the rest)
+                    gemm_grouped(groups, accumulate=not first, handed=dwh)
+                elif grouped:
+                    gemm_grouped(groups, accumulate=not first)
+                else:
+                    for gt, xt, out in products:
+                        gemm(gt, xt, out=out, accumulate=not first)
+            # the attention weight gradients stay on the deferred-work stream: on a stream of their own they are a fifth concurrent
+            # branch on the graph executor's four queues, which costs more than the shorter path buys (measured, DESIGN §4.0f)
+            d_wq = gemm(dq_sum.t(), XS[1:T + 1].reshape(TB, XW)[:, :H].t())            # (128,1024), from h_att_t
+            d_v = DV.sum((0, 1)).view(1, A)
+            d_loc_dense, d_loc_conv = attn_wgrad(dpre, AL, ACUM, loc_conv, loc_dense, B, T_in, T)
+            parts = [d_wq, d_loc_conv, d_loc_dense, d_v]
+            acc = parts if acc is None else [x + y for x, y in zip(acc, parts)]
+        # bias gradients flow on through an Add node (bias_ih + bias_hh) / are handed to two inputs: node's stream
+        return d_memory, d_pm, acc, [colsum(DGD.view(TB, G4))] + ([colsum(dga2)] if ctx.pre2 is not None else [])
+
+    @staticmethod
     def backward(ctx, dHC, _dalign):
+        """The chunk loop: each chunk's reverse pass (_bwd_persist | _bwd_steps, as plan() chose), its gradients
+        (_chunk_grads), the sums over the chunks and the return tuple."""
         lib = load_library()
-        Bt, T_in, T, p_att, p_dec, seed = ctx.dims
-        packs, bias_dec, wqT, wcomb, vv, loc_conv, loc_dense = ctx.consts
-        packF_att, packF_dec, packB_att, packB_dec = packs
         if ctx.chunks is None:
             raise T2VHipError("DecoderCore.backward without a saved arena (forward ran under no_grad)")
-        dev = dHC.device
-        f32 = dict(device=dev, dtype=torch.float32)
+        Bt, _T_in, T = ctx.dims[:3]
+        f32 = dict(device=dHC.device, dtype=torch.float32)
         dHC = _f32c(dHC)
-        tcap = (T_in + 15) // 16 * 16
-        acc = bacc = None
-        wg = None
-        wg_fresh = False        # wg was made in front of this chunk's reverse pass (weight-gradient epilogue): nothing is in it yet
+        acc = bacc = ctx.wg = None
         dga_l, dmem_l, dpm_l, dpre_l = [], [], [], []
         DecoderCore._note(chunk_bwd_kernels=[])
-        for ci, (plan, keep) in enumerate(zip(ctx.plans, ctx.chunks)):
-            gpre, memory, pm, lengths, XS, CA, CD, GA, GD, QP, AL, ACUM, S = keep
+        for ci, plan in enumerate(ctx.plans):
             b0, B = plan.b0, plan.b1 - plan.b0
-            kept = DecoderCore.keep_last and b0 == 0
             dhc_c = dHC if B == Bt else dHC[:, b0:b0 + B].contiguous()
-            DGA = torch.empty(T, B, G4, **f32)
-            DGD = torch.empty(T, B, G4, **f32)
-            DCTX = torch.empty(T, B, E, **f32)
-            # (a one-launch reverse pass has its own slice geometry, e.g. one workgroup per item up to 96 symbols)
-            eng = _BWD_ENGINES.get(plan.bwd)
-            NS = lib.t2v_attn_bwd_slices(T_in) if eng is None else getattr(lib, eng.slices)(T_in)
-            DV = torch.empty(B, NS, A, **f32)
-            Sb = _DecTrainBufs(*(_p(t) for t in keep))
-            dwh = None          # the GroupedHandOver of this chunk's weight-gradient epilogue
-            if eng is not None:
-                # the whole reverse pass as ONE persistent launch (csrc/decoder_train_bwd_persist.hip; bf16_run, B <= 16: on bf16
-                # MFMA tiles, csrc/decoder_train_bwd_persist16.hip)
-                PW = _persist_weights(ctx.raw, bias_dec, wcomb, vv)
-                prep, ctx.prepared[ci] = ctx.prepared[ci], None
-                if prep is not None:
-                    DQP, scratch, errw, pev = prep
-                    torch.cuda.current_stream().wait_event(pev)     # (always: the preparation ran on a side stream)
-                else:
-                    DQP, scratch, errw = DecoderCore._bwd_buffers(lib, eng, B, T_in, T, dev)
-                if plan.dw_epilogue and set_f32_gemm_mode(None) and T * B >= 32:
-                    # the decoder_rnn workgroups go on with decoder_rnn's weight gradients when their chain has ended: the gradient
-                    # tensors, the grouped launch's scratch and its groups have to exist before the pass
-                    if wg is None:
-                        wg, wg_fresh = DecoderCore._wgrad_tensors(ctx, f32), True
-                    pre_c = None
-                    if ctx.pre2 is not None:
-                        pre_c = ctx.pre2 if B == Bt else ctx.pre2.view(T, Bt, PRE)[:, b0:b0 + B].reshape(T * B, PRE)
-                    groups = DecoderCore._dw_groups(DGA, DGD, XS, wg, pre_c, T, B)
-                    dwh = GroupedHandOver(groups, 1, scratch[lib.t2v_decoder_bwd_achain_dw_offset(B, T_in, T):][:1], not wg_fresh,
-                                          DecoderCore.dw_tile_cap)
-                    if not wg_fresh and overlap() is not None:
-                        # this pass adds to d_w_*_dec on the current stream; the tiles an earlier chunk left over were added by its
-                        # grouped launch on the deferred-GEMM stream
-                        overlap().wait('g')
-                stamp('dec_bwd_begin')
-                bufs = (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw)
-                _bwd_launch(lib, eng, prep is not None, PW, Sb, bufs, (B, T_in, T, p_att, p_dec, _chunk_seed(seed, b0)),
-                            None if dwh is None else dwh.dw)
-                _err_note('decoder backward (persistent kernel hand-off)', errw)
-                dq_off = getattr(lib, eng.dq_offset)(B, T_in, T)       # slice 0 of every item has summed the slices already
-                rows = eng.dq_rows or B
-                dq_sum = scratch[dq_off:dq_off + T * rows * A].view(T, rows, A)[:, :B].reshape(T * B, A)
-                DecoderCore._note(bwd=plan.bwd)
-                if kept:
-                    DecoderCore._note(last_bwd_persist=(PW, Sb, bufs, (B, T_in, T, p_att, p_dec, seed), keep + (ctx.raw, wcomb, vv, bias_dec, dwh)))
-            else:
-                W = _DecWeights(_p(packF_att), _p(packF_dec), _p(packB_att), _p(packB_dec), None, _p(bias_dec),
-                                _p(wqT), _p(wcomb), _p(vv), int(bool(ctx.wbf)))
-                DQ = torch.empty(T, B, NS, A, 2, **f32)
-                YD = torch.empty(B, XW, **f32); YA = torch.empty(B, KATT, **f32)
-                DCA = torch.empty(B, H, **f32); DCD = torch.empty(B, H, **f32)
-                GPREV = torch.empty(2, B, NS, 2, 64, **f32); GCUM = torch.empty(B * NS * tcap + 64, **f32)
-                Gb = _DecBwdBufs(_p(dhc_c), _p(DGA), _p(DGD), _p(DQ), _p(DCTX), _p(YD), _p(YA), _p(DCA),
-                                 _p(DCD), _p(GPREV), _p(GCUM), _p(DV))
-                _check(lib.t2v_decoder_train_bwd(C.byref(W), C.byref(Sb), C.byref(Gb), B, T_in, T, p_att, p_dec,
-                                                 _chunk_seed(seed, b0), _stream()), 't2v_decoder_train_bwd')
-                _err_note('decoder backward (dq hand-off)', GCUM.view(torch.int32)[B * NS * tcap + 1:][:1])
-                dq_sum = DQ[..., 0].sum(2).view(T * B, A)
-                DecoderCore._note(bwd='steps')
-                if kept:
-                    DecoderCore._note(last_bwd=(W, Sb, Gb, (B, T_in, T, p_att, p_dec, seed),
-                                                keep + (dhc_c, DGA, DGD, DQ, DCTX, YD, YA, DCA, DCD, GPREV, GCUM, DV, packs, bias_dec,
-                                                        wqT, wcomb, vv)))
-            TB = T * B
-            stamp('dec_bwd_end')
-            fork = mark()
-            # ---- what the encoder's backward waits for stays on the current stream ...
-            d_memory = torch.empty(B, T_in, E, **f32)
-            # per item: alpha_b^T (T_in x T) · dctx_b (T x 512), all items in one launch
-            _check(lib.t2v_gemm_f32_batched(_p(AL[1:]), T_in, 1, B * T_in, _p(DCTX), E, 1, B * E, _p(d_memory), T_in * E, E, B,
-                                            T_in, E, T, _stream()), 't2v_gemm_f32_batched')
-            dpre = S                                   # overwritten in place by the backward kernels
-            d_pm = colsum(dpre.view(T, B * T_in * A)).view(B, T_in, A)
-            dmem_l.append(d_memory); dpm_l.append(d_pm)
-            if ctx.pre2 is not None and ctx.needs_input_grad[17] and not ctx.pre_on_side:
-                # the Prenet ran on the caller's stream: its backward is ordered behind THIS stream only
-                dpre_l.append(gemm(DGA.view(TB, G4), ctx.wrefs[0].detach()[:, :PRE].t()).view(T, B, PRE))
-            # ---- ... every weight gradient goes to the engine's deferred-work stream (inline without an engine): the
-            # ≈ 80 GFLOP of time-batched LSTM weight-gradient GEMMs then run next to the BiLSTM / reference-encoder
-            # backward chains instead of in front of them
-            with side('w', keep=(DGA, DGD, DCTX, DV, dq_sum, dhc_c) + tuple(keep), after=fork):
-                dga2, dgd2 = DGA.view(TB, G4), DGD.view(TB, G4)
-                x_prev = XS[0:T].reshape(TB, XW)          # [h_att_{t-1} | ctx_{t-1} | .]
-                x_cur = XS[1:T + 1].reshape(TB, XW)       # [h_att_t | ctx_t | h_dec_{t-1}]
-                first = wg is None or wg_fresh
-                if wg is None:  # gradient tensors of the four nn.LSTMCell weights (arena slots when FlatAdam registered them)
-                    wg = DecoderCore._wgrad_tensors(ctx, f32)
-                wg_fresh = False
-                if first and ctx.pre2 is None:      # the prenet columns of attention_rnn.weight_ih get their gradient via gpre
-                    wg[0][:, :PRE].zero_()
-                d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec = wg
-                # round 6: the five LSTM weight-gradient products as ONE launch of the plane kernel — both gate-gradient operands split
-                # (fp32: x3 planes; bf16_run: rounded) once, 1 024 tiles = two full rounds of the chip (T2V_DW_GROUPED=0: one by one)
-                grouped = os.environ.get('T2V_DW_GROUPED', '1') != '0'
-                if ctx.pre2 is not None:    # the input projection of the prenet output, folded into this node: the Prenet's
-                    # own backward (issued on this same stream when an engine is active) waits for d_pre, so it goes first
-                    pre_c = ctx.pre2 if B == Bt else ctx.pre2.view(T, Bt, PRE)[:, b0:b0 + B].reshape(TB, PRE)
-                    if ctx.needs_input_grad[17] and ctx.pre_on_side:
-                        dpre_l.append(gemm(dga2, ctx.wrefs[0].detach()[:, :PRE].t()).view(T, B, PRE))
-                    if not grouped:
-                        gemm(dga2.t(), pre_c.t(), out=d_w_ih_att[:, :PRE], accumulate=not first)
-                # each product lands in its own tensor (no split / copy afterwards).  fp32: the own large-tile fp32 MFMA GEMM;
-                # bf16_run: the own large-tile bf16 GEMM (k_gemm_bf16_big_rr: operands rounded to bf16 while staged, fp32
-                # accumulation) — no library GEMM is left in either step
-                # (measured round 4: without these four products the step is 0.71 ms shorter, alone they take 0.82 ms — they run
-                # NEXT to the other chains but the chip is shared, so almost all of their time is still on the step's clock)
-                with side('g', after=fork, keep=() if dwh is None else (dwh.scr,)):
-                    if dwh is not None:
-                        # (the pass has written the decoder_rnn group's planes and taken tiles of it: this launch does the rest)
-                        gemm_grouped(dwh.groups, accumulate=not first, handed=dwh)
-                    elif grouped:
-                        att = [(x_prev[:, :H].t(), d_w_hh_att), (x_prev[:, H:KATT].t(), d_w_ih_att[:, PRE:])]
-                        if ctx.pre2 is not None:
-                            att.insert(0, (pre_c.t(), d_w_ih_att[:, :PRE]))
-                        gemm_grouped([(dga2.t(), att),
-                                      (dgd2.t(), [(x_cur[:, :KATT].t(), d_w_ih_dec), (x_cur[:, KATT:].t(), d_w_hh_dec)])], accumulate=not first)
-                    else:
-                        gemm(dga2.t(), x_prev[:, :H].t(), out=d_w_hh_att, accumulate=not first)
-                        gemm(dga2.t(), x_prev[:, H:KATT].t(), out=d_w_ih_att[:, PRE:], accumulate=not first)
-                        gemm(dgd2.t(), x_cur[:, :KATT].t(), out=d_w_ih_dec, accumulate=not first)
-                        gemm(dgd2.t(), x_cur[:, KATT:].t(), out=d_w_hh_dec, accumulate=not first)
-                # the attention weight gradients stay on the deferred-work stream.  (Round 5: the captured DAG's longest path behind the
-                # reverse pass is this stream's serial order — Prenet data gradient, these ~450 us, the Prenet backward, the BiLSTM
-                # and encoder-conv weight gradients: 1.3 .. 1.7 ms — so they were tried on a stream of their own: fp32 step
-                # 11.24 -> 11.36 ms, bf16 12.86 -> 12.91, two alternating pairs of 60 steps.  A fifth concurrent branch on
-                # the graph executor's four queues costs more than the shorter path buys; tools/graph_critical_path.py)
-                d_wq = gemm(dq_sum.t(), x_cur[:, :H].t())            # (128,1024)
-                d_v = DV.sum((0, 1)).view(1, A)
-                d_loc_dense, d_loc_conv = attn_wgrad(dpre, AL, ACUM, loc_conv, loc_dense, B, T_in, T)
-                parts = [d_wq, d_loc_conv, d_loc_dense, d_v]
-                acc = parts if acc is None else [x + y for x, y in zip(acc, parts)]
-            # bias gradients flow on through an Add node (bias_ih + bias_hh) / are handed to two inputs: node's stream
-            bparts = [colsum(DGD.view(TB, G4))] + ([colsum(DGA.view(TB, G4))] if ctx.pre2 is not None else [])
+            DGA, DGD, DCTX = torch.empty(T, B, G4, **f32), torch.empty(T, B, G4, **f32), torch.empty(T, B, E, **f32)
+            reverse = DecoderCore._bwd_persist if plan.bwd in _BWD_ENGINES else DecoderCore._bwd_steps
+            rev = reverse(ctx, lib, ci, dhc_c, DGA, DGD, DCTX)              # DV, dq_sum, the epilogue's hand-over
+            d_memory, d_pm, acc, bparts = DecoderCore._chunk_grads(ctx, lib, ci, dhc_c, DGA, DGD, DCTX, *rev, acc, dpre_l)
             bacc = bparts if bacc is None else [x + y for x, y in zip(bacc, bparts)]
-            dga_l.append(DGA)
+            dmem_l.append(d_memory); dpm_l.append(d_pm); dga_l.append(DGA)
         ctx.chunks = ctx.prepared = None   # the arena is released as soon as the backward has consumed it (side-stream readers: keep=)
-        d_wq, d_loc_conv, d_loc_dense, d_v = acc
-        d_bias_dec = bacc[0]
-        d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec = wg
-        d_memory = dmem_l[0] if len(dmem_l) == 1 else torch.cat(dmem_l, 0)
-        d_pm = dpm_l[0] if len(dpm_l) == 1 else torch.cat(dpm_l, 0)
-        d_pre = d_b_att = None
+        wg, ctx.wg = ctx.wg, None          # d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec; acc: d_wq, d_loc_conv, d_loc_dense, d_v
+        d_memory, d_pm = _cat(dmem_l, 0), _cat(dpm_l, 0)
+        DGA = d_pre = d_b_att = None
         if ctx.pre2 is not None:
-            DGA = None
             d_b_att = bacc[1]
             if dpre_l and ctx.pre_on_side:
                 with side('w'):
-                    d_pre = dpre_l[0] if len(dpre_l) == 1 else torch.cat(dpre_l, 1)
+                    d_pre = _cat(dpre_l, 1)
             elif dpre_l:
-                d_pre = dpre_l[0] if len(dpre_l) == 1 else torch.cat(dpre_l, 1)
+                d_pre = _cat(dpre_l, 1)
         else:
-            DGA = dga_l[0] if len(dga_l) == 1 else torch.cat(dga_l, 1)
-        return (DGA, d_memory, d_pm, None, d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec, d_bias_dec,
-                d_wq, d_loc_conv, d_loc_dense, d_v, None, None, None, None, d_pre, d_b_att, d_b_att, None)
+            DGA = _cat(dga_l, 1)
+        return (DGA, d_memory, d_pm, None, *wg, bacc[0], *acc, None, None, None, None, d_pre, d_b_att, d_b_att, None)
 
 
 def attn_wgrad(dpre, AL, ACUM, loc_conv, loc_dense, B, T_in, T):
@@ -1477,12 +1491,29 @@ def mel_frontend(wav, n_samples, tables, scale=1.0, t_stride=None):
     return out
 
 
+def _checked_lengths(v, B, lo, hi, count_msg, range_msg, reject_float=True, reject_bool=True, default=None, dtype=torch.int32):
+    """The one check of a lengths argument: B values in lo..hi from a list, a CPU or a device tensor (None: B times `default`, for
+    a caller that has one), as a host tensor of `dtype` (None: as it came).  ValueError(count_msg + the values) on a wrong count or
+    a rejected element type, ValueError(range_msg + the values) outside the range.  reject_float / reject_bool: each caller's
+    acceptance as it has always been; a float that is let in is compared, and converted, truncated."""
+    n = torch.full((B,), default, dtype=torch.int64) if v is None and default is not None else torch.as_tensor(v).reshape(-1).cpu()
+    if (reject_float and n.dtype.is_floating_point) or (reject_bool and n.dtype == torch.bool) or n.numel() != B:
+        raise ValueError("%s, got %s" % (count_msg, n.tolist()))
+    if int(n.min()) < lo or int(n.max()) > hi:
+        raise ValueError("%s, got %s" % (range_msg, n.tolist()))
+    return n if dtype is None else n.to(dtype)
+
+
 def _frame_counts(n_frames, B, T, device, min_frames=1):
     """per-utterance frame counts as a device int32 vector (all T when None), checked on the host"""
-    n = torch.full((B,), T, dtype=torch.int64) if n_frames is None else torch.as_tensor(n_frames).reshape(-1).cpu()
-    if n.numel() != B or int(n.min()) < min_frames or int(n.max()) > T:
-        raise ValueError("every utterance needs %d <= frames <= %d, got %s" % (min_frames, T, n.tolist()))
-    return n.to(device=device, dtype=torch.int32)
+    msg = "every utterance needs %d <= frames <= %d" % (min_frames, T)
+    return _checked_lengths(n_frames, B, min_frames, T, msg, msg, reject_float=False, reject_bool=False, default=T).to(device)
+
+
+def _stft_lengths(n_samples, B, N):
+    """stft_polar's sample counts on the host, in the type they came in (all N when None); F.pad(mode='reflect') needs > n_fft/2 each"""
+    msg = "stft: every utterance needs 512 < n_samples <= %d" % N
+    return _checked_lengths(n_samples, B, 513, N, msg, msg, reject_float=False, reject_bool=False, default=N, dtype=None)
 
 
 def stft_polar(wav, n_samples, tables, t_stride=None):
@@ -1491,10 +1522,7 @@ def stft_polar(wav, n_samples, tables, t_stride=None):
     lib = _require_gpu(wav)
     B, N = wav.shape
     wav = _f32c(wav)
-    n = torch.full((B,), N, dtype=torch.int64) if n_samples is None else torch.as_tensor(n_samples).reshape(-1).cpu()
-    if n.numel() != B or int(n.min()) <= 512 or int(n.max()) > N:
-        # the reference's F.pad(mode='reflect') of n_fft/2 needs more than n_fft/2 samples
-        raise ValueError("stft: every utterance needs 512 < n_samples <= %d, got %s" % (N, n.tolist()))
+    n = _stft_lengths(n_samples, B, N)
     if t_stride is None:
         t_stride = int(n.max()) // 256 + 1
     mag = torch.empty(B, 513, t_stride, device=wav.device, dtype=torch.float32)
@@ -1628,13 +1656,10 @@ DTW_SCRATCH_CAP = 256 << 20             # bytes of scratch one t2v_mel_dtw call 
 
 def _dtw_lengths(n, B, stride, what):
     """frame counts of mel_dtw as a host list, checked: a list, a CPU tensor or a device int tensor"""
-    n = torch.as_tensor(n).reshape(-1).cpu()
-    if n.dtype.is_floating_point or n.numel() != B:
-        raise ValueError("mel_dtw: %s must be %d integer frame counts, got %s" % (what, B, n.tolist()))
-    if int(n.min()) < 1 or int(n.max()) > min(stride, DTW_MAX_FRAMES):
-        raise ValueError("mel_dtw: every %s must be in 1..%d (%d frames stored, at most %d supported), got %s"
-                         % (what, min(stride, DTW_MAX_FRAMES), stride, DTW_MAX_FRAMES, n.tolist()))
-    return n.to(torch.int32)
+    hi = min(stride, DTW_MAX_FRAMES)
+    return _checked_lengths(n, B, 1, hi, "mel_dtw: %s must be %d integer frame counts" % (what, B),
+                            "mel_dtw: every %s must be in 1..%d (%d frames stored, at most %d supported)"
+                            % (what, hi, stride, DTW_MAX_FRAMES), reject_bool=False)
 
 
 def mel_dtw(x, nx, y, ny):
@@ -1685,6 +1710,12 @@ def f0_lags(fmin=60.0, fmax=500.0):
     return tau_min, tau_max
 
 
+def _f0_lengths(lengths, B, S):
+    """sample counts of f0() as a host int32 tensor, checked: a list, a CPU tensor or a device int tensor"""
+    return _checked_lengths(lengths, B, 1, S, "f0: lengths must be %d integer sample counts" % B,
+                            "f0: every length must be in 1..%d (samples stored per row)" % S)
+
+
 def f0(y, lengths, fmin=60.0, fmax=500.0, threshold=0.1, return_aperiodicity=False):
     """YIN pitch tracks (csrc/f0.hip k_f0_yin): y (B, S) float32 CUDA tensor of 16 kHz waveforms, row b of lengths[b] samples
     (a list, a CPU tensor or a device int tensor); samples outside a row's length count as 0 and are not read.  Frames as
@@ -1702,17 +1733,13 @@ def f0(y, lengths, fmin=60.0, fmax=500.0, threshold=0.1, return_aperiodicity=Fal
     threshold = float(threshold)
     if not 0.0 < threshold < 1.0:
         raise ValueError("f0: threshold %g must lie in (0, 1)" % threshold)
-    n = torch.as_tensor(lengths).reshape(-1).cpu()
-    if n.dtype.is_floating_point or n.dtype == torch.bool or n.numel() != B:
-        raise ValueError("f0: lengths must be %d integer sample counts, got %s" % (B, n.tolist()))
-    if int(n.min()) < 1 or int(n.max()) > S:
-        raise ValueError("f0: every length must be in 1..%d (samples stored per row), got %s" % (S, n.tolist()))
+    n = _f0_lengths(lengths, B, S)
     T = int(n.max()) // F0_HOP + 1
     stride = S // F0_HOP + 1
     y = _f32c(y)
     hz = torch.empty(B, stride, device=y.device, dtype=torch.float32)
     ap = torch.empty(B, stride, device=y.device, dtype=torch.float32)
-    _check(lib.t2v_f0_yin(_p(y), _p(n.to(torch.int32).to(y.device)), S, B, tau_min, tau_max, threshold, _p(hz), _p(ap), stride,
+    _check(lib.t2v_f0_yin(_p(y), _p(n.to(y.device)), S, B, tau_min, tau_max, threshold, _p(hz), _p(ap), stride,
                           _stream()), 't2v_f0_yin')
     if T < stride:
         hz, ap = hz[:, :T].contiguous(), ap[:, :T].contiguous()
@@ -1740,12 +1767,8 @@ class _AlignDeviceError(T2VHipError, ValueError):
 
 def _align_lengths(v, B, hi, what, unit):
     """lengths of alignment_stats as a host int32 tensor, checked: a list, a CPU tensor or a device int tensor"""
-    v = torch.as_tensor(v).reshape(-1).cpu()
-    if v.dtype.is_floating_point or v.dtype == torch.bool or v.numel() != B:
-        raise ValueError("alignment_stats: %s must be %d integer %s counts, got %s" % (what, B, unit, v.tolist()))
-    if int(v.min()) < 1 or int(v.max()) > hi:
-        raise ValueError("alignment_stats: every %s must be in 1..%d (%s stored per row), got %s" % (what, hi, unit + 's', v.tolist()))
-    return v.to(torch.int32)
+    return _checked_lengths(v, B, 1, hi, "alignment_stats: %s must be %d integer %s counts" % (what, B, unit),
+                            "alignment_stats: every %s must be in 1..%d (%ss stored per row)" % (what, hi, unit))
 
 
 def alignment_stats(alignments, n_frames, text_lengths, max_jump=3, cover_min=0.5):
@@ -1978,15 +2001,11 @@ class InferenceSession(object):
                                _p(self.wq), _p(self.wcomb), _p(self.v), _p(self.proj_w), _p(self.proj_b), _p(self.w1))
         Bf = _DecPersistBufs(_p(self.memory), _p(self.pm), _p(self.lengths), _p(self.PRE[0]), _p(self.MEL), _p(self.GATE),
                              _p(self.AL), _p(self.stop), _p(self._gran), _p(self._perr))
-        if self._items is not None:
-            _check(lib.t2v_decoder_infer_persistent_items(C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
-                                                          float(gate_threshold), float(p_prenet), int(seed),
-                                                          C.byref(self._items), _stream()),
-                   't2v_decoder_infer_persistent_items')
-            return
-        _check(lib.t2v_decoder_infer_persistent(C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
-                                                float(gate_threshold), float(p_prenet), int(seed), _stream()),
-               't2v_decoder_infer_persistent')
+        name, args = 't2v_decoder_infer_persistent', [C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
+                                                      float(gate_threshold), float(p_prenet), int(seed)]
+        if self._items is not None:         # per-item seeds and stop frames: the *_items entry point takes them behind the seed
+            name, args = name + '_items', args + [C.byref(self._items)]
+        _check(getattr(lib, name)(*args, _stream()), name)
 
     def persistent_timed_out(self):
         """True when a bounded spin of the last run_persistent() gave up (the 256 workgroups were not co-resident);
@@ -2008,17 +2027,11 @@ class InferenceSession(object):
                                                                         False)
             self.W = _DecWeights(_p(self.packF_att), _p(self.packF_dec), None, None, _p(self.b_att), _p(self.b_dec),
                                  _p(self.wqT), _p(self.wcomb), _p(self.v))
+        name, args = 't2v_decoder_infer_steps', [C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0), int(t1),
+                                                 float(gate_threshold), float(p_prenet), int(bool(external_prenet)), int(seed)]
         if self._items is not None:
-            _check(load_library().t2v_decoder_infer_steps_items(C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0),
-                                                                int(t1), float(gate_threshold), float(p_prenet),
-                                                                int(bool(external_prenet)), int(seed), C.byref(self._items),
-                                                                _stream()),
-                   't2v_decoder_infer_steps_items')
-            return
-        _check(load_library().t2v_decoder_infer_steps(C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0),
-                                                      int(t1), float(gate_threshold), float(p_prenet),
-                                                      int(bool(external_prenet)), int(seed), _stream()),
-               't2v_decoder_infer_steps')
+            name, args = name + '_items', args + [C.byref(self._items)]
+        _check(getattr(load_library(), name)(*args, _stream()), name)
 
 
 def limit_host_threads(n=None):

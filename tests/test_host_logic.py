@@ -296,3 +296,109 @@ def test_error_ledger_blocks_are_recycled_and_slots_stay_in_bounds():
     assert 'graph 5 note 2' in str(ei.value)
     H.check_async_errors()
     H._ERR_POOL.pop('cpu', None)
+
+
+# ---- lengths arguments: one check (t2v_hip._checked_lengths) behind five callers.  The messages below were recorded from the five
+# hand-written validators this check replaced; GPU tests match on them too.
+def _length_checkers():
+    import t2v_hip as H
+    return {
+        'frames': (lambda v: H._frame_counts(v, 2, 8, 'cpu'),
+                   "every utterance needs 1 <= frames <= 8, got %s", "every utterance needs 1 <= frames <= 8, got %s"),
+        'frames4': (lambda v: H._frame_counts(v, 2, 8, 'cpu', min_frames=4),
+                    "every utterance needs 4 <= frames <= 8, got %s", "every utterance needs 4 <= frames <= 8, got %s"),
+        'dtw': (lambda v: H._dtw_lengths(v, 2, 8, 'nx'), "mel_dtw: nx must be 2 integer frame counts, got %s",
+                "mel_dtw: every nx must be in 1..8 (8 frames stored, at most 2048 supported), got %s"),
+        'f0': (lambda v: H._f0_lengths(v, 2, 8), "f0: lengths must be 2 integer sample counts, got %s",
+               "f0: every length must be in 1..8 (samples stored per row), got %s"),
+        'align': (lambda v: H._align_lengths(v, 2, 8, 'n_frames', 'frame'),
+                  "alignment_stats: n_frames must be 2 integer frame counts, got %s",
+                  "alignment_stats: every n_frames must be in 1..8 (frames stored per row), got %s"),
+    }
+
+
+@pytest.mark.parametrize("who", ['frames', 'frames4', 'dtw', 'f0', 'align'])
+def test_checked_lengths_messages_of_every_caller(who):
+    check, count_msg, range_msg = _length_checkers()[who]
+    for bad, msg in (([5, 6, 7], count_msg), ([0, 5], range_msg), ([5, 9], range_msg)):
+        with pytest.raises(ValueError) as e:
+            check(bad)
+        assert str(e.value) == msg % (bad,)
+    # a float tensor: the vocoder's frame counts have always been let in (compared and stored truncated); the others refuse
+    fl = torch.tensor([5.0, 6.0])
+    if who in ('frames', 'frames4'):
+        out = check(fl)
+        assert out.dtype == torch.int32 and out.tolist() == [5, 6]
+        with pytest.raises(ValueError) as e:
+            check(torch.tensor([5.0, 9.5]))
+        assert str(e.value) == range_msg % ([5.0, 9.5],)
+    else:
+        with pytest.raises(ValueError) as e:
+            check(fl)
+        assert str(e.value) == count_msg % ([5.0, 6.0],)
+    # bool tensors: f0 and alignment_stats refuse them, mel_dtw and the vocoder read them as 0 / 1
+    bl = torch.tensor([True, True])
+    if who in ('f0', 'align'):
+        with pytest.raises(ValueError) as e:
+            check(bl)
+        assert str(e.value) == count_msg % ([True, True],)
+    elif who != 'frames4':
+        assert check(bl).tolist() == [1, 1]
+    for ok in ([5, 8], torch.tensor([5, 8]), torch.tensor([5, 8], dtype=torch.int64), torch.tensor([5, 8], dtype=torch.int32)):
+        out = check(ok)
+        assert out.dtype == torch.int32 and out.device.type == 'cpu' and out.tolist() == [5, 8]
+
+
+def test_checked_lengths_messages_of_stft_polar():
+    """stft_polar's own bounds (more than n_fft / 2 samples) and its two leniencies: None means all, and the counts keep the
+    type they came in"""
+    import t2v_hip as H
+    check = lambda v, N=1600: H._stft_lengths(v, 2, N)
+    msg = "stft: every utterance needs 512 < n_samples <= 1600, got %s"
+    for bad in ([600, 800, 1000], [512, 800], [800, 1601], torch.tensor([400.0, 600.0])):
+        with pytest.raises(ValueError) as e:
+            check(bad)
+        assert str(e.value) == msg % (bad.tolist() if torch.is_tensor(bad) else bad,)
+    assert check(None).dtype == torch.int64 and check(None).tolist() == [1600, 1600]
+    for ok in ([513, 1600], torch.tensor([513, 1600]), torch.tensor([513, 1600], dtype=torch.int64),
+               torch.tensor([513, 1600], dtype=torch.int32), torch.tensor([513.0, 1600.0])):
+        out = check(ok)
+        assert out.tolist() == [513, 1600] and out.device.type == 'cpu'
+        assert out.dtype == (ok.dtype if torch.is_tensor(ok) else torch.int64)
+    assert H._frame_counts(None, 3, 7, 'cpu').tolist() == [7, 7, 7]
+
+
+@pytest.mark.parametrize("with_pre", [False, True])
+def test_dw_groups_describe_the_five_products_once(with_pre):
+    """DecoderCore._dw_groups is the only description of the LSTM weight-gradient products: two groups (attention_rnn: two products,
+    three with the Prenet folded in; decoder_rnn: two), every output a view of its gradient tensor"""
+    import t2v_hip as H
+    T, B = 3, 2
+    TB = T * B
+    DGA, DGD = torch.randn(T, B, H.G4), torch.randn(T, B, H.G4)
+    XS = torch.randn(T + 2, B, H.XW)
+    wg = [torch.zeros(H.G4, H.PRE + H.E), torch.zeros(H.G4, H.H), torch.zeros(H.G4, H.KATT), torch.zeros(H.G4, H.H)]
+    pre_c = torch.randn(TB, H.PRE) if with_pre else None
+    groups = H.DecoderCore._dw_groups(DGA, DGD, XS, wg, pre_c, T, B)
+    assert len(groups) == 2 and [len(parts) for _, parts in groups] == [3 if with_pre else 2, 2]
+    (ga, att), (gd, dec) = groups
+    assert ga.shape == gd.shape == (H.G4, TB)
+    assert torch.equal(ga, DGA.view(TB, H.G4).t()) and torch.equal(gd, DGD.view(TB, H.G4).t())
+    x_prev, x_cur = XS[0:T].reshape(TB, H.XW), XS[1:T + 1].reshape(TB, H.XW)
+    want_att = [(x_prev[:, :H.H], (H.G4, H.H)), (x_prev[:, H.H:H.KATT], (H.G4, H.E))]
+    if with_pre:
+        want_att.insert(0, (pre_c, (H.G4, H.PRE)))
+    want_dec = [(x_cur[:, :H.KATT], (H.G4, H.KATT)), (x_cur[:, H.KATT:], (H.G4, H.H))]
+    for parts, want in ((att, want_att), (dec, want_dec)):
+        for (xt, out), (x, shape) in zip(parts, want):
+            assert xt.shape == (x.shape[1], TB) and torch.equal(xt, x.t()) and tuple(out.shape) == shape
+    # the outputs alias the gradient tensors: written through the views, every column is reached exactly once (without the Prenet
+    # the columns [:, :PRE] of d_w_ih_att belong to nobody here)
+    outs = [out for _, parts in groups for _, out in parts]
+    for k, out in enumerate(outs):
+        out.fill_(k + 1.0)
+    d_w_ih_att, d_w_hh_att, d_w_ih_dec, d_w_hh_dec = wg
+    k0 = 1 if with_pre else 0
+    assert (d_w_ih_att[:, :H.PRE] == (1.0 if with_pre else 0.0)).all()
+    assert (d_w_hh_att == k0 + 1.0).all() and (d_w_ih_att[:, H.PRE:] == k0 + 2.0).all()
+    assert (d_w_ih_dec == k0 + 3.0).all() and (d_w_hh_dec == k0 + 4.0).all()
