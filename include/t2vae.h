@@ -810,6 +810,41 @@ int t2v_alignment_stats(const float* A, long long a_stride_b, long long a_stride
                         int path_stride, float* mass, int mass_stride, float* focus, int32_t* stats, void* scratch,
                         void* stream);
 
+/* ------------------------------------------------------------------ wavs at any rate: resample, trim, crop
+ * The stage in front of the mel front end (csrc/resample.hip).
+ *
+ * t2v_resample: polyphase resampling of B rows by the rational ratio up / down (lowest terms).  x is (B, x_stride), fp32 or,
+ * with x_is_pcm16, int16 PCM multiplied by `scale` (1 / 32768) as it is loaded (scale is ignored for fp32); row b has n[b]
+ * samples (device int32), every sample index outside [0, n[b]) counts as 0 and nothing outside is read.  taps: the device
+ * table t[0 .. 2 half] the caller made (fp32).  With n_out[b] = ceil(n[b] up / down):
+ *   y[b][m] = sum_i t[m down - i up + half] x[b][i]   over 0 <= i < n[b] and tap index in 0 .. 2 half,   m < n_out[b],
+ * y (B, out_stride) fp32 is 0 from n_out[b] to out_stride.
+ * The order of every sum depends on m alone: a row gives the same bits alone, in any batch and at any stride.
+ * up == down launches nothing and writes nothing.  A null pointer, B < 1, a stride < 1 or above 2^30, up or down < 1, half < 1
+ * or out_stride < ceil(x_stride up / down) is T2V_ERR_ARG; a table of more than T2V_RESAMPLE_MAX_TAPS entries (2 half + 1), or
+ * up > 2 half, is T2V_ERR_DIMS.  The lengths are the caller's to check on the host; the kernel clamps a length to 0..x_stride.
+ *
+ * t2v_trim_bounds: energy trim on the front end's grid.  Frame t of row b covers the samples [256 t - 512, 256 t + 512) (0
+ * outside [0, n)), ms[t] is its mean square, a row has n / 256 + 1 frames, ref = max_t ms[t].  A frame sounds when ref > 0 and
+ * ms[t] > ref 10^(-top_db / 10).  With first / last the outermost sounding frames: bounds[b] = (256 max(0, first - pad_frames),
+ * min(n, 256 (last + 1 + pad_frames))); a row with no sounding frame keeps (0, n).  bounds is (B, 2) int32; ms is
+ * (B, ms_stride) fp32 scratch of the caller's that holds the frames' mean squares afterwards (0 past a row's frame count).
+ * A frame's sum has a fixed order.  A null pointer, B < 1, y_stride < 1 or ms_stride < y_stride / 256 + 1 is T2V_ERR_ARG;
+ * top_db <= 0 or pad_frames outside 0..2^20 is T2V_ERR_DIMS.
+ *
+ * t2v_crop_rows: out[b][c] = y[b][start + c] for c < end - start, 0 up to out_stride, (start, end) = bounds[b] clamped to
+ * 0 <= start <= end <= y_stride; out of place.  out is fp32, or with out_is_pcm16 int16: y 32768 rounded to nearest-even and
+ * clamped to [-32768, 32767].  stats (int16 form only, may be null) is (B, 2) int32: the count of samples of [start, end) that
+ * were clamped, and the bit pattern of the fp32 max |y| over them.  Columns past out_stride are not written but are counted.
+ * A null pointer, B < 1, a stride < 1 or stats with fp32 output is T2V_ERR_ARG. */
+#define T2V_RESAMPLE_MAX_TAPS 32768
+int t2v_resample(const void* x, int x_is_pcm16, float scale, const int32_t* n, int x_stride, int B, const float* taps, int up,
+                 int down, int half, float* y, int out_stride, void* stream);
+int t2v_trim_bounds(const float* y, const int32_t* n, int y_stride, int B, float top_db, int pad_frames, float* ms, int ms_stride,
+                    int32_t* bounds, void* stream);
+int t2v_crop_rows(const float* y, int y_stride, const int32_t* bounds, int B, void* out, int out_is_pcm16, int out_stride,
+                  int32_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

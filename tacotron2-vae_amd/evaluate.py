@@ -56,6 +56,8 @@ def build_arg_parser():
                         "reach, end_reach, back_share, jump_share, stall_frames, uncovered_share, gap_symbols and n_symbols; "
                         "the summary their means and read_through_share")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
+    from wavio import add_wav_arguments
+    add_wav_arguments(p)
     return p
 
 
@@ -92,7 +94,8 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    syn = Synthesizer(hp)
+    from wavio import wav_options
+    syn = Synthesizer(hp, **wav_options(args))
     if args.condition == 'emotion':
         syn.load(args.load_path, vocoder=args.vocoder if args.prosody else None, filelist_path=args.filelist_path)
     else:

@@ -25,6 +25,8 @@ def build_arg_parser():
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     p.add_argument('--tsne', nargs='?', const='mus', default=None, choices=('mus', 'zs', 'prosody'),
                    help="also store the t-SNE map of this array (default mus) as tsne, tsne_kl")
+    from wavio import add_wav_arguments
+    add_wav_arguments(p)
     return p
 
 
@@ -57,7 +59,8 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    syn = Synthesizer(hp).load_checkpoint(args.load_path)
+    from wavio import wav_options
+    syn = Synthesizer(hp, **wav_options(args)).load_checkpoint(args.load_path)
     paths, emotions = read_filelist(args.filelist_path)
     prosody, mu, logvar, z = (t.cpu().numpy() for t in syn.latents(paths, args.batch_size))
     out = dict(prosody=prosody, mus=mu, logvars=logvar, zs=z, emotions=emotions, paths=np.array(paths))

@@ -1,0 +1,205 @@
+"""Corpus preparation: a filelist of wavs at any sampling rate becomes a training-ready one — every wav resampled to the
+front end's rate, trimmed of leading and trailing silence and written as 16-bit PCM, on the device (t2v_hip.resample,
+trim_bounds, crop; csrc/resample.hip).
+
+    python prepare_corpus.py --filelist_path F --out_dir D --out_filelist F2
+           [--sampling_rate 16000] [--trim_db 40 | --no_trim] [--pad_frames 2] [--batch_size 64] [--report R.json]
+
+Filelist rows are `path|text|speaker|emotion` (any column count, the path first).  Each wav is read as it lies in the file
+(int16 goes to the device as it is; int32 and float wavs are scaled to [-1, 1) on the host; a wav with more than one channel
+is skipped, with its reason in the report), and the rows run in length-sorted ragged batches of at most --batch_size, one
+resample launch per distinct source rate in a batch.  D/<basename>.wav is written at the target rate (a basename that
+several rows share gets its parent directories prefixed), F2 holds the new paths with the other columns untouched, in the
+order of F, without the skipped rows.  The report (R.json, default D/report.json) has per row: source rate, samples in and
+out, seconds trimmed at head and tail, peak, clipped samples and the all-silent flag; and totals by source rate."""
+import argparse
+import json
+import os
+
+DEFAULT_BATCH_SIZE = 64
+DEFAULT_SAMPLING_RATE = 16000
+
+
+def build_arg_parser():
+    from wavio import DEFAULT_PAD_FRAMES, DEFAULT_TRIM_DB
+    p = argparse.ArgumentParser(description="filelist of wavs at any rate -> resampled, trimmed 16-bit wavs and their filelist")
+    p.add_argument('--filelist_path', required=True, help="rows path|... (the wav's path first)")
+    p.add_argument('--out_dir', required=True, help="directory of the prepared wavs")
+    p.add_argument('--out_filelist', required=True, help="the filelist with the prepared wavs' paths")
+    p.add_argument('--sampling_rate', type=int, default=DEFAULT_SAMPLING_RATE, help="target rate in Hz")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument('--trim_db', type=float, default=DEFAULT_TRIM_DB, metavar='DB',
+                   help="trim frames more than DB dB below the wav's loudest frame from both ends")
+    g.add_argument('--no_trim', action='store_true', help="resample only")
+    p.add_argument('--pad_frames', type=int, default=DEFAULT_PAD_FRAMES, help="frames of 256 samples kept around what sounds")
+    p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="wavs per ragged batch")
+    p.add_argument('--report', default=None, help="report .json (default <out_dir>/report.json)")
+    return p
+
+
+def parse_args(argv=None):
+    args = build_arg_parser().parse_args(argv)
+    if args.batch_size < 1:
+        raise SystemExit("--batch_size must be >= 1")
+    if args.sampling_rate < 1:
+        raise SystemExit("--sampling_rate must be >= 1")
+    if args.pad_frames < 0:
+        raise SystemExit("--pad_frames must be >= 0")
+    if not args.no_trim and not 0.0 < args.trim_db < float('inf'):
+        raise SystemExit("--trim_db must be a positive number of dB")
+    if args.report is None:
+        args.report = os.path.join(args.out_dir, 'report.json')
+    return args
+
+
+def read_rows(path):
+    """the rows of a filelist as lists of columns (path first), blank lines dropped"""
+    with open(path, encoding='utf-8') as f:
+        return [line.rstrip('\r\n').split('|') for line in f if line.strip()]
+
+
+def output_names(paths):
+    """<basename>.wav for every path, unique: a basename that several paths share gets as many parent directories prefixed
+    (joined by '_') as it takes to tell them apart, and what still collides (the same path twice) a running number"""
+    def parts(p):
+        p = os.path.normpath(p)
+        stem = os.path.splitext(os.path.basename(p))[0]
+        dirs = [d for d in os.path.dirname(p).split(os.sep) if d not in ('', '.')]
+        return dirs, stem
+
+    split = [parts(p) for p in paths]
+    depth = [0] * len(paths)
+
+    def name(i):
+        dirs, stem = split[i]
+        return '_'.join(dirs[len(dirs) - depth[i]:] + [stem]) if depth[i] else stem
+
+    while True:
+        seen = {}
+        for i in range(len(paths)):
+            seen.setdefault(name(i), []).append(i)
+        grew = False
+        for idx in seen.values():
+            if len(idx) > 1:
+                for i in idx:
+                    if depth[i] < len(split[i][0]):
+                        depth[i] += 1
+                        grew = True
+        if not grew:
+            break
+    out, used = [], {}
+    for i in range(len(paths)):
+        base = name(i)
+        k = used.get(base, 0)
+        used[base] = k + 1
+        out.append((base if k == 0 else "%s_%d" % (base, k)) + '.wav')
+    if len(set(out)) != len(out):        # a running number that meets another row's own name
+        out = ["%06d_%s" % (i, n) for i, n in enumerate(out)]
+    return out
+
+
+def rewrite_rows(rows, new_paths):
+    """the rows with their first column replaced (None: the row is dropped), as filelist lines"""
+    return ['|'.join([p] + list(r[1:])) for r, p in zip(rows, new_paths) if p is not None]
+
+
+def summarize(records):
+    """totals by source rate of the per-row records"""
+    by_rate = {}
+    for r in records:
+        if r.get('skipped'):
+            continue
+        t = by_rate.setdefault(str(r['source_rate']), dict(rows=0, seconds_in=0.0, seconds_out=0.0, seconds_trimmed=0.0,
+                                                           clipped_samples=0, all_silent=0, peak_max=0.0))
+        t['rows'] += 1
+        t['seconds_in'] += r['samples_in'] / float(r['source_rate'])
+        t['seconds_out'] += r['samples_out'] / float(r['target_rate'])
+        t['seconds_trimmed'] += r['trimmed_head_s'] + r['trimmed_tail_s']
+        t['clipped_samples'] += r['clipped_samples']
+        t['all_silent'] += int(r['all_silent'])
+        t['peak_max'] = max(t['peak_max'], r['peak'])
+    return by_rate
+
+
+def process_batch(items, target_rate, trim_db, pad_frames):
+    """items: [(source rate, samples (int16 or float32 numpy))].  Returns per item (int16 numpy samples, record fields):
+    resample (one launch per distinct (rate, format)) -> trim_bounds -> crop to int16, as one ragged batch."""
+    import t2v_hip
+    from synthesizer import resample_rows
+    y, n = resample_rows(items, target_rate)
+    if trim_db is None:
+        bounds = [[0, k] for k in n]
+    else:
+        bounds = t2v_hip.trim_bounds(y, n, trim_db, pad_frames).cpu().tolist()
+    pcm, counts, stats = t2v_hip.crop(y, bounds, pcm16=True, return_stats=True)
+    pcm = pcm.cpu().numpy()
+    out = []
+    for b, (rate, data) in enumerate(items):
+        start, end = bounds[b]
+        clipped, peak = stats[b]
+        out.append((pcm[b, :counts[b]].copy(),
+                    dict(source_rate=rate, target_rate=target_rate, samples_in=int(len(data)), samples_resampled=n[b],
+                         samples_out=counts[b], trimmed_head_s=start / float(target_rate),
+                         trimmed_tail_s=(n[b] - end) / float(target_rate), peak=peak, clipped_samples=clipped,
+                         all_silent=bool(peak == 0.0))))
+    return out
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from scipy.io.wavfile import write
+    import t2v_hip
+    from synthesizer import length_groups
+    from wavio import read_wav, wav_header
+    rows = read_rows(args.filelist_path)
+    if not rows:
+        raise SystemExit("%s: no rows" % args.filelist_path)
+    os.makedirs(args.out_dir, exist_ok=True)
+    names = output_names([r[0] for r in rows])
+    records = [None] * len(rows)
+    lengths, keep = [], []
+    for i, r in enumerate(rows):
+        try:
+            rate, count, channels = wav_header(r[0])
+            if channels != 1:
+                raise ValueError("%d channels; only mono wavs are prepared" % channels)
+            if count < 1:
+                raise ValueError("no samples")
+            t2v_hip.resample_taps(rate, args.sampling_rate)             # a ratio outside the table limit is this row's reason
+            lengths.append(t2v_hip.resample_length(count, *t2v_hip.resample_ratio(rate, args.sampling_rate)))
+            keep.append(i)
+        except (ValueError, OSError) as e:
+            records[i] = dict(path=r[0], skipped=str(e))
+    new_paths = [None] * len(rows)
+    for idx in length_groups(lengths, args.batch_size):
+        group, items = [], []
+        for k in idx:
+            i = keep[k]
+            try:
+                items.append(read_wav(rows[i][0]))
+                group.append(i)
+            except (ValueError, OSError) as e:
+                records[i] = dict(path=rows[i][0], skipped=str(e))
+        if not items:
+            continue
+        done = process_batch(items, args.sampling_rate, None if args.no_trim else args.trim_db, args.pad_frames)
+        for i, (pcm, rec) in zip(group, done):
+            new_paths[i] = os.path.join(args.out_dir, names[i])
+            write(new_paths[i], args.sampling_rate, pcm)
+            records[i] = dict(rec, path=rows[i][0], out_path=new_paths[i])
+    with open(args.out_filelist, 'w', encoding='utf-8') as f:
+        for line in rewrite_rows(rows, new_paths):
+            f.write(line + '\n')
+    n_skipped = sum(1 for r in records if r.get('skipped'))
+    report = dict(target_rate=args.sampling_rate, trim_db=None if args.no_trim else args.trim_db, pad_frames=args.pad_frames,
+                  n_rows=len(rows), n_written=len(rows) - n_skipped, n_skipped=n_skipped, by_source_rate=summarize(records),
+                  rows=records)
+    with open(args.report, 'w', encoding='utf-8') as f:
+        json.dump(report, f, indent=1)
+    print("%s: %d wavs at %d Hz, %d skipped; %s" % (args.out_filelist, len(rows) - n_skipped, args.sampling_rate, n_skipped,
+                                                   args.report))
+    return report
+
+
+if __name__ == "__main__":
+    main()

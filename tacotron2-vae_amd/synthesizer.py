@@ -37,6 +37,33 @@ def wav_num_samples(path):
     return len(read(path, mmap=True)[1])
 
 
+def resample_rows(items, target_rate):
+    """items: [(sampling rate, 1-D numpy samples: int16 PCM or float32 in [-1, 1))], as `wavio.read_wav` gives them.  Returns
+    (y (B, max count) float32 on the device, zero-padded, in the order of the items; counts at target_rate): the rows are
+    grouped by (source rate, sample format), one upload and one `t2v_hip.resample` launch per group; a row's bits do not
+    depend on its group."""
+    import t2v_hip
+    groups = {}
+    for b, (rate, data) in enumerate(items):
+        groups.setdefault((rate, data.dtype.str), []).append(b)
+    parts, n = [], [0] * len(items)
+    for (rate, _), idx in groups.items():
+        counts = [len(items[b][1]) for b in idx]
+        x = np.zeros((len(idx), max(counts)), dtype=items[idx[0]][1].dtype)
+        for k, b in enumerate(idx):
+            x[k, :counts[k]] = items[b][1]
+        y_g, n_g = t2v_hip.resample(torch.from_numpy(x).cuda(), counts, rate, target_rate)
+        parts.append((idx, y_g))
+        for b, k in zip(idx, n_g):
+            n[b] = k
+    if len(parts) == 1:                                   # one group holds the items in their order
+        return parts[0][1], n
+    y = torch.zeros(len(items), max(n), device=parts[0][1].device)
+    for idx, y_g in parts:
+        y[torch.tensor(idx, device=y.device), :y_g.size(1)] = y_g
+    return y, n
+
+
 VOCODERS = ('griffin_lim', 'griffin_lim_fast')
 
 
@@ -90,13 +117,24 @@ class GriffinLimVocoder(object):
 
 
 class Synthesizer(object):
-    def __init__(self, hparams=None):
+    def __init__(self, hparams=None, resample=False, trim_db=None):
+        """resample: wavs at any sampling rate are resampled to hparams.sampling_rate on the device (`t2v_hip.resample`)
+        instead of being refused; trim_db: leading and trailing silence is cut from every wav that is read
+        (`t2v_hip.trim_bounds` at that many dB below the wav's loudest frame, 2 frames of margin, then `t2v_hip.crop`).
+        Both are off by default, and both act in `load_wavs`, through which every method here reads its wavs."""
         if hparams is None:             # the reference's constructor (synthesizer.py:47-51): defaults + two overrides
             hparams = create_hparams()
             hparams.sampling_rate = 16000
             hparams.max_decoder_steps = 600
         self.hparams = hparams
         hp = self.hparams
+        if trim_db is not None:
+            trim_db = float(trim_db)
+            if not 0.0 < trim_db < float('inf'):
+                raise ValueError("trim_db must be a positive number of dB, got %r" % (trim_db,))
+            if hp.hop_length != 256:
+                raise ValueError("trim_db: the trim is built for hop 256, the front end has hop %d" % hp.hop_length)
+        self.resample, self.trim_db = bool(resample), trim_db
         self.stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels,
                                  hp.sampling_rate, hp.mel_fmin, hp.mel_fmax)
         self.model = None
@@ -105,6 +143,9 @@ class Synthesizer(object):
 
     # ------------------------------------------------------------------ audio -> mel (synthesizer.py:57-68)
     def load_mel(self, path):
+        if self.resample or self.trim_db is not None:
+            y, n = self.load_wavs([path])
+            return self.stft.mel_spectrogram(y[:, :n[0]])
         audio, sampling_rate = load_wav_to_torch(path)
         if sampling_rate != self.hparams.sampling_rate:
             raise ValueError("{} SR doesn't match target {} SR".format(sampling_rate, self.hparams.sampling_rate))
@@ -113,7 +154,27 @@ class Synthesizer(object):
 
     def load_wavs(self, paths):
         """the wavs as one zero-padded batch on the device: (y (B, S_max) float32 in [-1, 1), sample counts); a wav whose rate
-        is not hparams.sampling_rate is a ValueError"""
+        is not hparams.sampling_rate is a ValueError, unless the Synthesizer was made with resample=True: then every wav is
+        resampled to it on the device, one `t2v_hip.resample` launch per distinct source rate, and the counts are the
+        resampled ones.  With trim_db the batch is trimmed and cropped before it is returned, and the counts are the trimmed
+        ones."""
+        if self.resample:
+            y, n = self._load_wavs_any_rate(list(paths))
+        else:
+            y, n = self._load_wavs_at_rate(paths)
+        if self.trim_db is not None:
+            import t2v_hip
+            from wavio import DEFAULT_PAD_FRAMES
+            y, n = t2v_hip.crop(y, t2v_hip.trim_bounds(y, n, self.trim_db, DEFAULT_PAD_FRAMES))
+        return y, n
+
+    def _load_wavs_any_rate(self, paths):
+        from wavio import read_wav
+        if not paths:
+            raise ValueError("load_wavs: no paths")
+        return resample_rows([read_wav(path) for path in paths], self.hparams.sampling_rate)
+
+    def _load_wavs_at_rate(self, paths):
         audios = []
         for path in paths:
             audio, sampling_rate = load_wav_to_torch(path)
@@ -127,6 +188,20 @@ class Synthesizer(object):
         for b, a in enumerate(audios):
             y[b, :n[b]] = a
         return y.cuda(), n
+
+    def wav_lengths(self, paths):
+        """sample counts of the wavs as `load_wavs` will count them before any trim, from their headers: the file's count, or
+        with resample=True ceil(count up / down) at the front end's rate; what the length sorting of `latents` and `pitch`
+        goes by"""
+        if not self.resample:
+            return [wav_num_samples(p) for p in paths]
+        import t2v_hip
+        from wavio import wav_header
+        out = []
+        for p in paths:
+            rate, count, _ = wav_header(p)
+            out.append(t2v_hip.resample_length(count, *t2v_hip.resample_ratio(rate, self.hparams.sampling_rate)))
+        return out
 
     def _mels_of(self, y, n):
         mels = self.stft.mel_spectrogram(y, torch.tensor(n, dtype=torch.int64))
@@ -153,7 +228,7 @@ class Synthesizer(object):
             raise ValueError("pitch: the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
                              % (t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
         tracks = [None] * len(paths)
-        for idx in length_groups([wav_num_samples(p) for p in paths], batch_size):
+        for idx in length_groups(self.wav_lengths(paths), batch_size):
             y, n = self.load_wavs([paths[i] for i in idx])
             hz = t2v_hip.f0(y, n)
             for b, i in enumerate(idx):
@@ -169,7 +244,7 @@ class Synthesizer(object):
         if not paths:
             raise ValueError("latents: no paths")
         parts, order = [], []
-        for idx in length_groups([wav_num_samples(p) for p in paths], batch_size):
+        for idx in length_groups(self.wav_lengths(paths), batch_size):
             mels, n = self.load_mels([paths[i] for i in idx])
             parts.append(self.model.vae_gst(mels, n))
             order += idx
@@ -494,6 +569,8 @@ def build_arg_parser():
     p.add_argument('--filelist_path', default='./web/static/uploads/koemo_spk_emo_all_test.txt',
                    help="reference utterances of the emotion centroids (or their cache next to the checkpoint)")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
+    from wavio import add_wav_arguments
+    add_wav_arguments(p)
     return p
 
 
@@ -516,13 +593,14 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
+    from wavio import wav_options
     args = parse_args(argv)
     hp = create_hparams()
     hp.sampling_rate = 16000                 # the reference's Synthesizer() overrides (synthesizer.py:47-51)
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    syn = Synthesizer(hp).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
+    syn = Synthesizer(hp, **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
     os.makedirs(args.sample_path, exist_ok=True)
     texts = args.texts
     for i0 in range(0, len(texts), args.batch_size):

@@ -104,7 +104,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
            't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
            't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes',
-           't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes')
+           't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes',
+           't2v_resample', 't2v_trim_bounds', 't2v_crop_rows')
 
 
 def lib_path():
@@ -245,6 +246,9 @@ def load_library():
     lib.t2v_tsne_gradient.argtypes = [vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
     lib.t2v_tsne_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
     lib.t2v_f0_yin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp]
+    lib.t2v_resample.argtypes = [vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
+    lib.t2v_trim_bounds.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp]
+    lib.t2v_crop_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.t2v_alignment_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_alignment_scratch_bytes.restype = C.c_size_t
     lib.t2v_alignment_stats.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp,
@@ -1744,6 +1748,153 @@ def f0(y, lengths, fmin=60.0, fmax=500.0, threshold=0.1, return_aperiodicity=Fal
     if T < stride:
         hz, ap = hz[:, :T].contiguous(), ap[:, :T].contiguous()
     return (hz, ap) if return_aperiodicity else hz
+
+
+RESAMPLE_MAX_TAPS = 32768               # T2V_RESAMPLE_MAX_TAPS of include/t2vae.h
+TRIM_HOP = 256                          # the trim's frames are the front end's: hop 256, window 1024
+_RESAMPLE_TAPS = {}                     # (up, down, zeros, beta, rolloff) -> (half, host taps, {device: device taps})
+
+
+def resample_ratio(sr_in, sr_out):
+    """(up, down) of sr_in -> sr_out in lowest terms; ValueError unless both are positive integers"""
+    if isinstance(sr_in, bool) or isinstance(sr_out, bool) or int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
+        raise ValueError("resample: the rates must be positive integers, got %r -> %r" % (sr_in, sr_out))
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    g = math.gcd(sr_in, sr_out)
+    return sr_out // g, sr_in // g
+
+
+def resample_length(n, up, down):
+    """ceil(n up / down): the samples t2v_resample gives for n"""
+    return -((-int(n) * up) // down)
+
+
+def resample_taps(sr_in, sr_out, zeros=16, beta=8.6, rolloff=0.95):
+    """(up, down, half, taps) of resample(): the ratio in lowest terms and the Kaiser-windowed sinc t[0 .. 2 half] = up g, with
+    g[k] = fc sinc(fc (k - half)) kaiser_beta(k) normalised to sum 1, half = zeros max(up, down), fc = rolloff / max(up, down),
+    made in fp64 with numpy and rounded to fp32 once (a read-only host array, cached per argument tuple).  g is the `window`
+    with which scipy.signal.resample_poly(x, up, down) computes the same outputs.  ValueError, naming the ratio, when the
+    table would exceed RESAMPLE_MAX_TAPS entries."""
+    import numpy as np
+    up, down = resample_ratio(sr_in, sr_out)
+    zeros, beta, rolloff = int(zeros), float(beta), float(rolloff)
+    if zeros < 1 or beta < 0.0 or not 0.0 < rolloff <= 1.0:
+        raise ValueError("resample_taps: zeros %r >= 1, beta %r >= 0 and 0 < rolloff %r <= 1 are supported" % (zeros, beta, rolloff))
+    key = (up, down, zeros, beta, rolloff)
+    hit = _RESAMPLE_TAPS.get(key)
+    if hit is None:
+        half = zeros * max(up, down)
+        if 2 * half + 1 > RESAMPLE_MAX_TAPS:
+            raise ValueError("resample: %d -> %d Hz is the ratio %d/%d, whose table of %d taps exceeds the %d supported"
+                             % (sr_in, sr_out, up, down, 2 * half + 1, RESAMPLE_MAX_TAPS))
+        fc = rolloff / max(up, down)
+        k = np.arange(2 * half + 1, dtype=np.float64)
+        g = fc * np.sinc(fc * (k - half)) * np.kaiser(2 * half + 1, beta)
+        g /= g.sum()
+        taps = (up * g).astype(np.float32)
+        taps.setflags(write=False)
+        hit = _RESAMPLE_TAPS[key] = (half, taps, {})
+    return up, down, hit[0], hit[1]
+
+
+def _wave_lengths(lengths, B, S, who):
+    return _checked_lengths(lengths, B, 1, S, "%s: lengths must be %d integer sample counts" % (who, B),
+                            "%s: every length must be in 1..%d (samples stored per row)" % (who, S))
+
+
+def resample(x, lengths, sr_in, sr_out):
+    """Polyphase resampling sr_in -> sr_out (csrc/resample.hip k_resample): x (B, S) float32 in [-1, 1) or int16 PCM (scaled by
+    1 / 32768 as it is loaded) CUDA tensor, row b of lengths[b] samples (a list, a CPU tensor or a device int tensor); samples
+    outside a row's length count as 0 and are not read.  Returns (y (B, max n_out) float32, n_out: the host list of
+    ceil(lengths[b] up / down)); y is 0 past each n_out.  What is computed is `resample_taps`' filter applied as
+    scipy.signal.resample_poly does.  Equal rates launch nothing: float32 comes back as it is, int16 scaled.  A row gives
+    the same bits alone, in any batch and at any stride."""
+    lib = _require_gpu(x)
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.int16):
+        raise ValueError("resample: x must be a float32 or int16 (B, S) tensor, got %s %s" % (x.dtype, tuple(x.shape)))
+    B, S = x.shape
+    if B < 1 or S < 1:
+        raise ValueError("resample: empty input %s" % (tuple(x.shape),))
+    up, down, half, taps = resample_taps(sr_in, sr_out)
+    n = _wave_lengths(lengths, B, S, "resample")
+    if up == down:
+        return (x.contiguous() if x.dtype == torch.float32 else x.float() * (1.0 / 32768.0)), n.tolist()
+    n_out = [resample_length(k, up, down) for k in n.tolist()]
+    stride = resample_length(S, up, down)
+    if S > (1 << 30) or stride > (1 << 30):
+        raise ValueError("resample: rows of %d samples (%d after resampling) exceed the 2^30 supported" % (S, stride))
+    dev_taps = _RESAMPLE_TAPS[(up, down, 16, 8.6, 0.95)][2]
+    t = dev_taps.get(x.device)
+    if t is None:
+        t = dev_taps[x.device] = torch.from_numpy(taps.copy()).to(x.device)
+    x = x.contiguous()
+    y = torch.empty(B, stride, device=x.device, dtype=torch.float32)
+    _check(lib.t2v_resample(_p(x), int(x.dtype == torch.int16), 1.0 / 32768.0, _p(n.to(x.device)), S, B, _p(t), up, down, half,
+                            _p(y), stride, _stream()), 't2v_resample')
+    if max(n_out) < stride:
+        y = y[:, :max(n_out)].contiguous()
+    return y, n_out
+
+
+def trim_bounds(y, lengths, top_db=40.0, pad_frames=2):
+    """Where each row sounds (csrc/resample.hip k_trim_ms, k_trim_bounds): y (B, S) float32 CUDA tensor, row b of lengths[b]
+    samples.  Frames as the mel front end's (hop 256, window 1024 centred on 256 t, lengths[b] // 256 + 1 of them); a frame
+    sounds when its mean square exceeds the row's loudest frame's by more than -top_db dB.  Returns a device int32 (B, 2)
+    tensor of (start, end): 256 max(0, first - pad_frames) and min(lengths[b], 256 (last + 1 + pad_frames)) for the outermost
+    sounding frames, (0, lengths[b]) for a row without one (all zeros)."""
+    lib = _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("trim_bounds: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("trim_bounds: empty input %s" % (tuple(y.shape),))
+    top_db = float(top_db)
+    if not 0.0 < top_db < float('inf'):
+        raise ValueError("trim_bounds: top_db %r must be positive and finite" % (top_db,))
+    if isinstance(pad_frames, bool) or int(pad_frames) != pad_frames or not 0 <= pad_frames <= (1 << 20):
+        raise ValueError("trim_bounds: pad_frames %r must be an integer in 0..2^20" % (pad_frames,))
+    n = _wave_lengths(lengths, B, S, "trim_bounds")
+    y = _f32c(y)
+    stride = S // TRIM_HOP + 1
+    ms = torch.empty(B, stride, device=y.device, dtype=torch.float32)
+    bounds = torch.empty(B, 2, device=y.device, dtype=torch.int32)
+    _check(lib.t2v_trim_bounds(_p(y), _p(n.to(y.device)), S, B, top_db, int(pad_frames), _p(ms), stride, _p(bounds), _stream()),
+           't2v_trim_bounds')
+    return bounds
+
+
+def crop(y, bounds, pcm16=False, return_stats=False):
+    """Rows cut to their bounds (csrc/resample.hip k_crop_rows): y (B, S) float32 CUDA tensor, bounds (B, 2) integers (start, end)
+    with 0 <= start <= end <= S, a device tensor (as trim_bounds gives it), a CPU tensor or a list.  Returns (out, counts): out
+    (B, max(end - start)) with y[b, start:end] from column 0 and zeros behind it, counts the host list of end - start.
+    pcm16: out is int16, y 32768 rounded to nearest-even and clamped to [-32768, 32767]; with return_stats (pcm16 only) a third
+    value, the host list of (clipped samples, max |y|) per row, over [start, end)."""
+    lib = _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("crop: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("crop: empty input %s" % (tuple(y.shape),))
+    if return_stats and not pcm16:
+        raise ValueError("crop: return_stats counts what the int16 conversion clips: it needs pcm16=True")
+    bd = torch.as_tensor(bounds)
+    if bd.dtype.is_floating_point or bd.dtype == torch.bool or tuple(bd.shape) != (B, 2):
+        raise ValueError("crop: bounds must be (%d, 2) integers, got %s %s" % (B, bd.dtype, tuple(bd.shape)))
+    host = bd.cpu().to(torch.int64)
+    if int(host.min()) < 0 or int(host.max()) > S or bool((host[:, 0] > host[:, 1]).any()):
+        raise ValueError("crop: every row needs 0 <= start <= end <= %d, got %s" % (S, host.tolist()))
+    counts = (host[:, 1] - host[:, 0]).tolist()
+    width = max(max(counts), 1)
+    y = _f32c(y)
+    bd = bd.to(device=y.device, dtype=torch.int32).contiguous()
+    out = torch.empty(B, width, device=y.device, dtype=torch.int16 if pcm16 else torch.float32)
+    stats = torch.empty(B, 2, device=y.device, dtype=torch.int32) if return_stats else None
+    _check(lib.t2v_crop_rows(_p(y), S, _p(bd), B, _p(out), int(bool(pcm16)), width, _p(stats), _stream()), 't2v_crop_rows')
+    if not return_stats:
+        return out, counts
+    s = stats.cpu()
+    peaks = s[:, 1].contiguous().view(torch.float32).tolist()
+    return out, counts, [(int(c), float(p)) for c, p in zip(s[:, 0].tolist(), peaks)]
 
 
 ALIGN_FRAMES = 16                       # T2V_ALIGN_FRAMES of include/t2vae.h: frames per workgroup of k_align_scan
