@@ -845,6 +845,41 @@ int t2v_trim_bounds(const float* y, const int32_t* n, int y_stride, int B, float
 int t2v_crop_rows(const float* y, int y_stride, const int32_t* bounds, int B, void* out, int out_is_pcm16, int out_stride,
                   int32_t* stats, void* stream);
 
+/* ------------------------------------------------------------------ scores of the latent space: neighbours and class sums
+ * All distances from M query vectors to N labelled reference vectors (csrc/latent.hip), reduced per query.  R (N, D) fp32,
+ * labels (N) int32 in 0..C-1, Q (M, D) fp32; Q null means Q = R and M = N (the M argument is then ignored).
+ * exclude (M) int32 or null: reference exclude[i] is skipped for query i in every output but rank; -1 skips nothing.  With Q
+ * null and exclude null the meaning is leave-one-out, exclude[i] = i.  Exclusion is by index, never by distance: an exact
+ * duplicate of the query at another index stays a neighbour.  target (M) int32 or null; -1 means no target.
+ * d2(i, j) = sum_c (q_c - r_c)^2 from the differences, accumulated in ascending c (fused multiply-add); not the
+ * |q|^2 + |r|^2 - 2 q.r expansion, so small-integer inputs give exact distances and exact ties.  References are ordered by
+ * (d2, index) ascending: ties go to the lower index.  Per query i:
+ *   nn_idx (M, k) int32, nn_dist (M, k) fp32: the k first non-excluded references in that order, nn_dist = sqrt(d2);
+ *   class_sum (M, C) fp32:  the sum of sqrt(d2) over the non-excluded references of each class;
+ *   class_cnt (M, C) int32: their counts;
+ *   rank (M) int32: with target[i] >= 0 the number of references (excluded or not) that sort strictly before reference
+ *     target[i]; -1 where target[i] is -1 or target is null.  rank may be null when target is.
+ * N or M outside 2..T2V_LATENT_MAX_POINTS, D outside 2..64, C outside 1..T2V_LATENT_MAX_CLASSES or k outside
+ * 1..T2V_LATENT_MAX_K is T2V_ERR_DIMS.  A null required pointer (scratch included), a target without rank, k above the
+ * smallest number of non-excluded references a query can have (N - 1 when exclude is given or implied, else N), or a
+ * slice_rows that is neither 0 nor a positive multiple of T2V_LATENT_TILE is T2V_ERR_ARG.  labels, exclude and target are
+ * device data and the caller's to check on the host (labels in 0..C-1, the others in -1..N-1), and the vectors must be
+ * finite.  An index outside its range addresses nothing: it is treated as -1, and such a label is counted in no class.
+ * Nothing past row N or M of any array is read or written.
+ * Lane per query; the references are cut into slices of slice_rows rows over the workgroups (0: a length chosen from (N, M)
+ * alone) and a second kernel merges the slices in order.  The class sums are closed per T2V_LATENT_TILE references and
+ * added in ascending tile order, so no output bit depends on slice_rows.  No floating-point atomics: the order of every sum
+ * depends on N alone, and equal inputs give equal bits.
+ * scratch: t2v_latent_scratch_bytes(N, M, C, k, slice_rows) bytes of device memory (0 for sizes that are refused). */
+#define T2V_LATENT_MAX_POINTS 16384
+#define T2V_LATENT_MAX_CLASSES 8
+#define T2V_LATENT_MAX_K 32
+#define T2V_LATENT_TILE 128         /* reference rows per LDS tile and per block of the class sums */
+size_t t2v_latent_scratch_bytes(int N, int M, int C, int k, int slice_rows);
+int t2v_latent_neighbours(const float* R, const int32_t* labels, int N, int D, int C, const float* Q, int M,
+                          const int32_t* exclude, const int32_t* target, int k, int slice_rows, int32_t* nn_idx,
+                          float* nn_dist, float* class_sum, int32_t* class_cnt, int32_t* rank, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

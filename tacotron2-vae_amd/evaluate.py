@@ -2,7 +2,8 @@
 with its own recording by mel-spectral distortion with dynamic time warping (`Synthesizer.evaluate`, csrc/dtw.hip).
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
-                       [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment] [--hparams ...]
+                       [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
+                       [--style [--style_k K]] [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
@@ -30,11 +31,24 @@ symbols) and n_symbols.  Every summary dict gains, over the n_alignment rows tha
 back_share_mean, jump_share_mean, uncovered_share_mean, stall_frames_mean / _max, gap_symbols_mean / _max, n_read_through and
 read_through_share: a row reads through when its last frame attends one of the last 4 symbols, fewer than 4 consecutive
 symbols stay uncovered and at most 2 steps go back.  These thresholds are choices, not calibrated on a trained model
-(DESIGN 7h); the per-row numbers are always written, so they can be cut again (evaluation.summarize takes the thresholds)."""
+(DESIGN 7h); the per-row numbers are always written, so they can be cut again (evaluation.summarize takes the thresholds).
+
+--style asks whether the decoder obeys the latent: a collapsed posterior, or a decoder that ignores the style it is given,
+hardly moves a DTW mel distance.  Every synthesised mel is encoded again (the ragged `model.vae_gst`), and its mu is placed
+among the mu of the filelist's distinct recordings, labelled with their emotions (`t2v_hip.latent_neighbours`,
+csrc/latent.hip), the row's own recording left out of the vote.  Every row gains style_emotion (the vote of the --style_k
+nearest other recordings), style_hit (it equals the row's label), style_own_rank (how many recordings lie closer than the
+row's own: 0 means the synthesis is nearest to the clip it copied, the retrieval reading under --condition ref; it is written
+under --condition emotion too), style_own_dist and style_silhouette (against the recorded clusters); null for a row decoded
+to fewer than 2 frames.  The summary gains "style": per emotion and overall accuracy, rank0_share, rank_median and
+silhouette_mean, the 4 x 4 confusion matrix, and ref_accuracy, the leave-one-out accuracy of the recordings themselves under
+the same k: the ceiling the synthesised accuracy has to be read against.  One path under two emotion labels, or fewer than 2
+distinct recordings, is an error; --style_k is lowered to (distinct recordings - 1) when there are too few."""
 import argparse
 import json
 
 DEFAULT_BATCH_SIZE = 8
+DEFAULT_STYLE_K = 5
 CONDITIONS = ('ref', 'emotion')
 
 
@@ -55,6 +69,10 @@ def build_arg_parser():
                    help="also score the attention alignment of each synthesis (did the decoder read the text?): rows gain focus, "
                         "reach, end_reach, back_share, jump_share, stall_frames, uncovered_share, gap_symbols and n_symbols; "
                         "the summary their means and read_through_share")
+    p.add_argument('--style', action='store_true',
+                   help="also encode each synthesis again and place its mu among the recordings' (style round trip): rows gain "
+                        "style_emotion, style_hit, style_own_rank, style_own_dist and style_silhouette; the summary a style block")
+    p.add_argument('--style_k', type=int, default=DEFAULT_STYLE_K, help="neighbours of the --style vote; unused without it")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
@@ -65,6 +83,8 @@ def parse_args(argv=None):
     args = build_arg_parser().parse_args(argv)
     if args.batch_size < 1:
         raise SystemExit("--batch_size must be >= 1")
+    if not 1 <= args.style_k <= 32:
+        raise SystemExit("--style_k must be in 1..32")
     if args.limit is not None and args.limit < 1:
         raise SystemExit("--limit must be >= 1")
     return args
@@ -103,7 +123,8 @@ def main(argv=None):
         if args.prosody:
             syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft)
     rows = read_rows(args.filelist_path, args.limit)
-    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment)
+    style = dict(style=True, style_k=args.style_k) if args.style else {}
+    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment, **style)
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)]}, f, indent=1)
@@ -112,6 +133,10 @@ def main(argv=None):
         for name, st in summary['by_emotion'].items():
             print("%s: dtw_mean %s, read_through_share %s (%d of %d rows that stopped)"
                   % (name, st['dtw_mean'], st['read_through_share'], st['n_read_through'], st['n_alignment']))
+    if args.style:
+        st = summary['style']
+        print("style: accuracy %s (recordings leave-one-out %s, k = %s), own recording nearest in %s of %d rows"
+              % (st['overall']['accuracy'], st['ref_accuracy'], st['k'], st['overall']['rank0_share'], st['overall']['n_style']))
     print("%s: %d utterances" % (args.out, len(records)))
 
 

@@ -17,7 +17,16 @@ forward by more than max_jump, over the n_frames - 1 transitions), `stall_frames
 `uncovered_share` (positions whose summed weight stays under cover_min, over L) and `gap_symbols` (longest run of such
 positions).  `summarize` cuts them into `read_through_share` with END_SLACK, GAP_MIN and BACK_SLACK.  Those three and the
 kernel's max_jump = 3 and cover_min = 0.5 are choices, not measurements (no trained checkpoint exists here); the raw per-row
-numbers are always in the records, so they can be cut again."""
+numbers are always in the records, so they can be cut again.
+
+`evaluate(style=True)` adds the style round trip (`t2v_hip.latent_neighbours` on the posterior means): the synthesised mel
+is encoded again, and its mu is placed among the mu of the distinct recordings of the filelist, its own recording left out of
+the vote.  `style_emotion` is the vote of the k nearest other recordings, `style_hit` whether that is the row's label,
+`style_own_rank` how many recordings lie closer than the row's own (0: the synthesis is nearest to the clip it copied),
+`style_own_dist` the distance to it, and `style_silhouette` the silhouette of the synthesised mu against the recorded clusters
+with the row's label as its own class.  All five are None for a row decoded to fewer frames than the encoder takes (and the
+silhouette alone where it is undefined).  `summarize` adds a `style` block, whose `ref_accuracy`, the leave-one-out accuracy
+of the recordings themselves under the same k, is the ceiling the synthesised accuracy has to be read against."""
 import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
@@ -126,6 +135,50 @@ def _alignment_stats(records, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=B
     return out
 
 
+STYLE_KEYS = ('style_emotion', 'style_hit', 'style_own_rank', 'style_own_dist', 'style_silhouette')
+
+
+class StyleRecords(list):
+    """the records of evaluate(style=True): a list, plus `style_info` = {'k', 'n_recordings', 'ref_accuracy'}, what the
+    recordings say about themselves, for `summarize`"""
+    style_info = None
+
+
+def style_fields(emotion, vote, own_rank, own_dist, silhouette):
+    """the STYLE_KEYS of one record; vote None: the row has no style fields (all None)"""
+    if vote is None:
+        return dict.fromkeys(STYLE_KEYS)
+    sil = None if silhouette is None or math.isnan(silhouette) else float(silhouette)
+    return {'style_emotion': int(vote), 'style_hit': bool(int(vote) == int(emotion)), 'style_own_rank': int(own_rank),
+            'style_own_dist': float(own_dist), 'style_silhouette': sil}
+
+
+def _style_stats(records):
+    """Over the `n_style` rows that have style fields (a row without them is counted out, not as a miss): `accuracy` (share of
+    style_hit), `rank0_share` (share whose own recording is the nearest of all), `rank_median` and `silhouette_mean` (over the
+    rows that have a silhouette)."""
+    rows = [r for r in records if r.get('style_emotion') is not None]
+    return {'n_style': len(rows),
+            'accuracy': _mean([1.0 if r['style_hit'] else 0.0 for r in rows]),
+            'rank0_share': _mean([1.0 if r['style_own_rank'] == 0 else 0.0 for r in rows]),
+            'rank_median': _median([r['style_own_rank'] for r in rows]),
+            'silhouette_mean': _mean([r['style_silhouette'] for r in rows if r['style_silhouette'] is not None])}
+
+
+def _style_block(records, emotions, info):
+    """the `style` entry of summarize(): overall, by_emotion, the confusion matrix (rows: the label, columns: the vote) and
+    what `info` holds (k, n_recordings, ref_accuracy; None where the caller has no info)"""
+    info = info or {}
+    conf = [[0] * len(emotions) for _ in emotions]
+    for r in records:
+        if r.get('style_emotion') is not None:
+            conf[int(r['emotion'])][int(r['style_emotion'])] += 1
+    return {'k': info.get('k'), 'n_recordings': info.get('n_recordings'), 'ref_accuracy': info.get('ref_accuracy'),
+            'overall': _style_stats(records),
+            'by_emotion': {name: _style_stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)},
+            'confusion': conf}
+
+
 def _stats(records):
     """`dtw_mean` / `dtw_median` cover only the `n_scored` rows whose decoding stopped at the gate: a row that ran to
     max_decoder_steps has no end to align, and its distance says nothing about the model but that it did not stop.  Those
@@ -141,11 +194,15 @@ def _stats(records):
             'length_ratio_mean': _mean([r['n_frames'] / r['n_ref_frames'] for r in records])}
 
 
-def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=BACK_SLACK):
+def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=BACK_SLACK, style_info=None):
     """{'overall': stats, 'by_emotion': {name: stats}} of evaluate() records; every name of `emotions` appears, with
     n_rows = 0 and None statistics when it has no rows.  A label outside `emotions` is an error.  When the records carry
     the prosody keys (evaluate(prosody=True)) every stats dict also holds those of `_prosody_stats`; when they carry the
-    alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack."""
+    alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack.
+    When they carry the style keys (evaluate(style=True)) the result gains 'style': `_style_block`, with k, n_recordings and
+    ref_accuracy from style_info, else from the records' own `style_info` (StyleRecords), else None."""
+    if style_info is None:
+        style_info = getattr(records, 'style_info', None)
     records = list(records)
     for r in records:
         if not 0 <= int(r['emotion']) < len(emotions):
@@ -160,5 +217,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
         if alignment:
             out.update(_alignment_stats(rows, end_slack, gap_min, back_slack))
         return out
-    return {'overall': stats(records),
-            'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}
+    out = {'overall': stats(records),
+           'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}
+    if any('style_emotion' in r for r in records):
+        out['style'] = _style_block(records, emotions, style_info)
+    return out

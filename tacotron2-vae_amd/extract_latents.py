@@ -3,11 +3,14 @@
 latent_map.py's (or --tsne here).
 
     python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...] [--tsne [KEY]]
+                              [--scores [KEY]]
 
 Filelist rows are `path|text|speaker|emotion`.  OUT.npz holds, row i for filelist row i: prosody (N, E), mus, logvars,
 zs (N, z_latent_dim), emotions (N,) int and paths (N,) str.  The wavs run through `Synthesizer.latents`: sorted by
 length, in ragged batches of at most --batch_size, each row what model.vae_gst(load_mel(path)) gives for the wav alone.  --tsne [mus|zs|prosody] adds tsne (N, 2), the
 map of that array by latent_map.compute_map with its defaults, and tsne_kl; without it the file is what it always was.
+--scores [mus|zs] adds scores, the dict of latent_report.py (leave-one-out kNN accuracy, silhouette, active units, KL per
+dimension) for that array as a JSON string; without it the file is what it always was.
 """
 import argparse
 
@@ -25,6 +28,8 @@ def build_arg_parser():
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     p.add_argument('--tsne', nargs='?', const='mus', default=None, choices=('mus', 'zs', 'prosody'),
                    help="also store the t-SNE map of this array (default mus) as tsne, tsne_kl")
+    p.add_argument('--scores', nargs='?', const='mus', default=None, choices=('mus', 'zs'),
+                   help="also store the latent_report.py scores of this array (default mus) as a JSON string under scores")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
     return p
@@ -69,6 +74,10 @@ def main(argv=None):
         latent_map.check_perplexity(latent_map.DEFAULT_PERPLEXITY, len(paths))
         points, trace = latent_map.compute_map(out[args.tsne])
         out.update(tsne=points, tsne_kl=trace[-1])
+    if args.scores:
+        import json
+        from latent_scores import corpus_report
+        out.update(scores=json.dumps(corpus_report(out[args.scores], emotions, mu, logvar)))
     np.savez(args.out, **out)
     print("%s: %d utterances" % (args.out, len(paths)))
 

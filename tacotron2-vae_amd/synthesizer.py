@@ -262,6 +262,20 @@ class Synthesizer(object):
             raise ValueError("key must be one of %s, got %r" % (', '.join(keys), key))
         return t2v_hip.tsne(self.latents(paths, batch_size)[keys.index(key)].float().contiguous(), **tsne_kwargs)
 
+    def latent_report(self, paths, emotions, key='mus', k=5, batch_size=64):
+        """Does the latent separate the emotions?  `latents(paths)` followed by `latent_scores.corpus_report` on mus or zs
+        (key) with the label ids `emotions`: leave-one-out kNN accuracy and confusion matrix, silhouette, active units and KL
+        per dimension (those two always from mus and logvars), as one JSON-serialisable dict."""
+        from latent_scores import corpus_report
+        keys = {'mus': 1, 'zs': 3}
+        if key not in keys:
+            raise ValueError("key must be one of mus, zs, got %r" % (key,))
+        paths, emotions = list(paths), [int(e) for e in emotions]
+        if len(paths) != len(emotions):
+            raise ValueError("latent_report: %d paths for %d emotion labels" % (len(paths), len(emotions)))
+        lat = [t.float().cpu().numpy() for t in self.latents(paths, batch_size)]
+        return corpus_report(lat[keys[key]], emotions, lat[1], lat[2], k)
+
     # ------------------------------------------------------------------ checkpoint + centroids (synthesizer.py:74-110)
     @staticmethod
     def centroid_cache_path(checkpoint_path, filelist_path):
@@ -469,7 +483,7 @@ class Synthesizer(object):
         return out
 
     @torch.no_grad()
-    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False):
+    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
         recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
@@ -483,7 +497,15 @@ class Synthesizer(object):
         fewer than the vocoder's 4 frames has no waveform, and None on its synthesised side.
         alignment=True adds what the decoder's alignments say about reading the text (evaluation.ALIGNMENT_KEYS):
         `t2v_hip.alignment_stats` on the alignments of each group, one call and one copy to the host per group.  It combines
-        freely with prosody and either condition; without it the records hold exactly the keys above."""
+        freely with prosody and either condition; without it the records hold exactly the keys above.
+        style=True adds the style round trip (evaluation.STYLE_KEYS): each group's post-net mels go once more through the
+        ragged `model.vae_gst` (eval mode, no random draws: the decoder's seeds and every other value stay as they are), and
+        after the last group one `t2v_hip.latent_neighbours` call places their mu among the mu of the distinct recordings of
+        `rows`, labelled with their emotions, each row's own recording excluded from the vote and taken as the rank's
+        target.  A row decoded to fewer than the encoder's 2 frames gets None.  style_k is lowered to (distinct recordings
+        - 1) when there are too few; fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The
+        result is then an evaluation.StyleRecords: the same list, with `style_info` (k, n_recordings and ref_accuracy, the
+        leave-one-out accuracy of the recordings themselves) for `evaluation.summarize`."""
         import t2v_hip
         from evaluation import prosody_fields
         if condition not in ('ref', 'emotion'):
@@ -504,6 +526,18 @@ class Synthesizer(object):
         for r in rows:                      # ratio order (neu, sad, hap, ang), label order EMOTIONS
             if r[3] not in one_hot:
                 raise ValueError("emotion label %r outside 0..3" % (r[3],))
+        if style:
+            if isinstance(style_k, bool) or int(style_k) != style_k or not 1 <= style_k <= t2v_hip.LATENT_MAX_K:
+                raise ValueError("style_k %r must be an integer in 1..%d" % (style_k, t2v_hip.LATENT_MAX_K))
+            rec_label = {}
+            for r in rows:
+                if rec_label.setdefault(r[0], r[3]) != r[3]:
+                    raise ValueError("evaluate(style=True): %r appears with the emotion labels %d and %d"
+                                     % (r[0], rec_label[r[0]], r[3]))
+            if len(rec_label) < 2:
+                raise ValueError("evaluate(style=True) needs at least 2 distinct recordings, got %d" % len(rec_label))
+            rec_index = {p: j for j, p in enumerate(rec_label)}          # recordings in order of first appearance
+            rec_mu, syn_mu = [None] * len(rec_label), [None] * len(rows)
         dec = self.model.decoder
         records = []
         for i0 in range(0, len(rows), batch_size):
@@ -545,7 +579,59 @@ class Synthesizer(object):
                 for b in range(len(group)):
                     syn_track = host[len(uniq) + can.index(b)][:n[b]] if b in can else None
                     records[i0 + b].update(prosody_fields(syn_track, host[which[b]][:n_ref[b]]))
-        return records
+            if style:
+                new = [j for j, p in enumerate(uniq) if rec_mu[rec_index[p]] is None]
+                if new:
+                    sel = torch.tensor(new, device=ref_mels.device)
+                    mu = self.model.vae_gst(ref_mels if len(new) == len(uniq) else ref_mels[sel], [n_uniq[j] for j in new])[1]
+                    for row, j in enumerate(new):
+                        rec_mu[rec_index[uniq[j]]] = mu[row]
+                can = [b for b in range(len(group)) if n[b] >= 2]
+                if can:
+                    sel = torch.tensor(can, device=mel_postnet.device)
+                    mu = self.model.vae_gst(mel_postnet if len(can) == len(group) else mel_postnet[sel], [n[b] for b in can])[1]
+                    for row, b in enumerate(can):
+                        syn_mu[i0 + b] = mu[row]
+        if not style:
+            return records
+        return self._style_records(rows, records, list(rec_label.values()), rec_index, rec_mu, syn_mu, int(style_k))
+
+    @staticmethod
+    def _style_records(rows, records, rec_labels, rec_index, rec_mu, syn_mu, style_k):
+        """the style fields of evaluate(style=True) from the recordings' mu (one per distinct path, with its label) and the
+        synthesised rows' mu (None: no style fields): one `latent_neighbours` call for the rows, one for the recordings'
+        own leave-one-out accuracy, and host arithmetic in fp64 (latent_scores)"""
+        import t2v_hip
+        from evaluation import EMOTIONS, StyleRecords, style_fields
+        from latent_scores import knn_predict, silhouette
+        refs = torch.stack(rec_mu).float().contiguous()
+        labels = np.asarray(rec_labels, dtype=np.int64)
+        k = min(style_k, len(rec_labels) - 1)
+        C = len(EMOTIONS)
+        loo = t2v_hip.latent_neighbours(refs, labels, k=k, n_classes=C)
+        out = StyleRecords(records)
+        out.style_info = {'k': k, 'n_recordings': len(rec_labels),
+                          'ref_accuracy': float((knn_predict(loo.idx.cpu().numpy(), labels, C) == labels).mean())}
+        have = [i for i, m in enumerate(syn_mu) if m is not None]
+        fields = {}
+        refs64 = refs.cpu().numpy().astype(np.float64)
+        for c0 in range(0, len(have), t2v_hip.LATENT_MAX_POINTS):
+            chunk = have[c0:c0 + t2v_hip.LATENT_MAX_POINTS]
+            own = [rec_index[rows[i][0]] for i in chunk]
+            rows_q = chunk if len(chunk) > 1 else chunk * 2          # the kernel takes 2 queries or more
+            own_q = own if len(chunk) > 1 else own * 2
+            q = torch.stack([syn_mu[i] for i in rows_q]).float().contiguous()
+            r = t2v_hip.latent_neighbours(refs, labels, q, k=k, n_classes=C, exclude=own_q, target=own_q)
+            vote = knn_predict(r.idx.cpu().numpy(), labels, C)
+            lab = np.asarray([rows[i][3] for i in rows_q], dtype=np.int64)
+            sil = silhouette(r.class_sum.cpu().numpy(), r.class_cnt.cpu().numpy(), lab)
+            rank = r.rank.cpu().tolist()
+            dist = np.sqrt(((q.cpu().numpy().astype(np.float64) - refs64[own_q]) ** 2).sum(axis=1))
+            for row, i in enumerate(chunk):
+                fields[i] = style_fields(rows[i][3], vote[row], rank[row], dist[row], sil[row])
+        for i, rec in enumerate(out):
+            rec.update(fields.get(i) or style_fields(rows[i][3], None, None, None, None))
+        return out
 
 
 # ---------------------------------------------------------------------- command line

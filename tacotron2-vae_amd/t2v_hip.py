@@ -105,7 +105,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
            't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes',
            't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes',
-           't2v_resample', 't2v_trim_bounds', 't2v_crop_rows')
+           't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours')
 
 
 def lib_path():
@@ -246,6 +246,9 @@ def load_library():
     lib.t2v_tsne_gradient.argtypes = [vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
     lib.t2v_tsne_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
     lib.t2v_f0_yin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp]
+    lib.t2v_latent_scratch_bytes.argtypes = [C.c_int] * 5
+    lib.t2v_latent_scratch_bytes.restype = C.c_size_t
+    lib.t2v_latent_neighbours.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int] + [vp] * 7
     lib.t2v_resample.argtypes = [vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     lib.t2v_trim_bounds.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp]
     lib.t2v_crop_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
@@ -2064,6 +2067,94 @@ def tsne(x, perplexity=30.0, n_iter=1000, seed=0, init=None, return_trace=False)
     scratch = _tsne_scratch(lib, N, D, x.device)
     _check(lib.t2v_tsne_run(_p(P), _p(Y), N, n_iter, tsne_learning_rate(N), _p(trace), _p(scratch), _stream()), 't2v_tsne_run')
     return (Y, trace) if return_trace else Y
+
+
+LATENT_MAX_POINTS = 16384               # T2V_LATENT_MAX_POINTS of include/t2vae.h
+LATENT_MAX_DIM = 64
+LATENT_MAX_CLASSES = 8                  # T2V_LATENT_MAX_CLASSES
+LATENT_MAX_K = 32                       # T2V_LATENT_MAX_K
+LATENT_TILE = 128                       # T2V_LATENT_TILE: slice_rows is a multiple of it
+
+LatentNeighbours = collections.namedtuple('LatentNeighbours', 'idx dist class_sum class_cnt rank')
+
+
+def _latent_check(what, N, M, D, C, k, excluding):
+    for name, v in (('refs', N), ('queries', M)):
+        if v < 2 or v > LATENT_MAX_POINTS:
+            raise ValueError("%s: %s has %d rows; 2..%d are supported" % (what, name, v, LATENT_MAX_POINTS))
+    if D < 2 or D > LATENT_MAX_DIM:
+        raise ValueError("%s: refs has %d dimensions; 2..%d are supported" % (what, D, LATENT_MAX_DIM))
+    if isinstance(C, bool) or int(C) != C or C < 1 or C > LATENT_MAX_CLASSES:
+        raise ValueError("%s: n_classes %r; 1..%d are supported" % (what, C, LATENT_MAX_CLASSES))
+    if isinstance(k, bool) or int(k) != k or k < 1 or k > LATENT_MAX_K:
+        raise ValueError("%s: k %r; 1..%d are supported" % (what, k, LATENT_MAX_K))
+    most = N - 1 if excluding else N
+    if k > most:
+        raise ValueError("%s: k %d, but a query has only %d references to choose from (%d refs%s)"
+                         % (what, k, most, N, ", one excluded" if excluding else ""))
+
+
+def _latent_indices(what, name, v, count, lo, hi, device):
+    """an index argument of latent_neighbours as a device int32 vector: `count` integers in lo..hi, else a ValueError that names
+    the first offending position"""
+    n = torch.as_tensor(v).reshape(-1).cpu()
+    if n.dtype.is_floating_point or n.dtype == torch.bool or n.numel() != count:
+        raise ValueError("%s: %s must be %d integers, got %s %s" % (what, name, count, n.dtype, tuple(torch.as_tensor(v).shape)))
+    n = n.to(torch.int64)
+    bad = ((n < lo) | (n > hi)).nonzero()
+    if len(bad):
+        at = int(bad[0])
+        raise ValueError("%s: %s[%d] = %d lies outside %d..%d" % (what, name, at, int(n[at]), lo, hi))
+    return n.to(torch.int32).to(device)
+
+
+def latent_neighbours(refs, labels, queries=None, k=5, n_classes=4, exclude=None, target=None, slice_rows=0):
+    """Neighbours and class distances in a labelled latent space (csrc/latent.hip k_latent_pairs + k_latent_merge): refs (N, D)
+    float32 CUDA tensor, labels N integers in 0..n_classes-1, queries (M, D) or None for the refs themselves.  exclude: M
+    reference indices (-1: none) that the query skips; with queries None and exclude None each row skips itself (leave one
+    out).  target: M reference indices (-1: none) whose rank is wanted.  Returns LatentNeighbours of device tensors:
+      idx (M, k) int32, dist (M, k) float32: the k nearest non-excluded references by (squared distance, index), ties to the
+        lower index, and their Euclidean distances;   class_sum (M, n_classes) float32, class_cnt (M, n_classes) int32: sum
+        of distances to, and count of, the non-excluded references of each class;   rank (M,) int32: how many references sort
+        strictly before the target (exclusion does not apply), -1 without one.
+    Distances come from the differences, so integer inputs give exact ties.  Equal inputs give equal bits; slice_rows (0, or a
+    multiple of LATENT_TILE: how many references one workgroup visits) changes the launch and no bit of the result.
+    Labels and indices are checked here, on the host (one copy each): a ValueError names the first offending position."""
+    what = "latent_neighbours"
+    for name, v in (('refs', refs), ('queries', queries)):
+        if v is None and name == 'queries':
+            continue
+        if not torch.is_tensor(v) or v.dim() != 2 or v.dtype != torch.float32:
+            raise ValueError("%s: %s must be a float32 (rows, D) tensor, got %s %s"
+                             % (what, name, getattr(v, 'dtype', type(v)), tuple(getattr(v, 'shape', ()))))
+    lib = _require_gpu(refs, queries)
+    N, D = refs.shape
+    M = N if queries is None else queries.size(0)
+    if queries is not None and queries.size(1) != D:
+        raise ValueError("%s: queries have %d dimensions, refs %d" % (what, queries.size(1), D))
+    excluding = exclude is not None or queries is None
+    _latent_check(what, N, M, D, n_classes, k, excluding)
+    if isinstance(slice_rows, bool) or int(slice_rows) != slice_rows or slice_rows < 0 or slice_rows % LATENT_TILE:
+        raise ValueError("%s: slice_rows %r must be 0 or a positive multiple of %d" % (what, slice_rows, LATENT_TILE))
+    dev = refs.device
+    lab = _latent_indices(what, 'labels', labels, N, 0, n_classes - 1, dev)
+    ex = None if exclude is None else _latent_indices(what, 'exclude', exclude, M, -1, N - 1, dev)
+    tg = None if target is None else _latent_indices(what, 'target', target, M, -1, N - 1, dev)
+    refs = _f32c(refs)
+    queries = None if queries is None else _f32c(queries)
+    if not bool(torch.isfinite(refs).all()) or (queries is not None and not bool(torch.isfinite(queries).all())):
+        raise ValueError("%s: refs and queries must be finite" % what)
+    k, C_, slice_rows = int(k), int(n_classes), int(slice_rows)
+    idx = torch.empty(M, k, device=dev, dtype=torch.int32)
+    dist = torch.empty(M, k, device=dev, dtype=torch.float32)
+    class_sum = torch.empty(M, C_, device=dev, dtype=torch.float32)
+    class_cnt = torch.empty(M, C_, device=dev, dtype=torch.int32)
+    rank = torch.empty(M, device=dev, dtype=torch.int32)
+    scratch = torch.empty(lib.t2v_latent_scratch_bytes(N, M, C_, k, slice_rows), device=dev, dtype=torch.uint8)
+    _check(lib.t2v_latent_neighbours(_p(refs), _p(lab), N, D, C_, _p(queries), M, _p(ex), _p(tg), k, slice_rows, _p(idx),
+                                     _p(dist), _p(class_sum), _p(class_cnt), _p(rank), _p(scratch), _stream()),
+           't2v_latent_neighbours')
+    return LatentNeighbours(idx, dist, class_sum, class_cnt, rank)
 
 
 class InferenceSession(object):
