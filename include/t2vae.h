@@ -880,6 +880,62 @@ int t2v_latent_neighbours(const float* R, const int32_t* labels, int N, int D, i
                           const int32_t* exclude, const int32_t* target, int k, int slice_rows, int32_t* nn_idx,
                           float* nn_dist, float* class_sum, int32_t* class_cnt, int32_t* rank, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------ frame-aligned scores: MCD and F0 errors on a DTW path
+ * What the prosody-transfer papers report (MCD-13 with DTW, gross pitch error, voicing decision error, F0 frame error), taken
+ * along the warping path between a synthesised and a recorded utterance (csrc/aligned.hip).
+ *
+ * Cepstrum.  M is the project's log-mel (natural log, (B, 80, m_stride) fp32, row b of n[b] frames; nothing past them is read):
+ *   c_k(t) = sqrt(2 / 80) sum_{n<80} M[n, t] cos(pi k (n + 1/2) / 80),   k = 1 .. T2V_NCEP;   c_0 is left out.
+ * This is the mel-cepstral distortion "from an 80-band log-mel" of the prosody-transfer papers, not the one of a vocoder's
+ * mel-generalised cepstrum.  table is the caller's device array (T2V_NCEP, 80) fp32, row k - 1 holding
+ * sqrt(2 / 80) cos(pi k (n + 1/2) / 80) computed in fp64 and rounded once; the kernel adds the 80 terms in index order (fused
+ * multiply-add).  out is (B, T2V_NCEP, out_stride) fp32, coefficient k at row k - 1, 0 from n[b] to out_stride.
+ *
+ * Path.  X is (B, n_cep, x_stride) and Y (B, n_cep, y_stride), fp32 cepstra; pair b uses the first nx[b] / ny[b] frames.
+ * Local cost d(i, j) = ||x_i - y_j||_2 from the differences; the recurrence is t2v_mel_dtw's (symmetric2, no band):
+ *   D(0, 0) = 2 d(0, 0),   D(i, j) = min(D(i-1, j-1) + 2 d, D(i-1, j) + d, D(i, j-1) + d);   dist[b] = D(Tx-1, Ty-1) / (Tx + Ty).
+ * Ties go to the diagonal, then to (i-1, j), then to (i, j-1).  The path is walked back from (Tx-1, Ty-1) to (0, 0) through
+ * the stored decisions and written start to end: path (B, path_stride, 2) int32 holds (i_p, j_p) for p < K[b], and is not
+ * written past K[b]; max(Tx, Ty) <= K <= Tx + Ty - 1.
+ * Lengths are 1 .. min(stride, T2V_DTW_MAX_FRAMES) per side and path_stride >= Tx + Ty - 1; they are device data and the
+ * caller's to check on the host.  A pair that breaks this is refused by the kernels before they address anything and before
+ * their first barrier: its dist[b] is NaN and its K[b] is 0.
+ * scratch: t2v_cep_dtw_scratch_bytes(B, x_stride, y_stride) bytes: one 2-bit decision per cell, 16 bits per thread and step,
+ * (ty + (tx - 1) / 8) * 512 bytes per pair (1.18 MB at the maximum).  t2v_cep_dtw_path is t2v_cep_dtw_forward (dist and the
+ * table) followed by t2v_cep_dtw_walk (K and path from the table); the halves are exported for timing them apart.
+ *
+ * Scores.  t2v_path_scores takes any path (points are clamped into the pair's lengths), the cepstra it indexes and two F0
+ * tracks fx (B, fx_stride), fy (B, fy_stride) in Hz per frame, 0 (or anything not > 0) meaning unvoiced; a null track is
+ * unvoiced everywhere.  Over the points p = (i_p, j_p), p < K[b]:
+ *   counts (B, T2V_ALIGNED_COUNTS) int32:  K;  n_both = #{both voiced};  n_vde = #{exactly one voiced};
+ *                                          n_gpe = #{both voiced and |fx - fy| > 0.2 fy}.
+ *   sums (B, T2V_ALIGNED_SUMS) fp32:  sum d_p;  sum e and sum e^2 with e = 1200 log2(fx / fy) cents over the both-voiced points;
+ *                                     S_xx, S_yy, S_xy: the second moments of (log2 fx, log2 fy) over the both-voiced points,
+ *                                     centred on their means (two passes: the means, then the centred sums);
+ *                                     sum |i_p / max(Tx-1, 1) - j_p / max(Ty-1, 1)|;  one reserved word, 0.
+ * The division into means is the caller's, in fp64: mcd_db = (10 / ln 10) sqrt(2) sum d / K, vde = n_vde / K,
+ * gpe = n_gpe / n_both, ffe = (n_vde + n_gpe) / K, lf0_rmse = sqrt(sum e^2 / n_both), lf0_corr = S_xy / sqrt(S_xx S_yy),
+ * warp_dev = the last sum / K (0 for a linear stretch).  A pair with bad lengths, K[b] outside 1..path_stride or a length above
+ * its track's stride gets counts 0 and sums NaN.
+ * Every sum is a fixed-order tree (thread t adds the points t, t + 256, ... in order, then a tree over the 256 threads): no
+ * floating-point atomics, nothing depends on B or a stride, so a pair gives the same bits alone and in any batch.
+ * n_mel = 80 and n_cep = T2V_NCEP only (T2V_ERR_DIMS); a null required pointer, B < 1 or a stride < 1 is T2V_ERR_ARG. */
+#define T2V_NCEP 13
+#define T2V_ALIGNED_COUNTS 4
+#define T2V_ALIGNED_SUMS 8
+int t2v_mel_cepstrum(const float* M, const int32_t* n, int m_stride, int B, int n_mel, int n_cep, const float* table, float* out,
+                     int out_stride, void* stream);
+size_t t2v_cep_dtw_scratch_bytes(int B, int tx_max, int ty_max);
+int t2v_cep_dtw_forward(const float* X, const int32_t* nx, int x_stride, const float* Y, const int32_t* ny, int y_stride, int B,
+                        int n_cep, float* dist, void* scratch, void* stream);
+int t2v_cep_dtw_walk(const int32_t* nx, int x_stride, const int32_t* ny, int y_stride, int B, const void* scratch, int32_t* K,
+                     int32_t* path, int path_stride, void* stream);
+int t2v_cep_dtw_path(const float* X, const int32_t* nx, int x_stride, const float* Y, const int32_t* ny, int y_stride, int B,
+                     int n_cep, float* dist, int32_t* K, int32_t* path, int path_stride, void* scratch, void* stream);
+int t2v_path_scores(const int32_t* path, const int32_t* K, int path_stride, const float* X, const int32_t* nx, int x_stride,
+                    const float* Y, const int32_t* ny, int y_stride, const float* fx, int fx_stride, const float* fy, int fy_stride,
+                    int B, int n_cep, int32_t* counts, float* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--hparams ...]
+                       [--style [--style_k K]] [--aligned] [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
@@ -43,7 +43,17 @@ under --condition emotion too), style_own_dist and style_silhouette (against the
 to fewer than 2 frames.  The summary gains "style": per emotion and overall accuracy, rank0_share, rank_median and
 silhouette_mean, the 4 x 4 confusion matrix, and ref_accuracy, the leave-one-out accuracy of the recordings themselves under
 the same k: the ceiling the synthesised accuracy has to be read against.  One path under two emotion labels, or fewer than 2
-distinct recordings, is an error; --style_k is lowered to (distinct recordings - 1) when there are too few."""
+distinct recordings, is an error; --style_k is lowered to (distinct recordings - 1) when there are too few.
+
+--aligned gives the frame-aligned numbers the prosody-transfer papers report.  Both mels are reduced to 13 mel-cepstral
+coefficients (the DCT of the 80-band log-mel, c_0 left out: the papers' MCD-13, not a vocoder's mel-generalised cepstrum), a DTW
+over them that keeps its decisions gives the warping path (`t2v_hip.aligned_scores`, csrc/aligned.hip), and the scores are
+taken over the path's points.  Every row gains mcd_db and warp_dev (mean |i / (Tx - 1) - j / (Ty - 1)| along the path: 0 when the
+synthesis is a linear stretch of the recording, so it scores the speaking rhythm).  With --prosody the two pitch tracks feed
+the same call and the row also gains vde (voicing decision error), gpe (gross pitch error: more than 20 % apart where both
+sides are voiced), ffe (F0 frame error: either), lf0_rmse_cents, lf0_bias_cents and lf0_corr; without it those six are null, and
+no vocoder is needed.  Every summary dict gains n_aligned (rows that stopped at the gate) and mcd_db_mean, vde_mean, gpe_mean,
+ffe_mean, lf0_rmse_cents_mean, lf0_corr_mean and warp_dev_mean, each over the rows that have the value."""
 import argparse
 import json
 
@@ -73,6 +83,10 @@ def build_arg_parser():
                    help="also encode each synthesis again and place its mu among the recordings' (style round trip): rows gain "
                         "style_emotion, style_hit, style_own_rank, style_own_dist and style_silhouette; the summary a style block")
     p.add_argument('--style_k', type=int, default=DEFAULT_STYLE_K, help="neighbours of the --style vote; unused without it")
+    p.add_argument('--aligned', action='store_true',
+                   help="also walk the DTW path over 13 mel-cepstral coefficients and score along it: rows gain mcd_db and "
+                        "warp_dev, and with --prosody vde, gpe, ffe, lf0_rmse_cents, lf0_bias_cents and lf0_corr; the summary "
+                        "their means")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
@@ -124,7 +138,8 @@ def main(argv=None):
             syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft)
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
-    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment, **style)
+    records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
+                           aligned=args.aligned, **style)
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)]}, f, indent=1)
@@ -133,6 +148,10 @@ def main(argv=None):
         for name, st in summary['by_emotion'].items():
             print("%s: dtw_mean %s, read_through_share %s (%d of %d rows that stopped)"
                   % (name, st['dtw_mean'], st['read_through_share'], st['n_read_through'], st['n_alignment']))
+    if args.aligned:
+        for name, st in summary['by_emotion'].items():
+            print("%s: dtw_mean %s, mcd_db_mean %s, ffe_mean %s, warp_dev_mean %s (%d rows that stopped)"
+                  % (name, st['dtw_mean'], st['mcd_db_mean'], st['ffe_mean'], st['warp_dev_mean'], st['n_aligned']))
     if args.style:
         st = summary['style']
         print("style: accuracy %s (recordings leave-one-out %s, k = %s), own recording nearest in %s of %d rows"

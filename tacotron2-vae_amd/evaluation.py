@@ -26,7 +26,16 @@ the vote.  `style_emotion` is the vote of the k nearest other recordings, `style
 `style_own_dist` the distance to it, and `style_silhouette` the silhouette of the synthesised mu against the recorded clusters
 with the row's label as its own class.  All five are None for a row decoded to fewer frames than the encoder takes (and the
 silhouette alone where it is undefined).  `summarize` adds a `style` block, whose `ref_accuracy`, the leave-one-out accuracy
-of the recordings themselves under the same k, is the ceiling the synthesised accuracy has to be read against."""
+of the recordings themselves under the same k, is the ceiling the synthesised accuracy has to be read against.
+
+`evaluate(aligned=True)` adds the frame-aligned numbers of the prosody-transfer papers (`t2v_hip.aligned_scores`): a DTW over
+13 mel-cepstral coefficients of both mels gives the warping path, and along its K points `mcd_db` (MCD-13, from the 80-band
+log-mel: (10 / ln 10) sqrt(2) times the mean cepstral distance), `warp_dev` (mean |i / (Tx - 1) - j / (Ty - 1)|: how far the
+synthesis is stretched unevenly against the recording, 0 for a linear stretch) and, when the pitch tracks are there
+(prosody=True), `vde` (voicing decision error: one side voiced, over K), `gpe` (gross pitch error: more than 20 % apart, over
+the both-voiced points), `ffe` (either, over K), `lf0_rmse_cents`, `lf0_bias_cents` and `lf0_corr` (Pearson, of log F0 over
+the both-voiced points).  The F0 values are None without tracks; gpe and the three log-F0 values also when no point is voiced
+on both sides, and the correlation under 2 such points or at a zero variance."""
 import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
@@ -135,6 +144,46 @@ def _alignment_stats(records, end_slack=END_SLACK, gap_min=GAP_MIN, back_slack=B
     return out
 
 
+ALIGNED_KEYS = ('mcd_db', 'vde', 'gpe', 'ffe', 'lf0_rmse_cents', 'lf0_bias_cents', 'lf0_corr', 'warp_dev')
+ALIGNED_MEANS = ('mcd_db', 'vde', 'gpe', 'ffe', 'lf0_rmse_cents', 'lf0_corr', 'warp_dev')
+MCD_DB = 10.0 / math.log(10.0) * math.sqrt(2.0)
+
+
+def aligned_fields(counts, sums, f0=True):
+    """the ALIGNED_KEYS of one record from one row of `t2v_hip.aligned_scores`: counts (n_points, n_both, n_vde, n_gpe, in
+    t2v_hip.ALIGNED_COUNTS order) and sums (sum_d, sum_e, sum_e2, s_xx, s_yy, s_xy, sum_warp, in t2v_hip.ALIGNED_SUMS order; a
+    reserved eighth word is ignored), divided here in fp64.  f0=False: the row had no pitch tracks, and its six F0 values are
+    None (not 0).  A refused row (n_points 0) has None everywhere."""
+    K, n_both, n_vde, n_gpe = [int(v) for v in list(counts)[:4]]
+    sum_d, sum_e, sum_e2, s_xx, s_yy, s_xy, sum_warp = [float(v) for v in list(sums)[:7]]
+    out = dict.fromkeys(ALIGNED_KEYS)
+    if K < 1:
+        return out
+    out['mcd_db'] = MCD_DB * sum_d / K
+    out['warp_dev'] = sum_warp / K
+    if not f0:
+        return out
+    out['vde'] = n_vde / K
+    out['ffe'] = (n_vde + n_gpe) / K
+    if n_both > 0:
+        out['gpe'] = n_gpe / n_both
+        out['lf0_rmse_cents'] = math.sqrt(sum_e2 / n_both)
+        out['lf0_bias_cents'] = sum_e / n_both
+        if n_both >= 2 and s_xx > 0.0 and s_yy > 0.0:
+            out['lf0_corr'] = max(-1.0, min(1.0, s_xy / math.sqrt(s_xx * s_yy)))
+    return out
+
+
+def _aligned_stats(records):
+    """Over the `n_aligned` rows that stopped at the gate and carry the aligned keys (a row that ran to max_decoder_steps has
+    no end to align): the mean of each of ALIGNED_MEANS over the rows that have that value."""
+    rows = [r for r in records if not r['hit_max'] and 'mcd_db' in r]
+    out = {'n_aligned': len(rows)}
+    for k in ALIGNED_MEANS:
+        out[k + '_mean'] = _mean([r[k] for r in rows if r.get(k) is not None])
+    return out
+
+
 STYLE_KEYS = ('style_emotion', 'style_hit', 'style_own_rank', 'style_own_dist', 'style_silhouette')
 
 
@@ -198,7 +247,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
     """{'overall': stats, 'by_emotion': {name: stats}} of evaluate() records; every name of `emotions` appears, with
     n_rows = 0 and None statistics when it has no rows.  A label outside `emotions` is an error.  When the records carry
     the prosody keys (evaluate(prosody=True)) every stats dict also holds those of `_prosody_stats`; when they carry the
-    alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack.
+    alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack; when
+    they carry the aligned keys (evaluate(aligned=True)), `n_aligned` and the means of `_aligned_stats`.
     When they carry the style keys (evaluate(style=True)) the result gains 'style': `_style_block`, with k, n_recordings and
     ref_accuracy from style_info, else from the records' own `style_info` (StyleRecords), else None."""
     if style_info is None:
@@ -209,6 +259,7 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
             raise ValueError("emotion label %r outside 0..%d" % (r['emotion'], len(emotions) - 1))
     prosody = any('f0_shift_st' in r for r in records)
     alignment = any('n_symbols' in r for r in records)
+    aligned = any('mcd_db' in r for r in records)
 
     def stats(rows):
         out = _stats(rows)
@@ -216,6 +267,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
             out.update(_prosody_stats(rows))
         if alignment:
             out.update(_alignment_stats(rows, end_slack, gap_min, back_slack))
+        if aligned:
+            out.update(_aligned_stats(rows))
         return out
     out = {'overall': stats(records),
            'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}

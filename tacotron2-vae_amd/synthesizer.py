@@ -483,7 +483,7 @@ class Synthesizer(object):
         return out
 
     @torch.no_grad()
-    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5):
+    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
         recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
@@ -505,9 +505,14 @@ class Synthesizer(object):
         target.  A row decoded to fewer than the encoder's 2 frames gets None.  style_k is lowered to (distinct recordings
         - 1) when there are too few; fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The
         result is then an evaluation.StyleRecords: the same list, with `style_info` (k, n_recordings and ref_accuracy, the
-        leave-one-out accuracy of the recordings themselves) for `evaluation.summarize`."""
+        leave-one-out accuracy of the recordings themselves) for `evaluation.summarize`.
+        aligned=True adds the frame-aligned scores (evaluation.ALIGNED_KEYS): per group the cepstra of the post-net mels and
+        of the recordings' mels (`t2v_hip.mel_cepstrum`), one `t2v_hip.aligned_scores` call and one copy to the host.  Alone
+        it gives every row mcd_db and warp_dev, None on the six F0 values, and needs no vocoder; with prosody=True the two
+        pitch tracks computed there, cut to n_frames and n_ref_frames, feed the same call (a row decoded to fewer than the
+        vocoder's 4 frames keeps None on its F0 values and still gets mcd_db).  It draws nothing and changes no other key."""
         import t2v_hip
-        from evaluation import prosody_fields
+        from evaluation import aligned_fields, prosody_fields
         if condition not in ('ref', 'emotion'):
             raise ValueError("condition must be 'ref' or 'emotion', got %r" % (condition,))
         if batch_size < 1:
@@ -579,6 +584,25 @@ class Synthesizer(object):
                 for b in range(len(group)):
                     syn_track = host[len(uniq) + can.index(b)][:n[b]] if b in can else None
                     records[i0 + b].update(prosody_fields(syn_track, host[which[b]][:n_ref[b]]))
+            if aligned:
+                cep = t2v_hip.mel_cepstrum(mel_postnet, n)
+                cep_ref = t2v_hip.mel_cepstrum(ref_mels, n_uniq)
+                same = which == list(range(len(paths)))
+                pick = None if same else torch.tensor(which, device=ref_mels.device)
+                f0x = f0y = None
+                if prosody:
+                    # the tracks above, on the device: a row without a waveform is unvoiced everywhere and gets no F0 values
+                    f0y = torch.nn.functional.pad(tracks[0], (0, max(0, max(n_ref) - tracks[0].size(1))))
+                    f0y = f0y if same else f0y[pick]
+                    f0x = torch.zeros(len(group), max(n), device=mel.device)
+                    if can:
+                        w = min(max(n), tracks[1].size(1))
+                        f0x[torch.tensor(can, device=mel.device), :w] = tracks[1][:, :w]
+                r = t2v_hip.aligned_scores(cep, n, cep_ref if same else cep_ref[pick], n_ref, f0x, f0y)
+                host = torch.cat([r.counts.double(), r.sums.double()], 1).cpu().tolist()
+                for b in range(len(group)):
+                    records[i0 + b].update(aligned_fields(host[b][:len(t2v_hip.ALIGNED_COUNTS)], host[b][len(t2v_hip.ALIGNED_COUNTS):],
+                                                          f0=prosody and n[b] >= 4))
             if style:
                 new = [j for j, p in enumerate(uniq) if rec_mu[rec_index[p]] is None]
                 if new:

@@ -105,7 +105,9 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
            't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes',
            't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes',
-           't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours')
+           't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours',
+           't2v_mel_cepstrum', 't2v_cep_dtw_scratch_bytes', 't2v_cep_dtw_path', 't2v_cep_dtw_forward', 't2v_cep_dtw_walk',
+           't2v_path_scores')
 
 
 def lib_path():
@@ -240,6 +242,14 @@ def load_library():
     lib.t2v_mel_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_mel_dtw_scratch_bytes.restype = C.c_size_t
     lib.t2v_mel_dtw.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.t2v_mel_cepstrum.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    lib.t2v_cep_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.t2v_cep_dtw_scratch_bytes.restype = C.c_size_t
+    lib.t2v_cep_dtw_forward.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.t2v_cep_dtw_walk.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
+    lib.t2v_cep_dtw_path.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    lib.t2v_path_scores.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                                    vp, vp, vp]
     lib.t2v_tsne_scratch_bytes.argtypes = [C.c_int, C.c_int]
     lib.t2v_tsne_scratch_bytes.restype = C.c_size_t
     lib.t2v_tsne_affinities.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
@@ -1698,6 +1708,136 @@ def mel_dtw(x, nx, y, ny):
         _check(lib.t2v_mel_dtw(_p(x[b0:]), _p(nx[b0:]), sx, _p(y[b0:]), _p(ny[b0:]), sy, nb, n_mel, _p(dist[b0:]), _p(scratch),
                                _stream()), 't2v_mel_dtw')
     return dist
+
+
+NCEP = 13                               # T2V_NCEP of include/t2vae.h
+CEP_DTW_SCRATCH_CAP = 256 << 20         # bytes of decision table one t2v_cep_dtw_path call may ask of the allocator; larger batches run in groups
+ALIGNED_COUNTS = ('n_points', 'n_both', 'n_vde', 'n_gpe')
+ALIGNED_SUMS = ('sum_d', 'sum_e', 'sum_e2', 's_xx', 's_yy', 's_xy', 'sum_warp')
+_CEP_TABLE = {}                         # 'host' -> the fp32 table, device -> its copy there
+
+
+def cepstrum_table(device=None):
+    """The (13, 80) table of mel_cepstrum: row k - 1 holds sqrt(2 / 80) cos(pi k (n + 1/2) / 80), k = 1..13, made in fp64 with
+    numpy and rounded to fp32 once.  device None: the read-only host array; else its cached copy on that device."""
+    import numpy as np
+    host = _CEP_TABLE.get('host')
+    if host is None:
+        k = np.arange(1, NCEP + 1, dtype=np.float64)[:, None]
+        n = np.arange(80, dtype=np.float64)[None, :]
+        host = (np.sqrt(2.0 / 80.0) * np.cos(np.pi * k * (n + 0.5) / 80.0)).astype(np.float32)
+        host.setflags(write=False)
+        _CEP_TABLE['host'] = host
+    if device is None:
+        return host
+    key = str(torch.device(device))
+    if key not in _CEP_TABLE:
+        _CEP_TABLE[key] = torch.from_numpy(host.copy()).to(device)
+    return _CEP_TABLE[key]
+
+
+def mel_cepstrum(mels, lengths):
+    """Mel cepstrum of log-mels (csrc/aligned.hip k_mel_cepstrum): mels (B, 80, T) float32 CUDA tensor, row b of lengths[b]
+    frames (a list, a CPU tensor or a device int tensor); nothing past a length is read.  Returns (B, 13, T) float32:
+    c_k(t) = sqrt(2 / 80) sum_n mels[n, t] cos(pi k (n + 1/2) / 80) for k = 1..13 at row k - 1 (c_0 is left out), 0 past each
+    length.  This is the cepstrum "from an 80-band log-mel" of the prosody-transfer papers' MCD-13, not a vocoder's
+    mel-generalised cepstrum.  A row gives the same bits alone, in any batch and at any stride."""
+    lib = _require_gpu(mels)
+    if mels.dim() != 3 or mels.dtype != torch.float32:
+        raise ValueError("mel_cepstrum: mels must be a float32 (B, 80, T) tensor")
+    B, n_mel, T = mels.shape
+    if n_mel != 80:
+        raise ValueError("mel_cepstrum: 80 mel channels only, got %d" % n_mel)
+    if B < 1 or T < 1:
+        raise ValueError("mel_cepstrum: empty input %s" % (tuple(mels.shape),))
+    n = _checked_lengths(lengths, B, 1, T, "mel_cepstrum: lengths must be %d integer frame counts" % B,
+                         "mel_cepstrum: every length must be in 1..%d (frames stored per row)" % T, reject_bool=False)
+    mels = _f32c(mels)
+    n = n.to(mels.device)
+    table = cepstrum_table(mels.device)
+    out = torch.empty(B, NCEP, T, device=mels.device, dtype=torch.float32)
+    for b0 in range(0, B, 65535):           # the batch is the grid's second dimension
+        _check(lib.t2v_mel_cepstrum(_p(mels[b0:]), _p(n[b0:]), T, min(65535, B - b0), n_mel, NCEP, _p(table), _p(out[b0:]), T,
+                                    _stream()), 't2v_mel_cepstrum')
+    return out
+
+
+class AlignedScores(collections.namedtuple('AlignedScores', 'dist n_points counts sums path')):
+    """What aligned_scores() returns.  dist (B,) float32: D(Tx-1, Ty-1) / (Tx + Ty); n_points (B,) int32: K, the points of the
+    warping path; counts (B, 4) int32 with the columns ALIGNED_COUNTS; sums (B, 8) float32 with the columns ALIGNED_SUMS and one
+    reserved word; path (B, Kmax, 2) int32 with (i_p, j_p) for p < n_points[b] (undefined past that), or None when it was not
+    asked for.  Every column of counts and sums is also an attribute (r.n_gpe: (B,) int32, r.sum_d: (B,) float32)."""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        if name in ALIGNED_COUNTS:
+            return self.counts[:, ALIGNED_COUNTS.index(name)]
+        if name in ALIGNED_SUMS:
+            return self.sums[:, ALIGNED_SUMS.index(name)]
+        raise AttributeError(name)
+
+
+def _aligned_lengths(n, B, stride, what):
+    """frame counts of aligned_scores as a host tensor, checked as mel_dtw's: a list, a CPU tensor or a device int tensor"""
+    hi = min(stride, DTW_MAX_FRAMES)
+    return _checked_lengths(n, B, 1, hi, "aligned_scores: %s must be %d integer frame counts" % (what, B),
+                            "aligned_scores: every %s must be in 1..%d (%d frames stored, at most %d supported)"
+                            % (what, hi, stride, DTW_MAX_FRAMES), reject_bool=False)
+
+
+def _aligned_track(f, B, n, what):
+    """an F0 track of aligned_scores: None, or a float32 (B, S) CUDA tensor that holds every row's frames"""
+    if f is None:
+        return None, 1
+    if not torch.is_tensor(f) or f.dim() != 2 or f.dtype != torch.float32 or f.size(0) != B or f.size(1) < 1:
+        raise ValueError("aligned_scores: %s must be a float32 (%d, frames) tensor" % (what, B))
+    if int(n.max()) > f.size(1):
+        raise ValueError("aligned_scores: %s holds %d frames per row, the lengths ask for %d" % (what, f.size(1), int(n.max())))
+    return _f32c(f), f.size(1)
+
+
+def aligned_scores(cx, nx, cy, ny, f0x=None, f0y=None, return_path=False):
+    """The warping path between two cepstra and the scores along it (csrc/aligned.hip k_cep_dtw_fwd, k_cep_dtw_back,
+    k_path_scores): cx (B, 13, Sx), cy (B, 13, Sy) float32 CUDA tensors (mel_cepstrum), pair b compared on its first nx[b] /
+    ny[b] frames (lists, CPU tensors or device int tensors); nothing past a length is read.  Local cost: the Euclidean distance
+    of two frames; recurrence: mel_dtw's (symmetric2, no band), ties to the diagonal, then (i-1, j), then (i, j-1).  f0x
+    (B, >= max nx) and f0y (B, >= max ny): F0 tracks in Hz per frame, 0 where unvoiced (t2v_hip.f0); a missing track counts as
+    unvoiced everywhere.  Returns an AlignedScores; evaluation.aligned_fields turns one row of its counts and sums into
+    mcd_db, vde, gpe, ffe, the log-F0 errors and warp_dev.  With return_path also path (B, max K, 2) int32.  A pair gives the
+    same bits alone and in any batch.  Batches whose decision tables would exceed CEP_DTW_SCRATCH_CAP run in groups."""
+    lib = _require_gpu(cx, cy, f0x, f0y)
+    if cx.dim() != 3 or cy.dim() != 3 or cx.dtype != torch.float32 or cy.dtype != torch.float32:
+        raise ValueError("aligned_scores: cx and cy must be float32 (B, 13, T) tensors")
+    B, n_cep, sx = cx.shape
+    if cy.size(0) != B or B < 1:
+        raise ValueError("aligned_scores: %d sequences in cx, %d in cy" % (B, cy.size(0)))
+    if n_cep != NCEP or cy.size(1) != NCEP:
+        raise ValueError("aligned_scores: %d cepstral coefficients only, got %d and %d" % (NCEP, n_cep, cy.size(1)))
+    sy = cy.size(2)
+    if sx < 1 or sy < 1:
+        raise ValueError("aligned_scores: empty time axis")
+    nx_h, ny_h = _aligned_lengths(nx, B, sx, 'nx'), _aligned_lengths(ny, B, sy, 'ny')
+    f0x, fsx = _aligned_track(f0x, B, nx_h, 'f0x')
+    f0y, fsy = _aligned_track(f0y, B, ny_h, 'f0y')
+    dev = cx.device
+    nx, ny = nx_h.to(dev), ny_h.to(dev)
+    cx, cy = _f32c(cx), _f32c(cy)
+    kmax = int((nx_h + ny_h).max()) - 1
+    dist = torch.empty(B, device=dev, dtype=torch.float32)
+    K = torch.empty(B, device=dev, dtype=torch.int32)
+    path = torch.empty(B, kmax, 2, device=dev, dtype=torch.int32)
+    counts = torch.empty(B, len(ALIGNED_COUNTS), device=dev, dtype=torch.int32)
+    sums = torch.empty(B, len(ALIGNED_SUMS) + 1, device=dev, dtype=torch.float32)
+    per_pair = lib.t2v_cep_dtw_scratch_bytes(1, sx, sy)
+    group = max(1, min(B, CEP_DTW_SCRATCH_CAP // per_pair))
+    for b0 in range(0, B, group):
+        nb = min(group, B - b0)
+        scratch = torch.empty(lib.t2v_cep_dtw_scratch_bytes(nb, sx, sy), device=dev, dtype=torch.uint8)
+        _check(lib.t2v_cep_dtw_path(_p(cx[b0:]), _p(nx[b0:]), sx, _p(cy[b0:]), _p(ny[b0:]), sy, nb, n_cep, _p(dist[b0:]), _p(K[b0:]),
+                                    _p(path[b0:]), kmax, _p(scratch), _stream()), 't2v_cep_dtw_path')
+    _check(lib.t2v_path_scores(_p(path), _p(K), kmax, _p(cx), _p(nx), sx, _p(cy), _p(ny), sy, _p(f0x), fsx, _p(f0y), fsy, B, n_cep,
+                               _p(counts), _p(sums), _stream()), 't2v_path_scores')
+    return AlignedScores(dist, K, counts, sums, path if return_path else None)
 
 
 F0_MAX_LAG = 400                        # T2V_F0_MAX_LAG of include/t2vae.h
