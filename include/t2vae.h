@@ -936,6 +936,45 @@ int t2v_path_scores(const int32_t* path, const int32_t* K, int path_stride, cons
                     const float* Y, const int32_t* ny, int y_stride, const float* fx, int fx_stride, const float* fy, int fy_stride,
                     int B, int n_cep, int32_t* counts, float* sums, void* stream);
 
+/* ------------------------------------------------------------------ loudness and energy: a BS.1770 meter
+ * The K-weighted, gated loudness of ITU-R BS.1770-4 / EBU R 128 (mono) and the K-weighted level per frame of the front end's
+ * grid, over a ragged batch (csrc/loudness.hip).  y is (B, y_stride) fp32, row b has n[b] samples (device int32); nothing at or
+ * past n[b] is read.  hop is the rate / 10 (100 ms in samples, 800 .. 4800: 8 to 48 kHz; else T2V_ERR_DIMS).
+ *
+ * table: the caller's device array of 8 + 16 * 65 fp64.  [0 .. 7) the K-weighting b0 b1 b2 a1 a2 (high shelf) d1 d2 (high
+ * pass, whose numerator is 1 -2 1) for the rate, each rounded to fp32 and held as fp64, [7] unused, then the 4 x 4 matrices
+ * M^0 .. M^64, row-major, M = A^T2V_LOUDNESS_CHUNK, A the zero-input step of the cascade in transposed direct form II on the
+ * state (s1, s2, t1, t2):
+ *   A = [-a1 1 0 0; -a2 0 0 0; -2 - d1 0 -d1 1; 1 - d2 0 -d2 0],
+ * computed in fp64 from those coefficients.  The filter state is fp64 (the high pass's poles lie 0.005 to 0.015 from z = 1: an
+ * fp32 state leaves a noise floor near -85 dBFS behind a loud passage); samples and sums of squares are fp32.  z is the weighted
+ * signal from a zero state, 0 outside [0, n).
+ * Building the table from C: round the seven coefficients to float, widen them to double, fill A as above, square A six times
+ * for M = A^64, then table[8 + 16 p + 4 i + j] = (M^p)[i][j] for p = 0 (the identity), 1, ..., 64 by repeated multiplication,
+ * all in double; upload the 1 048 doubles once per rate.  The entry cannot check that the powers belong to the coefficients: a
+ * table built otherwise gives a wrong state at every chunk boundary, not an error (t2v_hip.loudness_table is the model).
+ *
+ * frame_ms (B, ms_stride): ms[t] = mean of z^2 over [256 t - 512, 256 t + 512) for the n / 256 + 1 frames, +0 behind them.
+ * block_pw (B, blk_stride): the mean of z^2 over the complete 400 ms blocks [j hop, j hop + 4 hop), nb = (n - 4 hop) / hop + 1
+ *   of them (0 when n < 4 hop), +0 behind them.
+ * rows (B, 8) int32: [0] the bits of the fp32 sum of block_pw over the gated blocks (l_j = -0.691 + 10 log10 block_pw[j] above
+ *   -70 and above the relative gate, 10 below -0.691 + 10 log10 of the mean over the blocks above -70), [1] the bits of the
+ *   ungated mean square over [0, n), [2] the bits of the largest block power, [3] the count of gated blocks, [4] nb, the rest 0.
+ *   The gates compare powers in fp32.  Integrated loudness = -0.691 + 10 log10(sum / count) is the caller's, in fp64.
+ * Every sum has an order that depends on the position in the row alone, without floating-point atomics: a row gives the same
+ * bits alone, in any batch and at any stride.
+ * A null pointer, B < 1, y_stride < 1 or above 2^30, ms_stride < y_stride / 256 + 1, blk_stride < 1 or below the blocks of
+ * y_stride samples is T2V_ERR_ARG.  The lengths are the caller's to check on the host; the kernels clamp them to 0..y_stride.
+ * scratch: t2v_loudness_scratch_bytes(B, y_stride, hop) bytes of device memory (0 for sizes that are refused).
+ *
+ * t2v_scale_rows: y[b][c] *= gains[b] for c < n[b], in place; columns from n[b] on are not touched.  gains is device fp32 (B). */
+#define T2V_LOUDNESS_CHUNK 64       /* samples per lane of the filter kernel */
+#define T2V_LOUDNESS_TILE 16384     /* samples per workgroup tile: 256 chunks, between which the filter state is scanned */
+size_t t2v_loudness_scratch_bytes(int B, int y_stride, int hop);
+int t2v_loudness(const float* y, const int32_t* n, int y_stride, int B, const double* table, int hop, float* frame_ms,
+                 int ms_stride, float* block_pw, int blk_stride, int32_t* rows, void* scratch, void* stream);
+int t2v_scale_rows(float* y, const int32_t* n, int y_stride, int B, const float* gains, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

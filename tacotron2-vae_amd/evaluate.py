@@ -3,7 +3,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--hparams ...]
+                       [--style [--style_k K]] [--aligned] [--energy] [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
@@ -53,7 +53,18 @@ synthesis is a linear stretch of the recording, so it scores the speaking rhythm
 the same call and the row also gains vde (voicing decision error), gpe (gross pitch error: more than 20 % apart where both
 sides are voiced), ffe (F0 frame error: either), lf0_rmse_cents, lf0_bias_cents and lf0_corr; without it those six are null, and
 no vocoder is needed.  Every summary dict gains n_aligned (rows that stopped at the gate) and mcd_db_mean, vde_mean, gpe_mean,
-ffe_mean, lf0_rmse_cents_mean, lf0_corr_mean and warp_dev_mean, each over the rows that have the value."""
+ffe_mean, lf0_rmse_cents_mean, lf0_corr_mean and warp_dev_mean, each over the rows that have the value.
+
+--energy asks about the third correlate of prosody, the level: does an "ang" row come out louder than a "sad" one, as the
+recordings do?  The checkpoint is loaded with the Griffin-Lim vocoder (as for --prosody, which shares the waveforms), and the
+K-weighted, gated loudness of ITU-R BS.1770-4 and the K-weighted level per mel frame (`t2v_hip.loudness`, csrc/loudness.hip)
+are taken of each synthesised waveform and of its recording.  Every row gains loudness_lufs, loudness_ref_lufs,
+loudness_shift_lu (synthesis - recording) and energy_spread_db / energy_ref_spread_db (standard deviation of the frame level
+over the frames within 40 dB of the row's loudest: an uncalibrated choice); null for a side without a loudness (no waveform,
+under 400 ms, or below the gates).  With --aligned the row also gains energy_rmse_db and energy_corr of the two dB tracks
+along the warping path, over the points where both sides sound.  The summary gains "energy": overall and per emotion n_energy,
+loudness_shift_lu_mean / _abs_mean, energy_spread_ratio_mean (and the two path means), and per emotion loudness_vs_neu_lu and
+loudness_ref_vs_neu_lu, the emotion's mean loudness minus neutral's, synthesised and recorded."""
 import argparse
 import json
 
@@ -74,7 +85,7 @@ def build_arg_parser():
                    help="also track the pitch (YIN, 60-500 Hz) of each synthesised waveform (Griffin-Lim) and of its recording: "
                         "rows gain median F0, spread in semitones, voiced share and f0_shift_st; the summary their means")
     p.add_argument('--vocoder', choices=['griffin_lim', 'griffin_lim_fast'], default='griffin_lim',
-                   help="the vocoder of --prosody (griffin_lim_fast: momentum 0.99 and NNLS mel inversion); unused without it")
+                   help="the vocoder of --prosody and --energy (griffin_lim_fast: momentum 0.99 and NNLS mel inversion); unused without them")
     p.add_argument('--alignment', action='store_true',
                    help="also score the attention alignment of each synthesis (did the decoder read the text?): rows gain focus, "
                         "reach, end_reach, back_share, jump_share, stall_frames, uncovered_share, gap_symbols and n_symbols; "
@@ -87,6 +98,10 @@ def build_arg_parser():
                    help="also walk the DTW path over 13 mel-cepstral coefficients and score along it: rows gain mcd_db and "
                         "warp_dev, and with --prosody vde, gpe, ffe, lf0_rmse_cents, lf0_bias_cents and lf0_corr; the summary "
                         "their means")
+    p.add_argument('--energy', action='store_true',
+                   help="also measure the BS.1770 loudness and the frame level of each synthesised waveform (Griffin-Lim) and of "
+                        "its recording: rows gain loudness_lufs, loudness_ref_lufs, loudness_shift_lu and the energy spreads, "
+                        "with --aligned energy_rmse_db and energy_corr; the summary an energy block")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
@@ -131,15 +146,15 @@ def main(argv=None):
     from wavio import wav_options
     syn = Synthesizer(hp, **wav_options(args))
     if args.condition == 'emotion':
-        syn.load(args.load_path, vocoder=args.vocoder if args.prosody else None, filelist_path=args.filelist_path)
+        syn.load(args.load_path, vocoder=args.vocoder if args.prosody or args.energy else None, filelist_path=args.filelist_path)
     else:
         syn.load_checkpoint(args.load_path)
-        if args.prosody:
+        if args.prosody or args.energy:
             syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft)
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
-                           aligned=args.aligned, **style)
+                           aligned=args.aligned, energy=args.energy, **style)
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)]}, f, indent=1)
@@ -152,6 +167,11 @@ def main(argv=None):
         for name, st in summary['by_emotion'].items():
             print("%s: dtw_mean %s, mcd_db_mean %s, ffe_mean %s, warp_dev_mean %s (%d rows that stopped)"
                   % (name, st['dtw_mean'], st['mcd_db_mean'], st['ffe_mean'], st['warp_dev_mean'], st['n_aligned']))
+    if args.energy:
+        for name, st in summary['energy']['by_emotion'].items():
+            print("%s: loudness_shift_lu_mean %s, loudness_vs_neu_lu %s (recordings %s), energy_spread_ratio_mean %s (%d rows)"
+                  % (name, st['loudness_shift_lu_mean'], st['loudness_vs_neu_lu'], st['loudness_ref_vs_neu_lu'],
+                     st['energy_spread_ratio_mean'], st['n_energy']))
     if args.style:
         st = summary['style']
         print("style: accuracy %s (recordings leave-one-out %s, k = %s), own recording nearest in %s of %d rows"

@@ -35,7 +35,16 @@ synthesis is stretched unevenly against the recording, 0 for a linear stretch) a
 (prosody=True), `vde` (voicing decision error: one side voiced, over K), `gpe` (gross pitch error: more than 20 % apart, over
 the both-voiced points), `ffe` (either, over K), `lf0_rmse_cents`, `lf0_bias_cents` and `lf0_corr` (Pearson, of log F0 over
 the both-voiced points).  The F0 values are None without tracks; gpe and the three log-F0 values also when no point is voiced
-on both sides, and the correlation under 2 such points or at a zero variance."""
+on both sides, and the correlation under 2 such points or at a zero variance.
+
+`evaluate(energy=True)` adds the third correlate of prosody, the level (`t2v_hip.loudness`, the K-weighted gated loudness of
+ITU-R BS.1770-4, on the Griffin-Lim waveform of the synthesised mel and on the recording): `loudness_lufs` /
+`loudness_ref_lufs`, `loudness_shift_lu` = synthesis - recording, and `energy_spread_db` / `energy_ref_spread_db`, the standard
+deviation of the K-weighted frame level in dB over the sounding frames, those within ENERGY_FLOOR_DB of the row's loudest
+frame (the trim's rule; like the alignment thresholds an uncalibrated choice, not a measurement).  A side without a loudness
+(no waveform, shorter than one 400 ms block, or below the gates) has None.  With aligned=True as well, `energy_rmse_db` and
+`energy_corr` (Pearson) compare the two dB tracks along the warping path, over the points where both sides sound.  `summarize`
+adds an `energy` block."""
 import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
@@ -184,6 +193,98 @@ def _aligned_stats(records):
     return out
 
 
+ENERGY_KEYS = ('loudness_lufs', 'loudness_ref_lufs', 'loudness_shift_lu', 'energy_spread_db', 'energy_ref_spread_db')
+ENERGY_ALIGNED_KEYS = ('energy_rmse_db', 'energy_corr')
+ENERGY_FLOOR_DB = 40.0   # a frame sounds within this many dB of the row's loudest frame.  An uncalibrated choice (module docstring).
+
+
+def sounding_frames(track_db, floor_db=ENERGY_FLOOR_DB):
+    """one bool per frame of a dB track: within floor_db of the loudest frame"""
+    track = [float(v) for v in track_db]
+    top = max(track) if track else 0.0
+    return [v > top - floor_db for v in track]
+
+
+def energy_spread(track_db, floor_db=ENERGY_FLOOR_DB):
+    """standard deviation of the frame level in dB over the sounding frames; None for an empty track"""
+    track = [float(v) for v in track_db]
+    v = [x for x, s in zip(track, sounding_frames(track, floor_db)) if s]
+    if not v:
+        return None
+    mean = sum(v) / len(v)
+    return math.sqrt(sum((x - mean) ** 2 for x in v) / len(v))
+
+
+def _finite(v):
+    return None if v is None or math.isinf(v) or math.isnan(v) else float(v)
+
+
+def energy_fields(loudness, track_db, ref_loudness, ref_track_db):
+    """the ENERGY_KEYS of one record from the integrated loudness (LUFS) and the frame level track (dB) of the synthesised
+    waveform and of the recording.  loudness and track_db are None when the row has no waveform (fewer than the vocoder's 4
+    frames); a loudness of -inf (no gated block) becomes None, and so does the shift when either side's is."""
+    lu, ref = _finite(loudness), _finite(ref_loudness)
+    return {'loudness_lufs': lu, 'loudness_ref_lufs': ref,
+            'loudness_shift_lu': lu - ref if lu is not None and ref is not None else None,
+            'energy_spread_db': energy_spread(track_db) if track_db is not None else None,
+            'energy_ref_spread_db': energy_spread(ref_track_db) if ref_track_db is not None else None}
+
+
+def energy_path_fields(pairs):
+    """the ENERGY_ALIGNED_KEYS from the (synthesis dB, recording dB) pairs at the warping path's points where both sides sound:
+    the root mean square difference and the Pearson correlation (None under 2 points or at a zero variance)"""
+    pairs = [(float(a), float(b)) for a, b in pairs]
+    out = dict.fromkeys(ENERGY_ALIGNED_KEYS)
+    if not pairs:
+        return out
+    n = len(pairs)
+    out['energy_rmse_db'] = math.sqrt(sum((a - b) ** 2 for a, b in pairs) / n)
+    ma, mb = sum(a for a, _ in pairs) / n, sum(b for _, b in pairs) / n
+    sxx, syy = sum((a - ma) ** 2 for a, _ in pairs), sum((b - mb) ** 2 for _, b in pairs)
+    if n >= 2 and sxx > 0.0 and syy > 0.0:
+        out['energy_corr'] = max(-1.0, min(1.0, sum((a - ma) * (b - mb) for a, b in pairs) / math.sqrt(sxx * syy)))
+    return out
+
+
+def _energy_stats(records):
+    """Over the rows that stopped at the gate: `n_energy` of them have a loudness on both sides and carry
+    `loudness_shift_lu_mean` (signed), `loudness_shift_lu_abs_mean` and `energy_spread_ratio_mean` (synthesised spread /
+    recording's, over the rows whose recording's spread is not 0; far below 1 is a flat level contour); with the aligned keys
+    also `energy_rmse_db_mean` and `energy_corr_mean`, over the rows that have the value."""
+    stopped = [r for r in records if not r['hit_max']]
+    rows = [r for r in stopped if r.get('loudness_shift_lu') is not None]
+    out = {'n_energy': len(rows),
+           'loudness_shift_lu_mean': _mean([r['loudness_shift_lu'] for r in rows]),
+           'loudness_shift_lu_abs_mean': _mean([abs(r['loudness_shift_lu']) for r in rows]),
+           'energy_spread_ratio_mean': _mean([r['energy_spread_db'] / r['energy_ref_spread_db'] for r in rows
+                                              if r.get('energy_spread_db') is not None and r.get('energy_ref_spread_db')])}
+    if any('energy_rmse_db' in r for r in records):
+        for k in ENERGY_ALIGNED_KEYS:
+            out[k + '_mean'] = _mean([r[k] for r in stopped if r.get(k) is not None])
+    return out
+
+
+def _energy_block(records, emotions):
+    """the `energy` entry of summarize(): overall and by_emotion `_energy_stats`; every emotion also carries
+    `loudness_vs_neu_lu` and `loudness_ref_vs_neu_lu`, the mean loudness of its stopped rows minus that of the emotion named
+    'neu', for the synthesis and for the recordings (None where either has no row with a loudness, or no 'neu' is listed):
+    whether the emotions keep their level order."""
+    stopped = [r for r in records if not r['hit_max']]
+
+    def level(i, key):
+        return _mean([r[key] for r in stopped if int(r['emotion']) == i and r.get(key) is not None])
+
+    neu = list(emotions).index('neu') if 'neu' in emotions else None
+    by = {}
+    for i, name in enumerate(emotions):
+        st = _energy_stats([r for r in records if int(r['emotion']) == i])
+        for key, out_key in (('loudness_lufs', 'loudness_vs_neu_lu'), ('loudness_ref_lufs', 'loudness_ref_vs_neu_lu')):
+            a, b = level(i, key), level(neu, key) if neu is not None else None
+            st[out_key] = a - b if a is not None and b is not None else None
+        by[name] = st
+    return {'overall': _energy_stats(records), 'by_emotion': by}
+
+
 STYLE_KEYS = ('style_emotion', 'style_hit', 'style_own_rank', 'style_own_dist', 'style_silhouette')
 
 
@@ -250,7 +351,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
     alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack; when
     they carry the aligned keys (evaluate(aligned=True)), `n_aligned` and the means of `_aligned_stats`.
     When they carry the style keys (evaluate(style=True)) the result gains 'style': `_style_block`, with k, n_recordings and
-    ref_accuracy from style_info, else from the records' own `style_info` (StyleRecords), else None."""
+    ref_accuracy from style_info, else from the records' own `style_info` (StyleRecords), else None.
+    When they carry the energy keys (evaluate(energy=True)) the result gains 'energy': `_energy_block`."""
     if style_info is None:
         style_info = getattr(records, 'style_info', None)
     records = list(records)
@@ -274,4 +376,6 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
            'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}
     if any('style_emotion' in r for r in records):
         out['style'] = _style_block(records, emotions, style_info)
+    if any('loudness_shift_lu' in r for r in records):
+        out['energy'] = _energy_block(records, emotions)
     return out

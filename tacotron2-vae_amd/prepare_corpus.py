@@ -4,6 +4,7 @@ trim_bounds, crop; csrc/resample.hip).
 
     python prepare_corpus.py --filelist_path F --out_dir D --out_filelist F2
            [--sampling_rate 16000] [--trim_db 40 | --no_trim] [--pad_frames 2] [--batch_size 64] [--report R.json]
+           [--lufs TARGET [--lufs_scope utterance|speaker] [--peak_db -1.0]]
 
 Filelist rows are `path|text|speaker|emotion` (any column count, the path first).  Each wav is read as it lies in the file
 (int16 goes to the device as it is; int32 and float wavs are scaled to [-1, 1) on the host; a wav with more than one channel
@@ -11,13 +12,28 @@ is skipped, with its reason in the report), and the rows run in length-sorted ra
 resample launch per distinct source rate in a batch.  D/<basename>.wav is written at the target rate (a basename that
 several rows share gets its parent directories prefixed), F2 holds the new paths with the other columns untouched, in the
 order of F, without the skipped rows.  The report (R.json, default D/report.json) has per row: source rate, samples in and
-out, seconds trimmed at head and tail, peak, clipped samples and the all-silent flag; and totals by source rate."""
+out, seconds trimmed at head and tail, peak, clipped samples and the all-silent flag; and totals by source rate.
+
+--lufs TARGET (off by default: without it the written bits and the report are what they were) also normalises the level: the
+trimmed wav's integrated loudness (t2v_hip.loudness: ITU-R BS.1770-4 / EBU R 128, K-weighted and gated) is measured and the
+wav is scaled (t2v_hip.scale_rows) by TARGET minus that many dB before the 16-bit write-out, so `peak` and `clipped_samples`
+describe what is written.  A wav without a loudness (shorter than 400 ms, or below the gates) is written unscaled with
+`loudness_lufs: null`.  A gain that would push a wav's peak above --peak_db dBFS is lowered to exactly that (`gain_limited`).
+--lufs_scope speaker gives every speaker (filelist column 3) ONE gain, so that the level differences between that speaker's
+emotions survive: a first pass measures every row and writes nothing, the speaker's loudness is pooled from the rows' gated
+block sums and counts, -0.691 + 10 log10(sum of gated sums / sum of gated counts), and a second pass applies TARGET minus that.
+The relative gate stays per row here: it is not that of the speaker's concatenated recordings.  A peak limit lowers the whole
+speaker's gain.  The report then has per row `loudness_lufs` (before the gain), `gain_db` and `gain_limited`, per speaker the
+pooled loudness and the gain, and in `loudness` the mean and spread of the measured loudness."""
 import argparse
 import json
+import math
 import os
 
 DEFAULT_BATCH_SIZE = 64
 DEFAULT_SAMPLING_RATE = 16000
+DEFAULT_PEAK_DB = -1.0
+LUFS_SCOPES = ('utterance', 'speaker')
 
 
 def build_arg_parser():
@@ -34,6 +50,12 @@ def build_arg_parser():
     p.add_argument('--pad_frames', type=int, default=DEFAULT_PAD_FRAMES, help="frames of 256 samples kept around what sounds")
     p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="wavs per ragged batch")
     p.add_argument('--report', default=None, help="report .json (default <out_dir>/report.json)")
+    p.add_argument('--lufs', type=float, default=None, metavar='TARGET',
+                   help="normalise the integrated loudness (BS.1770) to TARGET LUFS; off by default")
+    p.add_argument('--lufs_scope', choices=LUFS_SCOPES, default='utterance',
+                   help="one gain per wav, or one per speaker (filelist column 3)")
+    p.add_argument('--peak_db', type=float, default=DEFAULT_PEAK_DB, metavar='DB',
+                   help="no gain lifts a wav's peak above DB dBFS (<= 0)")
     return p
 
 
@@ -47,9 +69,59 @@ def parse_args(argv=None):
         raise SystemExit("--pad_frames must be >= 0")
     if not args.no_trim and not 0.0 < args.trim_db < float('inf'):
         raise SystemExit("--trim_db must be a positive number of dB")
+    if not args.peak_db <= 0.0 or math.isinf(args.peak_db):
+        raise SystemExit("--peak_db must be a finite level <= 0 dBFS")
+    if args.lufs is not None and not math.isfinite(args.lufs):
+        raise SystemExit("--lufs must be a finite level in LUFS")
     if args.report is None:
         args.report = os.path.join(args.out_dir, 'report.json')
     return args
+
+
+def gain_for(target, loudness, peak, peak_db=DEFAULT_PEAK_DB):
+    """(gain in dB, limited) that brings `loudness` (LUFS; None or -inf: no loudness, gain 0) to `target`, lowered to exactly
+    peak_db - 20 log10(peak) where it would lift the peak (linear, of the same samples) above peak_db dBFS"""
+    if loudness is None or math.isinf(loudness) or math.isnan(loudness):
+        return 0.0, False
+    gain = float(target) - float(loudness)
+    if peak > 0.0:
+        room = float(peak_db) - 20.0 * math.log10(peak)
+        if gain > room:
+            return room, True
+    return gain, False
+
+
+def pooled_loudness(gated_sums, gated_blocks):
+    """-0.691 + 10 log10(sum of the rows' gated block sums / sum of their gated block counts); None without a gated block"""
+    total, count = sum(gated_sums), sum(gated_blocks)
+    return -0.691 + 10.0 * math.log10(total / count) if count > 0 and total > 0.0 else None
+
+
+def speaker_gains(rows, target, peak_db=DEFAULT_PEAK_DB):
+    """rows: (speaker, gated_sum, gated_blocks, peak) per measured wav.  {speaker: dict(loudness_lufs, gain_db, gain_limited,
+    rows)}: the pooled loudness of the speaker's rows, and target minus it, limited by the speaker's largest peak, so that one
+    gain serves all the speaker's rows; a speaker without a gated block keeps gain 0 and loudness None."""
+    by = {}
+    for speaker, gsum, gcount, peak in rows:
+        t = by.setdefault(speaker, dict(sums=[], counts=[], peak=0.0))
+        t['sums'].append(gsum)
+        t['counts'].append(gcount)
+        t['peak'] = max(t['peak'], peak)
+    out = {}
+    for speaker, t in by.items():
+        loud = pooled_loudness(t['sums'], t['counts'])
+        gain, limited = gain_for(target, loud, t['peak'], peak_db)
+        out[speaker] = dict(loudness_lufs=loud, gain_db=gain, gain_limited=limited, rows=len(t['sums']))
+    return out
+
+
+def loudness_totals(records):
+    """mean and spread (standard deviation) of the measured loudness over the written rows that have one"""
+    v = [r['loudness_lufs'] for r in records if not r.get('skipped') and r.get('loudness_lufs') is not None]
+    if not v:
+        return dict(rows=0, mean_lufs=None, spread_lu=None)
+    mean = sum(v) / len(v)
+    return dict(rows=len(v), mean_lufs=mean, spread_lu=math.sqrt(sum((x - mean) ** 2 for x in v) / len(v)))
 
 
 def read_rows(path):
@@ -145,6 +217,50 @@ def process_batch(items, target_rate, trim_db, pad_frames):
     return out
 
 
+def measure_batch(items, target_rate, trim_db, pad_frames):
+    """resample -> trim_bounds -> crop (fp32) -> loudness of one ragged batch.  Returns (y (B, max count) float32 on the device,
+    counts, per-item record fields without the write-out's, per-item (integrated LUFS or None, gated_sum, gated_blocks, peak))."""
+    import t2v_hip
+    from synthesizer import resample_rows
+    y, n = resample_rows(items, target_rate)
+    if trim_db is None:
+        bounds = [[0, k] for k in n]
+    else:
+        bounds = t2v_hip.trim_bounds(y, n, trim_db, pad_frames).cpu().tolist()
+    y, counts = t2v_hip.crop(y, bounds)
+    loud = t2v_hip.loudness(y, [max(c, 1) for c in counts], target_rate)
+    peaks = y.abs().amax(dim=1).tolist()
+    fields, measured = [], []
+    for b, (rate, data) in enumerate(items):
+        start, end = bounds[b]
+        fields.append(dict(source_rate=rate, target_rate=target_rate, samples_in=int(len(data)), samples_resampled=n[b],
+                           samples_out=counts[b], trimmed_head_s=start / float(target_rate),
+                           trimmed_tail_s=(n[b] - end) / float(target_rate)))
+        lu = loud.integrated[b]
+        measured.append((None if math.isinf(lu) else lu, loud.gated_sum[b], loud.gated_blocks[b], float(peaks[b])))
+    return y, counts, fields, measured
+
+
+def process_batch_lufs(items, target_rate, trim_db, pad_frames, target, peak_db, gains=None):
+    """process_batch with the level normalised: measure_batch -> gain -> scale_rows -> crop to int16.  gains: one
+    (gain_db, limited) per item (the speaker's), or None for each row's own, gain_for(target, its loudness, its peak)."""
+    import t2v_hip
+    y, counts, fields, measured = measure_batch(items, target_rate, trim_db, pad_frames)
+    if gains is None:
+        gains = [gain_for(target, lu, peak, peak_db) for lu, _, _, peak in measured]
+    lengths = [max(c, 1) for c in counts]
+    t2v_hip.scale_rows(y, lengths, [10.0 ** (g / 20.0) for g, _ in gains])
+    pcm, counts, stats = t2v_hip.crop(y, [[0, c] for c in counts], pcm16=True, return_stats=True)
+    pcm = pcm.cpu().numpy()
+    out = []
+    for b in range(len(items)):
+        clipped, peak = stats[b]
+        out.append((pcm[b, :counts[b]].copy(),
+                    dict(fields[b], peak=peak, clipped_samples=clipped, all_silent=bool(peak == 0.0),
+                         loudness_lufs=measured[b][0], gain_db=gains[b][0], gain_limited=gains[b][1])))
+    return out
+
+
 def main(argv=None):
     args = parse_args(argv)
     from scipy.io.wavfile import write
@@ -154,6 +270,15 @@ def main(argv=None):
     rows = read_rows(args.filelist_path)
     if not rows:
         raise SystemExit("%s: no rows" % args.filelist_path)
+    by_speaker = args.lufs is not None and args.lufs_scope == 'speaker'
+    if args.lufs is not None:
+        try:
+            t2v_hip.kweight_coefficients(args.sampling_rate)
+        except ValueError as e:
+            raise SystemExit("--lufs: %s" % e)
+    if by_speaker and any(len(r) < 3 for r in rows):
+        raise SystemExit("%s: --lufs_scope speaker needs the speaker in a third column (path|text|speaker|...)"
+                         % args.filelist_path)
     os.makedirs(args.out_dir, exist_ok=True)
     names = output_names([r[0] for r in rows])
     records = [None] * len(rows)
@@ -171,18 +296,36 @@ def main(argv=None):
         except (ValueError, OSError) as e:
             records[i] = dict(path=r[0], skipped=str(e))
     new_paths = [None] * len(rows)
-    for idx in length_groups(lengths, args.batch_size):
-        group, items = [], []
-        for k in idx:
-            i = keep[k]
-            try:
-                items.append(read_wav(rows[i][0]))
-                group.append(i)
-            except (ValueError, OSError) as e:
-                records[i] = dict(path=rows[i][0], skipped=str(e))
-        if not items:
-            continue
-        done = process_batch(items, args.sampling_rate, None if args.no_trim else args.trim_db, args.pad_frames)
+    trim_db = None if args.no_trim else args.trim_db
+
+    def batches():
+        for idx in length_groups(lengths, args.batch_size):
+            group, items = [], []
+            for k in idx:
+                i = keep[k]
+                if records[i] is not None and records[i].get('skipped'):
+                    continue
+                try:
+                    items.append(read_wav(rows[i][0]))
+                    group.append(i)
+                except (ValueError, OSError) as e:
+                    records[i] = dict(path=rows[i][0], skipped=str(e))
+            if items:
+                yield group, items
+
+    speakers = None
+    if by_speaker:                                                       # first pass: measure every row, write nothing
+        measured = []
+        for group, items in batches():
+            for i, m in zip(group, measure_batch(items, args.sampling_rate, trim_db, args.pad_frames)[3]):
+                measured.append((rows[i][2], m[1], m[2], m[3]))
+        speakers = speaker_gains(measured, args.lufs, args.peak_db)
+    for group, items in batches():
+        if args.lufs is None:
+            done = process_batch(items, args.sampling_rate, trim_db, args.pad_frames)
+        else:
+            gains = [(speakers[rows[i][2]]['gain_db'], speakers[rows[i][2]]['gain_limited']) for i in group] if by_speaker else None
+            done = process_batch_lufs(items, args.sampling_rate, trim_db, args.pad_frames, args.lufs, args.peak_db, gains)
         for i, (pcm, rec) in zip(group, done):
             new_paths[i] = os.path.join(args.out_dir, names[i])
             write(new_paths[i], args.sampling_rate, pcm)
@@ -194,6 +337,10 @@ def main(argv=None):
     report = dict(target_rate=args.sampling_rate, trim_db=None if args.no_trim else args.trim_db, pad_frames=args.pad_frames,
                   n_rows=len(rows), n_written=len(rows) - n_skipped, n_skipped=n_skipped, by_source_rate=summarize(records),
                   rows=records)
+    if args.lufs is not None:
+        report['loudness'] = dict(loudness_totals(records), target_lufs=args.lufs, scope=args.lufs_scope, peak_db=args.peak_db)
+        if speakers is not None:
+            report['speakers'] = speakers
     with open(args.report, 'w', encoding='utf-8') as f:
         json.dump(report, f, indent=1)
     print("%s: %d wavs at %d Hz, %d skipped; %s" % (args.out_filelist, len(rows) - n_skipped, args.sampling_rate, n_skipped,

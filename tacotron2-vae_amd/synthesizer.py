@@ -236,6 +236,30 @@ class Synthesizer(object):
         return tracks
 
     @torch.no_grad()
+    def loudness(self, paths, batch_size=64):
+        """Loudness and energy of the wavs (`t2v_hip.loudness`: ITU-R BS.1770-4, K-weighted and gated), in input order: one
+        dict per wav with `loudness_lufs` (integrated; -inf for a wav without a gated 400 ms block), `momentary_max_lufs` (its
+        loudest block) and `energy_db` (1-D device tensor: the K-weighted level of the front end's samples // 256 + 1 frames,
+        `t2v_hip.energy_db`), each what the meter gives for that wav alone.  The wavs go through `load_wavs` (resample= and
+        trim_db= apply), sorted by length, in ragged batches of at most batch_size."""
+        import t2v_hip
+        paths = list(paths)
+        if not paths:
+            raise ValueError("loudness: no paths")
+        if self.hparams.hop_length != t2v_hip.TRIM_HOP:
+            raise ValueError("loudness: the frame track is built for hop %d, the front end has hop %d"
+                             % (t2v_hip.TRIM_HOP, self.hparams.hop_length))
+        out = [None] * len(paths)
+        for idx in length_groups(self.wav_lengths(paths), batch_size):
+            y, n = self.load_wavs([paths[i] for i in idx])
+            r = t2v_hip.loudness(y, n, self.hparams.sampling_rate)
+            db = t2v_hip.energy_db(r.frame_ms)
+            for b, i in enumerate(idx):
+                out[i] = {'loudness_lufs': r.integrated[b], 'momentary_max_lufs': r.momentary_max[b],
+                          'energy_db': db[b, :n[b] // t2v_hip.TRIM_HOP + 1]}
+        return out
+
+    @torch.no_grad()
     def latents(self, paths, batch_size=64):
         """(prosody (N, E), mu, logvar, z (N, z_latent_dim)) of every wav, in input order, each row what
         `model.vae_gst(load_mel(paths[i]))` returns (up to fp32 summation order).  The wavs are sorted by length and run in
@@ -483,7 +507,8 @@ class Synthesizer(object):
         return out
 
     @torch.no_grad()
-    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False):
+    def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False,
+                 energy=False):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
         recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
@@ -510,9 +535,15 @@ class Synthesizer(object):
         of the recordings' mels (`t2v_hip.mel_cepstrum`), one `t2v_hip.aligned_scores` call and one copy to the host.  Alone
         it gives every row mcd_db and warp_dev, None on the six F0 values, and needs no vocoder; with prosody=True the two
         pitch tracks computed there, cut to n_frames and n_ref_frames, feed the same call (a row decoded to fewer than the
-        vocoder's 4 frames keeps None on its F0 values and still gets mcd_db).  It draws nothing and changes no other key."""
+        vocoder's 4 frames keeps None on its F0 values and still gets mcd_db).  It draws nothing and changes no other key.
+        energy=True (needs the Griffin-Lim vocoder, like prosody) adds the level of both sides (evaluation.ENERGY_KEYS):
+        `t2v_hip.loudness` on the same two waveforms as prosody=True, which it shares when both are on (the vocoder runs once,
+        with the np.random draws of prosody=True; alone it draws what prosody=True would), one copy of the frame tracks to the
+        host per group.  With aligned=True as well, evaluation.ENERGY_ALIGNED_KEYS compare the two dB tracks along the warping
+        path (a few index operations on the device per group, one more copy).  Without it every record and summary holds
+        exactly the keys it held."""
         import t2v_hip
-        from evaluation import aligned_fields, prosody_fields
+        from evaluation import aligned_fields, energy_fields, energy_path_fields, prosody_fields, ENERGY_ALIGNED_KEYS, ENERGY_FLOOR_DB
         if condition not in ('ref', 'emotion'):
             raise ValueError("condition must be 'ref' or 'emotion', got %r" % (condition,))
         if batch_size < 1:
@@ -523,6 +554,13 @@ class Synthesizer(object):
             raise RuntimeError("evaluate(condition='emotion') needs the emotion centroids: use load(), not load_checkpoint()")
         if prosody and not isinstance(self.vocoder, GriffinLimVocoder):
             raise RuntimeError("evaluate(prosody=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
+        if energy and not isinstance(self.vocoder, GriffinLimVocoder):
+            raise RuntimeError("evaluate(energy=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
+        if energy:
+            t2v_hip.kweight_coefficients(self.hparams.sampling_rate)        # an unsupported rate is refused before any work
+            if self.hparams.hop_length != t2v_hip.TRIM_HOP:
+                raise ValueError("evaluate(energy=True): the frame track is built for hop %d, the front end has hop %d"
+                                 % (t2v_hip.TRIM_HOP, self.hparams.hop_length))
         if prosody and (self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE or self.hparams.hop_length != t2v_hip.F0_HOP):
             raise ValueError("evaluate(prosody=True): the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
                              % (t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
@@ -568,9 +606,8 @@ class Synthesizer(object):
             if alignment:
                 for b, fields in enumerate(self._alignment_rows(al, n, lens)[0]):
                     records[i0 + b].update(fields)
-            if prosody:
-                # both sides' tracks side by side in one tensor: one copy to the host per group
-                tracks = [t2v_hip.f0(y_uniq, samples_uniq)]
+            if prosody or energy:
+                # the waveforms of the rows that have one, for the pitch and for the level
                 can = [b for b in range(len(group)) if n[b] >= 4]
                 if can:
                     sel = torch.tensor(can, device=mel.device)
@@ -578,12 +615,28 @@ class Synthesizer(object):
                     y_syn = torch.zeros(len(can), max(w.numel() for w in wavs), device=mel.device)
                     for k, w in enumerate(wavs):
                         y_syn[k, :w.numel()] = w
+            if prosody:
+                # both sides' tracks side by side in one tensor: one copy to the host per group
+                tracks = [t2v_hip.f0(y_uniq, samples_uniq)]
+                if can:
                     tracks.append(t2v_hip.f0(y_syn, [w.numel() for w in wavs]))
                 width = max(t.size(1) for t in tracks)
                 host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in tracks], 0).cpu().tolist()
                 for b in range(len(group)):
                     syn_track = host[len(uniq) + can.index(b)][:n[b]] if b in can else None
                     records[i0 + b].update(prosody_fields(syn_track, host[which[b]][:n_ref[b]]))
+            if energy:
+                loud = [t2v_hip.loudness(y_uniq, samples_uniq, self.hparams.sampling_rate)]
+                if can:
+                    loud.append(t2v_hip.loudness(y_syn, [w.numel() for w in wavs], self.hparams.sampling_rate))
+                levels = [t2v_hip.energy_db(r.frame_ms) for r in loud]
+                width = max(t.size(1) for t in levels)
+                host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in levels], 0).cpu().tolist()
+                for b in range(len(group)):
+                    k = can.index(b) if b in can else None
+                    records[i0 + b].update(energy_fields(loud[1].integrated[k] if k is not None else None,
+                                                         host[len(uniq) + k][:n[b]] if k is not None else None,
+                                                         loud[0].integrated[which[b]], host[which[b]][:n_ref[b]]))
             if aligned:
                 cep = t2v_hip.mel_cepstrum(mel_postnet, n)
                 cep_ref = t2v_hip.mel_cepstrum(ref_mels, n_uniq)
@@ -598,11 +651,34 @@ class Synthesizer(object):
                     if can:
                         w = min(max(n), tracks[1].size(1))
                         f0x[torch.tensor(can, device=mel.device), :w] = tracks[1][:, :w]
-                r = t2v_hip.aligned_scores(cep, n, cep_ref if same else cep_ref[pick], n_ref, f0x, f0y)
+                r = t2v_hip.aligned_scores(cep, n, cep_ref if same else cep_ref[pick], n_ref, f0x, f0y, return_path=energy)
                 host = torch.cat([r.counts.double(), r.sums.double()], 1).cpu().tolist()
                 for b in range(len(group)):
                     records[i0 + b].update(aligned_fields(host[b][:len(t2v_hip.ALIGNED_COUNTS)], host[b][len(t2v_hip.ALIGNED_COUNTS):],
                                                           f0=prosody and n[b] >= 4))
+                if energy:
+                    # the two dB tracks at the path's points, and whether both frames sound: one copy to the host per group
+                    for b in range(len(group)):
+                        records[i0 + b].update(dict.fromkeys(ENERGY_ALIGNED_KEYS))
+                    if can:
+                        dev = mel.device
+                        sel = torch.tensor(can, device=dev)
+                        n_x = torch.tensor([n[b] for b in can], device=dev)
+                        n_y = torch.tensor([n_ref[b] for b in can], device=dev)
+                        neg = float('-inf')
+                        ex = levels[1].masked_fill(torch.arange(levels[1].size(1), device=dev)[None, :] >= n_x[:, None], neg)
+                        ey = levels[0][torch.tensor([which[b] for b in can], device=dev)]
+                        ey = ey.masked_fill(torch.arange(ey.size(1), device=dev)[None, :] >= n_y[:, None], neg)
+                        path = r.path[sel].long()
+                        pi = torch.minimum(path[:, :, 0].clamp(min=0), n_x[:, None] - 1)
+                        pj = torch.minimum(path[:, :, 1].clamp(min=0), n_y[:, None] - 1)
+                        a, c = ex.gather(1, pi), ey.gather(1, pj)
+                        keep = ((a > ex.amax(1, keepdim=True) - ENERGY_FLOOR_DB) & (c > ey.amax(1, keepdim=True) - ENERGY_FLOOR_DB)
+                                & (torch.arange(path.size(1), device=dev)[None, :] < r.n_points[sel][:, None]))
+                        host = torch.stack([a.double(), c.double(), keep.double()], 1).cpu().tolist()
+                        for k, b in enumerate(can):
+                            pa, pc, pk = host[k]
+                            records[i0 + b].update(energy_path_fields([(u, v) for u, v, w in zip(pa, pc, pk) if w]))
             if style:
                 new = [j for j, p in enumerate(uniq) if rec_mu[rec_index[p]] is None]
                 if new:

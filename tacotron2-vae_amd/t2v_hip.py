@@ -107,7 +107,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes',
            't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours',
            't2v_mel_cepstrum', 't2v_cep_dtw_scratch_bytes', 't2v_cep_dtw_path', 't2v_cep_dtw_forward', 't2v_cep_dtw_walk',
-           't2v_path_scores')
+           't2v_path_scores', 't2v_loudness', 't2v_loudness_scratch_bytes', 't2v_scale_rows')
 
 
 def lib_path():
@@ -262,6 +262,10 @@ def load_library():
     lib.t2v_resample.argtypes = [vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     lib.t2v_trim_bounds.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp]
     lib.t2v_crop_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.t2v_loudness_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.t2v_loudness_scratch_bytes.restype = C.c_size_t
+    lib.t2v_loudness.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    lib.t2v_scale_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.t2v_alignment_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_alignment_scratch_bytes.restype = C.c_size_t
     lib.t2v_alignment_stats.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp,
@@ -2038,6 +2042,148 @@ def crop(y, bounds, pcm16=False, return_stats=False):
     s = stats.cpu()
     peaks = s[:, 1].contiguous().view(torch.float32).tolist()
     return out, counts, [(int(c), float(p)) for c, p in zip(s[:, 0].tolist(), peaks)]
+
+
+LOUDNESS_CHUNK = 64                     # T2V_LOUDNESS_CHUNK of include/t2vae.h: samples per lane of k_loud_filter
+LOUDNESS_TILE = 16384                   # T2V_LOUDNESS_TILE: samples per workgroup tile, between which the filter state is scanned
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 48000
+LOUDNESS_OFFSET = -0.691                # BS.1770: a full-scale 997 Hz sine reads -3.01 LUFS
+_LOUDNESS_TABLES = {}                   # rate -> (host table, {device: device table})
+
+
+class Loudness(collections.namedtuple('Loudness', 'integrated ungated momentary_max gated_sum gated_blocks n_blocks frame_ms')):
+    """What loudness() gives.  Host lists of one value per row: integrated (LUFS: gated as BS.1770-4 says, -inf for a row
+    without a gated block), ungated (LUFS of the whole row's mean square), momentary_max (LUFS of the loudest 400 ms block, -inf
+    without one), gated_sum and gated_blocks (the sum of the gated blocks' powers and their count: sum them over rows to pool,
+    -0.691 + 10 log10(sum / count)), n_blocks (complete 400 ms blocks); frame_ms (B, max frame count) float32 on the device,
+    the K-weighted mean square of the front end's frames, 0 past a row's frame count (energy_db turns it into dB)."""
+    __slots__ = ()
+
+
+def _loudness_rate(sr, who):
+    if isinstance(sr, bool) or int(sr) != sr or sr % 10 or not LOUDNESS_MIN_RATE <= sr <= LOUDNESS_MAX_RATE:
+        raise ValueError("%s: the rate %r is not supported: a multiple of 10 Hz in %d..%d (100 ms must be whole samples)"
+                         % (who, sr, LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE))
+    return int(sr)
+
+
+def kweight_coefficients(sr):
+    """The K-weighting of ITU-R BS.1770 at the rate sr, as libebur128 and pyloudnorm derive it, in fp64: the numpy array
+    (b0, b1, b2, a1, a2, d1, d2) of the high shelf b / (1, a1, a2) followed by the high pass (1, -2, 1) / (1, d1, d2).  At
+    48 000 Hz these are the standard's table.  ValueError, naming the rate, unless sr is a multiple of 10 Hz in 8 000..48 000."""
+    import numpy as np
+    sr = _loudness_rate(sr, "kweight_coefficients")
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = math.tan(math.pi * f0 / sr)
+    Vh = 10.0 ** (G / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+             2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = math.tan(math.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    return np.array(shelf + [2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], dtype=np.float64)
+
+
+def loudness_table(sr):
+    """The fp64 table t2v_loudness takes (include/t2vae.h): the coefficients rounded to fp32 (the six numbers the filter is
+    defined by, and the 1 -2 1 of the high pass), and the powers M^0 .. M^64 of M = A^LOUDNESS_CHUNK, A the zero-input step of
+    the cascade, computed from the rounded coefficients.  A read-only host array, cached per rate."""
+    import numpy as np
+    sr = _loudness_rate(sr, "loudness")
+    hit = _LOUDNESS_TABLES.get(sr)
+    if hit is None:
+        c32 = kweight_coefficients(sr).astype(np.float32)
+        b0, b1, b2, a1, a2, d1, d2 = c32.astype(np.float64)
+        A = np.array([[-a1, 1.0, 0.0, 0.0], [-a2, 0.0, 0.0, 0.0], [-2.0 - d1, 0.0, -d1, 1.0], [1.0 - d2, 0.0, -d2, 0.0]])
+        M = np.linalg.matrix_power(A, LOUDNESS_CHUNK)
+        table = np.zeros(8 + 16 * 65, dtype=np.float64)
+        table[:7] = c32
+        P = np.eye(4)
+        for p in range(65):
+            table[8 + 16 * p:24 + 16 * p] = P.reshape(-1)
+            P = M @ P
+        table.setflags(write=False)
+        hit = _LOUDNESS_TABLES[sr] = (table, {})
+    return hit[0]
+
+
+def energy_db(frame_ms):
+    """K-weighted frame level in dB (LUFS scale): -0.691 + 10 log10 max(ms, 1e-12); a tensor, a numpy array or a number"""
+    if torch.is_tensor(frame_ms):
+        return LOUDNESS_OFFSET + 10.0 * torch.log10(frame_ms.clamp(min=1e-12))
+    import numpy as np
+    return LOUDNESS_OFFSET + 10.0 * np.log10(np.maximum(np.asarray(frame_ms, dtype=np.float64), 1e-12))
+
+
+def _lufs(power):
+    return LOUDNESS_OFFSET + 10.0 * math.log10(power) if power > 0.0 else float('-inf')
+
+
+def loudness(y, lengths, sr=16000, return_blocks=False):
+    """BS.1770-4 / EBU R 128 loudness and the K-weighted frame energy (csrc/loudness.hip k_loud_filter, k_loud_reduce): y (B, S)
+    float32 CUDA tensor of waveforms at the rate sr, row b of lengths[b] samples (a list, a CPU tensor or a device int tensor);
+    samples at and past a row's length are not read.  Blocks are 400 ms with a 100 ms hop, complete blocks only; frames are the
+    mel front end's (hop 256, window 1024 centred on 256 t, lengths[b] // 256 + 1 of them: the grid of f0() and trim_bounds()).
+    Returns a `Loudness`; its per-row scalars come in one device-to-host copy.  With return_blocks also the block powers
+    (B, max block count) float32 on the device, 0 past a row's blocks.  A row gives the same bits alone, in any batch and at any
+    stride.  ValueError, naming the rate, unless sr is a multiple of 10 Hz in 8 000..48 000."""
+    lib = _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("loudness: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("loudness: empty input %s" % (tuple(y.shape),))
+    if S > (1 << 30):
+        raise ValueError("loudness: rows of %d samples exceed the 2^30 supported" % S)
+    table = loudness_table(sr)
+    hop = int(sr) // 10
+    n = _wave_lengths(lengths, B, S, "loudness")
+    dev_tables = _LOUDNESS_TABLES[int(sr)][1]
+    t = dev_tables.get(y.device)
+    if t is None:
+        t = dev_tables[y.device] = torch.from_numpy(table.copy()).to(y.device)
+    y = _f32c(y)
+    ms_stride = S // TRIM_HOP + 1
+    blk_stride = max((S - 4 * hop) // hop + 1 if S >= 4 * hop else 0, 1)
+    ms = torch.empty(B, ms_stride, device=y.device, dtype=torch.float32)
+    blocks = torch.empty(B, blk_stride, device=y.device, dtype=torch.float32)
+    rows = torch.empty(B, 8, device=y.device, dtype=torch.int32)
+    scratch = torch.empty(int(lib.t2v_loudness_scratch_bytes(B, S, hop)), device=y.device, dtype=torch.uint8)
+    _check(lib.t2v_loudness(_p(y), _p(n.to(y.device)), S, B, _p(t), hop, _p(ms), ms_stride, _p(blocks), blk_stride, _p(rows),
+                            _p(scratch), _stream()), 't2v_loudness')
+    r = rows.cpu()
+    f = r[:, :3].contiguous().view(torch.float32).double().tolist()
+    counts, nb = r[:, 3].tolist(), r[:, 4].tolist()
+    T = int(n.max()) // TRIM_HOP + 1
+    if T < ms_stride:
+        ms = ms[:, :T].contiguous()
+    out = Loudness(integrated=[_lufs(g / c) if c else float('-inf') for (g, _, _), c in zip(f, counts)],
+                   ungated=[_lufs(u) for _, u, _ in f], momentary_max=[_lufs(m) for _, _, m in f],
+                   gated_sum=[g for g, _, _ in f], gated_blocks=counts, n_blocks=nb, frame_ms=ms)
+    if not return_blocks:
+        return out
+    nb_max = max(max(nb), 1)
+    return out, (blocks[:, :nb_max].contiguous() if nb_max < blk_stride else blocks)
+
+
+def scale_rows(y, lengths, gains):
+    """y[b, :lengths[b]] *= gains[b] in place (csrc/loudness.hip k_scale_rows): y (B, S) contiguous float32 CUDA tensor, gains B
+    numbers (a list, a CPU or a device tensor).  Columns at and past a row's length are untouched.  Returns y."""
+    lib = _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("scale_rows: y must be a contiguous float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("scale_rows: empty input %s" % (tuple(y.shape),))
+    n = _wave_lengths(lengths, B, S, "scale_rows")
+    g = torch.as_tensor(gains, dtype=torch.float32).reshape(-1)
+    if g.numel() != B:
+        raise ValueError("scale_rows: gains must be %d numbers, got %d" % (B, g.numel()))
+    g = g.to(y.device).contiguous()
+    _check(lib.t2v_scale_rows(_p(y), _p(n.to(y.device)), S, B, _p(g), _stream()), 't2v_scale_rows')
+    return y
 
 
 ALIGN_FRAMES = 16                       # T2V_ALIGN_FRAMES of include/t2vae.h: frames per workgroup of k_align_scan
