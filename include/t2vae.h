@@ -394,6 +394,9 @@ int t2v_decoder_infer_persistent_items(const t2v_dec_persist_weights* w, const t
 int t2v_conv1d_stat_blocks(int B, int T, int Cin, int Cout, int KS);
 /* the same for t2v_conv1d_fwd_bf16 (bf16_run keeps the tiles of its own kernels) */
 int t2v_conv1d_stat_blocks_bf16(int B, int T, int Cin, int Cout, int KS);
+/* launches of t2v_conv1d_fwd / t2v_conv1d_bwd (data gradient) so far in this process that took the LDS-DMA kernel of the fp32-MFMA
+ * route (k_conv5_fwd_dma); those with T2V_CONV_STAGING=0 or with weights that are not 16-byte aligned take k_conv5_fwd and do not count */
+long long t2v_conv1d_staged_launches(void);
 int t2v_conv1d_fwd(const float* W, const float* X, const float* bias, float* Y, float* stat_part,
                    int B, int Cin, int T, int Cout, int KS, void* stream);
 int t2v_conv1d_dw_scratch_floats(int B, int Cin, int T, int Cout, int KS);   /* 0 -> dw_scratch may be NULL */

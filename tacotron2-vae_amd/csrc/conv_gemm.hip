@@ -12,9 +12,11 @@
 // (BatchNorm training statistics, biased variance over B*T incl. padded frames — Appendix B-3)
 // so BN needs no extra pass over Y.
 #include <stdlib.h>
+#include <type_traits>
 #include "t2v_common.h"
 #include "t2v_kernels.h"
 #include "t2v_coop.h"
+#include "t2v_x3.h"
 
 
 #define CG_BM 64
@@ -191,6 +193,72 @@ struct ConvTiledArgs {
     unsigned* ks_ctr;    // ... and one arrival counter per output tile (zero before and after the launch)
 };
 
+// What follows the k loop of both forward kernels: the exchange of the channel-split form (a + b), bias, store, BatchNorm partials
+template <int NTW>
+__device__ __forceinline__ void conv5_fwd_finish(const ConvTiledArgs& a, f32x4 (&acc)[NTW], int bb, int t0, int m0) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int kq = lane >> 4, j = lane & 15;
+    if (gridDim.z > 1) {
+        // write-through partial, arrival counter, and the second arriver adds the first one's tile (a + b == b + a: the same
+        // bits whichever half comes second); no fence — see the split-K epilogue of gemm.hip
+        const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, ntile = (size_t)gridDim.x * gridDim.y;
+        float* mine = a.ks_part + ((blockIdx.z * ntile + tile) * 256 + tid) * (4 * NTW);
+#pragma unroll
+        for (int n = 0; n < NTW; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) st_sc1(mine + 4 * n + r, acc[n][r]);
+        __shared__ unsigned second_;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) second_ = __hip_atomic_fetch_add(a.ks_ctr + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (second_ == 0u) return;
+        if (tid == 0) __hip_atomic_store(a.ks_ctr + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float* other = a.ks_part + (((1 - blockIdx.z) * ntile + tile) * 256 + tid) * (4 * NTW);
+        float o[NTW][4];
+#pragma unroll
+        for (int n = 0; n < NTW; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[n][r] = ld_sc1(other + 4 * n + r);
+#pragma unroll
+        for (int n = 0; n < NTW; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[n][r] += o[n][r];
+    }
+    // epilogue: lane holds rows m0 + 16w + 4kq + r (r = 0..3) of column t0 + 16n + j
+    float psum[4] = {0.f, 0.f, 0.f, 0.f}, psq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int m = m0 + 16 * wave + 4 * kq + r;
+        if (m < a.M) {
+            const float bv = a.bias ? a.bias[m] : 0.f;
+            float* yrow = a.Y + ((size_t)bb * a.M + m) * a.T;
+#pragma unroll
+            for (int n = 0; n < NTW; ++n) {
+                const int t = t0 + 16 * n + j;
+                if (t < a.T) {
+                    const float v = acc[n][r] + bv;
+                    yrow[t] = v;
+                    psum[r] += v;
+                    psq[r] = fmaf(v, v, psq[r]);
+                }
+            }
+        }
+    }
+    if (a.stat_part) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float s1 = row16_sum(psum[r]), s2 = row16_sum(psq[r]);
+            const int m = m0 + 16 * wave + 4 * kq + r;
+            if (j == 0 && m < a.M) {
+                float* dst = a.stat_part + ((size_t)blockIdx.x * a.M + m) * 2;
+                dst[0] = s1;
+                dst[1] = s2;
+            }
+        }
+    }
+}
+
 template <int NTW>
 __global__ __launch_bounds__(256) void k_conv5_fwd(ConvTiledArgs a) {
     constexpr int BN = 16 * NTW;
@@ -301,65 +369,152 @@ __global__ __launch_bounds__(256) void k_conv5_fwd(ConvTiledArgs a) {
         __syncthreads();
     }
     if (stamp) { a.prof[1] = __builtin_readcyclecounter(); a.prof[3] = wall_clock64(); }
-    if (gridDim.z > 1) {
-        // write-through partial, arrival counter, and the second arriver adds the first one's tile (a + b == b + a: the same
-        // bits whichever half comes second); no fence — see the split-K epilogue of gemm.hip
-        const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, ntile = (size_t)gridDim.x * gridDim.y;
-        float* mine = a.ks_part + ((blockIdx.z * ntile + tile) * 256 + tid) * (4 * NTW);
+    conv5_fwd_finish<NTW>(a, acc, bb, t0, m0);
+}
+
+// The same tile, k order and epilogue with both operands staged by LDS-DMA (global_load_lds, no destination registers) into a ring
+// of three k-tile stages.  The one barrier per tile stands in the MIDDLE of a tile: the operand reads run on across the tile
+// boundary and the MFMA stream never drains there; the requests of tile kt + 2 go out right behind it, so the first of them has
+// 20 k-steps to come back and the last 10 (2 000 cycles at the rate the loop runs at), against 1 760 at most for k_conv5_fwd's
+// register prefetch, and nothing of it passes through registers or ds_write.  Three stages are 84 KB (BN >= 80), which leaves
+// room for a 65 KB workgroup of k_conv5_dw on the same CU (a ring of four did not: DESIGN 4.0c).
+//   A : no transposition and no image of the weights (nothing to keep fresh between calls).  A k-tile of W is 64 rows of 80
+//       consecutive floats (5 channel + tap, 320 aligned bytes), and it goes to LDS in that order, 16 bytes per lane, as rows of
+//       CD_AS = 84 floats: the stage is 64 x 21 sixteen-byte pieces = 21 lane-linear requests (the 21st piece of a row is padding
+//       and repeats the 20th).  The MFMA lane (kq, j) of wave w reads W[16w + j][5 (4 (s % 4) + kq) + s / 4] at
+//       84 (16w + j) + 5 kq + constant, and 84 j + 5 kq = 5 (4 j + kq) mod 64 runs through all 64 banks: conflict-free.
+//   X : [16 channels][XS] as before, requested as 64-float runs of the flat stage in the 4-byte form (rows start at t0 - 2 of
+//       an arbitrary row); the halo outside the utterance and the padding columns take their zero from g_conv5_zero.
+// Every wave issues the same G requests per tile (waves 1..3 repeat piece 20 of A for that) and requests come back in order, so
+// the waits are counted.  Bit-identical to k_conv5_fwd: an output's products are summed in the same k order by the same MFMA.
+// W must be 16-byte aligned (the launcher checks).
+#define CD_RING 3
+#define CD_AS 84                 // A row stride: 80 + one 16-byte piece
+__device__ float g_conv5_zero[4];
+
+template <int NTW>
+__global__ __launch_bounds__(256) void k_conv5_fwd_dma(ConvTiledArgs a) {
+    constexpr int BN = 16 * NTW;
+    constexpr int XW = BN + 4;
+    constexpr int XS = BN == 32 ? 48 : BN <= 64 ? 80 : 112;   // as k_conv5_fwd
+    constexpr int NXD = 16 * XS / 256;                   // X requests per wave and k-tile (3, 5 or 7)
+    constexpr int G = 6 + NXD;                           // requests per wave and k-tile
+    constexpr int AST = CT_BM * CD_AS, STG = AST + 16 * XS;   // floats per stage: 28 KB at BN >= 80, 26 KB at 48 / 64, 24 KB at 32
+    static_assert(16 * XS % 256 == 0 && AST % 256 == 0, "whole 64-lane requests");
+    __shared__ __attribute__((aligned(16))) float lds_[CD_RING * STG];
+    const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) void*)&lds_[0];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int kq = lane >> 4, j = lane & 15;
+    const int bb = blockIdx.x / a.tiles_per_item, t0 = (blockIdx.x % a.tiles_per_item) * BN;
+    const int m0 = blockIdx.y * CT_BM;
+    const int CK = a.Cin * 5;
+    const int nkt_all = a.Cin / 16;                      // (the channel-split form: as k_conv5_fwd)
+    const int kt0 = gridDim.z > 1 ? (int)blockIdx.z * (nkt_all / 2) : 0;
+    const int nkt = gridDim.z > 1 ? (blockIdx.z == 0 ? nkt_all / 2 : nkt_all - nkt_all / 2) : nkt_all;
+
+    const bool stamp = a.prof && tid == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
+    if (stamp) { a.prof[0] = __builtin_readcyclecounter(); a.prof[2] = wall_clock64(); }
+    // every request keeps the source address of the NEXT tile it will be issued for and moves on by one tile as it goes out, so a
+    // request costs one address addition.  Rows past M are clamped (their outputs are never stored)
+    const float* a_ptr[6];
 #pragma unroll
-        for (int n = 0; n < NTW; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) st_sc1(mine + 4 * n + r, acc[n][r]);
-        __shared__ unsigned second_;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) second_ = __hip_atomic_fetch_add(a.ks_ctr + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (second_ == 0u) return;
-        if (tid == 0) __hip_atomic_store(a.ks_ctr + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float* other = a.ks_part + (((1 - blockIdx.z) * ntile + tile) * 256 + tid) * (4 * NTW);
-        float o[NTW][4];
-#pragma unroll
-        for (int n = 0; n < NTW; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[n][r] = ld_sc1(other + 4 * n + r);
-#pragma unroll
-        for (int n = 0; n < NTW; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[n][r] += o[n][r];
+    for (int i = 0; i < 6; ++i) {
+        const int u = 64 * min(wave + 4 * i, 20) + lane;                 // piece of the stage: row u / 21, floats 4 (u % 21) ..
+        const int row = u / 21, pc = u - 21 * row;
+        a_ptr[i] = a.W + (size_t)min(m0 + row, a.M - 1) * CK + 80 * kt0 + 4 * min(pc, 19);
     }
-    // epilogue: lane holds rows m0 + 16w + 4kq + r (r = 0..3) of column t0 + 16n + j
-    float psum[4] = {0.f, 0.f, 0.f, 0.f}, psq[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* x_ptr[NXD];
+    size_t x_step[NXD];                                  // 16 channels on, or 0: this element is zero in every k-tile
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int m = m0 + 16 * wave + 4 * kq + r;
-        if (m < a.M) {
-            const float bv = a.bias ? a.bias[m] : 0.f;
-            float* yrow = a.Y + ((size_t)bb * a.M + m) * a.T;
+    for (int i = 0; i < NXD; ++i) {
+        const int e = 64 * (wave + 4 * i) + lane;
+        const int c = e / XS, jj = e - c * XS;
+        const int t = t0 - 2 + jj;
+        const bool ok = jj < XW && t >= 0 && t < a.T;
+        x_ptr[i] = ok ? a.X + ((size_t)bb * a.Cin + 16 * kt0 + c) * a.T + t : g_conv5_zero;
+        x_step[i] = ok ? (size_t)16 * a.T : 0;
+    }
+    auto request = [&](unsigned dst, int q) {            // q-th request of a tile into the stage at LDS byte address dst (q compile-time)
+        if (q < 5) {
+            t2v_dma16(a_ptr[q], dst + 1024u * (unsigned)wave + 4096u * q);
+            a_ptr[q] += 80;
+        } else if (q == 5) {
+            t2v_dma16(a_ptr[5], dst + 20480u);            // piece 20, by every wave
+            a_ptr[5] += 80;
+        } else if (q < G) {
+            t2v_dma4(x_ptr[q - 6], dst + 4u * AST + 256u * (unsigned)wave + 1024u * (q - 6));
+            x_ptr[q - 6] += x_step[q - 6];
+        }
+    };
+
+    f32x4 acc[NTW];
+#pragma unroll
+    for (int n = 0; n < NTW; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // prologue: tiles 0 and 1 (if there is one); tile 0 has landed once only tile 1's requests are outstanding
+#pragma unroll
+    for (int q = 0; q < G; ++q) request(lds0, q);
+    if (nkt > 1) {
+#pragma unroll
+        for (int q = 0; q < G; ++q) request(lds0 + 4u * STG, q);
+    }
+    if (nkt > 1) t2v_wait_vmcnt<G>(); else t2v_wait_vmcnt<0>();
+    __syncthreads();
+    // k' = 4s + kq: tap = s/4, channel = 4*(s%4) + kq.  One wave per SIMD issues one instruction every four cycles, so an MFMA (32
+    // cycles) hides seven other instructions behind it and no more: everything else is dealt out over the gaps between the MFMAs
+    // of a k-step by hand.
+    //   gap 0 : the LDS operands of k-step s+1 — across the tile boundary too, where there is no barrier;
+    //   gaps 1, 2 : one request each (an address addition, the LDS address, and the five instructions of t2v_dma*);
+    //   in front of step CD_SYNC : the one barrier per tile.  Before it every wave waits for its requests of tile kt + 1 (nothing
+    //   younger is outstanding); behind it tile kt + 1 may be read (first at step 19) and the stage that held tile kt - 1 is
+    //   free: the requests of tile kt + 2 go out from there, two per step until the rest fit one per step.
+    constexpr int CD_SYNC = 10;
+    constexpr int TWO = G > 20 - CD_SYNC ? G - (20 - CD_SYNC) : 0;       // steps that carry two requests
+    static_assert(G <= 2 * (20 - CD_SYNC) && (TWO == 0 || NTW >= 3), "a tile's requests fit the steps behind the barrier");
+    const int lane_a = CD_AS * (16 * wave + j) + 5 * kq, lane_x = AST + kq * XS + j;
+    float av[2], bv[2][NTW];
+    auto fetch = [&](const float* ap, const float* xp, int s) {          // the operands of k-step s of the tile at (ap, xp)
+        av[s & 1] = ap[20 * (s & 3) + (s >> 2)];
+#pragma unroll
+        for (int n = 0; n < NTW; ++n) bv[s & 1][n] = xp[4 * (s & 3) * XS + 16 * n + (s >> 2)];
+    };
+    // one k-tile at (ap, xp); (ap1, xp1): the next one's stage, dst2: the stage of tile kt + 2, requested if MORE
+    auto tile = [&](auto more_c, const float* ap, const float* xp, const float* ap1, const float* xp1, unsigned dst2) {
+        constexpr bool MORE = decltype(more_c)::value;
+#pragma unroll
+        for (int s = 0; s < 20; ++s) {
+            if (s == CD_SYNC) {
+                t2v_wait_vmcnt<0>();
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const int sr = s - CD_SYNC;
+            const int q0 = !MORE || sr < 0 ? -1 : sr < TWO ? 2 * sr : sr + TWO;
+            const int q1 = MORE && sr >= 0 && sr < TWO ? 2 * sr + 1 : -1;
 #pragma unroll
             for (int n = 0; n < NTW; ++n) {
-                const int t = t0 + 16 * n + j;
-                if (t < a.T) {
-                    const float v = acc[n][r] + bv;
-                    yrow[t] = v;
-                    psum[r] += v;
-                    psq[r] = fmaf(v, v, psq[r]);
-                }
+                acc[n] = mfma16x4(av[s & 1], bv[s & 1][n], acc[n]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (n == 0) { if (s + 1 < 20) fetch(ap, xp, s + 1); else fetch(ap1, xp1, 0); }
+                if (n == 1 && q0 >= 0 && q0 < G) request(dst2, q0);
+                if (n == 2 && q1 >= 0) request(dst2, q1);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
+    };
+    fetch(&lds_[lane_a], &lds_[lane_x], 0);
+    int stg = 0;                                         // kt % CD_RING
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int stg1 = stg == CD_RING - 1 ? 0 : stg + 1, stg2 = stg == 0 ? CD_RING - 1 : stg - 1;   // stages of tiles kt + 1, kt + 2
+        const float* ap = &lds_[stg * STG + lane_a];
+        const float* xp = &lds_[stg * STG + lane_x];
+        const float* ap1 = &lds_[stg1 * STG + lane_a];    // (behind the last tile: read, never used)
+        const float* xp1 = &lds_[stg1 * STG + lane_x];
+        if (kt + 2 < nkt) tile(std::true_type{}, ap, xp, ap1, xp1, lds0 + 4u * (unsigned)(stg2 * STG));
+        else tile(std::false_type{}, ap, xp, ap1, xp1, 0u);
+        stg = stg1;
     }
-    if (a.stat_part) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float s1 = row16_sum(psum[r]), s2 = row16_sum(psq[r]);
-            const int m = m0 + 16 * wave + 4 * kq + r;
-            if (j == 0 && m < a.M) {
-                float* dst = a.stat_part + ((size_t)blockIdx.x * a.M + m) * 2;
-                dst[0] = s1;
-                dst[1] = s2;
-            }
-        }
-    }
+    if (stamp) { a.prof[1] = __builtin_readcyclecounter(); a.prof[3] = wall_clock64(); }
+    conv5_fwd_finish<NTW>(a, acc, bb, t0, m0);
 }
 
 // weight gradient: dW[m][c][kx] = sum_{b,t} dY[b][m][t] X[b][c][t+kx-2].  Workgroup = 64 rows m x 16 channels
@@ -979,6 +1134,9 @@ int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y
                      hipStream_t stream, int np);
 bool t2v_conv5_planes_bf16_ok(int B, int Cin, int T, int Cout, int KS);
 
+static std::atomic<long long> g_conv5_staged_launches{0};
+extern "C" long long t2v_conv1d_staged_launches(void) { return g_conv5_staged_launches.load(std::memory_order_relaxed); }
+
 static void launch_conv5_fwd(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B,
                              int Cin, int T, int M, hipStream_t stream) {
     int ks = 1;
@@ -997,6 +1155,18 @@ static void launch_conv5_fwd(const float* W, const float* X, const float* bias, 
         a.ks_part = conv_ks_scratch(pf);
         a.ks_ctr = a.ks_part ? t2v_arrival_counters((int)ntile) : nullptr;
         if (a.ks_part && a.ks_ctr) grid.z = 2; else a.ks_part = nullptr;
+    }
+    // T2V_CONV_STAGING=0: the register-staged kernel (the reference of tests/test_conv5_staging_gpu.py and of the A/B runs).
+    // Weights that are not 16-byte aligned take it too; g_conv5_staged_launches lets a caller see which kernel its launches took
+    static const int staging = getenv("T2V_CONV_STAGING") ? atoi(getenv("T2V_CONV_STAGING")) : 1;
+    if (staging && ((size_t)W & 15) == 0) {
+        g_conv5_staged_launches.fetch_add(1, std::memory_order_relaxed);
+        if (BN == 32) k_conv5_fwd_dma<2><<<grid, 256, 0, stream>>>(a);
+        else if (BN == 48) k_conv5_fwd_dma<3><<<grid, 256, 0, stream>>>(a);
+        else if (BN == 64) k_conv5_fwd_dma<4><<<grid, 256, 0, stream>>>(a);
+        else if (BN == 80) k_conv5_fwd_dma<5><<<grid, 256, 0, stream>>>(a);
+        else k_conv5_fwd_dma<6><<<grid, 256, 0, stream>>>(a);
+        return;
     }
     if (BN == 32) k_conv5_fwd<2><<<grid, 256, 0, stream>>>(a);
     else if (BN == 48) k_conv5_fwd<3><<<grid, 256, 0, stream>>>(a);

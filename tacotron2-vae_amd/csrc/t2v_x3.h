@@ -30,6 +30,14 @@ __device__ __forceinline__ void t2v_dma16(const void* gsrc, unsigned lds_addr) {
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_addr) : "memory");
 }
 
+// 4 bytes per lane: lane i lands at lds_addr + 4 i, and every lane brings its own source address (a gather; rows that are not
+// 16-byte aligned).  Same reasons for the inline-asm form as t2v_dma16.
+__device__ __forceinline__ void t2v_dma4(const void* gsrc, unsigned lds_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_addr) : "memory");
+}
+
 // wait until at most N of this wave's memory requests are outstanding (N a compile-time constant)
 template <int N>
 __device__ __forceinline__ void t2v_wait_vmcnt() {
@@ -38,8 +46,11 @@ __device__ __forceinline__ void t2v_wait_vmcnt() {
     else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
     else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
     else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+    else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
     else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    else if constexpr (N == 13) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
     else if constexpr (N == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
     else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else static_assert(N == 0, "add the literal");
