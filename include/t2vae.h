@@ -374,6 +374,32 @@ int t2v_decoder_infer_persistent_items(const t2v_dec_persist_weights* w, const t
                                        int t_end, float gate_threshold, float p_prenet, uint64_t seed,
                                        const t2v_dec_items* items, void* stream);
 
+/* Attention window of the free-running decode (an attention constraint; Decoder.attention_window = (back, ahead), two
+ * integers >= 0).  For item b at frame t:
+ *   - p is the index of the largest weight of the item's alignment of frame t-1.  Ties go to the lowest index.  Frame 0 sees
+ *     the all-zero initial weights, so p = 0.
+ *   - The energies of all positions outside p - back <= j <= p + ahead are treated as -inf.  So are all positions
+ *     j >= len_b (lengths[b]; T_in without lengths).
+ *   - Softmax, context, cumulative weights and everything downstream are unchanged.
+ * Weights outside the window are exactly 0.0.  The window always contains p, so it is never empty.  The cumulative weights
+ * keep accumulating the windowed weights, so the location features see what the constrained decoder did.
+ * Free-running decode only: the teacher-forced pass and training have no window.
+ * The two entries below take the arguments of the `_items` entries plus the window (a host struct, read during the call;
+ * back, ahead >= 0, values above T_in mean T_in).  `items` may be NULL here: one seed and the global stop rule, as the entries
+ * without `_items`.  A call of t2v_decoder_infer_steps_window with t_begin > 0 continues a decode begun with the same window.
+ * t2v_decoder_infer_persistent_window runs where t2v_decoder_persist_supported(B, T_in) != 0, as the other two. */
+typedef struct t2v_dec_window {
+    int32_t back;    /* positions kept behind p */
+    int32_t ahead;   /* positions kept in front of p */
+} t2v_dec_window;
+int t2v_decoder_infer_steps_window(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
+                                   int t_begin, int t_end, float gate_threshold, float p_prenet,
+                                   int external_prenet, uint64_t seed, const t2v_dec_items* items,
+                                   const t2v_dec_window* window, void* stream);
+int t2v_decoder_infer_persistent_window(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
+                                        int t_end, float gate_threshold, float p_prenet, uint64_t seed,
+                                        const t2v_dec_items* items, const t2v_dec_window* window, void* stream);
+
 /* ------------------------------------------------------------------ Conv1d + BatchNorm1d + activation
  * The encoder conv bank (model.py:159-177) and the Postnet (model.py:110-148): stride-1 "same" Conv1d as
  * an implicit GEMM on fp32 MFMA, BatchNorm1d (train: biased batch statistics over B*T incl. padded frames;

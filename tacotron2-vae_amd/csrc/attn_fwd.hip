@@ -15,12 +15,29 @@
 // Any T_in: NJT = 6 / 8 / 16 position tiles cover T_in <= 256 with every operand register-resident; longer
 // inputs (koemo reaches 555 symbols) take the BIG variant, which walks 256-position chunks.
 // Saved for the backward (training): tanh outputs S, alpha, cumulative alpha.
+// WIN (free-running decode only, include/t2vae.h t2v_dec_window): the energies outside [p - back, p + ahead], p = the position
+// of the largest previous weight (lowest index on a tie), count as -inf.  A template parameter with its own argument struct:
+// the instantiations the training engine uses are what they were.
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include <type_traits>
 
 #define AF_THREADS 256
 #define AF_NS 8
 #define AF_SPIN_LIMIT 4000000
+
+struct AttnFwdWinArgs : AttnFwdArgs {
+    int back, ahead;      // clamped to T_in by the launcher
+};
+// (value, index) of the larger value, the lower index on a tie, over the 64 lanes of a wave; every lane ends with the result
+__device__ __forceinline__ void af_argmax_wave(float& v, int& j) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(v, m, 64);
+        const int oj = __shfl_xor(j, m, 64);
+        if (ov > v || (ov == v && oj < j)) { v = ov; j = oj; }
+    }
+}
 
 __device__ __forceinline__ void af_put(t2v_u64* p, float v, unsigned tag) {
     __hip_atomic_store(p, ((t2v_u64)tag << 32) | (t2v_u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -51,8 +68,8 @@ extern "C" int t2v_fuse_location_weights(const float* loc_conv, const float* loc
     return t2v_check_launch();
 }
 
-template <int NJT, bool BIG>      // NJT 16-position tiles per chunk; !BIG: one chunk covers T_in
-__global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(AttnFwdArgs a) {
+template <int NJT, bool BIG, bool WIN = false>      // NJT 16-position tiles per chunk; !BIG: one chunk covers T_in
+__global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(std::conditional_t<WIN, AttnFwdWinArgs, AttnFwdArgs> a) {
     constexpr int TPAD = 16 * NJT;
     constexpr int NI = (NJT + 3) / 4;           // tiles per wave
     extern __shared__ __attribute__((aligned(16))) float eall[];     // Tcap energies -> attention weights
@@ -126,6 +143,31 @@ __global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(AttnFwdArgs a) {
     }
     __syncthreads();                      // alignment window visible
     T2V_STAMP(a, 7);
+    // attention window: like the location features a function of the previous weights alone.  Every wave scans all positions
+    // for itself (no barrier); the 8 slices of an item read the same previous row, so they take the same window.  The chunked
+    // form holds one 256-position chunk of the row in LDS and makes its own pass over al_prev[b, :T_in].
+    int wlo = 0, whi = 0;
+    if constexpr (WIN) {
+        float bv = -1.f;
+        int bj = 0;
+        if constexpr (BIG) {
+            for (int j = lane; j < Tp; j += 64) {
+                const float v = a.al_prev[(size_t)b * Tp + j];
+                if (v > bv) { bv = v; bj = j; }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < (TPAD + 63) / 64; ++i) {
+                const int j = lane + 64 * i;
+                const float v = j < Tp ? ap[0][15 + min(j, TPAD - 1)] : -1.f;
+                if (v > bv) { bv = v; bj = j; }
+            }
+        }
+        af_argmax_wave(bv, bj);
+        const int p = __builtin_amdgcn_readfirstlane(bj);
+        wlo = p - a.back;
+        whi = p + a.ahead;
+    }
     // location features of this wave's tiles (independent of the query)
     f32x4 lacc[NI];
     if constexpr (!BIG) {
@@ -258,7 +300,8 @@ __global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(AttnFwdArgs a) {
             }
         }
         const float ev = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-        ev0 = j < len ? ev : -INFINITY;
+        if constexpr (WIN) ev0 = (j < len && j >= wlo && j <= whi) ? ev : -INFINITY;
+        else ev0 = j < len ? ev : -INFINITY;
         if (BIG) eall[j] = ev0;
         mloc = fmaxf(mloc, ev0);
     }
@@ -367,4 +410,18 @@ void t2v_launch_attn_fwd(const AttnFwdArgs& f, int B, int T_in, hipStream_t stre
     else if (T_in <= 128) k_attn_fwd<8, false><<<grid, AF_THREADS, lds, stream>>>(f);
     else if (T_in <= 256) k_attn_fwd<16, false><<<grid, AF_THREADS, lds, stream>>>(f);
     else k_attn_fwd<16, true><<<grid, AF_THREADS, lds, stream>>>(f);
+}
+
+// the same step with the attention window (back, ahead >= 0) of the free-running decode
+void t2v_launch_attn_fwd_window(const AttnFwdArgs& f, int B, int T_in, int back, int ahead, hipStream_t stream) {
+    const dim3 grid(B, AF_NS);
+    const size_t lds = sizeof(float) * t2v_tcap(T_in);
+    AttnFwdWinArgs w;
+    static_cast<AttnFwdArgs&>(w) = f;
+    w.back = back < T_in ? back : T_in;      // (a window wider than the text covers it whatever p is; p +- it cannot overflow)
+    w.ahead = ahead < T_in ? ahead : T_in;
+    if (T_in <= 96) k_attn_fwd<6, false, true><<<grid, AF_THREADS, lds, stream>>>(w);
+    else if (T_in <= 128) k_attn_fwd<8, false, true><<<grid, AF_THREADS, lds, stream>>>(w);
+    else if (T_in <= 256) k_attn_fwd<16, false, true><<<grid, AF_THREADS, lds, stream>>>(w);
+    else k_attn_fwd<16, true, true><<<grid, AF_THREADS, lds, stream>>>(w);
 }

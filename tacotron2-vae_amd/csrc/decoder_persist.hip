@@ -219,12 +219,36 @@ struct PersistItems {
     const uint64_t* item_seeds;     // (B)
 };
 
+// Attention window (include/t2vae.h t2v_dec_window), clamped by the launcher so that p - back and p + ahead cannot overflow
+struct PersistWindow {
+    int back, ahead;
+};
+// (value, index) of the larger value, the lower index on a tie, over the 64 lanes of a wave; every lane ends with the result
+__device__ __forceinline__ void pd_argmax_wave(float& v, int& j) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(v, m, 64);
+        const int oj = __shfl_xor(j, m, 64);
+        if (ov > v || (ov == v && oj < j)) { v = ov; j = oj; }
+    }
+}
+
+#define PD_WINDOW 0
 #define PD_ITEMS 0
 #include "decoder_persist_kernel.inc"
 #undef PD_ITEMS
 #define PD_ITEMS 1
 #include "decoder_persist_kernel.inc"
 #undef PD_ITEMS
+#undef PD_WINDOW
+#define PD_WINDOW 1
+#define PD_ITEMS 0
+#include "decoder_persist_kernel.inc"
+#undef PD_ITEMS
+#define PD_ITEMS 1
+#include "decoder_persist_kernel.inc"
+#undef PD_ITEMS
+#undef PD_WINDOW
 
 static size_t pd_lds_bytes(int B, int T_in) {
     const size_t Tcap = (size_t)((T_in + 15) / 16) * 16;
@@ -247,21 +271,25 @@ static int pd_supported(const void* kernel, int B, int T_in) {
     if (!(B >= 1 && B <= PD_MAXB && T_in >= 1 && T_in <= PD_MAXT && pd_lds_bytes(B, T_in) <= T2V_LDS_MAX)) return 0;
     static bool raised = false;
     return t2v_persist_resident(kernel, PD_THREADS, pd_lds_bytes(B, T_in),
-                                {(const void*)k_decode_persist, (const void*)k_decode_persist_items}, raised);
+                                {(const void*)k_decode_persist, (const void*)k_decode_persist_items,
+                                 (const void*)k_decode_persist_win, (const void*)k_decode_persist_items_win}, raised);
 }
 extern "C" int t2v_decoder_persist_supported(int B, int T_in) {
     return pd_supported((const void*)k_decode_persist, B, T_in);
 }
 
 static int pd_launch(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in, int t_end,
-                     float gate_threshold, float p_prenet, uint64_t seed, const t2v_dec_items* items, hipStream_t stream) {
-    if (!w || !s || !pd_supported(items ? (const void*)k_decode_persist_items : (const void*)k_decode_persist, B, T_in) || t_end < 1)
-        return T2V_ERR_ARG;
+                     float gate_threshold, float p_prenet, uint64_t seed, const t2v_dec_items* items, const t2v_dec_window* window,
+                     hipStream_t stream) {
+    const void* kernel = window ? (items ? (const void*)k_decode_persist_items_win : (const void*)k_decode_persist_win)
+                                : (items ? (const void*)k_decode_persist_items : (const void*)k_decode_persist);
+    if (!w || !s || !pd_supported(kernel, B, T_in) || t_end < 1) return T2V_ERR_ARG;
     if (!w->w_ih_att || !w->w_hh_att || !w->w_ih_dec || !w->w_hh_dec || !w->bias_att || !w->bias_dec || !w->wq || !w->wcomb ||
         !w->v || !w->proj_w || !w->proj_b || !w->prenet_w1 || !s->memory || !s->pm || !s->pre_first || !s->MEL || !s->GATE ||
         !s->AL || !s->stop_flag || !s->exchange || !s->err_word)
         return T2V_ERR_ARG;
     if (items && (!items->stop_item || !items->item_seeds)) return T2V_ERR_ARG;
+    if (window && (window->back < 0 || window->ahead < 0)) return T2V_ERR_ARG;
     if (((uintptr_t)s->exchange & 15) || (size_t)t_end * pd_row(B) * 4 >= 0x7fffffffull) return T2V_ERR_ARG;      // 31-bit buffer offsets
     const size_t lds = pd_lds_bytes(B, T_in);     // (pd_supported raised the dynamic-LDS limit)
     t2v_fill_sentinel(s->exchange, (size_t)t_end * pd_row(B) / 4, 1024, stream);
@@ -277,14 +305,18 @@ static int pd_launch(const t2v_dec_persist_weights* w, const t2v_dec_persist_buf
     a.gate_logit_thr = gate_threshold <= 0.f ? -INFINITY : (gate_threshold >= 1.f ? INFINITY : logf(gate_threshold / (1.f - gate_threshold)));
     a.p_prenet = p_prenet; a.seed = seed;
     a.prof = g_t2v_prof;
-    if (items) k_decode_persist_items<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds});
+    // (a window wider than the text covers it whatever p is: clamped, so that the kernel's p - back / p + ahead stay small)
+    const PersistWindow wn = {window ? (window->back < T_in ? window->back : T_in) : 0, window ? (window->ahead < T_in ? window->ahead : T_in) : 0};
+    if (window && items) k_decode_persist_items_win<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds}, wn);
+    else if (window) k_decode_persist_win<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, wn);
+    else if (items) k_decode_persist_items<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds});
     else k_decode_persist<<<T2V_NWG, PD_THREADS, lds, stream>>>(a);
     return t2v_check_launch();
 }
 
 extern "C" int t2v_decoder_infer_persistent(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
                                             int t_end, float gate_threshold, float p_prenet, uint64_t seed, void* stream_) {
-    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, nullptr, (hipStream_t)stream_);
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 // the same with per-item stop frames and dropout seeds (batched synthesis); seed is unused when items->item_seeds is set
@@ -292,5 +324,13 @@ extern "C" int t2v_decoder_infer_persistent_items(const t2v_dec_persist_weights*
                                                   int t_end, float gate_threshold, float p_prenet, uint64_t seed,
                                                   const t2v_dec_items* items, void* stream_) {
     if (!items) return T2V_ERR_ARG;
-    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, (hipStream_t)stream_);
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, nullptr, (hipStream_t)stream_);
+}
+
+// the same with the attention window of t2v_dec_window; items may be NULL (one seed, the global stop rule alone)
+extern "C" int t2v_decoder_infer_persistent_window(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
+                                                   int t_end, float gate_threshold, float p_prenet, uint64_t seed,
+                                                   const t2v_dec_items* items, const t2v_dec_window* window, void* stream_) {
+    if (!window) return T2V_ERR_ARG;
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, window, (hipStream_t)stream_);
 }

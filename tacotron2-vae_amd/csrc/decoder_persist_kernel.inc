@@ -1,8 +1,14 @@
-// The frame loop of decoder_persist.hip, included twice: PD_ITEMS 0 defines k_decode_persist, PD_ITEMS 1 the per-item variant
+// The frame loop of decoder_persist.hip, included once per kernel: PD_ITEMS 0 defines k_decode_persist, PD_ITEMS 1 the per-item variant
 // k_decode_persist_items (batched synthesis: item b's first gate-fire frame -> it.stop_item[b]; item b's Prenet masks from
-// it.item_seeds[b] with the element index of item 0, i.e. the masks of a B = 1 decode with that seed).  Two preprocessor
+// it.item_seeds[b] with the element index of item 0, i.e. the masks of a B = 1 decode with that seed).  Preprocessor
 // instances rather than a template: the PD_ITEMS 0 text is the kernel as it was, so its instructions stay the same.
-#if PD_ITEMS
+// PD_WINDOW 1 (with either PD_ITEMS) adds the attention window of include/t2vae.h (t2v_dec_window): k_decode_persist_win and
+// k_decode_persist_items_win.  With PD_WINDOW 0 the text is what it was before the window existed.
+#if PD_ITEMS && PD_WINDOW
+__global__ __launch_bounds__(PD_THREADS) void k_decode_persist_items_win(PersistArgs a, PersistItems it, PersistWindow wn) {
+#elif PD_WINDOW
+__global__ __launch_bounds__(PD_THREADS) void k_decode_persist_win(PersistArgs a, PersistWindow wn) {
+#elif PD_ITEMS
 __global__ __launch_bounds__(PD_THREADS) void k_decode_persist_items(PersistArgs a, PersistItems it) {
 #else
 __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
@@ -66,6 +72,9 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
     for (int i = tid; i < B * PD_XW; i += PD_THREADS) X[i] = 0.f;
     if (tid < 2 * PD_MAXB * 4) cst[tid] = 0.f;
     if (tid == 0) flag[0] = 1;
+#if PD_WINDOW
+    if (tid == 0) flag[1] = 0;          // the window centre of frame 0
+#endif
     // role operands
     // (round 4: the fused location filter's MFMA operand lives in LDS — 16 registers per lane that only the attention
     // workgroups used, next to 136 weight registers and the carried partial gate sums, made the kernel spill)
@@ -273,6 +282,9 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
                 const unsigned e0 = xcur + pd_ex(B) + (unsigned)(ab * 8 * 256 + tid);
                 float p[8];
                 unsigned spins = 0;
+#if PD_WINDOW
+                const int wlo = flag[1] - wn.back, whi = flag[1] + wn.ahead;      // (read ahead of the wait, not behind it)
+#endif
                 for (int i = 0; i < nap_x; i += 4) __builtin_amdgcn_s_sleep(4);
                 for (;;) {
                     bool ok = true;
@@ -288,7 +300,11 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
                 }
                 nap_x = pd_adapt(nap_x, (int)spins);
                 const float ev = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+#if PD_WINDOW
+                ev0 = (tid < len && tid >= wlo && tid <= whi) ? ev : -INFINITY;
+#else
                 ev0 = tid < len ? ev : -INFINITY;
+#endif
             }
             {
                 float mloc = ev0;
@@ -467,6 +483,28 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
             // decoder_rnn(t+1), part 1 (the h_dec(t) columns) of the ATTENTION workgroups: in the tail of this frame — at the top
             // of the next one they go straight from "h_att published" to their gather of it and the attention (the chain).  The
             // projection workgroups are gathering the same row right now and ARE the chain: let them go first.
+#if PD_WINDOW
+            // attention window of the NEXT frame: p = position of the largest weight of this frame (lowest index on a tie; frame 0
+            // starts from p = 0, as the all-zero initial weights give), energies outside [p - back, p + ahead] count as -inf.  It
+            // depends on this frame's weights alone, so it is found here, where the attention workgroups idle: wave 0 scans
+            // win[15 ..] and leaves p in flag[1], which the softmax threads of frame t + 1 read behind the barrier below.  (In front
+            // of the h_att(t + 1) gather, next to the location features, the same scan cost 1.1 us per frame: DESIGN 7n.)  Every
+            // slice of an item derives p from its own copy of the weights: the copies are bit-identical (the same 8 partial
+            // energies summed in the same order, the same maximum and sum), so the 8 slices take the same window without
+            // exchanging anything.
+            if (wave == 0) {
+                float bv = -1.f;
+                int bj = 0;
+#pragma unroll
+                for (int i = 0; i < (PD_MAXT + 63) / 64; ++i) {
+                    const int j = lane + 64 * i;
+                    const float v = j < Tp ? win[15 + j] : -1.f;
+                    if (v > bv) { bv = v; bj = j; }
+                }
+                pd_argmax_wave(bv, bj);
+                if (lane == 0) flag[1] = bj;
+            }
+#endif
             __builtin_amdgcn_s_sleep(48);
             (void)pd_gather_items(X + PD_X_HD, rx, xcur + pd_hdec(B), 1024u, 1024, B, 0, a.err, flag);
             __syncthreads();

@@ -57,6 +57,7 @@ static inline int t2v_attn_bwd_js(int T_in) { return T_in <= 128 ? 16 : 32; }
 static inline int t2v_attn_bwd_slices_(int T_in) { const int js = t2v_attn_bwd_js(T_in); return (T_in + js - 1) / js; }
 void t2v_launch_lstm_fwd(int mode, const LstmFwdArgs& a, hipStream_t stream);
 void t2v_launch_attn_fwd(const AttnFwdArgs& f, int B, int T_in, hipStream_t stream);
+void t2v_launch_attn_fwd_window(const AttnFwdArgs& f, int B, int T_in, int back, int ahead, hipStream_t stream);   // free-running decode: t2v_dec_window
 // The two persistent forward launchers (fp32 / bf16), after their shape and offset checks: the checks of the remaining
 // arguments, then the per-pass resets — the sync / error words, the zero initial states of the arena (as
 // t2v_decoder_train_fwd).  Returns the sync words, or NULL (nothing issued) on a bad argument.

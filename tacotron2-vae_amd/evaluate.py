@@ -3,7 +3,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--energy] [--hparams ...]
+                       [--style [--style_k K]] [--aligned] [--energy] [--attention_window BACK,AHEAD] [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
@@ -64,7 +64,11 @@ over the frames within 40 dB of the row's loudest: an uncalibrated choice); null
 under 400 ms, or below the gates).  With --aligned the row also gains energy_rmse_db and energy_corr of the two dB tracks
 along the warping path, over the points where both sides sound.  The summary gains "energy": overall and per emotion n_energy,
 loudness_shift_lu_mean / _abs_mean, energy_spread_ratio_mean (and the two path means), and per emotion loudness_vs_neu_lu and
-loudness_ref_vs_neu_lu, the emotion's mean loudness minus neutral's, synthesised and recorded."""
+loudness_ref_vs_neu_lu, the emotion's mean loudness minus neutral's, synthesised and recorded.
+
+--attention_window BACK,AHEAD decodes every row under the attention constraint of `Decoder.attention_window` (each frame
+attends within BACK positions behind and AHEAD in front of the position the previous frame attended most).
+OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart."""
 import argparse
 import json
 
@@ -102,6 +106,10 @@ def build_arg_parser():
                    help="also measure the BS.1770 loudness and the frame level of each synthesised waveform (Griffin-Lim) and of "
                         "its recording: rows gain loudness_lufs, loudness_ref_lufs, loudness_shift_lu and the energy spreads, "
                         "with --aligned energy_rmse_db and energy_corr; the summary an energy block")
+    from evaluation import parse_attention_window
+    p.add_argument('--attention_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
+                   help="attention constraint of the free-running decode: every frame attends within BACK positions behind and "
+                        "AHEAD in front of the position the previous frame attended most; written into the report")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
@@ -144,7 +152,7 @@ def main(argv=None):
     if args.hparams:
         hp.parse(args.hparams)
     from wavio import wav_options
-    syn = Synthesizer(hp, **wav_options(args))
+    syn = Synthesizer(hp, attention_window=args.attention_window, **wav_options(args))
     if args.condition == 'emotion':
         syn.load(args.load_path, vocoder=args.vocoder if args.prosody or args.energy else None, filelist_path=args.filelist_path)
     else:
@@ -157,7 +165,8 @@ def main(argv=None):
                            aligned=args.aligned, energy=args.energy, **style)
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
-        json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)]}, f, indent=1)
+        json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)],
+                   'attention_window': None if syn.attention_window is None else list(syn.attention_window)}, f, indent=1)
     print(json.dumps(summary, indent=1))
     if args.alignment:
         for name, st in summary['by_emotion'].items():

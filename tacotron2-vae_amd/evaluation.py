@@ -379,3 +379,14 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
     if any('loudness_shift_lu' in r for r in records):
         out['energy'] = _energy_block(records, emotions)
     return out
+
+
+def parse_attention_window(text):
+    """'BACK,AHEAD' of the command lines -> (back, ahead), two integers >= 0 (`Decoder.attention_window`); ValueError otherwise"""
+    parts = str(text).split(',')
+    if len(parts) != 2:
+        raise ValueError("--attention_window takes BACK,AHEAD, got %r" % (text,))
+    back, ahead = (int(x) for x in parts)
+    if back < 0 or ahead < 0:
+        raise ValueError("--attention_window takes two integers >= 0, got %r" % (text,))
+    return back, ahead

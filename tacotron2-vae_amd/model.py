@@ -199,6 +199,7 @@ class Decoder(nn.Module):
                                      w_init_gain='sigmoid')
         self.dropout_seed = hparams.seed
         self._calls = 0
+        self._attention_window = None
 
     # -- helpers kept for the reference's call sequence (synthesizer.py:135-156)
     def get_go_frame(self, memory):
@@ -226,6 +227,19 @@ class Decoder(nn.Module):
                 a.location_layer.location_dense.weight, a.v.weight)
 
     # -- free-running decode ------------------------------------------------------------------
+    @property
+    def attention_window(self):
+        """None (default: no constraint) or (back, ahead), two integers >= 0: at every free-running frame the attention
+        energies outside [p - back, p + ahead] count as -inf, p being the position the previous frame attended most (lowest
+        index on a tie; 0 at the first frame).  Weights outside the window are exactly 0 and the cumulative weights add up the
+        windowed weights.  inference, inference_batch and the stepwise initialize_decoder_states / decode() honour it; the
+        teacher-forced forward and training do not have it."""
+        return self.__dict__.get('_attention_window')
+
+    @attention_window.setter
+    def attention_window(self, window):
+        self._attention_window = t2v_hip.check_attention_window(window)
+
     def _session(self, memory, mask, max_steps, item_seeds=None):
         att, dec, al = self.attention_rnn, self.decoder_rnn, self.attention_layer
         lengths = None if mask is None else (~mask).sum(1).to(device=memory.device, dtype=torch.int32)
@@ -235,7 +249,8 @@ class Decoder(nn.Module):
             dec.weight_hh, dec.bias_ih + dec.bias_hh, al.query_layer.weight,
             al.location_layer.location_conv.conv.weight, al.location_layer.location_dense.weight, al.v.weight,
             self.prenet.layers[0].weight, self.prenet.layers[1].weight, self.linear_projection.weight,
-            self.linear_projection.bias, self.gate_layer.weight, self.gate_layer.bias, max_steps, item_seeds)
+            self.linear_projection.bias, self.gate_layer.weight, self.gate_layer.bias, max_steps, item_seeds,
+            self.attention_window)
 
     def initialize_decoder_states(self, memory, mask):
         """reference model.py:260-291 — zero states; stores memory / processed memory / mask."""

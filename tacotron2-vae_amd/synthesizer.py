@@ -117,8 +117,11 @@ class GriffinLimVocoder(object):
 
 
 class Synthesizer(object):
-    def __init__(self, hparams=None, resample=False, trim_db=None):
-        """resample: wavs at any sampling rate are resampled to hparams.sampling_rate on the device (`t2v_hip.resample`)
+    def __init__(self, hparams=None, resample=False, trim_db=None, attention_window=None):
+        """attention_window: None, or (back, ahead) for the decoder of every model this object loads (`Decoder.attention_window`:
+        each free-running frame attends within [p - back, p + ahead] of the position p the previous frame attended most), so
+        synthesize, synthesize_batch, alignment and evaluate all decode under it;
+        resample: wavs at any sampling rate are resampled to hparams.sampling_rate on the device (`t2v_hip.resample`)
         instead of being refused; trim_db: leading and trailing silence is cut from every wav that is read
         (`t2v_hip.trim_bounds` at that many dB below the wav's loudest frame, 2 frames of margin, then `t2v_hip.crop`).
         Both are off by default, and both act in `load_wavs`, through which every method here reads its wavs."""
@@ -135,6 +138,8 @@ class Synthesizer(object):
             if hp.hop_length != 256:
                 raise ValueError("trim_db: the trim is built for hop 256, the front end has hop %d" % hp.hop_length)
         self.resample, self.trim_db = bool(resample), trim_db
+        from t2v_hip import check_attention_window
+        self.attention_window = check_attention_window(attention_window)
         self.stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels,
                                  hp.sampling_rate, hp.mel_fmin, hp.mel_fmax)
         self.model = None
@@ -313,6 +318,7 @@ class Synthesizer(object):
         self.model = load_model(self.hparams)
         self.model.load_state_dict(torch.load(checkpoint_path, map_location='cpu')['state_dict'])
         self.model.eval()
+        self.model.decoder.attention_window = self.attention_window
         return self
 
     def load(self, checkpoint_path, waveglow_path=None, vocoder=None,
@@ -754,6 +760,10 @@ def build_arg_parser():
     p.add_argument('--ref_audio', default=None, help="condition every text on this reference wav instead of --ratios")
     p.add_argument('--filelist_path', default='./web/static/uploads/koemo_spk_emo_all_test.txt',
                    help="reference utterances of the emotion centroids (or their cache next to the checkpoint)")
+    from evaluation import parse_attention_window
+    p.add_argument('--attention_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
+                   help="attention constraint: every frame attends within BACK positions behind and AHEAD in front of the "
+                        "position the previous frame attended most (default: none)")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
@@ -786,7 +796,7 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    syn = Synthesizer(hp, **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
+    syn = Synthesizer(hp, attention_window=args.attention_window, **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
     os.makedirs(args.sample_path, exist_ok=True)
     texts = args.texts
     for i0 in range(0, len(texts), args.batch_size):

@@ -7,6 +7,7 @@ is missing, so a silent eager path can never stand in for the HIP kernels.
 import collections
 import ctypes as C
 import math
+import operator
 import os
 
 import torch
@@ -79,6 +80,11 @@ class _DecItems(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('stop_item', 'item_seeds')]
 
 
+class _DecWindow(C.Structure):
+    C_NAME = 't2v_dec_window'
+    _fields_ = [('back', C.c_int32), ('ahead', C.c_int32)]
+
+
 EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_pack_lstm_weights', 't2v_pack_lstm_weights_bf16', 't2v_decoder_train_fwd',
            't2v_decoder_train_bwd', 't2v_clip_adam_step', 't2v_clip_adam_step_guarded', 't2v_decoder_replay_fwd_kernels', 't2v_mel_frontend', 't2v_set_phase_profile', 't2v_decoder_infer_steps', 't2v_conv1d_stat_blocks', 't2v_conv1d_stat_blocks_bf16', 't2v_conv1d_staged_launches', 't2v_conv1d_fwd', 't2v_conv1d_bwd', 't2v_conv1d_fwd_bf16', 't2v_conv1d_bwd_bf16', 't2v_conv1d_dw_scratch_floats', 't2v_conv1d_flip_weights', 't2v_gemm_bf16', 't2v_gemm_bf16_splitk', 't2v_gemm_bf16_splitk_scratch_floats', 't2v_attn_wgrad', 't2v_attn_wgrad_scratch_floats',
            't2v_bn_act_fwd', 't2v_bn_act_bwd', 't2v_bn_act_bwd_eval', 't2v_bilstm_fwd', 't2v_bilstm_bwd', 't2v_gemm_f32', 't2v_conv2d_s2_fwd', 't2v_conv2d_s2_bwd', 't2v_conv2d_s2_dw_scratch_floats', 't2v_conv2d_s2_fwd_gemm', 't2v_conv2d_s2_bwd_gemm',
@@ -107,7 +113,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes',
            't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours',
            't2v_mel_cepstrum', 't2v_cep_dtw_scratch_bytes', 't2v_cep_dtw_path', 't2v_cep_dtw_forward', 't2v_cep_dtw_walk',
-           't2v_path_scores', 't2v_loudness', 't2v_loudness_scratch_bytes', 't2v_scale_rows')
+           't2v_path_scores', 't2v_loudness', 't2v_loudness_scratch_bytes', 't2v_scale_rows',
+           't2v_decoder_infer_steps_window', 't2v_decoder_infer_persistent_window')
 
 
 def lib_path():
@@ -224,6 +231,10 @@ def load_library():
     lib.t2v_decoder_infer_steps.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecInferBufs), C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_void_p]
     lib.t2v_decoder_infer_steps_items.argtypes = lib.t2v_decoder_infer_steps.argtypes[:-1] + [C.POINTER(_DecItems), C.c_void_p]
+    # the windowed entries: the arguments of the per-item ones (items may be NULL) plus the t2v_dec_window pointer
+    lib.t2v_decoder_infer_steps_window.argtypes = lib.t2v_decoder_infer_steps_items.argtypes[:-1] + [C.POINTER(_DecWindow), C.c_void_p]
+    lib.t2v_decoder_infer_persistent_window.argtypes = lib.t2v_decoder_infer_persistent_items.argtypes[:-1] + [C.POINTER(_DecWindow),
+                                                                                                               C.c_void_p]
     vp = C.c_void_p
     lib.t2v_stft_polar.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
     lib.t2v_istft_scratch_bytes.argtypes = [C.c_int, C.c_int]
@@ -2445,13 +2456,29 @@ def latent_neighbours(refs, labels, queries=None, k=5, n_classes=4, exclude=None
     return LatentNeighbours(idx, dist, class_sum, class_cnt, rank)
 
 
+def check_attention_window(window):
+    """None, or (back, ahead) as a tuple of two Python ints >= 0; anything else raises ValueError"""
+    if window is None:
+        return None
+    try:
+        if isinstance(window, (str, bytes)) or any(isinstance(x, bool) for x in window):
+            raise TypeError
+        vals = tuple(operator.index(x) for x in window)
+    except TypeError:
+        vals = ()
+    if len(vals) != 2 or min(vals) < 0 or max(vals) > 2 ** 31 - 1:
+        raise ValueError("attention_window must be None or (back, ahead), two integers >= 0, got %r" % (window,))
+    return vals
+
+
 class InferenceSession(object):
     """Arena + packed weights of one free-running decode (Decoder.inference / the per-step
     initialize_decoder_states → prenet → decode call sequence of synthesizer.py:135-154)."""
     INT_MAX = 2 ** 31 - 1
 
     def __init__(self, memory, pm, lengths, w_ih_att, w_hh_att, b_att, w_ih_dec, w_hh_dec, b_dec, wq, loc_conv,
-                 loc_dense, v, prenet_w0, prenet_w1, proj_w, proj_b, gate_w, gate_b, max_steps, item_seeds=None):
+                 loc_dense, v, prenet_w0, prenet_w1, proj_w, proj_b, gate_w, gate_b, max_steps, item_seeds=None,
+                 attention_window=None):
         if 'T2V_HOST_THREADS' in os.environ:        # (ADVICE r3: an inference session no longer throttles the host application)
             limit_host_threads()
         lib = _require_gpu(memory, pm, w_ih_att)
@@ -2500,6 +2527,10 @@ class InferenceSession(object):
             self.item_seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
             self.stop_item = torch.full((B,), self.INT_MAX, device=dev, dtype=torch.int32)
             self._items = _DecItems(_p(self.stop_item), _p(self.item_seeds))
+        # attention_window (back, ahead): every frame's energies are masked to [p - back, p + ahead] around the position p of
+        # the previous frame's largest weight (include/t2vae.h t2v_dec_window); both decode loops, every run of this session
+        self.attention_window = check_attention_window(attention_window)
+        self._window = None if self.attention_window is None else _DecWindow(*self.attention_window)
 
     def _stage_arena(self):
         if self.S is not None:
@@ -2533,7 +2564,9 @@ class InferenceSession(object):
                              _p(self.AL), _p(self.stop), _p(self._gran), _p(self._perr))
         name, args = 't2v_decoder_infer_persistent', [C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
                                                       float(gate_threshold), float(p_prenet), int(seed)]
-        if self._items is not None:         # per-item seeds and stop frames: the *_items entry point takes them behind the seed
+        if self._window is not None:        # the *_window entry point: items (or NULL), then the window
+            name, args = name + '_window', args + [None if self._items is None else C.byref(self._items), C.byref(self._window)]
+        elif self._items is not None:       # per-item seeds and stop frames: the *_items entry point takes them behind the seed
             name, args = name + '_items', args + [C.byref(self._items)]
         _check(getattr(lib, name)(*args, _stream()), name)
 
@@ -2559,7 +2592,9 @@ class InferenceSession(object):
                                  _p(self.wqT), _p(self.wcomb), _p(self.v))
         name, args = 't2v_decoder_infer_steps', [C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0), int(t1),
                                                  float(gate_threshold), float(p_prenet), int(bool(external_prenet)), int(seed)]
-        if self._items is not None:
+        if self._window is not None:
+            name, args = name + '_window', args + [None if self._items is None else C.byref(self._items), C.byref(self._window)]
+        elif self._items is not None:
             name, args = name + '_items', args + [C.byref(self._items)]
         _check(getattr(load_library(), name)(*args, _stream()), name)
 
