@@ -1004,6 +1004,34 @@ int t2v_loudness(const float* y, const int32_t* n, int y_stride, int B, const do
                  int ms_stride, float* block_pw, int blk_stride, int32_t* rows, void* scratch, void* stream);
 int t2v_scale_rows(float* y, const int32_t* n, int y_stride, int B, const float* gains, void* stream);
 
+/* ------------------------------------------------------------------ tempo and pitch: a phase vocoder
+ * Time-scale modification of a ragged batch of polar spectrograms (csrc/tsm.hip).  mag and phase are (B, 513, t_stride) fp32
+ * as t2v_stft_polar writes them (hop = a quarter window), row b has n_frames[b] frames (device int32, clamped to 0..T; T <=
+ * t_stride is the most any row has); nothing at or past frame n_frames[b] is read.  The rate is num / den, each in
+ * 1..T2V_TSM_MAX_RATIO (else T2V_ERR_DIMS): above 1 is faster.  Row b gets n_out[b] = ceil(n_frames[b] den / num) frames of
+ * mag_out and phase_out (B, 513, out_stride); both are +0 from n_out[b] to out_stride.  For output frame j, with
+ * i = (j num) / den and a = ((j num) % den) / den in integers:
+ *   mag_out[j, k]   = (1 - a) mag[i, k] + a mag[i + 1, k], frame i + 1 == n_frames[b] counting as magnitude 0;
+ *   phase_out[j, k] = phase[0, k] + sum over j' < j of d[j', k], d = wrap(phase[i' + 1, k] - phase[i', k] - pi k / 2) + pi k / 2
+ *                     (past the end: pi k / 2 alone), given modulo 2 pi, in [-pi, pi).
+ * The sum is a prefix sum of 32-bit fixed-point fractions of a turn (round(p 2^32 / 2 pi) of each fp32 phase): integer
+ * addition, so a row gives the same bits alone, in any batch, at any stride, and output j is off by at most 2 (j + 1) 2^-33
+ * turns plus its one rounding to fp32.
+ * phase_lock != 0: identity phase locking.  The peaks of analysis frame i (mag[i, k] greater than mag[i, k +-1] and
+ * mag[i, k +-2]; neighbours outside 0..512 are not compared) keep their sums; every other bin takes its nearest peak's
+ * (a tie: the lower peak's) plus phase[i, k] - phase[i, kp]; a frame without a peak stays as it is.  The sums themselves are
+ * never locked.  It needs scratch: t2v_phase_vocoder_scratch_bytes(B, out_stride, phase_lock) bytes of device memory (0
+ * without locking), and B <= 65535.
+ * phase == phase_out == NULL: magnitudes only (no scratch, phase_lock ignored).
+ * A null required pointer, one of phase / phase_out alone, B < 1, T outside 1..T2V_TSM_MAX_FRAMES, t_stride < T or
+ * out_stride < ceil(T den / num) is T2V_ERR_ARG. */
+#define T2V_TSM_BINS 513
+#define T2V_TSM_MAX_RATIO 1023
+#define T2V_TSM_MAX_FRAMES (1 << 20)
+size_t t2v_phase_vocoder_scratch_bytes(int B, int out_stride, int phase_lock);
+int t2v_phase_vocoder(const float* mag, const float* phase, const int32_t* n_frames, int B, int T, int t_stride, int num, int den,
+                      int phase_lock, float* mag_out, float* phase_out, int out_stride, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--energy] [--attention_window BACK,AHEAD] [--hparams ...]
+                       [--style [--style_k K]] [--aligned] [--energy] [--attention_window BACK,AHEAD] [--speed R] [--pitch ST]
+                       [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
 (copy synthesis); --condition emotion takes the centroid of the row's emotion label (built from the filelist, or read from
@@ -68,7 +69,14 @@ loudness_ref_vs_neu_lu, the emotion's mean loudness minus neutral's, synthesised
 
 --attention_window BACK,AHEAD decodes every row under the attention constraint of `Decoder.attention_window` (each frame
 attends within BACK positions behind and AHEAD in front of the position the previous frame attended most).
-OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart."""
+OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart.
+
+--speed R and --pitch ST set the tempo and the pitch shift (semitones) of the vocoder leg (`GriffinLimVocoder(speed=, pitch=)`,
+DESIGN 7o): the waveforms that --prosody and --energy measure are the ones the synthesis command line would write with the
+same flags, and their pitch and level tracks run over those waveforms' own frames (ceil(n_frames / speed) of them, not
+n_frames).  The mels, and with them dtw and every score taken of mels, do not change.  --aligned together with --prosody or
+--energy is refused with them: the warping path is over mel frames, and the waveform's frames lie on another time axis.
+OUT.json always holds "speed" and "pitch" (1.0 and 0.0 without the flags)."""
 import argparse
 import json
 
@@ -113,6 +121,8 @@ def build_arg_parser():
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
+    from synthesizer import add_tempo_arguments
+    add_tempo_arguments(p)
     return p
 
 
@@ -124,6 +134,9 @@ def parse_args(argv=None):
         raise SystemExit("--style_k must be in 1..32")
     if args.limit is not None and args.limit < 1:
         raise SystemExit("--limit must be >= 1")
+    if args.aligned and (args.prosody or args.energy) and (args.speed != 1.0 or args.pitch != 0.0):
+        raise SystemExit("--aligned with --prosody / --energy scores tracks along the mels' warping path; with --speed / --pitch "
+                         "the waveform is on another time axis: drop --aligned or the two flags")
     return args
 
 
@@ -151,14 +164,15 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
+    from synthesizer import tempo_options
     from wavio import wav_options
-    syn = Synthesizer(hp, attention_window=args.attention_window, **wav_options(args))
+    syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args))
     if args.condition == 'emotion':
         syn.load(args.load_path, vocoder=args.vocoder if args.prosody or args.energy else None, filelist_path=args.filelist_path)
     else:
         syn.load_checkpoint(args.load_path)
         if args.prosody or args.energy:
-            syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft)
+            syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft, syn.speed, syn.pitch_st)
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
@@ -166,7 +180,8 @@ def main(argv=None):
     summary = summarize(records)
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)],
-                   'attention_window': None if syn.attention_window is None else list(syn.attention_window)}, f, indent=1)
+                   'attention_window': None if syn.attention_window is None else list(syn.attention_window),
+                   'speed': syn.speed, 'pitch': syn.pitch_st}, f, indent=1)
     print(json.dumps(summary, indent=1))
     if args.alignment:
         for name, st in summary['by_emotion'].items():

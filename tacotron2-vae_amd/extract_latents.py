@@ -3,7 +3,7 @@
 latent_map.py's (or --tsne here).
 
     python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...] [--tsne [KEY]]
-                              [--scores [KEY]]
+                              [--scores [KEY]] [--probe OUT.json]
 
 Filelist rows are `path|text|speaker|emotion`.  OUT.npz holds, row i for filelist row i: prosody (N, E), mus, logvars,
 zs (N, z_latent_dim), emotions (N,) int and paths (N,) str.  The wavs run through `Synthesizer.latents`: sorted by
@@ -11,6 +11,9 @@ length, in ragged batches of at most --batch_size, each row what model.vae_gst(l
 map of that array by latent_map.compute_map with its defaults, and tsne_kl; without it the file is what it always was.
 --scores [mus|zs] adds scores, the dict of latent_report.py (leave-one-out kNN accuracy, silhouette, active units, KL per
 dimension) for that array as a JSON string; without it the file is what it always was.
+--probe OUT.json also writes the latent probe (`Synthesizer.latent_probe` with its defaults): how far mu moves when
+a clip's pitch, tempo or level alone is changed, against the distance between the emotions' centroids; OUT.npz is not
+changed by it.
 """
 import argparse
 
@@ -30,6 +33,8 @@ def build_arg_parser():
                    help="also store the t-SNE map of this array (default mus) as tsne, tsne_kl")
     p.add_argument('--scores', nargs='?', const='mus', default=None, choices=('mus', 'zs'),
                    help="also store the latent_report.py scores of this array (default mus) as a JSON string under scores")
+    p.add_argument('--probe', default=None, metavar='OUT.json',
+                   help="also write the latent probe: mean and median move of mu under single pitch, tempo and level changes")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
     return p
@@ -79,6 +84,14 @@ def main(argv=None):
         from latent_scores import corpus_report
         out.update(scores=json.dumps(corpus_report(out[args.scores], emotions, mu, logvar)))
     np.savez(args.out, **out)
+    if args.probe:
+        import json
+        probe = syn.latent_probe(paths, emotions.tolist(), batch_size=args.batch_size)
+        with open(args.probe, 'w', encoding='utf-8') as f:
+            json.dump(probe, f, indent=1)
+        for r in probe['perturbations']:
+            print("%s %+g: mean |dmu| %.4g (%s of the scale)" % (r['kind'], r['value'], r['mean'],
+                                                                "n/a" if r['mean_rel'] is None else "%.3f" % r['mean_rel']))
     print("%s: %d utterances" % (args.out, len(paths)))
 
 

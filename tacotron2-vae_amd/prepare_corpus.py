@@ -5,6 +5,7 @@ trim_bounds, crop; csrc/resample.hip).
     python prepare_corpus.py --filelist_path F --out_dir D --out_filelist F2
            [--sampling_rate 16000] [--trim_db 40 | --no_trim] [--pad_frames 2] [--batch_size 64] [--report R.json]
            [--lufs TARGET [--lufs_scope utterance|speaker] [--peak_db -1.0]]
+           [--speed_perturb 0.9,1.1] [--pitch_perturb -1,1]
 
 Filelist rows are `path|text|speaker|emotion` (any column count, the path first).  Each wav is read as it lies in the file
 (int16 goes to the device as it is; int32 and float wavs are scaled to [-1, 1) on the host; a wav with more than one channel
@@ -24,7 +25,16 @@ emotions survive: a first pass measures every row and writes nothing, the speake
 block sums and counts, -0.691 + 10 log10(sum of gated sums / sum of gated counts), and a second pass applies TARGET minus that.
 The relative gate stays per row here: it is not that of the speaker's concatenated recordings.  A peak limit lowers the whole
 speaker's gain.  The report then has per row `loudness_lufs` (before the gain), `gain_db` and `gain_limited`, per speaker the
-pooled loudness and the gain, and in `loudness` the mean and spread of the measured loudness."""
+pooled loudness and the gain, and in `loudness` the mean and spread of the measured loudness.
+
+--speed_perturb R,... and --pitch_perturb ST,... (off by default; the usual augmentation of a small corpus) add one more copy of
+every row per listed value: the resampled and trimmed wav through t2v_hip.time_stretch at the rate R (0.25..4, above 1 is
+faster) or t2v_hip.pitch_shift by ST semitones (-12..12), the phase vocoder of csrc/tsm.hip, before the loudness normalisation
+and the 16-bit write-out.  A copy is written as D/<stem>_sp0.90.wav / D/<stem>_ps-1.wav and listed in F2 right behind its row,
+with the row's other columns.  With --lufs every copy gets its own gain, or its speaker's, lowered where the copy's own peak would pass --peak_db.  The row's record in the report
+gains `perturbed`: per copy kind ('speed' or 'pitch'), value, out_path, samples_out, peak, clipped_samples (and the loudness
+fields); a row of 512 samples or fewer after the trim has no copies and says so in `perturb_skipped`.  The unperturbed row is
+written exactly as without the flags."""
 import argparse
 import json
 import math
@@ -56,10 +66,54 @@ def build_arg_parser():
                    help="one gain per wav, or one per speaker (filelist column 3)")
     p.add_argument('--peak_db', type=float, default=DEFAULT_PEAK_DB, metavar='DB',
                    help="no gain lifts a wav's peak above DB dBFS (<= 0)")
+    p.add_argument('--speed_perturb', type=parse_speed_list, default=[], metavar='R,...',
+                   help="also write a copy of every wav at each of these tempo rates (0.25..4, not 1); off by default")
+    p.add_argument('--pitch_perturb', type=parse_pitch_list, default=[], metavar='ST,...',
+                   help="also write a copy of every wav shifted by each of these semitone counts (-12..12, not 0); a list that starts "
+                        "with a minus sign may also be written --pitch_perturb=-1,1; off by default")
     return p
 
 
+def _number_list(text, what, check, identity):
+    import t2v_hip
+    try:
+        values = [float(x) for x in text.split(',') if x.strip()]
+        for v in values:
+            getattr(t2v_hip, check)(v)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError("%s: %s" % (what, e))
+    if not values or identity in values or len(set(values)) != len(values):
+        raise argparse.ArgumentTypeError("%s takes distinct comma separated values other than %g, got %r" % (what, identity, text))
+    return values
+
+
+def parse_speed_list(text):
+    """'0.9,1.1' -> [0.9, 1.1]: tempo rates in 0.25..4, distinct, none of them 1"""
+    return _number_list(text, '--speed_perturb', 'stretch_ratio', 1.0)
+
+
+def parse_pitch_list(text):
+    """'-1,1' -> [-1.0, 1.0]: semitones in -12..12, distinct, none of them 0"""
+    return _number_list(text, '--pitch_perturb', 'pitch_ratio', 0.0)
+
+
+def perturbed_name(name, kind, value):
+    """the file name of a perturbed copy of <stem>.wav: <stem>_sp0.90.wav for a tempo rate, <stem>_ps-1.wav / <stem>_ps1.5.wav
+    for a pitch shift in semitones"""
+    stem = name[:-4] if name.lower().endswith('.wav') else name
+    if kind == 'speed':
+        return "%s_sp%.2f.wav" % (stem, value)
+    if kind == 'pitch':
+        return "%s_ps%s.wav" % (stem, "%d" % value if float(value) == int(value) else "%g" % value)
+    raise ValueError("perturbed_name: kind must be 'speed' or 'pitch', got %r" % (kind,))
+
+
 def parse_args(argv=None):
+    import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for k in range(len(argv) - 2, -1, -1):    # "--pitch_perturb -1,1": argparse takes a list that starts with '-' for a flag
+        if argv[k] in ('--pitch_perturb', '--speed_perturb') and argv[k + 1][:1] == '-' and argv[k + 1][1:2].isdigit():
+            argv[k:k + 2] = [argv[k] + '=' + argv[k + 1]]
     args = build_arg_parser().parse_args(argv)
     if args.batch_size < 1:
         raise SystemExit("--batch_size must be >= 1")
@@ -73,6 +127,9 @@ def parse_args(argv=None):
         raise SystemExit("--peak_db must be a finite level <= 0 dBFS")
     if args.lufs is not None and not math.isfinite(args.lufs):
         raise SystemExit("--lufs must be a finite level in LUFS")
+    tags = [perturbed_name('x.wav', 'speed', v) for v in args.speed_perturb] + [perturbed_name('x.wav', 'pitch', v) for v in args.pitch_perturb]
+    if len(set(tags)) != len(tags):
+        raise SystemExit("--speed_perturb / --pitch_perturb: two values give one file name (%s)" % ', '.join(sorted(tags)))
     if args.report is None:
         args.report = os.path.join(args.out_dir, 'report.json')
     return args
@@ -193,9 +250,10 @@ def summarize(records):
     return by_rate
 
 
-def process_batch(items, target_rate, trim_db, pad_frames):
-    """items: [(source rate, samples (int16 or float32 numpy))].  Returns per item (int16 numpy samples, record fields):
-    resample (one launch per distinct (rate, format)) -> trim_bounds -> crop to int16, as one ragged batch."""
+def front_end(items, target_rate, trim_db, pad_frames):
+    """items: [(source rate, samples (int16 or float32 numpy))].  Returns (y (B, max count) float32 on the device, the resampled
+    counts, the (start, end) each row is to be cropped to): resample (one launch per distinct (rate, format)) -> trim_bounds
+    of one ragged batch.  No caller writes into y, so one result serves the plain row and its perturbed copies."""
     import t2v_hip
     from synthesizer import resample_rows
     y, n = resample_rows(items, target_rate)
@@ -203,6 +261,14 @@ def process_batch(items, target_rate, trim_db, pad_frames):
         bounds = [[0, k] for k in n]
     else:
         bounds = t2v_hip.trim_bounds(y, n, trim_db, pad_frames).cpu().tolist()
+    return y, n, bounds
+
+
+def process_batch(items, target_rate, trim_db, pad_frames, front=None):
+    """Returns per item (int16 numpy samples, record fields): front_end (or its result `front`, when the caller has it) -> crop
+    to int16, as one ragged batch."""
+    import t2v_hip
+    y, n, bounds = front or front_end(items, target_rate, trim_db, pad_frames)
     pcm, counts, stats = t2v_hip.crop(y, bounds, pcm16=True, return_stats=True)
     pcm = pcm.cpu().numpy()
     out = []
@@ -217,16 +283,12 @@ def process_batch(items, target_rate, trim_db, pad_frames):
     return out
 
 
-def measure_batch(items, target_rate, trim_db, pad_frames):
-    """resample -> trim_bounds -> crop (fp32) -> loudness of one ragged batch.  Returns (y (B, max count) float32 on the device,
-    counts, per-item record fields without the write-out's, per-item (integrated LUFS or None, gated_sum, gated_blocks, peak))."""
+def measure_batch(items, target_rate, trim_db, pad_frames, front=None):
+    """front_end (or its result `front`) -> crop (fp32) -> loudness of one ragged batch.  Returns (y (B, max count) float32 on
+    the device, counts, per-item record fields without the write-out's, per-item (integrated LUFS or None, gated_sum,
+    gated_blocks, peak))."""
     import t2v_hip
-    from synthesizer import resample_rows
-    y, n = resample_rows(items, target_rate)
-    if trim_db is None:
-        bounds = [[0, k] for k in n]
-    else:
-        bounds = t2v_hip.trim_bounds(y, n, trim_db, pad_frames).cpu().tolist()
+    y, n, bounds = front or front_end(items, target_rate, trim_db, pad_frames)
     y, counts = t2v_hip.crop(y, bounds)
     loud = t2v_hip.loudness(y, [max(c, 1) for c in counts], target_rate)
     peaks = y.abs().amax(dim=1).tolist()
@@ -241,11 +303,11 @@ def measure_batch(items, target_rate, trim_db, pad_frames):
     return y, counts, fields, measured
 
 
-def process_batch_lufs(items, target_rate, trim_db, pad_frames, target, peak_db, gains=None):
+def process_batch_lufs(items, target_rate, trim_db, pad_frames, target, peak_db, gains=None, front=None):
     """process_batch with the level normalised: measure_batch -> gain -> scale_rows -> crop to int16.  gains: one
     (gain_db, limited) per item (the speaker's), or None for each row's own, gain_for(target, its loudness, its peak)."""
     import t2v_hip
-    y, counts, fields, measured = measure_batch(items, target_rate, trim_db, pad_frames)
+    y, counts, fields, measured = measure_batch(items, target_rate, trim_db, pad_frames, front)
     if gains is None:
         gains = [gain_for(target, lu, peak, peak_db) for lu, _, _, peak in measured]
     lengths = [max(c, 1) for c in counts]
@@ -258,6 +320,57 @@ def process_batch_lufs(items, target_rate, trim_db, pad_frames, target, peak_db,
         out.append((pcm[b, :counts[b]].copy(),
                     dict(fields[b], peak=peak, clipped_samples=clipped, all_silent=bool(peak == 0.0),
                          loudness_lufs=measured[b][0], gain_db=gains[b][0], gain_limited=gains[b][1])))
+    return out
+
+
+PERTURB_MIN_SAMPLES = 513                # the phase vocoder's transform reflect-pads by 512
+
+
+def process_batch_perturbed(front, target_rate, variants, target=None, peak_db=DEFAULT_PEAK_DB, gains=None):
+    """The perturbed copies of one ragged batch, from the front_end result the plain rows were written from: crop (fp32), then
+    per variant (kind, value) time_stretch or pitch_shift of the rows that are long enough, with a target the level
+    normalisation of process_batch_lufs, and the crop to int16.  gains: None for each copy's own, or one (gain_db, limited) per
+    item, the speaker's; that gain was limited by the peaks of the unperturbed rows, and a copy may overshoot them, so it is
+    lowered for a copy whose own peak it would lift above peak_db (`gain_limited` on that copy).  Returns per item None (512
+    samples or fewer) or a list, in the order of the variants, of (int16 numpy samples, record fields)."""
+    import torch
+    import t2v_hip
+    y, counts = t2v_hip.crop(front[0], front[2])
+    can = [b for b, c in enumerate(counts) if c >= PERTURB_MIN_SAMPLES]
+    out = [None] * len(counts)
+    if not can:
+        return out
+    if len(can) < len(out):
+        y = y[torch.tensor(can, device=y.device)].contiguous()
+    counts = [counts[b] for b in can]
+    for b in can:
+        out[b] = []
+    for kind, value in variants:
+        if kind == 'speed':
+            z, m = t2v_hip.time_stretch(y, counts, value)
+        else:
+            z, m = t2v_hip.pitch_shift(y, counts, value)
+        extra = [{} for _ in can]
+        if target is not None:
+            z = z.clone() if z is y else z
+            loud = t2v_hip.loudness(z, m, target_rate)
+            peaks = z.abs().amax(dim=1).tolist()
+            lus = [None if math.isinf(lu) else lu for lu in loud.integrated]
+            if gains is None:
+                g = [gain_for(target, lu, pk, peak_db) for lu, pk in zip(lus, peaks)]
+            else:
+                g = []
+                for b, pk in zip(can, peaks):
+                    room = float(peak_db) - 20.0 * math.log10(pk) if pk > 0.0 else float('inf')
+                    g.append((room, True) if gains[b][0] > room else gains[b])
+            t2v_hip.scale_rows(z, m, [10.0 ** (x / 20.0) for x, _ in g])
+            extra = [dict(loudness_lufs=lu, gain_db=x, gain_limited=lim) for lu, (x, lim) in zip(lus, g)]
+        pcm, m, stats = t2v_hip.crop(z, [[0, k] for k in m], pcm16=True, return_stats=True)
+        pcm = pcm.cpu().numpy()
+        for k, b in enumerate(can):
+            clipped, peak = stats[k]
+            out[b].append((pcm[k, :m[k]].copy(), dict(extra[k], kind=kind, value=value, samples_out=m[k], peak=peak,
+                                                     clipped_samples=clipped)))
     return out
 
 
@@ -297,6 +410,8 @@ def main(argv=None):
             records[i] = dict(path=r[0], skipped=str(e))
     new_paths = [None] * len(rows)
     trim_db = None if args.no_trim else args.trim_db
+    variants = [('speed', v) for v in args.speed_perturb] + [('pitch', v) for v in args.pitch_perturb]
+    copies = [[] for _ in rows]                                          # the perturbed copies' paths, per row
 
     def batches():
         for idx in length_groups(lengths, args.batch_size):
@@ -321,22 +436,40 @@ def main(argv=None):
                 measured.append((rows[i][2], m[1], m[2], m[3]))
         speakers = speaker_gains(measured, args.lufs, args.peak_db)
     for group, items in batches():
+        front = front_end(items, args.sampling_rate, trim_db, args.pad_frames) if variants else None
         if args.lufs is None:
-            done = process_batch(items, args.sampling_rate, trim_db, args.pad_frames)
+            done = process_batch(items, args.sampling_rate, trim_db, args.pad_frames, front)
         else:
             gains = [(speakers[rows[i][2]]['gain_db'], speakers[rows[i][2]]['gain_limited']) for i in group] if by_speaker else None
-            done = process_batch_lufs(items, args.sampling_rate, trim_db, args.pad_frames, args.lufs, args.peak_db, gains)
+            done = process_batch_lufs(items, args.sampling_rate, trim_db, args.pad_frames, args.lufs, args.peak_db, gains, front)
         for i, (pcm, rec) in zip(group, done):
             new_paths[i] = os.path.join(args.out_dir, names[i])
             write(new_paths[i], args.sampling_rate, pcm)
             records[i] = dict(rec, path=rows[i][0], out_path=new_paths[i])
+        if variants:
+            done = process_batch_perturbed(front, args.sampling_rate, variants, args.lufs, args.peak_db,
+                                           gains if args.lufs is not None else None)
+            for i, made in zip(group, done):
+                records[i]['perturbed'] = []
+                if made is None:
+                    records[i]['perturb_skipped'] = "%d samples or fewer after the trim" % (PERTURB_MIN_SAMPLES - 1)
+                    continue
+                for pcm, rec in made:
+                    path = os.path.join(args.out_dir, perturbed_name(names[i], rec['kind'], rec['value']))
+                    write(path, args.sampling_rate, pcm)
+                    copies[i].append(path)
+                    records[i]['perturbed'].append(dict(rec, out_path=path))
     with open(args.out_filelist, 'w', encoding='utf-8') as f:
-        for line in rewrite_rows(rows, new_paths):
-            f.write(line + '\n')
+        for r, p, extra in zip(rows, new_paths, copies):
+            for line in rewrite_rows([r] * (1 + len(extra)), [p] + extra):
+                f.write(line + '\n')
     n_skipped = sum(1 for r in records if r.get('skipped'))
     report = dict(target_rate=args.sampling_rate, trim_db=None if args.no_trim else args.trim_db, pad_frames=args.pad_frames,
                   n_rows=len(rows), n_written=len(rows) - n_skipped, n_skipped=n_skipped, by_source_rate=summarize(records),
                   rows=records)
+    if variants:
+        report['perturbations'] = dict(speed=args.speed_perturb, pitch=args.pitch_perturb,
+                                       n_written=sum(len(c) for c in copies))
     if args.lufs is not None:
         report['loudness'] = dict(loudness_totals(records), target_lufs=args.lufs, scope=args.lufs_scope, peak_db=args.peak_db)
         if speakers is not None:

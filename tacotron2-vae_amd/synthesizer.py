@@ -72,22 +72,29 @@ class GriffinLimVocoder(object):
     clamped at 0) and n_iters Griffin-Lim iterations on `stft.stft_fn` (audio_processing.griffin_lim, initial phase from
     np.random).  The samples are not clipped: Griffin-Lim's output may exceed +-1 slightly.  Needs T >= 4 frames.
     momentum > 0: fast Griffin-Lim; inversion='nnls': the non-negative least-squares inverse of the filterbank
-    (inversion_iters projected-gradient steps from the clamped pinv).  Neither changes which phases are drawn."""
+    (inversion_iters projected-gradient steps from the clamped pinv).  Neither changes which phases are drawn.
+    speed (0.25..4, above 1 is faster) and pitch (semitones, -12..12), with p / q = 2^(pitch / 12) from `t2v_hip.pitch_ratio`:
+    the linear magnitudes are stretched in time by speed q / p (`t2v_hip.stretch_magnitude`; Griffin-Lim makes the phases, so
+    no phase vocoder is needed), Griffin-Lim runs on the stretched frames (at least 4 per row), and its waveform is resampled
+    by p / q (`t2v_hip.resample`), which brings the duration back to 1 / speed and moves every frequency by p / q.  The
+    initial phases are then drawn for the stretched frame counts.  speed=1, pitch=0 is the vocoder without them."""
 
-    def __init__(self, stft, n_iters=60, momentum=0.0, inversion='pinv', inversion_iters=100):
-        from t2v_hip import check_momentum
+    def __init__(self, stft, n_iters=60, momentum=0.0, inversion='pinv', inversion_iters=100, speed=1.0, pitch=0.0):
+        from t2v_hip import check_momentum, vocoder_rates
         if inversion not in ('pinv', 'nnls'):
             raise ValueError("GriffinLimVocoder: inversion must be 'pinv' or 'nnls', got %r" % (inversion,))
         self.stft, self.n_iters = stft, n_iters
         self.momentum, self.inversion, self.inversion_iters = check_momentum(momentum), inversion, inversion_iters
+        self.speed, self.pitch = float(speed), float(pitch)
+        self.stretch, self.shift = vocoder_rates(speed, pitch)      # (num, den) of the magnitudes' rate, (p, q) of the pitch
 
     @classmethod
-    def named(cls, name, stft):
+    def named(cls, name, stft, speed=1.0, pitch=0.0):
         """the vocoder behind load(vocoder=name) and the command lines' --vocoder"""
         if name == 'griffin_lim':
-            return cls(stft)
+            return cls(stft, speed=speed, pitch=pitch)
         if name == 'griffin_lim_fast':
-            return cls(stft, momentum=0.99, inversion='nnls')
+            return cls(stft, momentum=0.99, inversion='nnls', speed=speed, pitch=pitch)
         raise ValueError("unknown vocoder %r (a callable, or one of %s)" % (name, ', '.join(repr(v) for v in VOCODERS)))
 
     def _magnitudes(self, mel, lengths):
@@ -95,10 +102,34 @@ class GriffinLimVocoder(object):
             return self.stft.mel_to_magnitude(mel, lengths)
         return self.stft.mel_to_magnitude(mel, lengths, self.inversion, self.inversion_iters)
 
+    def _stretched(self, magnitudes, n):
+        """the magnitudes at the rate self.stretch and their frame counts (as they came when the rate is 1)"""
+        import t2v_hip
+        if self.stretch[0] == self.stretch[1]:
+            return magnitudes, n
+        for b, k in enumerate(n):
+            if t2v_hip.stretch_frames(k, *self.stretch) < 4:
+                raise ValueError("GriffinLimVocoder: row %d has %d frames, fewer than Griffin-Lim's 4 at the rate %d/%d"
+                                 % (b, k, self.stretch[0], self.stretch[1]))
+        return t2v_hip.stretch_magnitude(self.stft.stft_fn.on_gpu(magnitudes), n, self.stretch)
+
+    def _shifted(self, wav, n):
+        """Griffin-Lim's waveforms ((n[b] - 1) 256 samples each) resampled by p / q: (wav, sample counts)"""
+        import t2v_hip
+        counts = [(k - 1) * 256 for k in n]
+        if self.shift[0] == self.shift[1]:
+            return wav, counts
+        return t2v_hip.resample(self.stft.stft_fn.on_gpu(wav), counts, *self.shift)
+
     def __call__(self, mel, lengths=None):
         from audio_processing import griffin_lim
         magnitudes = self._magnitudes(mel, lengths)
-        return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths, momentum=self.momentum)
+        if self.stretch[0] == self.stretch[1] and self.shift[0] == self.shift[1]:
+            return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths, momentum=self.momentum)
+        n = [magnitudes.size(2)] * magnitudes.size(0) if lengths is None else [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
+        stretched, n = self._stretched(magnitudes, n)
+        wav = griffin_lim(stretched, self.stft.stft_fn, self.n_iters, lengths=n, momentum=self.momentum)
+        return self._shifted(wav, n)[0].to(mel.device)
 
     def batch(self, mel, lengths):
         """A ragged batch in one set of launches, item by item as `self(mel[b:b+1, :, :lengths[b]])` would give it: the
@@ -106,19 +137,29 @@ class GriffinLimVocoder(object):
         a row draw.  Returns a list of B waveforms ((lengths[b]-1)*256 samples each) on the device."""
         from audio_processing import griffin_lim
         n = [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
-        B, T = mel.size(0), mel.size(2)
-        angles = np.zeros((B, 513, T), dtype=np.float32)
+        B = mel.size(0)
+        magnitudes, n = self._stretched(self._magnitudes(mel, n), n)
+        angles = np.zeros((B, 513, magnitudes.size(2)), dtype=np.float32)
         for b, nb in enumerate(n):
             angles[b, :, :nb] = np.angle(np.exp(2j * np.pi * np.random.rand(1, 513, nb)))[0]
-        magnitudes = self._magnitudes(mel, n)
         wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, angles=torch.from_numpy(angles), lengths=n,
                           momentum=self.momentum)
-        return [wav[b, :(nb - 1) * 256] for b, nb in enumerate(n)]
+        wav, counts = self._shifted(wav, n)
+        return [wav[b, :k] for b, k in enumerate(counts)]
 
 
 class Synthesizer(object):
-    def __init__(self, hparams=None, resample=False, trim_db=None, attention_window=None):
-        """attention_window: None, or (back, ahead) for the decoder of every model this object loads (`Decoder.attention_window`:
+    def __init__(self, hparams=None, resample=False, trim_db=None, attention_window=None, speed=1.0, pitch=0.0, ref_speed=1.0,
+                 ref_pitch=0.0):
+        """speed, pitch: the tempo (0.25..4, above 1 is faster) and the pitch shift in semitones (-12..12) of what the built-in
+        vocoder writes (`GriffinLimVocoder(speed=, pitch=)`, made in `load`): synthesize, synthesize_batch and the vocoder leg
+        of evaluate pick them up through the vocoder object; ref_speed, ref_pitch: every reference wav that is read goes
+        through `t2v_hip.time_stretch` / `t2v_hip.pitch_shift` before the mel front end ("say it like this clip, but faster /
+        higher").  The reference knobs act where the wavs are read (`load_wavs`), so every consumer gets the perturbed clip:
+        load_mel(s), latents, latent_map / latent_report, pitch, loudness, latent_probe (on top of its own perturbations) and
+        both uses of the recordings in evaluate, the style and the `truth` mels; `wav_lengths`, which only sorts, still counts the
+        files' samples.  All four are off by default.
+        attention_window: None, or (back, ahead) for the decoder of every model this object loads (`Decoder.attention_window`:
         each free-running frame attends within [p - back, p + ahead] of the position p the previous frame attended most), so
         synthesize, synthesize_batch, alignment and evaluate all decode under it;
         resample: wavs at any sampling rate are resampled to hparams.sampling_rate on the device (`t2v_hip.resample`)
@@ -138,6 +179,12 @@ class Synthesizer(object):
             if hp.hop_length != 256:
                 raise ValueError("trim_db: the trim is built for hop 256, the front end has hop %d" % hp.hop_length)
         self.resample, self.trim_db = bool(resample), trim_db
+        import t2v_hip
+        t2v_hip.vocoder_rates(speed, pitch)                              # refused here, not at load()
+        self.speed, self.pitch_st = float(speed), float(pitch)         # `pitch` is the F0 tracker's method
+        self.ref_speed, self.ref_pitch = float(ref_speed), float(ref_pitch)
+        self._ref_stretch, self._ref_shift = t2v_hip.stretch_ratio(ref_speed), t2v_hip.pitch_ratio(ref_pitch)
+        self._ref_perturbed = self._ref_stretch[0] != self._ref_stretch[1] or self._ref_shift[0] != self._ref_shift[1]
         from t2v_hip import check_attention_window
         self.attention_window = check_attention_window(attention_window)
         self.stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels,
@@ -148,7 +195,7 @@ class Synthesizer(object):
 
     # ------------------------------------------------------------------ audio -> mel (synthesizer.py:57-68)
     def load_mel(self, path):
-        if self.resample or self.trim_db is not None:
+        if self.resample or self.trim_db is not None or self._ref_perturbed:
             y, n = self.load_wavs([path])
             return self.stft.mel_spectrogram(y[:, :n[0]])
         audio, sampling_rate = load_wav_to_torch(path)
@@ -177,7 +224,15 @@ class Synthesizer(object):
         from wavio import read_wav
         if not paths:
             raise ValueError("load_wavs: no paths")
-        return resample_rows([read_wav(path) for path in paths], self.hparams.sampling_rate)
+        return self._perturb_refs(*resample_rows([read_wav(path) for path in paths], self.hparams.sampling_rate))
+
+    def _perturb_refs(self, y, n):
+        """ref_speed and ref_pitch on a batch of wavs that has just been read (as it came when both are off)"""
+        if not self._ref_perturbed:
+            return y, n
+        import t2v_hip
+        y, n = t2v_hip.time_stretch(y, n, self._ref_stretch)
+        return t2v_hip.pitch_shift(y, n, self.ref_pitch)
 
     def _load_wavs_at_rate(self, paths):
         audios = []
@@ -192,10 +247,11 @@ class Synthesizer(object):
         y = torch.zeros(len(audios), max(n))
         for b, a in enumerate(audios):
             y[b, :n[b]] = a
-        return y.cuda(), n
+        return self._perturb_refs(y.cuda(), n)
 
     def wav_lengths(self, paths):
-        """sample counts of the wavs as `load_wavs` will count them before any trim, from their headers: the file's count, or
+        """sample counts of the wavs as `load_wavs` will count them before any trim (and before ref_speed / ref_pitch, which
+        change them by the rate), from their headers: the file's count, or
         with resample=True ceil(count up / down) at the front end's rate; what the length sorting of `latents` and `pitch`
         goes by"""
         if not self.resample:
@@ -305,6 +361,76 @@ class Synthesizer(object):
         lat = [t.float().cpu().numpy() for t in self.latents(paths, batch_size)]
         return corpus_report(lat[keys[key]], emotions, lat[1], lat[2], k)
 
+    @torch.no_grad()
+    def latent_probe(self, paths, emotions=None, pitch=(-2, 2), speed=(0.85, 1.15), gain_db=(-6, 6), batch_size=64):
+        """What does the latent listen to?  Every wav is encoded as it is and under each single perturbation: a pitch shift
+        (semitones, `t2v_hip.pitch_shift`), a tempo change (`t2v_hip.time_stretch`) or a gain (dB, `t2v_hip.scale_rows`), applied
+        to the samples `load_wavs` gives, before the mel front end.  Returns a JSON-serialisable dict: `n_clips`, `scale`,
+        `scale_kind` and `perturbations`, one entry per value in the order pitch, speed, gain_db with `kind`, `value`, the
+        `mean` and `median` over the clips of ||mu' - mu||_2, and `mean_rel` / `median_rel`, those divided by `scale`.
+        scale: the mean distance between the emotions' centroids of mu when emotions (one label id per path) are given and
+        hold two labels or more (`scale_kind` 'emotion_centroids'), else the mean distance between different clips' mu
+        ('clip_pairs'); None, and None on the relative values, when there is no pair or the scale is 0.  There are no
+        thresholds.  The wavs are sorted by length and run in ragged batches of at most batch_size; a clip and its
+        perturbed copies are encoded in batches of the same rows, so the identity perturbation gives exactly 0."""
+        import t2v_hip
+        paths = list(paths)
+        if not paths:
+            raise ValueError("latent_probe: no paths")
+        if self.model is None:
+            raise RuntimeError("latent_probe: no model (load_checkpoint() or load() first)")
+        if emotions is not None:
+            emotions = [int(e) for e in emotions]
+            if len(emotions) != len(paths):
+                raise ValueError("latent_probe: %d paths for %d emotion labels" % (len(paths), len(emotions)))
+        probes = [('pitch', float(v)) for v in pitch] + [('speed', float(v)) for v in speed] + [('gain_db', float(v)) for v in gain_db]
+        for kind, v in probes:                                            # refused before any work
+            if kind == 'pitch':
+                t2v_hip.pitch_ratio(v)
+            elif kind == 'speed':
+                t2v_hip.stretch_ratio(v)
+        N = len(paths)
+        base = [None] * N
+        dist = [[0.0] * N for _ in probes]
+        for idx in length_groups(self.wav_lengths(paths), batch_size):
+            y, n = self.load_wavs([paths[i] for i in idx])
+            mu = self.model.vae_gst(*self._mels_of(y, n))[1].double()
+            for b, i in enumerate(idx):
+                base[i] = mu[b].cpu().numpy()
+            for k, (kind, v) in enumerate(probes):
+                if kind == 'pitch':
+                    y2, n2 = t2v_hip.pitch_shift(y, n, v)
+                elif kind == 'speed':
+                    y2, n2 = t2v_hip.time_stretch(y, n, v)
+                else:
+                    y2, n2 = t2v_hip.scale_rows(y.clone(), n, [10.0 ** (v / 20.0)] * len(idx)), n
+                mu2 = self.model.vae_gst(*self._mels_of(y2, n2))[1].double()
+                d = (mu2 - mu).pow(2).sum(1).sqrt().cpu().tolist()
+                for b, i in enumerate(idx):
+                    dist[k][i] = d[b]
+        base = np.stack(base)
+
+        def mean_pair_distance(x):
+            if len(x) < 2:
+                return None
+            d = np.sqrt(((x[:, None, :] - x[None, :, :]) ** 2).sum(-1))
+            return float(d[np.triu_indices(len(x), 1)].mean())
+
+        scale, kind = None, 'clip_pairs'
+        if emotions is not None and len(set(emotions)) >= 2:
+            lab = np.asarray(emotions)
+            scale, kind = mean_pair_distance(np.stack([base[lab == c].mean(0) for c in sorted(set(emotions))])), 'emotion_centroids'
+        else:
+            scale = mean_pair_distance(base)
+        if scale is not None and not scale > 0.0:
+            scale = None
+        out = []
+        for (pk, v), d in zip(probes, dist):
+            mean, median = float(np.mean(d)), float(np.median(d))
+            out.append({'kind': pk, 'value': v, 'mean': mean, 'median': median,
+                        'mean_rel': mean / scale if scale else None, 'median_rel': median / scale if scale else None})
+        return {'n_clips': N, 'scale': scale, 'scale_kind': kind, 'perturbations': out}
+
     # ------------------------------------------------------------------ checkpoint + centroids (synthesizer.py:74-110)
     @staticmethod
     def centroid_cache_path(checkpoint_path, filelist_path):
@@ -331,7 +457,7 @@ class Synthesizer(object):
         position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
         (`latents`), when there is no centroid cache yet."""
         if isinstance(vocoder, str):
-            vocoder = GriffinLimVocoder.named(vocoder, self.stft)       # an unknown name fails before anything is loaded
+            vocoder = GriffinLimVocoder.named(vocoder, self.stft, self.speed, self.pitch_st)       # an unknown name fails before anything is loaded
         self.load_checkpoint(checkpoint_path)
         if callable(waveglow_path) and vocoder is None:
             vocoder, waveglow_path = waveglow_path, None
@@ -542,6 +668,9 @@ class Synthesizer(object):
         it gives every row mcd_db and warp_dev, None on the six F0 values, and needs no vocoder; with prosody=True the two
         pitch tracks computed there, cut to n_frames and n_ref_frames, feed the same call (a row decoded to fewer than the
         vocoder's 4 frames keeps None on its F0 values and still gets mcd_db).  It draws nothing and changes no other key.
+        With speed or pitch on the vocoder the synthesised waveform has its own frame count, (samples // hop + 1), and its pitch
+        and level tracks are taken over exactly those frames; aligned=True together with prosody or energy is then a ValueError,
+        since the warping path is over mel frames and the waveform's frames lie on another time axis.
         energy=True (needs the Griffin-Lim vocoder, like prosody) adds the level of both sides (evaluation.ENERGY_KEYS):
         `t2v_hip.loudness` on the same two waveforms as prosody=True, which it shares when both are on (the vocoder runs once,
         with the np.random draws of prosody=True; alone it draws what prosody=True would), one copy of the frame tracks to the
@@ -562,6 +691,12 @@ class Synthesizer(object):
             raise RuntimeError("evaluate(prosody=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
         if energy and not isinstance(self.vocoder, GriffinLimVocoder):
             raise RuntimeError("evaluate(energy=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
+        if aligned and (prosody or energy) and (self.vocoder.stretch[0] != self.vocoder.stretch[1]
+                                                or self.vocoder.shift[0] != self.vocoder.shift[1]):
+            # the warping path is over mel frames; a vocoder with speed or pitch puts the waveform's frames on another time axis
+            raise ValueError("evaluate(aligned=True) with prosody or energy compares tracks frame by frame along the mels' path, "
+                             "and the vocoder's speed %g / pitch %g put its waveform on another time axis: use one or the other"
+                             % (self.vocoder.speed, self.vocoder.pitch))
         if energy:
             t2v_hip.kweight_coefficients(self.hparams.sampling_rate)        # an unsupported rate is refused before any work
             if self.hparams.hop_length != t2v_hip.TRIM_HOP:
@@ -621,6 +756,8 @@ class Synthesizer(object):
                     y_syn = torch.zeros(len(can), max(w.numel() for w in wavs), device=mel.device)
                     for k, w in enumerate(wavs):
                         y_syn[k, :w.numel()] = w
+                    # the frames of each waveform's own tracks: n[b] without speed or pitch on the vocoder, else what it wrote
+                    syn_frames = [w.numel() // self.hparams.hop_length + 1 for w in wavs]
             if prosody:
                 # both sides' tracks side by side in one tensor: one copy to the host per group
                 tracks = [t2v_hip.f0(y_uniq, samples_uniq)]
@@ -629,7 +766,7 @@ class Synthesizer(object):
                 width = max(t.size(1) for t in tracks)
                 host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in tracks], 0).cpu().tolist()
                 for b in range(len(group)):
-                    syn_track = host[len(uniq) + can.index(b)][:n[b]] if b in can else None
+                    syn_track = host[len(uniq) + can.index(b)][:syn_frames[can.index(b)]] if b in can else None
                     records[i0 + b].update(prosody_fields(syn_track, host[which[b]][:n_ref[b]]))
             if energy:
                 loud = [t2v_hip.loudness(y_uniq, samples_uniq, self.hparams.sampling_rate)]
@@ -641,7 +778,7 @@ class Synthesizer(object):
                 for b in range(len(group)):
                     k = can.index(b) if b in can else None
                     records[i0 + b].update(energy_fields(loud[1].integrated[k] if k is not None else None,
-                                                         host[len(uniq) + k][:n[b]] if k is not None else None,
+                                                         host[len(uniq) + k][:syn_frames[k]] if k is not None else None,
                                                          loud[0].integrated[which[b]], host[which[b]][:n_ref[b]]))
             if aligned:
                 cep = t2v_hip.mel_cepstrum(mel_postnet, n)
@@ -767,7 +904,26 @@ def build_arg_parser():
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
+    add_tempo_arguments(p)
     return p
+
+
+def add_tempo_arguments(p):
+    """--speed and --pitch of the synthesis command lines: what the built-in vocoder writes (GriffinLimVocoder(speed=, pitch=))"""
+    p.add_argument('--speed', type=float, default=1.0, metavar='R',
+                   help="speaking rate of the built-in vocoder's output, 0.25..4 (default 1: unchanged)")
+    p.add_argument('--pitch', type=float, default=0.0, metavar='ST',
+                   help="pitch shift of the built-in vocoder's output in semitones, -12..12 (default 0: unchanged)")
+
+
+def tempo_options(args):
+    """the Synthesizer keywords of add_tempo_arguments' flags; SystemExit on a value out of range"""
+    import t2v_hip
+    try:
+        t2v_hip.vocoder_rates(args.speed, args.pitch)
+    except ValueError as e:
+        raise SystemExit("--speed / --pitch: %s" % e)
+    return {'speed': args.speed, 'pitch': args.pitch}
 
 
 def parse_args(argv=None):
@@ -785,6 +941,9 @@ def parse_args(argv=None):
     if not texts:
         raise SystemExit("no text: give --text and/or --text_file")
     args.texts = texts
+    if (args.speed != 1.0 or args.pitch != 0.0) and args.vocoder is None:
+        raise SystemExit("--speed / --pitch act in the built-in vocoder: give --vocoder")
+    tempo_options(args)
     return args
 
 
@@ -796,7 +955,7 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    syn = Synthesizer(hp, attention_window=args.attention_window, **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
+    syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
     os.makedirs(args.sample_path, exist_ok=True)
     texts = args.texts
     for i0 in range(0, len(texts), args.batch_size):

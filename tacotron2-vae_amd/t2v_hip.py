@@ -114,7 +114,8 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours',
            't2v_mel_cepstrum', 't2v_cep_dtw_scratch_bytes', 't2v_cep_dtw_path', 't2v_cep_dtw_forward', 't2v_cep_dtw_walk',
            't2v_path_scores', 't2v_loudness', 't2v_loudness_scratch_bytes', 't2v_scale_rows',
-           't2v_decoder_infer_steps_window', 't2v_decoder_infer_persistent_window')
+           't2v_decoder_infer_steps_window', 't2v_decoder_infer_persistent_window',
+           't2v_phase_vocoder', 't2v_phase_vocoder_scratch_bytes')
 
 
 def lib_path():
@@ -277,6 +278,9 @@ def load_library():
     lib.t2v_loudness_scratch_bytes.restype = C.c_size_t
     lib.t2v_loudness.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     lib.t2v_scale_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.t2v_phase_vocoder_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.t2v_phase_vocoder_scratch_bytes.restype = C.c_size_t
+    lib.t2v_phase_vocoder.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [vp, vp, C.c_int, vp, vp]
     lib.t2v_alignment_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_alignment_scratch_bytes.restype = C.c_size_t
     lib.t2v_alignment_stats.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp,
@@ -1994,6 +1998,175 @@ def resample(x, lengths, sr_in, sr_out):
     if max(n_out) < stride:
         y = y[:, :max(n_out)].contiguous()
     return y, n_out
+
+
+TSM_MAX_RATIO = 1023                    # T2V_TSM_MAX_RATIO of include/t2vae.h: the largest numerator and denominator of a rate
+TSM_MAX_FRAMES = 1 << 20                # T2V_TSM_MAX_FRAMES
+TSM_HOP = 256                           # the STFT's hop, a quarter of its window
+_TSM_TABLES = {}                        # device -> the STFT tables of time_stretch
+
+
+def _small_ratio(x):
+    """x > 0 as a fractions.Fraction with numerator and denominator in 1..TSM_MAX_RATIO: limit_denominator on x, or on 1 / x
+    where x's own numerator would come out larger"""
+    import fractions
+    f = fractions.Fraction(x if isinstance(x, (int, fractions.Fraction)) else float(x))
+    g = f.limit_denominator(TSM_MAX_RATIO)
+    if g.numerator > TSM_MAX_RATIO:
+        g = 1 / (1 / f).limit_denominator(TSM_MAX_RATIO)
+    return g
+
+
+def stretch_ratio(rate):
+    """(num, den) of a tempo rate (above 1: faster), both in 1..1023: fractions.Fraction(rate).limit_denominator(1023).
+    ValueError unless 0.25 <= rate <= 4."""
+    try:
+        ok = not isinstance(rate, bool) and 0.25 <= rate <= 4.0
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("stretch_ratio: the rate must be a number in 0.25..4, got %r" % (rate,))
+    g = _small_ratio(rate)
+    return g.numerator, g.denominator
+
+
+def pitch_ratio(semitones):
+    """(p, q) with p / q the frequency factor 2^(semitones / 12), both in 1..1023.  ValueError outside +-12 semitones."""
+    try:
+        ok = not isinstance(semitones, bool) and -12.0 <= semitones <= 12.0
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("pitch_ratio: the shift must be a number of semitones in -12..12, got %r" % (semitones,))
+    g = _small_ratio(2.0 ** (float(semitones) / 12.0))
+    return g.numerator, g.denominator
+
+
+def vocoder_rates(speed, pitch):
+    """((num, den), (p, q)) of GriffinLimVocoder(speed=, pitch=): p / q = 2^(pitch / 12), and num / den = speed q / p, the rate
+    at which the magnitudes are stretched so that resampling by p / q leaves the duration at 1 / speed.  ValueError when the
+    combined rate leaves 0.25..4."""
+    import fractions
+    p, q = pitch_ratio(pitch)
+    sn, sd = stretch_ratio(speed)
+    f = fractions.Fraction(sn * q, sd * p)
+    if not 0.25 <= f <= 4:
+        raise ValueError("speed %r with pitch %r stretches the spectrogram by %s, outside 0.25..4" % (speed, pitch, f))
+    g = _small_ratio(f)
+    return (g.numerator, g.denominator), (p, q)
+
+
+def _rate_pair(rate, who):
+    """a rate argument as (num, den): a number goes through stretch_ratio, a pair of integers in 1..1023 is taken as it is"""
+    if isinstance(rate, (tuple, list)):
+        if len(rate) != 2 or any(isinstance(v, bool) or int(v) != v or not 1 <= v <= TSM_MAX_RATIO for v in rate):
+            raise ValueError("%s: a rate given as a pair must be two integers in 1..%d, got %r" % (who, TSM_MAX_RATIO, rate))
+        return int(rate[0]), int(rate[1])
+    return stretch_ratio(rate)
+
+
+def stretch_frames(n, num, den):
+    """ceil(n den / num): the frames t2v_phase_vocoder gives for n at the rate num / den"""
+    return -((-int(n) * den) // num)
+
+
+def _tsm_launch(who, mag, phase, n_frames, rate, phase_lock):
+    lib = _require_gpu(mag) if phase is None else _require_gpu(mag, phase)
+    if mag.dim() != 3 or mag.size(1) != 513 or mag.dtype != torch.float32 or (phase is not None and (
+            phase.shape != mag.shape or phase.dtype != torch.float32)):
+        raise ValueError("%s: magnitude%s must be float32 (B, 513, T)" % (who, "" if phase is None else " and phase"))
+    B, _, stride = mag.shape
+    if B < 1 or stride < 1:
+        raise ValueError("%s: empty input %s" % (who, tuple(mag.shape)))
+    num, den = _rate_pair(rate, who)
+    msg = "%s: every row needs 1 <= frames <= %d" % (who, stride)
+    n = _checked_lengths(n_frames, B, 1, stride, msg, msg, reject_float=False, reject_bool=False, default=stride)
+    T = int(n.max())
+    if T > TSM_MAX_FRAMES:
+        raise ValueError("%s: rows of %d frames exceed the %d supported" % (who, T, TSM_MAX_FRAMES))
+    n_out = [stretch_frames(k, num, den) for k in n.tolist()]
+    out_stride = max(n_out)
+    mag = mag.contiguous()
+    mag_out = torch.empty(B, 513, out_stride, device=mag.device, dtype=torch.float32)
+    phase_out = scratch = None
+    if phase is not None:
+        phase = phase.contiguous()
+        phase_out = torch.empty_like(mag_out)
+        if phase_lock:
+            scratch = torch.empty(int(lib.t2v_phase_vocoder_scratch_bytes(B, out_stride, 1)), device=mag.device, dtype=torch.uint8)
+    _check(lib.t2v_phase_vocoder(_p(mag), None if phase is None else _p(phase), _p(n.to(mag.device)), B, T, stride, num, den,
+                                 int(bool(phase_lock)), _p(mag_out), None if phase is None else _p(phase_out), out_stride,
+                                 None if scratch is None else _p(scratch), _stream()), 't2v_phase_vocoder')
+    return mag_out, phase_out, n_out
+
+
+def phase_vocoder(mag, phase, n_frames, rate, phase_lock=True):
+    """Time-scale modification of polar spectrograms (csrc/tsm.hip k_pv_scan, k_pv_lock): mag, phase (B, 513, T) float32 CUDA
+    tensors as `stft_polar` gives them, row b of n_frames[b] frames (a list, a CPU or a device tensor; None: all T); frames at
+    and past a row's count are not read.  rate: a number in 0.25..4 (`stretch_ratio`; above 1 is faster) or a pair (num, den).
+    Returns (mag_out, phase_out (B, 513, max n_out), n_out: the host list of ceil(n_frames[b] den / num)), both 0 past each
+    n_out.  What is computed is librosa.effects.time_stretch's phase vocoder with exact frame positions (include/t2vae.h); the
+    phases come modulo 2 pi, from a prefix sum in 32-bit fixed point.  phase_lock: identity phase locking to the peaks of each
+    analysis frame.  A row gives the same bits alone, in any batch and at any stride."""
+    return _tsm_launch("phase_vocoder", mag, phase, n_frames, rate, phase_lock)
+
+
+def stretch_magnitude(mag, n_frames, rate):
+    """The magnitude half of `phase_vocoder` alone, for a caller that makes its own phases (Griffin-Lim): returns
+    (mag_out (B, 513, max n_out), n_out)."""
+    mag_out, _, n_out = _tsm_launch("stretch_magnitude", mag, None, n_frames, rate, False)
+    return mag_out, n_out
+
+
+def _tsm_tables(device):
+    t = _TSM_TABLES.get(device)
+    if t is None:
+        from stft import fft_tables
+        t = _TSM_TABLES[device] = {k: torch.from_numpy(v).to(device) for k, v in fft_tables(1024).items()}
+    return t
+
+
+def time_stretch(y, lengths, rate, phase_lock=True):
+    """Change the tempo of waveforms and keep their pitch: y (B, S) float32 CUDA tensor, row b of lengths[b] samples, every one
+    more than 512 (`stft_polar`'s ValueError otherwise).  Exactly `stft_polar` -> `phase_vocoder` -> `istft` with the tables
+    of stft.STFT.  Returns (y_out (B, max n_out) float32, n_out: the host list of min((T_out[b] - 1) 256, ceil(lengths[b] den /
+    num)), T_out[b] the row's stretched frame count); y_out is 0 past each n_out.  A rate of 1 launches nothing and returns
+    the input."""
+    _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("time_stretch: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("time_stretch: empty input %s" % (tuple(y.shape),))
+    num, den = _rate_pair(rate, "time_stretch")
+    n = _wave_lengths(lengths, B, S, "time_stretch")
+    if num == den:
+        return y, n.tolist()
+    tables = _tsm_tables(y.device)
+    mag, phase = stft_polar(y, n.to(torch.int64), tables)            # the transform reads 64-bit counts
+    frames = [k // TSM_HOP + 1 for k in n.tolist()]
+    for b, f in enumerate(frames):
+        if stretch_frames(f, num, den) < 2:
+            raise ValueError("time_stretch: row %d has %d frames, fewer than 2 at the rate %d/%d" % (b, f, num, den))
+    mag, phase, t_out = phase_vocoder(mag, phase, frames, (num, den), phase_lock)
+    y_out = istft(mag, phase, t_out, tables)
+    n_out = [min((t - 1) * TSM_HOP, stretch_frames(k, num, den)) for t, k in zip(t_out, n.tolist())]
+    # istft is 0 past (t_out - 1) 256 samples; what lies between a row's n_out and that is cut here
+    y_out.masked_fill_(torch.arange(y_out.size(1), device=y.device)[None, :] >= torch.tensor(n_out, device=y.device)[:, None], 0.0)
+    if max(n_out) < y_out.size(1):
+        y_out = y_out[:, :max(n_out)].contiguous()
+    return y_out, n_out
+
+
+def pitch_shift(y, lengths, semitones, phase_lock=True):
+    """Change the pitch of waveforms by `semitones` (-12..12) and keep their duration to within a frame: `time_stretch` by q / p,
+    then `resample` by p / q read backwards (p / q = 2^(semitones / 12), `pitch_ratio`).  Returns (y_out, n_out) as `resample`
+    does.  0 semitones returns the input."""
+    p, q = pitch_ratio(semitones)
+    if p == q:
+        return time_stretch(y, lengths, (1, 1))                         # its checks, no launch
+    stretched, n = time_stretch(y, lengths, (q, p), phase_lock)
+    return resample(stretched, n, p, q)
 
 
 def trim_bounds(y, lengths, top_db=40.0, pad_frames=2):
