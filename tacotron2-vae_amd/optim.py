@@ -142,7 +142,11 @@ class FlatAdam(object):
         self._gathered = False
         g = self.param_groups[0]
         # a live parameter without a gradient is skipped by torch.optim.Adam (no weight decay, no moment decay, no
-        # step); the fused kernel updates the whole arena, so such slots are put back afterwards (rare: partial freezing)
+        # step); the fused kernel updates the whole arena, so such slots are put back afterwards (rare: partial freezing).
+        # DEVIATION from torch: there is ONE global step count.  torch.optim.Adam counts steps per parameter, so after a
+        # skipped step that parameter's bias corrections lag by one there; here they follow the global count (and
+        # load_state_dict refuses a state whose per-parameter counts differ).  tests/test_optim_gpu.py pins this down
+        # against tests/adam_ref.flat_adam_ref, not against torch.
         skipped = [(self._slot_of[id(p)],) for p in self._no_grad]
         saved = [(o, n, self.params[o:o + n].clone(), self.exp_avg[o:o + n].clone(), self.exp_avg_sq[o:o + n].clone())
                  for ((o, n),) in skipped]
@@ -158,6 +162,7 @@ class FlatAdam(object):
         rc = lib.t2v_clip_adam_step_guarded(
             C.c_void_p(self.params.data_ptr()), C.c_void_p(self.grads.data_ptr()),
             C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
+            # (the betas go in as floats: the step runs at their fp32 neighbours, 1 - beta2 = 0.00099998713 for 0.999; DESIGN a-20)
             C.c_uint64(self.numel), C.c_float(g['lr']), C.c_float(g['betas'][0]), C.c_float(g['betas'][1]),
             C.c_float(g['eps']), C.c_float(g['weight_decay']),
             C.c_float(self.grad_clip_thresh if self.grad_clip_thresh else 0.0),
