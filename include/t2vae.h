@@ -1032,6 +1032,32 @@ size_t t2v_phase_vocoder_scratch_bytes(int B, int out_stride, int phase_lock);
 int t2v_phase_vocoder(const float* mag, const float* phase, const int32_t* n_frames, int B, int T, int t_stride, int num, int den,
                       int phase_lock, float* mag_out, float* phase_out, int out_stride, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------ spectral envelope: pitch and timbre as two knobs
+ * The true-envelope estimate of a ragged batch of STFT magnitudes, and the spectrum with its envelope moved along frequency
+ * (csrc/envelope.hip, one launch).  mag is (B, 513, t_stride) fp32 as t2v_stft_polar writes it, row b has n_frames[b] frames
+ * (device int32, clamped to 0..T; T <= t_stride is the most any row has); nothing at or past frame n_frames[b] is read.
+ * Per frame, m[k] its 513 magnitudes:
+ *   floor = max(1e-7f * max_k m[k], 1e-10f) (the max is exact in fp32),  L[k] = log(max(m[k], floor)).
+ *   lifter(x), order 1..T2V_ENV_MAX_ORDER: x[0..512] is even-extended to 1024 points (x[1024 - k] = x[k]); its DFT / 1024 is
+ *     the real cepstrum c[n]; c[n] is kept for n <= order and n >= 1024 - order and zeroed elsewhere; the DFT of that, real
+ *     part of bins 0..512, is the result.  Both are the same forward real 1024-point FFT of a real even sequence; imaginary
+ *     parts are dropped.
+ *   True envelope (Roebel and Rodet), a fixed count iters in 0..T2V_ENV_MAX_ITERS: A = L; iters + 1 times E = lifter(A),
+ *     A = max(L, E).  The result is the last E, a natural-log envelope; iters = 0 is the plain cepstral envelope.  There is
+ *     no convergence test: a frame's bits depend on that frame alone, whatever the batch and the strides.
+ *   Warp by p / q, each in 1..T2V_TSM_MAX_RATIO, positions in integers: pos = k p, i = pos / q, a = (pos % q) / q,
+ *     Ew[k] = (1 - a) E[i] + a E[i + 1], and Ew[k] = E[512] for i >= 512;  mag_out[k] = m[k] exp(Ew[k] - E[k]): the envelope
+ *     read at k p / q, so it moves along frequency by q / p, and the fine structure stays.  p == q gives m[k], bit for bit.
+ * log_env_out and mag_out are (B, 513, out_stride), either may be NULL; both are +0 from n_frames[b] to out_stride.  The
+ * library keeps no scratch and reads no table.
+ * order, iters, p or q out of range, B < 1, T outside 1..T2V_TSM_MAX_FRAMES or more than 2^31 - 1 workgroups is T2V_ERR_DIMS;
+ * a null mag or n_frames, both outputs NULL, or a stride below T (or above 2^30) is T2V_ERR_ARG. */
+#define T2V_ENV_BINS 513
+#define T2V_ENV_MAX_ORDER 256
+#define T2V_ENV_MAX_ITERS 32
+int t2v_spectral_envelope(const float* mag, const int32_t* n_frames, int B, int T, int t_stride, int order, int iters, int p, int q,
+                          float* log_env_out, float* mag_out, int out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,31 +121,7 @@ __global__ __launch_bounds__(256, FE_WAVES_PER_EU) void k_mel_frontend(FrontendA
             v[k] = {s[0], s[1]};
         }
         // ---- 512-point complex FFT, Stockham radix-8: pass Ns = 1, 8, 64 (thread j = lane)
-        dft8(v);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) z[lane * 8 + r] = v[r];            // j0 = j*8, stride Ns = 1
-        // pass 2: Ns = 8
-        {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = z[lane + 64 * r];
-            const int k = lane & 7;
-#pragma unroll
-            for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], a.tw512[8 * k * r]);     // W_64^{k r}
-            dft8(v);
-            const int j0 = (lane >> 3) * 64 + k;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) z[j0 + 8 * r] = v[r];
-        }
-        // pass 3: Ns = 64
-        {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = z[lane + 64 * r];
-#pragma unroll
-            for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], a.tw512[lane * r]);      // W_512^{k r}
-            dft8(v);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) z[lane + 64 * r] = v[r];
-        }
+        fft512(v, z, a.tw512, lane);
         // ---- untangle to the real spectrum X[k], k = 0..512, magnitude
         // (eight bins per lane in two unrolled groups of four: the LDS reads and twiddle loads of a group are in flight together —
         // all eight at once cost 28 more registers and a wave per SIMD; bin 512 by lane 0)

@@ -1,4 +1,5 @@
-// Complex helpers and the in-register 8-point DFT shared by the STFT kernels (frontend.hip, vocoder.hip).
+// Complex helpers, the in-register 8-point DFT and the packed 512-point FFT of a real 1024-point frame, shared by the STFT
+// kernels (frontend.hip, vocoder.hip) and the spectral envelope (envelope.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,4 +25,46 @@ __device__ __forceinline__ void dft8(c32* v) {
     v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
     v[1] = cadd(b1, t5); v[5] = csub(b1, t5);
     v[3] = cadd(b3, t7); v[7] = csub(b3, t7);
+}
+
+// 512-point complex FFT of one wave's packed frame: v[r] holds point lane + 64 r on entry; z (LDS, 512) holds the
+// spectrum in natural order on exit (three radix-8 Stockham passes, Ns = 1, 8, 64; thread j = lane)
+__device__ __forceinline__ void fft512(c32* v, c32* z, const c32* tw512, int lane) {
+    dft8(v);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) z[lane * 8 + r] = v[r];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = z[lane + 64 * r];
+    const int k = lane & 7;
+#pragma unroll
+    for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], tw512[8 * k * r]);
+    dft8(v);
+    const int j0 = (lane >> 3) * 64 + k;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) z[j0 + 8 * r] = v[r];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = z[lane + 64 * r];
+#pragma unroll
+    for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], tw512[lane * r]);
+    dft8(v);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) z[lane + 64 * r] = v[r];
+}
+
+// real spectrum bins k and 512 - k from the packed FFT Z: X[k] = E - i W^k O, X[512-k] = conj(E) - i conj(W^k O)
+__device__ __forceinline__ void untangle(c32 zk, c32 zc, c32 w, c32& xk, c32& xc) {
+    const c32 e = {0.5f * (zk.x + zc.x), 0.5f * (zk.y - zc.y)};
+    const c32 o = {0.5f * (zk.x - zc.x), 0.5f * (zk.y + zc.y)};
+    const c32 wo = cmul(w, o);
+    xk = {e.x + wo.y, e.y - wo.x};
+    xc = {e.x - wo.y, -e.y - wo.x};
+}
+
+// the inverse: packed Z[k] and Z[512-k] from Y[k], Y[512-k] (Fe = (Y + conj Yc)/2, Fo = (Y - conj Yc)/2 conj(W^k), Z = Fe + i Fo)
+__device__ __forceinline__ void retangle(c32 yk, c32 yc, c32 w, c32& zk, c32& zc) {
+    const c32 fe = {0.5f * (yk.x + yc.x), 0.5f * (yk.y - yc.y)};
+    const c32 d = {0.5f * (yk.x - yc.x), 0.5f * (yk.y + yc.y)};
+    const c32 fo = cmul(d, c32{w.x, -w.y});
+    zk = {fe.x - fo.y, fe.y + fo.x};
+    zc = {fe.x + fo.y, -fe.y + fo.x};       // conj(Fe) + i conj(Fo)
 }

@@ -27,48 +27,6 @@
 
 namespace {
 
-// 512-point complex FFT of one wave's packed frame: v[r] holds point lane + 64 r on entry; z (LDS, 512) holds the
-// spectrum in natural order on exit (the front end's three radix-8 Stockham passes, frontend.hip)
-__device__ __forceinline__ void fft512(c32* v, c32* z, const c32* tw512, int lane) {
-    dft8(v);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) z[lane * 8 + r] = v[r];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = z[lane + 64 * r];
-    const int k = lane & 7;
-#pragma unroll
-    for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], tw512[8 * k * r]);
-    dft8(v);
-    const int j0 = (lane >> 3) * 64 + k;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) z[j0 + 8 * r] = v[r];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = z[lane + 64 * r];
-#pragma unroll
-    for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], tw512[lane * r]);
-    dft8(v);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) z[lane + 64 * r] = v[r];
-}
-
-// real spectrum bins k and 512 - k from the packed FFT Z: X[k] = E - i W^k O, X[512-k] = conj(E) - i conj(W^k O)
-__device__ __forceinline__ void untangle(c32 zk, c32 zc, c32 w, c32& xk, c32& xc) {
-    const c32 e = {0.5f * (zk.x + zc.x), 0.5f * (zk.y - zc.y)};
-    const c32 o = {0.5f * (zk.x - zc.x), 0.5f * (zk.y + zc.y)};
-    const c32 wo = cmul(w, o);
-    xk = {e.x + wo.y, e.y - wo.x};
-    xc = {e.x - wo.y, -e.y - wo.x};
-}
-
-// the inverse: packed Z[k] and Z[512-k] from Y[k], Y[512-k] (Fe = (Y + conj Yc)/2, Fo = (Y - conj Yc)/2 conj(W^k), Z = Fe + i Fo)
-__device__ __forceinline__ void retangle(c32 yk, c32 yc, c32 w, c32& zk, c32& zc) {
-    const c32 fe = {0.5f * (yk.x + yc.x), 0.5f * (yk.y - yc.y)};
-    const c32 d = {0.5f * (yk.x - yc.x), 0.5f * (yk.y + yc.y)};
-    const c32 fo = cmul(d, c32{w.x, -w.y});
-    zk = {fe.x - fo.y, fe.y + fo.x};
-    zc = {fe.x + fo.y, -fe.y + fo.x};       // conj(Fe) + i conj(Fo)
-}
-
 // M times the unit phasor of X; (M, 0) where |X| = 0, as cos/sin of atan2(0, 0) = 0
 __device__ __forceinline__ c32 with_magnitude(c32 x, float m) {
     const float r2 = x.x * x.x + x.y * x.y;

@@ -4,6 +4,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
                        [--style [--style_k K]] [--aligned] [--energy] [--attention_window BACK,AHEAD] [--speed R] [--pitch ST]
+                       [--formant ST] [--preserve_formants]
                        [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
@@ -76,7 +77,11 @@ DESIGN 7o): the waveforms that --prosody and --energy measure are the ones the s
 same flags, and their pitch and level tracks run over those waveforms' own frames (ceil(n_frames / speed) of them, not
 n_frames).  The mels, and with them dtw and every score taken of mels, do not change.  --aligned together with --prosody or
 --energy is refused with them: the warping path is over mel frames, and the waveform's frames lie on another time axis.
-OUT.json always holds "speed" and "pitch" (1.0 and 0.0 without the flags)."""
+OUT.json always holds "speed" and "pitch" (1.0 and 0.0 without the flags).
+
+--formant ST and --preserve_formants act in the same vocoder leg (`GriffinLimVocoder(formant=, preserve_formants=)`, DESIGN
+7p): the spectral envelope of the waveform moves by ST semitones with the harmonics in place, and --pitch moves F0 alone.
+OUT.json holds "formant" and "preserve_formants" only when one of the two flags is given."""
 import argparse
 import json
 
@@ -137,6 +142,8 @@ def parse_args(argv=None):
     if args.aligned and (args.prosody or args.energy) and (args.speed != 1.0 or args.pitch != 0.0):
         raise SystemExit("--aligned with --prosody / --energy scores tracks along the mels' warping path; with --speed / --pitch "
                          "the waveform is on another time axis: drop --aligned or the two flags")
+    from synthesizer import tempo_options
+    tempo_options(args)                                                   # a value out of range is refused here
     return args
 
 
@@ -172,16 +179,19 @@ def main(argv=None):
     else:
         syn.load_checkpoint(args.load_path)
         if args.prosody or args.energy:
-            syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft, syn.speed, syn.pitch_st)
+            syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft, syn.speed, syn.pitch_st, syn.formant, syn.preserve_formants)
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
                            aligned=args.aligned, energy=args.energy, **style)
     summary = summarize(records)
+    formant_keys = {}
+    if args.formant != 0.0 or args.preserve_formants:                     # the report gains its new keys only with a new flag
+        formant_keys = {'formant': syn.formant, 'preserve_formants': syn.preserve_formants}
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)],
                    'attention_window': None if syn.attention_window is None else list(syn.attention_window),
-                   'speed': syn.speed, 'pitch': syn.pitch_st}, f, indent=1)
+                   'speed': syn.speed, 'pitch': syn.pitch_st, **formant_keys}, f, indent=1)
     print(json.dumps(summary, indent=1))
     if args.alignment:
         for name, st in summary['by_emotion'].items():

@@ -3,7 +3,7 @@
 latent_map.py's (or --tsne here).
 
     python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...] [--tsne [KEY]]
-                              [--scores [KEY]] [--probe OUT.json]
+                              [--scores [KEY]] [--probe OUT.json [--probe_formant ST,...] [--probe_preserve_formants]]
 
 Filelist rows are `path|text|speaker|emotion`.  OUT.npz holds, row i for filelist row i: prosody (N, E), mus, logvars,
 zs (N, z_latent_dim), emotions (N,) int and paths (N,) str.  The wavs run through `Synthesizer.latents`: sorted by
@@ -13,7 +13,9 @@ map of that array by latent_map.compute_map with its defaults, and tsne_kl; with
 dimension) for that array as a JSON string; without it the file is what it always was.
 --probe OUT.json also writes the latent probe (`Synthesizer.latent_probe` with its defaults): how far mu moves when
 a clip's pitch, tempo or level alone is changed, against the distance between the emotions' centroids; OUT.npz is not
-changed by it.
+changed by it.  --probe_formant ST,... adds entries of kind 'formant', the spectral envelope alone moved by those semitones,
+and --probe_preserve_formants makes the pitch entries move F0 alone: the plain pitch shift moves the formants
+too, so only with it does the table tell pitch from timbre.  Both need --probe.
 """
 import argparse
 
@@ -35,15 +37,31 @@ def build_arg_parser():
                    help="also store the latent_report.py scores of this array (default mus) as a JSON string under scores")
     p.add_argument('--probe', default=None, metavar='OUT.json',
                    help="also write the latent probe: mean and median move of mu under single pitch, tempo and level changes")
+    p.add_argument('--probe_formant', default=[], type=_semitone_list, metavar='ST,...',
+                   help="with --probe: also shift the formants alone by these semitones (each in -12..12), entries of kind 'formant'")
+    p.add_argument('--probe_preserve_formants', action='store_true',
+                   help="with --probe: the pitch entries keep the formants in place (F0 alone)")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
     return p
+
+
+def _semitone_list(text):
+    try:
+        values = [float(x) for x in text.split(',')]
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is not a comma separated list of numbers" % (text,))
+    if not values or any(not -12.0 <= v <= 12.0 for v in values):
+        raise argparse.ArgumentTypeError("semitones must lie in -12..12, got %r" % (text,))
+    return values
 
 
 def parse_args(argv=None):
     args = build_arg_parser().parse_args(argv)
     if args.batch_size < 1:
         raise SystemExit("--batch_size must be >= 1")
+    if (args.probe_formant or args.probe_preserve_formants) and not args.probe:
+        raise SystemExit("--probe_formant / --probe_preserve_formants change the latent probe: give --probe")
     return args
 
 
@@ -86,7 +104,8 @@ def main(argv=None):
     np.savez(args.out, **out)
     if args.probe:
         import json
-        probe = syn.latent_probe(paths, emotions.tolist(), batch_size=args.batch_size)
+        probe = syn.latent_probe(paths, emotions.tolist(), batch_size=args.batch_size, formant=args.probe_formant,
+                                 preserve_formants=args.probe_preserve_formants)
         with open(args.probe, 'w', encoding='utf-8') as f:
             json.dump(probe, f, indent=1)
         for r in probe['perturbations']:

@@ -5,7 +5,7 @@ trim_bounds, crop; csrc/resample.hip).
     python prepare_corpus.py --filelist_path F --out_dir D --out_filelist F2
            [--sampling_rate 16000] [--trim_db 40 | --no_trim] [--pad_frames 2] [--batch_size 64] [--report R.json]
            [--lufs TARGET [--lufs_scope utterance|speaker] [--peak_db -1.0]]
-           [--speed_perturb 0.9,1.1] [--pitch_perturb -1,1]
+           [--speed_perturb 0.9,1.1] [--pitch_perturb -1,1] [--formant_perturb -1,1] [--preserve_formants]
 
 Filelist rows are `path|text|speaker|emotion` (any column count, the path first).  Each wav is read as it lies in the file
 (int16 goes to the device as it is; int32 and float wavs are scaled to [-1, 1) on the host; a wav with more than one channel
@@ -34,7 +34,14 @@ and the 16-bit write-out.  A copy is written as D/<stem>_sp0.90.wav / D/<stem>_p
 with the row's other columns.  With --lufs every copy gets its own gain, or its speaker's, lowered where the copy's own peak would pass --peak_db.  The row's record in the report
 gains `perturbed`: per copy kind ('speed' or 'pitch'), value, out_path, samples_out, peak, clipped_samples (and the loudness
 fields); a row of 512 samples or fewer after the trim has no copies and says so in `perturb_skipped`.  The unperturbed row is
-written exactly as without the flags."""
+written exactly as without the flags.
+
+--formant_perturb ST,... adds copies with the spectral envelope, the formants, moved by ST semitones and the harmonics in
+place (t2v_hip.formant_shift, csrc/envelope.hip), written as D/<stem>_fs-1.wav behind the pitch copies, kind
+'formant' in the report: a change of vocal-tract length, another voice at the same pitch.  --preserve_formants makes the
+--pitch_perturb copies move F0 alone (t2v_hip.pitch_shift(preserve_formants=True)); without it a pitch copy's formants move
+with its pitch, so the speaker drifts with the shift.  The report's `perturbations` gains `formant` and `preserve_formants`
+only when one of the two flags is given."""
 import argparse
 import json
 import math
@@ -71,6 +78,11 @@ def build_arg_parser():
     p.add_argument('--pitch_perturb', type=parse_pitch_list, default=[], metavar='ST,...',
                    help="also write a copy of every wav shifted by each of these semitone counts (-12..12, not 0); a list that starts "
                         "with a minus sign may also be written --pitch_perturb=-1,1; off by default")
+    p.add_argument('--formant_perturb', type=parse_formant_list, default=[], metavar='ST,...',
+                   help="also write a copy of every wav with its formants moved by each of these semitone counts (-12..12, not 0) "
+                        "and its pitch kept; off by default")
+    p.add_argument('--preserve_formants', action='store_true',
+                   help="the --pitch_perturb copies keep their formants in place (F0 alone moves); off by default")
     return p
 
 
@@ -97,22 +109,27 @@ def parse_pitch_list(text):
     return _number_list(text, '--pitch_perturb', 'pitch_ratio', 0.0)
 
 
+def parse_formant_list(text):
+    """'-1,1' -> [-1.0, 1.0]: semitones in -12..12, distinct, none of them 0"""
+    return _number_list(text, '--formant_perturb', 'pitch_ratio', 0.0)
+
+
 def perturbed_name(name, kind, value):
     """the file name of a perturbed copy of <stem>.wav: <stem>_sp0.90.wav for a tempo rate, <stem>_ps-1.wav / <stem>_ps1.5.wav
-    for a pitch shift in semitones"""
+    for a pitch shift in semitones, <stem>_fs-1.wav for a formant shift"""
     stem = name[:-4] if name.lower().endswith('.wav') else name
     if kind == 'speed':
         return "%s_sp%.2f.wav" % (stem, value)
-    if kind == 'pitch':
-        return "%s_ps%s.wav" % (stem, "%d" % value if float(value) == int(value) else "%g" % value)
-    raise ValueError("perturbed_name: kind must be 'speed' or 'pitch', got %r" % (kind,))
+    if kind in ('pitch', 'formant'):
+        return "%s_%s%s.wav" % (stem, 'ps' if kind == 'pitch' else 'fs', "%d" % value if float(value) == int(value) else "%g" % value)
+    raise ValueError("perturbed_name: kind must be 'speed', 'pitch' or 'formant', got %r" % (kind,))
 
 
 def parse_args(argv=None):
     import sys
     argv = list(sys.argv[1:] if argv is None else argv)
     for k in range(len(argv) - 2, -1, -1):    # "--pitch_perturb -1,1": argparse takes a list that starts with '-' for a flag
-        if argv[k] in ('--pitch_perturb', '--speed_perturb') and argv[k + 1][:1] == '-' and argv[k + 1][1:2].isdigit():
+        if argv[k] in ('--pitch_perturb', '--speed_perturb', '--formant_perturb') and argv[k + 1][:1] == '-' and argv[k + 1][1:2].isdigit():
             argv[k:k + 2] = [argv[k] + '=' + argv[k + 1]]
     args = build_arg_parser().parse_args(argv)
     if args.batch_size < 1:
@@ -128,8 +145,12 @@ def parse_args(argv=None):
     if args.lufs is not None and not math.isfinite(args.lufs):
         raise SystemExit("--lufs must be a finite level in LUFS")
     tags = [perturbed_name('x.wav', 'speed', v) for v in args.speed_perturb] + [perturbed_name('x.wav', 'pitch', v) for v in args.pitch_perturb]
+    tags += [perturbed_name('x.wav', 'formant', v) for v in args.formant_perturb]
     if len(set(tags)) != len(tags):
-        raise SystemExit("--speed_perturb / --pitch_perturb: two values give one file name (%s)" % ', '.join(sorted(tags)))
+        raise SystemExit("--speed_perturb / --pitch_perturb / --formant_perturb: two values give one file name (%s)"
+                         % ', '.join(sorted(tags)))
+    if args.preserve_formants and not args.pitch_perturb:
+        raise SystemExit("--preserve_formants changes the --pitch_perturb copies: give --pitch_perturb")
     if args.report is None:
         args.report = os.path.join(args.out_dir, 'report.json')
     return args
@@ -326,9 +347,10 @@ def process_batch_lufs(items, target_rate, trim_db, pad_frames, target, peak_db,
 PERTURB_MIN_SAMPLES = 513                # the phase vocoder's transform reflect-pads by 512
 
 
-def process_batch_perturbed(front, target_rate, variants, target=None, peak_db=DEFAULT_PEAK_DB, gains=None):
+def process_batch_perturbed(front, target_rate, variants, target=None, peak_db=DEFAULT_PEAK_DB, gains=None, preserve_formants=False):
     """The perturbed copies of one ragged batch, from the front_end result the plain rows were written from: crop (fp32), then
-    per variant (kind, value) time_stretch or pitch_shift of the rows that are long enough, with a target the level
+    per variant (kind, value) time_stretch, pitch_shift (with preserve_formants: F0 alone) or formant_shift of the rows that are
+    long enough, with a target the level
     normalisation of process_batch_lufs, and the crop to int16.  gains: None for each copy's own, or one (gain_db, limited) per
     item, the speaker's; that gain was limited by the peaks of the unperturbed rows, and a copy may overshoot them, so it is
     lowered for a copy whose own peak it would lift above peak_db (`gain_limited` on that copy).  Returns per item None (512
@@ -348,8 +370,10 @@ def process_batch_perturbed(front, target_rate, variants, target=None, peak_db=D
     for kind, value in variants:
         if kind == 'speed':
             z, m = t2v_hip.time_stretch(y, counts, value)
+        elif kind == 'formant':
+            z, m = t2v_hip.formant_shift(y, counts, value)
         else:
-            z, m = t2v_hip.pitch_shift(y, counts, value)
+            z, m = t2v_hip.pitch_shift(y, counts, value, preserve_formants=preserve_formants)
         extra = [{} for _ in can]
         if target is not None:
             z = z.clone() if z is y else z
@@ -411,6 +435,7 @@ def main(argv=None):
     new_paths = [None] * len(rows)
     trim_db = None if args.no_trim else args.trim_db
     variants = [('speed', v) for v in args.speed_perturb] + [('pitch', v) for v in args.pitch_perturb]
+    variants += [('formant', v) for v in args.formant_perturb]
     copies = [[] for _ in rows]                                          # the perturbed copies' paths, per row
 
     def batches():
@@ -448,7 +473,7 @@ def main(argv=None):
             records[i] = dict(rec, path=rows[i][0], out_path=new_paths[i])
         if variants:
             done = process_batch_perturbed(front, args.sampling_rate, variants, args.lufs, args.peak_db,
-                                           gains if args.lufs is not None else None)
+                                           gains if args.lufs is not None else None, args.preserve_formants)
             for i, made in zip(group, done):
                 records[i]['perturbed'] = []
                 if made is None:
@@ -470,6 +495,8 @@ def main(argv=None):
     if variants:
         report['perturbations'] = dict(speed=args.speed_perturb, pitch=args.pitch_perturb,
                                        n_written=sum(len(c) for c in copies))
+        if args.formant_perturb or args.preserve_formants:
+            report['perturbations'].update(formant=args.formant_perturb, preserve_formants=args.preserve_formants)
     if args.lufs is not None:
         report['loudness'] = dict(loudness_totals(records), target_lufs=args.lufs, scope=args.lufs_scope, peak_db=args.peak_db)
         if speakers is not None:

@@ -77,24 +77,32 @@ class GriffinLimVocoder(object):
     the linear magnitudes are stretched in time by speed q / p (`t2v_hip.stretch_magnitude`; Griffin-Lim makes the phases, so
     no phase vocoder is needed), Griffin-Lim runs on the stretched frames (at least 4 per row), and its waveform is resampled
     by p / q (`t2v_hip.resample`), which brings the duration back to 1 / speed and moves every frequency by p / q.  The
-    initial phases are then drawn for the stretched frame counts.  speed=1, pitch=0 is the vocoder without them."""
+    initial phases are then drawn for the stretched frame counts.  speed=1, pitch=0 is the vocoder without them.
+    formant (semitones, -12..12) moves the spectral envelope of the output up by 2^(formant / 12) and leaves the harmonics;
+    preserve_formants keeps the envelope where it was under `pitch`, which alone moves it with the harmonics.  Both are one
+    `t2v_hip.warp_envelope` of the linear magnitudes, before the stretch, by the ratio of `t2v_hip.vocoder_warp` (DESIGN 7p);
+    formant=0, preserve_formants=False is the vocoder without them."""
 
-    def __init__(self, stft, n_iters=60, momentum=0.0, inversion='pinv', inversion_iters=100, speed=1.0, pitch=0.0):
-        from t2v_hip import check_momentum, vocoder_rates
+    def __init__(self, stft, n_iters=60, momentum=0.0, inversion='pinv', inversion_iters=100, speed=1.0, pitch=0.0, formant=0.0,
+                 preserve_formants=False):
+        from t2v_hip import check_momentum, vocoder_rates, vocoder_warp
         if inversion not in ('pinv', 'nnls'):
             raise ValueError("GriffinLimVocoder: inversion must be 'pinv' or 'nnls', got %r" % (inversion,))
         self.stft, self.n_iters = stft, n_iters
         self.momentum, self.inversion, self.inversion_iters = check_momentum(momentum), inversion, inversion_iters
         self.speed, self.pitch = float(speed), float(pitch)
         self.stretch, self.shift = vocoder_rates(speed, pitch)      # (num, den) of the magnitudes' rate, (p, q) of the pitch
+        self.warp = vocoder_warp(pitch, formant, preserve_formants)  # (a, b): the envelope is read at k a / b
+        self.formant, self.preserve_formants = float(formant), bool(preserve_formants)
 
     @classmethod
-    def named(cls, name, stft, speed=1.0, pitch=0.0):
+    def named(cls, name, stft, speed=1.0, pitch=0.0, formant=0.0, preserve_formants=False):
         """the vocoder behind load(vocoder=name) and the command lines' --vocoder"""
+        knobs = dict(speed=speed, pitch=pitch, formant=formant, preserve_formants=preserve_formants)
         if name == 'griffin_lim':
-            return cls(stft, speed=speed, pitch=pitch)
+            return cls(stft, **knobs)
         if name == 'griffin_lim_fast':
-            return cls(stft, momentum=0.99, inversion='nnls', speed=speed, pitch=pitch)
+            return cls(stft, momentum=0.99, inversion='nnls', **knobs)
         raise ValueError("unknown vocoder %r (a callable, or one of %s)" % (name, ', '.join(repr(v) for v in VOCODERS)))
 
     def _magnitudes(self, mel, lengths):
@@ -103,8 +111,11 @@ class GriffinLimVocoder(object):
         return self.stft.mel_to_magnitude(mel, lengths, self.inversion, self.inversion_iters)
 
     def _stretched(self, magnitudes, n):
-        """the magnitudes at the rate self.stretch and their frame counts (as they came when the rate is 1)"""
+        """the magnitudes with their envelope warped by self.warp, at the rate self.stretch, and their frame counts (as they
+        came when neither is set)"""
         import t2v_hip
+        if self.warp[0] != self.warp[1]:
+            magnitudes = t2v_hip.warp_envelope(self.stft.stft_fn.on_gpu(magnitudes), n, self.warp)
         if self.stretch[0] == self.stretch[1]:
             return magnitudes, n
         for b, k in enumerate(n):
@@ -124,7 +135,7 @@ class GriffinLimVocoder(object):
     def __call__(self, mel, lengths=None):
         from audio_processing import griffin_lim
         magnitudes = self._magnitudes(mel, lengths)
-        if self.stretch[0] == self.stretch[1] and self.shift[0] == self.shift[1]:
+        if self.stretch[0] == self.stretch[1] and self.shift[0] == self.shift[1] and self.warp[0] == self.warp[1]:
             return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths, momentum=self.momentum)
         n = [magnitudes.size(2)] * magnitudes.size(0) if lengths is None else [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
         stretched, n = self._stretched(magnitudes, n)
@@ -150,7 +161,7 @@ class GriffinLimVocoder(object):
 
 class Synthesizer(object):
     def __init__(self, hparams=None, resample=False, trim_db=None, attention_window=None, speed=1.0, pitch=0.0, ref_speed=1.0,
-                 ref_pitch=0.0):
+                 ref_pitch=0.0, formant=0.0, ref_formant=0.0, preserve_formants=False):
         """speed, pitch: the tempo (0.25..4, above 1 is faster) and the pitch shift in semitones (-12..12) of what the built-in
         vocoder writes (`GriffinLimVocoder(speed=, pitch=)`, made in `load`): synthesize, synthesize_batch and the vocoder leg
         of evaluate pick them up through the vocoder object; ref_speed, ref_pitch: every reference wav that is read goes
@@ -159,6 +170,12 @@ class Synthesizer(object):
         load_mel(s), latents, latent_map / latent_report, pitch, loudness, latent_probe (on top of its own perturbations) and
         both uses of the recordings in evaluate, the style and the `truth` mels; `wav_lengths`, which only sorts, still counts the
         files' samples.  All four are off by default.
+        formant, ref_formant (semitones, -12..12) move the spectral envelope alone, the formants, and keep the harmonics: formant
+        in the vocoder (`GriffinLimVocoder(formant=)`), ref_formant on every reference wav (`t2v_hip.formant_shift`, after the
+        tempo and pitch steps).  preserve_formants makes both pitch knobs leave the envelope where it was: `pitch` through the
+        vocoder's `preserve_formants`, `ref_pitch` through `t2v_hip.pitch_shift(preserve_formants=True)`; without it a pitch
+        shift moves the formants with F0, which is another speaker ("like this clip, but higher" then wants it on).  All three
+        are off by default.
         attention_window: None, or (back, ahead) for the decoder of every model this object loads (`Decoder.attention_window`:
         each free-running frame attends within [p - back, p + ahead] of the position p the previous frame attended most), so
         synthesize, synthesize_batch, alignment and evaluate all decode under it;
@@ -181,10 +198,14 @@ class Synthesizer(object):
         self.resample, self.trim_db = bool(resample), trim_db
         import t2v_hip
         t2v_hip.vocoder_rates(speed, pitch)                              # refused here, not at load()
+        t2v_hip.vocoder_warp(pitch, formant, preserve_formants)
         self.speed, self.pitch_st = float(speed), float(pitch)         # `pitch` is the F0 tracker's method
         self.ref_speed, self.ref_pitch = float(ref_speed), float(ref_pitch)
+        self.formant, self.ref_formant, self.preserve_formants = float(formant), float(ref_formant), bool(preserve_formants)
         self._ref_stretch, self._ref_shift = t2v_hip.stretch_ratio(ref_speed), t2v_hip.pitch_ratio(ref_pitch)
-        self._ref_perturbed = self._ref_stretch[0] != self._ref_stretch[1] or self._ref_shift[0] != self._ref_shift[1]
+        self._ref_warp = t2v_hip.pitch_ratio(ref_formant)
+        self._ref_perturbed = (self._ref_stretch[0] != self._ref_stretch[1] or self._ref_shift[0] != self._ref_shift[1]
+                               or self._ref_warp[0] != self._ref_warp[1])
         from t2v_hip import check_attention_window
         self.attention_window = check_attention_window(attention_window)
         self.stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels,
@@ -227,12 +248,13 @@ class Synthesizer(object):
         return self._perturb_refs(*resample_rows([read_wav(path) for path in paths], self.hparams.sampling_rate))
 
     def _perturb_refs(self, y, n):
-        """ref_speed and ref_pitch on a batch of wavs that has just been read (as it came when both are off)"""
+        """ref_speed, ref_pitch and ref_formant on a batch of wavs that has just been read (as it came when all are off)"""
         if not self._ref_perturbed:
             return y, n
         import t2v_hip
         y, n = t2v_hip.time_stretch(y, n, self._ref_stretch)
-        return t2v_hip.pitch_shift(y, n, self.ref_pitch)
+        y, n = t2v_hip.pitch_shift(y, n, self.ref_pitch, preserve_formants=self.preserve_formants)
+        return t2v_hip.formant_shift(y, n, self.ref_formant)
 
     def _load_wavs_at_rate(self, paths):
         audios = []
@@ -362,7 +384,8 @@ class Synthesizer(object):
         return corpus_report(lat[keys[key]], emotions, lat[1], lat[2], k)
 
     @torch.no_grad()
-    def latent_probe(self, paths, emotions=None, pitch=(-2, 2), speed=(0.85, 1.15), gain_db=(-6, 6), batch_size=64):
+    def latent_probe(self, paths, emotions=None, pitch=(-2, 2), speed=(0.85, 1.15), gain_db=(-6, 6), batch_size=64, formant=(),
+                     preserve_formants=False):
         """What does the latent listen to?  Every wav is encoded as it is and under each single perturbation: a pitch shift
         (semitones, `t2v_hip.pitch_shift`), a tempo change (`t2v_hip.time_stretch`) or a gain (dB, `t2v_hip.scale_rows`), applied
         to the samples `load_wavs` gives, before the mel front end.  Returns a JSON-serialisable dict: `n_clips`, `scale`,
@@ -372,7 +395,11 @@ class Synthesizer(object):
         hold two labels or more (`scale_kind` 'emotion_centroids'), else the mean distance between different clips' mu
         ('clip_pairs'); None, and None on the relative values, when there is no pair or the scale is 0.  There are no
         thresholds.  The wavs are sorted by length and run in ragged batches of at most batch_size; a clip and its
-        perturbed copies are encoded in batches of the same rows, so the identity perturbation gives exactly 0."""
+        perturbed copies are encoded in batches of the same rows, so the identity perturbation gives exactly 0.
+        The plain pitch shift moves the formants with F0, two correlates at once.  preserve_formants=True makes the 'pitch'
+        entries `t2v_hip.pitch_shift(preserve_formants=True)`, F0 alone, and formant=(semitones, ...) adds entries of kind
+        'formant' after gain_db, `t2v_hip.formant_shift`: the envelope alone.  Together they tell whether mu listens to pitch
+        or to timbre."""
         import t2v_hip
         paths = list(paths)
         if not paths:
@@ -384,8 +411,9 @@ class Synthesizer(object):
             if len(emotions) != len(paths):
                 raise ValueError("latent_probe: %d paths for %d emotion labels" % (len(paths), len(emotions)))
         probes = [('pitch', float(v)) for v in pitch] + [('speed', float(v)) for v in speed] + [('gain_db', float(v)) for v in gain_db]
+        probes += [('formant', float(v)) for v in formant]
         for kind, v in probes:                                            # refused before any work
-            if kind == 'pitch':
+            if kind in ('pitch', 'formant'):
                 t2v_hip.pitch_ratio(v)
             elif kind == 'speed':
                 t2v_hip.stretch_ratio(v)
@@ -399,7 +427,9 @@ class Synthesizer(object):
                 base[i] = mu[b].cpu().numpy()
             for k, (kind, v) in enumerate(probes):
                 if kind == 'pitch':
-                    y2, n2 = t2v_hip.pitch_shift(y, n, v)
+                    y2, n2 = t2v_hip.pitch_shift(y, n, v, preserve_formants=bool(preserve_formants))
+                elif kind == 'formant':
+                    y2, n2 = t2v_hip.formant_shift(y, n, v)
                 elif kind == 'speed':
                     y2, n2 = t2v_hip.time_stretch(y, n, v)
                 else:
@@ -457,7 +487,8 @@ class Synthesizer(object):
         position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
         (`latents`), when there is no centroid cache yet."""
         if isinstance(vocoder, str):
-            vocoder = GriffinLimVocoder.named(vocoder, self.stft, self.speed, self.pitch_st)       # an unknown name fails before anything is loaded
+            # an unknown name fails before anything is loaded
+            vocoder = GriffinLimVocoder.named(vocoder, self.stft, self.speed, self.pitch_st, self.formant, self.preserve_formants)
         self.load_checkpoint(checkpoint_path)
         if callable(waveglow_path) and vocoder is None:
             vocoder, waveglow_path = waveglow_path, None
@@ -914,16 +945,31 @@ def add_tempo_arguments(p):
                    help="speaking rate of the built-in vocoder's output, 0.25..4 (default 1: unchanged)")
     p.add_argument('--pitch', type=float, default=0.0, metavar='ST',
                    help="pitch shift of the built-in vocoder's output in semitones, -12..12 (default 0: unchanged)")
+    p.add_argument('--formant', type=float, default=0.0, metavar='ST',
+                   help="shift of the spectral envelope (the formants) of the built-in vocoder's output in semitones, -12..12; the "
+                        "harmonics stay (default 0: unchanged)")
+    p.add_argument('--preserve_formants', action='store_true',
+                   help="--pitch moves F0 alone and leaves the formants where they were (default: they move with the pitch)")
 
 
 def tempo_options(args):
-    """the Synthesizer keywords of add_tempo_arguments' flags; SystemExit on a value out of range"""
+    """the Synthesizer keywords of add_tempo_arguments' flags (formant and preserve_formants only when their flags are used);
+    SystemExit on a value out of range"""
     import t2v_hip
     try:
         t2v_hip.vocoder_rates(args.speed, args.pitch)
     except ValueError as e:
         raise SystemExit("--speed / --pitch: %s" % e)
-    return {'speed': args.speed, 'pitch': args.pitch}
+    out = {'speed': args.speed, 'pitch': args.pitch}
+    try:
+        t2v_hip.vocoder_warp(args.pitch, args.formant, args.preserve_formants)
+    except ValueError as e:
+        raise SystemExit("--formant / --preserve_formants: %s" % e)
+    if args.formant != 0.0:
+        out['formant'] = args.formant
+    if args.preserve_formants:
+        out['preserve_formants'] = True
+    return out
 
 
 def parse_args(argv=None):
@@ -943,6 +989,8 @@ def parse_args(argv=None):
     args.texts = texts
     if (args.speed != 1.0 or args.pitch != 0.0) and args.vocoder is None:
         raise SystemExit("--speed / --pitch act in the built-in vocoder: give --vocoder")
+    if (args.formant != 0.0 or args.preserve_formants) and args.vocoder is None:
+        raise SystemExit("--formant / --preserve_formants act in the built-in vocoder: give --vocoder")
     tempo_options(args)
     return args
 

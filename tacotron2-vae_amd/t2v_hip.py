@@ -115,7 +115,7 @@ EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_
            't2v_mel_cepstrum', 't2v_cep_dtw_scratch_bytes', 't2v_cep_dtw_path', 't2v_cep_dtw_forward', 't2v_cep_dtw_walk',
            't2v_path_scores', 't2v_loudness', 't2v_loudness_scratch_bytes', 't2v_scale_rows',
            't2v_decoder_infer_steps_window', 't2v_decoder_infer_persistent_window',
-           't2v_phase_vocoder', 't2v_phase_vocoder_scratch_bytes')
+           't2v_phase_vocoder', 't2v_phase_vocoder_scratch_bytes', 't2v_spectral_envelope')
 
 
 def lib_path():
@@ -281,6 +281,7 @@ def load_library():
     lib.t2v_phase_vocoder_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_phase_vocoder_scratch_bytes.restype = C.c_size_t
     lib.t2v_phase_vocoder.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [vp, vp, C.c_int, vp, vp]
+    lib.t2v_spectral_envelope.argtypes = [vp, vp] + [C.c_int] * 7 + [vp, vp, C.c_int, vp]
     lib.t2v_alignment_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.t2v_alignment_scratch_bytes.restype = C.c_size_t
     lib.t2v_alignment_stats.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp,
@@ -2056,6 +2057,21 @@ def vocoder_rates(speed, pitch):
     return (g.numerator, g.denominator), (p, q)
 
 
+def vocoder_warp(pitch, formant=0.0, preserve_formants=False):
+    """(a, b) of the one `warp_envelope` call of GriffinLimVocoder(pitch=, formant=, preserve_formants=): the envelope is read at
+    k a / b.  With p / q = 2^(pitch / 12) and P / Q = 2^(formant / 12), a / b = (p / q when preserving, else 1) x Q / P: the
+    correction that undoes what the resampler will do to the envelope, and the formant factor, as one ratio in 1..1023 each.
+    (1, 1) when neither is asked for.  ValueError when the combined ratio leaves 0.25..4."""
+    import fractions
+    p, q = pitch_ratio(pitch) if preserve_formants else (1, 1)
+    P, Q = pitch_ratio(formant)
+    f = fractions.Fraction(p * Q, q * P)
+    if not 0.25 <= f <= 4:
+        raise ValueError("pitch %r (formants preserved) with formant %r warps the envelope by %s, outside 0.25..4" % (pitch, formant, f))
+    g = _small_ratio(f)
+    return g.numerator, g.denominator
+
+
 def _rate_pair(rate, who):
     """a rate argument as (num, den): a number goes through stretch_ratio, a pair of integers in 1..1023 is taken as it is"""
     if isinstance(rate, (tuple, list)):
@@ -2126,28 +2142,78 @@ def _tsm_tables(device):
     return t
 
 
-def time_stretch(y, lengths, rate, phase_lock=True):
-    """Change the tempo of waveforms and keep their pitch: y (B, S) float32 CUDA tensor, row b of lengths[b] samples, every one
-    more than 512 (`stft_polar`'s ValueError otherwise).  Exactly `stft_polar` -> `phase_vocoder` -> `istft` with the tables
-    of stft.STFT.  Returns (y_out (B, max n_out) float32, n_out: the host list of min((T_out[b] - 1) 256, ceil(lengths[b] den /
-    num)), T_out[b] the row's stretched frame count); y_out is 0 past each n_out.  A rate of 1 launches nothing and returns
-    the input."""
+ENV_MAX_ORDER = 256                      # T2V_ENV_MAX_ORDER of include/t2vae.h: the longest lifter, in cepstral bins
+ENV_MAX_ITERS = 32                       # T2V_ENV_MAX_ITERS: the most true-envelope iterations
+
+
+def _envelope_launch(who, mag, n_frames, order, iters, ratio, want_env, want_mag):
+    """one t2v_spectral_envelope call: (the log envelope or None, the warped magnitudes or None)"""
+    lib = _require_gpu(mag)
+    if mag.dim() != 3 or mag.size(1) != 513 or mag.dtype != torch.float32:
+        raise ValueError("%s: magnitude must be float32 (B, 513, T)" % who)
+    B, _, stride = mag.shape
+    if B < 1 or stride < 1:
+        raise ValueError("%s: empty input %s" % (who, tuple(mag.shape)))
+    if isinstance(order, bool) or int(order) != order or not 1 <= order <= ENV_MAX_ORDER:
+        raise ValueError("%s: order %r must be an integer in 1..%d" % (who, order, ENV_MAX_ORDER))
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= iters <= ENV_MAX_ITERS:
+        raise ValueError("%s: iters %r must be an integer in 0..%d" % (who, iters, ENV_MAX_ITERS))
+    if not isinstance(ratio, (tuple, list)):
+        raise ValueError("%s: the ratio must be a pair (p, q) of integers in 1..%d, got %r" % (who, TSM_MAX_RATIO, ratio))
+    p, q = _rate_pair(ratio, who)
+    msg = "%s: every row needs 1 <= frames <= %d" % (who, stride)
+    n = _checked_lengths(n_frames, B, 1, stride, msg, msg, reject_float=False, reject_bool=False, default=stride)
+    T = int(n.max())
+    if T > TSM_MAX_FRAMES:
+        raise ValueError("%s: rows of %d frames exceed the %d supported" % (who, T, TSM_MAX_FRAMES))
+    mag = mag.contiguous()
+    env = torch.empty_like(mag) if want_env else None
+    out = torch.empty_like(mag) if want_mag else None
+    _check(lib.t2v_spectral_envelope(_p(mag), _p(n.to(mag.device)), B, T, stride, int(order), int(iters), p, q,
+                                     None if env is None else _p(env), None if out is None else _p(out), stride, _stream()),
+           't2v_spectral_envelope')
+    return env, out
+
+
+def spectral_envelope(mag, n_frames, order=32, iters=8):
+    """The true-envelope estimate of STFT magnitudes (csrc/envelope.hip k_spectral_envelope): mag (B, 513, T) float32 CUDA tensor
+    as `stft_polar` gives it, row b of n_frames[b] frames (a list, a CPU or a device tensor; None: all T); frames at and past a
+    row's count are not read.  Returns the natural-log envelope (B, 513, T), 0 past each count: `iters` + 1 passes of a cepstral
+    lifter of `order` bins (1..256) over max(log magnitude, last envelope), a fixed count in 0..32 (include/t2vae.h); iters = 0
+    is the plain cepstral envelope.  The lifter must stay below half the pitch period in samples: 32 serves voices up to 250 Hz
+    at 16 kHz.  A frame gives the same bits alone, in any batch and at any stride."""
+    return _envelope_launch("spectral_envelope", mag, n_frames, order, iters, (1, 1), True, False)[0]
+
+
+def warp_envelope(mag, n_frames, ratio, order=32, iters=8):
+    """The magnitudes with their envelope read at k p / q: mag[k] exp(Ew[k] - E[k]), E the envelope of `spectral_envelope` and
+    Ew[k] its linear interpolation at bin k p / q (bin 512 beyond the end).  ratio is the pair (p, q), integers in 1..1023 as
+    `pitch_ratio` gives them: the envelope, and with it the formants, moves along frequency by q / p, and the harmonics stay
+    where they are.  Returns (B, 513, T), 0 past each count; p == q returns the magnitudes bit for bit."""
+    return _envelope_launch("warp_envelope", mag, n_frames, order, iters, ratio, False, True)[1]
+
+
+def _stretched(who, y, lengths, rate, phase_lock, warp=None, order=32, iters=8):
+    """The whole of `time_stretch`, and the middle it shares with the formant-preserving `pitch_shift`: `stft_polar`,
+    `warp_envelope` by `warp` when there is one, `phase_vocoder` at `rate`, `istft`, and the cut to each row's length"""
     _require_gpu(y)
     if y.dim() != 2 or y.dtype != torch.float32:
-        raise ValueError("time_stretch: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+        raise ValueError("%s: y must be a float32 (B, S) tensor, got %s %s" % (who, y.dtype, tuple(y.shape)))
     B, S = y.shape
     if B < 1 or S < 1:
-        raise ValueError("time_stretch: empty input %s" % (tuple(y.shape),))
-    num, den = _rate_pair(rate, "time_stretch")
-    n = _wave_lengths(lengths, B, S, "time_stretch")
-    if num == den:
+        raise ValueError("%s: empty input %s" % (who, tuple(y.shape)))
+    num, den = _rate_pair(rate, who)
+    n = _wave_lengths(lengths, B, S, who)
+    if num == den and warp is None:
         return y, n.tolist()
     tables = _tsm_tables(y.device)
     mag, phase = stft_polar(y, n.to(torch.int64), tables)            # the transform reads 64-bit counts
     frames = [k // TSM_HOP + 1 for k in n.tolist()]
     for b, f in enumerate(frames):
         if stretch_frames(f, num, den) < 2:
-            raise ValueError("time_stretch: row %d has %d frames, fewer than 2 at the rate %d/%d" % (b, f, num, den))
+            raise ValueError("%s: row %d has %d frames, fewer than 2 at the rate %d/%d" % (who, b, f, num, den))
+    if warp is not None:
+        mag = warp_envelope(mag, frames, warp, order, iters)
     mag, phase, t_out = phase_vocoder(mag, phase, frames, (num, den), phase_lock)
     y_out = istft(mag, phase, t_out, tables)
     n_out = [min((t - 1) * TSM_HOP, stretch_frames(k, num, den)) for t, k in zip(t_out, n.tolist())]
@@ -2158,15 +2224,52 @@ def time_stretch(y, lengths, rate, phase_lock=True):
     return y_out, n_out
 
 
-def pitch_shift(y, lengths, semitones, phase_lock=True):
+def time_stretch(y, lengths, rate, phase_lock=True):
+    """Change the tempo of waveforms and keep their pitch: y (B, S) float32 CUDA tensor, row b of lengths[b] samples, every one
+    more than 512 (`stft_polar`'s ValueError otherwise).  Exactly `stft_polar` -> `phase_vocoder` -> `istft` with the tables
+    of stft.STFT.  Returns (y_out (B, max n_out) float32, n_out: the host list of min((T_out[b] - 1) 256, ceil(lengths[b] den /
+    num)), T_out[b] the row's stretched frame count); y_out is 0 past each n_out.  A rate of 1 launches nothing and returns
+    the input."""
+    return _stretched("time_stretch", y, lengths, rate, phase_lock)
+
+
+def pitch_shift(y, lengths, semitones, phase_lock=True, preserve_formants=False, order=32, iters=8):
     """Change the pitch of waveforms by `semitones` (-12..12) and keep their duration to within a frame: `time_stretch` by q / p,
     then `resample` by p / q read backwards (p / q = 2^(semitones / 12), `pitch_ratio`).  Returns (y_out, n_out) as `resample`
-    does.  0 semitones returns the input."""
+    does.  0 semitones returns the input.  The resampler moves the spectral envelope with the harmonics, so the plain shift
+    changes the timbre too.  preserve_formants: the magnitudes go through `warp_envelope` by (p, q) (a lifter of `order`,
+    `iters` iterations) between `stft_polar` and `phase_vocoder`, which moves the envelope by q / p ahead of the resampler:
+    F0 moves and the formants stay."""
     p, q = pitch_ratio(semitones)
     if p == q:
         return time_stretch(y, lengths, (1, 1))                         # its checks, no launch
-    stretched, n = time_stretch(y, lengths, (q, p), phase_lock)
+    if not preserve_formants:
+        stretched, n = time_stretch(y, lengths, (q, p), phase_lock)
+    else:
+        stretched, n = _stretched("pitch_shift", y, lengths, (q, p), phase_lock, (p, q), order, iters)
     return resample(stretched, n, p, q)
+
+
+def formant_shift(y, lengths, semitones, order=32, iters=8):
+    """Move the spectral envelope of waveforms, their formants, up by 2^(semitones / 12) (-12..12) and keep harmonics and
+    duration: `stft_polar` -> `warp_envelope` by (q, p), p / q = `pitch_ratio`(semitones) -> `istft` with the analysis phases.
+    y (B, S) float32 CUDA tensor, row b of lengths[b] samples, every one more than 512.  Returns (y_out (B, max n_out), n_out: the
+    host list of (lengths[b] // 256) 256), 0 past each n_out.  0 semitones launches nothing and returns the input."""
+    _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("formant_shift: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("formant_shift: empty input %s" % (tuple(y.shape),))
+    p, q = pitch_ratio(semitones)
+    n = _wave_lengths(lengths, B, S, "formant_shift")
+    if p == q:
+        return y, n.tolist()
+    tables = _tsm_tables(y.device)
+    mag, phase = stft_polar(y, n.to(torch.int64), tables)
+    frames = [k // TSM_HOP + 1 for k in n.tolist()]
+    mag = warp_envelope(mag, frames, (q, p), order, iters)
+    return istft(mag, phase, frames, tables), [(f - 1) * TSM_HOP for f in frames]
 
 
 def trim_bounds(y, lengths, top_db=40.0, pad_frames=2):
