@@ -220,7 +220,7 @@ __device__ __forceinline__ void attn_bwd_body(const AttnBwdArgs& a, const int b,
         const int wv = tid & 3, r = tid >> 2;            // row jl = tid was summed by wave wv as its r-th row
         const float dalv = ((red[1 + r][4 * wv] + red[1 + r][4 * wv + 1]) + (red[1 + r][4 * wv + 2] + red[1 + r][4 * wv + 3])) +
                            gfull0[j0 + min(tid, nown - 1)] + gfull1[j0 + min(tid, nown - 1)];
-        de[tid] = tid < nown ? alf[j0 + tid] * (dalv - dsum[0]) : 0.f;
+        de[tid] = tid < nown ? softmax_de(alf[j0 + tid], dalv, dsum[0]) : 0.f;
     }
     __syncthreads();
 

@@ -187,7 +187,7 @@ __device__ __forceinline__ void t2v_attn_role_bwd(const Args& a, float* lds, con
             const int wv = tid % NWV, r = tid / NWV;              // position tid = wv + NWV r
             const float* rr = red + (1 + r) * 4 * NWV + 4 * wv;
             const float dalv = ((rr[0] + rr[1]) + (rr[2] + rr[3])) + gfull0[j0 + min(tid, nown - 1)] + gfull1[j0 + min(tid, nown - 1)];
-            de[tid] = tid < nown ? alf[j0 + tid] * (dalv - dsum) : 0.f;
+            de[tid] = tid < nown ? softmax_de(alf[j0 + tid], dalv, dsum) : 0.f;
         }
         __syncthreads();
         // ---- through v·tanh(.): dpre, partial dq / dv

@@ -74,6 +74,11 @@ __device__ __forceinline__ float4 ld_nt(const float4* p) {
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return fast_rcp(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f * fast_rcp(1.0f + __expf(2.0f * x)); }
+// softmax backward of one position, d e_j = alpha_j (dalpha_j - dot), dot = sum_k alpha_k dalpha_k.  The attention backward gets dot
+// as dctx . ctx_t + sum alpha G, summed in another order than dalpha_j itself.  A weight that is exactly 1 carries the whole mass
+// (one valid position, or every other weight below 2^-25): the softmax is constant there and d e_j is 0, not the round-off that
+// the two summation orders leave in dalpha_j - dot.
+__device__ __forceinline__ float softmax_de(float alpha, float dalpha, float dot) { return alpha == 1.0f ? 0.f : alpha * (dalpha - dot); }
 
 // value of the lane that DPP control CTRL selects (row_mask = bank_mask = 0xF, bound_ctrl)
 #define T2V_DPP_F(v, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (CTRL), 0xF, 0xF, true))

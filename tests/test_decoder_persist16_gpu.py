@@ -6,7 +6,8 @@ state, attention and saved activations in fp32 — the same arithmetic in a diff
 of 4).  Unlike the fp32 pair of test_decoder_persist_train_gpu.py the two do NOT agree to 1e-6: a last-bit fp32 difference in
 a state value now and then crosses a bf16 rounding boundary (2^-9 relative) and is carried on by the recurrence.  The bounds
 below are therefore a few bf16 ulps of the state on the worst element and 1e-4-ish on the mean; the bf16 path as a whole is
-bounded against the fp32 build in test_bf16_gpu.py (reference fp16_optimizer.py:51-382 is what bf16_run replaces)."""
+bounded against the fp32 build in test_bf16_gpu.py (reference fp16_optimizer.py:51-382 is what bf16_run replaces).  Each of the
+four bf16 engines is held to a float64 oracle at fp32 round-off, one time step at a time, in test_decoder_bf16_stepwise_gpu.py."""
 import pytest
 import torch
 

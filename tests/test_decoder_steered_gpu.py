@@ -19,7 +19,8 @@ carry ~1e-7 absolute error (csrc/t2v_common.h) where libm carries half an ulp, a
 sum in another order than the oracle.
 
 Every case prints its worst values next to floor, K and bound before it asserts (pytest -s); profiles/steered_attention_parity.txt
-is that table from an MI355X.  The bf16 engines are not covered: the oracle has no bf16 form.
+is that table from an MI355X.  The bf16 engines are not covered here: the oracle has no bf16 form — they meet a step-by-step
+rounding oracle (tests/bf16_ref.py) in test_decoder_bf16_stepwise_gpu.py.
 """
 import pytest
 import torch
