@@ -31,6 +31,31 @@ def test_reverse_pass_geometry(lib):
         assert lib.t2v_decoder_bwd_achain_dq_offset(6, 84, 400) == -1
 
 
+# the cooperative recurrences: (entry point, number of pointer arguments, indices of the optional ones).  Every call below must be
+# turned away by the argument guard, before anything is launched: the pointers are host dummies.
+_RECURRENT = (('t2v_bilstm_fwd', 8, (4, 5)), ('t2v_bilstm_bwd', 8, ()), ('t2v_gru_fwd', 7, (4,)), ('t2v_gru_fwd_len', 9, (4,)),
+              ('t2v_gru_bwd', 8, ()))
+
+
+@pytest.mark.parametrize("name,n_ptr,optional", _RECURRENT, ids=[r[0] for r in _RECURRENT])
+def test_recurrent_entry_points_turn_bad_arguments_away(lib, name, n_ptr, optional):
+    fn = getattr(lib, name)
+    dummy = C.create_string_buffer(64)
+    ptrs = [C.c_void_p(C.addressof(dummy))] * n_ptr
+    for B, T in ((0, 4), (17, 4), (-1, 4), (4, 0), (4, -3)):
+        assert fn(*ptrs, B, T, None) != 0, (B, T)
+    for i in range(n_ptr):
+        if i not in optional:
+            assert fn(*(ptrs[:i] + [None] + ptrs[i + 1:]), 4, 4, None) != 0, i
+
+
+def test_bilstm_fwd_wants_gates_and_cells_together(lib):
+    dummy = C.create_string_buffer(64)
+    p = C.c_void_p(C.addressof(dummy))
+    assert lib.t2v_bilstm_fwd(p, p, p, p, p, None, p, p, 4, 4, None) != 0          # gates without cells
+    assert lib.t2v_bilstm_fwd(p, p, p, p, None, p, p, p, 4, 4, None) != 0          # cells without gates
+
+
 def test_scratch_size_answers_are_monotonic(lib):
     assert lib.t2v_gemm_splitk_scratch_floats(81, 1536, 2400) > 0            # the projection's weight gradient is split
     # large products: no scratch for the fp32-MFMA kernels; the x3 path (round 6) keeps the bf16 planes of both operands there
