@@ -12,6 +12,8 @@ import os
 
 import torch
 
+import t2v_abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (T2V_LIB: another build of the same library — A/B measurements of two kernel variants on ONE GPU box, tools/dbg/ab_lib.sh)
 _LIB_PATH = os.environ.get('T2V_LIB') or os.path.join(_HERE, 'libt2vae_hip.so')
@@ -19,103 +21,22 @@ _lib = None
 
 H, E, PRE, A, F_LOC, KS, XW, KATT, KATT_INF, G4 = 1024, 512, 256, 128, 32, 31, 2560, 1536, 1792, 4096
 
+# The C ABI comes from include/t2vae.h itself (t2v_abi.py parses it once per process): the entry points with their
+# argument / return types, the struct layouts and the integer limits.  Nothing of it is restated here, so a new entry
+# point is declared in the header and needs no line in this file.
+_ABI = t2v_abi.load()
+T2VHipError = t2v_abi.T2VHipError
 
-class T2VHipError(RuntimeError):
-    pass
+# the ctypes.Structure of every struct the host fills (pointer fields are c_void_p; C_NAME is the C struct's name)
+(_DecWeights, _DecTrainBufs, _DecBwdBufs, _DecPersistWeights, _DecPersistBufs, _DecTrainPersistWeights, _GemmGroup, _AchainDw,
+ _DecInferBufs, _DecItems, _DecWindow) = (_ABI.classes[n] for n in (
+     't2v_dec_weights', 't2v_dec_train_bufs', 't2v_dec_bwd_bufs', 't2v_dec_persist_weights', 't2v_dec_persist_bufs',
+     't2v_dec_train_persist_weights', 't2v_gemm_group', 't2v_achain_dw', 't2v_dec_infer_bufs', 't2v_dec_items', 't2v_dec_window'))
+_StepRecord = _ABI.classes['t2v_step_params']       # lives in device memory: only its layout is used here (StepParams)
+if (_StepRecord.epoch.offset, _StepRecord.epoch.size) != (0, 8):        # StepParams.upload() writes it as a slot's first int64
+    raise T2VHipError("t2v_step_params.epoch is not the 8-byte field at offset 0 (include/t2vae.h)")
 
-
-class _DecWeights(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        'packF_att', 'packF_dec', 'packB_att', 'packB_dec', 'bias_att', 'bias_dec', 'wqT', 'wcomb', 'v')] + [
-        ('packs_bf16', C.c_int32)]
-
-
-class _DecTrainBufs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        'gpre', 'memory', 'pm', 'lengths', 'XS', 'CA', 'CD', 'GA', 'GD', 'QP', 'AL', 'ACUM', 'S')]
-
-
-class _DecBwdBufs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        'dHC', 'DGA', 'DGD', 'DQ', 'DCTX', 'YD', 'YA', 'DCA', 'DCD', 'GPREV', 'GCUM', 'DV')]
-
-
-class _DecPersistWeights(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        'w_ih_att', 'w_hh_att', 'w_ih_dec', 'w_hh_dec', 'bias_att', 'bias_dec', 'wq', 'wcomb', 'v', 'proj_w', 'proj_b',
-        'prenet_w1')]
-
-
-class _DecPersistBufs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        'memory', 'pm', 'lengths', 'pre_first', 'MEL', 'GATE', 'AL', 'stop_flag', 'exchange', 'err_word')]
-
-
-class _DecTrainPersistWeights(C.Structure):
-    C_NAME = 't2v_dec_train_persist_weights'
-    _fields_ = [(n, C.c_void_p) for n in (
-        'w_ih_att', 'w_hh_att', 'w_ih_dec', 'w_hh_dec', 'bias_dec', 'wq', 'wcomb', 'v')]
-
-
-class _GemmGroup(C.Structure):
-    C_NAME = 't2v_gemm_group'
-    _fields_ = [('A', C.c_void_p), ('sAi', C.c_long), ('sAk', C.c_long), ('nb', C.c_int), ('B', C.c_void_p * 3), ('sBj', C.c_long * 3),
-                ('sBk', C.c_long * 3), ('N', C.c_int * 3), ('C', C.c_void_p * 3), ('ldc', C.c_int * 3)]
-
-
-class _AchainDw(C.Structure):
-    C_NAME = 't2v_achain_dw'
-    _fields_ = [('planes', C.c_void_p), ('d_w_ih', C.c_void_p), ('ld_ih', C.c_int), ('d_w_hh', C.c_void_p), ('ld_hh', C.c_int),
-                ('accumulate', C.c_int), ('tile_cap', C.c_int)]
-
-
-class _DecInferBufs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        'memory', 'pm', 'lengths', 'XS', 'CA', 'CD', 'QP', 'AL', 'ACUM', 'PRE', 'MEL', 'GATE', 'stop_flag',
-        'prenet_w1', 'proj_w', 'proj_b')]
-
-
-class _DecItems(C.Structure):
-    C_NAME = 't2v_dec_items'
-    _fields_ = [(n, C.c_void_p) for n in ('stop_item', 'item_seeds')]
-
-
-class _DecWindow(C.Structure):
-    C_NAME = 't2v_dec_window'
-    _fields_ = [('back', C.c_int32), ('ahead', C.c_int32)]
-
-
-EXPORTS = ('t2v_version', 't2v_last_error', 't2v_stamp', 't2v_debug_spin', 't2v_pack_lstm_weights', 't2v_pack_lstm_weights_bf16', 't2v_decoder_train_fwd',
-           't2v_decoder_train_bwd', 't2v_clip_adam_step', 't2v_clip_adam_step_guarded', 't2v_decoder_replay_fwd_kernels', 't2v_mel_frontend', 't2v_set_phase_profile', 't2v_decoder_infer_steps', 't2v_conv1d_stat_blocks', 't2v_conv1d_stat_blocks_bf16', 't2v_conv1d_staged_launches', 't2v_conv1d_fwd', 't2v_conv1d_bwd', 't2v_conv1d_fwd_bf16', 't2v_conv1d_bwd_bf16', 't2v_conv1d_dw_scratch_floats', 't2v_conv1d_flip_weights', 't2v_gemm_bf16', 't2v_gemm_bf16_splitk', 't2v_gemm_bf16_splitk_scratch_floats', 't2v_attn_wgrad', 't2v_attn_wgrad_scratch_floats',
-           't2v_bn_act_fwd', 't2v_bn_act_bwd', 't2v_bn_act_bwd_eval', 't2v_bilstm_fwd', 't2v_bilstm_bwd', 't2v_gemm_f32', 't2v_conv2d_s2_fwd', 't2v_conv2d_s2_bwd', 't2v_conv2d_s2_dw_scratch_floats', 't2v_conv2d_s2_fwd_gemm', 't2v_conv2d_s2_bwd_gemm',
-           't2v_conv2d_s2_gemm_scratch_floats',
-           't2v_gru_fwd', 't2v_gru_bwd', 't2v_loss_fwd_bwd', 't2v_fuse_location_weights', 't2v_decoder_qp_floats',
-           't2v_set_step_params', 't2v_set_step_params_stream', 't2v_decoder_replay_bwd_kernels', 't2v_embedding_fwd', 't2v_embedding_bwd', 't2v_gemm_f32_splitk', 't2v_gemm_splitk_scratch_floats', 't2v_gemm_f32_batched',
-           't2v_decoder_infer_persistent', 't2v_decoder_persist_supported', 't2v_decoder_persist_scratch_floats',
-           't2v_attn_bwd_slices', 't2v_colsum', 't2v_colsum_scratch_floats', 't2v_gemm_epilogue_bwd',
-           't2v_decoder_train_fwd_persistent', 't2v_decoder_train_persist_supported',
-           't2v_decoder_train_persist_scratch_floats', 't2v_decoder_bwd_persist_supported',
-           't2v_decoder_bwd_achain_scratch_floats', 't2v_decoder_bwd_achain', 't2v_decoder_bwd_achain_prepare',
-           't2v_decoder_bwd_achain_prepared', 't2v_decoder_bwd_persist_slices', 't2v_decoder_bwd_achain_dq_offset',
-           't2v_decoder_bwd_achain_dw_offset', 't2v_gemm_f32_grouped_handed', 't2v_gemm_f32_grouped_group_offset', 't2v_mask_outputs', 't2v_reparam_fwd',
-           't2v_reparam_bwd', 't2v_gather_words', 't2v_concat2_rows',
-           't2v_decoder_train_fwd_persistent16', 't2v_decoder_train_persist16_supported',
-           't2v_decoder_train_persist16_scratch_floats', 't2v_decoder_bwd_persistent16', 't2v_decoder_bwd_persist16_supported',
-           't2v_decoder_bwd_persist16_scratch_floats', 't2v_decoder_bwd_persist16_dq_offset', 't2v_decoder_bwd_persist16_slices',
-           't2v_decoder_bwd_persist16_fits', 't2v_gemm_f32_set_mode', 't2v_conv1d_x3_set_mode', 't2v_gemm_f32_grouped',
-           't2v_gemm_f32_grouped_scratch_floats', 't2v_gemm_bf16_grouped', 't2v_gemm_bf16_grouped_scratch_floats',
-           't2v_decoder_bwd_persistent16_prepare', 't2v_decoder_bwd_persistent16_prepared',
-           't2v_stft_polar', 't2v_istft', 't2v_istft_scratch_bytes', 't2v_griffin_lim', 't2v_griffin_lim_scratch_bytes',
-           't2v_mel_to_magnitude', 't2v_decoder_infer_steps_items', 't2v_decoder_infer_persistent_items', 't2v_bn_act_fwd_len',
-           't2v_mask_time', 't2v_conv2d_s2_fwd_ragged', 't2v_conv2d_s2_fwd_gemm_ragged', 't2v_conv2d_s2_gemm_ragged_scratch_floats',
-           't2v_gru_fwd_len', 't2v_mel_dtw', 't2v_mel_dtw_scratch_bytes', 't2v_tsne_scratch_bytes', 't2v_tsne_affinities',
-           't2v_tsne_gradient', 't2v_tsne_run', 't2v_f0_yin', 't2v_alignment_stats', 't2v_alignment_scratch_bytes',
-           't2v_mel_to_magnitude_nnls', 't2v_griffin_lim_fast', 't2v_griffin_lim_fast_scratch_bytes',
-           't2v_resample', 't2v_trim_bounds', 't2v_crop_rows', 't2v_latent_scratch_bytes', 't2v_latent_neighbours',
-           't2v_mel_cepstrum', 't2v_cep_dtw_scratch_bytes', 't2v_cep_dtw_path', 't2v_cep_dtw_forward', 't2v_cep_dtw_walk',
-           't2v_path_scores', 't2v_loudness', 't2v_loudness_scratch_bytes', 't2v_scale_rows',
-           't2v_decoder_infer_steps_window', 't2v_decoder_infer_persistent_window',
-           't2v_phase_vocoder', 't2v_phase_vocoder_scratch_bytes', 't2v_spectral_envelope')
+EXPORTS = tuple(_ABI.prototypes)
 
 
 def lib_path():
@@ -123,7 +44,8 @@ def lib_path():
 
 
 def load_library():
-    """dlopen the in-tree library (no compute); raises T2VHipError when it is not built."""
+    """dlopen the in-tree library (no compute) and give every entry point of the header its types; raises T2VHipError when
+    the library is not built, AttributeError when it lacks a declared symbol."""
     global _lib
     if _lib is not None:
         return _lib
@@ -131,210 +53,9 @@ def load_library():
         raise T2VHipError("libt2vae_hip.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(or make -C tacotron2-vae_amd/csrc)")
     lib = C.CDLL(_LIB_PATH)
-    lib.t2v_version.restype = C.c_char_p
-    lib.t2v_last_error.restype = C.c_char_p
-    lib.t2v_pack_lstm_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t2v_pack_lstm_weights_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t2v_fuse_location_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t2v_decoder_qp_floats.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_qp_floats.restype = C.c_long
-    lib.t2v_attn_bwd_slices.argtypes = [C.c_int]
-    lib.t2v_decoder_train_fwd.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecTrainBufs), C.c_int, C.c_int,
-                                          C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_train_bwd.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecTrainBufs),
-                                          C.POINTER(_DecBwdBufs), C.c_int, C.c_int, C.c_int, C.c_float,
-                                          C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_train_fwd_persistent.argtypes = [C.POINTER(_DecTrainPersistWeights), C.POINTER(_DecTrainBufs), C.c_void_p,
-                                                     C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_train_persist_supported.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_train_fwd_persistent16.argtypes = lib.t2v_decoder_train_fwd_persistent.argtypes
-    lib.t2v_decoder_train_persist16_supported.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_train_persist16_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_train_persist16_scratch_floats.restype = C.c_long
-    lib.t2v_decoder_bwd_persistent16.argtypes = [C.POINTER(_DecTrainPersistWeights), C.POINTER(_DecTrainBufs)] + [C.c_void_p] * 8 + [
-        C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_bwd_persistent16_prepared.argtypes = lib.t2v_decoder_bwd_persistent16.argtypes
-    lib.t2v_decoder_bwd_persistent16_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.t2v_decoder_bwd_persist16_supported.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_persist16_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_persist16_scratch_floats.restype = C.c_long
-    lib.t2v_decoder_bwd_persist16_dq_offset.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_persist16_dq_offset.restype = C.c_long
-    lib.t2v_decoder_bwd_persist16_slices.argtypes = [C.c_int]
-    lib.t2v_decoder_bwd_persist16_fits.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_gemm_f32_set_mode.argtypes = [C.c_int]
-    lib.t2v_conv1d_x3_set_mode.argtypes = [C.c_int]
-    lib.t2v_gemm_f32_grouped_scratch_floats.argtypes = [C.POINTER(_GemmGroup), C.c_int, C.c_int, C.c_int]
-    lib.t2v_gemm_f32_grouped_scratch_floats.restype = C.c_long
-    lib.t2v_gemm_f32_grouped.argtypes = [C.POINTER(_GemmGroup), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.t2v_gemm_bf16_grouped_scratch_floats.argtypes = lib.t2v_gemm_f32_grouped_scratch_floats.argtypes
-    lib.t2v_gemm_bf16_grouped_scratch_floats.restype = C.c_long
-    lib.t2v_gemm_bf16_grouped.argtypes = lib.t2v_gemm_f32_grouped.argtypes
-    lib.t2v_decoder_train_persist_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_train_persist_scratch_floats.restype = C.c_long
-    lib.t2v_decoder_bwd_persist_supported.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_achain_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_achain_scratch_floats.restype = C.c_long
-    lib.t2v_gemm_f32_grouped_handed.argtypes = [C.POINTER(_GemmGroup), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                                C.c_int, C.c_void_p]
-    lib.t2v_gemm_f32_grouped_group_offset.argtypes = [C.POINTER(_GemmGroup), C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.t2v_gemm_f32_grouped_group_offset.restype = C.c_long
-    lib.t2v_decoder_bwd_achain_dw_offset.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_achain_dw_offset.restype = C.c_long
-    lib.t2v_decoder_bwd_achain.argtypes = [C.POINTER(_DecTrainPersistWeights), C.POINTER(_AchainDw), C.POINTER(_DecTrainBufs)] + [C.c_void_p] * 8 + [
-        C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_bwd_persist_slices.argtypes = [C.c_int]
-    lib.t2v_decoder_bwd_achain_dq_offset.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_decoder_bwd_achain_dq_offset.restype = C.c_long
-    lib.t2v_decoder_bwd_achain_prepared.argtypes = lib.t2v_decoder_bwd_achain.argtypes
-    lib.t2v_decoder_bwd_achain_prepare.argtypes = [C.POINTER(_DecTrainBufs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                   C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_replay_fwd_kernels.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecTrainBufs), C.c_int,
-                                                   C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_int,
-                                                   C.c_void_p]
-    lib.t2v_decoder_replay_bwd_kernels.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecTrainBufs),
-                                                   C.POINTER(_DecBwdBufs), C.c_int, C.c_int, C.c_int, C.c_float,
-                                                   C.c_float, C.c_uint64, C.c_int, C.c_void_p]
-    lib.t2v_clip_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float,
-                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t2v_clip_adam_step_guarded.argtypes = lib.t2v_clip_adam_step.argtypes[:-1] + [C.c_void_p, C.c_int, C.c_void_p]
-    lib.t2v_mask_outputs.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]
-    lib.t2v_reparam_fwd.argtypes = [C.c_void_p] * 4 + [C.c_long, C.c_void_p]
-    lib.t2v_reparam_bwd.argtypes = [C.c_void_p] * 4 + [C.c_long, C.c_void_p]
-    lib.t2v_concat2_rows.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
-    lib.t2v_gather_words.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
-    lib.t2v_embedding_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.t2v_embedding_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.t2v_gemm_epilogue_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
-    lib.t2v_colsum.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t2v_colsum_scratch_floats.argtypes = [C.c_long, C.c_long]
-    lib.t2v_colsum_scratch_floats.restype = C.c_long
-    lib.t2v_set_step_params.argtypes = [C.c_void_p]
-    lib.t2v_set_step_params.restype = None
-    lib.t2v_set_step_params_stream.argtypes = [C.c_void_p, C.c_void_p]
-    lib.t2v_mel_frontend.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
-                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    lib.t2v_set_phase_profile.argtypes = [C.c_void_p]
-    lib.t2v_set_phase_profile.restype = None
-    lib.t2v_stamp.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.t2v_debug_spin.argtypes = [C.c_int, C.c_int, C.c_void_p]
-    lib.t2v_decoder_infer_persistent.argtypes = [C.POINTER(_DecPersistWeights), C.POINTER(_DecPersistBufs), C.c_int, C.c_int,
-                                                 C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_infer_persistent_items.argtypes = lib.t2v_decoder_infer_persistent.argtypes[:-1] + [C.POINTER(_DecItems),
-                                                                                                        C.c_void_p]
-    lib.t2v_decoder_persist_supported.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_persist_scratch_floats.argtypes = [C.c_int, C.c_int]
-    lib.t2v_decoder_persist_scratch_floats.restype = C.c_long
-    lib.t2v_decoder_infer_steps.argtypes = [C.POINTER(_DecWeights), C.POINTER(_DecInferBufs), C.c_int, C.c_int, C.c_int,
-                                            C.c_int, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_void_p]
-    lib.t2v_decoder_infer_steps_items.argtypes = lib.t2v_decoder_infer_steps.argtypes[:-1] + [C.POINTER(_DecItems), C.c_void_p]
-    # the windowed entries: the arguments of the per-item ones (items may be NULL) plus the t2v_dec_window pointer
-    lib.t2v_decoder_infer_steps_window.argtypes = lib.t2v_decoder_infer_steps_items.argtypes[:-1] + [C.POINTER(_DecWindow), C.c_void_p]
-    lib.t2v_decoder_infer_persistent_window.argtypes = lib.t2v_decoder_infer_persistent_items.argtypes[:-1] + [C.POINTER(_DecWindow),
-                                                                                                               C.c_void_p]
-    vp = C.c_void_p
-    lib.t2v_stft_polar.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.t2v_istft_scratch_bytes.argtypes = [C.c_int, C.c_int]
-    lib.t2v_istft_scratch_bytes.restype = C.c_size_t
-    lib.t2v_istft.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.t2v_griffin_lim_scratch_bytes.argtypes = [C.c_int, C.c_int]
-    lib.t2v_griffin_lim_scratch_bytes.restype = C.c_size_t
-    lib.t2v_griffin_lim.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int,
-                                    vp]
-    lib.t2v_mel_to_magnitude.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.t2v_mel_to_magnitude_nnls.argtypes = [vp] * 7 + [C.c_float, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.t2v_griffin_lim_fast_scratch_bytes.argtypes = [C.c_int, C.c_int]
-    lib.t2v_griffin_lim_fast_scratch_bytes.restype = C.c_size_t
-    lib.t2v_griffin_lim_fast.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp,
-                                         vp, C.c_int, vp]
-    lib.t2v_mel_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_mel_dtw_scratch_bytes.restype = C.c_size_t
-    lib.t2v_mel_dtw.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-    lib.t2v_mel_cepstrum.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
-    lib.t2v_cep_dtw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_cep_dtw_scratch_bytes.restype = C.c_size_t
-    lib.t2v_cep_dtw_forward.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
-    lib.t2v_cep_dtw_walk.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]
-    lib.t2v_cep_dtw_path.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]
-    lib.t2v_path_scores.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int,
-                                    vp, vp, vp]
-    lib.t2v_tsne_scratch_bytes.argtypes = [C.c_int, C.c_int]
-    lib.t2v_tsne_scratch_bytes.restype = C.c_size_t
-    lib.t2v_tsne_affinities.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
-    lib.t2v_tsne_gradient.argtypes = [vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
-    lib.t2v_tsne_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
-    lib.t2v_f0_yin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, vp]
-    lib.t2v_latent_scratch_bytes.argtypes = [C.c_int] * 5
-    lib.t2v_latent_scratch_bytes.restype = C.c_size_t
-    lib.t2v_latent_neighbours.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int] + [vp] * 7
-    lib.t2v_resample.argtypes = [vp, C.c_int, C.c_float, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
-    lib.t2v_trim_bounds.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, vp, C.c_int, vp, vp]
-    lib.t2v_crop_rows.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
-    lib.t2v_loudness_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_loudness_scratch_bytes.restype = C.c_size_t
-    lib.t2v_loudness.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
-    lib.t2v_scale_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
-    lib.t2v_phase_vocoder_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_phase_vocoder_scratch_bytes.restype = C.c_size_t
-    lib.t2v_phase_vocoder.argtypes = [vp, vp, vp] + [C.c_int] * 6 + [vp, vp, C.c_int, vp, vp]
-    lib.t2v_spectral_envelope.argtypes = [vp, vp] + [C.c_int] * 7 + [vp, vp, C.c_int, vp]
-    lib.t2v_alignment_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_alignment_scratch_bytes.restype = C.c_size_t
-    lib.t2v_alignment_stats.argtypes = [vp, C.c_longlong, C.c_longlong, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp,
-                                        C.c_int, vp, C.c_int, vp, vp, vp, vp]
-    lib.t2v_conv1d_stat_blocks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.t2v_conv1d_stat_blocks_bf16.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.t2v_conv1d_staged_launches.argtypes = []
-    lib.t2v_conv1d_staged_launches.restype = C.c_longlong
-    lib.t2v_conv1d_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv1d_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv1d_dw_scratch_floats.argtypes = [C.c_int] * 5
-    lib.t2v_conv1d_flip_weights.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.t2v_conv1d_fwd_bf16.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv1d_bwd_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_bn_act_fwd.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, vp]
-    lib.t2v_bn_act_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                   C.c_uint64, C.c_uint32, C.c_uint32, vp]
-    lib.t2v_bn_act_bwd_eval.argtypes = lib.t2v_bn_act_bwd.argtypes
-    lib.t2v_bn_act_fwd_len.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]
-    lib.t2v_mask_time.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_bilstm_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.t2v_bilstm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.t2v_gemm_f32.argtypes = [vp, C.c_long, C.c_long, vp, C.c_long, C.c_long, vp, vp, C.c_int, C.c_int, C.c_int,
-                                 C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, vp]
-    lib.t2v_gemm_bf16.argtypes = lib.t2v_gemm_f32.argtypes
-    lib.t2v_gemm_bf16_splitk.argtypes = lib.t2v_gemm_f32.argtypes[:-1] + [vp, vp]
-    lib.t2v_gemm_bf16_splitk_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_gemm_bf16_splitk_scratch_floats.restype = C.c_long
-    lib.t2v_gemm_f32_splitk.argtypes = lib.t2v_gemm_f32.argtypes[:-1] + [vp, vp]
-    lib.t2v_gemm_f32_batched.argtypes = [vp, C.c_long, C.c_long, C.c_long, vp, C.c_long, C.c_long, C.c_long, vp, C.c_long,
-                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_gemm_splitk_scratch_floats.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.t2v_gemm_splitk_scratch_floats.restype = C.c_long
-    lib.t2v_attn_wgrad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]     # 8 pointers
-    lib.t2v_attn_wgrad_scratch_floats.argtypes = []
-    lib.t2v_conv2d_s2_fwd.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv2d_s2_bwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv2d_s2_fwd_gemm.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv2d_s2_bwd_gemm.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    lib.t2v_conv2d_s2_gemm_scratch_floats.argtypes = [C.c_int] * 6
-    lib.t2v_conv2d_s2_gemm_scratch_floats.restype = C.c_long
-    lib.t2v_conv2d_s2_dw_scratch_floats.argtypes = [C.c_int] * 6
-    lib.t2v_gru_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.t2v_gru_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.t2v_conv2d_s2_fwd_ragged.argtypes = [vp, vp, vp, vp, vp] + [C.c_int] * 7 + [vp]
-    lib.t2v_conv2d_s2_fwd_gemm_ragged.argtypes = [vp, vp, vp, vp, vp, vp] + [C.c_int] * 7 + [vp]
-    lib.t2v_conv2d_s2_gemm_ragged_scratch_floats.argtypes = [C.c_int] * 6
-    lib.t2v_conv2d_s2_gemm_ragged_scratch_floats.restype = C.c_long
-    lib.t2v_gru_fwd_len.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.t2v_loss_fwd_bwd.argtypes = [vp] * 15 + [C.c_uint64, C.c_int, C.c_int, C.c_float, vp]
-    for name in EXPORTS:
-        getattr(lib, name)
+    for name, (restype, argtypes) in _ABI.prototypes.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib
 
@@ -400,12 +121,13 @@ class StepParams(object):
     binding of its own); stream=<torch.cuda.Stream>: bound to that stream only (t2v_set_step_params_stream), so two engines
     in one process never share a record."""
     RING = 256
-    FIELDS = {'lr': 2, 'bc1': 3, 'bc2s': 4, 'kl_weight': 5}
+    WORDS = C.sizeof(_StepRecord) // 4       # the record as 4-byte words: the 8-byte epoch, then fp32 slots
+    SLOTS = {n: getattr(_StepRecord, n).offset // 4 for n, t in _StepRecord._fields_ if t is C.c_float}
 
     def __init__(self, device, stream=None):
         lib = load_library()
-        self.host = torch.zeros(self.RING, 8, dtype=torch.float32).pin_memory()
-        self.dev = torch.zeros(8, dtype=torch.float32, device=device)
+        self.host = torch.zeros(self.RING, self.WORDS, dtype=torch.float32).pin_memory()
+        self.dev = torch.zeros(self.WORDS, dtype=torch.float32, device=device)
         self.cur = dict(epoch=0, lr=0.0, bc1=1.0, bc2s=1.0, kl_weight=0.0)
         self.dirty = True
         self._i = 0
@@ -446,7 +168,7 @@ class StepParams(object):
         slot = self.host[self._i % self.RING]
         self._i += 1
         slot.view(torch.int64)[0] = self.cur['epoch']
-        for k, i in self.FIELDS.items():
+        for k, i in self.SLOTS.items():
             slot[i] = self.cur[k]
         self.dev.copy_(slot, non_blocking=True)
         self.dirty = False
@@ -1689,7 +1411,7 @@ def mel_to_magnitude_nnls(mel, n_frames, mel_basis, pinv_basis, n_iters=100):
     return mag
 
 
-DTW_MAX_FRAMES = 2048                   # T2V_DTW_MAX_FRAMES of include/t2vae.h
+DTW_MAX_FRAMES = _ABI.define('T2V_DTW_MAX_FRAMES')
 DTW_SCRATCH_CAP = 256 << 20             # bytes of scratch one t2v_mel_dtw call may ask of the allocator; larger batches run in groups
 
 
@@ -1732,7 +1454,7 @@ def mel_dtw(x, nx, y, ny):
     return dist
 
 
-NCEP = 13                               # T2V_NCEP of include/t2vae.h
+NCEP = _ABI.define('T2V_NCEP')
 CEP_DTW_SCRATCH_CAP = 256 << 20         # bytes of decision table one t2v_cep_dtw_path call may ask of the allocator; larger batches run in groups
 ALIGNED_COUNTS = ('n_points', 'n_both', 'n_vde', 'n_gpe')
 ALIGNED_SUMS = ('sum_d', 'sum_e', 'sum_e2', 's_xx', 's_yy', 's_xy', 'sum_warp')
@@ -1862,7 +1584,7 @@ def aligned_scores(cx, nx, cy, ny, f0x=None, f0y=None, return_path=False):
     return AlignedScores(dist, K, counts, sums, path if return_path else None)
 
 
-F0_MAX_LAG = 400                        # T2V_F0_MAX_LAG of include/t2vae.h
+F0_MAX_LAG = _ABI.define('T2V_F0_MAX_LAG')
 F0_SAMPLE_RATE = 16000                  # the tracker's geometry is the front end's: 16 kHz, hop 256, window 1024
 F0_HOP = 256
 
@@ -1915,7 +1637,7 @@ def f0(y, lengths, fmin=60.0, fmax=500.0, threshold=0.1, return_aperiodicity=Fal
     return (hz, ap) if return_aperiodicity else hz
 
 
-RESAMPLE_MAX_TAPS = 32768               # T2V_RESAMPLE_MAX_TAPS of include/t2vae.h
+RESAMPLE_MAX_TAPS = _ABI.define('T2V_RESAMPLE_MAX_TAPS')
 TRIM_HOP = 256                          # the trim's frames are the front end's: hop 256, window 1024
 _RESAMPLE_TAPS = {}                     # (up, down, zeros, beta, rolloff) -> (half, host taps, {device: device taps})
 
@@ -2001,8 +1723,8 @@ def resample(x, lengths, sr_in, sr_out):
     return y, n_out
 
 
-TSM_MAX_RATIO = 1023                    # T2V_TSM_MAX_RATIO of include/t2vae.h: the largest numerator and denominator of a rate
-TSM_MAX_FRAMES = 1 << 20                # T2V_TSM_MAX_FRAMES
+TSM_MAX_RATIO = _ABI.define('T2V_TSM_MAX_RATIO')      # the largest numerator and denominator of a rate
+TSM_MAX_FRAMES = _ABI.define('T2V_TSM_MAX_FRAMES')
 TSM_HOP = 256                           # the STFT's hop, a quarter of its window
 _TSM_TABLES = {}                        # device -> the STFT tables of time_stretch
 
@@ -2142,8 +1864,8 @@ def _tsm_tables(device):
     return t
 
 
-ENV_MAX_ORDER = 256                      # T2V_ENV_MAX_ORDER of include/t2vae.h: the longest lifter, in cepstral bins
-ENV_MAX_ITERS = 32                       # T2V_ENV_MAX_ITERS: the most true-envelope iterations
+ENV_MAX_ORDER = _ABI.define('T2V_ENV_MAX_ORDER')      # the longest lifter, in cepstral bins
+ENV_MAX_ITERS = _ABI.define('T2V_ENV_MAX_ITERS')      # the most true-envelope iterations
 
 
 def _envelope_launch(who, mag, n_frames, order, iters, ratio, want_env, want_mag):
@@ -2333,8 +2055,8 @@ def crop(y, bounds, pcm16=False, return_stats=False):
     return out, counts, [(int(c), float(p)) for c, p in zip(s[:, 0].tolist(), peaks)]
 
 
-LOUDNESS_CHUNK = 64                     # T2V_LOUDNESS_CHUNK of include/t2vae.h: samples per lane of k_loud_filter
-LOUDNESS_TILE = 16384                   # T2V_LOUDNESS_TILE: samples per workgroup tile, between which the filter state is scanned
+LOUDNESS_CHUNK = _ABI.define('T2V_LOUDNESS_CHUNK')      # samples per lane of k_loud_filter
+LOUDNESS_TILE = _ABI.define('T2V_LOUDNESS_TILE')      # samples per workgroup tile, between which the filter state is scanned
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 48000
 LOUDNESS_OFFSET = -0.691                # BS.1770: a full-scale 997 Hz sine reads -3.01 LUFS
 _LOUDNESS_TABLES = {}                   # rate -> (host table, {device: device table})
@@ -2475,7 +2197,7 @@ def scale_rows(y, lengths, gains):
     return y
 
 
-ALIGN_FRAMES = 16                       # T2V_ALIGN_FRAMES of include/t2vae.h: frames per workgroup of k_align_scan
+ALIGN_FRAMES = _ABI.define('T2V_ALIGN_FRAMES')      # frames per workgroup of k_align_scan
 ALIGN_STATS = ('furthest', 'p_last', 'n_back', 'n_jump', 'longest_stall', 'n_uncovered', 'longest_gap')
 
 
@@ -2548,9 +2270,9 @@ def alignment_stats(alignments, n_frames, text_lengths, max_jump=3, cover_min=0.
     return AlignmentStats(path, mass, focus, stats)
 
 
-TSNE_MAX_POINTS = 16384                 # T2V_TSNE_MAX_POINTS of include/t2vae.h: P is dense fp32, 1 GiB there
+TSNE_MAX_POINTS = _ABI.define('T2V_TSNE_MAX_POINTS')      # P is dense fp32, 1 GiB there
 TSNE_MAX_DIM = 64
-TSNE_EXAG_ITERS = 250                   # T2V_TSNE_EXAG_ITERS
+TSNE_EXAG_ITERS = _ABI.define('T2V_TSNE_EXAG_ITERS')
 TSNE_KL_EVERY = 50
 
 
@@ -2644,11 +2366,11 @@ def tsne(x, perplexity=30.0, n_iter=1000, seed=0, init=None, return_trace=False)
     return (Y, trace) if return_trace else Y
 
 
-LATENT_MAX_POINTS = 16384               # T2V_LATENT_MAX_POINTS of include/t2vae.h
+LATENT_MAX_POINTS = _ABI.define('T2V_LATENT_MAX_POINTS')
 LATENT_MAX_DIM = 64
-LATENT_MAX_CLASSES = 8                  # T2V_LATENT_MAX_CLASSES
-LATENT_MAX_K = 32                       # T2V_LATENT_MAX_K
-LATENT_TILE = 128                       # T2V_LATENT_TILE: slice_rows is a multiple of it
+LATENT_MAX_CLASSES = _ABI.define('T2V_LATENT_MAX_CLASSES')
+LATENT_MAX_K = _ABI.define('T2V_LATENT_MAX_K')
+LATENT_TILE = _ABI.define('T2V_LATENT_TILE')      # slice_rows is a multiple of it
 
 LatentNeighbours = collections.namedtuple('LatentNeighbours', 'idx dist class_sum class_cnt rank')
 

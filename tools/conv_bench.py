@@ -6,7 +6,6 @@ import torch, t2v_hip
 from t2v_hip import _p, _stream, _check
 lib = t2v_hip.load_library()
 import ctypes as C
-lib.t2v_set_phase_profile.argtypes = [C.c_void_p]
 prof = torch.zeros(32, dtype=torch.int64, device='cuda')
 shapes = [('postnet 80->512', 6, 80, 512, 400), ('postnet 512->512', 6, 512, 512, 400), ('postnet 512->80', 6, 512, 80, 400),
           ('encoder 512->512', 6, 512, 512, 84), ('postnet 512->512 B16', 16, 512, 512, 400)]

@@ -4,7 +4,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tacotron2-vae_amd')); sys.path.insert(0, ROOT)
 import torch, t2v_hip, hparams as HP, model as M
 lib = t2v_hip.load_library()
-lib.t2v_set_phase_profile.argtypes = [C.c_void_p]
 buf = torch.zeros(32, dtype=torch.int64, device='cuda')
 lib.t2v_set_phase_profile(C.c_void_p(buf.data_ptr()))
 hp = HP.create_hparams(); torch.manual_seed(0)
