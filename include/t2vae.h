@@ -603,6 +603,29 @@ int t2v_gemm_bf16_splitk(const float* A, long sAi, long sAk, const float* B, lon
                          float* C, int ldc, int M, int N, int K, int relu, int accumulate, float p_drop,
                          uint64_t seed, uint32_t rng_stream, uint32_t rng_t, float* splitk_scratch, void* stream);
 
+/* Which kernel t2v_gemm_f32[_splitk] (bf16 = 0) / t2v_gemm_bf16[_splitk] (bf16 = 1) run for a product: the answer of the very
+ * function the launches are dispatched by, so it follows t2v_gemm_f32_set_mode and the T2V_GEMM_* / T2V_X3_* / T2V_BF16_GEMM_PLANES
+ * switches of the process.  a_mod16 / b_mod16 / scratch_mod16: the base addresses modulo 16; has_scratch: a split-K scratch is
+ * passed (the plain entry points pass none).  Returns a T2V_GEMM_ROUTE_* value (T2V_ERR_ARG for an empty product);
+ * *form (may be NULL): bit 0 = the kernel stages A along k, bit 1 = B along k (otherwise along the rows);
+ * *splits (may be NULL): k-splits launched, empty trailing ones included (1 = none); *k_per_split (may be NULL): split z sums
+ * k in [z * k_per_split, (z + 1) * k_per_split) (K when there is no split).  Host only: nothing is launched. */
+#define T2V_GEMM_ROUTE_F32_64 0          /* k_gemm_f32: 64x64 tile, fp32 MFMA */
+#define T2V_GEMM_ROUTE_F32_64_SPLITK 1   /* ... cut over k, the last workgroup of a tile sums the partials */
+#define T2V_GEMM_ROUTE_F32_BIG_128 2     /* k_gemm_f32_big: 128x128 tile */
+#define T2V_GEMM_ROUTE_F32_BIG_64 3      /* k_gemm_f32_big: 128x64 tile */
+#define T2V_GEMM_ROUTE_F32_X3 4          /* k_x3_split + k_gemm_x3p<3,2>: three bf16 planes per operand */
+#define T2V_GEMM_ROUTE_BF16_64 5         /* k_gemm_bf16: 64x64 tile */
+#define T2V_GEMM_ROUTE_BF16_64_SPLITK 6
+#define T2V_GEMM_ROUTE_BF16_BIG 7        /* k_gemm_bf16_big_rr: 128x128 tile */
+#define T2V_GEMM_ROUTE_BF16_BIG_SPLITK 8
+#define T2V_GEMM_ROUTE_BF16_PLANES 9     /* k_x3_split + k_gemm_x3p<1,4>: one pre-rounded bf16 plane per operand */
+#define T2V_GEMM_ROUTE_BF16_TO_F32_BIG 10 /* a bf16 call that k_gemm_f32_big takes (fp32 operands, nothing rounded) */
+#define T2V_GEMM_ROUTES 11
+int t2v_gemm_route(int M, int N, int K, long sAi, long sAk, long sBj, long sBk, int a_mod16, int b_mod16, int scratch_mod16,
+                   int has_scratch, int relu, float p_drop, int bf16, int* form, int* splits, int* k_per_split);
+const char* t2v_gemm_route_name(int route);
+
 
 /* ------------------------------------------------------------------ reference encoder / VAE / loss
  * t2v_conv2d_s2_* : Conv2d 3x3 stride 2 pad 1 of ReferenceEncoder (modules.py:45-57); coord != 0 appends the

@@ -397,11 +397,20 @@ static double gemm_big_waste(int M, int N, int BN) {
 }
 
 // the large-tile kernel needs 16-byte-aligned float4 runs along each operand's contiguous index
-static bool gemm_big_ok(const GemmArgs& a) {
+// (the dispatch and the route query both decide on this record: shape, element strides, base addresses modulo 16, epilogue flags)
+struct GemmShape {
+    int M, N, K;
+    long sAi, sAk, sBj, sBk;
+    unsigned a_mod, b_mod;      // (uintptr_t)A & 15, (uintptr_t)B & 15
+    bool relu, drop;
+    bool scratch;               // the caller handed scratch over
+    unsigned scr_mod;           // (uintptr_t)scratch & 15
+};
+static bool gemm_big_ok(const GemmShape& a) {
     if (a.M < GB_BM || a.N < 128 || a.K < 4) return false;
     // the tiles must still fill the chip: mid-size GEMMs (Prenet, BiLSTM projections: < 256 tiles of 128x64) keep the 64x64 kernel
     if ((long)((a.M + GB_BM - 1) / GB_BM) * ((a.N + 63) / 64) < 256) return false;
-    if (((uintptr_t)a.A | (uintptr_t)a.B) & 15) return false;
+    if ((a.a_mod | a.b_mod) & 15) return false;
     const bool akc = a.sAk == 1, bkc = a.sBk == 1;
     if (akc ? ((a.K & 3) || (a.sAi & 3)) : (a.sAi != 1 || (a.M & 3) || (a.sAk & 3))) return false;
     if (bkc ? ((a.K & 3) || (a.sBj & 3)) : (a.sBj != 1 || (a.N & 3) || (a.sBk & 3))) return false;
@@ -678,11 +687,11 @@ static bool gemm_bf16_big_operand_ok(long s_row, long s_k, int K, bool* kc) {
     if (s_k == 1 && !(s_row & 3) && !(K % GBB_BK)) { *kc = true; return true; }
     return false;
 }
-static bool gemm_bf16_big_ok(const GemmArgs& a, bool* akc, bool* bkc) {
-    if (a.relu || a.p_drop > 0.f) return false;
+static bool gemm_bf16_big_ok(const GemmShape& a, bool* akc, bool* bkc) {
+    if (a.relu || a.drop) return false;
     if (!gemm_bf16_big_operand_ok(a.sAi, a.sAk, a.K, akc) || !gemm_bf16_big_operand_ok(a.sBj, a.sBk, a.K, bkc)) return false;
     if (a.M < GBB_BM || a.N < GBB_BN || (a.M & 3) || (a.N & 3)) return false;
-    if (((uintptr_t)a.A | (uintptr_t)a.B) & 15) return false;
+    if ((a.a_mod | a.b_mod) & 15) return false;
     // (round 5: from 64 tiles on — the 64x64 kernel it would fall to runs these shapes at 20-35 TFLOP/s)
     return (long)((a.M + GBB_BM - 1) / GBB_BM) * ((a.N + GBB_BN - 1) / GBB_BN) >= 64;
 }
@@ -819,6 +828,110 @@ static bool gemm_bf16_planes_ok(int M, int N, int K) {
     static const int on = getenv("T2V_BF16_GEMM_PLANES") ? atoi(getenv("T2V_BF16_GEMM_PLANES")) : 1;
     return on && K >= 64 && gemm_x3_shape_ok(M, N, K);
 }
+
+// ---- which kernel takes a product.  ONE decision, made here for t2v_gemm_f32[_splitk] / t2v_gemm_bf16[_splitk] and answered to
+// t2v_gemm_route() from the same code: the launches below only carry out what a GemmRoute says.
+struct GemmRoute {
+    int route;          // T2V_GEMM_ROUTE_*
+    int form;           // bit 0: the kernel stages A along k, bit 1: B along k (else along the rows)
+    int splits;         // k-splits launched (gridDim.z), empty ones included; 1 = no split
+    int chunk;          // k per split (64x64, 128x128 bf16), stages per split (plane kernels); 0 = no split
+};
+// the plane kernels' k-splits as launched: whole stages per split, no empty split
+static void gemm_x3_launch_splits(int M, int N, int K, int np, GemmRoute* r) {
+    const int ns = gemm_x3_splits(M, N, K, np);
+    r->splits = 1; r->chunk = 0;
+    if (ns > 1) {
+        const int nst = (int)(gx_groups(K, np) / (np == 3 ? 2 : GX_NG1));
+        const int chunk = (nst + ns - 1) / ns, nz = (nst + chunk - 1) / chunk;         // no empty split
+        if (nz >= 2) { r->splits = nz; r->chunk = chunk; }
+    }
+}
+// k-splits of the kernels that cut K in multiples of their k-tile `bk`; trim: launch the non-empty splits only
+static void gemm_k_splits(int K, int ns, int bk, bool trim, GemmRoute* r) {
+    r->splits = 1; r->chunk = 0;
+    if (ns > 1) {
+        const int tiles_k = (K + bk - 1) / bk;
+        const int chunk = ((tiles_k + ns - 1) / ns) * bk, nz = trim ? (K + chunk - 1) / chunk : ns;
+        if (nz >= 2) { r->splits = nz; r->chunk = chunk; }
+    }
+}
+static GemmRoute gemm_route_f32(const GemmShape& s) {
+    GemmRoute r;
+    r.form = (s.sAk == 1 ? 1 : 0) | (s.sBk == 1 ? 2 : 0); r.splits = 1; r.chunk = 0;
+    if (s.scratch && gemm_x3_mode() && gemm_x3_shape_ok(s.M, s.N, s.K) && !(s.scr_mod & 15)) {
+        r.route = T2V_GEMM_ROUTE_F32_X3;
+        gemm_x3_launch_splits(s.M, s.N, s.K, 3, &r);
+        return r;
+    }
+    if (gemm_big_ok(s)) {
+        // (T2V_GEMM_NARROW=1, measurement: always the 128x64 tile — twice the tiles, so a launch that shares CUs with long
+        // small-grid kernels balances itself instead of waiting for its slowest single-tile workgroup)
+        static const int narrow = getenv("T2V_GEMM_NARROW") ? atoi(getenv("T2V_GEMM_NARROW")) : 0;
+        const bool wide = !narrow && gemm_big_waste(s.M, s.N, 128) <= gemm_big_waste(s.M, s.N, 64) + 1e-6;
+        r.route = wide ? T2V_GEMM_ROUTE_F32_BIG_128 : T2V_GEMM_ROUTE_F32_BIG_64;
+        return r;
+    }
+    // (the fp32 64x64 kernel keeps gridDim.z = ns: a trailing split may be empty, its partial tile is zero)
+    gemm_k_splits(s.K, s.scratch ? gemm_splits(s.M, s.N, s.K) : 1, GM_BK, false, &r);
+    r.route = r.splits > 1 ? T2V_GEMM_ROUTE_F32_64_SPLITK : T2V_GEMM_ROUTE_F32_64;
+    return r;
+}
+static GemmRoute gemm_route_bf16(const GemmShape& s) {
+    GemmRoute r;
+    r.form = (s.sAk == 1 ? 1 : 0) | (s.sBk == 1 ? 2 : 0); r.splits = 1; r.chunk = 0;
+    if (s.scratch && !(s.scr_mod & 15) && gemm_bf16_planes_ok(s.M, s.N, s.K)) {
+        r.route = T2V_GEMM_ROUTE_BF16_PLANES;
+        gemm_x3_launch_splits(s.M, s.N, s.K, 1, &r);
+        return r;
+    }
+    bool big_akc = false, big_bkc = false;
+    if (gemm_bf16_big_ok(s, &big_akc, &big_bkc)) {
+        r.form = (big_akc ? 1 : 0) | (big_bkc ? 2 : 0);
+        gemm_k_splits(s.K, s.scratch ? gemm_bf16_big_splits(s.M, s.N, s.K) : 1, GBB_BK, true, &r);
+        r.route = r.splits > 1 ? T2V_GEMM_ROUTE_BF16_BIG_SPLITK : T2V_GEMM_ROUTE_BF16_BIG;
+        return r;
+    }
+    // large products in an operand form the 128x128 bf16 kernel does not take (the hoisted attention_rnn input term and the
+    // Prenet data gradient at B = 16: 13.4 GFLOP each): the 64x64 bf16 kernel ran them at ~35 TFLOP/s (361 / 399 us), the
+    // large-tile FP32 kernel does ~100 — bf16_run takes whichever is faster, fp32 operands lose no accuracy
+    if (gemm_big_ok(s)) { r.route = T2V_GEMM_ROUTE_BF16_TO_F32_BIG; return r; }
+    // the 64x64 kernel: one tile of prefetch per workgroup, so a grid of less than one workgroup per CU with a deep K is bound
+    // by the memory round trip per k-tile (the BiLSTM data gradients at B = 16: 168 workgroups, 32 k-tiles, 90-120 us for
+    // 1.4 GFLOP) — split over k like the fp32 kernel
+    gemm_k_splits(s.K, s.scratch ? gemm_splits(s.M, s.N, s.K) : 1, GM_BK, true, &r);
+    r.route = r.splits > 1 ? T2V_GEMM_ROUTE_BF16_64_SPLITK : T2V_GEMM_ROUTE_BF16_64;
+    return r;
+}
+static GemmShape gemm_shape_of(const GemmArgs& a, const float* scratch) {
+    GemmShape s;
+    s.M = a.M; s.N = a.N; s.K = a.K; s.sAi = a.sAi; s.sAk = a.sAk; s.sBj = a.sBj; s.sBk = a.sBk;
+    s.a_mod = (unsigned)((uintptr_t)a.A & 15); s.b_mod = (unsigned)((uintptr_t)a.B & 15);
+    s.relu = a.relu != 0; s.drop = a.p_drop > 0.f;
+    s.scratch = scratch != nullptr; s.scr_mod = (unsigned)((uintptr_t)scratch & 15);
+    return s;
+}
+extern "C" int t2v_gemm_route(int M, int N, int K, long sAi, long sAk, long sBj, long sBk, int a_mod16, int b_mod16, int scratch_mod16,
+                              int has_scratch, int relu, float p_drop, int bf16, int* form, int* splits, int* k_per_split) {
+    if (M < 1 || N < 1 || K < 1) return T2V_ERR_ARG;
+    GemmShape s;
+    s.M = M; s.N = N; s.K = K; s.sAi = sAi; s.sAk = sAk; s.sBj = sBj; s.sBk = sBk;
+    s.a_mod = (unsigned)a_mod16 & 15; s.b_mod = (unsigned)b_mod16 & 15;
+    s.relu = relu != 0; s.drop = p_drop > 0.f;
+    s.scratch = has_scratch != 0; s.scr_mod = (unsigned)scratch_mod16 & 15;
+    const GemmRoute r = bf16 ? gemm_route_bf16(s) : gemm_route_f32(s);
+    if (form) *form = r.form;
+    if (splits) *splits = r.splits;
+    // (the plane kernels cut K in stages: 16 k of three planes, 8 GX_NG1 k of one)
+    const int unit = r.route == T2V_GEMM_ROUTE_F32_X3 ? GX_SK : r.route == T2V_GEMM_ROUTE_BF16_PLANES ? 8 * GX_NG1 : 1;
+    if (k_per_split) *k_per_split = r.splits > 1 ? r.chunk * unit : K;
+    return r.route;
+}
+extern "C" const char* t2v_gemm_route_name(int route) {
+    static const char* const names[T2V_GEMM_ROUTES] = {"f32_64", "f32_64_splitk", "f32_big_128", "f32_big_64", "f32_x3", "bf16_64",
+                                                       "bf16_64_splitk", "bf16_big", "bf16_big_splitk", "bf16_planes", "bf16_to_f32_big"};
+    return route >= 0 && route < T2V_GEMM_ROUTES ? names[route] : "?";
+}
 static void gx_split_launch(const float* src, long s_row, long s_k, int rows, int K, uint4* planes, long Rp, long G, long row_off, hipStream_t stream,
                             int np = 3) {
     // (planes + row_off: the operand's rows start at slot row_off of every k-group — column blocks of one B operand gathered from
@@ -833,7 +946,7 @@ static void gx_split_launch(const float* src, long s_row, long s_k, int rows, in
         else k_x3_split<false, 1><<<grid, 256, 0, stream>>>(src, s_row, s_k, rows, K, planes + row_off, Rp, G);
     }
 }
-static int gemm_x3_run(const GemmArgs& g, float* scratch, hipStream_t stream, int np = 3) {
+static int gemm_x3_run(const GemmArgs& g, float* scratch, hipStream_t stream, const GemmRoute& rt, int np = 3) {
     const int M = g.M, N = g.N, K = g.K;
     uint4* Ap = (uint4*)scratch;
     uint4* Bp = Ap + gx_plane_slots(M, K, np);
@@ -852,15 +965,12 @@ static int gemm_x3_run(const GemmArgs& g, float* scratch, hipStream_t stream, in
     a.st_chunk = 0; a.part = nullptr; a.tile_ctr = nullptr;
     a.done_ctr = nullptr; a.done_prod = 0; a.done_cap = 0;
     dim3 gb(a.ntiles, 1, 1);
-    const int ns = gemm_x3_splits(M, N, K, np);
-    if (ns > 1) {
-        const int nst = (int)(G / (np == 3 ? 2 : GX_NG1));
-        a.st_chunk = (nst + ns - 1) / ns;
-        gb.z = (unsigned)((nst + a.st_chunk - 1) / a.st_chunk);         // no empty split
+    if (rt.splits > 1) {
+        a.st_chunk = rt.chunk;
+        gb.z = (unsigned)rt.splits;
         a.part = scratch + gemm_x3_plane_floats(M, N, K, np);
         a.tile_ctr = t2v_arrival_counters(a.ntiles);
         if (!a.tile_ctr) return T2V_ERR_LAUNCH;
-        if (gb.z < 2) { a.st_chunk = 0; a.part = nullptr; a.tile_ctr = nullptr; gb.z = 1; }
     }
     if (np == 3) k_gemm_x3p<3, 2><<<gb, 256, 0, stream>>>(a);
     else k_gemm_x3p<1, GX_NG1><<<gb, 256, 0, stream>>>(a);
@@ -1032,47 +1142,27 @@ static int gemm_bf16_impl(const float* A, long sAi, long sAk, const float* B, lo
     a.M = M; a.N = N; a.K = K; a.ldc = ldc; a.relu = relu; a.accumulate = accumulate;
     a.p_drop = p_drop; a.seed = seed; a.rng_stream = rng_stream; a.rng_t = rng_t; a.step = t2v_step_for(stream);
     a.kz_chunk = 0; a.part = nullptr; a.nbatch = 1; a.sAb = a.sBb = a.sCb = 0; a.nsub = 1; a.sAs = a.sBs = 0; a.bias_row = 0; a.tile_ctr = nullptr;
-    if (splitk_scratch && !((uintptr_t)splitk_scratch & 15) && gemm_bf16_planes_ok(M, N, K))
-        return gemm_x3_run(a, splitk_scratch, stream, 1);
-    bool big_akc = false, big_bkc = false;
-    if (gemm_bf16_big_ok(a, &big_akc, &big_bkc)) {
-        const int ns = splitk_scratch ? gemm_bf16_big_splits(M, N, K) : 1;
-        dim3 gb((N + GBB_BN - 1) / GBB_BN, (M + GBB_BM - 1) / GBB_BM, ns);
-        if (ns > 1) {
-            const int tiles_k = (K + GBB_BK - 1) / GBB_BK;
-            a.kz_chunk = ((tiles_k + ns - 1) / ns) * GBB_BK;
-            gb.z = (unsigned)((K + a.kz_chunk - 1) / a.kz_chunk);      // no empty split
-            a.part = splitk_scratch;
-            a.tile_ctr = t2v_arrival_counters((int)(gb.x * gb.y));
-            if (!a.tile_ctr) return T2V_ERR_LAUNCH;
-            if (gb.z < 2) { a.kz_chunk = 0; a.part = nullptr; a.tile_ctr = nullptr; gb.z = 1; }
-        }
-        if (big_akc && big_bkc) k_gemm_bf16_big_rr<true, true><<<gb, 256, 0, stream>>>(a);
-        else if (big_akc) k_gemm_bf16_big_rr<true, false><<<gb, 256, 0, stream>>>(a);
-        else if (big_bkc) k_gemm_bf16_big_rr<false, true><<<gb, 256, 0, stream>>>(a);
-        else k_gemm_bf16_big_rr<false, false><<<gb, 256, 0, stream>>>(a);
-        return t2v_check_launch();
-    }
-    // large products in an operand form the 128x128 bf16 kernel does not take (the hoisted attention_rnn input term and the
-    // Prenet data gradient at B = 16: 13.4 GFLOP each): the 64x64 bf16 kernel ran them at ~35 TFLOP/s (361 / 399 us), the
-    // large-tile FP32 kernel does ~100 — bf16_run takes whichever is faster, fp32 operands lose no accuracy
-    if (gemm_big_ok(a))
+    const GemmRoute rt = gemm_route_bf16(gemm_shape_of(a, splitk_scratch));
+    if (rt.route == T2V_GEMM_ROUTE_BF16_PLANES) return gemm_x3_run(a, splitk_scratch, stream, rt, 1);
+    if (rt.route == T2V_GEMM_ROUTE_BF16_TO_F32_BIG)
         return t2v_gemm_f32(A, sAi, sAk, B, sBj, sBk, bias, C, ldc, M, N, K, relu, accumulate, p_drop, seed, rng_stream, rng_t, stream_);
-    // the 64x64 kernel: one tile of prefetch per workgroup, so a grid of less than one workgroup per CU with a deep K is bound
-    // by the memory round trip per k-tile (the BiLSTM data gradients at B = 16: 168 workgroups, 32 k-tiles, 90-120 us for
-    // 1.4 GFLOP) — split over k like the fp32 kernel
-    const int ns = splitk_scratch ? gemm_splits(M, N, K) : 1;
-    dim3 grid((N + GM_BN - 1) / GM_BN, (M + GM_BM - 1) / GM_BM, ns);
-    if (ns > 1) {
-        const int tiles_k = (K + GM_BK - 1) / GM_BK;
-        a.kz_chunk = ((tiles_k + ns - 1) / ns) * GM_BK;
-        grid.z = (unsigned)((K + a.kz_chunk - 1) / a.kz_chunk);
+    const bool big = rt.route == T2V_GEMM_ROUTE_BF16_BIG || rt.route == T2V_GEMM_ROUTE_BF16_BIG_SPLITK;
+    const int bm = big ? GBB_BM : GM_BM, bn = big ? GBB_BN : GM_BN;
+    dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, rt.splits);
+    if (rt.splits > 1) {
+        a.kz_chunk = rt.chunk;
         a.part = splitk_scratch;
         a.tile_ctr = t2v_arrival_counters((int)(grid.x * grid.y));
         if (!a.tile_ctr) return T2V_ERR_LAUNCH;
-        if (grid.z < 2) { a.kz_chunk = 0; a.part = nullptr; a.tile_ctr = nullptr; grid.z = 1; }
     }
-    const bool akc = sAk == 1, bkc = sBk == 1;
+    const bool akc = rt.form & 1, bkc = (rt.form & 2) != 0;
+    if (big) {
+        if (akc && bkc) k_gemm_bf16_big_rr<true, true><<<grid, 256, 0, stream>>>(a);
+        else if (akc) k_gemm_bf16_big_rr<true, false><<<grid, 256, 0, stream>>>(a);
+        else if (bkc) k_gemm_bf16_big_rr<false, true><<<grid, 256, 0, stream>>>(a);
+        else k_gemm_bf16_big_rr<false, false><<<grid, 256, 0, stream>>>(a);
+        return t2v_check_launch();
+    }
     if (akc && bkc) k_gemm_bf16<true, true><<<grid, 256, 0, stream>>>(a);
     else if (akc) k_gemm_bf16<true, false><<<grid, 256, 0, stream>>>(a);
     else if (bkc) k_gemm_bf16<false, true><<<grid, 256, 0, stream>>>(a);
@@ -1105,14 +1195,11 @@ static int gemm_f32_impl(const float* A, long sAi, long sAk, const float* B, lon
     a.M = M; a.N = N; a.K = K; a.ldc = ldc; a.relu = relu; a.accumulate = accumulate;
     a.p_drop = p_drop; a.seed = seed; a.rng_stream = rng_stream; a.rng_t = rng_t; a.step = t2v_step_for(stream);
     a.kz_chunk = 0; a.part = nullptr; a.nbatch = 1; a.sAb = a.sBb = a.sCb = 0; a.nsub = 1; a.sAs = a.sBs = 0; a.bias_row = 0; a.tile_ctr = nullptr;
-    const bool akc = sAk == 1, bkc = sBk == 1;
-    if (splitk_scratch && gemm_x3_mode() && gemm_x3_shape_ok(M, N, K) && !((uintptr_t)splitk_scratch & 15))
-        return gemm_x3_run(a, splitk_scratch, stream);
-    if (gemm_big_ok(a)) {
-        // (T2V_GEMM_NARROW=1, measurement: always the 128x64 tile — twice the tiles, so a launch that shares CUs with long
-        // small-grid kernels balances itself instead of waiting for its slowest single-tile workgroup)
-        static const int narrow = getenv("T2V_GEMM_NARROW") ? atoi(getenv("T2V_GEMM_NARROW")) : 0;
-        const bool wide = !narrow && gemm_big_waste(M, N, 128) <= gemm_big_waste(M, N, 64) + 1e-6;
+    const GemmRoute rt = gemm_route_f32(gemm_shape_of(a, splitk_scratch));
+    const bool akc = rt.form & 1, bkc = (rt.form & 2) != 0;
+    if (rt.route == T2V_GEMM_ROUTE_F32_X3) return gemm_x3_run(a, splitk_scratch, stream, rt);
+    if (rt.route == T2V_GEMM_ROUTE_F32_BIG_128 || rt.route == T2V_GEMM_ROUTE_F32_BIG_64) {
+        const bool wide = rt.route == T2V_GEMM_ROUTE_F32_BIG_128;
         const int BN = wide ? 128 : 64;
         dim3 gb((N + BN - 1) / BN, (M + GB_BM - 1) / GB_BM);
 #define T2V_BIG(AK, BK)                                                             \
@@ -1125,11 +1212,9 @@ static int gemm_f32_impl(const float* A, long sAi, long sAk, const float* B, lon
 #undef T2V_BIG
         return t2v_check_launch();
     }
-    const int ns = splitk_scratch ? gemm_splits(M, N, K) : 1;
-    dim3 grid((N + GM_BN - 1) / GM_BN, (M + GM_BM - 1) / GM_BM, ns);
-    if (ns > 1) {
-        const int tiles_k = (K + GM_BK - 1) / GM_BK;
-        a.kz_chunk = ((tiles_k + ns - 1) / ns) * GM_BK;
+    dim3 grid((N + GM_BN - 1) / GM_BN, (M + GM_BM - 1) / GM_BM, rt.splits);
+    if (rt.splits > 1) {
+        a.kz_chunk = rt.chunk;
         a.part = splitk_scratch;
         a.tile_ctr = t2v_arrival_counters((int)(grid.x * grid.y));
         if (!a.tile_ctr) return T2V_ERR_LAUNCH;
