@@ -440,29 +440,11 @@ static void bn_bwd_launch(BnBwdArgs& a, hipStream_t stream) {
 
 // library-owned ring for the partial statistics above (a few hundred floats per launch; a slice comes round again 4 MB later —
 // a captured graph keeps the slices of its nodes, and graphs / eager steps of one engine never run at the same time)
-#include <atomic>
+#include "t2v_ring.h"
 static float* bn_part_scratch(size_t floats) {
     constexpr size_t RING = (size_t)1 << 20;
-    static float* ring = nullptr;
-    static std::atomic<size_t> pos{0};
-    static std::atomic<int> state{0};
-    floats = (floats + 63) & ~(size_t)63;
-    if (floats > RING / 4) return nullptr;
-    if (state.load(std::memory_order_acquire) != 2) {
-        int expect = 0;
-        if (state.compare_exchange_strong(expect, 1)) {
-            float* p = nullptr;
-            if (hipMalloc((void**)&p, RING * sizeof(float)) != hipSuccess) { state.store(0); return nullptr; }
-            ring = p;
-            state.store(2, std::memory_order_release);
-        } else {
-            while (state.load(std::memory_order_acquire) == 1) { }
-            if (state.load() != 2) return nullptr;
-        }
-    }
-    size_t at = pos.fetch_add(floats) % RING;
-    if (at + floats > RING) { pos.store(floats); at = 0; }
-    return ring + at;
+    static T2VRing<float, RING, RING / 4, false> ring;
+    return ring.take((floats + 63) & ~(size_t)63);
 }
 
 extern "C" int t2v_bn_act_fwd(const float* y, const float* stat_part, int nblk, const float* gamma, const float* beta,

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_ring.h"
 #include "t2v_coop.h"
 #include "t2v_x3.h"
 
@@ -1033,10 +1034,6 @@ __global__ __launch_bounds__(256) void k_conv5_dw_bf16(ConvTiledArgs a) {
     }
 }
 
-// Output positions per workgroup (BN = 32/48/64/80/96).  Cost model: workgroups run in rounds of one per CU; a
-// workgroup's time per k-tile is its MFMA work (~BN) plus the fixed staging cost (~40 in the same units).  Small
-// problems (encoder bank: 6 x 84 positions; 80-row layers) therefore take narrow tiles — more workgroups in the one
-// round they need — and the big Postnet layers the width that divides T (80 for T=400: 240 workgroups).
 // fixed-order sum of the K-split partials of the weight gradient
 __global__ void k_conv5_dw_reduce(const float* __restrict__ part, float* __restrict__ dw, int n, int nsplit) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1046,6 +1043,8 @@ __global__ void k_conv5_dw_reduce(const float* __restrict__ part, float* __restr
     dw[i] = s;
 }
 
+// positions per k-tile of the weight gradient, 80 or 96: whichever pads T less
+static inline int conv5_dw_bt(int T) { return (T + 79) / 80 * 80 <= (T + 95) / 96 * 96 ? 80 : 96; }
 // K-splits of the weight gradient: only when the (row tile, channel block) grid is far from filling the chip
 // Round 5: with ONE workgroup per CU every k-tile waits for its own global loads (one tile of prefetch); cut along K until several
 // workgroups share a CU, the launch alone runs 512->512 at B = 6, T = 400 in 83 instead of 107 us (fp32) and 62 instead of 100 us
@@ -1053,10 +1052,9 @@ __global__ void k_conv5_dw_reduce(const float* __restrict__ part, float* __restr
 // the bf16 kernel (bf16 B = 16 step 13.84 -> 13.78 ms): behind the reverse pass four streams share the chip and already fill each
 // other's stalls — the fp32 step got 0.06 ms SLOWER with the extra workgroups and reduce launches (same-box A/B against the
 // round-4 tree), so the fp32 kernel keeps its rule (split only while the launch does not fill the chip)
-static inline int conv5_dw_splits(int B, int Cin, int T, int Cout, bool bf16 = false) {
+static inline int conv5_dw_splits(int B, int Cin, int T, int Cout, int BT, bool bf16) {
     const int wgs = (Cin / 16) * ((Cout + CT_BM - 1) / CT_BM);
-    const int c80 = ((T + 79) / 80), c96 = ((T + 95) / 96);
-    const int nkt = B * (c80 * 80 <= c96 * 96 ? c80 : c96);
+    const int nkt = B * ((T + BT - 1) / BT);
     // (T2V_CONV_DW_SPLITS = target workgroups per launch, measurement override)
     static const int want_env = getenv("T2V_CONV_DW_SPLITS") ? atoi(getenv("T2V_CONV_DW_SPLITS")) : 0;
     const int want = want_env > 0 ? want_env : (bf16 ? 8 * T2V_NWG : T2V_NWG);
@@ -1067,33 +1065,20 @@ static inline int conv5_dw_splits(int B, int Cin, int T, int Cout, bool bf16 = f
 
 // scratch of the split launches: slices of one ring (a captured graph keeps the slices of its nodes; a slice comes round again
 // 64 MB of partial tiles later, long after its launch has retired)
-#include <atomic>
 static float* conv_ks_scratch(size_t floats) {
     constexpr size_t RING = (size_t)16 << 20;       // floats (64 MB)
-    static float* ring = nullptr;
-    static std::atomic<size_t> pos{0};
-    static std::atomic<int> state{0};
-    floats = (floats + 63) & ~(size_t)63;
-    if (floats > RING / 4) return nullptr;
-    if (state.load(std::memory_order_acquire) != 2) {
-        int expect = 0;
-        if (state.compare_exchange_strong(expect, 1)) {
-            float* p = nullptr;
-            if (hipMalloc((void**)&p, RING * sizeof(float)) != hipSuccess) { state.store(0); return nullptr; }
-            ring = p;
-            state.store(2, std::memory_order_release);
-        } else {
-            while (state.load(std::memory_order_acquire) == 1) { }
-            if (state.load() != 2) return nullptr;
-        }
-    }
-    size_t at = pos.fetch_add(floats) % RING;
-    if (at + floats > RING) { pos.store(floats); at = 0; }
-    return ring + at;
+    static T2VRing<float, RING, RING / 4, false> ring;
+    return ring.take((floats + 63) & ~(size_t)63);
 }
 
+// Output positions per workgroup (BN = 32/48/64/80/96).  Cost model: workgroups run in rounds of one per CU; a
+// workgroup's time per k-tile is its MFMA work (~BN) plus the fixed staging cost (~40 in the same units).  Small
+// problems (encoder bank: 6 x 84 positions; 80-row layers) therefore take narrow tiles — more workgroups in the one
+// round they need — and the big Postnet layers the width that divides T (80 for T=400: 240 workgroups).
+// T2V_CONV_BN (measurement), read once: 32 | 48 | 64 | 80 | 96 = that width for every launch; set at all = no channel split
+static inline const char* conv5_bn_env() { static const char* const e = getenv("T2V_CONV_BN"); return e; }
 static inline int conv5_pick_bn(int T, int B, int M) {
-    if (const char* e = getenv("T2V_CONV_BN")) { const int v = atoi(e); if (v == 32 || v == 48 || v == 64 || v == 80 || v == 96) return v; }
+    if (const char* e = conv5_bn_env()) { const int v = atoi(e); if (v == 32 || v == 48 || v == 64 || v == 80 || v == 96) return v; }
     const int cands[5] = {32, 48, 64, 80, 96};
     int best = 80;
     long best_cost = -1;
@@ -1111,7 +1096,7 @@ static inline int conv5_pick_bn_ks(int T, int B, int M, int Cin, int* ks) {
     static const int ksplit_on = getenv("T2V_CONV_KSPLIT") ? atoi(getenv("T2V_CONV_KSPLIT")) : 1;
     *ks = 1;
     const int bn1 = conv5_pick_bn(T, B, M);
-    if (!ksplit_on || Cin < 256 || getenv("T2V_CONV_BN")) return bn1;
+    if (!ksplit_on || Cin < 256 || conv5_bn_env()) return bn1;
     const int cands[5] = {32, 48, 64, 80, 96};
     const long w1 = (long)B * ((T + bn1 - 1) / bn1) * ((M + CT_BM - 1) / CT_BM);
     long best_cost = 2 * ((w1 + T2V_NWG - 1) / T2V_NWG) * (bn1 + 40);         // (costs doubled: halves stay integers)
@@ -1126,80 +1111,78 @@ static inline int conv5_pick_bn_ks(int T, int B, int M, int Cin, int* ks) {
     }
     return best;
 }
-static inline bool conv5_tiled_ok(int Cin, int KS) { return KS == 5 && Cin % 16 == 0; }
-// round 6 (conv_x3.hip): fp32 forward / data gradient on the bf16 matrix cores from exactly 3-way-split operands
-bool t2v_conv5_x3_ok(int B, int Cin, int T, int Cout, int KS);
+// round 6 (conv_x3.hip): forward / data gradient on the bf16 matrix cores from operands cut into np planes — 3: fp32, exactly
+// (x3); 1: bf16_run, rounded once
+bool t2v_conv5_planes_ok(int B, int Cin, int T, int Cout, int KS, int np);
 int t2v_conv5_x3_stat_blocks(int B, int T);
 int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B, int Cin, int T, int M,
                      hipStream_t stream, int np);
-bool t2v_conv5_planes_bf16_ok(int B, int Cin, int T, int Cout, int KS);
 
-static std::atomic<long long> g_conv5_staged_launches{0};
-extern "C" long long t2v_conv1d_staged_launches(void) { return g_conv5_staged_launches.load(std::memory_order_relaxed); }
-
-static void launch_conv5_fwd(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B,
-                             int Cin, int T, int M, hipStream_t stream) {
+// ---- which kernel takes a convolution.  ONE decision, made here for t2v_conv1d_fwd / _bwd / _fwd_bf16 / _bwd_bf16 and answered
+// to t2v_conv1d_stat_blocks[_bf16], t2v_conv1d_dw_scratch_floats and t2v_conv1d_takes_x3 from the same code: the launches below
+// only carry out what a ConvRoute says.
+enum { CONV_OP_FWD, CONV_OP_DX, CONV_OP_DW };
+enum { CONV_K_GEMM,         // k_conv_gemm: any Cin, KS = 3 or 5
+       CONV_K_FWD,          // k_conv5_fwd
+       CONV_K_FWD_DMA,      // k_conv5_fwd_dma
+       CONV_K_X3,           // k_conv5_x3<3, 2>
+       CONV_K_BF16,         // k_conv5_fwd_bf16
+       CONV_K_BF16K32,      // k_conv5_fwd_bf16k32
+       CONV_K_PLANE1,       // k_conv5_x3<1, 4>
+       CONV_K_DW,           // k_conv5_dw
+       CONV_K_DW_BF16 };    // k_conv5_dw_bf16
+struct ConvRoute {
+    int op;                 // CONV_OP_*
+    int B, Cin, T, M, KS;   // the convolution as it runs: a data gradient is the convolution Cout -> Cin of dY with the flipped, transposed weights
+    int family;             // CONV_K_*
+    int fallback;           // CONV_K_PLANE1 as a data gradient: the tiled family that runs instead when the library's ring has no slice
+                            // for the flipped weights (the one choice left to the launch; no BatchNorm partials depend on it)
+    int tile;               // forward / data gradient on the tiled kernels: NTW (16 positions each; under the plane kernels: of `fallback`);
+                            // tiled weight gradient: positions per k-tile BT, 80 or 96
+    int ksplit;             // k_conv5_fwd[_dma]: 2 = the input channels are cut in halves (gridDim.z), else 1
+    int dw_splits;          // weight gradient: k-splits (gridDim.z), their partials summed by k_conv5_dw_reduce; 1 = none
+    int stat_blocks;        // forward: BatchNorm partial blocks (rows of stat_part) the launch writes
+    int dw_scratch_floats;  // weight gradient: floats of dw_scratch the launch needs (0: none)
+};
+// bf16: the bf16_run entry points.  w_aligned: the weights the kernel reads start on a 16-byte boundary (k_conv5_fwd_dma needs it)
+static ConvRoute conv_route(int op, int B, int Cin, int T, int Cout, int KS, bool bf16, bool w_aligned) {
+    ConvRoute r;
+    r.op = op; r.B = B; r.T = T; r.KS = KS;
+    r.Cin = op == CONV_OP_DX ? Cout : Cin;
+    r.M = op == CONV_OP_DX ? Cin : Cout;
+    r.family = r.fallback = CONV_K_GEMM;
+    r.tile = 0; r.ksplit = 1; r.dw_splits = 1; r.dw_scratch_floats = 0;
+    r.stat_blocks = op == CONV_OP_DW ? 0 : (B * T + CG_BN - 1) / CG_BN;
+    if (KS != 5 || r.Cin % 16) return r;            // the tiled kernels: k = 5, whole 16-channel blocks
+    if (op == CONV_OP_DW) {
+        r.family = bf16 ? CONV_K_DW_BF16 : CONV_K_DW;
+        r.tile = conv5_dw_bt(T);
+        r.dw_splits = conv5_dw_splits(B, Cin, T, Cout, r.tile, bf16);
+        r.dw_scratch_floats = r.dw_splits > 1 ? r.dw_splits * Cout * Cin * 5 : 0;
+        return r;
+    }
+    // (the bf16 kernels keep the tile width of the fp32 ones and never cut the input channels)
     int ks = 1;
-    const int BN = conv5_pick_bn_ks(T, B, M, Cin, &ks);
-    ConvTiledArgs a;
-    a.W = W; a.X = X; a.dY = nullptr; a.bias = bias; a.Y = Y; a.stat_part = stat_part;
-    a.B = B; a.Cin = Cin; a.T = T; a.M = M; a.tiles_per_item = (T + BN - 1) / BN;
-    a.prof = g_t2v_prof;
-    a.ks_part = nullptr; a.ks_ctr = nullptr;
-    dim3 grid(B * a.tiles_per_item, (M + CT_BM - 1) / CT_BM);
-    // a launch that leaves half the chip idle and has a deep K: the input channels are cut in two (T2V_CONV_KSPLIT=0 switches
-    // it off for measurements)
-    const long ntile = (long)grid.x * grid.y;
-    if (ks == 2) {
-        const size_t pf = (size_t)2 * ntile * 256 * 4 * (BN / 16);
-        a.ks_part = conv_ks_scratch(pf);
-        a.ks_ctr = a.ks_part ? t2v_arrival_counters((int)ntile) : nullptr;
-        if (a.ks_part && a.ks_ctr) grid.z = 2; else a.ks_part = nullptr;
+    const int BN = conv5_pick_bn_ks(T, B, r.M, r.Cin, &ks);
+    r.tile = BN / 16;
+    r.stat_blocks = B * ((T + BN - 1) / BN);
+    if (bf16) {
+        static const int k32 = getenv("T2V_CONV_BF16_K32") ? atoi(getenv("T2V_CONV_BF16_K32")) : 1;      // 0: the 16-channel kernel (measurement)
+        r.family = k32 && r.Cin % 32 == 0 ? CONV_K_BF16K32 : CONV_K_BF16;
+    } else {
+        // T2V_CONV_STAGING=0: the register-staged kernel (the reference of tests/test_conv5_staging_gpu.py and of the A/B runs).
+        // Weights that are not 16-byte aligned take it too
+        static const int staging = getenv("T2V_CONV_STAGING") ? atoi(getenv("T2V_CONV_STAGING")) : 1;
+        r.family = staging && w_aligned ? CONV_K_FWD_DMA : CONV_K_FWD;
+        r.ksplit = ks;
     }
-    // T2V_CONV_STAGING=0: the register-staged kernel (the reference of tests/test_conv5_staging_gpu.py and of the A/B runs).
-    // Weights that are not 16-byte aligned take it too; g_conv5_staged_launches lets a caller see which kernel its launches took
-    static const int staging = getenv("T2V_CONV_STAGING") ? atoi(getenv("T2V_CONV_STAGING")) : 1;
-    if (staging && ((size_t)W & 15) == 0) {
-        g_conv5_staged_launches.fetch_add(1, std::memory_order_relaxed);
-        if (BN == 32) k_conv5_fwd_dma<2><<<grid, 256, 0, stream>>>(a);
-        else if (BN == 48) k_conv5_fwd_dma<3><<<grid, 256, 0, stream>>>(a);
-        else if (BN == 64) k_conv5_fwd_dma<4><<<grid, 256, 0, stream>>>(a);
-        else if (BN == 80) k_conv5_fwd_dma<5><<<grid, 256, 0, stream>>>(a);
-        else k_conv5_fwd_dma<6><<<grid, 256, 0, stream>>>(a);
-        return;
+    if (t2v_conv5_planes_ok(B, r.Cin, T, r.M, KS, bf16 ? 1 : 3)) {
+        r.fallback = r.family;
+        r.family = bf16 ? CONV_K_PLANE1 : CONV_K_X3;
+        r.ksplit = 1;
+        r.stat_blocks = t2v_conv5_x3_stat_blocks(B, T);
     }
-    if (BN == 32) k_conv5_fwd<2><<<grid, 256, 0, stream>>>(a);
-    else if (BN == 48) k_conv5_fwd<3><<<grid, 256, 0, stream>>>(a);
-    else if (BN == 64) k_conv5_fwd<4><<<grid, 256, 0, stream>>>(a);
-    else if (BN == 80) k_conv5_fwd<5><<<grid, 256, 0, stream>>>(a);
-    else k_conv5_fwd<6><<<grid, 256, 0, stream>>>(a);
-}
-
-static void launch_conv5_fwd_bf16(const float* W, int flipT, unsigned short* Wp, const float* X, const float* bias,
-                                  float* Y, float* stat_part, int B, int Cin, int T, int M, int W_M, int W_Cin,
-                                  hipStream_t stream) {
-    const size_t n = (size_t)W_M * W_Cin * 5;
-    k_conv5_pack_bf16<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(W, Wp, W_M, W_Cin, flipT);
-    int ks_unused = 1;      // (the same tile width as the fp32 launch: t2v_conv1d_stat_blocks answers for both)
-    const int BN = conv5_pick_bn_ks(T, B, M, Cin, &ks_unused);
-    ConvBf16Args a;
-    a.Wp = Wp; a.X = X; a.bias = bias; a.Y = Y; a.stat_part = stat_part;
-    a.B = B; a.Cin = Cin; a.T = T; a.M = M; a.tiles_per_item = (T + BN - 1) / BN;
-    dim3 grid(B * a.tiles_per_item, (M + CT_BM - 1) / CT_BM);
-    static const int k32 = getenv("T2V_CONV_BF16_K32") ? atoi(getenv("T2V_CONV_BF16_K32")) : 1;      // 0: the 16-channel kernel (measurement)
-    if (k32 && Cin % 32 == 0) {
-        if (BN == 32) k_conv5_fwd_bf16k32<2><<<grid, 256, 0, stream>>>(a);
-        else if (BN == 48) k_conv5_fwd_bf16k32<3><<<grid, 256, 0, stream>>>(a);
-        else if (BN == 64) k_conv5_fwd_bf16k32<4><<<grid, 256, 0, stream>>>(a);
-        else if (BN == 80) k_conv5_fwd_bf16k32<5><<<grid, 256, 0, stream>>>(a);
-        else k_conv5_fwd_bf16k32<6><<<grid, 256, 0, stream>>>(a);
-        return;
-    }
-    if (BN == 32) k_conv5_fwd_bf16<2><<<grid, 256, 0, stream>>>(a);
-    else if (BN == 48) k_conv5_fwd_bf16<3><<<grid, 256, 0, stream>>>(a);
-    else if (BN == 64) k_conv5_fwd_bf16<4><<<grid, 256, 0, stream>>>(a);
-    else if (BN == 80) k_conv5_fwd_bf16<5><<<grid, 256, 0, stream>>>(a);
-    else k_conv5_fwd_bf16<6><<<grid, 256, 0, stream>>>(a);
+    return r;
 }
 
 // W (M, Cin, KS) -> Wt (Cin, M, KS) with the taps flipped: conv(dY, Wt) is the data gradient
@@ -1242,48 +1225,137 @@ extern "C" int t2v_conv1d_flip_weights(const float* const* W, float* const* Wt, 
     return t2v_check_launch();
 }
 
+// ---- the launches: they carry out a ConvRoute and decide nothing (but for the one fallback named there)
+static std::atomic<long long> g_conv5_staged_launches{0};
+extern "C" long long t2v_conv1d_staged_launches(void) { return g_conv5_staged_launches.load(std::memory_order_relaxed); }
+
+// The end of a launch function: k_conv_gemm, MODE 0 (forward / data gradient: W, X -> Y over B * T columns) or 1 (weight gradient:
+// dY, X -> Y over Cin * KS columns).  (A macro, and each launch function names its tiled kernels before it: the device code of the
+// kernel templates comes out in the order of their first mention, which this keeps as it has been)
+#define T2V_CONV_GEMM(MODE, W_, X_, DY_, BIAS_, Y_, STAT_)                                              \
+    ConvGemmArgs g;                                                                                     \
+    g.W = W_; g.X = X_; g.dY = DY_; g.bias = BIAS_; g.Y = Y_; g.stat_part = STAT_;                      \
+    g.B = r.B; g.Cin = r.Cin; g.T = r.T; g.M = r.M; g.KS = r.KS;                                        \
+    const dim3 gg(((MODE == 0 ? r.B * r.T : r.Cin * r.KS) + CG_BN - 1) / CG_BN, (r.M + CG_BM - 1) / CG_BM);   \
+    if (r.KS == 5) k_conv_gemm<MODE, 5><<<gg, 256, 0, stream>>>(g);                                     \
+    else if (r.KS == 3) k_conv_gemm<MODE, 3><<<gg, 256, 0, stream>>>(g);                                \
+    else return T2V_ERR_DIMS;                                                                           \
+    return T2V_OK
+// the tiled forward kernels by tile width
+#define T2V_CONV5_NTW(KERNEL)                                       \
+    switch (r.tile) {                                               \
+    case 2: KERNEL<2><<<grid, 256, 0, stream>>>(a); break;          \
+    case 3: KERNEL<3><<<grid, 256, 0, stream>>>(a); break;          \
+    case 4: KERNEL<4><<<grid, 256, 0, stream>>>(a); break;          \
+    case 5: KERNEL<5><<<grid, 256, 0, stream>>>(a); break;          \
+    default: KERNEL<6><<<grid, 256, 0, stream>>>(a);                \
+    }
+// Forward / data gradient (r.op) of either precision.  W: the weights of the convolution as it runs, (r.M, r.Cin, KS) — from the bf16_run
+// entries the LAYER's weights, which the bf16 families pack / flip themselves (Wp: the caller's bf16 scratch of W's element count)
+static int conv_launch(const ConvRoute& r, const float* W, const float* X, const float* bias, float* Y, float* stat_part,
+                       unsigned short* Wp, hipStream_t stream) {
+    const int B = r.B, Cin = r.Cin, T = r.T, M = r.M, BN = 16 * r.tile;
+    const bool dx = r.op == CONV_OP_DX;
+    int family = r.family;
+    if (family == CONV_K_X3) return t2v_conv5_x3_run(W, X, bias, Y, stat_part, B, Cin, T, M, stream, 3);
+    if (family == CONV_K_PLANE1 && !dx) return t2v_conv5_x3_run(W, X, bias, Y, stat_part, B, Cin, T, M, stream, 1);
+    if (family == CONV_K_PLANE1) {
+        // the plane kernels read fp32 weights: the flipped, transposed copy lives in the library's ring (the caller's scratch is
+        // sized for bf16).  No slice: r.fallback
+        float* wt = conv_ks_scratch((size_t)M * Cin * 5);
+        if (wt) {
+            k_conv_flip_weight<<<(M * Cin * 5 + 255) / 256, 256, 0, stream>>>(W, wt, Cin, M, 5);
+            return t2v_conv5_x3_run(wt, X, bias, Y, stat_part, B, Cin, T, M, stream, 1);
+        }
+        family = r.fallback;
+    }
+    if (family == CONV_K_FWD || family == CONV_K_FWD_DMA) {
+        ConvTiledArgs a;
+        a.W = W; a.X = X; a.dY = nullptr; a.bias = bias; a.Y = Y; a.stat_part = stat_part;
+        a.B = B; a.Cin = Cin; a.T = T; a.M = M; a.tiles_per_item = (T + BN - 1) / BN;
+        a.prof = g_t2v_prof;
+        a.ks_part = nullptr; a.ks_ctr = nullptr;
+        dim3 grid(B * a.tiles_per_item, (M + CT_BM - 1) / CT_BM);
+        if (r.ksplit == 2) {
+            // a launch that leaves half the chip idle and has a deep K: the input channels are cut in two (T2V_CONV_KSPLIT=0 switches
+            // it off for measurements).  Without its scratch the same kernel runs uncut: the same tiles, the same partial blocks
+            const long ntile = (long)grid.x * grid.y;
+            a.ks_part = conv_ks_scratch((size_t)2 * ntile * 256 * 4 * r.tile);
+            a.ks_ctr = a.ks_part ? t2v_arrival_counters((int)ntile) : nullptr;
+            if (a.ks_part && a.ks_ctr) grid.z = 2; else a.ks_part = nullptr;
+        }
+        if (family == CONV_K_FWD_DMA) {
+            g_conv5_staged_launches.fetch_add(1, std::memory_order_relaxed);    // lets a caller see which kernel its launches took
+            T2V_CONV5_NTW(k_conv5_fwd_dma)
+        } else {
+            T2V_CONV5_NTW(k_conv5_fwd)
+        }
+        return T2V_OK;
+    }
+    if (family == CONV_K_BF16 || family == CONV_K_BF16K32) {
+        const size_t n = (size_t)M * Cin * 5;
+        k_conv5_pack_bf16<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(W, Wp, dx ? Cin : M, dx ? M : Cin, dx ? 1 : 0);
+        ConvBf16Args a;
+        a.Wp = Wp; a.X = X; a.bias = bias; a.Y = Y; a.stat_part = stat_part;
+        a.B = B; a.Cin = Cin; a.T = T; a.M = M; a.tiles_per_item = (T + BN - 1) / BN;
+        dim3 grid(B * a.tiles_per_item, (M + CT_BM - 1) / CT_BM);
+        if (family == CONV_K_BF16K32) { T2V_CONV5_NTW(k_conv5_fwd_bf16k32) } else { T2V_CONV5_NTW(k_conv5_fwd_bf16) }
+        return T2V_OK;
+    }
+    T2V_CONV_GEMM(0, W, X, nullptr, bias, Y, stat_part);
+}
+#undef T2V_CONV5_NTW
+
+// Weight gradient of either precision (the route was asked with it): X (B, Cin, T), dY (B, Cout, T) -> dW (Cout, Cin, KS)
+static int conv_dw_launch(const ConvRoute& r, const float* X, const float* dY, float* dW, float* dw_scratch, hipStream_t stream) {
+    if (r.family != CONV_K_GEMM) {
+        const int ns = r.dw_splits;
+        if (ns > 1 && !dw_scratch) return T2V_ERR_ARG;
+        ConvTiledArgs a;
+        a.W = nullptr; a.X = X; a.dY = dY; a.bias = nullptr; a.Y = ns > 1 ? dw_scratch : dW; a.stat_part = nullptr;
+        a.B = r.B; a.Cin = r.Cin; a.T = r.T; a.M = r.M; a.tiles_per_item = 0;
+        a.prof = nullptr; a.ks_part = nullptr; a.ks_ctr = nullptr;
+        dim3 grid(r.Cin / 16, (r.M + CT_BM - 1) / CT_BM, ns);
+        if (r.family == CONV_K_DW_BF16) {
+            if (r.tile == 80) k_conv5_dw_bf16<80><<<grid, 256, 0, stream>>>(a);
+            else k_conv5_dw_bf16<96><<<grid, 256, 0, stream>>>(a);
+        } else if (r.tile == 80) k_conv5_dw<80><<<grid, 256, 0, stream>>>(a);
+        else k_conv5_dw<96><<<grid, 256, 0, stream>>>(a);
+        if (ns > 1) {
+            const int n = r.M * r.Cin * 5;
+            k_conv5_dw_reduce<<<(n + 255) / 256, 256, 0, stream>>>(dw_scratch, dW, n, ns);
+        }
+        return T2V_OK;
+    }
+    T2V_CONV_GEMM(1, nullptr, X, dY, nullptr, dW, nullptr);
+}
+#undef T2V_CONV_GEMM
+
 extern "C" int t2v_conv1d_fwd(const float* W, const float* X, const float* bias, float* Y, float* stat_part,
                               int B, int Cin, int T, int Cout, int KS, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     if (!W || !X || !Y || B < 1 || Cin < 1 || T < 1 || Cout < 1 || KS < 1 || !(KS & 1)) return T2V_ERR_ARG;
-    if (t2v_conv5_x3_ok(B, Cin, T, Cout, KS)) {
-        const int rc = t2v_conv5_x3_run(W, X, bias, Y, stat_part, B, Cin, T, Cout, stream, 3);
-        return rc != T2V_OK ? rc : t2v_check_launch();
-    }
-    if (conv5_tiled_ok(Cin, KS)) {
-        launch_conv5_fwd(W, X, bias, Y, stat_part, B, Cin, T, Cout, stream);
-        return t2v_check_launch();
-    }
-    ConvGemmArgs a;
-    a.W = W; a.X = X; a.dY = nullptr; a.bias = bias; a.Y = Y; a.stat_part = stat_part;
-    a.B = B; a.Cin = Cin; a.T = T; a.M = Cout; a.KS = KS;
-    dim3 grid((B * T + CG_BN - 1) / CG_BN, (Cout + CG_BM - 1) / CG_BM);
-    if (KS == 5) k_conv_gemm<0, 5><<<grid, 256, 0, stream>>>(a);
-    else if (KS == 3) k_conv_gemm<0, 3><<<grid, 256, 0, stream>>>(a);
-    else return T2V_ERR_DIMS;
-    return t2v_check_launch();
+    const ConvRoute r = conv_route(CONV_OP_FWD, B, Cin, T, Cout, KS, false, ((size_t)W & 15) == 0);
+    const int rc = conv_launch(r, W, X, bias, Y, stat_part, nullptr, (hipStream_t)stream_);
+    return rc != T2V_OK ? rc : t2v_check_launch();
 }
 
 extern "C" int t2v_conv1d_stat_blocks(int B, int T, int Cin, int Cout, int KS) {
-    if (t2v_conv5_x3_ok(B, Cin, T, Cout, KS)) return t2v_conv5_x3_stat_blocks(B, T);
-    if (conv5_tiled_ok(Cin, KS)) { int ks; const int BN = conv5_pick_bn_ks(T, B, Cout, Cin, &ks); return B * ((T + BN - 1) / BN); }
-    return (B * T + CG_BN - 1) / CG_BN;
+    return conv_route(CONV_OP_FWD, B, Cin, T, Cout, KS, false, true).stat_blocks;
 }
-
-// ... for t2v_conv1d_fwd_bf16 (its kernels keep the tile choice of the fp32-MFMA kernels whatever the x3 mode says)
 extern "C" int t2v_conv1d_stat_blocks_bf16(int B, int T, int Cin, int Cout, int KS) {
-    if (t2v_conv5_planes_bf16_ok(B, Cin, T, Cout, KS)) return t2v_conv5_x3_stat_blocks(B, T);
-    if (conv5_tiled_ok(Cin, KS)) { int ks; const int BN = conv5_pick_bn_ks(T, B, Cout, Cin, &ks); return B * ((T + BN - 1) / BN); }
-    return (B * T + CG_BN - 1) / CG_BN;
+    return conv_route(CONV_OP_FWD, B, Cin, T, Cout, KS, true, true).stat_blocks;
 }
-
+// (sized for the bf16 kernel, which splits at least as far as the fp32 one: one scratch serves both backward entries)
 extern "C" int t2v_conv1d_dw_scratch_floats(int B, int Cin, int T, int Cout, int KS) {
-    if (!conv5_tiled_ok(Cin, KS)) return 0;
-    const int ns = conv5_dw_splits(B, Cin, T, Cout, true);        // (the bf16 kernel splits at least as far as the fp32 one)
-    return ns > 1 ? ns * Cout * Cin * 5 : 0;
+    return conv_route(CONV_OP_DW, B, Cin, T, Cout, KS, true, true).dw_scratch_floats;
+}
+// which form a k = 5 convolution Cin -> Cout takes (tests assert the path they were written for): 1 = the x3 / one-plane kernels of
+// conv_x3.hip, 0 = the kernels of this file
+extern "C" int t2v_conv1d_takes_x3(int B, int Cin, int T, int Cout, int KS, int bf16) {
+    const int family = conv_route(CONV_OP_FWD, B, Cin, T, Cout, KS, bf16 != 0, true).family;
+    return family == CONV_K_X3 || family == CONV_K_PLANE1 ? 1 : 0;
 }
 
-static thread_local bool g_conv_dw_bf16 = false;     // set by t2v_conv1d_bwd_bf16 around its call of t2v_conv1d_bwd (weight gradient on bf16 MFMA)
 extern "C" int t2v_conv1d_bwd(const float* W, const float* X, const float* dY, float* dX, float* dW, float* Wt_scratch,
                               float* dw_scratch, int B, int Cin, int T, int Cout, int KS, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -1293,67 +1365,27 @@ extern "C" int t2v_conv1d_bwd(const float* W, const float* X, const float* dY, f
         if (!Wt_scratch) return T2V_ERR_ARG;
         const int n = Cout * Cin * KS;
         if (W) k_conv_flip_weight<<<(n + 255) / 256, 256, 0, stream>>>(W, Wt_scratch, Cout, Cin, KS);
-        if (t2v_conv5_x3_ok(B, Cout, T, Cin, KS)) {         // the data gradient = the same convolution with the flipped, transposed weights
-            const int rc = t2v_conv5_x3_run(Wt_scratch, dY, nullptr, dX, nullptr, B, Cout, T, Cin, stream, 3);
-            if (rc != T2V_OK) return rc;
-        } else if (conv5_tiled_ok(Cout, KS)) {
-            launch_conv5_fwd(Wt_scratch, dY, nullptr, dX, nullptr, B, Cout, T, Cin, stream);
-        } else {
-            ConvGemmArgs a;
-            a.W = Wt_scratch; a.X = dY; a.dY = nullptr; a.bias = nullptr; a.Y = dX; a.stat_part = nullptr;
-            a.B = B; a.Cin = Cout; a.T = T; a.M = Cin; a.KS = KS;
-            dim3 grid((B * T + CG_BN - 1) / CG_BN, (Cin + CG_BM - 1) / CG_BM);
-            if (KS == 5) k_conv_gemm<0, 5><<<grid, 256, 0, stream>>>(a);
-            else if (KS == 3) k_conv_gemm<0, 3><<<grid, 256, 0, stream>>>(a);
-            else return T2V_ERR_DIMS;
-        }
+        const ConvRoute r = conv_route(CONV_OP_DX, B, Cin, T, Cout, KS, false, ((size_t)Wt_scratch & 15) == 0);
+        const int rc = conv_launch(r, Wt_scratch, dY, nullptr, dX, nullptr, nullptr, stream);
+        if (rc != T2V_OK) return rc;
     }
-    if (dW && conv5_tiled_ok(Cin, KS)) {
-        const bool dw_bf16 = g_conv_dw_bf16;
-        ConvTiledArgs a;
-        a.W = nullptr; a.X = X; a.dY = dY; a.bias = nullptr; a.Y = dW; a.stat_part = nullptr;
-        a.B = B; a.Cin = Cin; a.T = T; a.M = Cout; a.tiles_per_item = 0;
-        a.prof = nullptr; a.ks_part = nullptr; a.ks_ctr = nullptr;
-        const int ns = conv5_dw_splits(B, Cin, T, Cout, dw_bf16);
-        if (ns > 1 && !dw_scratch) return T2V_ERR_ARG;
-        if (ns > 1) a.Y = dw_scratch;
-        dim3 grid(Cin / 16, (Cout + CT_BM - 1) / CT_BM, ns);
-        const int c80 = ((T + 79) / 80) * 80, c96 = ((T + 95) / 96) * 96;
-        if (dw_bf16) {
-            if (c80 <= c96) k_conv5_dw_bf16<80><<<grid, 256, 0, stream>>>(a);
-            else k_conv5_dw_bf16<96><<<grid, 256, 0, stream>>>(a);
-        } else if (c80 <= c96) k_conv5_dw<80><<<grid, 256, 0, stream>>>(a);
-        else k_conv5_dw<96><<<grid, 256, 0, stream>>>(a);
-        if (ns > 1) {
-            const int n = Cout * Cin * 5;
-            k_conv5_dw_reduce<<<(n + 255) / 256, 256, 0, stream>>>(dw_scratch, dW, n, ns);
-        }
-    } else if (dW) {
-        ConvGemmArgs a;
-        a.W = nullptr; a.X = X; a.dY = dY; a.bias = nullptr; a.Y = dW; a.stat_part = nullptr;
-        a.B = B; a.Cin = Cin; a.T = T; a.M = Cout; a.KS = KS;
-        dim3 grid((Cin * KS + CG_BN - 1) / CG_BN, (Cout + CG_BM - 1) / CG_BM);
-        if (KS == 5) k_conv_gemm<1, 5><<<grid, 256, 0, stream>>>(a);
-        else if (KS == 3) k_conv_gemm<1, 3><<<grid, 256, 0, stream>>>(a);
-        else return T2V_ERR_DIMS;
+    if (dW) {
+        const int rc = conv_dw_launch(conv_route(CONV_OP_DW, B, Cin, T, Cout, KS, false, true), X, dY, dW, dw_scratch, stream);
+        if (rc != T2V_OK) return rc;
     }
     return t2v_check_launch();
 }
 
 // ---- bf16_run entry points: same contracts as t2v_conv1d_fwd / t2v_conv1d_bwd, plus a bf16 scratch of W's
-// element count (2 bytes each).  Forward and data gradient run on bf16 MFMA, the weight gradient stays on the
-// fp32 kernel.  T2V_ERR_DIMS when the shape is outside the tiled bf16 path (caller uses the fp32 entry points).
+// element count (2 bytes each).  Forward, data gradient and weight gradient run on bf16 MFMA.
+// T2V_ERR_DIMS when the shape is outside the tiled bf16 path (caller uses the fp32 entry points).
 extern "C" int t2v_conv1d_fwd_bf16(const float* W, const float* X, const float* bias, float* Y, float* stat_part,
                                    void* Wp_scratch, int B, int Cin, int T, int Cout, int KS, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     if (!W || !X || !Y || !Wp_scratch || B < 1 || Cin < 1 || T < 1 || Cout < 1) return T2V_ERR_ARG;
-    if (!conv5_tiled_ok(Cin, KS)) return T2V_ERR_DIMS;
-    if (t2v_conv5_planes_bf16_ok(B, Cin, T, Cout, KS)) {        // round 6: pre-rounded planes + the LDS-DMA kernel (conv_x3.hip, one plane)
-        const int rc = t2v_conv5_x3_run(W, X, bias, Y, stat_part, B, Cin, T, Cout, stream, 1);
-        return rc != T2V_OK ? rc : t2v_check_launch();
-    }
-    launch_conv5_fwd_bf16(W, 0, (unsigned short*)Wp_scratch, X, bias, Y, stat_part, B, Cin, T, Cout, Cout, Cin, stream);
-    return t2v_check_launch();
+    const ConvRoute r = conv_route(CONV_OP_FWD, B, Cin, T, Cout, KS, true, true);
+    if (r.family == CONV_K_GEMM) return T2V_ERR_DIMS;
+    const int rc = conv_launch(r, W, X, bias, Y, stat_part, (unsigned short*)Wp_scratch, (hipStream_t)stream_);
+    return rc != T2V_OK ? rc : t2v_check_launch();
 }
 
 extern "C" int t2v_conv1d_bwd_bf16(const float* W, const float* X, const float* dY, float* dX, float* dW,
@@ -1361,28 +1393,18 @@ extern "C" int t2v_conv1d_bwd_bf16(const float* W, const float* X, const float* 
                                    void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!X || !dY || B < 1 || Cin < 1 || T < 1 || Cout < 1) return T2V_ERR_ARG;
-    if (!conv5_tiled_ok(Cin, KS) || (dX && !conv5_tiled_ok(Cout, KS))) return T2V_ERR_DIMS;
+    const ConvRoute rw = conv_route(CONV_OP_DW, B, Cin, T, Cout, KS, true, true);
+    if (rw.family == CONV_K_GEMM) return T2V_ERR_DIMS;
     if (dX) {
+        const ConvRoute rx = conv_route(CONV_OP_DX, B, Cin, T, Cout, KS, true, true);
+        if (rx.family == CONV_K_GEMM) return T2V_ERR_DIMS;
         if (!W || !Wp_scratch) return T2V_ERR_ARG;
-        bool done = false;
-        if (t2v_conv5_planes_bf16_ok(B, Cout, T, Cin, KS)) {
-            // round 6: the data gradient = the same convolution with the flipped, transposed weights, on the one-plane form of
-            // conv_x3.hip (the flipped fp32 copy lives in the library's ring: the caller's scratch is sized for bf16)
-            float* wt = conv_ks_scratch((size_t)Cout * Cin * KS);
-            if (wt) {
-                k_conv_flip_weight<<<(Cout * Cin * KS + 255) / 256, 256, 0, stream>>>(W, wt, Cout, Cin, KS);
-                const int rc = t2v_conv5_x3_run(wt, dY, nullptr, dX, nullptr, B, Cout, T, Cin, stream, 1);
-                if (rc != T2V_OK) return rc;
-                done = true;
-            }
-        }
-        if (!done) launch_conv5_fwd_bf16(W, 1, (unsigned short*)Wp_scratch, dY, nullptr, dX, nullptr, B, Cout, T, Cin, Cout, Cin, stream);
+        const int rc = conv_launch(rx, W, dY, nullptr, dX, nullptr, (unsigned short*)Wp_scratch, stream);
+        if (rc != T2V_OK) return rc;
     }
-    if (dW) {           // (round 5) the weight gradient on bf16 MFMA as well: same tiling / K-splits as the fp32 kernel
-        g_conv_dw_bf16 = true;
-        const int rc = t2v_conv1d_bwd(W, X, dY, nullptr, dW, nullptr, dw_scratch, B, Cin, T, Cout, KS, stream_);
-        g_conv_dw_bf16 = false;
-        return rc;
+    if (dW) {
+        const int rc = conv_dw_launch(rw, X, dY, dW, dw_scratch, stream);
+        if (rc != T2V_OK) return rc;
     }
     return t2v_check_launch();
 }

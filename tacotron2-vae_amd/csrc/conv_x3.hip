@@ -15,9 +15,9 @@
 //      channels (gridDim.z), raw tiles to scratch, the last arriver adds them in fixed order (deterministic) and runs the epilogue:
 //      bias, store, and the per-channel partial sums / sums of squares BatchNorm needs (fixed order as well).
 #include <stdlib.h>
-#include <atomic>
 #include "t2v_common.h"
 #include "t2v_kernels.h"
+#include "t2v_ring.h"
 #include "t2v_coop.h"
 #include "t2v_x3.h"
 #include "t2v_xchg.h"
@@ -295,33 +295,8 @@ __global__ __launch_bounds__(256, 2) void k_conv5_x3(ConvX3Args a) {
 // keeps the slices of its nodes.  One call may take at most a quarter of the ring (CX_SCRATCH_CAP floats)
 #define CX_SCRATCH_RING ((size_t)256 << 20)      // floats (1 GB)
 #define CX_SCRATCH_CAP (CX_SCRATCH_RING / 4)
-static float* cx_ring() {           // the ring, allocated on first use; nullptr when it cannot be
-    static float* ring = nullptr;
-    static std::atomic<int> state{0};
-    if (state.load(std::memory_order_acquire) != 2) {
-        int expect = 0;
-        if (state.compare_exchange_strong(expect, 1)) {
-            float* p = nullptr;
-            if (hipMalloc((void**)&p, CX_SCRATCH_RING * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); state.store(0); return nullptr; }
-            ring = p;
-            state.store(2, std::memory_order_release);
-        } else {
-            while (state.load(std::memory_order_acquire) == 1) { }
-            if (state.load() != 2) return nullptr;
-        }
-    }
-    return ring;
-}
-static float* cx_scratch(size_t floats) {
-    static std::atomic<size_t> pos{0};
-    floats = (floats + 63) & ~(size_t)63;
-    if (floats > CX_SCRATCH_CAP) return nullptr;
-    float* ring = cx_ring();
-    if (!ring) return nullptr;
-    size_t at = pos.fetch_add(floats) % CX_SCRATCH_RING;
-    if (at + floats > CX_SCRATCH_RING) { pos.store(floats); at = 0; }
-    return ring + at;
-}
+static T2VRing<float, CX_SCRATCH_RING, CX_SCRATCH_CAP, false> g_cx_ring;
+static float* cx_scratch(size_t floats) { return g_cx_ring.take((floats + 63) & ~(size_t)63); }
 
 // launch geometry of t2v_conv5_x3_run and the scratch it takes (floats)
 struct CxPlan {
@@ -346,11 +321,10 @@ static CxPlan cx_plan(int B, int Cin, int T, int M, int np) {
     p.part_floats = p.ns > 1 ? (size_t)p.ns * p.tiles * CX_BM * CX_BN : 0;
     return p;
 }
-// can t2v_conv5_x3_run get its scratch for this call?  (the _ok functions ask, so that the BatchNorm partial count and the launch
-// agree: a call the ring cannot serve runs on the fp32 / bf16 tiled kernels instead of failing.  fp32, B = 64, 512 channels: up to
-// T = 1152)
+// can t2v_conv5_x3_run get its scratch for this call?  (t2v_conv5_planes_ok asks: a call the ring cannot serve is routed to the
+// fp32 / bf16 tiled kernels instead of failing.  fp32, B = 64, 512 channels: up to T = 1152)
 static bool cx_scratch_ok(int B, int Cin, int T, int M, int np) {
-    return ((cx_plan(B, Cin, T, M, np).floats() + 63) & ~(size_t)63) <= CX_SCRATCH_CAP && cx_ring() != nullptr;
+    return ((cx_plan(B, Cin, T, M, np).floats() + 63) & ~(size_t)63) <= CX_SCRATCH_CAP && g_cx_ring.available();
 }
 
 extern "C" int t2v_gemm_f32_set_mode(int x3);
@@ -362,8 +336,10 @@ extern "C" int t2v_conv1d_x3_set_mode(int mode) {
     if (mode >= 0 && mode <= 2) g_cx3_mode = mode;
     return prev;
 }
-// does the fp32 k = 5 convolution (Cin -> Cout channels) take the x3 path?  (t2v_conv1d_stat_blocks must give the same answer)
-bool t2v_conv5_x3_ok(int B, int Cin, int T, int Cout, int KS) {
+// does the k = 5 convolution Cin -> Cout take the kernels of this file — np = 3: the fp32 entries on three planes, np = 1: the bf16_run
+// entries on one (operands rounded to bf16 once by the split passes, LDS-DMA, 32 channels per step)?  Asked by conv_route() of
+// conv_gemm.hip and by nobody else: the BatchNorm partial count and the launch follow from its one answer.
+bool t2v_conv5_planes_ok(int B, int Cin, int T, int Cout, int KS, int np) {
     // t2v_conv1d_x3_set_mode / T2V_CONV_X3: 0 = never, 1 = whenever the shape allows it (tests, measurement), default 2: launches of >= 192 tiles only.  Measured on the
     // step's shapes (tools/dbg/conv_x3_time.py, T2V_CX3_DBG): at B = 6 the 512 -> 512 Postnet layer is 96 tiles; cut four ways over
     // its input channels the kernel's loop takes 45 us, but the two split passes (15 us), the raw tiles of the channel split going to
@@ -372,7 +348,7 @@ bool t2v_conv5_x3_ok(int B, int Cin, int T, int Cout, int KS) {
     const int mode = t2v_conv1d_x3_set_mode(-1);
     if (!mode || KS != 5 || Cin % 16 || Cin < 64 || Cout < 64 || B < 1 || T < 1) return false;
     if (mode == 2 && (long)B * ((T + CX_BN - 1) / CX_BN) * ((Cout + CX_BM - 1) / CX_BM) < 192) return false;
-    return t2v_gemm_f32_set_mode(-1) != 0 && cx_scratch_ok(B, Cin, T, Cout, 3);
+    return (np == 1 || t2v_gemm_f32_set_mode(-1) != 0) && cx_scratch_ok(B, Cin, T, Cout, np);
 }
 int t2v_conv5_x3_stat_blocks(int B, int T) { return B * ((T + CX_BN - 1) / CX_BN); }
 
@@ -392,21 +368,6 @@ static int cx_splits(long tiles, int nst) {
     return best;
 }
 
-// bf16_run: does the k = 5 convolution (t2v_conv1d_fwd_bf16 / the data gradient of t2v_conv1d_bwd_bf16) take the one-plane form of the
-// kernels above (operands rounded to bf16 once by the split passes, LDS-DMA, 32 channels per step)?  The same switch as the fp32 form
-// (t2v_conv1d_x3_set_mode: 0 never, 1 every eligible shape, 2 launches of >= 192 tiles); t2v_conv1d_stat_blocks_bf16 gives the
-// matching answer
-bool t2v_conv5_planes_bf16_ok(int B, int Cin, int T, int Cout, int KS) {
-    const int mode = t2v_conv1d_x3_set_mode(-1);
-    if (!mode || KS != 5 || Cin % 16 || Cin < 64 || Cout < 64 || B < 1 || T < 1) return false;
-    if (mode == 2 && (long)B * ((T + CX_BN - 1) / CX_BN) * ((Cout + CX_BM - 1) / CX_BM) < 192) return false;
-    return cx_scratch_ok(B, Cin, T, Cout, 1);
-}
-// which form a k = 5 convolution Cin -> Cout takes, as the entry points decide it (tests assert the path they were written for):
-// 1 = the x3 / one-plane kernels of this file, 0 = the tiled kernels of conv_gemm.hip
-extern "C" int t2v_conv1d_takes_x3(int B, int Cin, int T, int Cout, int KS, int bf16) {
-    return (bf16 ? t2v_conv5_planes_bf16_ok(B, Cin, T, Cout, KS) : t2v_conv5_x3_ok(B, Cin, T, Cout, KS)) ? 1 : 0;
-}
 // W: (M, Cin, 5) weights of the convolution to run (the data gradient passes the flipped, transposed weights); np = 3: fp32 operands
 // as three bf16 planes, np = 1: bf16_run
 int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B, int Cin, int T, int M,
@@ -414,7 +375,7 @@ int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y
     const CxPlan pl = cx_plan(B, Cin, T, M, np);
     const int Mp = pl.Mp, G = pl.G, ntile = pl.ntile, Tp = pl.Tp, nst = pl.nst, ns = pl.ns;
     const size_t w_slots = pl.w_slots, x_slots = pl.x_slots;
-    float* scr = cx_scratch(pl.floats());          // (the _ok functions checked that it is there)
+    float* scr = cx_scratch(pl.floats());          // (the route checked that it is there)
     if (!scr) return T2V_ERR_LAUNCH;
     uint4* Wp = (uint4*)scr;
     uint4* Xp = Wp + w_slots;

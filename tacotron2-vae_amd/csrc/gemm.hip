@@ -171,34 +171,11 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmArgs a) {
 // arrival counters of the split-K tiles (and of colsum.hip's column blocks): slices of one zero-initialised ring (every launch takes the next `tiles` words and
 // leaves them at zero; a slice comes round again 64 K tiles later, long after its launch has retired; a captured graph keeps
 // the slices of its nodes, and the launches of different graphs / eager steps of one engine never run at the same time)
-#include <atomic>
-#define GM_CTR_RING (1 << 16)
+#include "t2v_ring.h"
+#define GM_CTR_RING ((size_t)1 << 16)
 unsigned* t2v_arrival_counters(int tiles) {
-    static unsigned* ring = nullptr;
-    static std::atomic<unsigned> pos{0};
-    static std::atomic<int> state{0};
-    if (tiles > GM_CTR_RING) return nullptr;
-    int st = state.load(std::memory_order_acquire);
-    if (st != 2) {
-        int expect = 0;
-        if (state.compare_exchange_strong(expect, 1)) {
-            unsigned* p = nullptr;
-            if (hipMalloc((void**)&p, GM_CTR_RING * sizeof(unsigned)) != hipSuccess || hipMemset(p, 0, GM_CTR_RING * sizeof(unsigned)) != hipSuccess
-                || hipDeviceSynchronize() != hipSuccess) { state.store(0); return nullptr; }
-            ring = p;
-            state.store(2, std::memory_order_release);
-        } else {
-            while (state.load(std::memory_order_acquire) == 1) { }
-            if (state.load() != 2) return nullptr;
-        }
-    }
-    unsigned at = pos.fetch_add((unsigned)tiles);
-    at %= GM_CTR_RING;
-    if (at + (unsigned)tiles > GM_CTR_RING) {         // would wrap inside the slice: start over at the top
-        pos.store((unsigned)tiles);
-        at = 0;
-    }
-    return ring + at;
+    static T2VRing<unsigned, GM_CTR_RING, GM_CTR_RING, true> ring;
+    return ring.take((size_t)tiles);
 }
 // number of k-splits for the 64x64 kernel: deep-K products whose tiles leave CUs idle (r3 step trace: the 2400x256,
 // K = 4096 data gradient of the Prenet ran 174 us on 152 workgroups, the 2400x81, K = 1536 projection 61 us on 76) are

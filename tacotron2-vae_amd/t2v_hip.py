@@ -2650,6 +2650,30 @@ def preflip_conv_weights(weights):
         _PREFLIP[w.data_ptr()] = (t, st, ev)
 
 
+def _conv_bf16(Cin, Cout, KS):
+    """bf16_run: does the Conv1d Cin -> Cout run on the bf16 entry points?  Only the wide layers (the three 512->512 Postnet
+    convs, the encoder bank); the 80-channel first and last Postnet layers are cheap and stay fp32 (the output layer in
+    particular)"""
+    return _BF16 and KS == 5 and Cin % 16 == 0 and Cin >= 128 and Cout >= 128
+
+
+def _conv1d_fwd(lib, w, x, bias, y, want_stats):
+    """y = Conv1d(x) + bias by the fp32 or the bf16_run entry point.  Returns (part, nblk): the BatchNorm partials the
+    launch wrote (None unless want_stats) and their block count, which the library answers from the route the launch takes"""
+    B, Cin, T = x.shape
+    Cout, _, KS = w.shape
+    bf16 = _conv_bf16(Cin, Cout, KS)
+    nblk = (lib.t2v_conv1d_stat_blocks_bf16 if bf16 else lib.t2v_conv1d_stat_blocks)(B, T, Cin, Cout, KS)
+    part = torch.empty(nblk, Cout, 2, device=x.device, dtype=torch.float32) if want_stats else None
+    if bf16:
+        wp = torch.empty(w.numel(), device=x.device, dtype=torch.bfloat16)
+        _check(lib.t2v_conv1d_fwd_bf16(_p(w), _p(x), _p(bias), _p(y), _p(part), _p(wp), B, Cin, T, Cout, KS, _stream()),
+               't2v_conv1d_fwd_bf16')
+    else:
+        _check(lib.t2v_conv1d_fwd(_p(w), _p(x), _p(bias), _p(y), _p(part), B, Cin, T, Cout, KS, _stream()), 't2v_conv1d_fwd')
+    return part, nblk
+
+
 class ConvBNAct1d(torch.autograd.Function):
     """dropout(act(BatchNorm1d(Conv1d(x)))) — one block of the encoder conv bank / Postnet
     (reference model.py:143-148, 175-177) on the HIP implicit-GEMM conv + per-channel BN kernels.
@@ -2667,20 +2691,7 @@ class ConvBNAct1d(torch.autograd.Function):
         f32 = dict(device=dev, dtype=torch.float32)
         y = torch.empty(B, Cout, T, **f32)
         w = weight.contiguous()
-        # bf16 only for the wide layers (the three 512->512 Postnet convs, the encoder bank); the 80-channel first
-        # and last Postnet layers are cheap and stay fp32 (the output layer in particular)
-        use_bf16 = _BF16 and KS == 5 and Cin % 16 == 0 and Cin >= 128 and Cout >= 128
-        # (the number of BatchNorm partials follows the kernel that will run: the bf16 kernels keep their own tiles, the fp32 entry
-        #  may take the x3 convolution with its 128-position tiles)
-        nblk = (lib.t2v_conv1d_stat_blocks_bf16 if use_bf16 else lib.t2v_conv1d_stat_blocks)(B, T, Cin, Cout, KS)
-        part = torch.empty(nblk, Cout, 2, **f32) if training else None
-        if use_bf16:
-            wp = torch.empty(w.numel(), device=dev, dtype=torch.bfloat16)
-            _check(lib.t2v_conv1d_fwd_bf16(_p(w), _p(x), _p(bias), _p(y), _p(part), _p(wp), B, Cin, T, Cout, KS,
-                                           _stream()), 't2v_conv1d_fwd_bf16')
-        else:
-            _check(lib.t2v_conv1d_fwd(_p(w), _p(x), _p(bias), _p(y), _p(part), B, Cin, T, Cout, KS, _stream()),
-                   't2v_conv1d_fwd')
+        part, nblk = _conv1d_fwd(lib, w, x, bias, y, training)
         mean = torch.empty(Cout, **f32) if training else None
         rstd = torch.empty(Cout, **f32) if training else None
         out = torch.empty(B, Cout, T, **f32)
@@ -2716,7 +2727,7 @@ class ConvBNAct1d(torch.autograd.Function):
         dx = torch.empty(B, Cin, T, **f32) if need_dx else None
         fork = mark()       # the weight gradient below depends on dy only: it forks from HERE, not from behind the dX conv
         # the data gradient (what the next layer down waits for) on the current stream ...
-        if need_dx and _BF16 and KS == 5 and Cin % 16 == 0 and Cout % 16 == 0 and Cin >= 128 and Cout >= 128:
+        if need_dx and _conv_bf16(Cin, Cout, KS) and Cout % 16 == 0:
             wp = torch.empty(w.numel(), device=x.device, dtype=torch.bfloat16)
             _check(lib.t2v_conv1d_bwd_bf16(_p(w), _p(x), _p(dy), _p(dx), None, _p(wp), None, B, Cin, T, Cout, KS,
                                            _stream()), 't2v_conv1d_bwd_bf16')
@@ -2808,12 +2819,7 @@ def conv_bn_act_eval_len(x, weight, bias, gamma, beta, running_mean, running_var
     Cout, _, KS = weight.shape
     y = torch.empty(B, Cout, T, device=x.device, dtype=torch.float32)
     w = _f32c(weight.detach())
-    if _BF16 and KS == 5 and Cin % 16 == 0 and Cin >= 128 and Cout >= 128:      # the kernel ConvBNAct1d picks
-        wp = torch.empty(w.numel(), device=x.device, dtype=torch.bfloat16)
-        _check(lib.t2v_conv1d_fwd_bf16(_p(w), _p(x), _p(bias), _p(y), None, _p(wp), B, Cin, T, Cout, KS, _stream()),
-               't2v_conv1d_fwd_bf16')
-    else:
-        _check(lib.t2v_conv1d_fwd(_p(w), _p(x), _p(bias), _p(y), None, B, Cin, T, Cout, KS, _stream()), 't2v_conv1d_fwd')
+    _conv1d_fwd(lib, w, x, bias, y, False)           # the kernel ConvBNAct1d picks
     out = torch.empty_like(y)
     _check(lib.t2v_bn_act_fwd_len(_p(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(out), _p(lengths_i32),
                                   B, Cout, T, int(act), 1e-5, _stream()), 't2v_bn_act_fwd_len')

@@ -1,6 +1,9 @@
-"""Host-side helper entry points of the C ABI (no kernel is launched, no GPU needed): the geometry answers the Python mirror
-sizes its buffers with must stay consistent with what the launches use."""
+"""Host-side helper entry points of the C ABI (no kernel is launched, no GPU needed but by the one test marked `gpu`): the geometry
+answers the Python mirror sizes its buffers with must stay consistent with what the launches use."""
 import ctypes as C
+import importlib.util
+import json
+import os
 
 import pytest
 
@@ -18,6 +21,40 @@ def test_conv_stat_blocks_follow_the_tile_choice(lib):
     assert lib.t2v_conv1d_stat_blocks(6, 400, 512, 512, 5) == 30
     # generic kernel (Cin not a multiple of 16): 64 output positions per block over the flattened batch
     assert lib.t2v_conv1d_stat_blocks(2, 129, 33, 70, 3) == (2 * 129 + 63) // 64
+
+
+@pytest.fixture(scope="module")
+def conv_geometry(golden_dir):
+    """(tools/record_conv_geometry.py as a module, the answers it recorded from a build of before the conv routing changed)"""
+    path = os.path.join(os.path.dirname(os.path.dirname(golden_dir)), 'tools', 'record_conv_geometry.py')
+    spec = importlib.util.spec_from_file_location('record_conv_geometry', path)
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(golden_dir, 'conv_geometry.json')) as f:
+        return tool, json.load(f)
+
+
+def test_conv_geometry_answers_are_the_recorded_ones(lib, conv_geometry):
+    # x3 mode 0: the tiled and the generic kernels, 1000 shapes around every tile rule.  Exact
+    tool, golden = conv_geometry
+    assert golden['columns'] == tool.COLUMNS and len(golden['mode0']) == len(tool.MODE0_SHAPES) == 1000
+    mode = lib.t2v_conv1d_x3_set_mode(-1)
+    got = tool.section(lib, 'mode0')
+    assert lib.t2v_conv1d_x3_set_mode(-1) == mode
+    bad = [(g, w) for g, w in zip(got, golden['mode0']) if g != w]
+    assert not bad, bad[:5]
+
+
+@pytest.mark.gpu
+def test_conv_x3_eligibility_is_the_recorded_one(lib, conv_geometry):
+    # x3 modes 1 and 2 ask for the library's plane ring: recorded on the MI355X.  Exact
+    tool, golden = conv_geometry
+    got = tool.section(lib, 'x3')
+    for mode in ('1', '2'):
+        assert len(golden['x3'][mode]) == len(tool.X3_SHAPES) == 45
+        bad = [(g, w) for g, w in zip(got[mode], golden['x3'][mode]) if g != w]
+        assert not bad, (mode, bad[:5])
+    assert any(r[8] for r in golden['x3']['1']) and any(r[9] for r in golden['x3']['2'])    # (the section does see the plane kernels)
 
 
 def test_reverse_pass_geometry(lib):
