@@ -298,6 +298,33 @@ class Synthesizer(object):
             raise ValueError("load_mels: no paths")
         return self._mels_of(*self.load_wavs(paths))
 
+    def _wav_groups(self, who, paths, batch_size):
+        """the loop of pitch, loudness, latents and latent_probe: an empty list is refused in who's name; the wavs are sorted by
+        length (`wav_lengths`) and read (`load_wavs`) in ragged batches of at most batch_size; yields (indices into paths, y,
+        sample counts) per batch"""
+        if not paths:
+            raise ValueError("%s: no paths" % who)
+        for idx in length_groups(self.wav_lengths(paths), batch_size):
+            y, n = self.load_wavs([paths[i] for i in idx])
+            yield idx, y, n
+
+    # the refusals that pitch, loudness and evaluate share; `who` opens the message
+    def _need_griffin_lim(self, who):
+        if not isinstance(self.vocoder, GriffinLimVocoder):
+            raise RuntimeError("%s needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')" % who)
+
+    def _need_tracker_grid(self, who):
+        import t2v_hip
+        if self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE or self.hparams.hop_length != t2v_hip.F0_HOP:
+            raise ValueError("%s: the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
+                             % (who, t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
+
+    def _need_frame_grid(self, who):
+        import t2v_hip
+        if self.hparams.hop_length != t2v_hip.TRIM_HOP:
+            raise ValueError("%s: the frame track is built for hop %d, the front end has hop %d"
+                             % (who, t2v_hip.TRIM_HOP, self.hparams.hop_length))
+
     @torch.no_grad()
     def pitch(self, paths, batch_size=64):
         """F0 tracks of the wavs (`t2v_hip.f0`: YIN on the front end's frames, Hz, 0 where unvoiced), in input order: a list
@@ -305,14 +332,9 @@ class Synthesizer(object):
         wavs are sorted by length and run in ragged batches of at most batch_size."""
         import t2v_hip
         paths = list(paths)
-        if not paths:
-            raise ValueError("pitch: no paths")
-        if self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE or self.hparams.hop_length != t2v_hip.F0_HOP:
-            raise ValueError("pitch: the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
-                             % (t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
+        self._need_tracker_grid('pitch')
         tracks = [None] * len(paths)
-        for idx in length_groups(self.wav_lengths(paths), batch_size):
-            y, n = self.load_wavs([paths[i] for i in idx])
+        for idx, y, n in self._wav_groups('pitch', paths, batch_size):
             hz = t2v_hip.f0(y, n)
             for b, i in enumerate(idx):
                 tracks[i] = hz[b, :n[b] // t2v_hip.F0_HOP + 1]
@@ -327,14 +349,9 @@ class Synthesizer(object):
         trim_db= apply), sorted by length, in ragged batches of at most batch_size."""
         import t2v_hip
         paths = list(paths)
-        if not paths:
-            raise ValueError("loudness: no paths")
-        if self.hparams.hop_length != t2v_hip.TRIM_HOP:
-            raise ValueError("loudness: the frame track is built for hop %d, the front end has hop %d"
-                             % (t2v_hip.TRIM_HOP, self.hparams.hop_length))
+        self._need_frame_grid('loudness')
         out = [None] * len(paths)
-        for idx in length_groups(self.wav_lengths(paths), batch_size):
-            y, n = self.load_wavs([paths[i] for i in idx])
+        for idx, y, n in self._wav_groups('loudness', paths, batch_size):
             r = t2v_hip.loudness(y, n, self.hparams.sampling_rate)
             db = t2v_hip.energy_db(r.frame_ms)
             for b, i in enumerate(idx):
@@ -348,12 +365,9 @@ class Synthesizer(object):
         `model.vae_gst(load_mel(paths[i]))` returns (up to fp32 summation order).  The wavs are sorted by length and run in
         ragged batches of at most batch_size (one front-end call and one vae_gst call each)."""
         paths = list(paths)
-        if not paths:
-            raise ValueError("latents: no paths")
         parts, order = [], []
-        for idx in length_groups(self.wav_lengths(paths), batch_size):
-            mels, n = self.load_mels([paths[i] for i in idx])
-            parts.append(self.model.vae_gst(mels, n))
+        for idx, y, n in self._wav_groups('latents', paths, batch_size):
+            parts.append(self.model.vae_gst(*self._mels_of(y, n)))
             order += idx
         inv = torch.empty(len(paths), dtype=torch.int64)
         inv[torch.tensor(order)] = torch.arange(len(paths))
@@ -420,8 +434,7 @@ class Synthesizer(object):
         N = len(paths)
         base = [None] * N
         dist = [[0.0] * N for _ in probes]
-        for idx in length_groups(self.wav_lengths(paths), batch_size):
-            y, n = self.load_wavs([paths[i] for i in idx])
+        for idx, y, n in self._wav_groups('latent_probe', paths, batch_size):
             mu = self.model.vae_gst(*self._mels_of(y, n))[1].double()
             for b, i in enumerate(idx):
                 base[i] = mu[b].cpu().numpy()
@@ -673,43 +686,27 @@ class Synthesizer(object):
     def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False,
                  energy=False):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
-        (`synthesize_batch`, batch_size rows at a time, in input order) and its post-net mel compared with the mel of its own
-        recording by `t2v_hip.mel_dtw`.  condition='ref': the style comes from that recording (copy synthesis; its mel is
-        computed once, for the style and for the comparison); 'emotion': from the centroid of the row's emotion label, which
-        needs `load()`.  The decoder consumes its seeds as len(rows) consecutive synthesize() calls.
-        Returns one record per row, in input order: dtw, n_frames, n_ref_frames, hit_max (decoding ended at
-        max_decoder_steps, not at the gate; such a row is still scored) and emotion (the label id).
-        prosody=True (needs the Griffin-Lim vocoder) adds the pitch of both sides to every record (evaluation.PROSODY_KEYS):
-        `t2v_hip.f0` on the waveform `synthesize_batch(paths=...)` would have written (the vocoder on the pre-Postnet mel, with
-        the same np.random draws) and on the recording's samples, which are the ones read for its mel.  A row decoded to
-        fewer than the vocoder's 4 frames has no waveform, and None on its synthesised side.
-        alignment=True adds what the decoder's alignments say about reading the text (evaluation.ALIGNMENT_KEYS):
-        `t2v_hip.alignment_stats` on the alignments of each group, one call and one copy to the host per group.  It combines
-        freely with prosody and either condition; without it the records hold exactly the keys above.
-        style=True adds the style round trip (evaluation.STYLE_KEYS): each group's post-net mels go once more through the
-        ragged `model.vae_gst` (eval mode, no random draws: the decoder's seeds and every other value stay as they are), and
-        after the last group one `t2v_hip.latent_neighbours` call places their mu among the mu of the distinct recordings of
-        `rows`, labelled with their emotions, each row's own recording excluded from the vote and taken as the rank's
-        target.  A row decoded to fewer than the encoder's 2 frames gets None.  style_k is lowered to (distinct recordings
-        - 1) when there are too few; fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The
-        result is then an evaluation.StyleRecords: the same list, with `style_info` (k, n_recordings and ref_accuracy, the
-        leave-one-out accuracy of the recordings themselves) for `evaluation.summarize`.
-        aligned=True adds the frame-aligned scores (evaluation.ALIGNED_KEYS): per group the cepstra of the post-net mels and
-        of the recordings' mels (`t2v_hip.mel_cepstrum`), one `t2v_hip.aligned_scores` call and one copy to the host.  Alone
-        it gives every row mcd_db and warp_dev, None on the six F0 values, and needs no vocoder; with prosody=True the two
-        pitch tracks computed there, cut to n_frames and n_ref_frames, feed the same call (a row decoded to fewer than the
-        vocoder's 4 frames keeps None on its F0 values and still gets mcd_db).  It draws nothing and changes no other key.
-        With speed or pitch on the vocoder the synthesised waveform has its own frame count, (samples // hop + 1), and its pitch
-        and level tracks are taken over exactly those frames; aligned=True together with prosody or energy is then a ValueError,
-        since the warping path is over mel frames and the waveform's frames lie on another time axis.
-        energy=True (needs the Griffin-Lim vocoder, like prosody) adds the level of both sides (evaluation.ENERGY_KEYS):
-        `t2v_hip.loudness` on the same two waveforms as prosody=True, which it shares when both are on (the vocoder runs once,
-        with the np.random draws of prosody=True; alone it draws what prosody=True would), one copy of the frame tracks to the
-        host per group.  With aligned=True as well, evaluation.ENERGY_ALIGNED_KEYS compare the two dB tracks along the warping
-        path (a few index operations on the device per group, one more copy).  Without it every record and summary holds
-        exactly the keys it held."""
+        (`synthesize_batch`, batch_size rows at a time, in input order) and compared with its own recording.  condition='ref':
+        the style comes from that recording (copy synthesis; its mel is computed once, for the style and for the comparison);
+        'emotion': from the centroid of the row's emotion label, which needs `load()`.  The decoder consumes its seeds as
+        len(rows) consecutive synthesize() calls.  Returns one record per row, in input order: the fields of `scoring.plain`
+        and those of every score that is on, each a function of scoring.py whose docstring says what it computes; the scores
+        combine freely, and a score that is off leaves every record and summary with exactly the keys it held.
+        alignment: `scoring.alignment`, evaluation.ALIGNMENT_KEYS.
+        prosody, energy: `scoring.prosody`, evaluation.PROSODY_KEYS, and `scoring.energy`, evaluation.ENERGY_KEYS.  Both need
+        the Griffin-Lim vocoder, which runs once per group for the two (`scoring.Group`) with the np.random draws of
+        `synthesize_batch(paths=...)`; either alone draws what the other would.  A row decoded to fewer than the vocoder's 4
+        frames has no waveform, and None on its synthesised side.
+        aligned: `scoring.aligned`, evaluation.ALIGNED_KEYS; mcd_db and warp_dev need no vocoder, the six F0 values are None
+        without prosody, and with energy evaluation.ENERGY_ALIGNED_KEYS come with it.  With speed or pitch on the vocoder the
+        waveform's tracks lie on another time axis than the mels' warping path: aligned together with prosody or energy is
+        then a ValueError.
+        style: `scoring.style_mu` per group and `scoring.style_records` after the last, evaluation.STYLE_KEYS; None for a row
+        decoded to fewer than the encoder's 2 frames.  style_k is lowered to (distinct recordings - 1) when there are too few;
+        fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The result is then an
+        evaluation.StyleRecords: the same list, with `style_info` for `evaluation.summarize`."""
+        import scoring
         import t2v_hip
-        from evaluation import aligned_fields, energy_fields, energy_path_fields, prosody_fields, ENERGY_ALIGNED_KEYS, ENERGY_FLOOR_DB
         if condition not in ('ref', 'emotion'):
             raise ValueError("condition must be 'ref' or 'emotion', got %r" % (condition,))
         if batch_size < 1:
@@ -718,194 +715,52 @@ class Synthesizer(object):
             raise RuntimeError("evaluate: no model (load_checkpoint() or load() first)")
         if condition == 'emotion' and self.neu is None:
             raise RuntimeError("evaluate(condition='emotion') needs the emotion centroids: use load(), not load_checkpoint()")
-        if prosody and not isinstance(self.vocoder, GriffinLimVocoder):
-            raise RuntimeError("evaluate(prosody=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
-        if energy and not isinstance(self.vocoder, GriffinLimVocoder):
-            raise RuntimeError("evaluate(energy=True) needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')")
+        if prosody:
+            self._need_griffin_lim('evaluate(prosody=True)')
+        if energy:
+            self._need_griffin_lim('evaluate(energy=True)')
         if aligned and (prosody or energy) and (self.vocoder.stretch[0] != self.vocoder.stretch[1]
                                                 or self.vocoder.shift[0] != self.vocoder.shift[1]):
-            # the warping path is over mel frames; a vocoder with speed or pitch puts the waveform's frames on another time axis
             raise ValueError("evaluate(aligned=True) with prosody or energy compares tracks frame by frame along the mels' path, "
                              "and the vocoder's speed %g / pitch %g put its waveform on another time axis: use one or the other"
                              % (self.vocoder.speed, self.vocoder.pitch))
         if energy:
             t2v_hip.kweight_coefficients(self.hparams.sampling_rate)        # an unsupported rate is refused before any work
-            if self.hparams.hop_length != t2v_hip.TRIM_HOP:
-                raise ValueError("evaluate(energy=True): the frame track is built for hop %d, the front end has hop %d"
-                                 % (t2v_hip.TRIM_HOP, self.hparams.hop_length))
-        if prosody and (self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE or self.hparams.hop_length != t2v_hip.F0_HOP):
-            raise ValueError("evaluate(prosody=True): the tracker is built for %d Hz and hop %d, the front end has %d Hz and hop %d"
-                             % (t2v_hip.F0_SAMPLE_RATE, t2v_hip.F0_HOP, self.hparams.sampling_rate, self.hparams.hop_length))
+            self._need_frame_grid('evaluate(energy=True)')
+        if prosody:
+            self._need_tracker_grid('evaluate(prosody=True)')
         rows = [(r[0], r[1], r[2], int(r[3])) for r in rows]
         one_hot = {0: (1.0, 0.0, 0.0, 0.0), 1: (0.0, 1.0, 0.0, 0.0), 2: (0.0, 0.0, 0.0, 1.0), 3: (0.0, 0.0, 1.0, 0.0)}
-        for r in rows:                      # ratio order (neu, sad, hap, ang), label order EMOTIONS
-            if r[3] not in one_hot:
-                raise ValueError("emotion label %r outside 0..3" % (r[3],))
-        if style:
-            if isinstance(style_k, bool) or int(style_k) != style_k or not 1 <= style_k <= t2v_hip.LATENT_MAX_K:
-                raise ValueError("style_k %r must be an integer in 1..%d" % (style_k, t2v_hip.LATENT_MAX_K))
-            rec_label = {}
-            for r in rows:
-                if rec_label.setdefault(r[0], r[3]) != r[3]:
-                    raise ValueError("evaluate(style=True): %r appears with the emotion labels %d and %d"
-                                     % (r[0], rec_label[r[0]], r[3]))
-            if len(rec_label) < 2:
-                raise ValueError("evaluate(style=True) needs at least 2 distinct recordings, got %d" % len(rec_label))
-            rec_index = {p: j for j, p in enumerate(rec_label)}          # recordings in order of first appearance
-            rec_mu, syn_mu = [None] * len(rec_label), [None] * len(rows)
-        dec = self.model.decoder
+        for row in rows:                    # ratio order (neu, sad, hap, ang), label order EMOTIONS
+            if row[3] not in one_hot:
+                raise ValueError("emotion label %r outside 0..3" % (row[3],))
+        if style:       # the recordings' labels, and the mu of the recordings (by path) and of the synthesised rows as they come
+            rec_label, rec_mu, syn_mu = scoring.style_recordings(rows, style_k), {}, []
         records = []
         for i0 in range(0, len(rows), batch_size):
             group = rows[i0:i0 + batch_size]
-            paths, texts = [r[0] for r in group], [r[1] for r in group]
+            paths, texts = [row[0] for row in group], [row[1] for row in group]
             uniq = list(dict.fromkeys(paths))
-            y_uniq, samples_uniq = self.load_wavs(uniq)
-            ref_mels, n_uniq = self._mels_of(y_uniq, samples_uniq)
+            wavs = self.load_wavs(uniq)
+            mels = self._mels_of(*wavs)
             if condition == 'ref':
-                mel, mel_postnet, gate, al, n_frames, lens = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), (ref_mels, n_uniq))
+                synthesis = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), mels)
             else:
-                mel, mel_postnet, gate, al, n_frames, lens = self._synthesize_ragged(texts, False, None, [one_hot[r[3]] for r in group])
-            which = [uniq.index(p) for p in paths]
-            truth = ref_mels if which == list(range(len(paths))) else ref_mels[torch.tensor(which, device=ref_mels.device)]
-            n_ref = [n_uniq[k] for k in which]
-            n = n_frames.tolist()
-            dtw = t2v_hip.mel_dtw(mel_postnet, n, truth, n_ref).cpu().tolist()
-            last = gate[torch.arange(len(group), device=gate.device), (n_frames - 1).to(gate.device), 0].cpu()
-            fired = (torch.sigmoid(last) > dec.gate_threshold).tolist()
-            for b, r in enumerate(group):
-                records.append({'dtw': dtw[b], 'n_frames': n[b], 'n_ref_frames': n_ref[b],
-                                'hit_max': bool(n[b] >= dec.max_decoder_steps and not fired[b]), 'emotion': r[3]})
+                synthesis = self._synthesize_ragged(texts, False, None, [one_hot[row[3]] for row in group])
+            g = scoring.Group(self, group, synthesis, uniq, wavs, mels, waveforms=prosody or energy)
+            parts = [scoring.plain(g)]
             if alignment:
-                for b, fields in enumerate(self._alignment_rows(al, n, lens)[0]):
-                    records[i0 + b].update(fields)
-            if prosody or energy:
-                # the waveforms of the rows that have one, for the pitch and for the level
-                can = [b for b in range(len(group)) if n[b] >= 4]
-                if can:
-                    sel = torch.tensor(can, device=mel.device)
-                    wavs = self.vocoder.batch(mel if len(can) == len(group) else mel[sel], [n[b] for b in can])
-                    y_syn = torch.zeros(len(can), max(w.numel() for w in wavs), device=mel.device)
-                    for k, w in enumerate(wavs):
-                        y_syn[k, :w.numel()] = w
-                    # the frames of each waveform's own tracks: n[b] without speed or pitch on the vocoder, else what it wrote
-                    syn_frames = [w.numel() // self.hparams.hop_length + 1 for w in wavs]
+                parts.append(scoring.alignment(g))
             if prosody:
-                # both sides' tracks side by side in one tensor: one copy to the host per group
-                tracks = [t2v_hip.f0(y_uniq, samples_uniq)]
-                if can:
-                    tracks.append(t2v_hip.f0(y_syn, [w.numel() for w in wavs]))
-                width = max(t.size(1) for t in tracks)
-                host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in tracks], 0).cpu().tolist()
-                for b in range(len(group)):
-                    syn_track = host[len(uniq) + can.index(b)][:syn_frames[can.index(b)]] if b in can else None
-                    records[i0 + b].update(prosody_fields(syn_track, host[which[b]][:n_ref[b]]))
+                parts.append(scoring.prosody(g))
             if energy:
-                loud = [t2v_hip.loudness(y_uniq, samples_uniq, self.hparams.sampling_rate)]
-                if can:
-                    loud.append(t2v_hip.loudness(y_syn, [w.numel() for w in wavs], self.hparams.sampling_rate))
-                levels = [t2v_hip.energy_db(r.frame_ms) for r in loud]
-                width = max(t.size(1) for t in levels)
-                host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in levels], 0).cpu().tolist()
-                for b in range(len(group)):
-                    k = can.index(b) if b in can else None
-                    records[i0 + b].update(energy_fields(loud[1].integrated[k] if k is not None else None,
-                                                         host[len(uniq) + k][:syn_frames[k]] if k is not None else None,
-                                                         loud[0].integrated[which[b]], host[which[b]][:n_ref[b]]))
+                parts.append(scoring.energy(g))
             if aligned:
-                cep = t2v_hip.mel_cepstrum(mel_postnet, n)
-                cep_ref = t2v_hip.mel_cepstrum(ref_mels, n_uniq)
-                same = which == list(range(len(paths)))
-                pick = None if same else torch.tensor(which, device=ref_mels.device)
-                f0x = f0y = None
-                if prosody:
-                    # the tracks above, on the device: a row without a waveform is unvoiced everywhere and gets no F0 values
-                    f0y = torch.nn.functional.pad(tracks[0], (0, max(0, max(n_ref) - tracks[0].size(1))))
-                    f0y = f0y if same else f0y[pick]
-                    f0x = torch.zeros(len(group), max(n), device=mel.device)
-                    if can:
-                        w = min(max(n), tracks[1].size(1))
-                        f0x[torch.tensor(can, device=mel.device), :w] = tracks[1][:, :w]
-                r = t2v_hip.aligned_scores(cep, n, cep_ref if same else cep_ref[pick], n_ref, f0x, f0y, return_path=energy)
-                host = torch.cat([r.counts.double(), r.sums.double()], 1).cpu().tolist()
-                for b in range(len(group)):
-                    records[i0 + b].update(aligned_fields(host[b][:len(t2v_hip.ALIGNED_COUNTS)], host[b][len(t2v_hip.ALIGNED_COUNTS):],
-                                                          f0=prosody and n[b] >= 4))
-                if energy:
-                    # the two dB tracks at the path's points, and whether both frames sound: one copy to the host per group
-                    for b in range(len(group)):
-                        records[i0 + b].update(dict.fromkeys(ENERGY_ALIGNED_KEYS))
-                    if can:
-                        dev = mel.device
-                        sel = torch.tensor(can, device=dev)
-                        n_x = torch.tensor([n[b] for b in can], device=dev)
-                        n_y = torch.tensor([n_ref[b] for b in can], device=dev)
-                        neg = float('-inf')
-                        ex = levels[1].masked_fill(torch.arange(levels[1].size(1), device=dev)[None, :] >= n_x[:, None], neg)
-                        ey = levels[0][torch.tensor([which[b] for b in can], device=dev)]
-                        ey = ey.masked_fill(torch.arange(ey.size(1), device=dev)[None, :] >= n_y[:, None], neg)
-                        path = r.path[sel].long()
-                        pi = torch.minimum(path[:, :, 0].clamp(min=0), n_x[:, None] - 1)
-                        pj = torch.minimum(path[:, :, 1].clamp(min=0), n_y[:, None] - 1)
-                        a, c = ex.gather(1, pi), ey.gather(1, pj)
-                        keep = ((a > ex.amax(1, keepdim=True) - ENERGY_FLOOR_DB) & (c > ey.amax(1, keepdim=True) - ENERGY_FLOOR_DB)
-                                & (torch.arange(path.size(1), device=dev)[None, :] < r.n_points[sel][:, None]))
-                        host = torch.stack([a.double(), c.double(), keep.double()], 1).cpu().tolist()
-                        for k, b in enumerate(can):
-                            pa, pc, pk = host[k]
-                            records[i0 + b].update(energy_path_fields([(u, v) for u, v, w in zip(pa, pc, pk) if w]))
+                parts.append(scoring.aligned(g, f0=prosody, energy=energy))
             if style:
-                new = [j for j, p in enumerate(uniq) if rec_mu[rec_index[p]] is None]
-                if new:
-                    sel = torch.tensor(new, device=ref_mels.device)
-                    mu = self.model.vae_gst(ref_mels if len(new) == len(uniq) else ref_mels[sel], [n_uniq[j] for j in new])[1]
-                    for row, j in enumerate(new):
-                        rec_mu[rec_index[uniq[j]]] = mu[row]
-                can = [b for b in range(len(group)) if n[b] >= 2]
-                if can:
-                    sel = torch.tensor(can, device=mel_postnet.device)
-                    mu = self.model.vae_gst(mel_postnet if len(can) == len(group) else mel_postnet[sel], [n[b] for b in can])[1]
-                    for row, b in enumerate(can):
-                        syn_mu[i0 + b] = mu[row]
-        if not style:
-            return records
-        return self._style_records(rows, records, list(rec_label.values()), rec_index, rec_mu, syn_mu, int(style_k))
-
-    @staticmethod
-    def _style_records(rows, records, rec_labels, rec_index, rec_mu, syn_mu, style_k):
-        """the style fields of evaluate(style=True) from the recordings' mu (one per distinct path, with its label) and the
-        synthesised rows' mu (None: no style fields): one `latent_neighbours` call for the rows, one for the recordings'
-        own leave-one-out accuracy, and host arithmetic in fp64 (latent_scores)"""
-        import t2v_hip
-        from evaluation import EMOTIONS, StyleRecords, style_fields
-        from latent_scores import knn_predict, silhouette
-        refs = torch.stack(rec_mu).float().contiguous()
-        labels = np.asarray(rec_labels, dtype=np.int64)
-        k = min(style_k, len(rec_labels) - 1)
-        C = len(EMOTIONS)
-        loo = t2v_hip.latent_neighbours(refs, labels, k=k, n_classes=C)
-        out = StyleRecords(records)
-        out.style_info = {'k': k, 'n_recordings': len(rec_labels),
-                          'ref_accuracy': float((knn_predict(loo.idx.cpu().numpy(), labels, C) == labels).mean())}
-        have = [i for i, m in enumerate(syn_mu) if m is not None]
-        fields = {}
-        refs64 = refs.cpu().numpy().astype(np.float64)
-        for c0 in range(0, len(have), t2v_hip.LATENT_MAX_POINTS):
-            chunk = have[c0:c0 + t2v_hip.LATENT_MAX_POINTS]
-            own = [rec_index[rows[i][0]] for i in chunk]
-            rows_q = chunk if len(chunk) > 1 else chunk * 2          # the kernel takes 2 queries or more
-            own_q = own if len(chunk) > 1 else own * 2
-            q = torch.stack([syn_mu[i] for i in rows_q]).float().contiguous()
-            r = t2v_hip.latent_neighbours(refs, labels, q, k=k, n_classes=C, exclude=own_q, target=own_q)
-            vote = knn_predict(r.idx.cpu().numpy(), labels, C)
-            lab = np.asarray([rows[i][3] for i in rows_q], dtype=np.int64)
-            sil = silhouette(r.class_sum.cpu().numpy(), r.class_cnt.cpu().numpy(), lab)
-            rank = r.rank.cpu().tolist()
-            dist = np.sqrt(((q.cpu().numpy().astype(np.float64) - refs64[own_q]) ** 2).sum(axis=1))
-            for row, i in enumerate(chunk):
-                fields[i] = style_fields(rows[i][3], vote[row], rank[row], dist[row], sil[row])
-        for i, rec in enumerate(out):
-            rec.update(fields.get(i) or style_fields(rows[i][3], None, None, None, None))
-        return out
+                syn_mu += scoring.style_mu(g, rec_mu)
+            records += [{k: v for fields in parts for k, v in fields[b].items()} for b in range(len(group))]
+        return scoring.style_records(rows, records, rec_label, rec_mu, syn_mu, style_k) if style else records
 
 
 # ---------------------------------------------------------------------- command line
