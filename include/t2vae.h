@@ -1081,6 +1081,43 @@ int t2v_phase_vocoder(const float* mag, const float* phase, const int32_t* n_fra
 int t2v_spectral_envelope(const float* mag, const int32_t* n_frames, int B, int T, int t_stride, int order, int iters, int p, int q,
                           float* log_env_out, float* mag_out, int out_stride, void* stream);
 
+/* ------------------------------------------------------------------ voice quality: spectral balance and cepstral peak prominence
+ * The spectral-balance descriptors of eGeMAPS (Eyben et al. 2016) and the cepstral peak prominence of Hillenbrand et al. (1994)
+ * of a ragged batch of 16 kHz waveforms (csrc/voice.hip, one launch), on the grid of t2v_f0_yin, t2v_loudness and
+ * t2v_trim_bounds: y is (B, y_stride) fp32, row b has n[b] samples (device int32, clamped to 0..y_stride) and n[b] / 256 + 1
+ * frames (none for n[b] = 0); frame t covers the samples [256 t - 512, 256 t + 512), every sample index outside [0, n[b])
+ * counts as 0 and nothing outside is read.  Per frame, with x its 1024 samples, w the front end's periodic Hann window
+ * (0.5 - 0.5 cos(2 pi i / 1024) in fp64, rounded once), P[k] = |DFT1024(x w)[k]|^2 for k = 0..512 (a bin is 15.625 Hz),
+ * fl = max(1e-9 max_k P, the smallest normal fp32) and dB(v) = 10 log10 v, the T2V_VOICE_FEATS planes of out,
+ * (B, T2V_VOICE_FEATS, t_stride) fp32 with time contiguous, are
+ *   0 level_db       dB(max(sum_{k=4..319} P, fl)): the 50 Hz - 5 kHz band; the host gates on it;
+ *   1 alpha_db       dB(max(sum_{k=64..319} P, fl) / max(sum_{k=4..63} P, fl)): 1 - 5 kHz over 50 Hz - 1 kHz;
+ *   2 hammarberg_db  dB(max(max_{k=0..127} P, fl) / max(max_{k=128..319} P, fl)): the peak below 2 kHz over the peak in 2 - 5 kHz;
+ *   3 slope_db_khz   the least-squares slope of L[k] = dB(max(P[k], fl)) on 15.625 k / 1000 over k = 32..96 (500 - 1500 Hz),
+ *                    from centred abscissae: sum (k - 64) L[k] / 357.5;
+ *   4 cpp_db         c[q] = Re DFT1024(even extension of L)[q] / 1024 for q = 0..512 (L[1024 - k] = L[k]; the transform of the
+ *                    spectral envelope's lifter), C[q] = 20 log10 max(|c[q]|, 1e-3 max_{q=16..266} |c[q]|, 1e-4), q* the lowest q
+ *                    in 32..266 (the 60 - 500 Hz lags of the tracker) with the largest C[q]; cpp_db = C[q*] less the value at q*
+ *                    of the least-squares line of C on q over q = 16..266.  A difference of dB values: the scale of L drops out;
+ *   5 cpp_lag        (float)q*.
+ * The floor fl holds for every band sum and band maximum, so a band without energy in a frame that is not silent reads 90 dB
+ * under the frame's largest bin and no ratio divides by 0.  The absolute floor 1e-4 (dB: c has L's unit) is some four decades
+ * under the cepstral peak of a voice and far above the rounding of a flat L (a single impulse): such a frame has all C equal,
+ * cpp_db 0 to rounding and cpp_lag 32, whatever the rounding was.
+ * The transform of x w runs in fp64 and each P[k] is rounded to fp32 once (an fp32 transform is off by a fraction of an ulp
+ * of the largest bin in every bin, and the planes read bins 50 to 90 dB under it); everything from L on is fp32.
+ * A frame with sum_k P = 0 is silent: level_db = T2V_VOICE_SILENT_DB and +0 on the other five.  Frames at and past a row's
+ * count are +0 on all planes, up to t_stride.
+ * A workgroup owns T2V_VOICE_FRAMES consecutive frames of one row, a wave each.  Every sum and maximum is a wave reduction in
+ * a fixed order, ties go to the lower index, and there is no floating-point atomic: a frame's bits depend on that frame alone,
+ * so a row gives the same bits alone, in any batch and at any stride.  The call takes no table and no scratch.
+ * A null pointer, B < 1, y_stride < 1 or above 2^30, or t_stride < y_stride / 256 + 1 is T2V_ERR_ARG; more than 2^31 - 1
+ * workgroups (B ceil(t_stride / T2V_VOICE_FRAMES)) is T2V_ERR_DIMS. */
+#define T2V_VOICE_FEATS 6
+#define T2V_VOICE_FRAMES 8          /* frames per workgroup */
+#define T2V_VOICE_SILENT_DB -200
+int t2v_voice_quality(const float* y, const int32_t* n, int y_stride, int B, float* out, int t_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,38 +48,6 @@ __device__ __forceinline__ float env_log(float x) {
     return fmaf(fe, 0.693359375f, fmaf(fe, -2.12194440e-4f, logf(m)));
 }
 
-// sample n (0..1023) of the even extension of x[0..512]
-__device__ __forceinline__ int env_fold(int n) { return n <= 512 ? n : 1024 - n; }
-
-// Re of the forward 1024-point DFT of the even extension of s[0..512], times `scale`, bins n <= keep (the others 0), back
-// into s.  One wave; z: its 512 complex points.
-__device__ __forceinline__ void env_transform(float* s, c32* z, const c32* tw512, const c32* tw1024, int keep, float scale,
-                                              int lane) {
-    c32 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int j = lane + 64 * r;
-        v[r] = {s[env_fold(2 * j)], s[env_fold(2 * j + 1)]};
-    }
-    __builtin_amdgcn_wave_barrier();
-    fft512(v, z, tw512, lane);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int k = lane + 64 * r;
-        c32 xk, xc;
-        untangle(z[k], z[(512 - k) & 511], tw1024[k], xk, xc);
-        s[k] = k <= keep ? xk.x * scale : 0.f;
-        s[512 - k] = 512 - k <= keep ? xc.x * scale : 0.f;
-    }
-    if (lane == 0) {
-        c32 xk, xc;
-        untangle(z[256], z[256], tw1024[256], xk, xc);
-        s[256] = 256 <= keep ? xk.x * scale : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(64 * ENV_W) void k_spectral_envelope(const float* __restrict__ mag, const int32_t* __restrict__ n_frames,
                                                                   int T, int t_stride, int order, int iters, int p, int q,
                                                                   double inv_q, float* __restrict__ log_env_out,
@@ -149,8 +117,8 @@ __global__ __launch_bounds__(64 * ENV_W) void k_spectral_envelope(const float* _
             }
             __builtin_amdgcn_wave_barrier();
             for (int it = 0; it <= iters; ++it) {
-                env_transform(s, Z[w], TW512, TW1024, order, 1.f / 1024.f, lane);     // the liftered cepstrum
-                env_transform(s, Z[w], TW512, TW1024, 512, 1.f, lane);                // E - mu
+                even_transform(s, Z[w], TW512, TW1024, order, 1.f / 1024.f, lane);    // the liftered cepstrum
+                even_transform(s, Z[w], TW512, TW1024, 512, 1.f, lane);               // E - mu
 #pragma unroll
                 for (int r = 0; r < 8; ++r) E[r] = s[lane + 64 * r];
                 E512 = s[512];

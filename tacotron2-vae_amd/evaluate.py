@@ -3,8 +3,8 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--energy] [--attention_window BACK,AHEAD] [--speed R] [--pitch ST]
-                       [--formant ST] [--preserve_formants]
+                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--attention_window BACK,AHEAD] [--speed R]
+                       [--pitch ST] [--formant ST] [--preserve_formants]
                        [--hparams ...]
 
 Filelist rows are `path|text|speaker|emotion`.  --condition ref (default) takes the style from the row's own recording
@@ -68,15 +68,27 @@ along the warping path, over the points where both sides sound.  The summary gai
 loudness_shift_lu_mean / _abs_mean, energy_spread_ratio_mean (and the two path means), and per emotion loudness_vs_neu_lu and
 loudness_ref_vs_neu_lu, the emotion's mean loudness minus neutral's, synthesised and recorded.
 
+--voice asks about the fourth correlate, voice quality: is an "ang" row pressed (a flat spectral tilt) and a "sad" one lax and
+breathy (a steep tilt, a weak cepstral peak), as the recordings are?  A decoder can copy a clip's pitch and level and still
+render every emotion with the neutral voice's timbre.  On the same two waveforms as --prosody and --energy, the spectral-balance
+descriptors of eGeMAPS and the cepstral peak prominence are taken per mel frame (`t2v_hip.voice_quality`, csrc/voice.hip).
+Every row gains alpha_db / alpha_ref_db (1-5 kHz over 50 Hz-1 kHz), hammarberg_db / hammarberg_ref_db (the peak below 2 kHz
+over the peak in 2-5 kHz), slope_db_khz / slope_ref_db_khz (500-1500 Hz), cpp_db / cpp_ref_db and alpha_shift_db, cpp_shift_db
+(synthesis - recording), each the median over the frames that are not silent and lie within 40 dB of the row's loudest; null
+for a side without such a frame or without a waveform.  With --aligned the row also gains alpha_rmse_db and alpha_corr of the
+two alpha_db tracks along the warping path.  The summary gains "voice": overall and per emotion n_voice and the means of the
+keys, and per emotion alpha_vs_neu_db, alpha_ref_vs_neu_db, cpp_vs_neu_db and cpp_ref_vs_neu_db, the emotion's mean minus
+neutral's, synthesised and recorded; no thresholds.
+
 --attention_window BACK,AHEAD decodes every row under the attention constraint of `Decoder.attention_window` (each frame
 attends within BACK positions behind and AHEAD in front of the position the previous frame attended most).
 OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart.
 
 --speed R and --pitch ST set the tempo and the pitch shift (semitones) of the vocoder leg (`GriffinLimVocoder(speed=, pitch=)`,
-DESIGN 7o): the waveforms that --prosody and --energy measure are the ones the synthesis command line would write with the
-same flags, and their pitch and level tracks run over those waveforms' own frames (ceil(n_frames / speed) of them, not
-n_frames).  The mels, and with them dtw and every score taken of mels, do not change.  --aligned together with --prosody or
---energy is refused with them: the warping path is over mel frames, and the waveform's frames lie on another time axis.
+DESIGN 7o): the waveforms that --prosody, --energy and --voice measure are the ones the synthesis command line would write
+with the same flags, and their tracks run over those waveforms' own frames (ceil(n_frames / speed) of them, not n_frames).
+The mels, and with them dtw and every score taken of mels, do not change.  --aligned together with --prosody, --energy or
+--voice is refused with them: the warping path is over mel frames, and the waveform's frames lie on another time axis.
 OUT.json always holds "speed" and "pitch" (1.0 and 0.0 without the flags).
 
 --formant ST and --preserve_formants act in the same vocoder leg (`GriffinLimVocoder(formant=, preserve_formants=)`, DESIGN
@@ -102,7 +114,8 @@ def build_arg_parser():
                    help="also track the pitch (YIN, 60-500 Hz) of each synthesised waveform (Griffin-Lim) and of its recording: "
                         "rows gain median F0, spread in semitones, voiced share and f0_shift_st; the summary their means")
     p.add_argument('--vocoder', choices=['griffin_lim', 'griffin_lim_fast'], default='griffin_lim',
-                   help="the vocoder of --prosody and --energy (griffin_lim_fast: momentum 0.99 and NNLS mel inversion); unused without them")
+                   help="the vocoder of --prosody, --energy and --voice (griffin_lim_fast: momentum 0.99 and NNLS mel inversion); unused "
+                        "without them")
     p.add_argument('--alignment', action='store_true',
                    help="also score the attention alignment of each synthesis (did the decoder read the text?): rows gain focus, "
                         "reach, end_reach, back_share, jump_share, stall_frames, uncovered_share, gap_symbols and n_symbols; "
@@ -119,6 +132,10 @@ def build_arg_parser():
                    help="also measure the BS.1770 loudness and the frame level of each synthesised waveform (Griffin-Lim) and of "
                         "its recording: rows gain loudness_lufs, loudness_ref_lufs, loudness_shift_lu and the energy spreads, "
                         "with --aligned energy_rmse_db and energy_corr; the summary an energy block")
+    p.add_argument('--voice', action='store_true',
+                   help="also measure the voice quality of each synthesised waveform (Griffin-Lim) and of its recording: rows gain "
+                        "the medians of alpha ratio, Hammarberg index, spectral slope and cepstral peak prominence on both sides, "
+                        "alpha_shift_db and cpp_shift_db, with --aligned alpha_rmse_db and alpha_corr; the summary a voice block")
     from evaluation import parse_attention_window
     p.add_argument('--attention_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
                    help="attention constraint of the free-running decode: every frame attends within BACK positions behind and "
@@ -139,8 +156,8 @@ def parse_args(argv=None):
         raise SystemExit("--style_k must be in 1..32")
     if args.limit is not None and args.limit < 1:
         raise SystemExit("--limit must be >= 1")
-    if args.aligned and (args.prosody or args.energy) and (args.speed != 1.0 or args.pitch != 0.0):
-        raise SystemExit("--aligned with --prosody / --energy scores tracks along the mels' warping path; with --speed / --pitch "
+    if args.aligned and (args.prosody or args.energy or args.voice) and (args.speed != 1.0 or args.pitch != 0.0):
+        raise SystemExit("--aligned with --prosody / --energy / --voice scores tracks along the mels' warping path; with --speed / --pitch "
                          "the waveform is on another time axis: drop --aligned or the two flags")
     from synthesizer import tempo_options
     tempo_options(args)                                                   # a value out of range is refused here
@@ -173,17 +190,18 @@ def main(argv=None):
         hp.parse(args.hparams)
     from synthesizer import tempo_options
     from wavio import wav_options
+    waveforms = args.prosody or args.energy or args.voice                 # the scores that need the vocoder
     syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args))
     if args.condition == 'emotion':
-        syn.load(args.load_path, vocoder=args.vocoder if args.prosody or args.energy else None, filelist_path=args.filelist_path)
+        syn.load(args.load_path, vocoder=args.vocoder if waveforms else None, filelist_path=args.filelist_path)
     else:
         syn.load_checkpoint(args.load_path)
-        if args.prosody or args.energy:
+        if waveforms:
             syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft, syn.speed, syn.pitch_st, syn.formant, syn.preserve_formants)
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
-                           aligned=args.aligned, energy=args.energy, **style)
+                           aligned=args.aligned, energy=args.energy, voice=args.voice, **style)
     summary = summarize(records)
     formant_keys = {}
     if args.formant != 0.0 or args.preserve_formants:                     # the report gains its new keys only with a new flag
@@ -206,6 +224,11 @@ def main(argv=None):
             print("%s: loudness_shift_lu_mean %s, loudness_vs_neu_lu %s (recordings %s), energy_spread_ratio_mean %s (%d rows)"
                   % (name, st['loudness_shift_lu_mean'], st['loudness_vs_neu_lu'], st['loudness_ref_vs_neu_lu'],
                      st['energy_spread_ratio_mean'], st['n_energy']))
+    if args.voice:
+        for name, st in summary['voice']['by_emotion'].items():
+            print("%s: alpha_shift_db_mean %s, alpha_vs_neu_db %s (recordings %s), cpp_vs_neu_db %s (recordings %s) (%d rows)"
+                  % (name, st['alpha_shift_db_mean'], st['alpha_vs_neu_db'], st['alpha_ref_vs_neu_db'], st['cpp_vs_neu_db'],
+                     st['cpp_ref_vs_neu_db'], st['n_voice']))
     if args.style:
         st = summary['style']
         print("style: accuracy %s (recordings leave-one-out %s, k = %s), own recording nearest in %s of %d rows"

@@ -44,7 +44,16 @@ deviation of the K-weighted frame level in dB over the sounding frames, those wi
 frame (the trim's rule; like the alignment thresholds an uncalibrated choice, not a measurement).  A side without a loudness
 (no waveform, shorter than one 400 ms block, or below the gates) has None.  With aligned=True as well, `energy_rmse_db` and
 `energy_corr` (Pearson) compare the two dB tracks along the warping path, over the points where both sides sound.  `summarize`
-adds an `energy` block."""
+adds an `energy` block.
+
+`evaluate(voice=True)` adds the fourth correlate, voice quality (`t2v_hip.voice_quality` on the same two waveforms): the
+spectral-balance descriptors of eGeMAPS and the cepstral peak prominence, each the median over the side's counted frames (not
+silent and within VOICE_FLOOR_DB of the row's loudest frame): `alpha_db` / `alpha_ref_db` (1 - 5 kHz over 50 Hz - 1 kHz; a
+pressed voice has more), `hammarberg_db` / `hammarberg_ref_db` (the peak below 2 kHz over the peak in 2 - 5 kHz), `slope_db_khz`
+/ `slope_ref_db_khz` (over 500 - 1500 Hz), `cpp_db` / `cpp_ref_db` (a breathy voice has a weak cepstral peak), and
+`alpha_shift_db` and `cpp_shift_db` = synthesis - recording.  A side without a counted frame or without a waveform has None.
+With aligned=True as well, `alpha_rmse_db` and `alpha_corr` compare the two alpha_db tracks along the warping path, over the
+points where both frames are counted.  `summarize` adds a `voice` block."""
 import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
@@ -230,20 +239,25 @@ def energy_fields(loudness, track_db, ref_loudness, ref_track_db):
             'energy_ref_spread_db': energy_spread(ref_track_db) if ref_track_db is not None else None}
 
 
-def energy_path_fields(pairs):
-    """the ENERGY_ALIGNED_KEYS from the (synthesis dB, recording dB) pairs at the warping path's points where both sides sound:
-    the root mean square difference and the Pearson correlation (None under 2 points or at a zero variance)"""
+def _path_rmse_corr(pairs):
+    """(root mean square difference, Pearson correlation) of (synthesis, recording) pairs: both None without a pair, the
+    correlation also under 2 pairs or at a zero variance"""
     pairs = [(float(a), float(b)) for a, b in pairs]
-    out = dict.fromkeys(ENERGY_ALIGNED_KEYS)
     if not pairs:
-        return out
+        return None, None
     n = len(pairs)
-    out['energy_rmse_db'] = math.sqrt(sum((a - b) ** 2 for a, b in pairs) / n)
+    rmse = math.sqrt(sum((a - b) ** 2 for a, b in pairs) / n)
     ma, mb = sum(a for a, _ in pairs) / n, sum(b for _, b in pairs) / n
     sxx, syy = sum((a - ma) ** 2 for a, _ in pairs), sum((b - mb) ** 2 for _, b in pairs)
     if n >= 2 and sxx > 0.0 and syy > 0.0:
-        out['energy_corr'] = max(-1.0, min(1.0, sum((a - ma) * (b - mb) for a, b in pairs) / math.sqrt(sxx * syy)))
-    return out
+        return rmse, max(-1.0, min(1.0, sum((a - ma) * (b - mb) for a, b in pairs) / math.sqrt(sxx * syy)))
+    return rmse, None
+
+
+def energy_path_fields(pairs):
+    """the ENERGY_ALIGNED_KEYS from the (synthesis dB, recording dB) pairs at the warping path's points where both sides sound:
+    the root mean square difference and the Pearson correlation (None under 2 points or at a zero variance)"""
+    return dict(zip(ENERGY_ALIGNED_KEYS, _path_rmse_corr(pairs)))
 
 
 def _energy_stats(records):
@@ -283,6 +297,87 @@ def _energy_block(records, emotions):
             st[out_key] = a - b if a is not None and b is not None else None
         by[name] = st
     return {'overall': _energy_stats(records), 'by_emotion': by}
+
+
+VOICE_KEYS = ('alpha_db', 'alpha_ref_db', 'alpha_shift_db', 'hammarberg_db', 'hammarberg_ref_db', 'slope_db_khz', 'slope_ref_db_khz',
+              'cpp_db', 'cpp_ref_db', 'cpp_shift_db')
+VOICE_ALIGNED_KEYS = ('alpha_rmse_db', 'alpha_corr')
+VOICE_TRACKS = ('level_db', 'alpha_db', 'hammarberg_db', 'slope_db_khz', 'cpp_db')      # the planes voice_fields reads
+VOICE_SILENT_DB = -200.0   # level_db of a frame without energy (T2V_VOICE_SILENT_DB)
+VOICE_FLOOR_DB = 40.0      # a frame is counted within this many dB of the row's loudest frame: ENERGY_FLOOR_DB's rule
+
+
+def voice_counted(level_db, floor_db=VOICE_FLOOR_DB):
+    """one bool per frame of a level_db track: not silent and within floor_db of the loudest frame that is not; a track of
+    silent frames alone has none (`t2v_hip.voice_counted` on the host)"""
+    track = [float(v) for v in level_db]
+    heard = [v for v in track if v > VOICE_SILENT_DB]
+    top = max(heard) if heard else 0.0
+    return [v > VOICE_SILENT_DB and v > top - floor_db for v in track]
+
+
+def voice_medians(tracks):
+    """{plane: median over the counted frames} of one side's VOICE_TRACKS (a dict of per-frame lists), the four planes
+    behind level_db; None everywhere for a side without a waveform (tracks None) or without a counted frame"""
+    names = VOICE_TRACKS[1:]
+    if tracks is None:
+        return dict.fromkeys(names)
+    keep = voice_counted(tracks['level_db'])
+    return {k: _median([float(v) for v, c in zip(tracks[k], keep) if c]) for k in names}
+
+
+def voice_fields(syn_tracks, ref_tracks):
+    """the VOICE_KEYS of one record from the voice-quality tracks (`t2v_hip.voice_quality`, cut to the side's frames) of the
+    synthesised waveform and of the recording: each value the median over its side's counted frames, the two shifts synthesis
+    minus recording.  syn_tracks is None when the row has no waveform (fewer than the vocoder's 4 frames)."""
+    syn, ref = voice_medians(syn_tracks), voice_medians(ref_tracks)
+
+    def shift(k):
+        return syn[k] - ref[k] if syn[k] is not None and ref[k] is not None else None
+    return {'alpha_db': syn['alpha_db'], 'alpha_ref_db': ref['alpha_db'], 'alpha_shift_db': shift('alpha_db'),
+            'hammarberg_db': syn['hammarberg_db'], 'hammarberg_ref_db': ref['hammarberg_db'],
+            'slope_db_khz': syn['slope_db_khz'], 'slope_ref_db_khz': ref['slope_db_khz'],
+            'cpp_db': syn['cpp_db'], 'cpp_ref_db': ref['cpp_db'], 'cpp_shift_db': shift('cpp_db')}
+
+
+def voice_path_fields(pairs):
+    """the VOICE_ALIGNED_KEYS from the (synthesis, recording) alpha_db pairs at the warping path's points where both frames
+    are counted, as `energy_path_fields`"""
+    return dict(zip(VOICE_ALIGNED_KEYS, _path_rmse_corr(pairs)))
+
+
+def _voice_stats(records):
+    """Over the rows that stopped at the gate: `n_voice` of them have an alpha ratio on both sides (`alpha_shift_db` not
+    None); `<key>_mean` for every key of VOICE_KEYS, and with the aligned keys of VOICE_ALIGNED_KEYS, over the rows that have
+    the value."""
+    stopped = [r for r in records if not r['hit_max']]
+    out = {'n_voice': sum(1 for r in stopped if r.get('alpha_shift_db') is not None)}
+    keys = VOICE_KEYS + (VOICE_ALIGNED_KEYS if any('alpha_rmse_db' in r for r in records) else ())
+    for k in keys:
+        out[k + '_mean'] = _mean([r[k] for r in stopped if r.get(k) is not None])
+    return out
+
+
+def _voice_block(records, emotions):
+    """the `voice` entry of summarize(): overall and by_emotion `_voice_stats`; every emotion also carries `alpha_vs_neu_db`,
+    `alpha_ref_vs_neu_db`, `cpp_vs_neu_db` and `cpp_ref_vs_neu_db`, the mean alpha_db and cpp_db of its stopped rows minus
+    those of the emotion named 'neu', for the synthesis and for the recordings (None where either has no row with the value,
+    or no 'neu' is listed): whether the emotions keep their order of tilt and of breathiness.  No thresholds."""
+    stopped = [r for r in records if not r['hit_max']]
+
+    def level(i, key):
+        return _mean([r[key] for r in stopped if int(r['emotion']) == i and r.get(key) is not None])
+
+    neu = list(emotions).index('neu') if 'neu' in emotions else None
+    by = {}
+    for i, name in enumerate(emotions):
+        st = _voice_stats([r for r in records if int(r['emotion']) == i])
+        for key, out_key in (('alpha_db', 'alpha_vs_neu_db'), ('alpha_ref_db', 'alpha_ref_vs_neu_db'),
+                             ('cpp_db', 'cpp_vs_neu_db'), ('cpp_ref_db', 'cpp_ref_vs_neu_db')):
+            a, b = level(i, key), level(neu, key) if neu is not None else None
+            st[out_key] = a - b if a is not None and b is not None else None
+        by[name] = st
+    return {'overall': _voice_stats(records), 'by_emotion': by}
 
 
 STYLE_KEYS = ('style_emotion', 'style_hit', 'style_own_rank', 'style_own_dist', 'style_silhouette')
@@ -352,7 +447,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
     they carry the aligned keys (evaluate(aligned=True)), `n_aligned` and the means of `_aligned_stats`.
     When they carry the style keys (evaluate(style=True)) the result gains 'style': `_style_block`, with k, n_recordings and
     ref_accuracy from style_info, else from the records' own `style_info` (StyleRecords), else None.
-    When they carry the energy keys (evaluate(energy=True)) the result gains 'energy': `_energy_block`."""
+    When they carry the energy keys (evaluate(energy=True)) the result gains 'energy': `_energy_block`; when they carry the
+    voice keys (evaluate(voice=True)), 'voice': `_voice_block`."""
     if style_info is None:
         style_info = getattr(records, 'style_info', None)
     records = list(records)
@@ -378,6 +474,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
         out['style'] = _style_block(records, emotions, style_info)
     if any('loudness_shift_lu' in r for r in records):
         out['energy'] = _energy_block(records, emotions)
+    if any('alpha_shift_db' in r for r in records):
+        out['voice'] = _voice_block(records, emotions)
     return out
 
 

@@ -2,8 +2,8 @@
 
 The Group holds what the scores share, under one name each: the synthesis and the recordings of the group, which recording
 each row is compared with, which rows are long enough for the vocoder and for the reference encoder, the synthesised
-waveforms, and the pitch and level tracks of both sides.  Every score is a function of the Group that returns one dict of
-fields per row; none reads what another left behind except through the Group."""
+waveforms, and the pitch, level and voice-quality tracks of both sides.  Every score is a function of the Group that returns
+one dict of fields per row; none reads what another left behind except through the Group."""
 from functools import cached_property
 
 import numpy as np
@@ -33,7 +33,7 @@ class Group(object):
     with_wav: the rows that have a waveform (empty without `waveforms`), wav_slot their places among the waveforms, wav_index
     with_wav on the device; y_syn, syn_samples, syn_frames: the waveforms zero-padded in one tensor, their sample counts and the
     frames of their own tracks (n[b] without speed or pitch on the vocoder, else what it wrote); those four are None for a
-    group without a waveform.  f0_tracks, loudness, levels: both sides' tracks, made by the first score that asks."""
+    group without a waveform.  f0_tracks, loudness, levels, voice: both sides' tracks, made by the first score that asks."""
 
     def __init__(self, syn, rows, synthesis, uniq, wavs, mels, waveforms=False):
         self.syn, self.rows, self.uniq = syn, rows, uniq
@@ -79,16 +79,29 @@ class Group(object):
         """both sides' K-weighted level in dB per frame, on the device"""
         return tuple(None if r is None else t2v_hip.energy_db(r.frame_ms) for r in self.loudness)
 
+    @cached_property
+    def voice(self):
+        """both sides' `t2v_hip.voice_quality`"""
+        return self._both_sides(t2v_hip.voice_quality)
+
     def tracks_on_host(self, tracks):
         """per row (its waveform's track or None, its recording's track) as host lists cut to their frames, from both sides'
-        per-frame tensors: side by side in one tensor, one copy to the host"""
+        per-frame tensors, (rows, frames) or with planes, (rows, planes, frames), which give a list per plane: side by side in
+        one tensor, one copy to the host"""
         both = [t for t in tracks if t is not None]
-        width = max(t.size(1) for t in both)
-        host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(1))) for t in both], 0).cpu().tolist()
+        width = max(t.size(-1) for t in both)
+        host = torch.cat([torch.nn.functional.pad(t, (0, width - t.size(-1))) for t in both], 0).cpu().tolist()
+        if both[0].dim() == 2:
+            def cut(row, frames):
+                return row[:frames]
+        else:
+            def cut(row, frames):
+                return [plane[:frames] for plane in row]
         out = []
         for b in range(len(self.rows)):
             k = self.wav_slot.get(b)
-            out.append((None if k is None else host[len(self.uniq) + k][:self.syn_frames[k]], host[self.which[b]][:self.n_ref[b]]))
+            out.append((None if k is None else cut(host[len(self.uniq) + k], self.syn_frames[k]),
+                        cut(host[self.which[b]], self.n_ref[b])))
         return out
 
 
@@ -132,12 +145,13 @@ def energy(g):
     return fields
 
 
-def aligned(g, f0=False, energy=False):
+def aligned(g, f0=False, energy=False, voice=False):
     """The frame-aligned scores (evaluation.ALIGNED_KEYS): the cepstra of the post-net mels and of the recordings' mels
     (`t2v_hip.mel_cepstrum`), one `t2v_hip.aligned_scores` call and one copy to the host.  Without f0 every row gets mcd_db and
     warp_dev, None on the six F0 values, and no vocoder is needed; with f0 (prosody is on) g.f0_tracks, cut to n_frames and
     n_ref_frames, feed the same call: a row without a waveform is unvoiced everywhere, keeps None on its F0 values and still
-    gets mcd_db.  energy (energy is on) adds `energy_along_path` on the path of the same call.  It draws nothing."""
+    gets mcd_db.  energy (energy is on) adds `energy_along_path` on the path of the same call, voice (voice is on)
+    `voice_along_path`.  It draws nothing."""
     cep = t2v_hip.mel_cepstrum(g.mel_postnet, g.n)
     cep_ref = g.ref(t2v_hip.mel_cepstrum(g.ref_mels, g.n_uniq))
     f0x = f0y = None
@@ -148,13 +162,14 @@ def aligned(g, f0=False, energy=False):
         if syn_track is not None:
             width = min(max(g.n), syn_track.size(1))
             f0x[g.wav_index, :width] = syn_track[:, :width]
-    scores = t2v_hip.aligned_scores(cep, g.n, cep_ref, g.n_ref, f0x, f0y, return_path=energy)
+    scores = t2v_hip.aligned_scores(cep, g.n, cep_ref, g.n_ref, f0x, f0y, return_path=energy or voice)
     host = torch.cat([scores.counts.double(), scores.sums.double()], 1).cpu().tolist()
     n_counts = len(t2v_hip.ALIGNED_COUNTS)
     fields = [E.aligned_fields(host[b][:n_counts], host[b][n_counts:], f0=f0 and b in g.wav_slot) for b in range(len(g.rows))]
-    if energy:
-        for row, more in zip(fields, energy_along_path(g, scores)):
-            row.update(more)
+    for on, along_path in ((energy, energy_along_path), (voice, voice_along_path)):
+        if on:
+            for row, more in zip(fields, along_path(g, scores)):
+                row.update(more)
     return fields
 
 
@@ -166,22 +181,58 @@ def energy_along_path(g, scores):
     if not g.with_wav:
         return fields
     ref_db, syn_db = g.levels
-    dev, sel, neg = syn_db.device, g.wav_index, float('-inf')
+    neg = float('-inf')
+
+    def sounding(level, counts):
+        counts = torch.tensor(counts, device=level.device)
+        level = level.masked_fill(torch.arange(level.size(1), device=level.device)[None, :] >= counts[:, None], neg)
+        return level > level.amax(1, keepdim=True) - E.ENERGY_FLOOR_DB
+    keep = sounding(syn_db, [g.n[b] for b in g.with_wav]), sounding(ref_db, g.n_uniq)
+    for b, pairs in _pairs_along_path(g, scores, (syn_db, ref_db), keep):
+        fields[b] = E.energy_path_fields(pairs)
+    return fields
+
+
+def _pairs_along_path(g, scores, tracks, keep):
+    """(row, [(synthesis, recording) values]) for every row with a waveform: tracks = two per-frame tensors, of the rows with
+    a waveform and of the recordings, read at the points of the warping path (scores: an AlignedScores with its path) where
+    keep, two bool tensors of the same shapes, holds on both sides.  A few index operations on the device and one copy to the
+    host."""
+    dev, sel = tracks[0].device, g.wav_index
     n_x = torch.tensor([g.n[b] for b in g.with_wav], device=dev)
     n_y = torch.tensor([g.n_ref[b] for b in g.with_wav], device=dev)
-    ex = syn_db.masked_fill(torch.arange(syn_db.size(1), device=dev)[None, :] >= n_x[:, None], neg)
-    ey = g.ref(ref_db)[sel]
-    ey = ey.masked_fill(torch.arange(ey.size(1), device=dev)[None, :] >= n_y[:, None], neg)
     path = scores.path[sel].long()
     pi = torch.minimum(path[:, :, 0].clamp(min=0), n_x[:, None] - 1)
     pj = torch.minimum(path[:, :, 1].clamp(min=0), n_y[:, None] - 1)
-    a, c = ex.gather(1, pi), ey.gather(1, pj)
-    keep = ((a > ex.amax(1, keepdim=True) - E.ENERGY_FLOOR_DB) & (c > ey.amax(1, keepdim=True) - E.ENERGY_FLOOR_DB)
+    a, c = tracks[0].gather(1, pi), g.ref(tracks[1])[sel].gather(1, pj)
+    both = (keep[0].gather(1, pi) & g.ref(keep[1])[sel].gather(1, pj)
             & (torch.arange(path.size(1), device=dev)[None, :] < scores.n_points[sel][:, None]))
-    host = torch.stack([a.double(), c.double(), keep.double()], 1).cpu().tolist()
+    host = torch.stack([a.double(), c.double(), both.double()], 1).cpu().tolist()
     for k, b in enumerate(g.with_wav):
         pa, pc, pk = host[k]
-        fields[b] = E.energy_path_fields([(u, v) for u, v, w in zip(pa, pc, pk) if w])
+        yield b, [(u, v) for u, v, w in zip(pa, pc, pk) if w]
+
+
+def voice(g):
+    """The voice quality of both sides (evaluation.VOICE_KEYS): `t2v_hip.voice_quality` on the same two waveforms as `prosody`
+    and `energy`, which it shares (the vocoder runs once per group).  One copy of the planes evaluation.VOICE_TRACKS to the
+    host; the tracks stay on the device in g.voice for `aligned`.  It draws nothing."""
+    stacked = tuple(None if side is None else torch.stack([getattr(side, k) for k in E.VOICE_TRACKS], 1) for side in g.voice)
+    named = lambda planes: None if planes is None else dict(zip(E.VOICE_TRACKS, planes))
+    return [E.voice_fields(named(syn_planes), named(ref_planes)) for syn_planes, ref_planes in g.tracks_on_host(stacked)]
+
+
+def voice_along_path(g, scores):
+    """evaluation.VOICE_ALIGNED_KEYS: the two alpha_db tracks of g.voice at the points of the warping path, compared where
+    both frames are counted (`t2v_hip.voice_counted` of the level_db tracks); None for a row without a waveform."""
+    fields = [dict.fromkeys(E.VOICE_ALIGNED_KEYS) for _ in g.rows]
+    if not g.with_wav:
+        return fields
+    ref_vq, syn_vq = g.voice
+    keep = (t2v_hip.voice_counted(syn_vq.level_db, [g.n[b] for b in g.with_wav], E.VOICE_FLOOR_DB),
+            t2v_hip.voice_counted(ref_vq.level_db, g.n_uniq, E.VOICE_FLOOR_DB))
+    for b, pairs in _pairs_along_path(g, scores, (syn_vq.alpha_db, ref_vq.alpha_db), keep):
+        fields[b] = E.voice_path_fields(pairs)
     return fields
 
 

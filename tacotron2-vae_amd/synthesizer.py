@@ -299,16 +299,16 @@ class Synthesizer(object):
         return self._mels_of(*self.load_wavs(paths))
 
     def _wav_groups(self, who, paths, batch_size):
-        """the loop of pitch, loudness, latents and latent_probe: an empty list is refused in who's name; the wavs are sorted by
-        length (`wav_lengths`) and read (`load_wavs`) in ragged batches of at most batch_size; yields (indices into paths, y,
-        sample counts) per batch"""
+        """the loop of pitch, loudness, voice_quality, latents and latent_probe: an empty list is refused in who's name; the
+        wavs are sorted by length (`wav_lengths`) and read (`load_wavs`) in ragged batches of at most batch_size; yields
+        (indices into paths, y, sample counts) per batch"""
         if not paths:
             raise ValueError("%s: no paths" % who)
         for idx in length_groups(self.wav_lengths(paths), batch_size):
             y, n = self.load_wavs([paths[i] for i in idx])
             yield idx, y, n
 
-    # the refusals that pitch, loudness and evaluate share; `who` opens the message
+    # the refusals that pitch, loudness, voice_quality and evaluate share; `who` opens the message
     def _need_griffin_lim(self, who):
         if not isinstance(self.vocoder, GriffinLimVocoder):
             raise RuntimeError("%s needs the Griffin-Lim vocoder: load(..., vocoder='griffin_lim')" % who)
@@ -357,6 +357,30 @@ class Synthesizer(object):
             for b, i in enumerate(idx):
                 out[i] = {'loudness_lufs': r.integrated[b], 'momentary_max_lufs': r.momentary_max[b],
                           'energy_db': db[b, :n[b] // t2v_hip.TRIM_HOP + 1]}
+        return out
+
+    def _need_voice_grid(self, who):
+        """the voice-quality bands are bins of the front end's frames at 16 kHz"""
+        import t2v_hip
+        self._need_frame_grid(who)
+        if self.hparams.sampling_rate != t2v_hip.F0_SAMPLE_RATE:
+            raise ValueError("%s: the voice-quality bands are laid out for %d Hz, the front end has %d Hz"
+                             % (who, t2v_hip.F0_SAMPLE_RATE, self.hparams.sampling_rate))
+
+    @torch.no_grad()
+    def voice_quality(self, paths, batch_size=64):
+        """Voice quality of the wavs (`t2v_hip.voice_quality`: spectral balance and cepstral peak prominence per frame), in
+        input order: one dict per wav with the six tracks of `t2v_hip.VOICE_FEATS` by name, 1-D device tensors of the front
+        end's samples // 256 + 1 frames, each what the kernel gives for that wav alone.  The wavs go through `load_wavs`
+        (resample= and trim_db= apply), sorted by length, in ragged batches of at most batch_size."""
+        import t2v_hip
+        paths = list(paths)
+        self._need_voice_grid('voice_quality')
+        out = [None] * len(paths)
+        for idx, y, n in self._wav_groups('voice_quality', paths, batch_size):
+            vq = t2v_hip.voice_quality(y, n)
+            for b, i in enumerate(idx):
+                out[i] = {k: getattr(vq, k)[b, :n[b] // t2v_hip.TRIM_HOP + 1] for k in t2v_hip.VOICE_FEATS}
         return out
 
     @torch.no_grad()
@@ -684,7 +708,7 @@ class Synthesizer(object):
 
     @torch.no_grad()
     def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False,
-                 energy=False):
+                 energy=False, voice=False):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and compared with its own recording.  condition='ref':
         the style comes from that recording (copy synthesis; its mel is computed once, for the style and for the comparison);
@@ -693,14 +717,14 @@ class Synthesizer(object):
         and those of every score that is on, each a function of scoring.py whose docstring says what it computes; the scores
         combine freely, and a score that is off leaves every record and summary with exactly the keys it held.
         alignment: `scoring.alignment`, evaluation.ALIGNMENT_KEYS.
-        prosody, energy: `scoring.prosody`, evaluation.PROSODY_KEYS, and `scoring.energy`, evaluation.ENERGY_KEYS.  Both need
-        the Griffin-Lim vocoder, which runs once per group for the two (`scoring.Group`) with the np.random draws of
-        `synthesize_batch(paths=...)`; either alone draws what the other would.  A row decoded to fewer than the vocoder's 4
-        frames has no waveform, and None on its synthesised side.
+        prosody, energy, voice: `scoring.prosody`, evaluation.PROSODY_KEYS, `scoring.energy`, evaluation.ENERGY_KEYS, and
+        `scoring.voice`, evaluation.VOICE_KEYS.  They need the Griffin-Lim vocoder, which runs once per group for the three
+        (`scoring.Group`) with the np.random draws of `synthesize_batch(paths=...)`; any of them alone draws what the others
+        would.  A row decoded to fewer than the vocoder's 4 frames has no waveform, and None on its synthesised side.
         aligned: `scoring.aligned`, evaluation.ALIGNED_KEYS; mcd_db and warp_dev need no vocoder, the six F0 values are None
-        without prosody, and with energy evaluation.ENERGY_ALIGNED_KEYS come with it.  With speed or pitch on the vocoder the
-        waveform's tracks lie on another time axis than the mels' warping path: aligned together with prosody or energy is
-        then a ValueError.
+        without prosody, and with energy evaluation.ENERGY_ALIGNED_KEYS, with voice evaluation.VOICE_ALIGNED_KEYS come with
+        it.  With speed or pitch on the vocoder the waveform's tracks lie on another time axis than the mels' warping path:
+        aligned together with prosody, energy or voice is then a ValueError.
         style: `scoring.style_mu` per group and `scoring.style_records` after the last, evaluation.STYLE_KEYS; None for a row
         decoded to fewer than the encoder's 2 frames.  style_k is lowered to (distinct recordings - 1) when there are too few;
         fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The result is then an
@@ -719,16 +743,20 @@ class Synthesizer(object):
             self._need_griffin_lim('evaluate(prosody=True)')
         if energy:
             self._need_griffin_lim('evaluate(energy=True)')
-        if aligned and (prosody or energy) and (self.vocoder.stretch[0] != self.vocoder.stretch[1]
-                                                or self.vocoder.shift[0] != self.vocoder.shift[1]):
-            raise ValueError("evaluate(aligned=True) with prosody or energy compares tracks frame by frame along the mels' path, "
-                             "and the vocoder's speed %g / pitch %g put its waveform on another time axis: use one or the other"
+        if voice:
+            self._need_griffin_lim('evaluate(voice=True)')
+        if aligned and (prosody or energy or voice) and (self.vocoder.stretch[0] != self.vocoder.stretch[1]
+                                                         or self.vocoder.shift[0] != self.vocoder.shift[1]):
+            raise ValueError("evaluate(aligned=True) with prosody, energy or voice compares tracks frame by frame along the mels' "
+                             "path, and the vocoder's speed %g / pitch %g put its waveform on another time axis: use one or the other"
                              % (self.vocoder.speed, self.vocoder.pitch))
         if energy:
             t2v_hip.kweight_coefficients(self.hparams.sampling_rate)        # an unsupported rate is refused before any work
             self._need_frame_grid('evaluate(energy=True)')
         if prosody:
             self._need_tracker_grid('evaluate(prosody=True)')
+        if voice:
+            self._need_voice_grid('evaluate(voice=True)')
         rows = [(r[0], r[1], r[2], int(r[3])) for r in rows]
         one_hot = {0: (1.0, 0.0, 0.0, 0.0), 1: (0.0, 1.0, 0.0, 0.0), 2: (0.0, 0.0, 0.0, 1.0), 3: (0.0, 0.0, 1.0, 0.0)}
         for row in rows:                    # ratio order (neu, sad, hap, ang), label order EMOTIONS
@@ -747,7 +775,7 @@ class Synthesizer(object):
                 synthesis = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), mels)
             else:
                 synthesis = self._synthesize_ragged(texts, False, None, [one_hot[row[3]] for row in group])
-            g = scoring.Group(self, group, synthesis, uniq, wavs, mels, waveforms=prosody or energy)
+            g = scoring.Group(self, group, synthesis, uniq, wavs, mels, waveforms=prosody or energy or voice)
             parts = [scoring.plain(g)]
             if alignment:
                 parts.append(scoring.alignment(g))
@@ -755,8 +783,10 @@ class Synthesizer(object):
                 parts.append(scoring.prosody(g))
             if energy:
                 parts.append(scoring.energy(g))
+            if voice:
+                parts.append(scoring.voice(g))
             if aligned:
-                parts.append(scoring.aligned(g, f0=prosody, energy=energy))
+                parts.append(scoring.aligned(g, f0=prosody, energy=energy, voice=voice))
             if style:
                 syn_mu += scoring.style_mu(g, rec_mu)
             records += [{k: v for fields in parts for k, v in fields[b].items()} for b in range(len(group))]

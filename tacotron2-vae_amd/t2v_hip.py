@@ -2197,6 +2197,62 @@ def scale_rows(y, lengths, gains):
     return y
 
 
+VOICE_FEATS = ('level_db', 'alpha_db', 'hammarberg_db', 'slope_db_khz', 'cpp_db', 'cpp_lag')      # the planes of t2v_voice_quality, in order
+VOICE_FRAMES = _ABI.define('T2V_VOICE_FRAMES')      # frames per workgroup of k_voice_quality
+VOICE_SILENT_DB = _ABI.define('T2V_VOICE_SILENT_DB')      # level_db of a frame without energy
+VOICE_FLOOR_DB = 40.0                   # a frame is counted within this many dB of the row's loudest frame (the trim's rule)
+assert len(VOICE_FEATS) == _ABI.define('T2V_VOICE_FEATS')
+
+
+class VoiceQuality(collections.namedtuple('VoiceQuality', VOICE_FEATS)):
+    """What voice_quality() gives: six (B, max frame count) float32 tracks on the device, +0 past a row's frame count.
+    level_db: the 50 Hz - 5 kHz band level, VOICE_SILENT_DB for a frame without energy (`voice_counted` gates on it);
+    alpha_db: 1 - 5 kHz over 50 Hz - 1 kHz; hammarberg_db: the peak below 2 kHz over the peak in 2 - 5 kHz; slope_db_khz: the
+    spectral slope over 500 - 1500 Hz; cpp_db: the cepstral peak prominence over the 60 - 500 Hz quefrencies; cpp_lag: the
+    peak's quefrency in samples.  include/t2vae.h has the definitions."""
+    __slots__ = ()
+
+
+def voice_quality(y, lengths):
+    """Spectral balance and cepstral peak prominence per frame (csrc/voice.hip k_voice_quality): y (B, S) float32 CUDA tensor of
+    16 kHz waveforms, row b of lengths[b] samples (a list, a CPU tensor or a device int tensor); samples outside a row's length
+    count as 0 and are not read.  Frames as the mel front end's (hop 256, window 1024 centred on 256 t, lengths[b] // 256 + 1
+    of them: the grid of f0(), loudness() and trim_bounds()).  Returns a `VoiceQuality`.  A row gives the same bits alone, in
+    any batch and at any stride."""
+    lib = _require_gpu(y)
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("voice_quality: y must be a float32 (B, S) tensor, got %s %s" % (y.dtype, tuple(y.shape)))
+    B, S = y.shape
+    if B < 1 or S < 1:
+        raise ValueError("voice_quality: empty input %s" % (tuple(y.shape),))
+    if S > (1 << 30):
+        raise ValueError("voice_quality: rows of %d samples exceed the 2^30 supported" % S)
+    n = _wave_lengths(lengths, B, S, "voice_quality")
+    y = _f32c(y)
+    stride = S // TRIM_HOP + 1
+    out = torch.empty(B, len(VOICE_FEATS), stride, device=y.device, dtype=torch.float32)
+    _check(lib.t2v_voice_quality(_p(y), _p(n.to(y.device)), S, B, _p(out), stride, _stream()), 't2v_voice_quality')
+    T = int(n.max()) // TRIM_HOP + 1
+    return VoiceQuality(*(out[:, k, :T].contiguous() for k in range(len(VOICE_FEATS))))
+
+
+def voice_counted(level_db, n_frames=None, floor_db=VOICE_FLOOR_DB):
+    """The frames of a level_db track that the voice-quality statistics count: not silent, and within floor_db of the row's
+    loudest frame.  level_db: a (frames,) or (B, frames) tensor; n_frames: the rows' frame counts where the tensor is wider
+    than a row (a list or a tensor), frames at and past them are not counted and do not set the maximum.  Returns a bool
+    tensor of level_db's shape; a row without a counted frame (all silent) has none."""
+    level = torch.as_tensor(level_db)
+    rows = level if level.dim() == 2 else level[None]
+    valid = rows > VOICE_SILENT_DB
+    if n_frames is not None:
+        count = torch.as_tensor(n_frames, device=rows.device).reshape(-1, 1)
+        valid = valid & (torch.arange(rows.size(1), device=rows.device)[None, :] < count)
+    if rows.size(1) == 0:
+        return valid.reshape(level.shape)
+    top = rows.masked_fill(~valid, float('-inf')).amax(1, keepdim=True)
+    return (valid & (rows > top - floor_db)).reshape(level.shape)
+
+
 ALIGN_FRAMES = _ABI.define('T2V_ALIGN_FRAMES')      # frames per workgroup of k_align_scan
 ALIGN_STATS = ('furthest', 'p_last', 'n_back', 'n_jump', 'longest_stall', 'n_uncovered', 'longest_gap')
 
