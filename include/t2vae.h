@@ -461,6 +461,13 @@ int t2v_bn_act_bwd_eval(const float* y, const float* dout, const float* mean, co
                    const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta,
                    float* dconv_bias, int B, int M, int T, int act, float p_drop, uint64_t seed,
                    uint32_t rng_stream, uint32_t rng_t, void* stream);
+/* gridDim.y that t2v_bn_act_fwd (backward = 0) / t2v_bn_act_bwd[_eval] (backward != 0) plans for these dimensions: 1 = one
+ * workgroup per channel, > 1 = every channel cut into that many slices of B*T (few wide channels: M <= 128 and B*T >= 16384
+ * forward, >= 8192 backward; at most 64 slices and about 1024 / M).  The forward cuts only in training and without partials
+ * (training, has_partials: what the call passes; the backward ignores both, it cuts in eval mode too).  It answers the PLAN, from
+ * the code the launches read: a sliced launch takes its partials from a ring of the library, and if the ring has no room the
+ * launch runs unsliced all the same.  T2V_ERR_ARG for a dimension below 1. */
+int t2v_bn_act_slices(int backward, int B, int M, int T, int training, int has_partials);
 
 /* ------------------------------------------------------------------ symbol embedding
  * nn.Embedding(n_symbols, C) of the text encoder (model.py:474-482) as used at model.py:528

@@ -416,23 +416,45 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(BnBwdArgs a, const float* 
     }
 }
 static float* bn_part_scratch(size_t floats);
+
+// How a launch cuts its channels: the ONE place that decides it.  Few wide channels (M <= 128; forward: training without a
+// convolution's partials and B*T >= 16384, backward: B*T >= 8192) are cut over gridDim.y (T2V_BN_SPLIT=0: never); t2v_bn_act_fwd,
+// bn_bwd_launch and t2v_bn_act_slices() read this plan, the launches only carry it out.
+struct BnPlan {
+    int S;       // slices asked for (sizes the partials' scratch); < 2: one workgroup per channel
+    int Sy;      // gridDim.y: the slices that hold an element (the chunk is rounded up to 256, so Sy <= S)
+    int chunk;   // elements of a channel per slice
+};
+static BnPlan bn_plan(int backward, int B, int M, int T, int training, int has_partials) {
+    static const int split_on = getenv("T2V_BN_SPLIT") ? atoi(getenv("T2V_BN_SPLIT")) : 1;
+    BnPlan p = {1, 1, 0};
+    const long nel = (long)B * T;
+    const long per = backward ? 2048 : 4096;            // >= this many values per workgroup ...
+    if (!split_on || M > 128 || nel < 4 * per) return p;
+    if (!backward && (!training || has_partials)) return p;
+    long S = (nel + per - 1) / per;
+    if (S * M > 1024) S = 1024 / M;                     // ... and at most ~4 workgroups per CU
+    if (S > 64) S = 64;
+    if (S < 2) return p;
+    p.S = (int)S;
+    p.chunk = (int)(((nel + S - 1) / S + 255) / 256 * 256);
+    p.Sy = (int)((nel + p.chunk - 1) / p.chunk);
+    return p;
+}
+extern "C" int t2v_bn_act_slices(int backward, int B, int M, int T, int training, int has_partials) {
+    if (B < 1 || M < 1 || T < 1) return T2V_ERR_ARG;
+    return bn_plan(backward, B, M, T, training, has_partials).Sy;
+}
+
 // launches the backward of `a`: sliced for few wide channels, else one workgroup per channel
 static void bn_bwd_launch(BnBwdArgs& a, hipStream_t stream) {
-    static const int split_on = getenv("T2V_BN_SPLIT") ? atoi(getenv("T2V_BN_SPLIT")) : 1;
-    const long nel = (long)a.B * a.T;
-    if (split_on && a.M <= 128 && nel >= 8192) {
-        long S = (nel + 2047) / 2048;                   // >= 2048 values per workgroup ...
-        if (S * a.M > 1024) S = 1024 / a.M;             // ... and at most ~4 workgroups per CU
-        if (S > 64) S = 64;
-        if (S >= 2) {
-            float* part = bn_part_scratch((size_t)S * a.M * 2);
-            if (part) {
-                const int chunk = (int)(((nel + S - 1) / S + 255) / 256 * 256);
-                const int Sy = (int)((nel + chunk - 1) / chunk);
-                k_bn_bwd_part<<<dim3(a.M, Sy), 256, 0, stream>>>(a, part, chunk);
-                k_bn_bwd_apply<<<dim3(a.M, Sy), 256, 0, stream>>>(a, part, chunk);
-                return;
-            }
+    const BnPlan p = bn_plan(1, a.B, a.M, a.T, !a.eval_mode, 0);
+    if (p.S >= 2) {
+        float* part = bn_part_scratch((size_t)p.S * a.M * 2);
+        if (part) {
+            k_bn_bwd_part<<<dim3(a.M, p.Sy), 256, 0, stream>>>(a, part, p.chunk);
+            k_bn_bwd_apply<<<dim3(a.M, p.Sy), 256, 0, stream>>>(a, part, p.chunk);
+            return;
         }
     }
     k_bn_act_bwd<<<a.M, 256, 0, stream>>>(a);
@@ -461,25 +483,17 @@ extern "C" int t2v_bn_act_fwd(const float* y, const float* stat_part, int nblk, 
     a.momentum = momentum; a.eps = eps; a.seed = seed; a.rng_stream = rng_stream; a.rng_t = rng_t; a.step = t2v_step_for(stream);
     a.chunk = 0;
     // few wide channels without partials from a convolution's epilogue (BatchNorm2d of the reference encoder): cut every channel
-    // over gridDim.y (T2V_BN_SPLIT=0: one workgroup per channel as before)
-    static const int split_on = getenv("T2V_BN_SPLIT") ? atoi(getenv("T2V_BN_SPLIT")) : 1;
-    const long nel = (long)B * T;
-    if (split_on && training && !stat_part && M <= 128 && nel >= 16384) {
-        long S = (nel + 4095) / 4096;                   // >= 4096 values per workgroup ...
-        if (S * M > 1024) S = 1024 / M;                 // ... and at most ~4 workgroups per CU
-        if (S > 64) S = 64;
-        if (S >= 2) {
-            float* part = bn_part_scratch((size_t)S * M * 2);
-            if (part) {
-                a.chunk = (int)(((nel + S - 1) / S + 255) / 256 * 256);
-                const int Sy = (int)((nel + a.chunk - 1) / a.chunk);
-                k_bn_stat_part<<<dim3(M, Sy), 256, 0, stream>>>(y, part, B, M, T, a.chunk);
-                a.stat_part = part;
-                a.nblk = Sy;
-                k_bn_act_fwd<<<dim3(M, Sy), 256, 0, stream>>>(a);
-                return t2v_check_launch();
-            }
-            a.chunk = 0;
+    // over gridDim.y (bn_plan; T2V_BN_SPLIT=0: one workgroup per channel as before)
+    const BnPlan p = bn_plan(0, B, M, T, training, stat_part != nullptr);
+    if (p.S >= 2) {
+        float* part = bn_part_scratch((size_t)p.S * M * 2);
+        if (part) {
+            a.chunk = p.chunk;
+            k_bn_stat_part<<<dim3(M, p.Sy), 256, 0, stream>>>(y, part, B, M, T, a.chunk);
+            a.stat_part = part;
+            a.nblk = p.Sy;
+            k_bn_act_fwd<<<dim3(M, p.Sy), 256, 0, stream>>>(a);
+            return t2v_check_launch();
         }
     }
     k_bn_act_fwd<<<M, 256, 0, stream>>>(a);

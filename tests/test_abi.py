@@ -44,6 +44,7 @@ def _expected():
         't2v_decoder_qp_floats': (l, [i, i]),
         't2v_conv1d_staged_launches': (C.c_longlong, []),
         't2v_conv1d_takes_x3': (i, [i] * 6),
+        't2v_bn_act_slices': (i, [i] * 6),
         't2v_istft_scratch_bytes': (C.c_size_t, [i, i]),
         't2v_gemm_epilogue_bwd': (i, [vp, vp, vp, C.c_size_t, f, vp]),
         't2v_gemm_f32': (i, [vp, l, l, vp, l, l, vp, vp, i, i, i, i, i, i, f, u64, u32, u32, vp]),
@@ -197,8 +198,8 @@ def test_every_declared_entry_point_is_a_parsed_prototype_in_header_order():
     text = re.sub(r'//[^\n]*', '', text)
     seen = re.findall(r'\b(t2v_\w+)\s*\(', text)
     protos = t2v_abi.load().prototypes
-    assert seen == list(protos) and len(seen) == len(set(seen)) >= 143
-    assert t2v_hip.EXPORTS == tuple(seen) and 't2v_conv1d_takes_x3' in t2v_hip.EXPORTS
+    assert seen == list(protos) and len(seen) == len(set(seen)) >= 144
+    assert t2v_hip.EXPORTS == tuple(seen) and 't2v_conv1d_takes_x3' in t2v_hip.EXPORTS and 't2v_bn_act_slices' in t2v_hip.EXPORTS
     assert 't2v_gemm_route' in t2v_hip.EXPORTS and 't2v_gemm_route_name' in t2v_hip.EXPORTS
     lib = t2v_hip.load_library()
     for name, (restype, argtypes) in protos.items():
