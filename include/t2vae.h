@@ -1062,6 +1062,24 @@ size_t t2v_phase_vocoder_scratch_bytes(int B, int out_stride, int phase_lock);
 int t2v_phase_vocoder(const float* mag, const float* phase, const int32_t* n_frames, int B, int T, int t_stride, int num, int den,
                       int phase_lock, float* mag_out, float* phase_out, int out_stride, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------ a phase from magnitudes alone
+ * Single-pass spectrogram inversion (Beauregard, Harish and Wyse 2015) of a ragged batch (csrc/phase_init.hip): the start that
+ * Griffin-Lim otherwise draws at random.  mag and phase_out are (B, 513, t_stride) fp32 as t2v_stft_polar writes them (n_fft
+ * 1024, hop 256: a quarter turn per bin and frame), row b has n_frames[b] frames (device int32, clamped to 0..T; T <= t_stride
+ * is the most any row has); nothing at or past frame n_frames[b] is read, and phase_out is +0 from there to t_stride.
+ * Turns are 32-bit fixed-point fractions of a turn, uint32, wrapping.  In frame m:
+ *   a peak is a bin k in 1..511 with mag[k] > mag[k - 1] and mag[k] > mag[k + 1] in fp32 (a plateau has none);
+ *   p = (0.5 (a - c)) / ((a - 2 b) + c) in fp64, uncontracted, from a, b, c = mag[k - 1], mag[k], mag[k + 1];
+ *   adv(k, m) = ((k & 3) << 30) + rint(p 2^30) at a peak and 0 elsewhere;  acc(k, m) = sum of adv(k, m') over m' <= m;
+ *   bin k takes its nearest peak kp (a tie: the lower one): turns = acc(kp, m) - ((k - kp) << 31) + rint(p(kp, m) 2^31),
+ *   phase_out = (float)((double)(int32_t)turns 2 pi / 2^32), in [-pi, pi);  a frame without a peak is +0 in every bin.
+ * The sums are integer sums: a row gives the same bits alone, in any batch and at any stride.
+ * scratch: t2v_spsi_scratch_bytes(B, t_stride) bytes of device memory (the accumulators); the library allocates nothing.
+ * B < 1, T outside 1..T2V_TSM_MAX_FRAMES, t_stride < T or above 2^30, or more than 2^31 - 1 workgroups is T2V_ERR_DIMS; a null
+ * pointer is T2V_ERR_ARG. */
+size_t t2v_spsi_scratch_bytes(int B, int t_stride);
+int t2v_spsi(const float* mag, const int32_t* n_frames, int B, int T, int t_stride, float* phase_out, void* scratch, void* stream);
+
 /* ------------------------------------------------------------------ spectral envelope: pitch and timbre as two knobs
  * The true-envelope estimate of a ragged batch of STFT magnitudes, and the spectrum with its envelope moved along frequency
  * (csrc/envelope.hip, one launch).  mag is (B, 513, t_stride) fp32 as t2v_stft_polar writes it, row b has n_frames[b] frames

@@ -113,8 +113,9 @@ def build_arg_parser():
     p.add_argument('--prosody', action='store_true',
                    help="also track the pitch (YIN, 60-500 Hz) of each synthesised waveform (Griffin-Lim) and of its recording: "
                         "rows gain median F0, spread in semitones, voiced share and f0_shift_st; the summary their means")
-    p.add_argument('--vocoder', choices=['griffin_lim', 'griffin_lim_fast'], default='griffin_lim',
-                   help="the vocoder of --prosody, --energy and --voice (griffin_lim_fast: momentum 0.99 and NNLS mel inversion); unused "
+    p.add_argument('--vocoder', choices=['griffin_lim', 'griffin_lim_fast', 'spsi'], default='griffin_lim',
+                   help="the vocoder of --prosody, --energy and --voice (griffin_lim_fast: momentum 0.99 and NNLS mel inversion; spsi: NNLS "
+                        "and the phase from the magnitudes' peaks, no iterations, which keeps low voices voiced); unused "
                         "without them")
     p.add_argument('--alignment', action='store_true',
                    help="also score the attention alignment of each synthesis (did the decoder read the text?): rows gain focus, "

@@ -64,7 +64,7 @@ def resample_rows(items, target_rate):
     return y, n
 
 
-VOCODERS = ('griffin_lim', 'griffin_lim_fast')
+VOCODERS = ('griffin_lim', 'griffin_lim_fast', 'spsi')
 
 
 class GriffinLimVocoder(object):
@@ -81,11 +81,17 @@ class GriffinLimVocoder(object):
     formant (semitones, -12..12) moves the spectral envelope of the output up by 2^(formant / 12) and leaves the harmonics;
     preserve_formants keeps the envelope where it was under `pitch`, which alone moves it with the harmonics.  Both are one
     `t2v_hip.warp_envelope` of the linear magnitudes, before the stretch, by the ratio of `t2v_hip.vocoder_warp` (DESIGN 7p);
-    formant=0, preserve_formants=False is the vocoder without them."""
+    formant=0, preserve_formants=False is the vocoder without them.
+    init='spsi': the initial phase is not drawn but computed on the device from the magnitudes Griffin-Lim sees, after the
+    warp and the stretch (`t2v_hip.spsi_phase`, single-pass spectrogram inversion); np.random is not touched and no phase
+    crosses from the host.  n_iters=0 then writes that start as it is, one inverse transform: `named('spsi')`, which keeps
+    low voices voiced where the iterations lose them."""
 
     def __init__(self, stft, n_iters=60, momentum=0.0, inversion='pinv', inversion_iters=100, speed=1.0, pitch=0.0, formant=0.0,
-                 preserve_formants=False):
+                 preserve_formants=False, init='random'):
+        from audio_processing import check_init
         from t2v_hip import check_momentum, vocoder_rates, vocoder_warp
+        self.init = check_init(init)
         if inversion not in ('pinv', 'nnls'):
             raise ValueError("GriffinLimVocoder: inversion must be 'pinv' or 'nnls', got %r" % (inversion,))
         self.stft, self.n_iters = stft, n_iters
@@ -103,6 +109,8 @@ class GriffinLimVocoder(object):
             return cls(stft, **knobs)
         if name == 'griffin_lim_fast':
             return cls(stft, momentum=0.99, inversion='nnls', **knobs)
+        if name == 'spsi':
+            return cls(stft, n_iters=0, momentum=0.0, inversion='nnls', init='spsi', **knobs)
         raise ValueError("unknown vocoder %r (a callable, or one of %s)" % (name, ', '.join(repr(v) for v in VOCODERS)))
 
     def _magnitudes(self, mel, lengths):
@@ -136,25 +144,29 @@ class GriffinLimVocoder(object):
         from audio_processing import griffin_lim
         magnitudes = self._magnitudes(mel, lengths)
         if self.stretch[0] == self.stretch[1] and self.shift[0] == self.shift[1] and self.warp[0] == self.warp[1]:
-            return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths, momentum=self.momentum)
+            return griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=lengths, momentum=self.momentum, init=self.init)
         n = [magnitudes.size(2)] * magnitudes.size(0) if lengths is None else [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
         stretched, n = self._stretched(magnitudes, n)
-        wav = griffin_lim(stretched, self.stft.stft_fn, self.n_iters, lengths=n, momentum=self.momentum)
+        wav = griffin_lim(stretched, self.stft.stft_fn, self.n_iters, lengths=n, momentum=self.momentum, init=self.init)
         return self._shifted(wav, n)[0].to(mel.device)
 
     def batch(self, mel, lengths):
         """A ragged batch in one set of launches, item by item as `self(mel[b:b+1, :, :lengths[b]])` would give it: the
         initial phases are drawn from np.random per item, in item order, with shape (1, 513, lengths[b]) — what B calls in
-        a row draw.  Returns a list of B waveforms ((lengths[b]-1)*256 samples each) on the device."""
+        a row draw.  With init='spsi' nothing is drawn and no phase array is built on the host: the start is a function of each
+        row's magnitudes alone.  Returns a list of B waveforms ((lengths[b]-1)*256 samples each) on the device."""
         from audio_processing import griffin_lim
         n = [int(x) for x in torch.as_tensor(lengths).reshape(-1).tolist()]
         B = mel.size(0)
         magnitudes, n = self._stretched(self._magnitudes(mel, n), n)
-        angles = np.zeros((B, 513, magnitudes.size(2)), dtype=np.float32)
-        for b, nb in enumerate(n):
-            angles[b, :, :nb] = np.angle(np.exp(2j * np.pi * np.random.rand(1, 513, nb)))[0]
-        wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, angles=torch.from_numpy(angles), lengths=n,
-                          momentum=self.momentum)
+        if self.init == 'spsi':
+            wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, lengths=n, momentum=self.momentum, init='spsi')
+        else:
+            angles = np.zeros((B, 513, magnitudes.size(2)), dtype=np.float32)
+            for b, nb in enumerate(n):
+                angles[b, :, :nb] = np.angle(np.exp(2j * np.pi * np.random.rand(1, 513, nb)))[0]
+            wav = griffin_lim(magnitudes, self.stft.stft_fn, self.n_iters, angles=torch.from_numpy(angles), lengths=n,
+                              momentum=self.momentum)
         wav, counts = self._shifted(wav, n)
         return [wav[b, :k] for b, k in enumerate(counts)]
 
@@ -520,7 +532,8 @@ class Synthesizer(object):
         app.py:161).  waveglow_path: a WaveGlow checkpoint `{'model': module}` exactly as the reference loads it
         (needs the `waveglow` package importable: it is an un-vendored submodule of the reference); `vocoder`: any
         callable mel (1,80,T) -> audio instead, or 'griffin_lim' for GriffinLimVocoder(self.stft), or 'griffin_lim_fast' for
-        the same with momentum 0.99 and the non-negative least-squares mel inversion.  A callable passed in the second
+        the same with momentum 0.99 and the non-negative least-squares mel inversion, or 'spsi' for that inversion, a phase made
+        from the magnitudes' peaks and no iteration (GriffinLimVocoder.named).  A callable passed in the second
         position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
         (`latents`), when there is no centroid cache yet."""
         if isinstance(vocoder, str):
@@ -808,7 +821,8 @@ def build_arg_parser():
     p.add_argument('--text_file', default=None, help="one sentence per line (after the --text sentences)")
     p.add_argument('--batch_size', type=int, default=DEFAULT_BATCH_SIZE, help="texts per synthesize_batch call")
     p.add_argument('--vocoder', choices=list(VOCODERS), default=None,
-                   help="without it the post-net mels are written; griffin_lim_fast: momentum 0.99 and NNLS mel inversion")
+                   help="without it the post-net mels are written; griffin_lim_fast: momentum 0.99 and NNLS mel inversion; "
+                        "spsi: NNLS and the phase from the magnitudes' peaks, no iterations (low voices stay voiced)")
     p.add_argument('--ratios', default='1,0,0,0', help="emotion mix neu,sad,hap,ang")
     p.add_argument('--ref_audio', default=None, help="condition every text on this reference wav instead of --ratios")
     p.add_argument('--filelist_path', default='./web/static/uploads/koemo_spk_emo_all_test.txt',

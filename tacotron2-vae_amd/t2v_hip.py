@@ -1335,6 +1335,27 @@ def griffin_lim(mag, angles, n_frames, tables, n_iters, momentum=0.0):
     return out
 
 
+def spsi_phase(mag, n_frames=None):
+    """A phase for magnitudes alone, on device (csrc/phase_init.hip k_spsi_scan, k_spsi_assign): single-pass spectrogram
+    inversion, the start `griffin_lim(init='spsi')` takes instead of a random draw.  mag: (B, 513, T) float32 CUDA tensor as
+    `stft_polar` gives it; n_frames: (B) frame counts or None (all T), at least 1 per row; frames at and past a count are not
+    read.  Returns the phase (B, 513, T) in [-pi, pi), +0 past each count and in frames without a spectral peak.  Every bin
+    follows its frame's nearest peak, whose phase advances by (k + p) / 4 turns per frame, summed in 32-bit fixed point
+    (include/t2vae.h): a row gives the same bits alone, in any batch and at any stride."""
+    lib = _require_gpu(mag)
+    if mag.dim() != 3 or mag.size(1) != 513 or mag.size(0) < 1 or mag.size(2) < 1:
+        raise ValueError("spsi_phase: magnitudes must be (B, 513, T), got %s" % (tuple(mag.shape),))
+    B, _, T = mag.shape
+    if T > TSM_MAX_FRAMES:
+        raise ValueError("spsi_phase: rows of %d frames exceed the %d supported" % (T, TSM_MAX_FRAMES))
+    mag = _f32c(mag)
+    n = _frame_counts(n_frames, B, T, mag.device)
+    phase = torch.empty_like(mag)
+    scratch = torch.empty(lib.t2v_spsi_scratch_bytes(B, T), device=mag.device, dtype=torch.uint8)
+    _check(lib.t2v_spsi(_p(mag), _p(n), B, T, T, _p(phase), _p(scratch), _stream()), 't2v_spsi')
+    return phase
+
+
 def check_momentum(momentum):
     """fast Griffin-Lim's momentum as a float in [0, 1); ValueError otherwise"""
     m = float(momentum)
