@@ -710,6 +710,21 @@ int t2v_clip_adam_step_guarded(float* params, float* grads, float* exp_avg, floa
                                float lr, float beta1, float beta2, float eps, float weight_decay,
                                float max_norm, float inv_world, float bc1, float bc2, float* partials,
                                float* norm_out, const uint32_t* guard, int guard_n, void* stream);
+/* The guarded step with a weight average folded in: `ema` (n floats, 16-byte aligned like the other arenas) holds an
+ * exponential moving average of the parameters and is updated in the same launch, right behind each parameter:
+ *     ema = fmaf(rate_t, p_new - ema, ema)        p_new: the fp32 value this step stores to params
+ *     rate_t = ema_warmup ? max(ema_rate, 9 / (10 + t)) : ema_rate       (TensorFlow's min(decay, (1 + t) / (10 + t)) as a rate)
+ * ema_rate = 1 - decay, formed by the caller in double and rounded once (the fp32 neighbour of 1e-4 for decay 0.9999, not
+ * 1 - (float)0.9999, which is 1.7e-4 relative off); it must lie in (0, 1].  t counts the updates made so far: `epoch` of the
+ * device step record when one is bound to `stream` (so that a replayed graph sees the rate of ITS step, like lr and bc1),
+ * else the by-value ema_t.  A skipped step (non-zero guard word) leaves `ema` untouched like the other arenas; a NULL or
+ * misaligned `ema` or an ema_rate outside (0, 1] is T2V_ERR_ARG before anything is launched.  36 instead of 28 bytes of
+ * traffic per element; params, both moments and norm_out get the very bits of t2v_clip_adam_step_guarded. */
+int t2v_clip_adam_ema_step_guarded(float* params, float* grads, float* exp_avg, float* exp_avg_sq, uint64_t n,
+                                   float lr, float beta1, float beta2, float eps, float weight_decay,
+                                   float max_norm, float inv_world, float bc1, float bc2, float* partials,
+                                   float* norm_out, const uint32_t* guard, int guard_n, float* ema, float ema_rate,
+                                   int ema_warmup, uint64_t ema_t, void* stream);
 
 /* ------------------------------------------------------------------ STFT -> mel front end
  * TacotronSTFT.mel_spectrogram (layers.py:75-92): reflect pad n_fft/2, periodic-Hann STFT

@@ -3,7 +3,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--attention_window BACK,AHEAD] [--speed R]
+                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--attention_window BACK,AHEAD] [--weights raw|ema] [--speed R]
                        [--pitch ST] [--formant ST] [--preserve_formants]
                        [--hparams ...]
 
@@ -84,6 +84,10 @@ neutral's, synthesised and recorded; no thresholds.
 attends within BACK positions behind and AHEAD in front of the position the previous frame attended most).
 OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart.
 
+--weights ema scores the averaged weights of the checkpoint ('ema_state_dict', written by a training run with
+hparams.ema_decay > 0) instead of the last iteration's; with --condition emotion the centroid cache is a file of its own.
+OUT.json always holds "weights": "raw" or "ema".
+
 --speed R and --pitch ST set the tempo and the pitch shift (semitones) of the vocoder leg (`GriffinLimVocoder(speed=, pitch=)`,
 DESIGN 7o): the waveforms that --prosody, --energy and --voice measure are the ones the synthesis command line would write
 with the same flags, and their tracks run over those waveforms' own frames (ceil(n_frames / speed) of them, not n_frames).
@@ -144,8 +148,9 @@ def build_arg_parser():
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
-    from synthesizer import add_tempo_arguments
+    from synthesizer import add_tempo_arguments, add_weights_argument
     add_tempo_arguments(p)
+    add_weights_argument(p)
     return p
 
 
@@ -189,14 +194,15 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    from synthesizer import tempo_options
+    from synthesizer import tempo_options, weights_option
     from wavio import wav_options
     waveforms = args.prosody or args.energy or args.voice                 # the scores that need the vocoder
     syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args))
     if args.condition == 'emotion':
-        syn.load(args.load_path, vocoder=args.vocoder if waveforms else None, filelist_path=args.filelist_path)
+        syn.load(args.load_path, vocoder=args.vocoder if waveforms else None, filelist_path=args.filelist_path,
+                 **weights_option(args))
     else:
-        syn.load_checkpoint(args.load_path)
+        syn.load_checkpoint(args.load_path, **weights_option(args))
         if waveforms:
             syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft, syn.speed, syn.pitch_st, syn.formant, syn.preserve_formants)
     rows = read_rows(args.filelist_path, args.limit)
@@ -210,7 +216,7 @@ def main(argv=None):
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)],
                    'attention_window': None if syn.attention_window is None else list(syn.attention_window),
-                   'speed': syn.speed, 'pitch': syn.pitch_st, **formant_keys}, f, indent=1)
+                   'weights': args.weights or 'raw', 'speed': syn.speed, 'pitch': syn.pitch_st, **formant_keys}, f, indent=1)
     print(json.dumps(summary, indent=1))
     if args.alignment:
         for name, st in summary['by_emotion'].items():

@@ -3,6 +3,7 @@
 latent_map.py's (or --tsne here).
 
     python extract_latents.py --load_path CKPT --filelist_path F --out OUT.npz [--batch_size N] [--hparams ...] [--tsne [KEY]]
+                              [--weights raw|ema]
                               [--scores [KEY]] [--probe OUT.json [--probe_formant ST,...] [--probe_preserve_formants]]
 
 Filelist rows are `path|text|speaker|emotion`.  OUT.npz holds, row i for filelist row i: prosody (N, E), mus, logvars,
@@ -16,6 +17,7 @@ a clip's pitch, tempo or level alone is changed, against the distance between th
 changed by it.  --probe_formant ST,... adds entries of kind 'formant', the spectral envelope alone moved by those semitones,
 and --probe_preserve_formants makes the pitch entries move F0 alone: the plain pitch shift moves the formants
 too, so only with it does the table tell pitch from timbre.  Both need --probe.
+--weights ema encodes with the averaged weights of the checkpoint ('ema_state_dict', hparams.ema_decay > 0 in training).
 """
 import argparse
 
@@ -43,6 +45,8 @@ def build_arg_parser():
                    help="with --probe: the pitch entries keep the formants in place (F0 alone)")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
+    from synthesizer import add_weights_argument
+    add_weights_argument(p)
     return p
 
 
@@ -81,14 +85,14 @@ def read_filelist(path):
 def main(argv=None):
     args = parse_args(argv)
     from hparams import create_hparams
-    from synthesizer import Synthesizer
+    from synthesizer import Synthesizer, weights_option
     hp = create_hparams()
     hp.sampling_rate = 16000                 # the reference's Synthesizer() overrides, as synthesizer.py's command line
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
     from wavio import wav_options
-    syn = Synthesizer(hp, **wav_options(args)).load_checkpoint(args.load_path)
+    syn = Synthesizer(hp, **wav_options(args)).load_checkpoint(args.load_path, **weights_option(args))
     paths, emotions = read_filelist(args.filelist_path)
     prosody, mu, logvar, z = (t.cpu().numpy() for t in syn.latents(paths, args.batch_size))
     out = dict(prosody=prosody, mus=mu, logvars=logvar, zs=z, emotions=emotions, paths=np.array(paths))

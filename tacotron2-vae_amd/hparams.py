@@ -57,6 +57,16 @@ _GROUPS = {
 #                     rounded to bf16 and summed over the ranks in bf16: relative error ~ sqrt(world) * 2^-9 per element)
 _EXTENSIONS = dict(device_frontend=False, bucket_batches=False, bf16_run=False, graph_step=True, fp32_allreduce=True)
 
+# The training recipe's own switches: what the loop does with the weights, not how the build runs a step.  A third group,
+# reported by `recipe()` alone (`values()` stays the reference's set, `extensions()` the build's):
+#   ema_decay  : 0 (default) = off.  Otherwise an exponential moving average of the weights is kept beside Adam, in the
+#                same fused launch (optim.FlatAdam), saved in the checkpoint as 'ema_state_dict' and validated next to the
+#                raw weights; `--weights ema` of synthesizer.py / evaluate.py / extract_latents.py reads it.  0.9999 is the
+#                usual choice for Tacotron-like models
+#   ema_warmup : the decay of update t is min(ema_decay, (1 + t) / (10 + t)), so that the average does not sit on the
+#                initial weights for the first 1 / (1 - ema_decay) iterations
+_RECIPE = dict(ema_decay=0.0, ema_warmup=True)
+
 
 def _coerce(old, text):
     if isinstance(old, bool):
@@ -92,10 +102,13 @@ class HParams(object):
 
     def values(self):
         """the reference's hyper-parameters (build-specific switches excluded)"""
-        return {k: v for k, v in self._store.items() if k not in _EXTENSIONS}
+        return {k: v for k, v in self._store.items() if k not in _EXTENSIONS and k not in _RECIPE}
 
     def extensions(self):
         return {k: v for k, v in self._store.items() if k in _EXTENSIONS}
+
+    def recipe(self):
+        return {k: v for k, v in self._store.items() if k in _RECIPE}
 
     def parse(self, spec):
         for item in filter(None, (s.strip() for s in spec.split(','))):
@@ -115,6 +128,7 @@ def create_hparams(hparams_string=None, verbose=False):
         for k, v in grp.items():
             flat[k] = list(v) if isinstance(v, list) else v
     flat.update(_EXTENSIONS)
+    flat.update(_RECIPE)
     hp = HParams(**flat)
     if hparams_string:
         hp.parse(hparams_string)

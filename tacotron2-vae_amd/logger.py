@@ -322,6 +322,11 @@ class Tacotron2Logger(EventFileWriter):
         self.add_scalar("recon_loss", recon_loss, iteration)
         self.flush()
 
+    def log_validation_ema(self, reduced_loss, iteration):
+        """the validation loss of the averaged weights (hparams.ema_decay > 0), next to log_validation's"""
+        self.add_scalar("validation.loss.ema", reduced_loss, iteration)
+        self.flush()
+
     def log_validation(self, reduced_loss, model, y, y_pred, iteration):
         self.add_scalar("validation.loss", reduced_loss, iteration)
         _, mel_outputs, gate_outputs, alignments, mus, _, _, emotions = y_pred

@@ -6,6 +6,7 @@ arena and clip-by-global-norm + Adam is two HIP launches (csrc/optim.hip) instea
 small kernels.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format so the
 checkpoint dict of reference train.py:113-119 stays interchangeable.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -27,10 +28,18 @@ class FlatAdam(object):
     """clip_grad_norm_ + Adam over a flat arena.  Mirrors the bits of torch.optim.Adam the
     reference loop touches: `.param_groups[i]['lr']`, `.step()`, `.state_dict()`,
     `.load_state_dict()`; plus `.zero_grad()` (the loop's `model.zero_grad()` also works) and
-    `.grad_norm` (device scalar written by the last step)."""
+    `.grad_norm` (device scalar written by the last step).
+
+    ema_decay > 0 keeps an exponential moving average of the live parameters in a fifth arena, `ema`, updated by the same
+    launch that updates the parameters (t2v_clip_adam_ema_step_guarded: s += rate_t * (p_new - s), rate = 1 - ema_decay;
+    ema_warmup: rate_t = max(rate, 9 / (10 + t)), TensorFlow's min(decay, (1 + t) / (10 + t))).  t is the number of updates
+    so far: the `epoch` of the device step record when the stream has one (every TrainEngine: the training iteration),
+    else step_count - 1.  ema_decay == 0 (default) allocates nothing and calls the entry it always called."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_clip_thresh=1.0,
-                 world_size=1):
+                 world_size=1, ema_decay=0.0, ema_warmup=True):
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must lie in [0, 1), got %r" % (ema_decay,))
         named = list(model.named_parameters())
         self._all_names = [n for n, _ in named]
         self._live = [(i, n, p) for i, (n, p) in enumerate(named) if not is_dead_param(n)]
@@ -64,6 +73,12 @@ class FlatAdam(object):
             p.data = view                                   # parameter now lives in the arena
             p.grad = None
             self._grad_views.append(self.grads[o:o + p.numel()].view_as(p))
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        # (1 - decay in double, rounded ONCE when it crosses the C ABI: the fp32 neighbour of 1e-4 for 0.9999, where
+        # 1 - fp32(0.9999) is 1.7e-4 relative off; tests/adam_ref.py has the same remark about beta2)
+        self.ema_rate = 1.0 - self.ema_decay
+        self.ema = self.params.clone() if self.ema_decay else None       # the shadow starts as a copy of the weights
         self._view_of = {id(p): v for (_, _, p), v in zip(self._live, self._grad_views)}
         # backward passes that know these slots write weight gradients straight into the arena (t2v_hip.grad_slot)
         t2v_hip.register_grad_slots({p.data_ptr(): (self.grads, o, tuple(p.shape))
@@ -150,6 +165,7 @@ class FlatAdam(object):
         skipped = [(self._slot_of[id(p)],) for p in self._no_grad]
         saved = [(o, n, self.params[o:o + n].clone(), self.exp_avg[o:o + n].clone(), self.exp_avg_sq[o:o + n].clone())
                  for ((o, n),) in skipped]
+        saved_ema = [self.ema[o:o + n].clone() for ((o, n),) in skipped] if self.ema is not None else []
         self._no_grad = []
         self.step_count += 1
         bc1, bc2 = self.bias_corrections(self.step_count)
@@ -159,7 +175,7 @@ class FlatAdam(object):
             sp.upload()
         lib = t2v_hip.load_library()
         guard, self.guard = self.guard, None
-        rc = lib.t2v_clip_adam_step_guarded(
+        args = [
             C.c_void_p(self.params.data_ptr()), C.c_void_p(self.grads.data_ptr()),
             C.c_void_p(self.exp_avg.data_ptr()), C.c_void_p(self.exp_avg_sq.data_ptr()),
             # (the betas go in as floats: the step runs at their fp32 neighbours, 1 - beta2 = 0.00099998713 for 0.999; DESIGN a-20)
@@ -168,15 +184,84 @@ class FlatAdam(object):
             C.c_float(self.grad_clip_thresh if self.grad_clip_thresh else 0.0),
             C.c_float(1.0 / self.world_size), C.c_float(bc1), C.c_float(bc2),
             C.c_void_p(self._partials.data_ptr()), C.c_void_p(self.grad_norm.data_ptr()),
-            None if guard is None else C.c_void_p(guard.data_ptr()), 0 if guard is None else int(guard.numel()),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            None if guard is None else C.c_void_p(guard.data_ptr()), 0 if guard is None else int(guard.numel())]
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.ema is None:
+            rc = lib.t2v_clip_adam_step_guarded(*(args + [stream]))
+        else:
+            rc = lib.t2v_clip_adam_ema_step_guarded(*(args + [
+                C.c_void_p(self.ema.data_ptr()), C.c_float(self.ema_rate), int(self.ema_warmup),
+                C.c_uint64(self.step_count - 1), stream]))
         if rc != 0:
             raise t2v_hip.T2VHipError("t2v_clip_adam_step rc=%d" % rc)
         for o, n, p0, m0, v0 in saved:
             self.params[o:o + n].copy_(p0)
             self.exp_avg[o:o + n].copy_(m0)
             self.exp_avg_sq[o:o + n].copy_(v0)
+        if saved_ema:
+            # the shadow follows the parameters as they stand AFTER the step: a slot that was put back gets
+            # s0 + rate_t * (p0 - s0), not an average of the value the kernel wrote and the lines above took back
+            rate = self._ema_rate_tensor(sp)
+            for (o, n, p0, _, _), s0 in zip(saved, saved_ema):
+                self.ema[o:o + n].copy_(s0 + rate * (p0 - s0))
         return self.grad_norm
+
+    def _ema_rate_tensor(self, sp):
+        """rate_t of the step that was just issued as a one-element device tensor, from where the kernel took its t: the
+        epoch of the device record `sp` (read on the device: the line may be part of a captured graph), else step_count - 1"""
+        rate = torch.full((1,), self.ema_rate, dtype=torch.float32, device=self.params.device)
+        if not self.ema_warmup:
+            return rate
+        if sp is not None:
+            t = sp.dev.view(torch.int64)[:1].to(torch.float32)
+        else:
+            t = torch.full((1,), float(self.step_count - 1), dtype=torch.float32, device=self.params.device)
+        return torch.maximum(rate, 9.0 / (10.0 + t))
+
+    # -- the weight average (ema_decay > 0)
+    def _need_ema(self):
+        if self.ema is None:
+            raise ValueError("this FlatAdam keeps no weight average (ema_decay=0)")
+
+    def reset_ema(self):
+        """the shadow starts over from the parameters as they are now (a model load without an average of its own)"""
+        if self.ema is not None:
+            self.ema.copy_(self.params)
+
+    def ema_state_dict(self, model):
+        """model.state_dict() with every live parameter taken from the shadow; dead parameters and buffers (the BatchNorm
+        running statistics among them: they are not averaged) come from the model.  Every tensor is a clone."""
+        self._need_ema()
+        sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        for (_, n, p), o in zip(self._live, self._offsets):
+            if n not in sd:
+                raise KeyError("the model has no parameter %r" % n)
+            sd[n] = self.ema[o:o + p.numel()].view_as(p).clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """the live parameters of `sd` (a dict of ema_state_dict()) become the shadow"""
+        self._need_ema()
+        for (_, n, p), o in zip(self._live, self._offsets):
+            self.ema[o:o + p.numel()].view_as(p).copy_(sd[n])
+
+    @contextlib.contextmanager
+    def swapped_ema(self):
+        """`with opt.swapped_ema():` the model computes with the averaged weights: the CONTENTS of `params` and `ema` are
+        exchanged in place and exchanged back on exit (bit-exact), so every pointer, view, gradient slot and captured graph
+        stays valid.  Plain torch copies: once per checkpoint, not per step.  The weight packs of the decoder kernels are
+        rebuilt from the parameters on every forward call, so nothing computed before the swap is reused inside it."""
+        self._need_ema()
+
+        def swap():
+            tmp = self.params.clone()
+            self.params.copy_(self.ema)
+            self.ema.copy_(tmp)
+        swap()
+        try:
+            yield self
+        finally:
+            swap()
 
     # -- checkpoint interchange with torch.optim.Adam (reference train.py:100-119)
     def state_dict(self):
@@ -209,4 +294,5 @@ class FlatAdam(object):
         if len(steps) > 1:
             raise ValueError("per-parameter Adam step counts differ: %s" % sorted(steps))
         self.step_count = steps.pop() if steps else 0
+        self.reset_ema()        # torch.optim.Adam's format carries no average: load_ema_state_dict() follows when there is one
 

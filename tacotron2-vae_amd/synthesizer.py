@@ -65,6 +65,17 @@ def resample_rows(items, target_rate):
 
 
 VOCODERS = ('griffin_lim', 'griffin_lim_fast', 'spsi')
+# which weights of a checkpoint a Synthesizer loads -> the checkpoint key that holds them (train.save_checkpoint)
+WEIGHTS = {'raw': 'state_dict', 'ema': 'ema_state_dict'}
+
+
+def check_weights(weights):
+    """None (= 'raw') or a name of WEIGHTS -> the name; ValueError otherwise"""
+    if weights is None:
+        return 'raw'
+    if weights not in WEIGHTS:
+        raise ValueError("weights must be one of %s or None, got %r" % (sorted(WEIGHTS), weights))
+    return weights
 
 
 class GriffinLimVocoder(object):
@@ -223,6 +234,7 @@ class Synthesizer(object):
         self.stft = TacotronSTFT(hp.filter_length, hp.hop_length, hp.win_length, hp.n_mel_channels,
                                  hp.sampling_rate, hp.mel_fmin, hp.mel_fmax)
         self.model = None
+        self.weights = 'raw'         # the weight set of the loaded checkpoint (load_checkpoint(weights=))
         self.vocoder = None
         self.neu = self.sad = self.ang = self.hap = None
 
@@ -512,22 +524,33 @@ class Synthesizer(object):
 
     # ------------------------------------------------------------------ checkpoint + centroids (synthesizer.py:74-110)
     @staticmethod
-    def centroid_cache_path(checkpoint_path, filelist_path):
-        """`<dir of ckpt>/<ckpt name>_<last '_' field of the filelist name, sans extension>.npz`"""
+    def centroid_cache_path(checkpoint_path, filelist_path, weights=None):
+        """`<dir of ckpt>/<ckpt name>_<last '_' field of the filelist name, sans extension>.npz`; the averaged weights have
+        latents of their own, hence a cache of their own: `<ckpt name>_ema_<...>.npz` with weights='ema'"""
         suffix = filelist_path.rsplit('_', 1)[1].split('.')[0] if '_' in filelist_path else 'refs'
+        if check_weights(weights) == 'ema':
+            suffix = 'ema_' + suffix
         return os.path.join(os.path.dirname(checkpoint_path), os.path.basename(checkpoint_path) + '_' + suffix + '.npz')
 
-    def load_checkpoint(self, checkpoint_path):
-        """the model of a train.py checkpoint, in eval mode (the first step of `load`)"""
+    def load_checkpoint(self, checkpoint_path, weights=None):
+        """the model of a train.py checkpoint, in eval mode (the first step of `load`).  weights: None or 'raw' = the
+        checkpoint's 'state_dict'; 'ema' = its 'ema_state_dict', the averaged weights a run with hparams.ema_decay > 0 saves
+        (ValueError when the checkpoint has none)."""
         from train import load_model
+        key = WEIGHTS[check_weights(weights)]
+        ckpt = torch.load(checkpoint_path, map_location='cpu')
+        if key not in ckpt:
+            raise ValueError("checkpoint %r holds no %r (weights=%r needs a run with hparams.ema_decay > 0)"
+                             % (checkpoint_path, key, weights))
         self.model = load_model(self.hparams)
-        self.model.load_state_dict(torch.load(checkpoint_path, map_location='cpu')['state_dict'])
+        self.model.load_state_dict(ckpt[key])
         self.model.eval()
         self.model.decoder.attention_window = self.attention_window
+        self.weights = check_weights(weights)
         return self
 
     def load(self, checkpoint_path, waveglow_path=None, vocoder=None,
-             filelist_path='./web/static/uploads/koemo_spk_emo_all_test.txt', batch_size=64):
+             filelist_path='./web/static/uploads/koemo_spk_emo_all_test.txt', batch_size=64, weights=None):
         """Positional order of the reference (synthesizer.py:74: `load(checkpoint_path, waveglow_path)`, called from
         app.py:161).  waveglow_path: a WaveGlow checkpoint `{'model': module}` exactly as the reference loads it
         (needs the `waveglow` package importable: it is an un-vendored submodule of the reference); `vocoder`: any
@@ -535,11 +558,13 @@ class Synthesizer(object):
         the same with momentum 0.99 and the non-negative least-squares mel inversion, or 'spsi' for that inversion, a phase made
         from the magnitudes' peaks and no iteration (GriffinLimVocoder.named).  A callable passed in the second
         position is taken as the vocoder.  batch_size: wavs per ragged vae_gst call of the centroid pass
-        (`latents`), when there is no centroid cache yet."""
+        (`latents`), when there is no centroid cache yet.  weights: see load_checkpoint (the centroid cache of the averaged
+        weights is a file of its own)."""
+        check_weights(weights)
         if isinstance(vocoder, str):
             # an unknown name fails before anything is loaded
             vocoder = GriffinLimVocoder.named(vocoder, self.stft, self.speed, self.pitch_st, self.formant, self.preserve_formants)
-        self.load_checkpoint(checkpoint_path)
+        self.load_checkpoint(checkpoint_path, weights=weights)
         if callable(waveglow_path) and vocoder is None:
             vocoder, waveglow_path = waveglow_path, None
         self.waveglow = None
@@ -553,7 +578,7 @@ class Synthesizer(object):
                 waveglow = self.waveglow
                 vocoder = lambda mel: waveglow.infer(mel, sigma=0.666)      # reference synthesizer.py:163
         self.vocoder = vocoder
-        npz_path = self.centroid_cache_path(checkpoint_path, filelist_path)
+        npz_path = self.centroid_cache_path(checkpoint_path, filelist_path, weights)
         if os.path.exists(npz_path):
             d = np.load(npz_path)
             zs, emotions = d['zs'], d['emotions']
@@ -810,6 +835,18 @@ class Synthesizer(object):
 DEFAULT_BATCH_SIZE = 8
 
 
+def add_weights_argument(p):
+    """--weights of the three command lines that load a checkpoint (synthesizer.py, evaluate.py, extract_latents.py)"""
+    p.add_argument('--weights', choices=sorted(WEIGHTS), default=None,
+                   help="which weights of the checkpoint: raw (default) = the last iteration's, ema = the moving average a "
+                        "run with hparams.ema_decay > 0 keeps beside them")
+
+
+def weights_option(args):
+    """the load / load_checkpoint keyword of --weights: nothing without the flag, so the call is the one it always was"""
+    return {} if args.weights is None else {'weights': args.weights}
+
+
 def build_arg_parser():
     """The reference's flags where they exist (synthesizer.py:171-179: --load_path, --sample_path, --text) and the batched
     front end's own."""
@@ -832,6 +869,7 @@ def build_arg_parser():
                    help="attention constraint: every frame attends within BACK positions behind and AHEAD in front of the "
                         "position the previous frame attended most (default: none)")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
+    add_weights_argument(p)
     from wavio import add_wav_arguments
     add_wav_arguments(p)
     add_tempo_arguments(p)
@@ -902,7 +940,7 @@ def main(argv=None):
     hp.max_decoder_steps = 600
     if args.hparams:
         hp.parse(args.hparams)
-    syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path)
+    syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path, **weights_option(args))
     os.makedirs(args.sample_path, exist_ok=True)
     texts = args.texts
     for i0 in range(0, len(texts), args.batch_size):

@@ -40,11 +40,14 @@ def load_model(hparams):
     return model
 
 
-def warm_start_model(checkpoint_path, model):
+def warm_start_model(checkpoint_path, model, optimizer=None):
+    """reference train.py:92-97.  optimizer: a FlatAdam that keeps a weight average seeds it from the loaded weights."""
     assert os.path.isfile(checkpoint_path)
     print("Warm starting model from checkpoint '{}'".format(checkpoint_path))
     ckpt = torch.load(checkpoint_path, map_location='cpu')
     model.load_state_dict(ckpt['state_dict'])
+    if getattr(optimizer, 'ema', None) is not None:
+        optimizer.reset_ema()
     return model
 
 
@@ -54,16 +57,27 @@ def load_checkpoint(checkpoint_path, model, optimizer):
     ckpt = torch.load(checkpoint_path, map_location='cpu')
     model.load_state_dict(ckpt['state_dict'])
     optimizer.load_state_dict(ckpt['optimizer'])
+    if getattr(optimizer, 'ema', None) is not None:
+        if 'ema_state_dict' in ckpt:
+            optimizer.load_ema_state_dict(ckpt['ema_state_dict'])
+        else:       # (load_state_dict above already made the shadow a copy of the loaded weights)
+            print("Checkpoint '{}' holds no 'ema_state_dict': the weight average starts from its weights".format(checkpoint_path))
     print("Loaded checkpoint '{}' from iteration {}".format(checkpoint_path, ckpt['iteration']))
     return model, optimizer, ckpt['learning_rate'], ckpt['iteration']
 
 
 def save_checkpoint(model, optimizer, learning_rate, iteration, filepath):
-    """dict layout of reference train.py:116-119 (tensors cloned out of the arena)."""
+    """dict layout of reference train.py:116-119 (tensors cloned out of the arena).  An optimiser that keeps a weight
+    average (hparams.ema_decay > 0) adds 'ema_state_dict' (the keys of 'state_dict', live parameters averaged) and
+    'ema': {'decay', 'warmup'}; without one the dict is the reference's four keys and nothing else."""
     print("Saving model and optimizer state at iteration {} to {}".format(iteration, filepath))
     state = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    torch.save({'iteration': iteration, 'state_dict': state, 'optimizer': optimizer.state_dict(),
-                'learning_rate': learning_rate}, filepath)
+    ckpt = {'iteration': iteration, 'state_dict': state, 'optimizer': optimizer.state_dict(),
+            'learning_rate': learning_rate}
+    if getattr(optimizer, 'ema', None) is not None:
+        ckpt['ema_state_dict'] = optimizer.ema_state_dict(model)
+        ckpt['ema'] = {'decay': optimizer.ema_decay, 'warmup': optimizer.ema_warmup}
+    torch.save(ckpt, filepath)
 
 
 def t2v_hip_check():
@@ -91,7 +105,8 @@ class TrainEngine(object):
         self.model = load_model(hparams)
         self.criterion = Tacotron2Loss_VAE(hparams)
         self.optimizer = FlatAdam(self.model, lr=hparams.learning_rate, weight_decay=hparams.weight_decay,
-                                  grad_clip_thresh=hparams.grad_clip_thresh, world_size=world_size)
+                                  grad_clip_thresh=hparams.grad_clip_thresh, world_size=world_size,
+                                  ema_decay=getattr(hparams, 'ema_decay', 0.0), ema_warmup=getattr(hparams, 'ema_warmup', True))
         self.allreduce = None
         if world_size > 1 or force_dist:      # force_dist: 1-rank RCCL group (tests of the launch path on one GPU)
             named, offs = self.optimizer.arena_layout()
@@ -316,7 +331,9 @@ class TrainEngine(object):
         kernels (256 workgroups that need the whole chip to themselves: a GPU shared with another process, a communication
         kernel holding CUs), the device skipped that step's update — weights and Adam moments are intact.  Latch the
         launch-per-step kernels, drop the captured graphs, restore the BatchNorm running statistics (the failed forward pass
-        fed them garbage), take the optimiser's step counter back, and tell the caller to run the iteration again."""
+        fed them garbage), take the optimiser's step counter back, and tell the caller to run the iteration again.
+        The weight average (hparams.ema_decay > 0) needs no repair: it is updated by the very launch that skipped, which
+        leaves the shadow untouched like the weights, and the re-run publishes the same iteration, hence the same rate."""
         import t2v_hip
         labels = getattr(err, 'labels', None) or []
         if not labels or not all('persistent kernel' in l for l in labels):
@@ -735,8 +752,10 @@ def prepare_dataloaders(hparams):
     return loader, valset, collate_fn
 
 
-def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn, logger, distributed_run, rank):
-    """reference train.py:122-147, including its habit of reporting the LAST batch's loss (B-13)."""
+def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn, logger, distributed_run, rank, ema=False):
+    """reference train.py:122-147, including its habit of reporting the LAST batch's loss (B-13).  ema=True: the caller has
+    put the averaged weights into the model (FlatAdam.swapped_ema); the loss is printed and logged under its own name and
+    the histograms / images of log_validation are not written a second time."""
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
     model.eval()
@@ -753,7 +772,11 @@ def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn
             reduced = (t2v_dist.reduce_tensor(loss.data, n_gpus) if distributed_run else loss).item()
     model.train()
     t2v_hip_check()
-    if rank == 0:
+    if rank == 0 and ema:
+        print("Validation loss (ema) {}: {:9f}  ".format(iteration, reduced))
+        if logger is not None and y_pred is not None:
+            logger.log_validation_ema(reduced, iteration)
+    elif rank == 0:
         print("Validation loss {}: {:9f}  ".format(iteration, reduced))
         if logger is not None and y_pred is not None:
             logger.log_validation(reduced, model, y, y_pred, iteration)
@@ -775,7 +798,7 @@ def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, 
     iteration, epoch_offset = 0, 0
     if checkpoint_path is not None:
         if warm_start:
-            warm_start_model(checkpoint_path, model)
+            warm_start_model(checkpoint_path, model, optimizer)
         else:
             _, _, saved_lr, iteration = load_checkpoint(checkpoint_path, model, optimizer)
             if hparams.use_saved_learning_rate:
@@ -810,6 +833,10 @@ def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, 
                 if iteration % hparams.iters_per_checkpoint == 0:
                     validate(model, criterion, valset, iteration, hparams.batch_size, n_gpus, collate_fn, logger,
                              hparams.distributed_run, rank)
+                    if optimizer.ema is not None:
+                        with optimizer.swapped_ema():
+                            validate(model, criterion, valset, iteration, hparams.batch_size, n_gpus, collate_fn, logger,
+                                     hparams.distributed_run, rank, ema=True)
                     if rank == 0:
                         save_checkpoint(model, optimizer, learning_rate, iteration,
                                         os.path.join(output_directory, "checkpoint_{}".format(iteration)))

@@ -29,7 +29,7 @@ with open(trace_path) as f:
             n *= max(int(r['Grid_Size_' + d]) // max(int(r['Workgroup_Size_' + d]), 1), 1)
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'], r.get('Queue_Id', '?'), n))
 rows.sort()
-adam = [i for i, r in enumerate(rows) if r[2].startswith('k_clip_adam')]
+adam = [i for i, r in enumerate(rows) if 'k_clip_adam' in r[2]]
 step = rows[adam[-2] + 1:adam[-1] + 1]
 t0 = step[0][0]
 bykey = collections.defaultdict(list)

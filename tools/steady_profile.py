@@ -6,7 +6,7 @@ with open(path) as f:
     for r in csv.DictReader(f):
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name']))
 rows.sort()
-adam = [i for i, r in enumerate(rows) if r[2].startswith('k_clip_adam')]
+adam = [i for i, r in enumerate(rows) if 'k_clip_adam' in r[2]]
 lo, hi = adam[-nsteps - 1], adam[-1]
 sel = rows[lo + 1:hi + 1]
 agg = collections.defaultdict(lambda: [0, 0])
@@ -84,7 +84,7 @@ if os.environ.get('T2V_PROFILE_SEQ'):
             full.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'],
                          r.get('Grid_Size_X', '?'), r.get('Grid_Size_Y', '?'), r.get('Grid_Size_Z', '?'), r.get('Workgroup_Size_X', '?')))
     full.sort()
-    ad = [i for i, r in enumerate(full) if r[2].startswith('k_clip_adam')]
+    ad = [i for i, r in enumerate(full) if 'k_clip_adam' in r[2]]
     with open(os.environ['T2V_PROFILE_SEQ'], 'w') as out:
         prev = None
         for s_, e_, n_, gx, gy, gz, wx in full[ad[-2] + 1:ad[-1] + 1]:

@@ -13,7 +13,7 @@ with open(path) as f:
         grid = int(r.get('Grid_Size_X', r.get('Grid_Size', 0)) or 0)
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'], q, grid // max(wg, 1)))
 rows.sort()
-adam = [i for i, r in enumerate(rows) if r[2].startswith('k_clip_adam')]
+adam = [i for i, r in enumerate(rows) if 'k_clip_adam' in r[2]]
 lo, hi = adam[-2], adam[-1]
 step = rows[lo + 1:hi + 1]
 anc = [r for r in step if r[2].startswith(anchor)]

@@ -12,7 +12,7 @@ with open(sys.argv[1]) as f:
             wgs = -1
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'], r.get('Queue_Id', '?'), wgs))
 rows.sort()
-ad = [i for i, r in enumerate(rows) if r[2].startswith('k_clip_adam')]
+ad = [i for i, r in enumerate(rows) if 'k_clip_adam' in r[2]]
 lo, hi = ad[-2], ad[-1]
 t0 = rows[lo][1]
 sel = rows[lo + 1:hi + 1]

@@ -7,7 +7,7 @@ import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 print(list(rows[0].keys()))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
-adam = [i for i, r in enumerate(rows) if r['Kernel_Name'].startswith('k_clip_adam')]
+adam = [i for i, r in enumerate(rows) if 'k_clip_adam' in r['Kernel_Name']]
 lo, hi = adam[-2], adam[-1]
 t0 = int(rows[lo]['End_Timestamp'])
 for r in rows[lo + 1:hi + 1]:
