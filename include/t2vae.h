@@ -591,6 +591,42 @@ int t2v_conv1d_x3_set_mode(int mode);
 /* 1 when the k = 5 convolution Cin -> Cout of t2v_conv1d_fwd (bf16 = 0) / t2v_conv1d_fwd_bf16 (bf16 = 1) takes the plane kernels of
  * conv_x3.hip in the current mode, 0 when it runs on the tiled kernels (mode, tile count, and whether the call's scratch fits) */
 int t2v_conv1d_takes_x3(int B, int Cin, int T, int Cout, int KS, int bf16);
+/* Which kernel a Conv1d call runs: the answer of the one function (conv_route of csrc/conv_gemm.hip) that t2v_conv1d_fwd / _bwd /
+ * _fwd_bf16 / _bwd_bf16 are dispatched by, so it follows t2v_conv1d_x3_set_mode, t2v_gemm_f32_set_mode and the T2V_CONV_* switches
+ * of the process.  op: T2V_CONV_OP_FWD, _DX (the data gradient: the convolution Cout -> Cin of dY with the flipped, transposed
+ * weights) or _DW; B, Cin, T, Cout, KS: the LAYER's dimensions as the entry points take them; bf16: the bf16_run entries;
+ * w_mod16: the address modulo 16 of the weights the kernel reads (W forward, Wt_scratch for the data gradient; the bf16 entries and
+ * the weight gradient ignore it).  Returns a T2V_CONV_ROUTE_* value, T2V_ERR_ARG for a dimension below 1 or an even KS,
+ * T2V_ERR_DIMS with bf16 where this launch has no bf16 kernel (the bf16 entries then return it).  Every output pointer may be NULL:
+ *   *fallback           the tiled family that runs instead when T2V_CONV_ROUTE_PLANE1 as a data gradient finds no slice of the
+ *                       library's ring for the flipped weights (equal to the return value everywhere else);
+ *   *tile               forward / data gradient on the tiled kernels: output positions per workgroup / 16 (2 .. 6; under the plane
+ *                       kernels: of *fallback); tiled weight gradient: positions per k-tile, 80 or 96; k_conv_gemm: 0;
+ *   *ksplit             2 = the input channels are cut in halves (gridDim.z of k_conv5_fwd[_dma]), else 1;
+ *   *dw_splits          weight gradient: k-splits, empty trailing ones included (1 = none);
+ *   *stat_blocks        forward: rows of stat_part the launch writes (t2v_conv1d_stat_blocks[_bf16]);
+ *   *dw_scratch_floats  weight gradient: floats of dw_scratch THIS launch writes (t2v_conv1d_dw_scratch_floats is the bf16 answer,
+ *                       which is never smaller);
+ *   *plane_splits, *plane_chunk   plane kernels: gridDim.z over the input channels and the stages (16 channels on T2V_CONV_ROUTE_X3,
+ *                       32 on _PLANE1) per split, the last split holding what is left; 0, 0 on every other family.
+ * It answers the PLAN, like t2v_bn_act_slices: a ksplit = 2 launch takes its raw tiles from a ring of the library, and if the ring
+ * has no slice the same kernel runs uncut (same tiles, same partial blocks).  Host only: nothing is launched. */
+#define T2V_CONV_OP_FWD 0
+#define T2V_CONV_OP_DX 1
+#define T2V_CONV_OP_DW 2
+#define T2V_CONV_ROUTE_GEMM 0            /* k_conv_gemm: any Cin, KS = 3 or 5 */
+#define T2V_CONV_ROUTE_FWD 1             /* k_conv5_fwd: register-staged */
+#define T2V_CONV_ROUTE_FWD_DMA 2         /* k_conv5_fwd_dma: staged by LDS-DMA */
+#define T2V_CONV_ROUTE_X3 3              /* k_conv5_x3<3, 2>: three bf16 planes per operand */
+#define T2V_CONV_ROUTE_BF16 4            /* k_conv5_fwd_bf16: 16 channels per k-tile */
+#define T2V_CONV_ROUTE_BF16K32 5         /* k_conv5_fwd_bf16k32: 32 channels per k-tile */
+#define T2V_CONV_ROUTE_PLANE1 6          /* k_conv5_x3<1, 4>: one pre-rounded bf16 plane per operand */
+#define T2V_CONV_ROUTE_DW 7              /* k_conv5_dw */
+#define T2V_CONV_ROUTE_DW_BF16 8         /* k_conv5_dw_bf16 */
+#define T2V_CONV_ROUTES 9
+int t2v_conv1d_route(int op, int B, int Cin, int T, int Cout, int KS, int bf16, int w_mod16, int* fallback, int* tile, int* ksplit,
+                     int* dw_splits, int* stat_blocks, int* dw_scratch_floats, int* plane_splits, int* plane_chunk);
+const char* t2v_conv1d_route_name(int route);
 
 /* nbatch independent products C_z = A_z · B_z^T (z-th operands at A + z*sAb, B + z*sBb, C + z*sCb; element strides as in
  * t2v_gemm_f32, no bias / epilogue) in one launch.  Replaces the per-item loop that autograd's bmm backward of

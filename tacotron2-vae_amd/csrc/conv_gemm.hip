@@ -1115,6 +1115,7 @@ static inline int conv5_pick_bn_ks(int T, int B, int M, int Cin, int* ks) {
 // (x3); 1: bf16_run, rounded once
 bool t2v_conv5_planes_ok(int B, int Cin, int T, int Cout, int KS, int np);
 int t2v_conv5_x3_stat_blocks(int B, int T);
+int t2v_conv5_x3_splits(int B, int Cin, int T, int M, int np, int* st_chunk);
 int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B, int Cin, int T, int M,
                      hipStream_t stream, int np);
 
@@ -1354,6 +1355,36 @@ extern "C" int t2v_conv1d_dw_scratch_floats(int B, int Cin, int T, int Cout, int
 extern "C" int t2v_conv1d_takes_x3(int B, int Cin, int T, int Cout, int KS, int bf16) {
     const int family = conv_route(CONV_OP_FWD, B, Cin, T, Cout, KS, bf16 != 0, true).family;
     return family == CONV_K_X3 || family == CONV_K_PLANE1 ? 1 : 0;
+}
+// what conv_route() decides for a call, for tests that must know which kernel they are looking at (include/t2vae.h).  The
+// T2V_CONV_ROUTE_* values are the CONV_K_* enumerators, T2V_CONV_OP_* the CONV_OP_* ones
+static_assert(CONV_OP_FWD == T2V_CONV_OP_FWD && CONV_OP_DX == T2V_CONV_OP_DX && CONV_OP_DW == T2V_CONV_OP_DW, "t2vae.h");
+static_assert(CONV_K_GEMM == T2V_CONV_ROUTE_GEMM && CONV_K_FWD == T2V_CONV_ROUTE_FWD && CONV_K_FWD_DMA == T2V_CONV_ROUTE_FWD_DMA &&
+              CONV_K_X3 == T2V_CONV_ROUTE_X3 && CONV_K_BF16 == T2V_CONV_ROUTE_BF16 && CONV_K_BF16K32 == T2V_CONV_ROUTE_BF16K32 &&
+              CONV_K_PLANE1 == T2V_CONV_ROUTE_PLANE1 && CONV_K_DW == T2V_CONV_ROUTE_DW && CONV_K_DW_BF16 == T2V_CONV_ROUTE_DW_BF16 &&
+              CONV_K_DW_BF16 + 1 == T2V_CONV_ROUTES, "t2vae.h");
+extern "C" int t2v_conv1d_route(int op, int B, int Cin, int T, int Cout, int KS, int bf16, int w_mod16, int* fallback, int* tile,
+                                int* ksplit, int* dw_splits, int* stat_blocks, int* dw_scratch_floats, int* plane_splits,
+                                int* plane_chunk) {
+    if (op < CONV_OP_FWD || op > CONV_OP_DW || B < 1 || Cin < 1 || T < 1 || Cout < 1 || KS < 1 || !(KS & 1)) return T2V_ERR_ARG;
+    const ConvRoute r = conv_route(op, B, Cin, T, Cout, KS, bf16 != 0, (w_mod16 & 15) == 0);
+    if (bf16 && r.family == CONV_K_GEMM) return T2V_ERR_DIMS;       // (as the bf16_run entries answer)
+    if (fallback) *fallback = r.fallback;
+    if (tile) *tile = r.tile;
+    if (ksplit) *ksplit = r.ksplit;
+    if (dw_splits) *dw_splits = r.dw_splits;
+    if (stat_blocks) *stat_blocks = r.stat_blocks;
+    if (dw_scratch_floats) *dw_scratch_floats = r.dw_scratch_floats;
+    int chunk = 0;
+    const bool planes = r.family == CONV_K_X3 || r.family == CONV_K_PLANE1;
+    const int nz = planes ? t2v_conv5_x3_splits(B, r.Cin, T, r.M, r.family == CONV_K_X3 ? 3 : 1, &chunk) : 0;
+    if (plane_splits) *plane_splits = nz;
+    if (plane_chunk) *plane_chunk = chunk;
+    return r.family;
+}
+extern "C" const char* t2v_conv1d_route_name(int route) {
+    static const char* const names[T2V_CONV_ROUTES] = {"gemm", "fwd", "fwd_dma", "x3", "bf16", "bf16k32", "plane1", "dw", "dw_bf16"};
+    return route >= 0 && route < T2V_CONV_ROUTES ? names[route] : "?";
 }
 
 extern "C" int t2v_conv1d_bwd(const float* W, const float* X, const float* dY, float* dX, float* dW, float* Wt_scratch,

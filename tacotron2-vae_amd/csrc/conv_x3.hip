@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void k_cx3_split_w(const float* __restrict__ W
     const int m = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
     if (m >= Mp) return;
     const bool min_ = m < M;
-    const float* row = W + ((size_t)min(m, M - 1) * Cin + 8 * g) * 5;
+    const float* row = W + ((size_t)min(m, M - 1) * Cin + min(8 * g, Cin - 1)) * 5;     // (a padded group, 8 g >= Cin, reads W's last channel and keeps none of it)
     float w[8][5];
 #pragma unroll
     for (int c = 0; c < 8; ++c)
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void k_cx3_split_x(const float* __restrict__ X
     if (s >= Tp) return;
     const int t = s - 2;
     const bool tin = t >= 0 && t < T;
-    const float* col = X + ((size_t)b * Cin + 8 * g) * T + min(max(t, 0), T - 1);
+    const float* col = X + ((size_t)b * Cin + min(8 * g, Cin - 1)) * T + min(max(t, 0), T - 1);     // (padded group: as k_cx3_split_w)
     float v[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -301,6 +301,7 @@ static float* cx_scratch(size_t floats) { return g_cx_ring.take((floats + 63) & 
 // launch geometry of t2v_conv5_x3_run and the scratch it takes (floats)
 struct CxPlan {
     int NG, Mp, G, ntile, Tp, nst, ns;
+    int st_chunk, nz;           // the launch: stages per blockIdx.z and gridDim.z (<= ns: whole chunks of stages, none of them empty)
     size_t w_slots, x_slots, part_floats;
     long tiles;
     size_t floats() const { return 4 * (w_slots + x_slots) + part_floats; }
@@ -319,6 +320,11 @@ static CxPlan cx_plan(int B, int Cin, int T, int M, int np) {
     p.nst = p.G / p.NG;
     p.ns = cx_splits(p.tiles, p.nst);
     p.part_floats = p.ns > 1 ? (size_t)p.ns * p.tiles * CX_BM * CX_BN : 0;
+    p.st_chunk = p.nst; p.nz = 1;
+    if (p.ns > 1) {
+        const int chunk = (p.nst + p.ns - 1) / p.ns, nz = (p.nst + chunk - 1) / chunk;
+        if (nz > 1) { p.st_chunk = chunk; p.nz = nz; }
+    }
     return p;
 }
 // can t2v_conv5_x3_run get its scratch for this call?  (t2v_conv5_planes_ok asks: a call the ring cannot serve is routed to the
@@ -368,12 +374,20 @@ static int cx_splits(long tiles, int nst) {
     return best;
 }
 
+// the channel splits (gridDim.z) cx_plan chooses for the convolution Cin -> M as it runs, and the stages (16 channels at np = 3, 32 at
+// np = 1) each of them sums: the last may hold fewer.  For t2v_conv1d_route of conv_gemm.hip
+int t2v_conv5_x3_splits(int B, int Cin, int T, int M, int np, int* st_chunk) {
+    const CxPlan pl = cx_plan(B, Cin, T, M, np);
+    if (st_chunk) *st_chunk = pl.st_chunk;
+    return pl.nz;
+}
+
 // W: (M, Cin, 5) weights of the convolution to run (the data gradient passes the flipped, transposed weights); np = 3: fp32 operands
 // as three bf16 planes, np = 1: bf16_run
 int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y, float* stat_part, int B, int Cin, int T, int M,
                      hipStream_t stream, int np) {
     const CxPlan pl = cx_plan(B, Cin, T, M, np);
-    const int Mp = pl.Mp, G = pl.G, ntile = pl.ntile, Tp = pl.Tp, nst = pl.nst, ns = pl.ns;
+    const int Mp = pl.Mp, G = pl.G, ntile = pl.ntile, Tp = pl.Tp;
     const size_t w_slots = pl.w_slots, x_slots = pl.x_slots;
     float* scr = cx_scratch(pl.floats());          // (the route checked that it is there)
     if (!scr) return T2V_ERR_LAUNCH;
@@ -389,18 +403,12 @@ int t2v_conv5_x3_run(const float* W, const float* X, const float* bias, float* Y
     ConvX3Args a;
     a.Wp = Wp; a.Xp = Xp; a.bias = bias; a.Y = Y; a.stat_part = stat_part;
     a.B = B; a.M = M; a.T = T; a.Mp = Mp; a.Tp = Tp; a.G = G; a.tiles_per_item = ntile;
-    a.st_chunk = nst; a.part = nullptr; a.tile_ctr = nullptr;
-    dim3 grid(B * ntile, Mp / CX_BM, 1);
-    if (ns > 1) {
-        a.st_chunk = (nst + ns - 1) / ns;
-        grid.z = (unsigned)((nst + a.st_chunk - 1) / a.st_chunk);
-        if (grid.z > 1) {
-            a.part = scr + 4 * (w_slots + x_slots);
-            a.tile_ctr = t2v_arrival_counters((int)(grid.x * grid.y));
-            if (!a.tile_ctr) return T2V_ERR_LAUNCH;
-        } else {
-            a.st_chunk = nst;
-        }
+    a.st_chunk = pl.st_chunk; a.part = nullptr; a.tile_ctr = nullptr;
+    dim3 grid(B * ntile, Mp / CX_BM, (unsigned)pl.nz);
+    if (pl.nz > 1) {
+        a.part = scr + 4 * (w_slots + x_slots);
+        a.tile_ctr = t2v_arrival_counters((int)(grid.x * grid.y));
+        if (!a.tile_ctr) return T2V_ERR_LAUNCH;
     }
     if (np == 3) k_conv5_x3<3, 2><<<grid, 256, 0, stream>>>(a);
     else k_conv5_x3<1, 4><<<grid, 256, 0, stream>>>(a);

@@ -56,6 +56,8 @@ def _expected():
         't2v_gemm_f32_grouped': (i, [P(H._GemmGroup), i, i, i, i, vp, vp]),
         't2v_gemm_route': (i, [i, i, i, l, l, l, l, i, i, i, i, i, f, i, vp, vp, vp]),   # int* form, splits, k_per_split: host words
         't2v_gemm_route_name': (C.c_char_p, [i]),
+        't2v_conv1d_route': (i, [i] * 8 + [vp] * 8),                          # eight int* outputs: host words
+        't2v_conv1d_route_name': (C.c_char_p, [i]),
         't2v_decoder_infer_persistent_window': (i, [P(H._DecPersistWeights), P(H._DecPersistBufs), i, i, i, f, f, u64,
                                                     P(H._DecItems), P(H._DecWindow), vp]),
         't2v_clip_adam_step_guarded': (i, [vp, vp, vp, vp, u64] + [f] * 9 + [vp, vp, vp, i, vp]),
@@ -201,6 +203,7 @@ def test_every_declared_entry_point_is_a_parsed_prototype_in_header_order():
     assert seen == list(protos) and len(seen) == len(set(seen)) >= 144
     assert t2v_hip.EXPORTS == tuple(seen) and 't2v_conv1d_takes_x3' in t2v_hip.EXPORTS and 't2v_bn_act_slices' in t2v_hip.EXPORTS
     assert 't2v_gemm_route' in t2v_hip.EXPORTS and 't2v_gemm_route_name' in t2v_hip.EXPORTS
+    assert 't2v_conv1d_route' in t2v_hip.EXPORTS and 't2v_conv1d_route_name' in t2v_hip.EXPORTS
     lib = t2v_hip.load_library()
     for name, (restype, argtypes) in protos.items():
         fn = getattr(lib, name)
