@@ -1194,6 +1194,29 @@ int t2v_spectral_envelope(const float* mag, const int32_t* n_frames, int B, int 
 #define T2V_VOICE_SILENT_DB -200
 int t2v_voice_quality(const float* y, const int32_t* n, int y_stride, int B, float* out, int t_stride, void* stream);
 
+/* ------------------------------------------------------------------ batch collate from the resident corpus (csrc/collate.hip)
+ * The training set lives on the device as flat stores (corpus.ResidentCorpus): utterance u has its log-mel (80, n_frames[u])
+ * fp32, row-major with its OWN row stride n_frames[u], at mel_store + mel_off[u], and its n_ids[u] symbol ids (int32) at
+ * id_store + id_off[u]; speaker[u] and emotion[u] are class indices.  All of these and idx are device memory.
+ *
+ * One launch writes the reference's collated batch (data_utils.py:88-137) for the B utterances idx[0 .. B), row b from
+ * utterance idx[b] (the caller has sorted the rows), with T_b = n_frames[idx[b]] and L_b = n_ids[idx[b]]:
+ *   text_padded (B, T_in) int64       the ids, then 0;
+ *   mel_padded (B, 80, T_out) fp32    the stored frames, then 0.0;
+ *   gate_padded (B, T_out) fp32       1.0 from frame T_b - 1 on, 0.0 before;
+ *   output_lengths (B) int64          T_b;
+ *   speakers (B, n_speakers), emotions (B, n_emotions) int64   one-hot rows (all 0 for a class index outside the width).
+ * Every output element is written exactly once, pads included, so the outputs may be uninitialised memory; no atomics: equal
+ * inputs give equal bits.  The indices and the two widths are the caller's to check on the host (0 <= idx[b] < n_utts,
+ * L_b <= T_in, T_b <= T_out); the kernel clamps an index to 0..n_utts-1 and the counts to T_in / T_out, so nothing outside a
+ * store is read and nothing outside an output is written, whatever idx holds.
+ * A null pointer, B < 1, n_utts < 1, T_in < 1, T_out < 1, n_speakers < 1 or n_emotions < 1 is T2V_ERR_ARG. */
+int t2v_collate_batch(const float* mel_store, const int64_t* mel_off, const int32_t* n_frames, const int32_t* id_store,
+                      const int64_t* id_off, const int32_t* n_ids, const int32_t* speaker, const int32_t* emotion,
+                      const int32_t* idx, int B, int n_utts, int T_in, int T_out, int n_speakers, int n_emotions,
+                      int64_t* text_padded, float* mel_padded, float* gate_padded, int64_t* output_lengths,
+                      int64_t* speakers, int64_t* emotions, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

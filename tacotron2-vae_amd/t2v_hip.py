@@ -1252,6 +1252,80 @@ def mel_frontend(wav, n_samples, tables, scale=1.0, t_stride=None):
     return out
 
 
+class CorpusStore(object):
+    """The device side of corpus.ResidentCorpus, as t2v_collate_batch reads it (include/t2vae.h): flat fp32 mels with int64
+    offsets, flat int32 symbol ids with int64 offsets, and one int32 per utterance for the frame count, the symbol count, the
+    speaker and the emotion.  host_frames / host_ids are the same counts on the host (CPU int64 tensors): every check of a
+    batch runs on them, never on device memory."""
+    TENSORS = ('mel', 'mel_off', 'n_frames', 'ids', 'id_off', 'n_ids', 'speaker', 'emotion')
+    DTYPES = (torch.float32, torch.int64, torch.int32, torch.int32, torch.int64, torch.int32, torch.int32, torch.int32)
+
+    def __init__(self, n_speakers, n_emotions, host_frames, host_ids, **tensors):
+        self.n_speakers, self.n_emotions = int(n_speakers), int(n_emotions)
+        self.host_frames, self.host_ids = host_frames, host_ids
+        self.n_utts = int(host_frames.numel())
+        for name, dt in zip(self.TENSORS, self.DTYPES):
+            t = tensors[name]
+            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise T2VHipError("CorpusStore.%s: a contiguous %s device tensor is needed" % (name, dt))
+            setattr(self, name, t)
+        for name in self.TENSORS:
+            if name not in ('mel', 'ids') and getattr(self, name).numel() != self.n_utts:
+                raise T2VHipError("CorpusStore.%s: %d entries for %d utterances" % (name, getattr(self, name).numel(), self.n_utts))
+
+    def nbytes(self):
+        return sum(getattr(self, n).numel() * getattr(self, n).element_size() for n in self.TENSORS)
+
+
+def collate_check(store, indices, T_in, T_out):
+    """the host's check of one batch against the store's host tables: ValueError, nothing launched.  Returns the indices as a list."""
+    indices = [int(i) for i in (indices.tolist() if torch.is_tensor(indices) else indices)]
+    if not indices:
+        raise ValueError("collate_batch: an empty batch")
+    if min(indices) < 0 or max(indices) >= store.n_utts:
+        raise ValueError("collate_batch: utterance indices must lie in [0, %d), got %s" % (store.n_utts, indices))
+    need_in = int(store.host_ids[indices].max())
+    need_out = int(store.host_frames[indices].max())
+    if T_in < need_in or T_out < need_out:
+        raise ValueError("collate_batch: T_in = %d, T_out = %d do not cover the batch (%d symbols, %d frames)"
+                         % (T_in, T_out, need_in, need_out))
+    return indices
+
+
+COLLATE_OUT = (('text_padded', torch.int64), ('mel_padded', torch.float32), ('gate_padded', torch.float32),
+               ('output_lengths', torch.int64), ('speakers', torch.int64), ('emotions', torch.int64))
+
+
+def collate_batch(store, idx, T_in, T_out, out=None):
+    """One launch of t2v_collate_batch on the current stream: rows idx[0 .. B) of the store as the reference's padded batch.
+    idx: the utterance indices in row order.  A list or a CPU tensor is checked here (collate_check) and uploaded; a device
+    int32 tensor is taken as checked by its maker (corpus.ResidentCollate checks before its asynchronous upload, so this
+    path never reads device memory back).  out: the six tensors (text_padded, mel_padded, gate_padded, output_lengths,
+    speakers, emotions), contiguous and of the right shapes, instead of fresh torch.empty memory.  Returns the six."""
+    lib = _require_gpu(store.mel)
+    T_in, T_out = int(T_in), int(T_out)
+    if not (torch.is_tensor(idx) and idx.is_cuda):
+        idx = torch.tensor(collate_check(store, idx, T_in, T_out), dtype=torch.int32).to(store.mel.device)
+    if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != store.mel.device:
+        raise T2VHipError("collate_batch: idx must be a contiguous int32 vector on the store's device")
+    B = idx.numel()
+    shapes = ((B, T_in), (B, 80, T_out), (B, T_out), (B,), (B, store.n_speakers), (B, store.n_emotions))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=dt, device=idx.device) for s, (_, dt) in zip(shapes, COLLATE_OUT))
+    else:
+        out = tuple(out)
+        if len(out) != len(COLLATE_OUT):
+            raise ValueError("collate_batch: out= takes %d tensors" % len(COLLATE_OUT))
+        for t, s, (name, dt) in zip(out, shapes, COLLATE_OUT):
+            if not t.is_cuda or t.device != idx.device or t.dtype != dt or tuple(t.shape) != s or not t.is_contiguous():
+                raise ValueError("collate_batch: out= %s must be a contiguous %s device tensor of shape %s" % (name, dt, s))
+    _check(lib.t2v_collate_batch(_p(store.mel), _p(store.mel_off), _p(store.n_frames), _p(store.ids), _p(store.id_off),
+                                 _p(store.n_ids), _p(store.speaker), _p(store.emotion), _p(idx), B, store.n_utts, T_in, T_out,
+                                 store.n_speakers, store.n_emotions, *([_p(t) for t in out] + [_stream()])),
+           't2v_collate_batch')
+    return out
+
+
 def _checked_lengths(v, B, lo, hi, count_msg, range_msg, reject_float=True, reject_bool=True, default=None, dtype=torch.int32):
     """The one check of a lengths argument: B values in lo..hi from a list, a CPU or a device tensor (None: B times `default`, for
     a caller that has one), as a host tensor of `dtype` (None: as it came).  ValueError(count_msg + the values) on a wrong count or

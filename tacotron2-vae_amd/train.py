@@ -721,9 +721,13 @@ def prepare_directories_and_logger(output_directory, log_directory, rank):
     return Tacotron2Logger(os.path.join(output_directory or '.', log_directory))
 
 
-def prepare_dataloaders(hparams):
+def prepare_dataloaders(hparams, resident_corpus=False):
     """reference train.py:52-65 (DistributedSampler shards, drop_last, the reference's collate layout).
-    Two switches the reference does not have, both off by default:
+    Switches the reference does not have, all off by default:
+      resident_corpus=True : (an argument, not a hyper-parameter) the training and the validation list are turned into mels
+                             once and kept on the GPU (corpus.ResidentCorpus, every rank holds the whole store); trainset and
+                             valset are its two views, whose items are utterance indices, and corpus.ResidentCollate
+                             assembles a batch with one launch.  Samplers and bucketing are the code below, unchanged;
       device_frontend=True : the dataset returns raw int16 audio, the collate pads it, and the whole batch goes
                              through ONE STFT->mel launch on the GPU (data_utils.DeviceFrontendCollate);
       bucket_batches=True  : batches are drawn from length buckets (data_utils.BucketBatchSampler), so that a
@@ -735,10 +739,21 @@ def prepare_dataloaders(hparams):
     if device_fe and getattr(hparams, 'load_mel_from_disk', False):
         raise ValueError("device_frontend=True needs raw audio: it cannot be combined with load_mel_from_disk=True "
                          "(the collate would run the STFT over stored mels)")
-    trainset = TextMelLoader(hparams.training_files, hparams, return_audio=device_fe)
-    valset = TextMelLoader(hparams.validation_files, hparams, return_audio=device_fe)
-    collate_fn = (DeviceFrontendCollate(hparams, stft=trainset.stft) if device_fe
-                  else TextMelCollate(hparams.n_frames_per_step))
+    if resident_corpus:
+        if getattr(hparams, 'load_mel_from_disk', False):
+            raise ValueError("resident_corpus=True needs raw audio: it cannot be combined with load_mel_from_disk=True "
+                             "(the store is built by the device front end from the wavs)")
+        from corpus import ResidentCollate, ResidentCorpus
+        corpus = ResidentCorpus([hparams.training_files, hparams.validation_files], hparams)
+        if not hparams.distributed_run or dist.get_rank() == 0:
+            print(corpus.describe(), flush=True)
+        trainset, valset = corpus.view(0), corpus.view(1)
+        collate_fn = ResidentCollate(corpus, hparams)
+    else:
+        trainset = TextMelLoader(hparams.training_files, hparams, return_audio=device_fe)
+        valset = TextMelLoader(hparams.validation_files, hparams, return_audio=device_fe)
+        collate_fn = (DeviceFrontendCollate(hparams, stft=trainset.stft) if device_fe
+                      else TextMelCollate(hparams.n_frames_per_step))
     if getattr(hparams, 'bucket_batches', False):
         world, rank = (dist.get_world_size(), dist.get_rank()) if hparams.distributed_run else (1, 0)
         batch_sampler = BucketBatchSampler(trainset.lengths(), hparams.batch_size, world_size=world, rank=rank,
@@ -783,7 +798,8 @@ def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn
     return reduced
 
 
-def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, rank, group_name, hparams):
+def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, rank, group_name, hparams,
+          resident_corpus=False):
     if hparams.distributed_run:
         t2v_dist.init_distributed(hparams, n_gpus, rank, group_name)
         n_gpus, rank = dist.get_world_size(), dist.get_rank()
@@ -793,7 +809,7 @@ def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, 
     model, optimizer, criterion = engine.model, engine.optimizer, engine.criterion
     learning_rate = hparams.learning_rate
     logger = prepare_directories_and_logger(output_directory, log_directory, rank)
-    train_loader, valset, collate_fn = prepare_dataloaders(hparams)
+    train_loader, valset, collate_fn = prepare_dataloaders(hparams, resident_corpus=resident_corpus)
 
     iteration, epoch_offset = 0, 0
     if checkpoint_path is not None:
@@ -845,7 +861,7 @@ def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, 
         logger.close()
 
 
-if __name__ == '__main__':
+def cli_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('-o', '--output_directory', type=str, help='directory to save checkpoints')
     ap.add_argument('-l', '--log_directory', type=str, help='directory to save tensorboard logs')
@@ -855,8 +871,14 @@ if __name__ == '__main__':
     ap.add_argument('--rank', type=int, default=0, required=False, help='rank of current gpu')
     ap.add_argument('--group_name', type=str, default='group_name', required=False, help='Distributed group name')
     ap.add_argument('--hparams', type=str, required=False, help='comma separated name=value pairs')
-    args = ap.parse_args()
+    ap.add_argument('--resident_corpus', action='store_true',
+                    help='keep the training and validation sets on the GPU as mels and collate every batch with one kernel')
+    return ap
+
+
+if __name__ == '__main__':
+    args = cli_parser().parse_args()
     hp = create_hparams(args.hparams)
     print("Distributed Run:", hp.distributed_run)
     train(args.output_directory, args.log_directory, args.checkpoint_path, args.warm_start, args.n_gpus,
-          args.rank, args.group_name, hp)
+          args.rank, args.group_name, hp, resident_corpus=args.resident_corpus)
