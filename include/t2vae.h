@@ -1217,6 +1217,48 @@ int t2v_collate_batch(const float* mel_store, const int64_t* mel_off, const int3
                       int64_t* text_padded, float* mel_padded, float* gate_padded, int64_t* output_lengths,
                       int64_t* speakers, int64_t* emotions, void* stream);
 
+/* ------------------------------------------------------------------ forced alignment: symbol durations by monotonic search
+ * The best monotonic path through B alignment matrices (csrc/durations.hip), with the strides and lengths of
+ * t2v_alignment_stats: A fp32 with element (b, t, j) at A[b a_stride_b + t a_stride_t + j]; row b has n = n_frames[b] valid
+ * frames and L = n_ids[b] valid symbols (device int32).  Only A[b, t < n, j < L] is read and A is never written.  Measure:
+ *   a(t, j) = max(A[b, t, j], T2V_MAS_FLOOR); a NaN counts as the floor;
+ *   a path p has p_0 = 0, p_{n-1} = L - 1 and p_t - p_{t-1} in {0, ..., max_step};
+ *   Q(0, 0) = ln a(0, 0);  Q(t, j) = ln a(t, j) + max_{s = 0..max_step} Q(t-1, j-s), one fp32 add per cell (logf, then +);
+ *   on equal Q the smallest step wins (staying beats advancing);
+ *   cells outside the reachable band (j <= t S and L - 1 - j <= (n - 1 - t) S, S = max_step) are -inf and never chosen.
+ * Outputs, by a walk back from (n - 1, L - 1) along the kept decisions:
+ *   path      (B, path_stride) int32: p_t for t < n, -1 from n to the stride;
+ *   durations (B, sym_stride) int32:  the number of frames t with p_t = j for j < L, 0 from L to the stride;
+ *   starts    (B, sym_stride) int32:  the first frame of symbol j, or, where its duration is 0 (a skipped symbol, max_step >=
+ *                                     2), the frame where it would start: the prefix sums of durations.  0 from L on;
+ *   score     (B) fp32:               Q(n-1, L-1) / n, the mean over frames of ln a(t, p_t).
+ * A row with no feasible path (L - 1 > (n - 1) max_step, or a length clamped to 0) gets score NaN, path -1, durations 0 and
+ * starts 0 over the whole strides; the other rows of the batch are not affected.
+ * One workgroup per row; a row gives the same bits alone, in any batch, at any stride and with any padding.  No atomics.
+ * Any B, N >= 1; 1 <= T_in <= T2V_MAS_MAX_SYMBOLS and 1 <= max_step <= 3, else T2V_ERR_DIMS.  A null pointer, B, N or
+ * T_in < 1, a_stride_t < T_in, a_stride_b < (N - 1) a_stride_t + T_in, path_stride < N or sym_stride < T_in is T2V_ERR_ARG.
+ * The lengths are the caller's to check on the host (1 <= n <= N, 1 <= L <= T_in); the kernel clamps them to 0..N and 0..T_in,
+ * so none addresses outside the tensor.
+ * scratch: t2v_mas_scratch_bytes(B, N, T_in) bytes of device memory, the caller's: one decision byte per cell (0 for sizes
+ * that are refused).
+ *
+ * t2v_segment_means: sums of a frame track over the segments of such a path.  v (B, v_stride) fp32; counted (B, v_stride)
+ * bytes, non-zero where a frame counts, or NULL (every frame counts); starts / durations (B, seg_stride) int32.  For symbol
+ * j < T_in of row b, with the segment [starts, starts + durations) clamped to 0..v_stride:
+ *   sums (B, out_stride) fp32:    0.f + the v of its counted frames, added in ascending frame order;
+ *   counts (B, out_stride) int32: the number of those frames.
+ * One thread per symbol: the order of every sum depends on the row alone.  A segment of duration 0 gives 0 and 0.  Columns
+ * from T_in to out_stride are not written.  A null pointer other than counted, B, T_in or v_stride < 1, seg_stride < T_in or
+ * out_stride < T_in is T2V_ERR_ARG. */
+#define T2V_MAS_MAX_SYMBOLS 2048    /* the two live rows of Q in LDS: 2 x 2048 fp32 */
+#define T2V_MAS_FLOOR 1e-8f         /* below fp32's epsilon next to a row sum of 1; |ln| = 18.42 bounds a cell's penalty */
+size_t t2v_mas_scratch_bytes(int B, int N, int T_in);
+int t2v_mas(const float* A, long long a_stride_b, long long a_stride_t, const int32_t* n_frames, const int32_t* n_ids, int B,
+            int N, int T_in, int max_step, int32_t* path, int path_stride, int32_t* durations, int32_t* starts, int sym_stride,
+            float* score, void* scratch, void* stream);
+int t2v_segment_means(const float* v, const void* counted, int v_stride, const int32_t* starts, const int32_t* durations,
+                      int seg_stride, int B, int T_in, float* sums, int32_t* counts, int out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--attention_window BACK,AHEAD] [--weights raw|ema] [--speed R]
+                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--durations [--max_step S]] [--attention_window BACK,AHEAD] [--weights raw|ema] [--speed R]
                        [--pitch ST] [--formant ST] [--preserve_formants]
                        [--hparams ...]
 
@@ -80,6 +80,17 @@ two alpha_db tracks along the warping path.  The summary gains "voice": overall 
 keys, and per emotion alpha_vs_neu_db, alpha_ref_vs_neu_db, cpp_vs_neu_db and cpp_ref_vs_neu_db, the emotion's mean minus
 neutral's, synthesised and recorded; no thresholds.
 
+--durations asks about timing per symbol, which warp_dev gives as one number per utterance.  The best monotonic path through
+an alignment matrix (`t2v_hip.mas`, csrc/durations.hip: monotonic alignment search, steps of at most --max_step symbols per
+frame) says that symbol j occupies the frames [s, e).  It is run on the free-running alignments of the synthesis and on the
+teacher-forced alignments of the recording against the same text (one forward per row), so both sides are segmented into the
+text's own symbols.  Every row gains dur_rmse_frames, dur_corr (Pearson over the symbols), dur_log_ratio_spread (standard
+deviation of ln((1 + d_syn) / (1 + d_rec)): 0 for a uniform change of tempo), align_logp_syn and align_logp_rec (the mean log
+weight along each path: low where text and audio do not match); with --prosody also seg_f0_rmse_cents and seg_f0_corr, of the
+mean F0 per symbol over the symbols voiced on both sides.  A side whose text has more symbols than its frames can reach has
+null.  Every summary dict gains n_durations and the means; OUT.json then holds "max_step".  --durations with --prosody is
+refused together with --speed / --pitch, as --aligned is.
+
 --attention_window BACK,AHEAD decodes every row under the attention constraint of `Decoder.attention_window` (each frame
 attends within BACK positions behind and AHEAD in front of the position the previous frame attended most).
 OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart.
@@ -103,6 +114,7 @@ import json
 
 DEFAULT_BATCH_SIZE = 8
 DEFAULT_STYLE_K = 5
+DEFAULT_MAX_STEP = 1
 CONDITIONS = ('ref', 'emotion')
 
 
@@ -141,6 +153,14 @@ def build_arg_parser():
                    help="also measure the voice quality of each synthesised waveform (Griffin-Lim) and of its recording: rows gain "
                         "the medians of alpha ratio, Hammarberg index, spectral slope and cepstral peak prominence on both sides, "
                         "alpha_shift_db and cpp_shift_db, with --aligned alpha_rmse_db and alpha_corr; the summary a voice block")
+    p.add_argument('--durations', action='store_true',
+                   help="also force the alignments of each synthesis and of its recording (teacher-forced) onto the text by "
+                        "monotonic search and compare the frames per symbol: rows gain dur_rmse_frames, dur_corr, "
+                        "dur_log_ratio_spread, align_logp_syn and align_logp_rec, with --prosody seg_f0_rmse_cents and "
+                        "seg_f0_corr; the summary their means")
+    p.add_argument('--max_step', type=int, default=DEFAULT_MAX_STEP, metavar='S',
+                   help="symbols the --durations path may advance per frame, 1..3 (above 1 a symbol may be skipped); unused "
+                        "without it")
     from evaluation import parse_attention_window
     p.add_argument('--attention_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
                    help="attention constraint of the free-running decode: every frame attends within BACK positions behind and "
@@ -162,6 +182,11 @@ def parse_args(argv=None):
         raise SystemExit("--style_k must be in 1..32")
     if args.limit is not None and args.limit < 1:
         raise SystemExit("--limit must be >= 1")
+    if not 1 <= args.max_step <= 3:
+        raise SystemExit("--max_step must be in 1..3")
+    if args.durations and args.prosody and (args.speed != 1.0 or args.pitch != 0.0):
+        raise SystemExit("--durations with --prosody reads the pitch track over the frames of the alignments' path; with --speed / "
+                         "--pitch the waveform is on another time axis: drop one of the two or the tempo flags")
     if args.aligned and (args.prosody or args.energy or args.voice) and (args.speed != 1.0 or args.pitch != 0.0):
         raise SystemExit("--aligned with --prosody / --energy / --voice scores tracks along the mels' warping path; with --speed / --pitch "
                          "the waveform is on another time axis: drop --aligned or the two flags")
@@ -207,16 +232,19 @@ def main(argv=None):
             syn.vocoder = GriffinLimVocoder.named(args.vocoder, syn.stft, syn.speed, syn.pitch_st, syn.formant, syn.preserve_formants)
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
+    timing = dict(durations=True, max_step=args.max_step) if args.durations else {}
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
-                           aligned=args.aligned, energy=args.energy, voice=args.voice, **style)
+                           aligned=args.aligned, energy=args.energy, voice=args.voice, **style, **timing)
     summary = summarize(records)
     formant_keys = {}
     if args.formant != 0.0 or args.preserve_formants:                     # the report gains its new keys only with a new flag
         formant_keys = {'formant': syn.formant, 'preserve_formants': syn.preserve_formants}
+    timing_keys = {'max_step': args.max_step} if args.durations else {}   # likewise
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)],
                    'attention_window': None if syn.attention_window is None else list(syn.attention_window),
-                   'weights': args.weights or 'raw', 'speed': syn.speed, 'pitch': syn.pitch_st, **formant_keys}, f, indent=1)
+                   'weights': args.weights or 'raw', 'speed': syn.speed, 'pitch': syn.pitch_st, **formant_keys, **timing_keys},
+                  f, indent=1)
     print(json.dumps(summary, indent=1))
     if args.alignment:
         for name, st in summary['by_emotion'].items():
@@ -226,6 +254,11 @@ def main(argv=None):
         for name, st in summary['by_emotion'].items():
             print("%s: dtw_mean %s, mcd_db_mean %s, ffe_mean %s, warp_dev_mean %s (%d rows that stopped)"
                   % (name, st['dtw_mean'], st['mcd_db_mean'], st['ffe_mean'], st['warp_dev_mean'], st['n_aligned']))
+    if args.durations:
+        for name, st in summary['by_emotion'].items():
+            print("%s: dtw_mean %s, dur_rmse_frames_mean %s, dur_corr_mean %s, dur_log_ratio_spread_mean %s, align_logp_rec_mean %s "
+                  "(%d rows that stopped)" % (name, st['dtw_mean'], st['dur_rmse_frames_mean'], st['dur_corr_mean'],
+                                              st['dur_log_ratio_spread_mean'], st['align_logp_rec_mean'], st['n_durations']))
     if args.energy:
         for name, st in summary['energy']['by_emotion'].items():
             print("%s: loudness_shift_lu_mean %s, loudness_vs_neu_lu %s (recordings %s), energy_spread_ratio_mean %s (%d rows)"

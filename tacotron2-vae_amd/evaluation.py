@@ -53,7 +53,16 @@ pressed voice has more), `hammarberg_db` / `hammarberg_ref_db` (the peak below 2
 / `slope_ref_db_khz` (over 500 - 1500 Hz), `cpp_db` / `cpp_ref_db` (a breathy voice has a weak cepstral peak), and
 `alpha_shift_db` and `cpp_shift_db` = synthesis - recording.  A side without a counted frame or without a waveform has None.
 With aligned=True as well, `alpha_rmse_db` and `alpha_corr` compare the two alpha_db tracks along the warping path, over the
-points where both frames are counted.  `summarize` adds a `voice` block."""
+points where both frames are counted.  `summarize` adds a `voice` block.
+
+`evaluate(durations=True)` adds the timing per symbol (`t2v_hip.mas`, the best monotonic path through an alignment matrix): the
+free-running alignments of the synthesis and the teacher-forced alignments of the recording are each forced onto the row's
+text, which gives frames per symbol on both sides.  `dur_rmse_frames`, `dur_corr` (Pearson over the symbols) and
+`dur_log_ratio_spread` (standard deviation of ln((1 + d_syn) / (1 + d_rec)): 0 for a uniform change of tempo) compare them;
+`align_logp_syn` / `align_logp_rec` are the mean log attention weight along each path (low: the text does not match).  With
+prosody=True as well, `seg_f0_rmse_cents` and `seg_f0_corr` compare the mean F0 per symbol (`t2v_hip.segment_means` over the
+voiced frames) on the symbols voiced on both sides.  A side without a feasible path (more symbols than frames can reach) has
+None.  `summarize` adds `n_durations` and the means to every stats dict."""
 import math
 
 EMOTIONS = ('neu', 'sad', 'ang', 'hap')      # label ids 0..3 of the koemo filelists (synthesizer.EMOTIONS)
@@ -380,6 +389,76 @@ def _voice_block(records, emotions):
     return {'overall': _voice_stats(records), 'by_emotion': by}
 
 
+DURATION_KEYS = ('dur_rmse_frames', 'dur_corr', 'dur_log_ratio_spread', 'align_logp_syn', 'align_logp_rec')
+DURATION_F0_KEYS = ('seg_f0_rmse_cents', 'seg_f0_corr')
+
+
+def _pearson(x, y):
+    """Pearson correlation of two equally long fp64 lists; None under 2 values or at a zero variance"""
+    n = len(x)
+    if n < 2:
+        return None
+    mx, my = sum(x) / n, sum(y) / n
+    sxx, syy = sum((a - mx) ** 2 for a in x), sum((b - my) ** 2 for b in y)
+    if not (sxx > 0.0 and syy > 0.0):
+        return None
+    return max(-1.0, min(1.0, sum((a - mx) * (b - my) for a, b in zip(x, y)) / math.sqrt(sxx * syy)))
+
+
+def duration_fields(d_syn, d_rec, logp_syn, logp_rec):
+    """the DURATION_KEYS of one record from the symbol durations (frames per symbol, `t2v_hip.mas`) of the synthesis and of the
+    recording over the same symbols, and the two mean log-probabilities along the paths.  A side without a feasible path
+    (durations None) leaves the three comparisons None and keeps the other side's align_logp.  dur_rmse_frames: root mean
+    square of d_syn - d_rec over the symbols; dur_corr: their Pearson correlation (None under 2 symbols or at a zero variance);
+    dur_log_ratio_spread: the standard deviation over the symbols of ln((1 + d_syn) / (1 + d_rec)), 0 when every symbol is
+    stretched alike."""
+    out = dict.fromkeys(DURATION_KEYS)
+    out['align_logp_syn'] = None if logp_syn is None or d_syn is None else _finite(logp_syn)
+    out['align_logp_rec'] = None if logp_rec is None or d_rec is None else _finite(logp_rec)
+    if d_syn is None or d_rec is None:
+        return out
+    a, b = [float(v) for v in d_syn], [float(v) for v in d_rec]
+    if len(a) != len(b) or not a:
+        raise ValueError("duration_fields: %d and %d symbols; both sides are searched over the same text" % (len(a), len(b)))
+    L = len(a)
+    out['dur_rmse_frames'] = math.sqrt(sum((u - v) ** 2 for u, v in zip(a, b)) / L)
+    out['dur_corr'] = _pearson(a, b)
+    ratio = [math.log((1.0 + u) / (1.0 + v)) for u, v in zip(a, b)]
+    mean = sum(ratio) / L
+    out['dur_log_ratio_spread'] = math.sqrt(sum((r - mean) ** 2 for r in ratio) / L)
+    return out
+
+
+def segment_f0_fields(sum_syn, count_syn, sum_rec, count_rec):
+    """the DURATION_F0_KEYS of one record from `t2v_hip.segment_means` of both sides' F0 tracks over their voiced frames (sums in
+    Hz and counts per symbol; None for a side without a track or a path): the mean F0 of a symbol is sum / count, the symbols
+    with a voiced frame on both sides are compared.  seg_f0_rmse_cents: root mean square of 1200 log2(syn / rec); seg_f0_corr:
+    Pearson correlation of the two log2 means.  None without such a symbol (the correlation also under 2, or at a zero
+    variance)."""
+    out = dict.fromkeys(DURATION_F0_KEYS)
+    if sum_syn is None or sum_rec is None:
+        return out
+    pairs = [(math.log2(float(s) / c), math.log2(float(r) / k))
+             for s, c, r, k in zip(sum_syn, count_syn, sum_rec, count_rec) if c > 0 and k > 0 and s > 0 and r > 0]
+    if not pairs:
+        return out
+    out['seg_f0_rmse_cents'] = 1200.0 * math.sqrt(sum((u - v) ** 2 for u, v in pairs) / len(pairs))
+    out['seg_f0_corr'] = _pearson([u for u, _ in pairs], [v for _, v in pairs])
+    return out
+
+
+def _duration_stats(records):
+    """Over the `n_durations` rows that stopped at the gate and have durations on both sides (`dur_rmse_frames` not None; a row
+    that ran to max_decoder_steps has no end to force the path to): the mean of each of DURATION_KEYS, and of
+    DURATION_F0_KEYS when the records carry them, over the rows that have the value."""
+    stopped = [r for r in records if not r['hit_max']]
+    out = {'n_durations': sum(1 for r in stopped if r.get('dur_rmse_frames') is not None)}
+    keys = DURATION_KEYS + (DURATION_F0_KEYS if any('seg_f0_corr' in r for r in records) else ())
+    for k in keys:
+        out[k + '_mean'] = _mean([r[k] for r in stopped if r.get(k) is not None])
+    return out
+
+
 STYLE_KEYS = ('style_emotion', 'style_hit', 'style_own_rank', 'style_own_dist', 'style_silhouette')
 
 
@@ -444,7 +523,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
     n_rows = 0 and None statistics when it has no rows.  A label outside `emotions` is an error.  When the records carry
     the prosody keys (evaluate(prosody=True)) every stats dict also holds those of `_prosody_stats`; when they carry the
     alignment keys (evaluate(alignment=True)), those of `_alignment_stats`, cut with end_slack, gap_min and back_slack; when
-    they carry the aligned keys (evaluate(aligned=True)), `n_aligned` and the means of `_aligned_stats`.
+    they carry the aligned keys (evaluate(aligned=True)), `n_aligned` and the means of `_aligned_stats`; when they carry the
+    duration keys (evaluate(durations=True)), `n_durations` and the means of `_duration_stats`.
     When they carry the style keys (evaluate(style=True)) the result gains 'style': `_style_block`, with k, n_recordings and
     ref_accuracy from style_info, else from the records' own `style_info` (StyleRecords), else None.
     When they carry the energy keys (evaluate(energy=True)) the result gains 'energy': `_energy_block`; when they carry the
@@ -458,6 +538,7 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
     prosody = any('f0_shift_st' in r for r in records)
     alignment = any('n_symbols' in r for r in records)
     aligned = any('mcd_db' in r for r in records)
+    durations = any('dur_rmse_frames' in r for r in records)
 
     def stats(rows):
         out = _stats(rows)
@@ -467,6 +548,8 @@ def summarize(records, emotions=EMOTIONS, end_slack=END_SLACK, gap_min=GAP_MIN, 
             out.update(_alignment_stats(rows, end_slack, gap_min, back_slack))
         if aligned:
             out.update(_aligned_stats(rows))
+        if durations:
+            out.update(_duration_stats(rows))
         return out
     out = {'overall': stats(records),
            'by_emotion': {name: stats([r for r in records if int(r['emotion']) == i]) for i, name in enumerate(emotions)}}

@@ -213,6 +213,42 @@ def _pairs_along_path(g, scores, tracks, keep):
         yield b, [(u, v) for u, v, w in zip(pa, pc, pk) if w]
 
 
+def durations(g, max_step=1, f0=False):
+    """The timing per symbol of both sides (evaluation.DURATION_KEYS): `t2v_hip.mas` forces the free-running alignments the
+    group already holds onto each row's text, and the teacher-forced alignments of the row's recording against the same text
+    (`Synthesizer._forced_alignments`: one forward per row, no decoder seed taken) onto the same symbols; one search call and
+    one copy to the host per side.  A side whose text has more symbols than its frames can reach has no path, and None.  f0
+    (prosody is on) adds evaluation.DURATION_F0_KEYS: `t2v_hip.segment_means` of g.f0_tracks over the voiced frames of each
+    symbol's segment, both sides, one more copy to the host; None for a row without a waveform or without a path.  It draws
+    nothing."""
+    B = len(g.rows)
+    syn_found, syn_dur, syn_start = g.syn._search_rows([g.alignments[b, :g.n[b], :g.lens[b]] for b in range(B)], max_step)
+    rec_als = g.syn._forced_alignments([row[1] for row in g.rows], g.ref_mels, g.n_uniq, g.which)
+    rec_found, rec_dur, rec_start = g.syn._search_rows(rec_als, max_step)
+    none = (None, None, None)
+    fields = [E.duration_fields((syn_found[b] or none)[0], (rec_found[b] or none)[0], (syn_found[b] or none)[2],
+                                (rec_found[b] or none)[2]) for b in range(B)]
+    if not f0:
+        return fields
+    for row in fields:
+        row.update(dict.fromkeys(E.DURATION_F0_KEYS))
+    if not g.with_wav:
+        return fields
+    ref_track, syn_track = g.f0_tracks
+    f0y = g.ref(ref_track).contiguous()
+    f0x = torch.zeros(B, max(g.n), device=g.mel.device)
+    width = min(max(g.n), syn_track.size(1))
+    f0x[g.wav_index, :width] = syn_track[:, :width]
+    seg_x = t2v_hip.segment_means(f0x, f0x > 0, syn_start, syn_dur)
+    seg_y = t2v_hip.segment_means(f0y, f0y > 0, rec_start, rec_dur)
+    host = torch.stack([seg_x.sums.double(), seg_x.counts.double(), seg_y.sums.double(), seg_y.counts.double()], 1).cpu().tolist()
+    for b in g.with_wav:
+        if syn_found[b] is not None and rec_found[b] is not None:
+            L = g.lens[b]
+            fields[b].update(E.segment_f0_fields(*(plane[:L] for plane in host[b])))
+    return fields
+
+
 def voice(g):
     """The voice quality of both sides (evaluation.VOICE_KEYS): `t2v_hip.voice_quality` on the same two waveforms as `prosody`
     and `energy`, which it shares (the vocoder runs once per group).  One copy of the planes evaluation.VOICE_TRACKS to the

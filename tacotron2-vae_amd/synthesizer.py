@@ -713,13 +713,105 @@ class Synthesizer(object):
         fields = [alignment_fields(focus[b], stats[b], n[b], lens[b]) for b in range(len(n))]
         return fields, (host[:, 9:] if with_path else None)
 
+    def _forced_alignments(self, texts, mels, n_frames, which=None):
+        """The teacher-forced alignments of recordings against texts: row b is texts[b] read against the first
+        n_frames[which[b]] frames of mels[which[b]] (which: None = row b's own).  One model forward per row, B = 1: the
+        reference's encoder convolutions see the pad embedding of a padded batch, so only a batch of one gives the utterance
+        alone.  eval mode, no gradients; the Prenet dropout stays on as in the reference (model.Prenet), with the masks of
+        hparams.seed at the teacher-forced mask index of a model's first forward: the conv-block counter that index is taken
+        from is set to 0 for every row and put back afterwards, and so is the decoder's call counter, so a row's alignment
+        depends on nothing that ran before it and the free-running seeds go on as if this had not run.  Returns a list of
+        (n_frames, n_symbols) device tensors."""
+        import model as M
+        self.model.eval()
+        dec = self.model.decoder
+        calls, blocks = dec._calls, M._block_calls[0]
+        out = []
+        try:
+            with torch.no_grad():
+                for b, text in enumerate(texts):
+                    k = b if which is None else which[b]
+                    ids = text_to_sequence(text, ['korean_cleaners'])
+                    if len(ids) < 1:
+                        raise ValueError("a text maps to no symbols")
+                    M._block_calls[0] = 0
+                    dev = mels.device
+                    inputs = (torch.tensor([ids], dtype=torch.int64, device=dev), torch.tensor([len(ids)], dtype=torch.int64, device=dev),
+                              mels[k:k + 1, :, :n_frames[k]].contiguous(), len(ids),
+                              torch.tensor([n_frames[k]], dtype=torch.int64, device=dev), None, None)
+                    out.append(self.model(inputs)[3][0, :n_frames[k], :len(ids)])      # cut to the true frame count
+        finally:
+            dec._calls, M._block_calls[0] = calls, blocks
+        return out
+
+    @staticmethod
+    def _search_rows(als, max_step):
+        """`t2v_hip.mas` on a list of (frames, symbols) device tensors: they are copied into one zero-padded tensor and searched
+        in one call; a row without a feasible path is left out of it.  Returns (per row None or (durations, starts: host lists of
+        its symbols, mean log-probability), durations, starts: (rows, widest symbols) int32 on the device, 0 for the rows left
+        out).  One copy to the host (the score rides along as an int32 bit pattern)."""
+        import t2v_hip
+        live = [b for b, a in enumerate(als) if t2v_hip.mas_feasible(a.size(0), a.size(1), max_step)]
+        found = [None] * len(als)
+        dev = als[0].device
+        width = max(a.size(1) for a in als)
+        durations = torch.zeros(len(als), width, device=dev, dtype=torch.int32)
+        starts = torch.zeros(len(als), width, device=dev, dtype=torch.int32)
+        if not live:
+            return found, durations, starts
+        n, L = [als[b].size(0) for b in live], [als[b].size(1) for b in live]
+        A = torch.zeros(len(live), max(n), max(L), device=dev)
+        for k, b in enumerate(live):
+            A[k, :n[k], :L[k]] = als[b]
+        r = t2v_hip.mas(A, n, L, max_step)
+        at = torch.tensor(live, device=dev)
+        durations[at, :max(L)] = r.durations
+        starts[at, :max(L)] = r.starts
+        host = torch.cat([r.durations, r.starts, r.score.view(torch.int32)[:, None]], 1).cpu()
+        logp = host[:, 2 * max(L)].contiguous().view(torch.float32).tolist()
+        for k, b in enumerate(live):
+            found[b] = (host[k, :L[k]].tolist(), host[k, max(L):max(L) + L[k]].tolist(), logp[k])
+        return found, durations, starts
+
+    def durations(self, rows, batch_size=8, max_step=1):
+        """How long does each symbol of a recording last?  rows: filelist rows (audio_path, text, speaker, emotion).  The model
+        runs teacher-forced on each recording (`_forced_alignments`: one utterance per forward call, eval mode, no gradients)
+        and the best monotonic path through its alignments (`t2v_hip.mas`, steps of at most max_step symbols per frame) segments
+        the recording into the text's own symbols; only the search is batched, over the alignments of batch_size rows.
+        Returns one dict per row, in input order: `durations` and `starts` (host lists of n_symbols frame counts and first
+        frames; the durations sum to n_frames), `n_frames`, `n_symbols` and `align_logp`, the mean log attention weight along
+        the path (low for a transcript that does not match its audio).  A row whose text has more symbols than its frames can
+        reach has None for durations, starts and align_logp.  A row's result does not depend on its group."""
+        import t2v_hip
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
+        if isinstance(max_step, bool) or int(max_step) != max_step or not 1 <= max_step <= t2v_hip.MAS_MAX_STEP:
+            raise ValueError("max_step %r must be an integer in 1..%d" % (max_step, t2v_hip.MAS_MAX_STEP))
+        if self.model is None:
+            raise RuntimeError("durations: no model (load_checkpoint() or load() first)")
+        rows = list(rows)
+        out = []
+        for i0 in range(0, len(rows), batch_size):
+            group = rows[i0:i0 + batch_size]
+            uniq = list(dict.fromkeys(r[0] for r in group))
+            mels, n_uniq = self.load_mels(uniq)
+            als = self._forced_alignments([r[1] for r in group], mels, n_uniq, [uniq.index(r[0]) for r in group])
+            for al, found in zip(als, self._search_rows(als, int(max_step))[0]):
+                d, s, logp = found or (None, None, None)
+                out.append({'durations': d, 'starts': s, 'n_frames': al.size(0), 'n_symbols': al.size(1), 'align_logp': logp})
+        return out
+
     @torch.no_grad()
-    def alignment(self, texts, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0), batch_size=8):
+    def alignment(self, texts, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0), batch_size=8, mas=False,
+                  max_step=1):
         """Did the decoder read these sentences?  The texts are synthesised as `synthesize_batch` does (same conditioning
         arguments, batch_size texts at a time, in input order, the decoder's seeds as len(texts) synthesize() calls) and
         their alignments scored by `t2v_hip.alignment_stats`.  Returns one dict per text: evaluation.ALIGNMENT_KEYS,
         `n_frames`, and `durations`, a host list of n_symbols frame counts: how many frames attended each text symbol most
-        (the histogram of the argmax path; it sums to n_frames)."""
+        (the histogram of the argmax path; it sums to n_frames).  mas=True adds `mas_durations`, the frames per symbol along
+        the best monotonic path through the same alignments (`t2v_hip.mas` with steps of at most max_step: a segmentation,
+        which the histogram is not), and `align_logp`, the mean log weight along it; both None for a text with more symbols
+        than its frames can reach."""
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
         if self.model is None:
@@ -738,15 +830,19 @@ class Synthesizer(object):
                 list(ratios[i0:i0 + batch_size]) if per_text else ratios)
             n = n_frames.tolist()
             fields, paths = self._alignment_rows(al, n, lens, with_path=True)
+            if mas:
+                forced = self._search_rows([al[b, :n[b], :lens[b]] for b in range(len(chunk))], max_step)[0]
             for b, f in enumerate(fields):
                 f['n_frames'] = n[b]
                 f['durations'] = torch.bincount(paths[b, :n[b]].long(), minlength=lens[b]).tolist()
+                if mas:
+                    f['mas_durations'], _, f['align_logp'] = forced[b] or (None, None, None)
                 out.append(f)
         return out
 
     @torch.no_grad()
     def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False,
-                 energy=False, voice=False):
+                 energy=False, voice=False, durations=False, max_step=1):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and compared with its own recording.  condition='ref':
         the style comes from that recording (copy synthesis; its mel is computed once, for the style and for the comparison);
@@ -763,6 +859,10 @@ class Synthesizer(object):
         without prosody, and with energy evaluation.ENERGY_ALIGNED_KEYS, with voice evaluation.VOICE_ALIGNED_KEYS come with
         it.  With speed or pitch on the vocoder the waveform's tracks lie on another time axis than the mels' warping path:
         aligned together with prosody, energy or voice is then a ValueError.
+        durations: `scoring.durations`, evaluation.DURATION_KEYS: the free-running alignments of the synthesis and the
+        teacher-forced alignments of the recording, each forced onto the row's text by `t2v_hip.mas` with steps of at most
+        max_step; with prosody evaluation.DURATION_F0_KEYS come with it, and with speed or pitch on the vocoder the two together
+        are the ValueError of aligned, for its reason.  The teacher-forced passes take no decoder seed.
         style: `scoring.style_mu` per group and `scoring.style_records` after the last, evaluation.STYLE_KEYS; None for a row
         decoded to fewer than the encoder's 2 frames.  style_k is lowered to (distinct recordings - 1) when there are too few;
         fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The result is then an
@@ -788,6 +888,13 @@ class Synthesizer(object):
             raise ValueError("evaluate(aligned=True) with prosody, energy or voice compares tracks frame by frame along the mels' "
                              "path, and the vocoder's speed %g / pitch %g put its waveform on another time axis: use one or the other"
                              % (self.vocoder.speed, self.vocoder.pitch))
+        if durations:
+            if isinstance(max_step, bool) or int(max_step) != max_step or not 1 <= max_step <= t2v_hip.MAS_MAX_STEP:
+                raise ValueError("max_step %r must be an integer in 1..%d" % (max_step, t2v_hip.MAS_MAX_STEP))
+            if prosody and (self.vocoder.stretch[0] != self.vocoder.stretch[1] or self.vocoder.shift[0] != self.vocoder.shift[1]):
+                raise ValueError("evaluate(durations=True) with prosody reads the pitch track over the frames of the alignments' "
+                                 "path, and the vocoder's speed %g / pitch %g put its waveform on another time axis: use one or "
+                                 "the other" % (self.vocoder.speed, self.vocoder.pitch))
         if energy:
             t2v_hip.kweight_coefficients(self.hparams.sampling_rate)        # an unsupported rate is refused before any work
             self._need_frame_grid('evaluate(energy=True)')
@@ -825,6 +932,8 @@ class Synthesizer(object):
                 parts.append(scoring.voice(g))
             if aligned:
                 parts.append(scoring.aligned(g, f0=prosody, energy=energy, voice=voice))
+            if durations:
+                parts.append(scoring.durations(g, int(max_step), f0=prosody))
             if style:
                 syn_mu += scoring.style_mu(g, rec_mu)
             records += [{k: v for fields in parts for k, v in fields[b].items()} for b in range(len(group))]

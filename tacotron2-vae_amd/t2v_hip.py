@@ -2421,6 +2421,111 @@ def alignment_stats(alignments, n_frames, text_lengths, max_jump=3, cover_min=0.
     return AlignmentStats(path, mass, focus, stats)
 
 
+MAS_MAX_SYMBOLS = _ABI.define('T2V_MAS_MAX_SYMBOLS')      # the two live rows of Q sit in LDS
+MAS_FLOOR = float(_ABI._macros['T2V_MAS_FLOOR'].rstrip('fF'))      # the header's fp32 literal: a(t, j) = max(A, floor)
+MAS_MAX_STEP = 3
+
+MonotonicAlignment = collections.namedtuple('MonotonicAlignment', 'path durations starts score')
+MonotonicAlignment.__doc__ = """What mas() returns.  path (B, N) int32, -1 past n_frames[b]; durations (B, T_in) int32, 0 past
+n_ids[b]; starts (B, T_in) int32, the prefix sums of durations (0 past n_ids[b]); score (B,) float32, the mean over the row's
+frames of ln max(alignments[b, t, path[t]], MAS_FLOOR)."""
+
+
+def mas_feasible(n_frames, n_ids, max_step=1):
+    """whether a monotonic path from symbol 0 at frame 0 to symbol n_ids - 1 at frame n_frames - 1 exists with steps of at most
+    max_step symbols per frame (host integers)"""
+    return n_frames >= 1 and n_ids >= 1 and n_ids - 1 <= (n_frames - 1) * max_step
+
+
+def mas(alignments, n_frames, n_ids, max_step=1):
+    """Forced alignment by monotonic alignment search (csrc/durations.hip k_mas): the best monotonic path through each
+    alignment matrix.  alignments: (B, N, T_in) float32 CUDA tensor of attention weights, row b valid on its first n_frames[b]
+    frames and n_ids[b] symbols (lists, CPU tensors or device int tensors); nothing outside is read and the tensor is never
+    written.  Strides as `alignment_stats`: the last dimension has stride 1, the other two are passed through.  A path p has
+    p[0] = 0, p[n-1] = L - 1 and 0 <= p[t] - p[t-1] <= max_step (1..3; above 1 a symbol may be skipped and gets duration 0);
+    the one returned maximises sum_t ln max(alignments[b, t, p[t]], MAS_FLOOR) by the fp32 recurrence of include/t2vae.h, ties
+    going to the smaller step.  Returns a MonotonicAlignment.  A row without a feasible path (n_ids - 1 > (n_frames - 1)
+    max_step) is a ValueError before anything is launched; T_in above MAS_MAX_SYMBOLS too.  A row gives the same bits alone,
+    in any batch, at any stride and with any padding."""
+    lib = load_library()
+    if not torch.is_tensor(alignments) or alignments.dim() != 3 or alignments.dtype != torch.float32:
+        raise ValueError("mas: alignments must be a float32 (B, N, T_in) tensor, got %s %s"
+                         % (getattr(alignments, 'dtype', type(alignments)), tuple(getattr(alignments, 'shape', ()))))
+    if not alignments.is_cuda:
+        raise _AlignDeviceError("mas: alignments %s live on %s; this path has no CPU fallback"
+                                % (tuple(alignments.shape), alignments.device))
+    B, N, T_in = alignments.shape
+    if B < 1 or N < 1 or T_in < 1:
+        raise ValueError("mas: empty input %s" % (tuple(alignments.shape),))
+    if T_in > MAS_MAX_SYMBOLS:
+        raise ValueError("mas: %d symbols per row; at most %d are supported" % (T_in, MAS_MAX_SYMBOLS))
+    sb, st, sj = alignments.stride()
+    if (T_in > 1 and sj != 1) or (N > 1 and st < T_in) or (B > 1 and sb < (N - 1) * st + T_in):
+        raise ValueError("mas: strides %s of shape %s; the last dimension must have stride 1 and rows and frames may not overlap"
+                         % ((sb, st, sj), (B, N, T_in)))
+    st = max(st, T_in) if N == 1 else st              # a dimension of size 1 may report any stride
+    sb = max(sb, (N - 1) * st + T_in) if B == 1 else sb
+    if isinstance(max_step, bool) or int(max_step) != max_step or not 1 <= max_step <= MAS_MAX_STEP:
+        raise ValueError("mas: max_step %r must be an integer in 1..%d" % (max_step, MAS_MAX_STEP))
+    max_step = int(max_step)
+    n = _checked_lengths(n_frames, B, 1, N, "mas: n_frames must be %d integer frame counts" % B,
+                         "mas: every n_frames must be in 1..%d (frames stored per row)" % N)
+    L = _checked_lengths(n_ids, B, 1, T_in, "mas: n_ids must be %d integer symbol counts" % B,
+                         "mas: every n_ids must be in 1..%d (symbols stored per row)" % T_in)
+    for b, (nb, Lb) in enumerate(zip(n.tolist(), L.tolist())):
+        if not mas_feasible(nb, Lb, max_step):
+            raise ValueError("mas: row %d has %d symbols and %d frames: no monotonic path with steps <= %d reaches the last "
+                             "symbol" % (b, Lb, nb, max_step))
+    dev = alignments.device
+    n, L = n.to(dev), L.to(dev)
+    path = torch.empty(B, N, device=dev, dtype=torch.int32)
+    durations = torch.empty(B, T_in, device=dev, dtype=torch.int32)
+    starts = torch.empty(B, T_in, device=dev, dtype=torch.int32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    scratch = torch.empty(lib.t2v_mas_scratch_bytes(B, N, T_in), device=dev, dtype=torch.uint8)
+    _check(lib.t2v_mas(_p(alignments), sb, st, _p(n), _p(L), B, N, T_in, max_step, _p(path), N, _p(durations), _p(starts), T_in,
+                       _p(score), _p(scratch), _stream()), 't2v_mas')
+    return MonotonicAlignment(path, durations, starts, score)
+
+
+class SegmentMeans(collections.namedtuple('SegmentMeans', 'sums counts')):
+    """What segment_means() returns: sums (B, T_in) float32 and counts (B, T_in) int32 per symbol; `means` divides them (NaN
+    where a symbol has no counted frame)."""
+    __slots__ = ()
+
+    @property
+    def means(self):
+        return self.sums / self.counts.to(self.sums.dtype)
+
+
+def segment_means(track, counted, starts, durations):
+    """Sums of a frame track over the segments of a monotonic path (csrc/durations.hip k_segment_means).  track: (B, frames)
+    float32 CUDA tensor (an F0 or a level track); counted: None (every frame counts) or a bool / uint8 tensor of track's shape;
+    starts, durations: (B, T_in) int32 as `mas` returns them.  Symbol j of row b covers the frames [starts, starts + durations),
+    clamped to the track; its counted frames are added in ascending frame order.  Returns a SegmentMeans; a segment of
+    duration 0, or without a counted frame, has sum 0 and count 0."""
+    lib = _require_gpu(track, counted, starts, durations)
+    if track.dim() != 2 or track.dtype != torch.float32 or track.size(0) < 1 or track.size(1) < 1:
+        raise ValueError("segment_means: track must be a non-empty float32 (B, frames) tensor, got %s %s"
+                         % (track.dtype, tuple(track.shape)))
+    B, frames = track.shape
+    for name, t in (('starts', starts), ('durations', durations)):
+        if t.dim() != 2 or t.dtype != torch.int32 or t.size(0) != B or t.size(1) < 1 or t.shape != starts.shape:
+            raise ValueError("segment_means: %s must be an int32 (%d, T_in) tensor, got %s %s" % (name, B, t.dtype, tuple(t.shape)))
+    if counted is not None:
+        if counted.dtype not in (torch.bool, torch.uint8) or counted.shape != track.shape:
+            raise ValueError("segment_means: counted must be a bool or uint8 tensor of track's shape %s, got %s %s"
+                             % (tuple(track.shape), counted.dtype, tuple(counted.shape)))
+        counted = counted.contiguous()
+    track, starts, durations = track.contiguous(), starts.contiguous(), durations.contiguous()
+    T_in = starts.size(1)
+    sums = torch.empty(B, T_in, device=track.device, dtype=torch.float32)
+    counts = torch.empty(B, T_in, device=track.device, dtype=torch.int32)
+    _check(lib.t2v_segment_means(_p(track), _p(counted), frames, _p(starts), _p(durations), T_in, B, T_in, _p(sums), _p(counts),
+                                 T_in, _stream()), 't2v_segment_means')
+    return SegmentMeans(sums, counts)
+
+
 TSNE_MAX_POINTS = _ABI.define('T2V_TSNE_MAX_POINTS')      # P is dense fp32, 1 GiB there
 TSNE_MAX_DIM = 64
 TSNE_EXAG_ITERS = _ABI.define('T2V_TSNE_EXAG_ITERS')
