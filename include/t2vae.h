@@ -294,6 +294,44 @@ int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, cons
                            uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                            void* stream);
 
+/* ------------------------------------------------------------------ reverse passes with an alignment gradient
+ * The five reverse passes above for a loss that reads the attention itself (t2v_guided_attention): the same calls with one more
+ * operand, dAL — the upstream gradient of the alignments, contiguous (T_out, B, T_in) floats, dAL[t] belonging to the alignment of
+ * decoder step t (arena row AL[t + 1]).  Inside the softmax backward of step t it is one more addend of the gradient with respect
+ * to alpha(t).  dAL == NULL: no such gradient — the pass is then the kernel of the call above, bit for bit (the calls above are
+ * these with NULL). */
+int t2v_decoder_train_bwd_align(const t2v_dec_weights* w, const t2v_dec_train_bufs* s,
+                                const t2v_dec_bwd_bufs* g, const float* dAL, int B, int T_in, int T_out,
+                                float p_att, float p_dec, uint64_t seed, void* stream);
+int t2v_decoder_bwd_achain_align(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
+                                 const float* dHC, const float* dAL, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP,
+                                 float* scratch, uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec,
+                                 uint64_t seed, void* stream);
+int t2v_decoder_bwd_achain_prepared_align(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw,
+                                          const t2v_dec_train_bufs* s, const float* dHC, const float* dAL, float* DGA, float* DGD,
+                                          float* DCTX, float* DV, float* DQP, float* scratch, uint32_t* err_word, int B, int T_in,
+                                          int T_out, float p_att, float p_dec, uint64_t seed, void* stream);
+int t2v_decoder_bwd_persistent16_align(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* dHC,
+                                       const float* dAL, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
+                                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
+                                       void* stream);
+int t2v_decoder_bwd_persistent16_prepared_align(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s,
+                                                const float* dHC, const float* dAL, float* DGA, float* DGD, float* DCTX, float* DV,
+                                                float* DQP, float* scratch, uint32_t* err_word, int B, int T_in, int T_out,
+                                                float p_att, float p_dec, uint64_t seed, void* stream);
+
+/* ------------------------------------------------------------------ guided attention loss (csrc/guided_attention.hip)
+ * The penalty on attention weight far from the diagonal (Tachibana et al., DCTTS; ESPnet's GuidedAttentionLoss), value and gradient:
+ *   W[b][t][j] = 1 - exp(-(j / N_b - t / T_b)^2 / (2 sigma^2))  for t < T_b and j < N_b, else 0      (N_b = in_len[b], T_b = out_len[b])
+ *   D = sum_b T_b N_b,   L = sum A W / D,   G = W / D.
+ * A: alignments (B, T, T_in) with element strides sb, st, sj (whatever layout the decoder returned them in).  loss: one float.
+ * G: contiguous (T, B, T_in) — the dAL operand of the passes above.  part: t2v_guided_attention_part_doubles(B, T) doubles of
+ * scratch.  Products in fp32, summed in fp64 in an order fixed by the shapes: the same bits from run to run.  D is computed on the
+ * device; nothing is read back, and the call can be captured in a graph.  Lengths are clamped to [0, T] / [0, T_in]. */
+long t2v_guided_attention_part_doubles(int B, int T);
+int t2v_guided_attention(const float* A, long sb, long st, long sj, const int64_t* in_len, const int64_t* out_len,
+                         float* loss, float* G, double* part, int B, int T, int T_in, float sigma, void* stream);
+
 /* ------------------------------------------------------------------ free-running decode
  * Decoder.inference (model.py:428-464) == the synthesizer loop (synthesizer.py:139-154): steps
  * t_begin..t_end-1, each = attention_rnn → attention → decoder_rnn → 80-mel/gate projection → Prenet of

@@ -100,7 +100,9 @@ __global__ __launch_bounds__(256) void k_lstm_bwd256(LstmBwdArgs a) {
 #define ATB_THREADS 256
 #define ATB_SPIN_LIMIT 4000000u
 
-template <int JS>
+// DAL: a.dal_t, the upstream gradient of alpha(t) itself (a loss that reads the attention), joins gp: gfull0 feeds the own
+// positions' dalpha and the dot product, nothing else.
+template <int JS, bool DAL>
 __device__ __forceinline__ void attn_bwd_body(const AttnBwdArgs& a, const int b, const int s, const int S) {
     constexpr int NJT = JS / 16;           // 16-position MFMA tiles per slice
     constexpr int PW = JS + 30;            // width of a partial dcat row
@@ -170,6 +172,7 @@ __device__ __forceinline__ void attn_bwd_body(const AttnBwdArgs& a, const int b,
         }
 #pragma unroll
         for (int u = 0; u < 3; ++u) { gp += pv[u][0]; gc += pv[u][1]; }
+        if (DAL) gp += a.dal_t[(size_t)b * Tp + j];
         a.GC[((size_t)b * S + s) * Tcap + j] = gc;
         gfull0[j] = gp;
         gfull1[j] = gc;
@@ -458,19 +461,19 @@ __device__ __forceinline__ void cell_bwd_body(const CellBwdArgs& a, const int cb
 }
 
 // One launch per reverse step: workgroups [0, B*S) = attention backward slices, then 64 cell-backward workgroups.
-template <int JS, int NPP>
+template <int JS, int NPP, bool DAL>
 __global__ __launch_bounds__(256) void k_attn_cell_bwd(AttnBwdArgs a, CellBwdArgs c, int nattn, int S) {
     const int blk = blockIdx.x;
-    if (blk < nattn) attn_bwd_body<JS>(a, blk / S, blk % S, S);
+    if (blk < nattn) attn_bwd_body<JS, DAL>(a, blk / S, blk % S, S);
     else cell_bwd_body<NPP>(c, blk - nattn);
 }
-template <int JS>
+template <int JS, bool DAL>
 static void launch_attn_cell_bwd(const AttnBwdArgs& fa, const CellBwdArgs& c, int nattn, int S, int B, size_t lds, hipStream_t stream) {
     const dim3 grid(nattn + T2V_H / 16);
-    if (B <= 2) k_attn_cell_bwd<JS, 1><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
-    else if (B <= 4) k_attn_cell_bwd<JS, 2><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
-    else if (B <= 8) k_attn_cell_bwd<JS, 4><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
-    else k_attn_cell_bwd<JS, 8><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
+    if (B <= 2) k_attn_cell_bwd<JS, 1, DAL><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
+    else if (B <= 4) k_attn_cell_bwd<JS, 2, DAL><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
+    else if (B <= 8) k_attn_cell_bwd<JS, 4, DAL><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
+    else k_attn_cell_bwd<JS, 8, DAL><<<grid, 256, lds, stream>>>(fa, c, nattn, S);
 }
 
 extern "C" int t2v_attn_bwd_slices(int T_in) { return T_in < 1 ? 0 : t2v_attn_bwd_slices_(T_in); }
@@ -478,7 +481,7 @@ extern "C" int t2v_attn_bwd_slices(int T_in) { return T_in < 1 ? 0 : t2v_attn_bw
 // mask bits: 1 = k_lstm_bwd256, 2 = k_attn_cell_bwd (3 = the reverse pass; single bits = measurement replays)
 static int launch_train_bwd(const t2v_dec_weights* w, const t2v_dec_train_bufs* s,
                             const t2v_dec_bwd_bufs* g, int B, int T_in, int T_out,
-                            float p_att, float p_dec, uint64_t seed, void* stream_, int mask) {
+                            float p_att, float p_dec, uint64_t seed, void* stream_, int mask, const float* dAL = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!w || !s || !g || B < 1 || B > 16 || T_in < 1 || T_in > T2V_MAX_T_IN || T_out < 1) return T2V_ERR_ARG;
     if (!w->packB_att || !w->packB_dec || !w->wcomb) return T2V_ERR_ARG;
@@ -522,6 +525,7 @@ static int launch_train_bwd(const t2v_dec_weights* w, const t2v_dec_train_bufs* 
             f.YD = g->YD;
             f.YA = g->YA;
             f.al_cur = s->AL + (size_t)(t + 1) * B * T_in;
+            f.dal_t = dAL ? dAL + (size_t)t * B * T_in : nullptr;
             f.memory = s->memory;
             f.wcomb = w->wcomb;
             f.v = w->v;
@@ -567,16 +571,28 @@ static int launch_train_bwd(const t2v_dec_weights* w, const t2v_dec_train_bufs* 
         c.prof = g_t2v_prof ? g_t2v_prof + 24 : nullptr;
         const int nattn = have_attn ? B * S : 0;
         if (!(mask & 2)) continue;
-        if (JS == 16) launch_attn_cell_bwd<16>(fa, c, nattn, S, B, lds, stream);
-        else launch_attn_cell_bwd<32>(fa, c, nattn, S, B, lds, stream);
+        // without an alignment gradient the step is the pointer-less kernel, as it always was
+        if (dAL) {
+            if (JS == 16) launch_attn_cell_bwd<16, true>(fa, c, nattn, S, B, lds, stream);
+            else launch_attn_cell_bwd<32, true>(fa, c, nattn, S, B, lds, stream);
+        } else {
+            if (JS == 16) launch_attn_cell_bwd<16, false>(fa, c, nattn, S, B, lds, stream);
+            else launch_attn_cell_bwd<32, false>(fa, c, nattn, S, B, lds, stream);
+        }
     }
     return t2v_check_launch();
 }
 
+// dAL: upstream gradient of the alignments, contiguous (T_out, B, T_in), or NULL
+extern "C" int t2v_decoder_train_bwd_align(const t2v_dec_weights* w, const t2v_dec_train_bufs* s,
+                                           const t2v_dec_bwd_bufs* g, const float* dAL, int B, int T_in, int T_out,
+                                           float p_att, float p_dec, uint64_t seed, void* stream_) {
+    return launch_train_bwd(w, s, g, B, T_in, T_out, p_att, p_dec, seed, stream_, 3, dAL);
+}
 extern "C" int t2v_decoder_train_bwd(const t2v_dec_weights* w, const t2v_dec_train_bufs* s,
                                      const t2v_dec_bwd_bufs* g, int B, int T_in, int T_out,
                                      float p_att, float p_dec, uint64_t seed, void* stream_) {
-    return launch_train_bwd(w, s, g, B, T_in, T_out, p_att, p_dec, seed, stream_, 3);
+    return t2v_decoder_train_bwd_align(w, s, g, nullptr, B, T_in, T_out, p_att, p_dec, seed, stream_);
 }
 
 extern "C" int t2v_decoder_replay_bwd_kernels(const t2v_dec_weights* w, const t2v_dec_train_bufs* s,

@@ -3,7 +3,7 @@
 // transposed weight stream per reverse step) stays the general path; this file serves B <= 6, T_in <= 576
 // (t2v_decoder_bwd_persist_supported); decoder_train_bwd_persist16.hip is its bf16 counterpart for B <= 16.
 //
-// k_achain_bwd<NB, LONG> runs the whole reverse recurrence on 256 resident workgroups in three roles (details at PBAArgs and
+// k_achain_bwd<NB, LONG, DAL> runs the whole reverse recurrence on 256 resident workgroups in three roles (details at PBAArgs and
 // at pba_na below):
 //   T  attention(t) backward of one item and one slice of encoder positions (t2v_attn_role_bwd.h, shared with the bf16 kernel),
 //   A  attention_rnn: dga(t+1) -> Wcat_att^T -> [d h_att(t) | d ctx(t)] -> (T role) -> dq(t) -> W_q^T -> cell backward -> dga(t)
@@ -267,7 +267,8 @@ struct PBAArgs {
     unsigned long long* prof;
     // weight-gradient epilogue of the decoder_rnn role (pba_dw_epilogue; dw_planes == nullptr: the role returns as before)
     uint4* dw_planes; float* dw_ih; float* dw_hh; unsigned* dw_ctr;
-    int dw_ld_ih, dw_ld_hh, dw_accumulate, dw_cap, dw_margin;
+    int dw_ld_ih, dw_ld_hh, dw_accumulate, dw_cap, dw_margin;    // last, so that every field above sits where it sat before the operand existed
+    const float* dAL;           // (T,B,T_in) upstream gradient of the alignments (the DAL kernels; nullptr in the others)
 };
 // phase profile (tools/dbg/persist_bwd_prof.py): slot I accumulates, over all steps, the cycles since the previous stamp
 #define PBA_STAMP(COND, I) do { if (a.prof && (COND) && threadIdx.x == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); \
@@ -339,9 +340,9 @@ struct PBAAttnHooks {
     }
     __device__ __forceinline__ void pass_end() { PBA_PROF_FLUSH(blockIdx.x == 0, 8, 4); }
 };
-template <int JS, int NWV, int NB>
+template <int JS, int NWV, int NB, bool DAL>
 __device__ __forceinline__ void pba_attention(const PBAArgs& a, float* lds, const int b, const int s) {
-    t2v_attn_role_bwd<JS, NWV, PBAAttnHooks<NB>>(a, lds, b, s);
+    t2v_attn_role_bwd<JS, NWV, PBAAttnHooks<NB>, DAL>(a, lds, b, s);
 }
 
 // y[C0 + c][pair] = sum_j w[C0 + c][j] * x[k_j][pair] for NC <= 2 of the thread's columns into v[16] (two columns x 8 item
@@ -981,7 +982,8 @@ __device__ __forceinline__ void pba_attention_rnn_role(const PBAArgs& a, float* 
 // NB — 4: B <= 4, 6: B = 5, 6.  LONG — 224 < T_in <= 576: the attention role as 96-position slices on all eight waves (the form
 // round 4 built for "one workgroup per item"; with S <= 6 slices an item of 555 symbols takes as many workgroups as the
 // headline shape's 84 symbols in 16-position slices, so the LSTM roles keep their 4 / 5 units per workgroup).
-template <int NB, bool LONG>
+// DAL — the attention role adds a.dAL (t2v_attn_role_bwd.h); the other roles are the same.
+template <int NB, bool LONG, bool DAL>
 __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wg = blockIdx.x;
@@ -989,7 +991,7 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     // (-DPBA_ONLY=1..4 builds ONE role into the kernel: `hipcc -Rpass-analysis=kernel-resource-usage` then reports that role's
     // own register pressure — the combined kernel always shows the maximum over the roles; tools/dbg/role_regs.sh)
 #if defined(PBA_ONLY) && PBA_ONLY == 1
-    pba_attention<16, 4, NB>(a, lds, wg / S, wg % S);
+    pba_attention<16, 4, NB, DAL>(a, lds, wg / S, wg % S);
 #elif defined(PBA_ONLY) && PBA_ONLY == 2
     pba_attention_rnn_role<NB, 12, 6>(a, lds, wg - NT, NA);
 #elif defined(PBA_ONLY) && PBA_ONLY == 3
@@ -998,9 +1000,9 @@ __global__ __launch_bounds__(PB_THREADS) void k_achain_bwd(PBAArgs a) {
     pba_decoder_role<NB>(a, lds, wg - NT - NA, ND);
 #else
     if (wg < NT) {
-        if (LONG) pba_attention<96, 8, NB>(a, lds, wg / S, wg % S);
-        else if (a.T_in <= 128) pba_attention<16, 4, NB>(a, lds, wg / S, wg % S);
-        else pba_attention<32, 4, NB>(a, lds, wg / S, wg % S);
+        if (LONG) pba_attention<96, 8, NB, DAL>(a, lds, wg / S, wg % S);
+        else if (a.T_in <= 128) pba_attention<16, 4, NB, DAL>(a, lds, wg / S, wg % S);
+        else pba_attention<32, 4, NB, DAL>(a, lds, wg / S, wg % S);
     } else if (wg < NT + NA) {
         if (NA >= 114) pba_attention_rnn_role<NB, 9, 5>(a, lds, wg - NT, NA);
         else if (NA >= 86) pba_attention_rnn_role<NB, 12, 6>(a, lds, wg - NT, NA);
@@ -1084,12 +1086,18 @@ static int pba_dw_margin(int B, int T_out) {
     return (int)(1.25 * pair_us / 10.58) + 1;
 }
 
+template <int NB, bool LONG>
+static void pba_launch_kernel(const PBAArgs& a, size_t lds, hipStream_t stream) {
+    if (a.dAL) k_achain_bwd<NB, LONG, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
+    else k_achain_bwd<NB, LONG, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
+}
+
 // do_prepare: error word, sentinel fills, the factor arrays of both cells (functions of the forward activations alone: they may
 // run long before the reverse pass, next to the Postnet).  do_run: the pass itself.
 static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s,
                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
-                      void* stream_, bool do_prepare, bool do_run, const t2v_achain_dw* dw = nullptr) {
+                      void* stream_, bool do_prepare, bool do_run, const t2v_achain_dw* dw = nullptr, const float* dAL = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!s || !DQP || !scratch || !err_word) return T2V_ERR_ARG;
     if (do_run && (!w || !dHC || !DGA || !DGD || !DCTX || !DV)) return T2V_ERR_ARG;
@@ -1103,8 +1111,10 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
                          (long)T_out * B < 32))
         return T2V_ERR_ARG;
     static bool raised = false;
-    if (!t2v_persist_raise_lds({(const void*)k_achain_bwd<4, false>, (const void*)k_achain_bwd<6, false>,
-                                (const void*)k_achain_bwd<4, true>, (const void*)k_achain_bwd<6, true>}, raised))
+    if (!t2v_persist_raise_lds({(const void*)k_achain_bwd<4, false, false>, (const void*)k_achain_bwd<6, false, false>,
+                                (const void*)k_achain_bwd<4, true, false>, (const void*)k_achain_bwd<6, true, false>,
+                                (const void*)k_achain_bwd<4, false, true>, (const void*)k_achain_bwd<6, false, true>,
+                                (const void*)k_achain_bwd<4, true, true>, (const void*)k_achain_bwd<6, true, true>}, raised))
         return t2v_check_launch();
     if (do_prepare) {
         (void)hipMemsetAsync(err_word, 0, sizeof(uint32_t), stream);
@@ -1118,7 +1128,7 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
         a.wq = w->wq; a.wcomb = w->wcomb; a.v = w->v;
     }
     a.memory = s->memory; a.XS = s->XS; a.CA = s->CA; a.CD = s->CD; a.GA = s->GA; a.GD = s->GD; a.AL = s->AL; a.S = s->S;
-    a.dHC = dHC; a.DGA = DGA; a.DGD = DGD; a.DCTX = DCTX; a.DV = DV; a.DQX = DQP;
+    a.dHC = dHC; a.dAL = dAL; a.DGA = DGA; a.DGD = DGD; a.DCTX = DCTX; a.DV = DV; a.DQX = DQP;
     // the walk over the sections of pba_layout, in its order
     a.GXA = scratch;
     a.GXD = a.GXA + l.n_gx;
@@ -1154,22 +1164,30 @@ static int pba_launch(const t2v_dec_train_persist_weights* w, const t2v_dec_trai
     }
     if (!do_run) return t2v_check_launch();
     const size_t lds = pba_lds_bytes(B, T_in);
+    // without an alignment gradient the pass is the pointer-less kernel, as it always was
     if (T_in > PB_MAXT) {
-        if (B > 4) k_achain_bwd<6, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
-        else k_achain_bwd<4, true><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
+        if (B > 4) pba_launch_kernel<6, true>(a, lds, stream);
+        else pba_launch_kernel<4, true>(a, lds, stream);
     } else {
-        if (B > 4) k_achain_bwd<6, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
-        else k_achain_bwd<4, false><<<T2V_NWG, PB_THREADS, lds, stream>>>(a);
+        if (B > 4) pba_launch_kernel<6, false>(a, lds, stream);
+        else pba_launch_kernel<4, false>(a, lds, stream);
     }
     return t2v_check_launch();
 }
 
-// preparation + pass
+// preparation + pass; dAL: upstream gradient of the alignments, contiguous (T_out, B, T_in), or NULL
+extern "C" int t2v_decoder_bwd_achain_align(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
+                                            const float* dHC, const float* dAL, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP,
+                                            float* scratch, uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec,
+                                            uint64_t seed, void* stream_) {
+    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true, true, dw, dAL);
+}
 extern "C" int t2v_decoder_bwd_achain(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
                                       const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                       uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                                       void* stream_) {
-    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true, true, dw);
+    return t2v_decoder_bwd_achain_align(w, dw, s, dHC, nullptr, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed,
+                                        stream_);
 }
 
 // The preparation on its own (everything it needs exists when the FORWARD pass has ended) ...
@@ -1178,10 +1196,17 @@ extern "C" int t2v_decoder_bwd_achain_prepare(const t2v_dec_train_bufs* s, float
     return pba_launch(nullptr, s, nullptr, nullptr, nullptr, nullptr, nullptr, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed,
                       stream_, true, false);
 }
-// ... and the pass without it (same arguments as t2v_decoder_bwd_achain; scratch / DQP / err_word as handed to _prepare)
+// ... and the pass without it (same arguments as t2v_decoder_bwd_achain_align; scratch / DQP / err_word as handed to _prepare)
+extern "C" int t2v_decoder_bwd_achain_prepared_align(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw,
+                                                     const t2v_dec_train_bufs* s, const float* dHC, const float* dAL, float* DGA, float* DGD,
+                                                     float* DCTX, float* DV, float* DQP, float* scratch, uint32_t* err_word, int B, int T_in,
+                                                     int T_out, float p_att, float p_dec, uint64_t seed, void* stream_) {
+    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false, true, dw, dAL);
+}
 extern "C" int t2v_decoder_bwd_achain_prepared(const t2v_dec_train_persist_weights* w, const t2v_achain_dw* dw, const t2v_dec_train_bufs* s,
                                                const float* dHC, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                                uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                                                void* stream_) {
-    return pba_launch(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false, true, dw);
+    return t2v_decoder_bwd_achain_prepared_align(w, dw, s, dHC, nullptr, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att,
+                                                 p_dec, seed, stream_);
 }

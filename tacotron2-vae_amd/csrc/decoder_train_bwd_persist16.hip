@@ -63,6 +63,8 @@ struct Q16Args {
     uint64_t seed;
     const t2v_step_params* step;
     unsigned long long* prof;
+    // last, so that every field above sits where it sat before the operand existed
+    const float* dAL;           // (T,B,T_in) upstream gradient of the alignments (the DAL kernels; nullptr in the others)
 };
 // per-workgroup time line of TWO consecutive steps (t = T/2 + 1: slots 4..7, t = T/2: slots 0..3) on the chip-wide 100 MHz
 // counter: prof[64 + workgroup * 8 + slot] (tools/dbg/persist16_bwd_prof.py follows one turn of the chain through the roles)
@@ -390,21 +392,22 @@ struct Q16AttnHooks {
     __device__ __forceinline__ void stamp(int t, int point) { Q16_RT(point); }
     __device__ __forceinline__ void pass_end() {}
 };
-template <int JS, int NWV>
+template <int JS, int NWV, bool DAL>
 __device__ __forceinline__ void q16_attention(const Q16Args& a, float* lds, const int b, const int s) {
-    t2v_attn_role_bwd<JS, NWV, Q16AttnHooks>(a, lds, b, s);
+    t2v_attn_role_bwd<JS, NWV, Q16AttnHooks, DAL>(a, lds, b, s);
 }
 
-template <bool LONG>          // the attention role on 96-position slices (T_in > Q16_T32); the other roles are the same
+// LONG: the attention role on 96-position slices (T_in > Q16_T32); DAL: it adds a.dAL (t2v_attn_role_bwd.h); the other roles are the same
+template <bool LONG, bool DAL>
 __global__ __launch_bounds__(Q16_THREADS) void k_bwd_persist16(Q16Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int wg = blockIdx.x;
     const int S = a.S_sl, NT = a.B * S;
 #if defined(Q16_ONLY_T)
     if (wg < NT) {
-        if (LONG) q16_attention<96, 8>(a, lds, wg / S, wg % S);
-        else if (a.T_in <= 96) q16_attention<16, 4>(a, lds, wg / S, wg % S);
-        else q16_attention<32, 4>(a, lds, wg / S, wg % S);
+        if (LONG) q16_attention<96, 8, DAL>(a, lds, wg / S, wg % S);
+        else if (a.T_in <= 96) q16_attention<16, 4, DAL>(a, lds, wg / S, wg % S);
+        else q16_attention<32, 4, DAL>(a, lds, wg / S, wg % S);
     }
 #elif defined(Q16_ONLY_G)
     if (wg < 48) q16_gemv_role<false>(a, lds, wg); else q16_gemv_role<true>(a, lds, wg - 48);
@@ -413,9 +416,9 @@ __global__ __launch_bounds__(Q16_THREADS) void k_bwd_persist16(Q16Args a) {
 #else
     if (wg < Q16_MAXTWG) {
         if (wg >= NT) return;
-        if (LONG) q16_attention<96, 8>(a, lds, wg / S, wg % S);
-        else if (a.T_in <= 96) q16_attention<16, 4>(a, lds, wg / S, wg % S);
-        else q16_attention<32, 4>(a, lds, wg / S, wg % S);
+        if (LONG) q16_attention<96, 8, DAL>(a, lds, wg / S, wg % S);
+        else if (a.T_in <= 96) q16_attention<16, 4, DAL>(a, lds, wg / S, wg % S);
+        else q16_attention<32, 4, DAL>(a, lds, wg / S, wg % S);
         return;
     }
     const int j = wg - Q16_MAXTWG;
@@ -444,8 +447,11 @@ extern "C" int t2v_decoder_bwd_persist16_supported(int B, int T_in) {
     if (!(B >= 1 && B <= Q16_MAXB && T_in >= 1 && T_in <= Q16_MAXT_LONG)) return 0;
     if (B * q16_slices(T_in) > Q16_MAXTWG || q16_lds_bytes(T_in) > T2V_LDS_MAX) return 0;
     static bool raised = false;
-    return t2v_persist_resident(T_in > Q16_T32 ? (const void*)k_bwd_persist16<true> : (const void*)k_bwd_persist16<false>, Q16_THREADS,
-                                q16_lds_bytes(T_in), {(const void*)k_bwd_persist16<false>, (const void*)k_bwd_persist16<true>}, raised);
+    // (the DAL kernels differ from these by one load and one add of the attention role: same resources, same residency)
+    return t2v_persist_resident(T_in > Q16_T32 ? (const void*)k_bwd_persist16<true, false> : (const void*)k_bwd_persist16<false, false>,
+                                Q16_THREADS, q16_lds_bytes(T_in),
+                                {(const void*)k_bwd_persist16<false, false>, (const void*)k_bwd_persist16<true, false>,
+                                 (const void*)k_bwd_persist16<false, true>, (const void*)k_bwd_persist16<true, true>}, raised);
 }
 // layout of `scratch` (floats): GXA | GXD | PA | PD | GPX | DQT
 static void q16_layout(int B, int T_in, int T_out, size_t (&n)[6]) {
@@ -501,7 +507,7 @@ extern "C" int t2v_decoder_bwd_persistent16_prepare(float* DQP, float* scratch, 
     return t2v_check_launch();
 }
 
-static int q16_run(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* dHC,
+static int q16_run(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* dHC, const float* dAL,
                    float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                    uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                    void* stream_, bool prepare) {
@@ -523,7 +529,7 @@ static int q16_run(const t2v_dec_train_persist_weights* w, const t2v_dec_train_b
     a.w_ih_att = w->w_ih_att; a.w_hh_att = w->w_hh_att; a.w_ih_dec = w->w_ih_dec; a.w_hh_dec = w->w_hh_dec;
     a.wq = w->wq; a.wcomb = w->wcomb; a.v = w->v;
     a.memory = s->memory; a.XS = s->XS; a.CA = s->CA; a.CD = s->CD; a.GA = s->GA; a.GD = s->GD; a.AL = s->AL; a.S = s->S;
-    a.dHC = dHC; a.DGA = DGA; a.DGD = DGD; a.DCTX = DCTX; a.DV = DV;
+    a.dHC = dHC; a.dAL = dAL; a.DGA = DGA; a.DGD = DGD; a.DCTX = DCTX; a.DV = DV;
     float* p = scratch;
     a.GXA = p; p += n[0];
     a.GXD = p; p += n[1];
@@ -536,21 +542,43 @@ static int q16_run(const t2v_dec_train_persist_weights* w, const t2v_dec_train_b
     a.B = B; a.T_in = T_in; a.T = T_out; a.S_sl = S; a.p_att = p_att; a.p_dec = p_dec; a.seed = seed;
     a.step = t2v_step_for(stream);
     a.prof = g_t2v_prof;
-    if (T_in > Q16_T32) k_bwd_persist16<true><<<T2V_NWG, Q16_THREADS, q16_lds_bytes(T_in), stream>>>(a);
-    else k_bwd_persist16<false><<<T2V_NWG, Q16_THREADS, q16_lds_bytes(T_in), stream>>>(a);
+    // without an alignment gradient the pass is the pointer-less kernel, as it always was
+    const size_t lds = q16_lds_bytes(T_in);
+    if (dAL) {
+        if (T_in > Q16_T32) k_bwd_persist16<true, true><<<T2V_NWG, Q16_THREADS, lds, stream>>>(a);
+        else k_bwd_persist16<false, true><<<T2V_NWG, Q16_THREADS, lds, stream>>>(a);
+    } else {
+        if (T_in > Q16_T32) k_bwd_persist16<true, false><<<T2V_NWG, Q16_THREADS, lds, stream>>>(a);
+        else k_bwd_persist16<false, false><<<T2V_NWG, Q16_THREADS, lds, stream>>>(a);
+    }
     return t2v_check_launch();
 }
 
+// dAL: upstream gradient of the alignments, contiguous (T_out, B, T_in), or NULL
+extern "C" int t2v_decoder_bwd_persistent16_align(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* dHC,
+                                                  const float* dAL, float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
+                                                  uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
+                                                  void* stream_) {
+    return q16_run(w, s, dHC, dAL, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true);
+}
 extern "C" int t2v_decoder_bwd_persistent16(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* dHC,
                                             float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                             uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                                             void* stream_) {
-    return q16_run(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, true);
+    return t2v_decoder_bwd_persistent16_align(w, s, dHC, nullptr, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec,
+                                              seed, stream_);
 }
 // ... the pass without its preparation (scratch / DQP / err_word as handed to t2v_decoder_bwd_persistent16_prepare)
+extern "C" int t2v_decoder_bwd_persistent16_prepared_align(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s,
+                                                           const float* dHC, const float* dAL, float* DGA, float* DGD, float* DCTX, float* DV,
+                                                           float* DQP, float* scratch, uint32_t* err_word, int B, int T_in, int T_out,
+                                                           float p_att, float p_dec, uint64_t seed, void* stream_) {
+    return q16_run(w, s, dHC, dAL, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false);
+}
 extern "C" int t2v_decoder_bwd_persistent16_prepared(const t2v_dec_train_persist_weights* w, const t2v_dec_train_bufs* s, const float* dHC,
                                                      float* DGA, float* DGD, float* DCTX, float* DV, float* DQP, float* scratch,
                                                      uint32_t* err_word, int B, int T_in, int T_out, float p_att, float p_dec, uint64_t seed,
                                                      void* stream_) {
-    return q16_run(w, s, dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att, p_dec, seed, stream_, false);
+    return t2v_decoder_bwd_persistent16_prepared_align(w, s, dHC, nullptr, DGA, DGD, DCTX, DV, DQP, scratch, err_word, B, T_in, T_out, p_att,
+                                                       p_dec, seed, stream_);
 }

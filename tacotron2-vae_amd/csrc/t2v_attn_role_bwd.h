@@ -33,7 +33,12 @@ static inline size_t t2v_attn_bwd_lds_floats(int T_in, int js) {
            2 * 2 * NWV * T2V_A + 40 + (NWV == 8 ? 64 * 132 : 0);
 }
 
-template <int JS, int NWV, class HK, class Args>
+// DAL: the pass has an upstream gradient of the alignments themselves, a.dAL (T,B,T_in) — a loss that reads the attention.  It is
+// one more addend of the gradient wrt alpha(t), so it joins gp where that is assembled: from there it reaches the own positions'
+// dalpha and the softmax's dot product, which are all that gfull0 feeds.  A plain load: the tensor is complete before the launch.
+// Without DAL the role is the code it was (the kernels are at their register limit; the pointer-less form is what launches when
+// the caller has no such gradient).
+template <int JS, int NWV, class HK, bool DAL, class Args>
 __device__ __forceinline__ void t2v_attn_role_bwd(const Args& a, float* lds, const int b, const int s) {
     constexpr int NJT = JS / 16;
     constexpr int PW = JS + 30;
@@ -147,6 +152,7 @@ __device__ __forceinline__ void t2v_attn_role_bwd(const Args& a, float* lds, con
                     gc += __uint_as_float(x1);
                 }
             }
+            if (DAL) gp += a.dAL[((size_t)t * B + b) * Tp + j];
             gcum[j] = gc;
             gfull0[j] = gp;
             gfull1[j] = gc;

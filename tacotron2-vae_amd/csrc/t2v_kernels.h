@@ -167,6 +167,8 @@ struct AttnBwdArgs {
     float* DV;              // (B,S,128) per-slice accumulators
     int T_in;
     unsigned long long* prof;
+    // last, so that every field above sits where it sat before the operand existed
+    const float* dal_t;     // (B,T_in) upstream gradient of the alignment of step t (k_attn_cell_bwd<.., true>; nullptr in the others)
 };
 
 struct CellBwdArgs {

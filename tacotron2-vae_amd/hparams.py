@@ -65,7 +65,17 @@ _EXTENSIONS = dict(device_frontend=False, bucket_batches=False, bf16_run=False, 
 #                usual choice for Tacotron-like models
 #   ema_warmup : the decay of update t is min(ema_decay, (1 + t) / (10 + t)), so that the average does not sit on the
 #                initial weights for the first 1 / (1 - ema_decay) iterations
-_RECIPE = dict(ema_decay=0.0, ema_warmup=True)
+#   guided_attention_weight : 0 (default) = off.  Otherwise weight x the guided attention loss (Tachibana et al.; ESPnet's
+#                GuidedAttentionLoss) is added to the TRAINING loss: a penalty on attention weight far from the diagonal, which
+#                helps the decoder find a monotonic alignment early.  1.0 is the usual choice.  A training aid, not a model
+#                score: the validation loss stays the reference's (the term is left out there), so that validation.loss is
+#                comparable between runs with and without it.  Constant over a run (no schedule)
+#   guided_attention_sigma  : width of the diagonal band the penalty leaves free (ESPnet's default 0.4)
+_RECIPE = dict(ema_decay=0.0, ema_warmup=True, guided_attention_weight=0.0, guided_attention_sigma=0.4)
+# Switches of the group that an hparams object stores only once they are set: left alone, they read as their defaults above and
+# appear in no listing, so `recipe()`, the store and whatever is printed or saved from them are, for a run that does not use
+# such a switch, what they were before the switch existed.
+_RECIPE_UNSTORED = ('guided_attention_weight', 'guided_attention_sigma')
 
 
 def _coerce(old, text):
@@ -92,6 +102,8 @@ class HParams(object):
         store = object.__getattribute__(self, '_store')
         if k in store:
             return store[k]
+        if k in _RECIPE_UNSTORED:
+            return _RECIPE[k]
         raise AttributeError(k)
 
     def __setattr__(self, k, v):
@@ -115,9 +127,9 @@ class HParams(object):
             if '=' not in item:
                 raise ValueError("bad hparams item %r (want name=value)" % item)
             k, v = (s.strip() for s in item.split('=', 1))
-            if k not in self._store:
+            if k not in self._store and k not in _RECIPE_UNSTORED:
                 raise ValueError("unknown hparam %r" % k)
-            self._store[k] = _coerce(self._store[k], v)
+            self._store[k] = _coerce(getattr(self, k), v)
         return self
 
 
@@ -128,7 +140,7 @@ def create_hparams(hparams_string=None, verbose=False):
         for k, v in grp.items():
             flat[k] = list(v) if isinstance(v, list) else v
     flat.update(_EXTENSIONS)
-    flat.update(_RECIPE)
+    flat.update({k: v for k, v in _RECIPE.items() if k not in _RECIPE_UNSTORED})
     hp = HParams(**flat)
     if hparams_string:
         hp.parse(hparams_string)

@@ -312,8 +312,10 @@ class Tacotron2Logger(EventFileWriter):
         super(Tacotron2Logger, self).__init__(logdir)
 
     def log_training(self, reduced_loss, grad_norm, learning_rate, duration, recon_loss, kl_div, kl_weight,
-                     iteration):
+                     iteration, guided_attention=None):
         self.add_scalar("training.loss", reduced_loss, iteration)
+        if guided_attention is not None:        # hparams.guided_attention_weight > 0: the unweighted term, inside training.loss
+            self.add_scalar("training.guided_attention", guided_attention, iteration)
         self.add_scalar("grad.norm", grad_norm, iteration)
         self.add_scalar("learning.rate", learning_rate, iteration)
         self.add_scalar("duration", duration, iteration)

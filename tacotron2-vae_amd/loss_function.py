@@ -1,4 +1,5 @@
-"""Tacotron2Loss_VAE (reference loss_function.py:6-44): 2×MSE + BCE-with-logits + w(step)·KL."""
+"""Tacotron2Loss_VAE (reference loss_function.py:6-44): 2×MSE + BCE-with-logits + w(step)·KL
+(+ hparams.guided_attention_weight × the guided attention loss, a recipe switch that is off by default)."""
 import numpy as np
 import torch
 from torch import nn
@@ -21,11 +22,29 @@ class Tacotron2Loss_VAE(nn.Module):
         self.anneal_function = hparams.anneal_function
         self.lag, self.k = hparams.anneal_lag, hparams.anneal_k
         self.x0, self.upper = hparams.anneal_x0, hparams.anneal_upper
+        # (getattr: the reference's hparams know neither)
+        self.guided_weight = float(getattr(hparams, 'guided_attention_weight', 0.0))
+        self.guided_sigma = float(getattr(hparams, 'guided_attention_sigma', 0.4))
+        self.guided = None      # the detached, unweighted guided attention term of the most recent training call
 
     def kl_anneal_function(self, anneal_function, lag, step, k, x0, upper):
         return kl_anneal_weight(anneal_function, step, lag, k, x0, upper)
 
-    def forward(self, model_output, targets, step):
+    def forward(self, model_output, targets, step, lengths=None):
+        """lengths = (input_lengths, output_lengths): what the guided attention term needs (guided_attention_weight > 0).
+        The term is a training aid: it is added where gradients are recorded and left out under no_grad (validation)."""
+        if self.guided_weight > 0 and lengths is None:
+            raise ValueError("guided_attention_weight > 0 needs lengths=(input_lengths, output_lengths)")
+        total, recon, kl, w = self._reference(model_output, targets, step)
+        if self.guided_weight > 0:
+            if torch.is_grad_enabled():
+                import t2v_hip
+                g = t2v_hip.GuidedAttention.apply(model_output[3], lengths[0], lengths[1], self.guided_sigma)
+                self.guided = g.detach()
+                total = total + self.guided_weight * g
+        return total, recon, kl, w
+
+    def _reference(self, model_output, targets, step):
         mel_out, mel_post, gate_out, _, mu, logvar = model_output[:6]
         w = kl_anneal_weight(self.anneal_function, step, self.lag, self.k, self.x0, self.upper)
         if mel_out.is_cuda:      # fused value+gradient kernel

@@ -677,14 +677,18 @@ def _persist_weights(raw, bias_dec, wcomb, vv):
     return _DecTrainPersistWeights(_p(w_ih_att), _p(w_hh_att), _p(w_ih_dec), _p(w_hh_dec), _p(bias_dec), _p(wq), _p(wcomb), _p(vv))
 
 
-def _bwd_launch(lib, eng, prepared, PW, Sb, bufs, dims, dw=None):
+def _bwd_launch(lib, eng, prepared, PW, Sb, bufs, dims, dw=None, dal=None):
     """one-launch reverse pass of engine `eng`: bufs = (dHC, DGA, DGD, DCTX, DV, DQP, scratch, err_word),
     dims = (B, T_in, T, p_att, p_dec, seed); prepared: the preparation has been issued on these buffers;
-    dw: the _AchainDw of the weight-gradient epilogue ('achain' only: the slot behind the weights)"""
+    dw: the _AchainDw of the weight-gradient epilogue ('achain' only: the slot behind the weights);
+    dal: the alignment gradient, contiguous (T, B, T_in) — the entry point's *_align sibling takes it behind dHC"""
     name = eng.prepared if prepared else eng.run
     assert dw is None or eng.reserved
     head = (C.byref(PW), None if dw is None else C.byref(dw), C.byref(Sb)) if eng.reserved else (C.byref(PW), C.byref(Sb))
-    _check(getattr(lib, name)(*(head + tuple(_p(t) for t in bufs) + tuple(dims) + (_stream(),))), name)
+    ptrs = tuple(_p(t) for t in bufs)
+    if dal is not None:
+        name, ptrs = name + '_align', ptrs[:1] + (_p(dal),) + ptrs[1:]
+    _check(getattr(lib, name)(*(head + ptrs + tuple(dims) + (_stream(),))), name)
 
 
 def replay_fwd_kernels(kernel_mask):
@@ -772,6 +776,8 @@ class DecoderCore(torch.autograd.Function):
              attention_rnn weight_ih/weight_hh, decoder_rnn weight_ih/weight_hh, bias_dec (4096),
              query weight (128,1024), location conv (32,2,31), location dense (128,32), v (1,128)
     outputs: HC (T,B,1536) = [h_dec_t | ctx_t],  alignments (B,T,T_in)
+    Both outputs are differentiable: a gradient of the alignments (a loss that reads the attention, GuidedAttention) enters the
+    softmax backward of every step inside the reverse kernels; an output the loss does not use arrives as None and costs nothing.
     Batches larger than 16 run as independent chunks of <= 16 items (the loop has no cross-item coupling), so the
     reference's default batch_size = 64 works; weight gradients are summed over the chunks.
     forward() asks plan() once which kernels every chunk runs on and carries the answer on the autograd context.
@@ -1023,7 +1029,7 @@ class DecoderCore(torch.autograd.Function):
         ctx.plans = plans
         ctx.chunks = [k for _, _, k, _ in chunks] if need_grad else None
         ctx.prepared = [pr for _, _, _, pr in chunks] if need_grad else None
-        ctx.mark_non_differentiable(align)
+        ctx.set_materialize_grads(False)        # an output without a gradient arrives in backward as None, not as zeros
         if DecoderCore.keep_last:
             W0, S0, k0, _ = chunks[0]
             DecoderCore._note(last_call=(W0, S0, (k0[0].shape[1], T_in, T, float(p_att), float(p_dec), int(seed)),
@@ -1037,7 +1043,7 @@ class DecoderCore(torch.autograd.Function):
         return ctx.pre2 if ctx.pre2 is None or B == Bt else ctx.pre2.view(T, Bt, PRE)[:, b0:b0 + B].reshape(T * B, PRE)
 
     @staticmethod
-    def _bwd_persist(ctx, lib, ci, dhc_c, DGA, DGD, DCTX):
+    def _bwd_persist(ctx, lib, ci, dhc_c, dal_c, DGA, DGD, DCTX):
         """The reverse pass of chunk ci as ONE persistent launch (csrc/decoder_train_bwd_persist.hip; bf16_run, B <= 16: on bf16
         MFMA tiles, csrc/decoder_train_bwd_persist16.hip).  Returns DV, dq_sum (T * B, 128) and the GroupedHandOver of the
         chunk's weight-gradient epilogue (None: the pass has none)."""
@@ -1069,7 +1075,7 @@ class DecoderCore(torch.autograd.Function):
         stamp('dec_bwd_begin')
         bufs = (dhc_c, DGA, DGD, DCTX, DV, DQP, scratch, errw)
         _bwd_launch(lib, eng, prep is not None, PW, Sb, bufs, (B, T_in, T, p_att, p_dec, _chunk_seed(seed, b0)),
-                    None if dwh is None else dwh.dw)
+                    None if dwh is None else dwh.dw, dal_c)
         _err_note('decoder backward (persistent kernel hand-off)', errw)
         dq_off = getattr(lib, eng.dq_offset)(B, T_in, T)       # slice 0 of every item has summed the slices already
         rows = eng.dq_rows or B
@@ -1091,7 +1097,7 @@ class DecoderCore(torch.autograd.Function):
         return DQ, YD, YA, DCA, DCD, GPREV, GCUM, GCUM.view(torch.int32)[B * NS * tcap + 1:][:1]
 
     @staticmethod
-    def _bwd_steps(ctx, lib, ci, dhc_c, DGA, DGD, DCTX):
+    def _bwd_steps(ctx, lib, ci, dhc_c, dal_c, DGA, DGD, DCTX):
         """The reverse pass of chunk ci as one launch pair per step (k_lstm_bwd256 + k_attn_cell_bwd).  Returns DV, dq_sum
         (T * B, 128) and None (no weight-gradient epilogue)."""
         keep, b0, B = ctx.chunks[ci], ctx.plans[ci].b0, DGA.size(1)
@@ -1104,8 +1110,12 @@ class DecoderCore(torch.autograd.Function):
         DQ, YD, YA, DCA, DCD, GPREV, GCUM, errw = DecoderCore._bwd_step_buffers(lib, B, T_in, T, NS, dhc_c.device)
         gb = (dhc_c, DGA, DGD, DQ, DCTX, YD, YA, DCA, DCD, GPREV, GCUM, DV)             # the fields of t2v_dec_bwd_bufs
         Gb = _DecBwdBufs(*(_p(t) for t in gb))
-        _check(lib.t2v_decoder_train_bwd(C.byref(W), C.byref(Sb), C.byref(Gb), B, T_in, T, p_att, p_dec,
-                                         _chunk_seed(seed, b0), _stream()), 't2v_decoder_train_bwd')
+        if dal_c is None:
+            _check(lib.t2v_decoder_train_bwd(C.byref(W), C.byref(Sb), C.byref(Gb), B, T_in, T, p_att, p_dec,
+                                             _chunk_seed(seed, b0), _stream()), 't2v_decoder_train_bwd')
+        else:
+            _check(lib.t2v_decoder_train_bwd_align(C.byref(W), C.byref(Sb), C.byref(Gb), _p(dal_c), B, T_in, T, p_att, p_dec,
+                                                   _chunk_seed(seed, b0), _stream()), 't2v_decoder_train_bwd_align')
         _err_note('decoder backward (dq hand-off)', errw)
         dq_sum = DQ[..., 0].sum(2).view(T * B, A)
         DecoderCore._note(bwd='steps')
@@ -1179,15 +1189,29 @@ class DecoderCore(torch.autograd.Function):
         return d_memory, d_pm, acc, [colsum(DGD.view(TB, G4))] + ([colsum(dga2)] if ctx.pre2 is not None else [])
 
     @staticmethod
-    def backward(ctx, dHC, _dalign):
+    def _dal_chunk(dalign, b0, B, Bt):
+        """rows [b0, b0 + B) of the alignment gradient (Bt, T, T_in) as the kernels read them: contiguous (T, B, T_in).  No copy
+        when the call has one chunk and the tensor is a (B, T, T_in) view of such storage (what guided_attention writes)."""
+        if dalign is None:
+            return None
+        tb = dalign.permute(1, 0, 2)
+        if B == Bt and tb.is_contiguous():
+            return tb
+        return tb[:, b0:b0 + B].contiguous()
+
+    @staticmethod
+    def backward(ctx, dHC, dalign):
         """The chunk loop: each chunk's reverse pass (_bwd_persist | _bwd_steps, as plan() chose), its gradients
-        (_chunk_grads), the sums over the chunks and the return tuple."""
+        (_chunk_grads), the sums over the chunks and the return tuple.  dHC / dalign: None for an output the loss did not use."""
         lib = load_library()
         if ctx.chunks is None:
             raise T2VHipError("DecoderCore.backward without a saved arena (forward ran under no_grad)")
-        Bt, _T_in, T = ctx.dims[:3]
-        f32 = dict(device=dHC.device, dtype=torch.float32)
-        dHC = _f32c(dHC)
+        Bt, T_in, T = ctx.dims[:3]
+        dev = ctx.chunks[0][4].device
+        f32 = dict(device=dev, dtype=torch.float32)
+        dHC = torch.zeros(T, Bt, H + E, **f32) if dHC is None else _f32c(dHC)
+        if dalign is not None:
+            assert dalign.dtype == torch.float32 and dalign.shape == (Bt, T, T_in), (dalign.dtype, tuple(dalign.shape))
         acc = bacc = ctx.wg = None
         dga_l, dmem_l, dpm_l, dpre_l = [], [], [], []
         DecoderCore._note(chunk_bwd_kernels=[])
@@ -1196,7 +1220,8 @@ class DecoderCore(torch.autograd.Function):
             dhc_c = dHC if B == Bt else dHC[:, b0:b0 + B].contiguous()
             DGA, DGD, DCTX = torch.empty(T, B, G4, **f32), torch.empty(T, B, G4, **f32), torch.empty(T, B, E, **f32)
             reverse = DecoderCore._bwd_persist if plan.bwd in _BWD_ENGINES else DecoderCore._bwd_steps
-            rev = reverse(ctx, lib, ci, dhc_c, DGA, DGD, DCTX)              # DV, dq_sum, the epilogue's hand-over
+            dal_c = DecoderCore._dal_chunk(dalign, b0, B, Bt)
+            rev = reverse(ctx, lib, ci, dhc_c, dal_c, DGA, DGD, DCTX)       # DV, dq_sum, the epilogue's hand-over
             d_memory, d_pm, acc, bparts = DecoderCore._chunk_grads(ctx, lib, ci, dhc_c, DGA, DGD, DCTX, *rev, acc, dpre_l)
             bacc = bparts if bacc is None else [x + y for x, y in zip(bacc, bparts)]
             dmem_l.append(d_memory); dpm_l.append(d_pm); dga_l.append(DGA)
@@ -3579,6 +3604,41 @@ def refenc_ragged(mel, n_frames, layers, gru):
                                    _p(h_last[b0:b1]), b1 - b0, Hh, _stream()), 't2v_gru_fwd_len')
         _err_note('GRU forward', sync[1:2])
     return h_last
+
+
+def guided_attention(align, in_lengths, out_lengths, sigma=0.4):
+    """Guided attention loss of the alignments (B, T, T_in), read in whatever strides they have (csrc/guided_attention.hip):
+    returns (L, G) — L the loss as a 0-d tensor, G = dL/dalign as a (B, T, T_in) view of contiguous (T, B, T_in) storage, the layout
+    DecoderCore.backward hands to the reverse kernels without a copy.  Nothing is read back: capturable."""
+    lib = _require_gpu(align)
+    if align.dim() != 3 or align.dtype != torch.float32:
+        raise T2VHipError("guided_attention takes float32 alignments (B, T, T_in)")
+    B, T, T_in = align.shape
+    dev = align.device
+    lens = [t.to(device=dev, dtype=torch.int64).contiguous() for t in (in_lengths, out_lengths)]
+    if lens[0].numel() != B or lens[1].numel() != B:
+        raise T2VHipError("guided_attention: one input length and one output length per item")
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    G = torch.empty(T, B, T_in, device=dev, dtype=torch.float32)
+    part = torch.empty(lib.t2v_guided_attention_part_doubles(B, T), device=dev, dtype=torch.float64)
+    sb, st, sj = align.stride()
+    _check(lib.t2v_guided_attention(_p(align), sb, st, sj, _p(lens[0]), _p(lens[1]), _p(loss), _p(G), _p(part), B, T, T_in,
+                                    float(sigma), _stream()), 't2v_guided_attention')
+    return loss[0], G.permute(1, 0, 2)
+
+
+class GuidedAttention(torch.autograd.Function):
+    """guided_attention as a differentiable scalar: the gradient comes with the value, the backward is one multiply."""
+
+    @staticmethod
+    def forward(ctx, align, in_lengths, out_lengths, sigma):
+        loss, G = guided_attention(align.detach(), in_lengths, out_lengths, sigma)
+        ctx.G = G
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        return ctx.G * dloss, None, None, None
 
 
 class VAELoss(torch.autograd.Function):

@@ -223,7 +223,7 @@ class TrainEngine(object):
         opt.zero_grad()
         t2v_hip.stamp('step_begin')
         y_pred = self._forward(x)
-        loss, recon, kl, w = self.criterion(y_pred, y, iteration)
+        loss, recon, kl, w = self.criterion(y_pred, y, iteration, lengths=(x[1], x[4]))
         t2v_hip.stamp('loss_end')
         self._backward(loss)
         t2v_hip.stamp('bwd_main_end')
@@ -278,7 +278,7 @@ class TrainEngine(object):
         opt.zero_grad()
         t2v_hip.stamp('step_begin')
         y_pred = self.model(x) if self.allreduce is not None else self._forward(x)
-        loss, recon, kl, w = self.criterion(y_pred, y, iteration)
+        loss, recon, kl, w = self.criterion(y_pred, y, iteration, lengths=(x[1], x[4]))
         t2v_hip.stamp('loss_end')
         if self.allreduce is not None:
             self.allreduce.begin()
@@ -783,7 +783,9 @@ def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn
         for batch in loader:
             x, y = model.parse_batch(batch)
             y_pred = model(x)
-            loss, _, _, _ = criterion(y_pred, y, iteration)
+            # (the lengths go along as in a training step; under no_grad the criterion leaves the guided attention term out:
+            # validation.loss stays the reference's)
+            loss, _, _, _ = criterion(y_pred, y, iteration, lengths=(x[1], x[4]))
             reduced = (t2v_dist.reduce_tensor(loss.data, n_gpus) if distributed_run else loss).item()
     model.train()
     t2v_hip_check()
@@ -841,11 +843,13 @@ def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, 
                 reduced = (t2v_dist.reduce_tensor(loss, n_gpus) if hparams.distributed_run else loss).item()
                 if not math.isnan(reduced) and rank == 0:
                     duration = time.perf_counter() - start
+                    guided = criterion.guided.item() if hparams.guided_attention_weight > 0 else None
                     print("Train loss {} {:.6f} Grad Norm {:.6f} {:.2f}s/it".format(
-                        iteration, reduced, grad_norm.item(), duration))
+                        iteration, reduced, grad_norm.item(), duration) +
+                        ("" if guided is None else " Guided attention {:.6f}".format(guided)))
                     if logger is not None:
                         logger.log_training(reduced, grad_norm.item(), learning_rate, duration, recon.item(), kl.item(),
-                                            kl_w, iteration)
+                                            kl_w, iteration, guided_attention=guided)
                 if iteration % hparams.iters_per_checkpoint == 0:
                     validate(model, criterion, valset, iteration, hparams.batch_size, n_gpus, collate_fn, logger,
                              hparams.distributed_run, rank)
