@@ -438,6 +438,51 @@ int t2v_decoder_infer_persistent_window(const t2v_dec_persist_weights* w, const 
                                         int t_end, float gate_threshold, float p_prenet, uint64_t seed,
                                         const t2v_dec_items* items, const t2v_dec_window* window, void* stream);
 
+/* Duration plan of the free-running decode (rhythm control; Decoder.inference(plan=, n_plan=)).  The window centre p of the
+ * attention window above no longer comes from the previous frame's weights but from a plan, device data that names one symbol
+ * per frame.  For item b at frame t:
+ *   - q = plan[b * plan_stride + min(t, n_plan[b] - 1)];
+ *   - p = min(max(q, 0), len_b - 1)  (len_b = lengths[b]; T_in without lengths);
+ *   - everything else is the window's: the energies of all positions outside p - back <= j <= p + ahead, and of all positions
+ *     j >= len_b, are treated as -inf.  Weights outside the window are exactly 0.0.  The cumulative weights keep accumulating
+ *     the constrained weights, so the location features see what the constrained decoder did.  The window contains p, so it
+ *     is never empty.
+ * t is the absolute frame index: a call of t2v_decoder_infer_steps_plan with t_begin > 0 continues a plan.  Behind its end
+ * (t >= n_plan[b]) the plan holds its last symbol.  Free-running decode only: the teacher-forced pass and training have no
+ * plan.
+ * The two entries below take the arguments of the `_window` entries plus plan (B rows of plan_stride int32), plan_stride and
+ * n_plan (B int32), device pointers.  `window` is required; (0, 0) is the hard, one-hot form.  1 <= n_plan[b] <= plan_stride
+ * is the caller's to check on the host; the kernels clamp the index to 0 .. plan_stride - 1, so no n_plan addresses outside
+ * the plan.  A null plan or n_plan, or plan_stride < 1, is T2V_ERR_ARG.
+ * t2v_duration_plan below makes a plan from symbol durations. */
+int t2v_decoder_infer_steps_plan(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
+                                 int t_begin, int t_end, float gate_threshold, float p_prenet,
+                                 int external_prenet, uint64_t seed, const t2v_dec_items* items,
+                                 const t2v_dec_window* window, const int32_t* plan, int plan_stride, const int32_t* n_plan,
+                                 void* stream);
+int t2v_decoder_infer_persistent_plan(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
+                                      int t_end, float gate_threshold, float p_prenet, uint64_t seed,
+                                      const t2v_dec_items* items, const t2v_dec_window* window, const int32_t* plan,
+                                      int plan_stride, const int32_t* n_plan, void* stream);
+
+/* Length regulator (csrc/plan.hip): symbol durations -> the plan above.  dur (B, dur_stride) fp32, frames per symbol,
+ * fractions allowed; n_ids (B) int32, the symbols of row b; rate: NULL (1), or fp32 factors multiplied in, element (b, j) at
+ * rate[b rate_stride_b + j rate_stride_j] (a scalar on the device: both strides 0).  All in integers, so that a row's result
+ * depends neither on its batch nor on the order of a scan (the fixed-point choice of t2v_tsm):
+ *   q_j = llrint((double)dur_j * (double)rate_j * 65536.0) for j < n_ids[b]  (round to nearest, ties to even);
+ *   C_j = q_0 + ... + q_j in int64;  E_j = (C_j + 32768) >> 16,  E_{-1} = 0;
+ *   symbol j owns the frames E_{j-1} <= t < E_j; a symbol with an empty range is skipped;
+ *   n_plan[b] = min(E_last, T_max);  plan[b, t] = j for t < n_plan[b];
+ *   plan[b, t] for n_plan[b] <= t < T_max is the last value, or 0 for an empty plan.
+ * A row with a negative or non-finite dur_j * rate_j, or with dur_j * rate_j > 2^20, gets n_plan[b] = -1 and a plan of zeros;
+ * the other rows are not affected.  n_ids is clamped to 0 .. S.
+ * One workgroup per row, one launch.  1 <= S <= T2V_PLAN_MAX_SYMBOLS, else T2V_ERR_DIMS.  A null dur, n_ids, plan or n_plan,
+ * B or T_max < 1, dur_stride < S, plan_stride < T_max or a negative rate stride is T2V_ERR_ARG. */
+#define T2V_PLAN_MAX_SYMBOLS 4096   /* the frame ends E_j of a row in LDS: 4096 int32 (T2V_MAX_T_IN symbols) */
+int t2v_duration_plan(const float* dur, int dur_stride, const int32_t* n_ids, const float* rate, int rate_stride_b,
+                      int rate_stride_j, int B, int S, int T_max, int32_t* plan, int plan_stride, int32_t* n_plan,
+                      void* stream);
+
 /* ------------------------------------------------------------------ Conv1d + BatchNorm1d + activation
  * The encoder conv bank (model.py:159-177) and the Postnet (model.py:110-148): stride-1 "same" Conv1d as
  * an implicit GEMM on fp32 MFMA, BatchNorm1d (train: biased batch statistics over B*T incl. padded frames;

@@ -18,9 +18,10 @@
 // WIN (free-running decode only, include/t2vae.h t2v_dec_window): the energies outside [p - back, p + ahead], p = the position
 // of the largest previous weight (lowest index on a tie), count as -inf.  A template parameter with its own argument struct:
 // the instantiations the training engine uses are what they were.
+// WIN 2 (the planned decode, include/t2vae.h t2v_decoder_infer_steps_plan): the same mask around a centre that is data, p =
+// plan[b, min(t, n_plan[b] - 1)] clamped to the item, loaded at entry with the other operands: no scan of the previous weights.
 #include "t2v_common.h"
 #include "t2v_kernels.h"
-#include <type_traits>
 
 #define AF_THREADS 256
 #define AF_NS 8
@@ -29,6 +30,14 @@
 struct AttnFwdWinArgs : AttnFwdArgs {
     int back, ahead;      // clamped to T_in by the launcher
 };
+struct AttnFwdPlanArgs : AttnFwdWinArgs {
+    const int32_t* plan;  // (B, plan_stride) symbol of every frame
+    const int32_t* n_plan;// (B) frames of the plan; behind them it holds its last symbol
+    int plan_stride, t;   // t: the absolute index of this frame
+};
+template <int WIN> struct AttnFwdArgsOf { typedef AttnFwdArgs type; };
+template <> struct AttnFwdArgsOf<1> { typedef AttnFwdWinArgs type; };
+template <> struct AttnFwdArgsOf<2> { typedef AttnFwdPlanArgs type; };
 // (value, index) of the larger value, the lower index on a tie, over the 64 lanes of a wave; every lane ends with the result
 __device__ __forceinline__ void af_argmax_wave(float& v, int& j) {
 #pragma unroll
@@ -68,8 +77,8 @@ extern "C" int t2v_fuse_location_weights(const float* loc_conv, const float* loc
     return t2v_check_launch();
 }
 
-template <int NJT, bool BIG, bool WIN = false>      // NJT 16-position tiles per chunk; !BIG: one chunk covers T_in
-__global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(std::conditional_t<WIN, AttnFwdWinArgs, AttnFwdArgs> a) {
+template <int NJT, bool BIG, int WIN = 0>      // NJT 16-position tiles per chunk; !BIG: one chunk covers T_in; WIN 1: window, 2: plan
+__global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(typename AttnFwdArgsOf<WIN>::type a) {
     constexpr int TPAD = 16 * NJT;
     constexpr int NI = (NJT + 3) / 4;           // tiles per wave
     extern __shared__ __attribute__((aligned(16))) float eall[];     // Tcap energies -> attention weights
@@ -87,6 +96,11 @@ __global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(std::conditional_t<WIN,
     // ---- entry: every global read that does not depend on the exchange is issued here, in the order the results are
     // needed (VMEM returns in order): alignment window and query partials first, the context operands last
     if (tid == 0) ok_flag = 1;
+    int plan_q = 0;                             // WIN 2: the planned symbol of this frame (uniform; in flight with the loads below)
+    if constexpr (WIN == 2) {
+        const int ti = min(max(min(a.t, a.n_plan[b] - 1), 0), a.plan_stride - 1);
+        plan_q = a.plan[(size_t)b * a.plan_stride + ti];
+    }
     float apv[(2 * (TPAD + 32) + AF_THREADS - 1) / AF_THREADS];
 #pragma unroll
     for (int u = 0; u < (2 * (TPAD + 32) + AF_THREADS - 1) / AF_THREADS; ++u) {      // window index x <-> position x - 15
@@ -147,7 +161,12 @@ __global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(std::conditional_t<WIN,
     // for itself (no barrier); the 8 slices of an item read the same previous row, so they take the same window.  The chunked
     // form holds one 256-position chunk of the row in LDS and makes its own pass over al_prev[b, :T_in].
     int wlo = 0, whi = 0;
-    if constexpr (WIN) {
+    if constexpr (WIN == 2) {
+        const int p = min(max(plan_q, 0), len - 1);
+        wlo = p - a.back;
+        whi = p + a.ahead;
+    }
+    if constexpr (WIN == 1) {
         float bv = -1.f;
         int bj = 0;
         if constexpr (BIG) {
@@ -300,7 +319,7 @@ __global__ __launch_bounds__(AF_THREADS) void k_attn_fwd(std::conditional_t<WIN,
             }
         }
         const float ev = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-        if constexpr (WIN) ev0 = (j < len && j >= wlo && j <= whi) ? ev : -INFINITY;
+        if constexpr (WIN != 0) ev0 = (j < len && j >= wlo && j <= whi) ? ev : -INFINITY;
         else ev0 = j < len ? ev : -INFINITY;
         if (BIG) eall[j] = ev0;
         mloc = fmaxf(mloc, ev0);
@@ -420,8 +439,24 @@ void t2v_launch_attn_fwd_window(const AttnFwdArgs& f, int B, int T_in, int back,
     static_cast<AttnFwdArgs&>(w) = f;
     w.back = back < T_in ? back : T_in;      // (a window wider than the text covers it whatever p is; p +- it cannot overflow)
     w.ahead = ahead < T_in ? ahead : T_in;
-    if (T_in <= 96) k_attn_fwd<6, false, true><<<grid, AF_THREADS, lds, stream>>>(w);
-    else if (T_in <= 128) k_attn_fwd<8, false, true><<<grid, AF_THREADS, lds, stream>>>(w);
-    else if (T_in <= 256) k_attn_fwd<16, false, true><<<grid, AF_THREADS, lds, stream>>>(w);
-    else k_attn_fwd<16, true, true><<<grid, AF_THREADS, lds, stream>>>(w);
+    if (T_in <= 96) k_attn_fwd<6, false, 1><<<grid, AF_THREADS, lds, stream>>>(w);
+    else if (T_in <= 128) k_attn_fwd<8, false, 1><<<grid, AF_THREADS, lds, stream>>>(w);
+    else if (T_in <= 256) k_attn_fwd<16, false, 1><<<grid, AF_THREADS, lds, stream>>>(w);
+    else k_attn_fwd<16, true, 1><<<grid, AF_THREADS, lds, stream>>>(w);
+}
+
+// the same step of the planned decode: the window (back, ahead) around plan[b, min(t, n_plan[b] - 1)], t the absolute frame
+void t2v_launch_attn_fwd_plan(const AttnFwdArgs& f, int B, int T_in, int back, int ahead, const int32_t* plan, int plan_stride,
+                              const int32_t* n_plan, int t, hipStream_t stream) {
+    const dim3 grid(B, AF_NS);
+    const size_t lds = sizeof(float) * t2v_tcap(T_in);
+    AttnFwdPlanArgs w;
+    static_cast<AttnFwdArgs&>(w) = f;
+    w.back = back < T_in ? back : T_in;
+    w.ahead = ahead < T_in ? ahead : T_in;
+    w.plan = plan; w.n_plan = n_plan; w.plan_stride = plan_stride; w.t = t;
+    if (T_in <= 96) k_attn_fwd<6, false, 2><<<grid, AF_THREADS, lds, stream>>>(w);
+    else if (T_in <= 128) k_attn_fwd<8, false, 2><<<grid, AF_THREADS, lds, stream>>>(w);
+    else if (T_in <= 256) k_attn_fwd<16, false, 2><<<grid, AF_THREADS, lds, stream>>>(w);
+    else k_attn_fwd<16, true, 2><<<grid, AF_THREADS, lds, stream>>>(w);
 }

@@ -1,7 +1,8 @@
 // Free-running decode (reference Decoder.inference model.py:428-464 / the loop at
 // synthesizer.py:139-154).  Per emitted frame four launches, no skew (frame t feeds step t+1):
 //   k_lstm_fwd<1>  attention_rnn(t), prenet columns inside K
-//   k_attn_fwd     location-sensitive attention (mask = None; with a t2v_dec_window: its windowed instantiation)
+//   k_attn_fwd     location-sensitive attention (mask = None; with a t2v_dec_window: its windowed instantiation; with a plan
+//                  too: the instantiation that takes the window's centre from the plan)
 //   k_lstm_fwd<2>  decoder_rnn(t)
 //   k_proj_prenet  80-mel + gate projection of [h_dec_t | ctx_t], stop flag, Prenet of the new frame (layer 0 folded
 //                  into the projection, one granule hop to layer 1)
@@ -44,9 +45,17 @@ struct ProjPrenetArgs {
 #include "proj_prenet_kernel.inc"
 #undef PP_ITEMS
 
+// the plan of the planned decode (include/t2vae.h t2v_decoder_infer_steps_plan): device pointers
+struct InferPlan {
+    const int32_t* plan;
+    int plan_stride;
+    const int32_t* n_plan;
+};
+
 static int infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in, int t_begin, int t_end,
                        float gate_threshold, float p_prenet, int external_prenet, uint64_t seed, const t2v_dec_items* items,
-                       const t2v_dec_window* window, hipStream_t stream) {
+                       const t2v_dec_window* window, const InferPlan* plan, hipStream_t stream) {
+    if (plan && (!window || !plan->plan || !plan->n_plan || plan->plan_stride < 1)) return T2V_ERR_ARG;
     if (!w || !s || B < 1 || B > 8 || T_in < 1 || T_in > T2V_MAX_T_IN || t_begin < 0 || t_end <= t_begin) return T2V_ERR_ARG;
     if (items && (!items->stop_item || !items->item_seeds)) return T2V_ERR_ARG;
     if (window && (window->back < 0 || window->ahead < 0)) return T2V_ERR_ARG;
@@ -110,7 +119,8 @@ static int infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, in
         f.ex = ex;
         f.err = sync + 31;
         f.epoch = (unsigned)t + 1u;
-        if (window) t2v_launch_attn_fwd_window(f, B, T_in, window->back, window->ahead, stream);
+        if (plan) t2v_launch_attn_fwd_plan(f, B, T_in, window->back, window->ahead, plan->plan, plan->plan_stride, plan->n_plan, t, stream);
+        else if (window) t2v_launch_attn_fwd_window(f, B, T_in, window->back, window->ahead, stream);
         else t2v_launch_attn_fwd(f, B, T_in, stream);
         DBG(2, "attention");
 
@@ -154,7 +164,7 @@ static int infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, in
 extern "C" int t2v_decoder_infer_steps(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
                                        int t_begin, int t_end, float gate_threshold, float p_prenet,
                                        int external_prenet, uint64_t seed, void* stream_) {
-    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, nullptr, nullptr, (hipStream_t)stream_);
+    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, nullptr, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 // per-item stop frames and dropout seeds (batched synthesis, include/t2vae.h)
@@ -162,7 +172,7 @@ extern "C" int t2v_decoder_infer_steps_items(const t2v_dec_weights* w, const t2v
                                              int t_begin, int t_end, float gate_threshold, float p_prenet,
                                              int external_prenet, uint64_t seed, const t2v_dec_items* items, void* stream_) {
     if (!items) return T2V_ERR_ARG;
-    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, items, nullptr, (hipStream_t)stream_);
+    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, items, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 // the attention window of t2v_dec_window on every step; items may be NULL (one seed, the global stop rule alone)
@@ -171,5 +181,16 @@ extern "C" int t2v_decoder_infer_steps_window(const t2v_dec_weights* w, const t2
                                               int external_prenet, uint64_t seed, const t2v_dec_items* items,
                                               const t2v_dec_window* window, void* stream_) {
     if (!window) return T2V_ERR_ARG;
-    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, items, window, (hipStream_t)stream_);
+    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, items, window, nullptr, (hipStream_t)stream_);
+}
+
+// the planned decode: the window around plan[b, min(t, n_plan[b] - 1)], t the absolute frame; items may be NULL
+extern "C" int t2v_decoder_infer_steps_plan(const t2v_dec_weights* w, const t2v_dec_infer_bufs* s, int B, int T_in,
+                                            int t_begin, int t_end, float gate_threshold, float p_prenet,
+                                            int external_prenet, uint64_t seed, const t2v_dec_items* items,
+                                            const t2v_dec_window* window, const int32_t* plan, int plan_stride,
+                                            const int32_t* n_plan, void* stream_) {
+    if (!window) return T2V_ERR_ARG;
+    const InferPlan pl = {plan, plan_stride, n_plan};
+    return infer_steps(w, s, B, T_in, t_begin, t_end, gate_threshold, p_prenet, external_prenet, seed, items, window, &pl, (hipStream_t)stream_);
 }

@@ -223,6 +223,13 @@ struct PersistItems {
 struct PersistWindow {
     int back, ahead;
 };
+// The planned decode (include/t2vae.h t2v_decoder_infer_persistent_plan): the window and the plan its centre is read from
+struct PersistPlan {
+    int back, ahead;
+    const int32_t* plan;            // (B, plan_stride)
+    const int32_t* n_plan;          // (B)
+    int plan_stride;
+};
 // (value, index) of the larger value, the lower index on a tie, over the 64 lanes of a wave; every lane ends with the result
 __device__ __forceinline__ void pd_argmax_wave(float& v, int& j) {
 #pragma unroll
@@ -242,6 +249,14 @@ __device__ __forceinline__ void pd_argmax_wave(float& v, int& j) {
 #undef PD_ITEMS
 #undef PD_WINDOW
 #define PD_WINDOW 1
+#define PD_ITEMS 0
+#include "decoder_persist_kernel.inc"
+#undef PD_ITEMS
+#define PD_ITEMS 1
+#include "decoder_persist_kernel.inc"
+#undef PD_ITEMS
+#undef PD_WINDOW
+#define PD_WINDOW 2
 #define PD_ITEMS 0
 #include "decoder_persist_kernel.inc"
 #undef PD_ITEMS
@@ -272,7 +287,8 @@ static int pd_supported(const void* kernel, int B, int T_in) {
     static bool raised = false;
     return t2v_persist_resident(kernel, PD_THREADS, pd_lds_bytes(B, T_in),
                                 {(const void*)k_decode_persist, (const void*)k_decode_persist_items,
-                                 (const void*)k_decode_persist_win, (const void*)k_decode_persist_items_win}, raised);
+                                 (const void*)k_decode_persist_win, (const void*)k_decode_persist_items_win,
+                                 (const void*)k_decode_persist_plan, (const void*)k_decode_persist_items_plan}, raised);
 }
 extern "C" int t2v_decoder_persist_supported(int B, int T_in) {
     return pd_supported((const void*)k_decode_persist, B, T_in);
@@ -280,8 +296,9 @@ extern "C" int t2v_decoder_persist_supported(int B, int T_in) {
 
 static int pd_launch(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in, int t_end,
                      float gate_threshold, float p_prenet, uint64_t seed, const t2v_dec_items* items, const t2v_dec_window* window,
-                     hipStream_t stream) {
-    const void* kernel = window ? (items ? (const void*)k_decode_persist_items_win : (const void*)k_decode_persist_win)
+                     const PersistPlan* plan, hipStream_t stream) {
+    if (plan && (!window || !plan->plan || !plan->n_plan || plan->plan_stride < 1)) return T2V_ERR_ARG;
+    const void* kernel = plan ? (items ? (const void*)k_decode_persist_items_plan : (const void*)k_decode_persist_plan) : window ? (items ? (const void*)k_decode_persist_items_win : (const void*)k_decode_persist_win)
                                 : (items ? (const void*)k_decode_persist_items : (const void*)k_decode_persist);
     if (!w || !s || !pd_supported(kernel, B, T_in) || t_end < 1) return T2V_ERR_ARG;
     if (!w->w_ih_att || !w->w_hh_att || !w->w_ih_dec || !w->w_hh_dec || !w->bias_att || !w->bias_dec || !w->wq || !w->wcomb ||
@@ -307,7 +324,11 @@ static int pd_launch(const t2v_dec_persist_weights* w, const t2v_dec_persist_buf
     a.prof = g_t2v_prof;
     // (a window wider than the text covers it whatever p is: clamped, so that the kernel's p - back / p + ahead stay small)
     const PersistWindow wn = {window ? (window->back < T_in ? window->back : T_in) : 0, window ? (window->ahead < T_in ? window->ahead : T_in) : 0};
-    if (window && items) k_decode_persist_items_win<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds}, wn);
+    if (plan) {
+        const PersistPlan pl = {wn.back, wn.ahead, plan->plan, plan->n_plan, plan->plan_stride};
+        if (items) k_decode_persist_items_plan<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds}, pl);
+        else k_decode_persist_plan<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, pl);
+    } else if (window && items) k_decode_persist_items_win<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds}, wn);
     else if (window) k_decode_persist_win<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, wn);
     else if (items) k_decode_persist_items<<<T2V_NWG, PD_THREADS, lds, stream>>>(a, PersistItems{items->stop_item, items->item_seeds});
     else k_decode_persist<<<T2V_NWG, PD_THREADS, lds, stream>>>(a);
@@ -316,7 +337,7 @@ static int pd_launch(const t2v_dec_persist_weights* w, const t2v_dec_persist_buf
 
 extern "C" int t2v_decoder_infer_persistent(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
                                             int t_end, float gate_threshold, float p_prenet, uint64_t seed, void* stream_) {
-    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, nullptr, nullptr, (hipStream_t)stream_);
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, nullptr, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 // the same with per-item stop frames and dropout seeds (batched synthesis); seed is unused when items->item_seeds is set
@@ -324,7 +345,7 @@ extern "C" int t2v_decoder_infer_persistent_items(const t2v_dec_persist_weights*
                                                   int t_end, float gate_threshold, float p_prenet, uint64_t seed,
                                                   const t2v_dec_items* items, void* stream_) {
     if (!items) return T2V_ERR_ARG;
-    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, nullptr, (hipStream_t)stream_);
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, nullptr, nullptr, (hipStream_t)stream_);
 }
 
 // the same with the attention window of t2v_dec_window; items may be NULL (one seed, the global stop rule alone)
@@ -332,5 +353,15 @@ extern "C" int t2v_decoder_infer_persistent_window(const t2v_dec_persist_weights
                                                    int t_end, float gate_threshold, float p_prenet, uint64_t seed,
                                                    const t2v_dec_items* items, const t2v_dec_window* window, void* stream_) {
     if (!window) return T2V_ERR_ARG;
-    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, window, (hipStream_t)stream_);
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, window, nullptr, (hipStream_t)stream_);
+}
+
+// the planned decode: the window around plan[b, min(t, n_plan[b] - 1)]; items may be NULL
+extern "C" int t2v_decoder_infer_persistent_plan(const t2v_dec_persist_weights* w, const t2v_dec_persist_bufs* s, int B, int T_in,
+                                                 int t_end, float gate_threshold, float p_prenet, uint64_t seed,
+                                                 const t2v_dec_items* items, const t2v_dec_window* window, const int32_t* plan,
+                                                 int plan_stride, const int32_t* n_plan, void* stream_) {
+    if (!window) return T2V_ERR_ARG;
+    const PersistPlan pl = {0, 0, plan, n_plan, plan_stride};
+    return pd_launch(w, s, B, T_in, t_end, gate_threshold, p_prenet, seed, items, window, &pl, (hipStream_t)stream_);
 }

@@ -4,7 +4,14 @@
 // instances rather than a template: the PD_ITEMS 0 text is the kernel as it was, so its instructions stay the same.
 // PD_WINDOW 1 (with either PD_ITEMS) adds the attention window of include/t2vae.h (t2v_dec_window): k_decode_persist_win and
 // k_decode_persist_items_win.  With PD_WINDOW 0 the text is what it was before the window existed.
-#if PD_ITEMS && PD_WINDOW
+// PD_WINDOW 2 is the planned decode (include/t2vae.h t2v_decoder_infer_persistent_plan): k_decode_persist_plan and
+// k_decode_persist_items_plan mask as PD_WINDOW 1 does, around a centre read from the plan instead of found by a scan.  With
+// PD_WINDOW 0 or 1 the text is what it was before the plan existed.
+#if PD_ITEMS && PD_WINDOW == 2
+__global__ __launch_bounds__(PD_THREADS) void k_decode_persist_items_plan(PersistArgs a, PersistItems it, PersistPlan wn) {
+#elif PD_WINDOW == 2
+__global__ __launch_bounds__(PD_THREADS) void k_decode_persist_plan(PersistArgs a, PersistPlan wn) {
+#elif PD_ITEMS && PD_WINDOW
 __global__ __launch_bounds__(PD_THREADS) void k_decode_persist_items_win(PersistArgs a, PersistItems it, PersistWindow wn) {
 #elif PD_WINDOW
 __global__ __launch_bounds__(PD_THREADS) void k_decode_persist_win(PersistArgs a, PersistWindow wn) {
@@ -72,7 +79,14 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
     for (int i = tid; i < B * PD_XW; i += PD_THREADS) X[i] = 0.f;
     if (tid < 2 * PD_MAXB * 4) cst[tid] = 0.f;
     if (tid == 0) flag[0] = 1;
-#if PD_WINDOW
+#if PD_WINDOW == 2
+    // the plan row of this attention workgroup's item, the last frame the plan names and the item's length: uniform over the
+    // workgroup (wave-uniform values, no vector register per lane).  The window centre of frame 0 is the plan's first symbol.
+    const int32_t* plan_row = wn.plan + (size_t)(wg < 8 * B ? wg >> 3 : 0) * wn.plan_stride;
+    const int plan_last = min(max(wn.n_plan[wg < 8 * B ? wg >> 3 : 0], 1), wn.plan_stride) - 1;
+    const int plan_len = a.lengths ? a.lengths[wg < 8 * B ? wg >> 3 : 0] : Tp;
+    if (tid == 0) flag[1] = min(max(plan_row[0], 0), plan_len - 1);
+#elif PD_WINDOW
     if (tid == 0) flag[1] = 0;          // the window centre of frame 0
 #endif
     // role operands
@@ -483,7 +497,17 @@ __global__ __launch_bounds__(PD_THREADS) void k_decode_persist(PersistArgs a) {
             // decoder_rnn(t+1), part 1 (the h_dec(t) columns) of the ATTENTION workgroups: in the tail of this frame — at the top
             // of the next one they go straight from "h_att published" to their gather of it and the attention (the chain).  The
             // projection workgroups are gathering the same row right now and ARE the chain: let them go first.
-#if PD_WINDOW
+#if PD_WINDOW == 2
+            // window centre of the NEXT frame: the plan's symbol of frame t + 1 (its last one behind the plan's end), clamped to
+            // the item.  It is data, so nothing of it waits for this frame: one load in the idle tail, where PD_WINDOW 1 scans the
+            // weights, left in flag[1] for the softmax threads of frame t + 1 behind the barrier below.  (Issued a frame earlier
+            // and carried in a register, so that no round trip to memory sits in this tail, it measured the same and spilled 8
+            // bytes more: DESIGN 7w.)  The 8 slices of an item read the same word.
+            {
+                const int q = plan_row[min(t + 1, plan_last)];
+                if (tid == 0) flag[1] = min(max(q, 0), plan_len - 1);
+            }
+#elif PD_WINDOW
             // attention window of the NEXT frame: p = position of the largest weight of this frame (lowest index on a tie; frame 0
             // starts from p = 0, as the all-zero initial weights give), energies outside [p - back, p + ahead] count as -inf.  It
             // depends on this frame's weights alone, so it is found here, where the attention workgroups idle: wave 0 scans

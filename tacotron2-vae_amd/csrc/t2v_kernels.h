@@ -58,6 +58,8 @@ static inline int t2v_attn_bwd_slices_(int T_in) { const int js = t2v_attn_bwd_j
 void t2v_launch_lstm_fwd(int mode, const LstmFwdArgs& a, hipStream_t stream);
 void t2v_launch_attn_fwd(const AttnFwdArgs& f, int B, int T_in, hipStream_t stream);
 void t2v_launch_attn_fwd_window(const AttnFwdArgs& f, int B, int T_in, int back, int ahead, hipStream_t stream);   // free-running decode: t2v_dec_window
+void t2v_launch_attn_fwd_plan(const AttnFwdArgs& f, int B, int T_in, int back, int ahead, const int32_t* plan, int plan_stride,
+                              const int32_t* n_plan, int t, hipStream_t stream);                                   // the planned decode
 // The two persistent forward launchers (fp32 / bf16), after their shape and offset checks: the checks of the remaining
 // arguments, then the per-pass resets — the sync / error words, the zero initial states of the arena (as
 // t2v_decoder_train_fwd).  Returns the sync words, or NULL (nothing issued) on a bad argument.

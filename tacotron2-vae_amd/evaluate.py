@@ -3,7 +3,7 @@ with its own recording by mel-spectral distortion with dynamic time warping (`Sy
 
     python evaluate.py --load_path CKPT --filelist_path F --out OUT.json
                        [--batch_size N] [--condition ref|emotion] [--limit N] [--prosody] [--alignment]
-                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--durations [--max_step S]] [--attention_window BACK,AHEAD] [--weights raw|ema] [--speed R]
+                       [--style [--style_k K]] [--aligned] [--energy] [--voice] [--durations [--max_step S]] [--attention_window BACK,AHEAD] [--rhythm ref [--rhythm_window BACK,AHEAD]] [--weights raw|ema] [--speed R]
                        [--pitch ST] [--formant ST] [--preserve_formants]
                        [--hparams ...]
 
@@ -95,6 +95,12 @@ refused together with --speed / --pitch, as --aligned is.
 attends within BACK positions behind and AHEAD in front of the position the previous frame attended most).
 OUT.json always holds "attention_window": [BACK, AHEAD], or null without the flag, so that two reports can be told apart.
 
+--rhythm ref gives every synthesis the rhythm of its own recording: the recording's symbol durations, found by the forced
+alignment of --durations, become the decoder's plan (`Synthesizer.evaluate(rows, rhythm='ref')`), and every frame
+attends within --rhythm_window BACK,AHEAD (default 1,1) of its planned symbol.  The synthesis then has the recording's frame
+count, so what remains in dtw, mcd_db or the F0 errors is not timing.  Every row gains "rhythm"; OUT.json holds "rhythm" and
+"rhythm_window" only when the flag is given.
+
 --weights ema scores the averaged weights of the checkpoint ('ema_state_dict', written by a training run with
 hparams.ema_decay > 0) instead of the last iteration's; with --condition emotion the centroid cache is a file of its own.
 OUT.json always holds "weights": "raw" or "ema".
@@ -165,6 +171,12 @@ def build_arg_parser():
     p.add_argument('--attention_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
                    help="attention constraint of the free-running decode: every frame attends within BACK positions behind and "
                         "AHEAD in front of the position the previous frame attended most; written into the report")
+    p.add_argument('--rhythm', choices=['ref'], default=None,
+                   help="decode every synthesis along the symbol durations of its own recording (forced alignment), which takes "
+                        "rhythm out of the comparison; written into the report")
+    p.add_argument('--rhythm_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
+                   help="positions the decoder may look behind and in front of the planned symbol under --rhythm (default 1,1, "
+                        "an uncalibrated choice)")
     p.add_argument('--hparams', default='', help="comma separated name=value overrides")
     from wavio import add_wav_arguments
     add_wav_arguments(p)
@@ -190,6 +202,8 @@ def parse_args(argv=None):
     if args.aligned and (args.prosody or args.energy or args.voice) and (args.speed != 1.0 or args.pitch != 0.0):
         raise SystemExit("--aligned with --prosody / --energy / --voice scores tracks along the mels' warping path; with --speed / --pitch "
                          "the waveform is on another time axis: drop --aligned or the two flags")
+    if args.rhythm is None and args.rhythm_window is not None:
+        raise SystemExit("--rhythm_window acts on a plan: give --rhythm ref")
     from synthesizer import tempo_options
     tempo_options(args)                                                   # a value out of range is refused here
     return args
@@ -233,13 +247,16 @@ def main(argv=None):
     rows = read_rows(args.filelist_path, args.limit)
     style = dict(style=True, style_k=args.style_k) if args.style else {}
     timing = dict(durations=True, max_step=args.max_step) if args.durations else {}
+    rhythm = dict(rhythm=args.rhythm, rhythm_window=args.rhythm_window) if args.rhythm else {}
     records = syn.evaluate(rows, args.batch_size, args.condition, prosody=args.prosody, alignment=args.alignment,
-                           aligned=args.aligned, energy=args.energy, voice=args.voice, **style, **timing)
+                           aligned=args.aligned, energy=args.energy, voice=args.voice, **style, **timing, **rhythm)
     summary = summarize(records)
     formant_keys = {}
     if args.formant != 0.0 or args.preserve_formants:                     # the report gains its new keys only with a new flag
         formant_keys = {'formant': syn.formant, 'preserve_formants': syn.preserve_formants}
     timing_keys = {'max_step': args.max_step} if args.durations else {}   # likewise
+    if args.rhythm:
+        timing_keys.update(rhythm=args.rhythm, rhythm_window=list(args.rhythm_window or Synthesizer.RHYTHM_WINDOW))
     with open(args.out, 'w', encoding='utf-8') as f:
         json.dump({'summary': summary, 'rows': [dict(r, path=row[0]) for r, row in zip(records, rows)],
                    'attention_window': None if syn.attention_window is None else list(syn.attention_window),

@@ -240,7 +240,34 @@ class Decoder(nn.Module):
     def attention_window(self, window):
         self._attention_window = t2v_hip.check_attention_window(window)
 
-    def _session(self, memory, mask, max_steps, item_seeds=None):
+    PLAN_STOPS = ('plan', 'gate')
+    _NEVER = 2.0        # a gate threshold above 1: no sigmoid reaches it, so the loop runs its frames without touching a kernel
+
+    def _checked_plan(self, plan, n_plan, plan_window, plan_stop, B, device):
+        """None without a plan, else (plan, n_plan, window, n_plan on the host, plan_stop) after t2v_hip.check_plan"""
+        if plan is None and n_plan is None:
+            return None
+        if plan_stop not in self.PLAN_STOPS:
+            raise ValueError("plan_stop must be one of %s, got %r" % (self.PLAN_STOPS, plan_stop))
+        window = t2v_hip.check_attention_window(plan_window)
+        plan, n_host = t2v_hip.check_plan(plan, n_plan, B, self.max_decoder_steps, device, window)
+        return plan, n_plan, window, n_host, plan_stop
+
+    @staticmethod
+    def _plan_rows(pl, idx, device):
+        """the plan of the items idx (a list of rows), in that order"""
+        if pl is None:
+            return None
+        sel = torch.as_tensor(idx, device=device)
+        return (pl[0].index_select(0, sel), pl[1].index_select(0, sel), pl[2], [pl[3][b] for b in idx], pl[4])
+
+    def _plan_steps(self, pl):
+        """(decoder steps of a session under the plan pl, the gate threshold of its loop)"""
+        if pl is not None and pl[4] == 'plan':
+            return max(pl[3]), self._NEVER
+        return self.max_decoder_steps, self.gate_threshold
+
+    def _session(self, memory, mask, max_steps, item_seeds=None, pl=None):
         att, dec, al = self.attention_rnn, self.decoder_rnn, self.attention_layer
         lengths = None if mask is None else (~mask).sum(1).to(device=memory.device, dtype=torch.int32)
         pm = t2v_hip.LinearHIP.apply(memory, al.memory_layer.weight, None, False, 0.0, 0, 0, 0)
@@ -250,11 +277,18 @@ class Decoder(nn.Module):
             al.location_layer.location_conv.conv.weight, al.location_layer.location_dense.weight, al.v.weight,
             self.prenet.layers[0].weight, self.prenet.layers[1].weight, self.linear_projection.weight,
             self.linear_projection.bias, self.gate_layer.weight, self.gate_layer.bias, max_steps, item_seeds,
-            self.attention_window)
+            self.attention_window if pl is None else pl[2], None if pl is None else pl[0], None if pl is None else pl[1],
+            None if pl is None else pl[3])
 
-    def initialize_decoder_states(self, memory, mask):
-        """reference model.py:260-291 — zero states; stores memory / processed memory / mask."""
-        self._sess = self._session(memory, mask, self.max_decoder_steps)
+    def initialize_decoder_states(self, memory, mask, plan=None, n_plan=None, plan_window=(1, 1), plan_stop='plan'):
+        """reference model.py:260-291 — zero states; stores memory / processed memory / mask.
+        plan, n_plan, plan_window: the planned decode of inference(); the stepwise decode() calls that follow read the plan at
+        their frame index.  The caller of decode() ends its own loop, so plan_stop is only checked here."""
+        pl = self._checked_plan(plan, n_plan, plan_window, plan_stop, memory.size(0), memory.device)
+        self._init_states(memory, mask, self.max_decoder_steps, pl)
+
+    def _init_states(self, memory, mask, max_steps, pl):
+        self._sess = self._session(memory, mask, max_steps, pl=pl)
         self.memory, self.processed_memory, self.mask = memory, self._sess.pm, mask
         B = memory.size(0)
         z = lambda n: memory.new_zeros(B, n)
@@ -280,16 +314,18 @@ class Decoder(nn.Module):
         self.attention_weights, self.attention_weights_cum = s.AL[t + 1], s.ACUM[t + 1]
         return s.MEL[t], s.GATE[t].unsqueeze(1), s.AL[t + 1]
 
-    def _run_to_end(self, s, chunk, persistent, seed):
+    def _run_to_end(self, s, chunk, persistent, seed, gate_threshold=None):
         """Run the prepared session s (PRE[0] holds Prenet(go frame)) until every gate has fired or max_decoder_steps; returns
         the stop flag as it was last read (>= s.max_steps: no stop).  One read of the flag, one synchronisation, per launch."""
         if persistent is None:
             persistent = os.environ.get('T2V_DECODE_PERSISTENT', '1') != '0'
+        if gate_threshold is None:
+            gate_threshold = self.gate_threshold
         stop, t = s.max_steps, 0
         if persistent and s.persistent_supported():
             # one persistent launch for the whole utterance: weights resident on chip, state handed between CUs as
             # tagged granules, the loop ends on the frame the gate fires
-            s.run_persistent(self.gate_threshold, drop_rate, seed)
+            s.run_persistent(gate_threshold, drop_rate, seed)
             stop = int(s.stop.item())
             if not s.persistent_timed_out():
                 t2v_hip.check_async_errors()
@@ -300,39 +336,58 @@ class Decoder(nn.Module):
             s.reset_for_rerun()
         while t < s.max_steps:
             t1 = min(s.max_steps, t + chunk)
-            s.run(t, t1, self.gate_threshold, drop_rate, False, seed)
+            s.run(t, t1, gate_threshold, drop_rate, False, seed)
             stop = int(s.stop.item())
             if stop < t1:
                 break
             t = t1
         return stop
 
-    def inference(self, memory, chunk=32, persistent=None):
+    def inference(self, memory, chunk=32, persistent=None, plan=None, n_plan=None, plan_window=(1, 1), plan_stop='plan'):
         """reference model.py:428-464: decode until sigmoid(gate) > gate_threshold or max_decoder_steps.
         The loop runs on the GPU in chunks of `chunk` frames between stop-flag reads.
         More than 8 utterances (the decode kernels take 8 per call; the reference's own loop only works for one) are decoded
         8 at a time, each group until all of ITS gates have fired, and padded to the longest group: mel 0, gate logit +1e3
-        (fired), attention weights 0 (round 4; it used to raise)."""
+        (fired), attention weights 0 (round 4; it used to raise).
+        plan (B, N) int32, n_plan (B) int32 on memory's device (t2v_hip.duration_plan makes them): the planned decode of
+        DESIGN 7w.  Frame t of item b attends within plan_window = (back, ahead) around the symbol plan[b, min(t,
+        n_plan[b] - 1)], which replaces attention_window for this call; (0, 0) is the one-hot form.  The default (1, 1) is an
+        uncalibrated choice: no trained checkpoint has been decoded under a plan yet.  plan_stop = 'plan': item b has exactly
+        n_plan[b] frames (behind them, in a batch: mel 0, gate logit +1e3, weights 0), the gate is returned but ends nothing
+        and nothing warns about max decoder steps; 'gate': the gate ends the decode as without a plan, and behind its end the
+        plan holds its last symbol."""
+        pl = self._checked_plan(plan, n_plan, plan_window, plan_stop, memory.size(0), memory.device)
         if memory.size(0) > 8:
-            outs = [self.inference(memory[b0:b0 + 8], chunk, persistent) for b0 in range(0, memory.size(0), 8)]
+            outs = [self.inference(memory[b0:b0 + 8], chunk, persistent,
+                                   *(() if pl is None else (pl[0][b0:b0 + 8], pl[1][b0:b0 + 8], pl[2], pl[4])))
+                    for b0 in range(0, memory.size(0), 8)]
             n = max(o[0].size(2) for o in outs)
             F_pad = torch.nn.functional.pad
             return (torch.cat([F_pad(o[0], (0, n - o[0].size(2))) for o in outs], 0),
                     torch.cat([F_pad(o[1], (0, 0, 0, n - o[1].size(1)), value=1e3) for o in outs], 0),
                     torch.cat([F_pad(o[2], (0, 0, 0, n - o[2].size(1))) for o in outs], 0))
-        self.initialize_decoder_states(memory, mask=None)
+        max_steps, thr = self._plan_steps(pl)
+        self._init_states(memory, None, max_steps, pl)
         s = self._sess
         s.PRE[0].copy_(self.prenet(self.get_go_frame(memory)))
         self._calls += 1
         seed = (int(self.dropout_seed) * 1000003 + self._calls) & 0x7FFFFFFFFFFFFFFF
-        n = self._run_to_end(s, chunk, persistent, seed) + 1
+        n = self._run_to_end(s, chunk, persistent, seed, thr) + 1
+        by_plan = pl is not None and pl[4] == 'plan'
         if n > s.max_steps:
-            print("Warning! Reached max decoder steps")
+            if not by_plan:
+                print("Warning! Reached max decoder steps")
             n = s.max_steps
         s.t = n
         mel = s.MEL[:n].permute(1, 2, 0).contiguous()           # (B,80,T)
         gate = s.GATE[:n].transpose(0, 1).unsqueeze(-1).contiguous()   # (B,T,1)
-        return mel, gate, s.AL[1:n + 1].transpose(0, 1)
+        al = s.AL[1:n + 1].transpose(0, 1)
+        if by_plan and min(pl[3]) < n:          # a batch of plans of different lengths: item b ends with its own plan
+            past = torch.arange(n, device=memory.device)[None, :] >= pl[1][:, None]
+            mel = mel.masked_fill(past[:, None, :], 0.0)
+            gate = gate.masked_fill(past[:, :, None], 1e3)
+            al = al.masked_fill(past[:, :, None], 0.0)
+        return mel, gate, al
 
     # -- batched free-running decode (Synthesizer.synthesize_batch) ------------------------------------------------
     SEED_MASK = 0x7FFFFFFFFFFFFFFF
@@ -347,13 +402,16 @@ class Decoder(nn.Module):
         self._calls += n
         return seeds
 
-    def inference_batch(self, memory, memory_lengths, seeds=None, chunk=32, persistent=None):
+    def inference_batch(self, memory, memory_lengths, seeds=None, chunk=32, persistent=None, plan=None, n_plan=None,
+                        plan_window=(1, 1), plan_stop='plan'):
         """Decode B texts of different lengths together; item b comes out as `inference(memory[b:b+1, :L_b])` would give it
         with Prenet dropout seed seeds[b] (default: the seeds of the next B inference() calls, in item order — so a batch
         equals B sequential inference() calls).  Returns (mel (B,80,N), gate (B,N,1), alignments (B,N,T_in),
         n_frames (B,) int64 on the host), N = max n_frames; past n_frames[b]: mel 0, gate logit 1e3, alignment 0.
         The items are sorted by length and decoded in groups of at most 8 (one decode session each, attention masked to
-        each item's length, a group runs until all of its gates fired); each group on the persistent kernel when it fits."""
+        each item's length, a group runs until all of its gates fired); each group on the persistent kernel when it fits.
+        plan, n_plan, plan_window, plan_stop: the planned decode of inference(), one plan row per item; the rows travel with
+        their items through the sort and the groups.  With plan_stop = 'plan' n_frames equals n_plan."""
         B, T_in = memory.size(0), memory.size(1)
         lens = [int(x) for x in torch.as_tensor(memory_lengths).cpu().tolist()]
         if len(lens) != B or min(lens) < 1 or max(lens) > T_in:
@@ -363,6 +421,7 @@ class Decoder(nn.Module):
         seeds = [int(x) for x in seeds]
         if len(seeds) != B:
             raise ValueError("seeds: %d seeds for %d utterances" % (len(seeds), B))
+        pl = self._checked_plan(plan, n_plan, plan_window, plan_stop, B, memory.device)
         order = sorted(range(B), key=lambda b: -lens[b])
         items = [None] * B
         for g0 in range(0, B, 8):
@@ -370,7 +429,7 @@ class Decoder(nn.Module):
             L = max(lens[b] for b in idx)
             sel = torch.as_tensor(idx, device=memory.device)
             outs = self._decode_group(memory.index_select(0, sel)[:, :L].contiguous(), [lens[b] for b in idx],
-                                      [seeds[b] for b in idx], chunk, persistent)
+                                      [seeds[b] for b in idx], chunk, persistent, self._plan_rows(pl, idx, memory.device))
             for b, o in zip(idx, outs):
                 items[b] = o
         N = max(o[0].size(1) for o in items)
@@ -384,13 +443,16 @@ class Decoder(nn.Module):
             al[b, :n, :a.size(1)] = a
         return mel, gate, al, torch.tensor([o[0].size(1) for o in items], dtype=torch.int64)
 
-    def _decode_group(self, memory, lens, seeds, chunk, persistent):
+    def _decode_group(self, memory, lens, seeds, chunk, persistent, pl=None):
         """one decode session over <= 8 items; returns per item (mel (80,n), gate (n,), alignments (n,T_in))"""
         lengths = torch.tensor(lens, dtype=torch.int32).to(memory.device)
         mask = torch.arange(memory.size(1), device=memory.device)[None, :] >= lengths[:, None]
-        s = self._session(memory, mask, self.max_decoder_steps, item_seeds=seeds)
+        max_steps, thr = self._plan_steps(pl)
+        s = self._session(memory, mask, max_steps, item_seeds=seeds, pl=pl)
         s.PRE[0].copy_(self.prenet(self.get_go_frame(memory)))
-        self._run_to_end(s, chunk, persistent, 0)
+        self._run_to_end(s, chunk, persistent, 0, thr)
+        if pl is not None and pl[4] == 'plan':          # item j has the frames of its plan, whatever its gate said
+            return [(s.MEL[:n, j].t(), s.GATE[:n, j], s.AL[1:n + 1, j]) for j, n in enumerate(pl[3])]
         stops = s.stop_item.cpu().tolist()
         out = []
         for j, st in enumerate(stops):

@@ -613,13 +613,74 @@ class Synthesizer(object):
         mix = ratios[0] * self.neu + ratios[1] * self.sad + ratios[2] * self.hap + ratios[3] * self.ang
         return self.model.vae_gst.fc3(torch.as_tensor(mix, dtype=torch.float32).cuda())
 
+    RHYTHM_WINDOW = (1, 1)      # the window around a planned symbol; uncalibrated: no trained checkpoint has been decoded under a plan
+
+    def rhythm_plan(self, texts, lens, durations=None, rhythm_from=None, rhythm_scale=1.0, rhythm_window=None):
+        """The decoder's plan keywords for `texts` (lens: their symbol counts), or {} when neither durations nor rhythm_from is
+        given.  durations: per text n_symbols numbers, frames per symbol (fractions allowed); rhythm_from: per text a wav that
+        speaks the same text, whose symbol durations `self.durations` measures (a wav on which the search finds no path is a
+        ValueError naming it); rhythm_scale: a number, or per text n_symbols factors, multiplied in; rhythm_window: the
+        (back, ahead) the decoder may look around the planned symbol (default RHYTHM_WINDOW; (0, 0) reads exactly one symbol per
+        frame).  The plan is made by `t2v_hip.duration_plan` and cut at the decoder's max_decoder_steps; a text that gets no
+        frame at all is a ValueError."""
+        import t2v_hip
+        B = len(texts)
+        if durations is None and rhythm_from is None:
+            if rhythm_window is not None or not (np.isscalar(rhythm_scale) and float(rhythm_scale) == 1.0):
+                raise ValueError("rhythm_scale and rhythm_window act on a plan: give durations or rhythm_from")
+            return {}
+        if durations is not None and rhythm_from is not None:
+            raise ValueError("give durations or rhythm_from, not both")
+        if rhythm_from is not None:
+            if len(rhythm_from) != B:
+                raise ValueError("rhythm_from: %d wavs for %d texts" % (len(rhythm_from), B))
+            found = self.durations([(w, t, None, 0) for w, t in zip(rhythm_from, texts)])
+            for b, r in enumerate(found):
+                if r['durations'] is None:
+                    raise ValueError("rhythm_from: text %d has %d symbols and %s only %d frames: no monotonic path reads it"
+                                     % (b, r['n_symbols'], rhythm_from[b], r['n_frames']))
+            durations = [r['durations'] for r in found]
+        if len(durations) != B:
+            raise ValueError("durations: %d rows for %d texts" % (len(durations), B))
+        dur = np.zeros((B, max(lens)), dtype=np.float32)
+        for b, d in enumerate(durations):
+            d = np.asarray(d, dtype=np.float32).reshape(-1)
+            if d.size != lens[b]:
+                raise ValueError("durations: text %d has %d symbols, got %d durations" % (b, lens[b], d.size))
+            dur[b, :lens[b]] = d
+        if np.isscalar(rhythm_scale):
+            rate = float(rhythm_scale)
+        else:
+            if len(rhythm_scale) != B:
+                raise ValueError("rhythm_scale: %d rows for %d texts" % (len(rhythm_scale), B))
+            r = np.ones((B, max(lens)), dtype=np.float32)
+            for b, f in enumerate(rhythm_scale):
+                f = np.asarray(f, dtype=np.float32).reshape(-1)
+                if f.size != lens[b]:
+                    raise ValueError("rhythm_scale: text %d has %d symbols, got %d factors" % (b, lens[b], f.size))
+                r[b, :lens[b]] = f
+            rate = torch.from_numpy(r).cuda()
+        out = t2v_hip.duration_plan(torch.from_numpy(dur).cuda(), lens, self.model.decoder.max_decoder_steps, rate=rate)
+        for b, n in enumerate(out.n_plan.tolist()):
+            if n < 1:
+                raise ValueError("durations: text %d gets no frame" % b)
+        return dict(plan=out.plan, n_plan=out.n_plan, plan_stop='plan',
+                    plan_window=self.RHYTHM_WINDOW if rhythm_window is None else rhythm_window)
+
     @torch.no_grad()
-    def synthesize(self, text, path=None, condition_on_ref=False, ref_audio=None, ratios=(1.0, 0.0, 0.0, 0.0)):
+    def synthesize(self, text, path=None, condition_on_ref=False, ref_audio=None, ratios=(1.0, 0.0, 0.0, 0.0), durations=None,
+                   rhythm_from=None, rhythm_scale=1.0, rhythm_window=None):
         """Returns (mel_outputs_postnet (1,80,T), alignments (1,T,T_in)); writes `path` (wav through the vocoder,
-        else `<path>.npy`) when a path is given."""
+        else `<path>.npy`) when a path is given.
+        durations (n_symbols numbers), rhythm_from (a wav speaking the same text), rhythm_scale (a number or n_symbols factors),
+        rhythm_window: the rhythm of `rhythm_plan`, for this one text; the output then has the plan's frame count.  The style
+        stays what condition_on_ref / ratios say."""
         transcript_outputs = self.encode_text(text)
         encoder_outputs = transcript_outputs + self.style_vector(transcript_outputs, condition_on_ref, ref_audio, ratios)
-        mel_outputs, gate_outputs, alignments = self.model.decoder.inference(encoder_outputs)
+        plan = self.rhythm_plan([text], [transcript_outputs.size(1)], None if durations is None else [durations],
+                                None if rhythm_from is None else [rhythm_from],
+                                rhythm_scale if np.isscalar(rhythm_scale) else [rhythm_scale], rhythm_window)
+        mel_outputs, gate_outputs, alignments = self.model.decoder.inference(encoder_outputs, **plan)
         mel_outputs_postnet = mel_outputs + self.model.postnet(mel_outputs)
         if path is not None:
             if self.vocoder is not None:
@@ -633,9 +694,10 @@ class Synthesizer(object):
         audio = audio[0] if torch.is_tensor(audio) and audio.dim() > 1 else audio
         write(path, self.hparams.sampling_rate, np.asarray(torch.as_tensor(audio).detach().cpu().float()))
 
-    def _synthesize_ragged(self, texts, condition_on_ref, ref_audios, ratios, ref_mels=None):
+    def _synthesize_ragged(self, texts, condition_on_ref, ref_audios, ratios, ref_mels=None, rhythm=None):
         """The device part of synthesize_batch: (mel, mel_postnet (B,80,N), gate (B,N,1), alignments, n_frames (B,) int64 on
-        the host, text lengths).  ref_mels: `load_mels(list(dict.fromkeys(ref_audios)))` when the caller has it already."""
+        the host, text lengths).  ref_mels: `load_mels(list(dict.fromkeys(ref_audios)))` when the caller has it already.
+        rhythm: None, or the keywords of `rhythm_plan` behind (texts, lens)."""
         B = len(texts)
         if condition_on_ref and (ref_audios is None or len(ref_audios) != B):
             raise ValueError("condition_on_ref needs one reference audio per text")
@@ -665,25 +727,34 @@ class Synthesizer(object):
             styles = [self.style_vector(transcript_outputs[b:b + 1, :lens[b]], False, None, per_text[b]) for b in range(B)]
         encoder_outputs = torch.cat([transcript_outputs[b:b + 1] + styles[b].reshape(1, -1, styles[b].size(-1))[:, :1]
                                      for b in range(B)], 0)
-        mel, gate, alignments, n_frames = self.model.decoder.inference_batch(encoder_outputs, lens)
+        plan = self.rhythm_plan(texts, lens, **rhythm) if rhythm else {}
+        mel, gate, alignments, n_frames = self.model.decoder.inference_batch(encoder_outputs, lens, **plan)
         mel_postnet = mel + self.model.postnet(mel, n_frames.to(torch.int32).cuda())
         return mel, mel_postnet, gate, alignments, n_frames, lens
 
     @torch.no_grad()
-    def synthesize_batch(self, texts, paths=None, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0)):
+    def synthesize_batch(self, texts, paths=None, condition_on_ref=False, ref_audios=None, ratios=(1.0, 0.0, 0.0, 0.0),
+                         durations=None, rhythm_from=None, rhythm_scale=1.0, rhythm_window=None):
         """`synthesize` for several texts at once: returns the list of what `synthesize(texts[i], paths[i], ...)` called
         for i = 0, 1, ... in turn would return from the same model state — frame counts, mels, alignments and Prenet dropout
         masks (the decoder reserves the seeds of len(texts) consecutive inference() calls), and, with the Griffin-Lim
         vocoder and the same np.random state, the same waveforms.  The texts run through the encoder, the decoder (groups
         of <= 8, sorted by length) and the Postnet as one ragged batch; each is masked to its own length.
         ratios: one (neu, sad, hap, ang) tuple for all texts, or one per text; ref_audios: one path per text
-        (condition_on_ref); paths: None or one output path per text (wav through the vocoder, else `<path>.npy`)."""
+        (condition_on_ref); paths: None or one output path per text (wav through the vocoder, else `<path>.npy`).
+        durations, rhythm_from (one entry per text), rhythm_scale, rhythm_window: the rhythm of `rhythm_plan`.  Text i then
+        has the frames of its plan and reads symbol j over the frames the plan gives it."""
         B = len(texts)
         if B == 0:
             return []
         if paths is not None and len(paths) != B:
             raise ValueError("paths: %d paths for %d texts" % (len(paths), B))
-        mel, mel_postnet, _, alignments, n_frames, lens = self._synthesize_ragged(texts, condition_on_ref, ref_audios, ratios)
+        rhythm = dict(durations=durations, rhythm_from=rhythm_from, rhythm_scale=rhythm_scale, rhythm_window=rhythm_window)
+        if durations is None and rhythm_from is None:
+            self.rhythm_plan(texts, [], **rhythm)          # (refuses a scale or a window without a plan)
+            rhythm = None
+        mel, mel_postnet, _, alignments, n_frames, lens = self._synthesize_ragged(texts, condition_on_ref, ref_audios, ratios,
+                                                                                  rhythm=rhythm)
         n = n_frames.tolist()
         out = [(mel_postnet[b:b + 1, :, :n[b]], alignments[b:b + 1, :n[b], :lens[b]]) for b in range(B)]
         if paths is not None:
@@ -842,7 +913,7 @@ class Synthesizer(object):
 
     @torch.no_grad()
     def evaluate(self, rows, batch_size=8, condition='ref', prosody=False, alignment=False, style=False, style_k=5, aligned=False,
-                 energy=False, voice=False, durations=False, max_step=1):
+                 energy=False, voice=False, durations=False, max_step=1, rhythm=None, rhythm_window=None):
         """Score filelist rows (audio_path, text, speaker, emotion) by free-running synthesis: each text is synthesised
         (`synthesize_batch`, batch_size rows at a time, in input order) and compared with its own recording.  condition='ref':
         the style comes from that recording (copy synthesis; its mel is computed once, for the style and for the comparison);
@@ -866,11 +937,20 @@ class Synthesizer(object):
         style: `scoring.style_mu` per group and `scoring.style_records` after the last, evaluation.STYLE_KEYS; None for a row
         decoded to fewer than the encoder's 2 frames.  style_k is lowered to (distinct recordings - 1) when there are too few;
         fewer than 2 distinct recordings, or one path under two labels, is a ValueError.  The result is then an
-        evaluation.StyleRecords: the same list, with `style_info` for `evaluation.summarize`."""
+        evaluation.StyleRecords: the same list, with `style_info` for `evaluation.summarize`.
+        rhythm: None, or 'ref': every synthesis is decoded along the symbol durations of its own recording (`rhythm_plan` with
+        rhythm_from = the row's wav, rhythm_window around each planned symbol), which takes rhythm out of the comparison: the
+        synthesis has the recording's frame count, and what is left in the scores is not timing.  Every record then holds
+        'rhythm': 'ref'; without it the records hold the keys they held.  A recording whose text has more symbols than its
+        frames can reach is a ValueError naming the row."""
         import scoring
         import t2v_hip
         if condition not in ('ref', 'emotion'):
             raise ValueError("condition must be 'ref' or 'emotion', got %r" % (condition,))
+        if rhythm not in (None, 'ref'):
+            raise ValueError("rhythm must be None or 'ref', got %r" % (rhythm,))
+        if rhythm is None and rhythm_window is not None:
+            raise ValueError("rhythm_window acts on a plan: give rhythm='ref'")
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
         if self.model is None:
@@ -916,10 +996,11 @@ class Synthesizer(object):
             uniq = list(dict.fromkeys(paths))
             wavs = self.load_wavs(uniq)
             mels = self._mels_of(*wavs)
+            timing = dict(rhythm=dict(rhythm_from=paths, rhythm_window=rhythm_window)) if rhythm else {}
             if condition == 'ref':
-                synthesis = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), mels)
+                synthesis = self._synthesize_ragged(texts, True, paths, (1.0, 0.0, 0.0, 0.0), mels, **timing)
             else:
-                synthesis = self._synthesize_ragged(texts, False, None, [one_hot[row[3]] for row in group])
+                synthesis = self._synthesize_ragged(texts, False, None, [one_hot[row[3]] for row in group], **timing)
             g = scoring.Group(self, group, synthesis, uniq, wavs, mels, waveforms=prosody or energy or voice)
             parts = [scoring.plain(g)]
             if alignment:
@@ -934,6 +1015,8 @@ class Synthesizer(object):
                 parts.append(scoring.aligned(g, f0=prosody, energy=energy, voice=voice))
             if durations:
                 parts.append(scoring.durations(g, int(max_step), f0=prosody))
+            if rhythm:
+                parts.append([{'rhythm': rhythm}] * len(group))
             if style:
                 syn_mu += scoring.style_mu(g, rec_mu)
             records += [{k: v for fields in parts for k, v in fields[b].items()} for b in range(len(group))]
@@ -982,7 +1065,37 @@ def build_arg_parser():
     from wavio import add_wav_arguments
     add_wav_arguments(p)
     add_tempo_arguments(p)
+    add_rhythm_arguments(p)
     return p
+
+
+def add_rhythm_arguments(p):
+    """--rhythm_from, --durations, --rhythm_scale and --rhythm_window: decode along a duration plan (Synthesizer.rhythm_plan)"""
+    from evaluation import parse_attention_window
+    p.add_argument('--rhythm_from', default=None, metavar='WAV',
+                   help="say every text with the timing of this recording of the same text: its symbol durations, measured by "
+                        "forced alignment, become the decoder's plan")
+    p.add_argument('--durations', default=None, metavar='FILE.npz',
+                   help="frames per symbol as extract_durations.py writes them, row i for text i")
+    p.add_argument('--rhythm_scale', type=float, default=1.0, metavar='R',
+                   help="factor on every planned duration (2 is twice as slow); needs --rhythm_from or --durations")
+    p.add_argument('--rhythm_window', type=parse_attention_window, default=None, metavar='BACK,AHEAD',
+                   help="positions the decoder may look behind and in front of the planned symbol (default 1,1, an "
+                        "uncalibrated choice; 0,0 reads exactly the planned symbol)")
+
+
+def read_durations(path, n_texts):
+    """the rows of an extract_durations.py file as a list of n_texts float32 arrays; SystemExit when the file has another
+    number of rows or a row without a path (durations -1)"""
+    with np.load(path) as z:
+        offsets, durations = z['offsets'], z['durations']
+    if len(offsets) - 1 != n_texts:
+        raise SystemExit("--durations: %s holds %d rows for %d texts" % (path, len(offsets) - 1, n_texts))
+    rows = [durations[offsets[i]:offsets[i + 1]].astype(np.float32) for i in range(n_texts)]
+    for i, r in enumerate(rows):
+        if r.size and r.min() < 0:
+            raise SystemExit("--durations: row %d of %s has no path (its durations are -1)" % (i, path))
+    return rows
 
 
 def add_tempo_arguments(p):
@@ -1038,6 +1151,12 @@ def parse_args(argv=None):
     if (args.formant != 0.0 or args.preserve_formants) and args.vocoder is None:
         raise SystemExit("--formant / --preserve_formants act in the built-in vocoder: give --vocoder")
     tempo_options(args)
+    if args.rhythm_from is not None and args.durations is not None:
+        raise SystemExit("--rhythm_from and --durations both set the plan: give one")
+    if args.rhythm_from is None and args.durations is None and (args.rhythm_scale != 1.0 or args.rhythm_window is not None):
+        raise SystemExit("--rhythm_scale / --rhythm_window act on a plan: give --rhythm_from or --durations")
+    if not args.rhythm_scale > 0.0:
+        raise SystemExit("--rhythm_scale must be > 0")
     return args
 
 
@@ -1052,11 +1171,19 @@ def main(argv=None):
     syn = Synthesizer(hp, attention_window=args.attention_window, **tempo_options(args), **wav_options(args)).load(args.load_path, vocoder=args.vocoder, filelist_path=args.filelist_path, **weights_option(args))
     os.makedirs(args.sample_path, exist_ok=True)
     texts = args.texts
+    planned = read_durations(args.durations, len(texts)) if args.durations is not None else None
     for i0 in range(0, len(texts), args.batch_size):
         chunk = texts[i0:i0 + args.batch_size]
         paths = [os.path.join(args.sample_path, str(i0 + j) + ('.wav' if syn.vocoder is not None else '')) for j in range(len(chunk))]
+        rhythm = {}                                 # without the rhythm flags the call is the one it always was
+        if planned is not None:
+            rhythm = dict(durations=planned[i0:i0 + len(chunk)])
+        elif args.rhythm_from is not None:
+            rhythm = dict(rhythm_from=[args.rhythm_from] * len(chunk))
+        if rhythm:
+            rhythm.update(rhythm_scale=args.rhythm_scale, rhythm_window=args.rhythm_window)
         syn.synthesize_batch(chunk, paths, args.ref_audio is not None,
-                             [args.ref_audio] * len(chunk) if args.ref_audio else None, args.ratios)
+                             [args.ref_audio] * len(chunk) if args.ref_audio else None, args.ratios, **rhythm)
         for p in paths:
             print(p if syn.vocoder is not None else p + '.npy')
 

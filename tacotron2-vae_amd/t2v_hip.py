@@ -2750,6 +2750,84 @@ def check_attention_window(window):
     return vals
 
 
+PLAN_MAX_SYMBOLS = _ABI.define('T2V_PLAN_MAX_SYMBOLS')      # the frame ends of a row sit in LDS
+PLAN_MAX_FRAMES_PER_SYMBOL = 2 ** 20
+
+DurationPlan = collections.namedtuple('DurationPlan', 'plan n_plan')
+DurationPlan.__doc__ = """What duration_plan() returns.  plan (B, T_max) int32: the symbol of every frame, the last one held
+behind n_plan[b] (0 for an empty plan); n_plan (B,) int32: min(total frames, T_max)."""
+
+
+def duration_plan(dur, n_ids, T_max, rate=None):
+    """Length regulator (csrc/plan.hip k_duration_plan): symbol durations -> the frame-by-frame plan of a planned decode.
+    dur: (B, S) float32 CUDA tensor, frames per symbol (fractions allowed); n_ids: B symbol counts in 0..S (a list, a CPU or a
+    device tensor); rate: None, a number, or a (B, S) float32 tensor of factors multiplied in; T_max: the plan's width.
+    In integers (include/t2vae.h): q_j = rint(dur_j rate_j 65536) in fp64, C = cumsum(q), E_j = (C_j + 32768) >> 16; symbol j
+    owns the frames E_{j-1} <= t < E_j (none: skipped); n_plan = min(E_last, T_max).  A row gives the same plan alone and in
+    any batch.  Returns a DurationPlan.  A row with a negative or non-finite dur * rate, or one above 2^20 frames per symbol,
+    is a ValueError naming the row (this reads n_plan back: one synchronisation)."""
+    lib = load_library()
+    if not torch.is_tensor(dur) or dur.dim() != 2 or dur.dtype != torch.float32 or dur.size(0) < 1 or dur.size(1) < 1:
+        raise ValueError("duration_plan: dur must be a non-empty float32 (B, S) tensor, got %s %s"
+                         % (getattr(dur, 'dtype', type(dur)), tuple(getattr(dur, 'shape', ()))))
+    if not dur.is_cuda:
+        raise T2VHipError("duration_plan: dur %s lives on %s; this path has no CPU fallback" % (tuple(dur.shape), dur.device))
+    B, S = dur.shape
+    if S > PLAN_MAX_SYMBOLS:
+        raise ValueError("duration_plan: %d symbols per row; at most %d are supported" % (S, PLAN_MAX_SYMBOLS))
+    if isinstance(T_max, bool) or int(T_max) != T_max or not 1 <= T_max <= 2 ** 31 - 1:
+        raise ValueError("duration_plan: T_max %r must be an integer >= 1" % (T_max,))
+    T_max = int(T_max)
+    dev = dur.device
+    dur = dur.contiguous()
+    L = _checked_lengths(n_ids, B, 0, S, "duration_plan: n_ids must be %d integer symbol counts" % B,
+                         "duration_plan: every n_ids must be in 0..%d (symbols stored per row)" % S).to(dev)
+    rsb = rsj = 0
+    if rate is None:
+        r = None
+    elif torch.is_tensor(rate) and rate.dim() > 0:
+        if rate.shape != dur.shape or rate.dtype != torch.float32 or rate.device != dev:
+            raise ValueError("duration_plan: a rate tensor must be float32 %s on %s, got %s %s on %s"
+                             % (tuple(dur.shape), dev, rate.dtype, tuple(rate.shape), rate.device))
+        r, rsb, rsj = rate.contiguous(), S, 1
+    else:
+        r = torch.full((1,), float(rate), dtype=torch.float32).to(dev)       # a scalar on the device: both strides 0
+    plan = torch.empty(B, T_max, device=dev, dtype=torch.int32)
+    n_plan = torch.empty(B, device=dev, dtype=torch.int32)
+    _check(lib.t2v_duration_plan(_p(dur), S, _p(L), _p(r), rsb, rsj, B, S, T_max, _p(plan), T_max, _p(n_plan), _stream()),
+           't2v_duration_plan')
+    bad = [b for b, n in enumerate(n_plan.tolist()) if n < 0]
+    if bad:
+        raise ValueError("duration_plan: row %s: every dur * rate must be finite and in 0..%d frames"
+                         % (', '.join(str(b) for b in bad), PLAN_MAX_FRAMES_PER_SYMBOL))
+    return DurationPlan(plan, n_plan)
+
+
+def check_plan(plan, n_plan, B, max_steps, device, window):
+    """The plan of a planned decode (include/t2vae.h t2v_decoder_infer_steps_plan), checked on the host: plan an int32 (B, N)
+    tensor on `device` with last stride 1 and N <= max_steps columns, n_plan B int32 counts on `device` in 1..N, `window` a
+    (back, ahead).  Returns (plan, n_plan as a host list); anything else raises ValueError.  Reads n_plan back (one
+    synchronisation, at session set-up)."""
+    if window is None:
+        raise ValueError("a plan needs a window (back, ahead) around its symbols; (0, 0) is the one-hot form")
+    for name, t in (('plan', plan), ('n_plan', n_plan)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise ValueError("%s must be an int32 tensor, got %s" % (name, getattr(t, 'dtype', type(t))))
+        if t.device != torch.device(device):
+            raise ValueError("%s lives on %s; the decode runs on %s" % (name, t.device, device))
+    if plan.dim() != 2 or plan.size(0) != B or plan.size(1) < 1 or (plan.size(1) > 1 and plan.stride(1) != 1) or \
+            (B > 1 and plan.stride(0) < plan.size(1)):
+        raise ValueError("plan must be (%d, N >= 1) with rows of stride 1, got %s strides %s" % (B, tuple(plan.shape), plan.stride()))
+    if tuple(n_plan.shape) != (B,):
+        raise ValueError("n_plan must hold %d frame counts, got %s" % (B, tuple(n_plan.shape)))
+    n = n_plan.tolist()
+    if min(n) < 1 or max(n) > plan.size(1):
+        raise ValueError("every n_plan must be in 1..%d (the plan's columns), got %s" % (plan.size(1), n))
+    if max(n) > max_steps:
+        raise ValueError("a plan of %d frames is longer than the %d decoder steps of this session" % (max(n), max_steps))
+    return plan, n
+
+
 class InferenceSession(object):
     """Arena + packed weights of one free-running decode (Decoder.inference / the per-step
     initialize_decoder_states → prenet → decode call sequence of synthesizer.py:135-154)."""
@@ -2757,7 +2835,7 @@ class InferenceSession(object):
 
     def __init__(self, memory, pm, lengths, w_ih_att, w_hh_att, b_att, w_ih_dec, w_hh_dec, b_dec, wq, loc_conv,
                  loc_dense, v, prenet_w0, prenet_w1, proj_w, proj_b, gate_w, gate_b, max_steps, item_seeds=None,
-                 attention_window=None):
+                 attention_window=None, plan=None, n_plan=None, n_plan_host=None):
         if 'T2V_HOST_THREADS' in os.environ:        # (an inference session no longer throttles the host application)
             limit_host_threads()
         lib = _require_gpu(memory, pm, w_ih_att)
@@ -2810,6 +2888,27 @@ class InferenceSession(object):
         # the previous frame's largest weight (include/t2vae.h t2v_dec_window); both decode loops, every run of this session
         self.attention_window = check_attention_window(attention_window)
         self._window = None if self.attention_window is None else _DecWindow(*self.attention_window)
+        # plan (B, N) int32, n_plan (B) int32 on the device: the window's centre of frame t is plan[b, min(t, n_plan[b] - 1)]
+        # instead of the previous frame's largest weight (include/t2vae.h t2v_decoder_infer_steps_plan); both decode loops
+        # (n_plan_host: the counts as a check_plan of the caller's has read them back already; no second synchronisation)
+        self.plan = self.n_plan = self.n_plan_host = None
+        if plan is not None or n_plan is not None:
+            if n_plan_host is None:
+                plan, n_plan_host = check_plan(plan, n_plan, B, self.max_steps, dev, self.attention_window)
+            self.plan, self.n_plan, self.n_plan_host = plan, n_plan, [int(x) for x in n_plan_host]
+
+    def _constrained(self, name, args):
+        """the entry point and arguments of a run under the session's constraints: *_plan (items or NULL, the window, the
+        plan), *_window (items or NULL, the window), *_items, or the plain entry"""
+        items = None if self._items is None else C.byref(self._items)
+        if self.plan is not None:
+            stride = self.plan.stride(0) if self.B > 1 else self.plan.size(1)
+            return name + '_plan', args + [items, C.byref(self._window), _p(self.plan), stride, _p(self.n_plan)]
+        if self._window is not None:
+            return name + '_window', args + [items, C.byref(self._window)]
+        if self._items is not None:
+            return name + '_items', args + [items]
+        return name, args
 
     def _stage_arena(self):
         if self.S is not None:
@@ -2843,10 +2942,7 @@ class InferenceSession(object):
                              _p(self.AL), _p(self.stop), _p(self._gran), _p(self._perr))
         name, args = 't2v_decoder_infer_persistent', [C.byref(W), C.byref(Bf), self.B, self.T_in, self.max_steps,
                                                       float(gate_threshold), float(p_prenet), int(seed)]
-        if self._window is not None:        # the *_window entry point: items (or NULL), then the window
-            name, args = name + '_window', args + [None if self._items is None else C.byref(self._items), C.byref(self._window)]
-        elif self._items is not None:       # per-item seeds and stop frames: the *_items entry point takes them behind the seed
-            name, args = name + '_items', args + [C.byref(self._items)]
+        name, args = self._constrained(name, args)
         _check(getattr(lib, name)(*args, _stream()), name)
 
     def persistent_timed_out(self):
@@ -2871,10 +2967,7 @@ class InferenceSession(object):
                                  _p(self.wqT), _p(self.wcomb), _p(self.v))
         name, args = 't2v_decoder_infer_steps', [C.byref(self.W), C.byref(self.S), self.B, self.T_in, int(t0), int(t1),
                                                  float(gate_threshold), float(p_prenet), int(bool(external_prenet)), int(seed)]
-        if self._window is not None:
-            name, args = name + '_window', args + [None if self._items is None else C.byref(self._items), C.byref(self._window)]
-        elif self._items is not None:
-            name, args = name + '_items', args + [C.byref(self._items)]
+        name, args = self._constrained(name, args)
         _check(getattr(load_library(), name)(*args, _stream()), name)
 
 
