@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 
 import distributed as t2v_dist
+from graph_cache import CAPTURE, COMPARE, REPLAY, GraphCache
 from hparams import create_hparams
 from loss_function import Tacotron2Loss_VAE
 from model import BatchLayout, Tacotron2
@@ -97,6 +98,13 @@ class TrainEngine(object):
 
     GRAPH_AFTER = 2          # eager executions of a shape before it is captured (allocator / lazy-init warm-up)
     MAX_GRAPHS = 8
+    _test_after_replay = None    # tests: called with the span of every replayed graph (a time-out inside a REPLAY)
+
+    # what the graph cache knows, under the names the benchmark, the tools and the tests read
+    graph_fallbacks = property(lambda self: self._cache.fallbacks)
+    graph_watchdog = property(lambda self: self._cache.watchdog, lambda self, on: setattr(self._cache, 'watchdog', bool(on)))
+    _graphs = property(lambda self: self._cache.live())             # shape key -> Entry, least recently replayed first
+    _no_graph = property(lambda self: self._cache.verdicts())       # shape key -> (replay ms, eager ms) of a graph that was dropped
 
     def __init__(self, hparams, world_size=1, graph=None, force_dist=False):
         import t2v_hip
@@ -124,22 +132,13 @@ class TrainEngine(object):
         # bucket overlap of the eager engine is given up for it: an eager step is host-bound (1 860 launches: 23-32 ms
         # depending on the host), the exposed all-reduce of 115 MB costs well under 1 ms
         self.graph_ddp = self.use_graph and self.allreduce is not None
-        self._graphs = {}
-        self._seen = {}
-        # round 5: the replay watchdog.  A captured step is a DAG of ~220 nodes and ROCm's graph executor decides how its branches
-        # share the runtime's queues (four by default; DESIGN 4.0f: the same graph replays in 11.3 ms on 4 queues, 13.5 ms on 6) —
-        # a replay that is SLOWER than the same step issued eagerly means the executor serialised independent branches.  The second
-        # and third replay of every new graph are timed with events, the step after them is issued EAGERLY once (a valid training
-        # step like any other — the warm-up executions before the capture are no baseline: allocator growth and lazy initialisation
-        # make them several times slower) and timed the same way; a graph that loses by more than WATCHDOG_MS (+ 5 %) is dropped and
-        # the shape keeps running eagerly (one host sync per captured shape; T2V_GRAPH_WATCHDOG=0 switches it off).  Rank-local in a
-        # multi-rank job: replay-or-eager is every rank's own choice already (see _body).
-        self.graph_watchdog = os.environ.get('T2V_GRAPH_WATCHDOG', '1') != '0'
-        self._probe = {}            # shape key -> [(start, end) events of the first replays] (None entries once decided)
-        self._no_graph = {}         # shape key -> (replay ms, eager ms) of a graph that was dropped
-        self._suspect = {}          # shape key -> eager ms of a graph that lost the first comparison and is being re-timed
-        self._pending_key = None
-        self.graph_fallbacks = 0
+        # which shapes replay a captured graph and which run eagerly, replay watchdog included (T2V_GRAPH_WATCHDOG=0 switches it off)
+        self._cache = GraphCache(lambda: torch.cuda.Event(enable_timing=True), t2v_hip.err_release, self.GRAPH_AFTER, self.MAX_GRAPHS,
+                                 watchdog=os.environ.get('T2V_GRAPH_WATCHDOG', '1') != '0')
+        self._compare_key = None    # shape whose eager comparison step this step is (never outlives the step)
+        self._calib_want = False    # multi-rank graph mode, comparison step: _body marks the end of the timed region in _calib_end
+        self._calib_end = None
+        self._eager_events = []     # end events of the last two eager steps
         self._test_replay_drag_us = 0   # tests: a kernel that holds 8 workgroups for this long behind every probed replay
         # (round 6, T2V_MAIN_PRIO=-1 — the higher of the two stream priorities for this stream — measured: alone it buys the bf16 step
         # 12.34 -> 12.28 ms and the fp32 step nothing, but the THIRD engine of one process (bench.py's secondary bf16 leg) then replays at
@@ -182,7 +181,7 @@ class TrainEngine(object):
         sp, self.step_params = self.step_params, None
         if sp is not None:
             t2v_hip.drop_step_params(sp)
-        self._drop_graphs()         # (their error-ledger blocks go back to the free list)
+        self._cache.clear()         # (the graphs' error-ledger blocks go back to the free list)
         prev, self._host_threads = getattr(self, '_host_threads', None), None
         if prev is not None and prev > torch.get_num_threads():
             torch.set_num_threads(prev)         # the host-thread cap belonged to this engine's loop
@@ -269,7 +268,7 @@ class TrainEngine(object):
             # rank sees different shapes), so the collective pattern must not depend on that choice — the bucketed
             # hook-issued exchange below belongs to the eager engine only
             fb = self._body_fb(x, y, iteration)
-            if self.__dict__.get('_calib_want'):      # the watchdog's eager comparison step: timed up to here, like a probed replay
+            if self._calib_want:      # the watchdog's eager comparison step: timed up to here, like a probed replay
                 self._calib_end = torch.cuda.Event(enable_timing=True)
                 self._calib_end.record()
             return self._reduce_and_step(fb)
@@ -342,14 +341,10 @@ class TrainEngine(object):
               % ", ".join(labels))
         t2v_hip.DecoderCore.persistent = False
         t2v_hip.DecoderCore.persistent_bwd = False
-        self._drop_graphs()
-        self._seen.clear()
         # the watchdog's timings belong to the graphs (and the kernel set) that just went: a re-captured graph on the launch-per-step
         # kernels is probed from scratch, and a shape dropped because it lost against the old eager step gets another chance
-        self._probe.clear()
-        self._suspect.clear()
-        self._no_graph.clear()
-        self._pending_key = None
+        self._cache.clear()
+        self._compare_key = None
         if self._bn_snap is not None:
             torch._foreach_copy_(self._bn_bufs, self._bn_snap)
         self.optimizer.step_count = max(0, self.optimizer.step_count - 1)
@@ -428,11 +423,10 @@ class TrainEngine(object):
         import t2v_hip
         self._err_mark = t2v_hip.err_mark()
         self._err_span = None
-        self._pending_key = None        # (a calibration request never outlives the step that made it)
+        self._compare_key = None        # (a comparison request never outlives the step that made it)
         self._calib_end = None
-        for span in self.__dict__.pop('_release_later', ()):
-            t2v_hip.err_release(span)   # ledger block of a graph the watchdog dropped during the PREVIOUS step (its words were
-                                        # still that step's error record: released only now, after the caller's check; ADVICE r5)
+        self._cache.flush_released()    # ledger block of a graph the watchdog dropped during the PREVIOUS step (its words were
+                                        # still that step's error record: released only now, after the caller's check)
         if self._bn_snap is None:
             self.note_good_step()       # BatchNorm statistics as loaded (checkpoint / warm start included): what a time-out on
                                         # the very first step restores
@@ -441,30 +435,46 @@ class TrainEngine(object):
             opt.param_groups[0]['lr'] = learning_rate
         w = self._publish(iteration)
         graphable = self.use_graph and self.model.training
+        out = None
         if not any(t.is_cuda for t in batch):
             # host batch: one pinned staging buffer, one H2D copy — straight into the static input buffer of the
             # captured graph when this shape has one
             lay = BatchLayout(batch)
             if graphable:
-                out = self._graph_step_staged(lay, batch, iteration)
-                if out is not None:
-                    return out[0], out[1], out[2], w, out[3]
-            x, y = lay.views(lay.upload(batch))
+                def make_static():
+                    buf = torch.empty(lay.nbytes, dtype=torch.uint8, device='cuda')
+                    lay.upload(batch, into=buf)
+                    return lay.views(buf) + ([buf],)
+                out = self._graph_step(('staged',) + lay.key, make_static, lambda static: lay.upload(batch, into=static[0]), iteration)
+            if out is None:
+                x, y = lay.views(lay.upload(batch))
         else:           # the device front end already produced device tensors
             x, y = self.model.parse_batch(batch)
             if graphable:
-                out = self._graph_step(x, y, iteration)
-                if out is not None:
-                    return out[0], out[1], out[2], w, out[3]
+                tensors = [t for t in x if torch.is_tensor(t)] + list(y)
+
+                def make_static():
+                    static_x = tuple(t.clone() if torch.is_tensor(t) else t for t in x)
+                    static_y = tuple(t.clone() for t in y)
+                    return static_x, static_y, [t for t in static_x if torch.is_tensor(t)] + list(static_y)
+
+                def load(static):
+                    for dst, src in zip(static, tensors):
+                        if dst.data_ptr() != src.data_ptr():
+                            dst.copy_(src, non_blocking=True)
+                key = tuple((tuple(t.shape), str(t.dtype)) for t in tensors) + (int(x[3]),)
+                out = self._graph_step(key, make_static, load, iteration)
+        if out is not None:
+            return out[0], out[1], out[2], w, out[3]
         # Eager steps: keep the host at most two steps ahead of the GPU (it issues a step in ~5.5 ms, the GPU needs 13.5): a
         # caller that never reads a result back (the reference loop does, train.py:230 `loss.item()`) would otherwise run
         # hundreds of steps ahead until the hardware queue is full.
-        ring = self.__dict__.setdefault('_eager_events', [])
+        ring = self._eager_events
         if len(ring) >= 2:
             ring.pop(0).synchronize()
-        key, self._pending_key = self._pending_key, None
+        key, self._compare_key = self._compare_key, None
         t0 = None
-        if key is not None and self.graph_watchdog:      # the calibration step of a freshly captured shape (see __init__)
+        if key is not None:      # the watchdog's eager comparison step of a freshly captured shape (graph_cache.py)
             t0 = torch.cuda.Event(enable_timing=True)
             t0.record()
         self._calib_want = t0 is not None
@@ -473,206 +483,46 @@ class TrainEngine(object):
         ev = torch.cuda.Event(enable_timing=t0 is not None)
         ev.record()
         if t0 is not None:
-            self._watchdog_decide(key, t0, self._calib_end or ev)
+            self._cache.compared(key, t0, self._calib_end or ev)
         ring.append(ev)
         return loss, recon, kl, w, grad_norm
 
     # -- graph path
-    def _graph_step_staged(self, lay, batch, iteration):
-        key = ('staged',) + lay.key
-        if key in self._no_graph:
-            return None
-        entry = self._graphs.get(key)
-        if entry is None:
-            n = self._seen.get(key, 0)
-            self._seen[key] = n + 1
-            if n < self.GRAPH_AFTER:
-                self._trim_seen()
-                return None
-            self._evict_graphs()
-            static_buf = torch.empty(lay.nbytes, dtype=torch.uint8, device='cuda')
-            lay.upload(batch, into=static_buf)
-            x, y = lay.views(static_buf)
-            cap = self._capture_static(x, y, iteration)
+    def _graph_step(self, key, make_static, load, iteration):
+        """One sight of the shape `key`: the step's results when it ran as a graph, None when it has to run eagerly (a shape that is
+        still warming up, the watchdog's comparison step, a dropped graph, no ledger block free for the capture).
+        make_static() -> (x, y, static inputs) holding this batch, for a capture; load(static inputs) brings this batch into the
+        static inputs of a graph that exists."""
+        what, entry = self._cache.sight(key)
+        if what == CAPTURE:
+            static_x, static_y, static = make_static()
+            cap = self._capture_static(static_x, static_y, iteration)
             if cap is None:
                 return None
-            graph, out, no_grad, span = cap
-            entry = self._graphs[key] = (graph, static_buf, out, no_grad, span)
-        elif self._calibration_due(key):
-            return None                                 # this one step runs eagerly and is timed
+            self._cache.store(key, cap[0], static, *cap[1:])
+        elif what == REPLAY:
+            load(entry.static)
         else:
-            lay.upload(batch, into=entry[1])
-        self._graphs[key] = self._graphs.pop(key)       # most recently used last
-        t0 = self._probe_begin(key)
-        entry[0].replay()
-        t1 = self._probe_mark(t0)
-        out = self._after_replay(entry[2], entry[3], entry[4])
-        self._probe_end(key, t0, t1)
-        return out
-
-    def _graph_step(self, x, y, iteration):
-        import t2v_hip
-        tensors = [t for t in x if torch.is_tensor(t)] + list(y)
-        key = tuple((tuple(t.shape), str(t.dtype)) for t in tensors) + (int(x[3]),)
-        if key in self._no_graph:
+            if what == COMPARE:
+                self._compare_key = key
             return None
-        entry = self._graphs.get(key)
-        if entry is None:
-            n = self._seen.get(key, 0)
-            self._seen[key] = n + 1
-            if n < self.GRAPH_AFTER:
-                self._trim_seen()
-                return None
-            self._evict_graphs()
-            entry = self._capture(x, y, iteration)
-            if entry is None:
-                return None
-            self._graphs[key] = entry
-        elif self._calibration_due(key):
-            return None
-        self._graphs[key] = self._graphs.pop(key)       # most recently used last
-        graph, static_in, static_out, no_grad, span = entry
-        for dst, src in zip(static_in, tensors):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src, non_blocking=True)
-        t0 = self._probe_begin(key)
-        graph.replay()
-        t1 = self._probe_mark(t0)
-        out = self._after_replay(static_out, no_grad, span)
-        self._probe_end(key, t0, t1)
-        return out
+        return self._cache.replay(key, self._after_replay, self._replay_drag if self._test_replay_drag_us else None)
 
-    # -- replay watchdog (see __init__)
-    PROBE_REPLAYS = 3           # the first replay (executor set-up) is not counted
-    PROBE_CONFIRM = 3           # replays timed behind the eager comparison step before a suspect graph is dropped
-    WATCHDOG_MS = 0.5
-
-    def _probe_begin(self, key):
-        # PROBE_REPLAYS replays in front of the eager comparison step, PROBE_CONFIRM more behind it (a suspect graph only)
-        n = len(self._probe.get(key, ()))
-        if not self.graph_watchdog or n >= self.PROBE_REPLAYS + self.PROBE_CONFIRM or (n >= self.PROBE_REPLAYS and key not in self._suspect):
-            return None
-        t0 = torch.cuda.Event(enable_timing=True)
-        t0.record()
-        return t0
-
-    def _probe_mark(self, t0):
-        """end of the probed region = right behind the replay, BEFORE _after_replay: in the multi-rank graph engine that call runs
-        the whole-arena all-reduce, whose duration depends on what the peer ranks are doing (warm-up, capture, their own
-        calibration) — the watchdog compares what this rank's executor did with the graph, nothing else"""
-        if t0 is None:
-            return None
+    def _replay_drag(self):
         import t2v_hip
-        if self._test_replay_drag_us:
-            t2v_hip.load_library().t2v_debug_spin(8, int(self._test_replay_drag_us), t2v_hip._stream())
-        t1 = torch.cuda.Event(enable_timing=True)
-        t1.record()
-        return t1
+        t2v_hip.load_library().t2v_debug_spin(8, int(self._test_replay_drag_us), t2v_hip._stream())
 
-    def _probe_end(self, key, t0, t1):
-        if t0 is None:
-            return
-        probes = self._probe.setdefault(key, [])
-        probes.append((t0, t1))
-        if key in self._suspect and len(probes) == self.PROBE_REPLAYS + self.PROBE_CONFIRM:
-            self._watchdog_confirm(key)
-
-    def _calibration_due(self, key):
-        """True exactly once per captured shape: when its probed replays are in and the eager comparison step is still to come"""
-        probes = self._probe.get(key)
-        if (not self.graph_watchdog or probes is None or len(probes) != self.PROBE_REPLAYS or probes[-1] is None
-                or key in self._suspect):
-            return False
-        self._pending_key = key
-        return True
-
-    def _watchdog_decide(self, key, e0, e1):
-        """after the eager comparison step: a graph that lost is SUSPECT — PROBE_CONFIRM more replays are timed before it is dropped
-        (one slow pair of replays next to one lucky eager step is noise, e.g. with a neighbour process on the GPU)"""
-        probes = self._probe.get(key)
-        if not probes or probes[-1] is None:
-            return
-        e1.synchronize()
-        eager_ms = e0.elapsed_time(e1)
-        replay_ms = min(a.elapsed_time(b) for a, b in probes[1:])
-        if replay_ms > eager_ms * 1.05 + self.WATCHDOG_MS:
-            self._suspect[key] = eager_ms
-        else:
-            self._probe[key] = [None] * (self.PROBE_REPLAYS + self.PROBE_CONFIRM)       # (events released; the count stops further probing)
-
-    def _watchdog_confirm(self, key):
-        import t2v_hip
-        probes = self._probe[key]
-        probes[-1][1].synchronize()
-        eager_ms = self._suspect.pop(key)
-        replay_ms = min(a.elapsed_time(b) for a, b in probes[1:])
-        self._probe[key] = [None] * (self.PROBE_REPLAYS + self.PROBE_CONFIRM)
-        if replay_ms > eager_ms * 1.05 + self.WATCHDOG_MS:
-            entry = self._graphs.pop(key, None)
-            if entry is not None:
-                # NOT released here: this is the graph that was replayed in this very step — its block holds the step's error
-                # words until the caller's check_async_errors() has run (_step releases it at the top of the next step)
-                self.__dict__.setdefault('_release_later', []).append(entry[-1])
-            self._no_graph[key] = (replay_ms, eager_ms)
-            self.graph_fallbacks += 1
-            print("TrainEngine: the captured graph of this batch shape replays in %.2f ms (best of %d), the same step issued eagerly takes "
-                  "%.2f ms — the graph executor serialised independent branches; the shape keeps running eagerly" % (
-                      replay_ms, len(probes) - 1, eager_ms), flush=True)
-
-    MAX_SEEN = 4096
-
-    def _evict_graphs(self):
-        """a ragged loader (shapes that recur now and then) must not pin MAX_GRAPHS private pools for ever — the
-        least recently replayed graph (and its activation pool) goes when a new shape wants a slot"""
-        import t2v_hip
-        while len(self._graphs) >= self.MAX_GRAPHS:
-            old = next(iter(self._graphs))
-            t2v_hip.err_release(self._graphs[old][-1])       # its ledger block goes back to the free list (ADVICE r4)
-            del self._graphs[old]
-            self._seen.pop(old, None)
-            self._probe.pop(old, None)          # (a shape that comes back is warmed up, captured and probed again)
-            self._suspect.pop(old, None)
-
-    def _drop_graphs(self):
-        import t2v_hip
-        for entry in self._graphs.values():
-            t2v_hip.err_release(entry[-1])
-        self._graphs.clear()
-
-    def _trim_seen(self):
-        """... and the shape-history dictionary is bounded (one key per distinct batch shape otherwise, for the whole run)"""
-        if len(self._seen) > self.MAX_SEEN:
-            for k in list(self._seen)[:len(self._seen) // 2]:
-                if k not in self._graphs:
-                    del self._seen[k]
-                    self._probe.pop(k, None)
-        if len(self._no_graph) > self.MAX_SEEN:
-            for k in list(self._no_graph)[:len(self._no_graph) // 2]:
-                del self._no_graph[k]
-
-    def _after_replay(self, static_out, no_grad, span=None):
+    def _after_replay(self, entry):
         """the captured graph writes its scalars (loss, recon, kl[, grad_norm]) into static tensors that the NEXT replay
         overwrites: hand the caller fresh copies (one small launch), like the eager path does"""
-        vals = torch.cat([t.reshape(1) for t in static_out])
-        self._err_span = span       # the words this replay wrote: what _poison() / the optimiser guard read (ADVICE r4, high)
-        hook = self.__dict__.get('_test_after_replay')
-        if hook is not None:        # (tests: a time-out inside a REPLAY — no host code runs there that could be intercepted)
-            hook(span)
+        vals = torch.cat([t.reshape(1) for t in entry.out])
+        self._err_span = entry.span       # the words this replay wrote: what _poison() / the optimiser guard read (ADVICE r4, high)
+        if self._test_after_replay is not None:     # (tests: a time-out inside a REPLAY — no host code runs there that could be intercepted)
+            self._test_after_replay(entry.span)
         if self.graph_ddp:
-            return self._reduce_and_step((vals[0], vals[1], vals[2]), no_grad)
+            return self._reduce_and_step((vals[0], vals[1], vals[2]), entry.no_grad)
         self.optimizer.step_count += 1
         return vals[0], vals[1], vals[2], vals[3:4]
-
-    def _capture(self, x, y, iteration):
-        import t2v_hip
-        static_x = tuple(t.clone() if torch.is_tensor(t) else t for t in x)
-        static_y = tuple(t.clone() for t in y)
-        static_in = [t for t in static_x if torch.is_tensor(t)] + list(static_y)
-        cap = self._capture_static(static_x, static_y, iteration)
-        if cap is None:
-            return None
-        graph, out, no_grad, span = cap
-        return graph, static_in, out, no_grad, span
 
     def _capture_static(self, static_x, static_y, iteration):
         import t2v_hip

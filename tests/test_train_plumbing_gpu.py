@@ -351,7 +351,7 @@ def test_timeout_on_the_first_step_after_a_resume_restores_the_loaded_batchnorm_
             if n in loaded:
                 assert torch.equal(b, loaded[n]), n
         # the watchdog forgets what it knew about the graphs that went
-        assert not eng._probe and not eng._suspect and not eng._no_graph and eng._pending_key is None
+        assert not eng._cache.records and not eng._no_graph and eng._compare_key is None and not eng._graphs
     finally:
         H.DecoderCore.persistent, H.DecoderCore.persistent_bwd = old
         H._ERR_INJECT[0] = None
@@ -393,6 +393,40 @@ def test_replay_watchdog_drops_a_graph_that_is_slower_than_the_eager_step():
     e2, l2, p2 = run(4000, watchdog=False)
     assert e2.graph_fallbacks == 0 and len(e2._graphs) == 1                            # switched off: nothing is probed
     assert l2 == l0
+
+
+def test_replay_watchdog_keeps_a_suspect_graph_that_wins_the_confirming_replays():
+    """The path "suspect, then acquitted": the same batch and engine as the test above, but only the three timed replays in front of
+    the eager comparison step are dragged by 4 ms.  The graph loses the comparison, the three confirming replays run undragged, and
+    the best of all five counted replays no longer loses: the graph stays, nothing is recorded against the shape, and the training
+    trajectory is bit for bit that of the undragged run.  (Like the undragged run above it relies on a healthy replay not being
+    slower than the eager step by 5 % + 0.5 ms at this shape.)"""
+    import hparams as HP
+    import train as TR
+    from bench import synthetic_batch
+    batch = synthetic_batch(3, 30, 40, 5, lens_in=[30, 22, 17], lens_out=[40, 33, 25])
+
+    def run(drag_us):
+        hp = HP.create_hparams("batch_size=3,anneal_function=constant,graph_step=True")
+        torch.manual_seed(hp.seed)
+        torch.cuda.manual_seed(hp.seed)
+        eng = TR.TrainEngine(hp)
+        eng.model.vae_gst.eps_override = torch.full((3, 32), 0.125, device='cuda')
+        losses, phases = [], []
+        with eng.stream_context():
+            for it in range(12):       # 2 warm-ups, capture + 3 timed replays (steps 2-4), the comparison step, 3 confirming replays, 3 more
+                eng._test_replay_drag_us = drag_us if it <= 4 else 0
+                losses.append(eng.step(batch, it)[0])
+                phases.append(next(iter(eng._cache.records.values())).phase)
+        torch.cuda.synchronize()
+        return eng, [float(x) for x in losses], eng.optimizer.params.clone(), phases
+
+    e0, l0, p0, ph0 = run(0)
+    assert ph0 == ['warming'] * 2 + ['probing'] * 2 + ['calibrating'] + ['kept'] * 7
+    e1, l1, p1, ph1 = run(4000)
+    assert ph1 == ['warming'] * 2 + ['probing'] * 2 + ['calibrating'] + ['suspect'] * 3 + ['kept'] * 4
+    assert e1.graph_fallbacks == 0 and len(e1._graphs) == 1 and not e1._no_graph
+    assert l1 == l0 and torch.equal(p1, p0)
 
 
 def test_engine_stream_is_ordered_behind_what_the_caller_issued_before_the_first_step():

@@ -10,7 +10,8 @@ eng = TR.TrainEngine(hp, graph=True)
 batch = tuple(t.pin_memory() for t in synthetic_batch(6, 84, 400, 1234))
 for it in range(6): eng.step(batch, it)
 torch.cuda.synchronize()
-(graph, static_in, static_out), = eng._graphs.values()
+entry, = eng._graphs.values()
+graph, static_in = entry.graph, entry.static
 def timeit(fn, n=20):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for i in range(n): fn(i)

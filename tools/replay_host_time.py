@@ -12,8 +12,8 @@ with eng.stream_context():
     for it in range(8):
         eng.step(batch, it)
     torch.cuda.synchronize()
-    (key, entry), = eng._graphs.items()
-    g = entry[0]
+    entry, = eng._graphs.values()
+    g = entry.graph
     host = []
     for _ in range(10):
         torch.cuda.synchronize()
