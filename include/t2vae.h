@@ -808,6 +808,21 @@ int t2v_loss_fwd_bwd(const float* mel, const float* post, const float* mel_t, co
                      const float* gate_t, const float* mu, const float* logvar, float* dmel, float* dpost,
                      float* dgate, float* dmu, float* dlogvar, float* part192, float* out4, uint32_t* ticket,
                      uint64_t n_mel, int n_gate, int n_lat, float kl_weight, void* stream);
+/* KL control (csrc/kl_control.hip): t2v_loss_fwd_bwd with free bits and a KL capacity target, still one launch.  mu, logvar (B, D),
+ * 1 <= D <= 256.  k[d] = the batch mean of kl[:, d];  K' = B * sum_d max(k[d], free_bits), a dimension with k[d] <= free_bits is
+ * floored: it adds B * free_bits and its dmu / dlogvar are exactly 0 (free_bits == 0: off, K' = KL).  capacity >= 0:
+ * T = |K' - B * capacity| and the latent gradients carry s = sign(K' - B * capacity), 0 at equality; capacity < 0: off, T = K',
+ * s = 1.  total = recon + w * T, w from the device step record when one is installed, else kl_weight.
+ * out8 = [total, recon, KL (raw, as t2v_loss_fwd_bwd), w, K', T, number of floored dimensions, s]; part128 = 128 floats scratch,
+ * ticket = zeroed uint32.  monitor: NULL, or 3 * D + 2 doubles the launch updates: [0] rows seen, [1] launches seen, then per
+ * dimension the running mean of mu[:, d], its M2 (sum of squared deviations, merged batch by batch) and sum kl[:, d]; zero it
+ * to start a window.  Deterministic: the same bits from run to run, issued eagerly or replayed from a graph.
+ * T2V_ERR_ARG for a null pointer (monitor excepted), B < 1, D outside 1..256, free_bits < 0 or a NaN. */
+int t2v_loss_fwd_bwd_klc(const float* mel, const float* post, const float* mel_t, const float* gate,
+                         const float* gate_t, const float* mu, const float* logvar, float* dmel, float* dpost,
+                         float* dgate, float* dmu, float* dlogvar, float* part128, float* out8, uint32_t* ticket,
+                         double* monitor, uint64_t n_mel, int n_gate, int B, int D, float kl_weight, float free_bits,
+                         float capacity, void* stream);
 
 /* ------------------------------------------------------------------ optimiser
  * clip_grad_norm_(params, max_norm) + Adam.step() of the reference loop (train.py:226-229,

@@ -71,11 +71,26 @@ _EXTENSIONS = dict(device_frontend=False, bucket_batches=False, bf16_run=False, 
 #                score: the validation loss stays the reference's (the term is left out there), so that validation.loss is
 #                comparable between runs with and without it.  Constant over a run (no schedule)
 #   guided_attention_sigma  : width of the diagonal band the penalty leaves free (ESPnet's default 0.4)
+#   kl_free_bits : 0 (default) = off.  Otherwise lambda, in nats per latent dimension (free bits, Kingma et al. 2016, in the
+#                batch-mean form): the KL term of the TRAINING loss becomes K' = B * sum_d max(k[d], lambda), k[d] the batch mean
+#                of the KL of dimension d.  A dimension at or under lambda is floored: it costs the constant B * lambda and gets no
+#                KL gradient, so the optimiser gains nothing by emptying it further
+#   kl_capacity  : negative (default) = off.  Otherwise C, in nats per utterance (Burgess et al. 2018; Battenberg et al. 2019
+#                for expressive Tacotron): the KL term becomes |K' - B * C|, which pulls the KL TOWARDS C instead of towards 0.
+#                Constant over a run (no schedule), frozen in a captured step like guided_attention_weight
+#   anneal_cycle, anneal_ratio : anneal_function=cyclical (Fu et al. 2019): the KL weight ramps from 0 to anneal_upper over the first
+#                anneal_ratio of every anneal_cycle steps and stays there for the rest of the cycle
+#   kl_monitor   : True keeps a running per-dimension record of the posterior inside the loss launch (t2v_hip.KLMonitor): the loop
+#                prints and logs the active units of the window at every validation.  A free-bits or capacity run keeps one anyway
+# Like the guided attention term these shape the training loss only: validation.loss and the logged kl_div stay the reference's.
 _RECIPE = dict(ema_decay=0.0, ema_warmup=True, guided_attention_weight=0.0, guided_attention_sigma=0.4)
+# (the VAE half of the group, kept under a name of its own: tests/test_guided_host.py pins the keys of _RECIPE)
+_RECIPE_VAE = dict(kl_free_bits=0.0, kl_capacity=-1.0, anneal_cycle=10000, anneal_ratio=0.5, kl_monitor=False)
+_RECIPE_ALL = dict(_RECIPE, **_RECIPE_VAE)      # the recipe group: what recipe() reports and values() leaves out
 # Switches of the group that an hparams object stores only once they are set: left alone, they read as their defaults above and
 # appear in no listing, so `recipe()`, the store and whatever is printed or saved from them are, for a run that does not use
 # such a switch, what they were before the switch existed.
-_RECIPE_UNSTORED = ('guided_attention_weight', 'guided_attention_sigma')
+_RECIPE_UNSTORED = ('guided_attention_weight', 'guided_attention_sigma') + tuple(_RECIPE_VAE)
 
 
 def _coerce(old, text):
@@ -103,7 +118,7 @@ class HParams(object):
         if k in store:
             return store[k]
         if k in _RECIPE_UNSTORED:
-            return _RECIPE[k]
+            return _RECIPE_ALL[k]
         raise AttributeError(k)
 
     def __setattr__(self, k, v):
@@ -114,13 +129,13 @@ class HParams(object):
 
     def values(self):
         """the reference's hyper-parameters (build-specific switches excluded)"""
-        return {k: v for k, v in self._store.items() if k not in _EXTENSIONS and k not in _RECIPE}
+        return {k: v for k, v in self._store.items() if k not in _EXTENSIONS and k not in _RECIPE_ALL}
 
     def extensions(self):
         return {k: v for k, v in self._store.items() if k in _EXTENSIONS}
 
     def recipe(self):
-        return {k: v for k, v in self._store.items() if k in _RECIPE}
+        return {k: v for k, v in self._store.items() if k in _RECIPE_ALL}
 
     def parse(self, spec):
         for item in filter(None, (s.strip() for s in spec.split(','))):

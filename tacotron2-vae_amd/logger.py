@@ -312,10 +312,14 @@ class Tacotron2Logger(EventFileWriter):
         super(Tacotron2Logger, self).__init__(logdir)
 
     def log_training(self, reduced_loss, grad_norm, learning_rate, duration, recon_loss, kl_div, kl_weight,
-                     iteration, guided_attention=None):
+                     iteration, guided_attention=None, kl_objective=None, kl_floored_dims=None):
         self.add_scalar("training.loss", reduced_loss, iteration)
         if guided_attention is not None:        # hparams.guided_attention_weight > 0: the unweighted term, inside training.loss
             self.add_scalar("training.guided_attention", guided_attention, iteration)
+        if kl_objective is not None:            # hparams.kl_free_bits / kl_capacity: T, inside training.loss as kl_weight * T
+            self.add_scalar("training.kl_objective", kl_objective, iteration)
+        if kl_floored_dims is not None:         # latent dimensions at or under the free-bits floor in this step
+            self.add_scalar("training.kl_floored_dims", kl_floored_dims, iteration)
         self.add_scalar("grad.norm", grad_norm, iteration)
         self.add_scalar("learning.rate", learning_rate, iteration)
         self.add_scalar("duration", duration, iteration)
@@ -329,8 +333,10 @@ class Tacotron2Logger(EventFileWriter):
         self.add_scalar("validation.loss.ema", reduced_loss, iteration)
         self.flush()
 
-    def log_validation(self, reduced_loss, model, y, y_pred, iteration):
+    def log_validation(self, reduced_loss, model, y, y_pred, iteration, kl_active_units=None):
         self.add_scalar("validation.loss", reduced_loss, iteration)
+        if kl_active_units is not None:         # the KL monitor's count over the TRAINING batches since the last validation
+            self.add_scalar("training.kl_active_units", kl_active_units, iteration)
         _, mel_outputs, gate_outputs, alignments, mus, _, _, emotions = y_pred
         mel_targets, gate_targets = y
         for tag, value in model.named_parameters():

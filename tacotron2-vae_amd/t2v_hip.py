@@ -3765,3 +3765,70 @@ class VAELoss(torch.autograd.Function):
     def backward(ctx, dtotal, _dout):
         g = torch._foreach_mul(ctx.grads, dtotal)       # one multi-tensor launch instead of five
         return (g[0], g[1], g[2], g[3], g[4], None, None, None)
+
+
+class KLMonitor(object):
+    """Running per-dimension record of the posterior over the training batches of a window, kept by the loss launch itself
+    (csrc/kl_control.hip): 3 * dims + 2 doubles on the device — rows seen, launches seen, and per dimension the running mean of mu, its
+    M2 and the sum of the KL.  The buffer's address is fixed for the monitor's life, so a captured step keeps updating it."""
+
+    def __init__(self, dims, device='cuda'):
+        dims = int(dims)
+        if not 1 <= dims <= 256:
+            raise T2VHipError("KLMonitor: 1..256 latent dimensions, got %d" % dims)
+        self.dims = dims
+        self.buf = torch.zeros(3 * dims + 2, device=device, dtype=torch.float64)
+
+    def reset(self):
+        self.buf.zero_()        # a memset on the current stream: ordered with the launches around it, no host round trip
+
+    def read(self):
+        """{'n': rows seen, 'launches', 'mean', 'm2', 'active_units', 'kl_per_dim'} of the window so far (synchronises).
+        active_units: dimensions whose variance of mu, M2 / (n - 1), exceeds latent_scores.ACTIVE_THRESHOLD (Burda et al.);
+        kl_per_dim: mean nats per utterance, (dims,) fp64."""
+        from latent_scores import ACTIVE_THRESHOLD
+        v = self.buf.cpu().numpy()
+        D, n = self.dims, int(v[0])
+        mean, m2, skl = v[2:2 + D], v[2 + D:2 + 2 * D], v[2 + 2 * D:2 + 3 * D]
+        return {'n': n, 'launches': int(v[1]), 'mean': mean.copy(), 'm2': m2.copy(),
+                'active_units': int((m2 / (n - 1) > ACTIVE_THRESHOLD).sum()) if n > 1 else 0,
+                'kl_per_dim': skl / n if n > 0 else skl.copy()}
+
+
+class VAELossKLC(torch.autograd.Function):
+    """Tacotron2Loss_VAE with free bits, a KL capacity target and the monitor update, value + gradient in one HIP launch
+    (csrc/kl_control.hip).  Returns (total, out8): out8 = [total, recon, raw KL, w, K', T, floored dimensions, s]."""
+
+    @staticmethod
+    def forward(ctx, mel, post, gate, mu, logvar, mel_t, gate_t, kl_weight, free_bits, capacity, monitor):
+        lib = _require_gpu(mel, post, gate, mu, logvar)
+        dev = mel.device
+        key = str(dev)
+        if key not in VAELoss._scratch:
+            VAELoss._scratch[key] = (torch.empty(192, device=dev), torch.zeros(1, device=dev, dtype=torch.int32))
+        part, ticket = VAELoss._scratch[key]
+        mel, post, gate, mu, logvar = (_f32c(t) for t in (mel, post, gate, mu, logvar))
+        mel_t, gate_t = _f32c(mel_t), _f32c(gate_t)
+        if mu.dim() != 2 or mu.shape != logvar.shape:
+            raise T2VHipError("VAELossKLC takes mu and logvar of one (B, D) shape")
+        B, D = mu.shape
+        if monitor is not None and (monitor.dims != D or monitor.buf.device != dev):
+            raise T2VHipError("VAELossKLC: the monitor was made for %d dimensions on %s" % (monitor.dims, monitor.buf.device))
+        out = torch.empty(8, device=dev, dtype=torch.float32)
+        sp = step_params(create=False)
+        if sp is not None:       # the kernel reads the KL weight from the device record once one is installed
+            sp.set(kl_weight=kl_weight)
+            sp.upload()
+        grads = [torch.empty_like(t) for t in (mel, post, gate, mu, logvar)]
+        _check(lib.t2v_loss_fwd_bwd_klc(_p(mel), _p(post), _p(mel_t), _p(gate), _p(gate_t), _p(mu), _p(logvar),
+                                        *[_p(g) for g in grads], _p(part), _p(out), _p(ticket),
+                                        _p(monitor.buf) if monitor is not None else None, mel.numel(), gate.numel(), B, D,
+                                        float(kl_weight), float(free_bits), float(capacity), _stream()), 't2v_loss_fwd_bwd_klc')
+        ctx.grads = grads
+        ctx.mark_non_differentiable(out)
+        return out[0], out
+
+    @staticmethod
+    def backward(ctx, dtotal, _dout):
+        g = torch._foreach_mul(ctx.grads, dtotal)       # VAELoss's one multi-tensor multiply
+        return (g[0], g[1], g[2], g[3], g[4], None, None, None, None, None, None)

@@ -112,6 +112,11 @@ class TrainEngine(object):
         self.hparams = hparams
         self.model = load_model(hparams)
         self.criterion = Tacotron2Loss_VAE(hparams)
+        # hparams.kl_monitor, or a free-bits / capacity run: the training loss launch keeps a per-dimension record of the posterior.
+        # One buffer per engine, made before any capture: its address is part of the captured step
+        self.kl_monitor = None
+        if getattr(hparams, 'kl_monitor', False) or self.criterion.kl_control:
+            self.kl_monitor = self.criterion.monitor = t2v_hip.KLMonitor(hparams.z_latent_dim)
         self.optimizer = FlatAdam(self.model, lr=hparams.learning_rate, weight_decay=hparams.weight_decay,
                                   grad_clip_thresh=hparams.grad_clip_thresh, world_size=world_size,
                                   ema_decay=getattr(hparams, 'ema_decay', 0.0), ema_warmup=getattr(hparams, 'ema_warmup', True))
@@ -393,7 +398,7 @@ class TrainEngine(object):
     def _publish(self, iteration):
         """everything the kernels of this iteration read from the device record, in one upload before the first launch"""
         c = self.criterion
-        w = c.kl_anneal_function(c.anneal_function, c.lag, iteration, c.k, c.x0, c.upper)
+        w = c.kl_weight(iteration)
         sp = self.step_params
         import t2v_hip
         t2v_hip.activate_step_params(sp)
@@ -516,6 +521,9 @@ class TrainEngine(object):
         """the captured graph writes its scalars (loss, recon, kl[, grad_norm]) into static tensors that the NEXT replay
         overwrites: hand the caller fresh copies (one small launch), like the eager path does"""
         vals = torch.cat([t.reshape(1) for t in entry.out])
+        base = 3 if self.graph_ddp else 4
+        if len(entry.out) > base:         # a graph with the KL control launch: the criterion shows THIS step's K', T and floored count
+            self.criterion.kl_floored_sum, self.criterion.kl_objective, self.criterion.kl_floored_dims = vals[base:base + 3].unbind()
         self._err_span = entry.span       # the words this replay wrote: what _poison() / the optimiser guard read (ADVICE r4, high)
         if self._test_after_replay is not None:     # (tests: a time-out inside a REPLAY — no host code runs there that could be intercepted)
             self._test_after_replay(entry.span)
@@ -555,7 +563,11 @@ class TrainEngine(object):
                 t2v_hip.err_capture_end(keep=False)
         self.optimizer.step_count = count0      # capture executes nothing; the replay below is this iteration's step
         no_grad = list(self.optimizer._no_grad) if self.graph_ddp else None
-        return graph, tuple(out), no_grad, span
+        out = tuple(out)
+        if self.kl_monitor is not None:     # the KL control launch was captured: its K', T and floored count travel with the step's scalars
+            c = self.criterion
+            out += (c.kl_floored_sum, c.kl_objective, c.kl_floored_dims)
+        return graph, out, no_grad, span
 
 
 def prepare_directories_and_logger(output_directory, log_directory, rank):
@@ -617,10 +629,12 @@ def prepare_dataloaders(hparams, resident_corpus=False):
     return loader, valset, collate_fn
 
 
-def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn, logger, distributed_run, rank, ema=False):
+def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn, logger, distributed_run, rank, ema=False,
+             kl_active_units=None):
     """reference train.py:122-147, including its habit of reporting the LAST batch's loss (B-13).  ema=True: the caller has
     put the averaged weights into the model (FlatAdam.swapped_ema); the loss is printed and logged under its own name and
-    the histograms / images of log_validation are not written a second time."""
+    the histograms / images of log_validation are not written a second time.  kl_active_units: what the KL monitor counted over
+    the training batches since the last validation (a run that keeps one), logged beside the validation loss."""
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
     model.eval()
@@ -646,7 +660,10 @@ def validate(model, criterion, valset, iteration, batch_size, n_gpus, collate_fn
     elif rank == 0:
         print("Validation loss {}: {:9f}  ".format(iteration, reduced))
         if logger is not None and y_pred is not None:
-            logger.log_validation(reduced, model, y, y_pred, iteration)
+            if kl_active_units is None:
+                logger.log_validation(reduced, model, y, y_pred, iteration)
+            else:
+                logger.log_validation(reduced, model, y, y_pred, iteration, kl_active_units=kl_active_units)
     return reduced
 
 
@@ -694,15 +711,29 @@ def train(output_directory, log_directory, checkpoint_path, warm_start, n_gpus, 
                 if not math.isnan(reduced) and rank == 0:
                     duration = time.perf_counter() - start
                     guided = criterion.guided.item() if hparams.guided_attention_weight > 0 else None
+                    # free bits / capacity: the KL objective T (training.loss carries w * T; kl_div stays the raw KL) and the
+                    # number of floored dimensions of this step
+                    klc = ({'kl_objective': criterion.kl_objective.item(), 'kl_floored_dims': int(criterion.kl_floored_dims.item())}
+                           if criterion.kl_control else {})
                     print("Train loss {} {:.6f} Grad Norm {:.6f} {:.2f}s/it".format(
                         iteration, reduced, grad_norm.item(), duration) +
-                        ("" if guided is None else " Guided attention {:.6f}".format(guided)))
+                        ("" if guided is None else " Guided attention {:.6f}".format(guided)) +
+                        ("" if not klc else " KL objective {kl_objective:.6f} floored dims {kl_floored_dims}".format(**klc)))
                     if logger is not None:
                         logger.log_training(reduced, grad_norm.item(), learning_rate, duration, recon.item(), kl.item(),
-                                            kl_w, iteration, guided_attention=guided)
+                                            kl_w, iteration, guided_attention=guided, **klc)
                 if iteration % hparams.iters_per_checkpoint == 0:
+                    active = None
+                    if engine.kl_monitor is not None:
+                        # the window since the last validation (this rank's training batches), read where the loop synchronises anyway
+                        seen = engine.kl_monitor.read()
+                        engine.kl_monitor.reset()
+                        active = seen['active_units']
+                        if rank == 0:
+                            print("KL monitor {}: active units {} of {} over {} utterances".format(
+                                iteration, active, engine.kl_monitor.dims, seen['n']))
                     validate(model, criterion, valset, iteration, hparams.batch_size, n_gpus, collate_fn, logger,
-                             hparams.distributed_run, rank)
+                             hparams.distributed_run, rank, kl_active_units=active)
                     if optimizer.ema is not None:
                         with optimizer.swapped_ema():
                             validate(model, criterion, valset, iteration, hparams.batch_size, n_gpus, collate_fn, logger,
